@@ -7,16 +7,27 @@ Metric (BASELINE.json): clique-tree messages/sec (+ log-likelihood evals/sec), h
 One "step" = one calibrate!() (postorder + preorder over the whole clique tree = 2 * n_sepsets
 directed canonical messages, src/calibration.jl:72-84) on factors already resident in HBM.
 
-    python bench.py [--gpus N --steps K --warmup W]
+    python bench.py [--gpus N --steps K --warmup W] [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 N > 1: one process per GPU, each calibrating its own replica of the workload (one big tree does
 not shard -- "replicas only"); no data-path collective; timing = barrier +
 synchronize on both sides, MAX over ranks; value = all ranks' messages / that time.
-The same line carries, for every N, the block `site_sharded_cfg4`: BASELINE.json configs[3] (8000
-independent univariate OU problems on a 20k-tip tree) sharded over the N ranks -- the configuration
-that does shard (strong scaling), its one all-gather (RCCL, behind the C ABI) inside the timed region.
 Rank 0 prints ONE JSON line.
+
+A plain run of the tree workload does only what its headline figure needs: set up, W warm-up steps, the K timed steps,
+the outputs (--dump-outputs), the line (metric, value, unit, higher_is_better, dtype, ms_per_step, ...).  --full adds
+everything else the line used to carry: the parity gates against the independent pruning log-likelihood, the
+log-likelihood evaluation figures, the drop-in call timings, the roofline, the 50k-clique and cfg2 side readings, the
+CPU baselines and, for every N, the blocks `site_sharded_cfg4` (BASELINE.json configs[3]: 8000 independent univariate OU
+problems on a 20k-tip tree sharded over the N ranks, its one all-gather inside the timed region) and `network_cfg5`.
+The sites and network workloads (--workload) print their whole line either way.
+
+--dump-outputs DIR: after the timed steps, what the last step computed, as DIR/<name>.npy (float64): the tree workload
+writes a fixed, seeded sample of the calibrated belief records (`beliefs_sample`, records concatenated in increasing
+belief index) and the root's integratebelief! (`root_loglik`, `root_mean`); the sites workload the all-gathered
+per-problem log-likelihoods (`loglik`); the network workload a sample of the calibrated beliefs.  Inputs depend on the
+arguments alone, so two builds can be compared output for output.
 """
 import argparse
 import ctypes as C
@@ -35,7 +46,8 @@ sys.path.insert(0, ROOT)
 HBM_PEAK_GBS = 8000.0  # MI355X HBM3E spec peak (/opt/skills/guides/MI355X_MICROARCH.md)
 
 
-def build_workload(ntips, p, seed, graph):
+def build_workload(ntips, p, seed, graph, check=True):
+    """check=False: no independent pruning log-likelihood (None in its place); the workload itself is the same."""
     from pgbp_amd import synth as S
     rng = np.random.default_rng(seed)
     tr = S.random_tree(ntips, rng)
@@ -48,8 +60,44 @@ def build_workload(ntips, p, seed, graph):
     else:
         prob = S.bethe_of_tree(tr, p)
         packed = S.bm_factors_bethe(tr, prob, R, mu, X)
-    ll_check = S.bm_loglik_pruning(tr, R, mu, X)
+    ll_check = S.bm_loglik_pruning(tr, R, mu, X) if check else None
     return tr, prob, packed, ll_check, (R, mu, X)
+
+
+DUMP_LIMIT_BYTES = 64 << 20     # all the arrays of one --dump-outputs together
+SAMPLE_LIMIT_BYTES = 48 << 20   # the belief sample's share of it
+
+
+def dump_outputs(dirname, arrays):
+    """--dump-outputs: every array as DIR/<name>.npy in float64; their sum stays within DUMP_LIMIT_BYTES."""
+    os.makedirs(dirname, exist_ok=True)
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float64) for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit(f"--dump-outputs: {total} bytes of outputs, more than the {DUMP_LIMIT_BYTES} allowed")
+    for k, a in arrays.items():
+        np.save(os.path.join(dirname, k + ".npy"), a)
+
+
+def sample_indices(record_sizes, n_max=4096, seed=20260101):
+    """The beliefs of the --dump-outputs sample, in increasing index: a seeded random subset of at most n_max of them
+    whose records (record_sizes doubles each) fit in SAMPLE_LIMIT_BYTES."""
+    order = np.random.default_rng(seed).permutation(len(record_sizes))
+    sizes = np.asarray(record_sizes, np.int64)[order]
+    n = min(n_max, len(order), int(np.searchsorted(np.cumsum(sizes) * 8, SAMPLE_LIMIT_BYTES, side="right")))
+    return np.sort(order[:max(1, n)]).astype(np.int32)
+
+
+def belief_sample(cgb, lib, site=0):
+    """The records (J, h, g each) of the sample_indices beliefs of one site, gathered on the device into one buffer
+    (pgbp_pack_beliefs, one transfer), back to back."""
+    from pgbp_amd import _lib as L
+    idx = sample_indices(np.diff(cgb._poff))
+    m = int(lib.pgbp_packed_beliefs_size(cgb._eng, len(idx), L.i32p(idx)))
+    buf = np.zeros(max(1, m))
+    if lib.pgbp_pack_beliefs(cgb._eng, site, len(idx), L.i32p(idx), L.f64p(buf)) != 0:
+        raise RuntimeError(lib.pgbp_last_error(cgb._eng).decode())
+    return buf[:m]
 
 
 def host_cores():
@@ -324,6 +372,8 @@ def run_sites(args, torch, dist, rank, world, local_rank, emit=True):
         for _ in range(args.steps):
             one_sharded_step()
     dt_sh = timed_region(k_sharded_steps, dist, torch.cuda.synchronize)
+    if emit and args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"loglik": full})   # every problem's log-likelihood of the last sharded step
     rel_all = float(np.max(np.abs(full[lo:hi] - ll_check) / np.maximum(1.0, np.abs(ll_check))))
     if rel_all > 1e-8:
         raise SystemExit(f"parity gate failed (sites, gathered): max rel err {rel_all:.3e}")
@@ -477,6 +527,8 @@ def run_network(args, torch, dist, rank, world, local_rank, emit=True):
     dt = timed_region(k_steps, dist, torch.cuda.synchronize)
     if rank != 0:
         return None
+    if emit and args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"beliefs_sample": belief_sample(cgb, lib)})   # after the last timed iteration
     ms_step = dt / args.steps * 1e3
     net_traffic = load_pmc_traffic(f"pmc_traffic_network_{args.graph}_latest.json")
     default_net = (args.ntips == 20000 and args.traits == 4 and args.seed == 5 and args.blob_style == "varied"
@@ -578,6 +630,12 @@ def main():
                     help="tree: the headline one-big-tree workload (default, cfg3 / cfg2); sites: cfg4 site-sharded batch; "
                          "network: cfg5 loopy BP on a level-3 network")
     ap.add_argument("--sites", type=int, default=1000)
+    ap.add_argument("--full", action="store_true",
+                    help="tree workload: everything beside the headline figure as well -- parity gates, log-likelihood "
+                         "evaluation figures, drop-in timings, roofline, side readings, CPU baselines, the site_sharded_cfg4 "
+                         "and network_cfg5 blocks (the --no-* options above and --ll-batch / --cpu-budget shape these)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step computed as DIR/<name>.npy (float64, <= 64 MB)")
     args = ap.parse_args()
     if args.ntips is None:
         args.ntips = 50000 if args.workload == "tree" else 20000
@@ -637,7 +695,8 @@ def main():
     from pgbp_amd import _lib as L
     lib = pgbp_amd.load()
 
-    tr, prob, packed, ll_check, (R, mu, X) = build_workload(args.ntips, args.traits, args.seed + rank, args.graph)
+    tr, prob, packed, ll_check, (R, mu, X) = build_workload(args.ntips, args.traits, args.seed + rank, args.graph,
+                                                            check=args.full)
     cgb = pgbp_amd.ClusterGraphBelief.from_arrays(prob.dims, prob.sepset_clusters, prob.scope_off,
                                                   prob.scope_idx, packed, device=local_rank)
     cgb.set_schedule(prob.schedule)
@@ -654,14 +713,15 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
 
-    # ---- parity gate for the timed configuration: log-likelihood vs the independent pruning check
     norm = np.zeros(1)
     info = np.zeros(1, dtype=np.int32)
-    check(lib.pgbp_enqueue_loglik(eng, 1, C.byref(opts)))
-    check(lib.pgbp_fetch_loglik(eng, L.f64p(norm), L.i32p(info)))
-    rel = abs(norm[0] - ll_check) / max(1.0, abs(ll_check))
-    if not (info[0] == 0 and rel <= 1e-8):
-        raise SystemExit(f"parity gate failed: loglik {norm[0]!r} vs {ll_check!r} (rel {rel:.3e}, info {info[0]})")
+    if args.full:
+        # ---- parity gate for the timed configuration: log-likelihood vs the independent pruning check
+        check(lib.pgbp_enqueue_loglik(eng, 1, C.byref(opts)))
+        check(lib.pgbp_fetch_loglik(eng, L.f64p(norm), L.i32p(info)))
+        rel = abs(norm[0] - ll_check) / max(1.0, abs(ll_check))
+        if not (info[0] == 0 and rel <= 1e-8):
+            raise SystemExit(f"parity gate failed: loglik {norm[0]!r} vs {ll_check!r} (rel {rel:.3e}, info {info[0]})")
 
     # ---- warmup + timed calibrate steps
     check(lib.pgbp_reset_from_factors(eng))
@@ -674,6 +734,31 @@ def main():
         check(lib.pgbp_sync(eng))
     dt = timed_region(k_steps, dist, torch.cuda.synchronize)
     value = whole_job_rate(msgs_per_cal, args.steps, world, dt)
+    if args.dump_outputs and rank == 0:
+        # what a caller of calibrate!() receives after the last timed step: the calibrated beliefs (a seeded sample of
+        # the records) and the root's integratebelief!
+        sample = belief_sample(cgb, lib)
+        mu_d, n_d, i_d = cgb.integratebelief_(prob.root_cluster, all_sites=True)
+        if i_d.any():
+            raise SystemExit(f"--dump-outputs: integratebelief! of the root failed (info {i_d.tolist()})")
+        dump_outputs(args.dump_outputs, {"beliefs_sample": sample, "root_loglik": n_d, "root_mean": mu_d})
+    headline = {
+        "metric": "clique-tree messages/sec (calibrate!: postorder+preorder), 16-trait BM",
+        "value": value, "unit": "messages/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": dt / args.steps * 1e3, "higher_is_better": True, "scaling": "weak",
+        "vs_baseline": None, "dtype": "f64", "data": "synthetic",
+        "config": {"workload": f"{'cfg3' if (args.traits, args.ntips, args.graph) == (16, 50000, 'cliquetree') else 'custom'}: homogeneous BM, {args.traits} traits, {args.ntips}-tip random "
+                               f"bifurcating tree (seed {args.seed}), {args.graph}, fixed root",
+                   "clusters": int(prob.nclusters), "sepsets": int(len(prob.dims) - prob.nclusters),
+                   "messages_per_step": int(msgs_per_cal), "tree_depth": int(tr.depth().max()),
+                   "parallelism": "replicas only" if world > 1 else "single GPU"},
+    }
+    if not args.full:
+        if dist is not None:
+            dist.destroy_process_group()
+        if rank == 0:
+            print(json.dumps(headline))
+        return
     ms_k, nl_k = C.c_float(), C.c_int32()
     check(lib.pgbp_fetch_kernel_time(eng, C.byref(ms_k), C.byref(nl_k)))
 
@@ -789,15 +874,7 @@ def main():
         launches_pmc = (pmc or {}).get("launches_per_calibrate") or 76   # (76: the round-1 file, one launch per level)
         copy_bw = measured_copy_bandwidth(torch, local_rank) if rank == 0 else None
         out = {
-            "metric": "clique-tree messages/sec (calibrate!: postorder+preorder), 16-trait BM",
-            "value": value, "unit": "messages/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": dt / args.steps * 1e3, "higher_is_better": True, "scaling": "weak",
-            "vs_baseline": None, "dtype": "f64", "data": "synthetic",
-            "config": {"workload": f"{'cfg3' if (args.traits, args.ntips, args.graph) == (16, 50000, 'cliquetree') else 'custom'}: homogeneous BM, {args.traits} traits, {args.ntips}-tip random "
-                                   f"bifurcating tree (seed {args.seed}), {args.graph}, fixed root",
-                       "clusters": int(prob.nclusters), "sepsets": int(len(prob.dims) - prob.nclusters),
-                       "messages_per_step": int(msgs_per_cal), "tree_depth": int(tr.depth().max()),
-                       "parallelism": "replicas only" if world > 1 else "single GPU"},
+            **headline,
             "loglik": float(norm[0]), "loglik_rel_err_vs_pruning": float(rel),
             "ranks_loglik": ranks_loglik, "ranks_gather": ranks_gather,
             "ll_evals_per_s": ll_evals, "ll_evals_per_s_without_factor_fill": ll_evals_nofill,

@@ -335,3 +335,32 @@ def test_comm_create_failure_on_one_rank_is_raised_by_every_rank():
     got = sorted(q.get(timeout=10) for _ in range(4))
     assert [g for g in got if g[0] == 0] == [(0, "ValueError"), (0, "raised: pgbp_comm: another rank could not create its communicator")]
     assert [g for g in got if g[0] == 1] == [(1, "ValueError"), (1, "raised: ncclCommInitRank: injected failure")]
+
+
+def test_dump_outputs_float64_files_within_the_limit(tmp_path):
+    """bench.py --dump-outputs: every array lands as DIR/<name>.npy in float64; more than 64 MB in all is refused."""
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    d = tmp_path / "out"
+    bench.dump_outputs(str(d), {"a": np.arange(5, dtype=np.float32), "b": np.ones((2, 3))})
+    a, b = np.load(d / "a.npy"), np.load(d / "b.npy")
+    assert a.dtype == b.dtype == np.float64 and a.tolist() == [0, 1, 2, 3, 4] and b.shape == (2, 3)
+    with pytest.raises(SystemExit):
+        bench.dump_outputs(str(tmp_path / "big"), {"x": np.zeros((64 << 20) // 8 + 1)})
+    assert not (tmp_path / "big" / "x.npy").exists()
+
+
+def test_dump_sample_is_seeded_sorted_and_bounded():
+    """The belief sample of --dump-outputs: the same beliefs on every run, in increasing index, within its byte share."""
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    dims = np.array([32] * 99998 + [16] * 99997)            # the cfg3 clique tree: 16 traits, 2 nodes per clique
+    sizes = dims * dims + dims + 1
+    idx = bench.sample_indices(sizes)
+    assert np.array_equal(idx, bench.sample_indices(sizes))
+    assert np.all(np.diff(idx) > 0) and 0 < len(idx) <= 4096
+    assert 8 * int(sizes[idx].sum()) <= bench.SAMPLE_LIMIT_BYTES <= bench.DUMP_LIMIT_BYTES
+    assert len(bench.sample_indices(np.full(10, 1 << 22))) == 1   # records of 32 MB: one fits
+    assert np.array_equal(bench.sample_indices(np.full(7, 3)), np.arange(7))

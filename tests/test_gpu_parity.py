@@ -1489,7 +1489,7 @@ def test_network_differential_fuzz(P, env):
     ["--workload", "network", "--graph", "joingraph", "--ntips", "240", "--steps", "2", "--warmup", "1"],
 ], ids=["tree", "tree_bethe", "sites_ou", "sites_bm", "network_bethe", "network_joingraph"])
 def test_bench_workloads_at_test_size(P, argv):
-    """bench.py end to end at test size for every workload: its parity gates (log-likelihood against the independent
+    """bench.py --full end to end at test size for every workload: its parity gates (log-likelihood against the independent
     pruning value; network: beliefs and convergence against the C engine) pass and one JSON line with the contract's
     keys comes out."""
     import json
@@ -1497,7 +1497,8 @@ def test_bench_workloads_at_test_size(P, argv):
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    out = subprocess.run([sys.executable, os.path.join(root, "bench.py")] + argv, capture_output=True, text=True, timeout=600)
+    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--full"] + argv, capture_output=True, text=True,
+                         timeout=600)
     assert out.returncode == 0, (out.stdout[-1500:], out.stderr[-1500:])
     line = json.loads(out.stdout.strip().splitlines()[-1])
     for key in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
@@ -1505,6 +1506,54 @@ def test_bench_workloads_at_test_size(P, argv):
         assert key in line, key
     assert line["value"] > 0 and line["dtype"] == "f64" and "workload" in line["config"]
     assert {"bound", "achieved", "peak", "unit", "frac", "traffic"} <= set(line["roofline"])
+
+
+def test_bench_plain_line_and_dumped_outputs(P, tmp_path):
+    """A plain bench.py run (no --full) at test size: the headline line alone, --steps timed steps, and --dump-outputs
+    writes what the last step left -- the seeded sample of calibrated belief records equals the same records after the
+    oracle's sequential calibrate!() of the same workload, the root's log-likelihood the independent pruning value."""
+    import json
+    import os
+    import subprocess
+    import sys
+    from oracle import cengine
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    sys.path.insert(0, root)
+    import bench
+    d = tmp_path / "out"
+    argv = ["--ntips", "400", "--traits", "16", "--steps", "3", "--warmup", "1", "--dump-outputs", str(d)]
+    out = subprocess.run([sys.executable, os.path.join(root, "bench.py")] + argv, capture_output=True, text=True, timeout=600)
+    assert out.returncode == 0, (out.stdout[-1500:], out.stderr[-1500:])
+    lines = [ln for ln in out.stdout.strip().splitlines() if ln.startswith("{")]
+    assert len(lines) == 1
+    line = json.loads(lines[0])
+    for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert key in line, key
+    assert line["steps"] == 3 and line["warmup"] == 1 and line["value"] > 0 and line["ms_per_step"] > 0
+    assert line["dtype"] == "f64" and line["higher_is_better"] is True
+    assert "roofline" not in line and "cpu_baseline" not in line and "site_sharded_cfg4" not in line
+    got = {f.stem: np.load(f) for f in d.iterdir()}
+    assert set(got) == {"beliefs_sample", "root_loglik", "root_mean"}
+    assert all(a.dtype == np.float64 for a in got.values())
+    assert sum(a.nbytes for a in got.values()) <= 64 << 20
+    tr, prob, packed, ll_check, _ = bench.build_workload(400, 16, 3, "cliquetree")
+    assert abs(got["root_loglik"][0] - ll_check) <= 1e-8 * max(1.0, abs(ll_check))
+    assert got["root_mean"].shape == (1, int(prob.dims[prob.root_cluster]))
+    dims = np.asarray(prob.dims, np.int64)
+    poff = np.concatenate([[0], np.cumsum(dims * dims + dims + 1)])
+    idx = bench.sample_indices(np.diff(poff))
+    eng = cengine.Engine(prob.dims, prob.sepset_clusters, prob.scope_off, prob.scope_idx, packed)
+    pa, ch = prob.schedule[0]
+    eng.prepare(pa, ch)
+    assert eng.calibrate()
+    ref = np.concatenate([eng.packed()[poff[i]:poff[i + 1]] for i in idx])
+    assert got["beliefs_sample"].shape == ref.shape
+    at = 0
+    for i in idx:                         # per record: max |difference| <= 1e-8 * max(1, max |oracle|)
+        n = int(poff[i + 1] - poff[i])
+        a, b = got["beliefs_sample"][at:at + n], ref[at:at + n]
+        assert np.max(np.abs(a - b)) <= 1e-8 * max(1.0, np.max(np.abs(b))), int(i)
+        at += n
 
 
 def test_auto_stop_speculative_batches(P):
@@ -1586,7 +1635,7 @@ def test_bench_two_ranks_rehearsal(P, argv):
     env = dict(os.environ, PGBP_BENCH_REHEARSAL="1")
     port = 29600 + (os.getpid() % 300)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-           "--master-port", str(port), os.path.join(root, "bench.py"), "--gpus", "2"] + argv
+           "--master-port", str(port), os.path.join(root, "bench.py"), "--gpus", "2", "--full"] + argv
     out = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, (out.stdout[-1500:], out.stderr[-3000:])
     lines = [ln for ln in out.stdout.strip().splitlines() if ln.startswith("{")]

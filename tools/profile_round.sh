@@ -15,7 +15,7 @@ keep_stats() {  # $1 = rocprof output dir, $2 = name
 }
 cd $R
 step "cfg3 kernel stats"
-rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/p1 -- python3 bench.py --steps 20 --warmup 3 --no-cpu-baseline --no-alt-reading --ll-batch 1 > $out/bench_cfg3_under_profiler.json 2>$out/e1.txt || exit 1
+rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/p1 -- python3 bench.py --full --steps 20 --warmup 3 --no-cpu-baseline --no-alt-reading --ll-batch 1 > $out/bench_cfg3_under_profiler.json 2>$out/e1.txt || exit 1
 keep_stats /tmp/p1 cfg3_kernel_stats.csv; rm -rf /tmp/p1
 step "cfg3 level times"
 rocprofv3 --kernel-trace --output-format csv -d /tmp/p2 -- python3 tools/level_times.py run > $out/lt_run.txt 2>&1 || exit 1
@@ -70,7 +70,7 @@ step "seam microbenchmark"
 step "Mueller clique tree: large beliefs, KL residuals, free energy"
 python3 tools/time_muller.py 2 3 4 6 > $out/muller_cliquetree_times.jsonl 2>$out/e_muller.txt
 step "plain bench lines"
-python3 bench.py > $out/bench_default.json 2>$out/e10.txt || exit 1
+python3 bench.py --full > $out/bench_default.json 2>$out/e10.txt || exit 1
 python3 bench.py --workload sites > $out/bench_cfg4.json 2>$out/e11.txt || exit 1
 python3 bench.py --workload network > $out/bench_cfg5_joingraph.json 2>$out/e12.txt || exit 1
 python3 bench.py --workload network --graph bethe > $out/bench_cfg5_bethe.json 2>$out/e13.txt || exit 1

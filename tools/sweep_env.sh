@@ -9,7 +9,7 @@ for setting in "$@"; do
   i=$((i+1))
   (
     if [ "$setting" != "-" ]; then IFS=','; for kv in $setting; do export "$kv"; done; unset IFS; fi
-    python3 bench.py $args > $out/${tag}_$i.json 2> $out/${tag}_$i.err
+    python3 bench.py --full $args > $out/${tag}_$i.json 2> $out/${tag}_$i.err
   ) || { echo "FAILED $setting"; tail -5 $out/${tag}_$i.err; exit 1; }
   python3 - $out/${tag}_$i.json "$setting" <<'PY'
 import json, sys
