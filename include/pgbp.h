@@ -171,6 +171,15 @@ int  pgbp_plan_records(const pgbp_plan* p, int32_t tree, int32_t dir, int32_t* n
  * messages of the task << 8}.  mult! into a receiver happens in the order of the positions: the sequential task's sums. */
 int  pgbp_plan_rows(const pgbp_plan* p, int32_t tree, int32_t dir, int64_t* n_rows, int64_t* level_row0,
                     int32_t* level_nrows, int32_t* rowmap);
+/* The LEVELLED walk of regularizebeliefs_onschedule! (src/clustergraphbeliefs.jl:376-403; pgbp_regularize_onschedule),
+ * built on first use.  The walk visits the clusters in index order; every sepset carries one message, from its lower
+ * cluster to its higher one, sent in the walk's order (clusters, then each one's sepsets in index order).
+ * cluster_level[n_clusters]: level of the cluster's step (its eps edits) = 1 + the largest level of a message into it (0: none);
+ * msg_level[2*n_sepsets]: level of each directed message, -1 unsent: max(cluster_level[sender], level of the previous
+ * message into the same receiver), so that the messages into a receiver keep the walk's order;
+ * walk_pos[2*n_sepsets]: position of each sent message in the walk's order, -1 unsent.  Any pointer may be NULL. */
+int  pgbp_plan_onschedule(const pgbp_plan* p, int32_t* n_levels, int32_t* cluster_level, int32_t* msg_level,
+                          int32_t* walk_pos);
 const char* pgbp_plan_last_error(const pgbp_plan* p);
 
 /* ---- engine lifetime ------------------------------------------------------------------ */
@@ -240,6 +249,18 @@ int  pgbp_residual_kldiv(pgbp_engine* e, int32_t cluster_to, int32_t sepset, int
  * per cluster eps = max(eps(Float64), max|J|); +eps on the cluster's diagonal at the scope of each
  * incident sepset, and on the sepset's diagonal.  Asynchronous on the engine's stream. */
 int  pgbp_regularize_bycluster(pgbp_engine* e);
+/* regularizebeliefs_onschedule!(beliefs, clustergraph) (src/clustergraphbeliefs.jl:343-403) on the device, for the sites
+ * [site_begin, site_end) (other sites untouched): clusters in index order, each adds eps = max(max|J|, sqrt(eps(Float64)))
+ * on its diagonal at the scope of every sepset to a later neighbour and on that sepset's diagonal, then sends its real
+ * message (propagate_belief!, as pgbp_propagate: same arithmetic, bit for bit) to those neighbours in sepset order --
+ * level by level (pgbp_plan_onschedule), a few launches per level, one synchronisation at the end.
+ * fail_msg[n_sites] = directed message id of the first failing message in walk order or -1, fail_info[n_sites] =
+ * PosDefException.info or 0 (either may be NULL; sites outside the range get -1 / 0).  A failed site is left with every
+ * message before the failure in walk order applied; the failed message leaves its receiver, sepset and residual as
+ * pgbp_propagate does; messages later in walk order that do not depend on the failure, and the eps edits of later
+ * clusters, may already be applied. */
+int  pgbp_regularize_onschedule(pgbp_engine* e, int32_t site_begin, int32_t site_end, const pgbp_opts* opts,
+                                int32_t* fail_msg, int32_t* fail_info);
 /* propagate_1traversal_postorder! / _preorder! (src/calibration.jl:111-161), dir 0 / 1.
  * results[n_sites]: succ, fail_* filled. */
 int  pgbp_traverse(pgbp_engine* e, int32_t tree, int32_t dir, const pgbp_opts* opts, pgbp_result* results);

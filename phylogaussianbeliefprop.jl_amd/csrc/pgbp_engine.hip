@@ -100,6 +100,11 @@ struct pgbp_engine {
   bool layout_sm = false;           // the live state is in the site-minor buffers
   bool layout_bs16 = false;         // current device layout of 16/32-dim beliefs and 16-dim residuals
   bool sym_known = false, sym_ok = false;
+  // pgbp_regularize_onschedule: the levelled walk (OnSchedule) on the device, uploaded at its first call
+  bool os_ready = false;
+  int32_t *d_os_a_cl = nullptr, *d_os_ed_off = nullptr, *d_os_ed_msg = nullptr, *d_os_task_off = nullptr;
+  GRec* d_os_grecs = nullptr;
+  Entry* d_os_entries = nullptr;
   int32_t* d_one_task_off = nullptr;  // single-message task for pgbp_propagate
   Entry* d_one_entry = nullptr;
   GRec* d_one_rec = nullptr;
@@ -632,7 +637,9 @@ void pgbp_destroy(pgbp_engine* e) {
                   (void*)e->d_rpacked_off, (void*)e->d_mu, (void*)e->d_norm, (void*)e->d_info,
                   (void*)e->d_one_task_off, (void*)e->d_one_entry, (void*)e->d_one_rec, (void*)e->d_bdim, (void*)e->d_rdim,
                   (void*)e->d_symflag, (void*)e->d_bm_kind, (void*)e->d_bm_row, (void*)e->d_bm_length, (void*)e->d_bm_ithl,
-                  (void*)e->d_bm_data, (void*)e->d_bm_Rinv, (void*)e->d_bm_logdet, (void*)e->d_bm_mu})
+                  (void*)e->d_bm_data, (void*)e->d_bm_Rinv, (void*)e->d_bm_logdet, (void*)e->d_bm_mu,
+                  (void*)e->d_os_a_cl, (void*)e->d_os_ed_off, (void*)e->d_os_ed_msg, (void*)e->d_os_task_off,
+                  (void*)e->d_os_grecs, (void*)e->d_os_entries})
     if (p) (void)hipFree(p);
   for (void* p : e->lg_bufs)
     if (p) (void)hipFree(p);
@@ -1201,6 +1208,71 @@ int pgbp_regularize_bycluster(pgbp_engine* e) {
                               e->d_idx, e->d_sepcl, e->d_eps, p.n_clusters, p.n_sepsets, p.n_sites, e->st);
   e->sym_known = false;
   HIPCHK(e, hipGetLastError());
+  return PGBP_OK;
+}
+
+int pgbp_regularize_onschedule(pgbp_engine* e, int32_t site_begin, int32_t site_end, const pgbp_opts* opts,
+                               int32_t* fail_msg, int32_t* fail_info) {
+  DeviceScope device_scope(e);
+  if (!e) return PGBP_ERR_INVALID;
+  const Plan& p = e->plan;
+  if (site_begin < 0 || site_end > p.n_sites || site_begin > site_end)
+    return e->fail(PGBP_ERR_INVALID, "pgbp_regularize_onschedule: site range outside [0, n_sites]");
+  int rc = check_opts(e, opts);
+  if (rc) return rc;
+  const OnSchedule& os = plan_onschedule(p);
+  if (!e->os_ready) {
+    if ((rc = upload(e, &e->d_os_a_cl, os.a_cl)) || (rc = upload(e, &e->d_os_ed_off, os.ed_off)) ||
+        (rc = upload(e, &e->d_os_ed_msg, os.ed_msg)) || (rc = upload(e, &e->d_os_task_off, os.task_off)) ||
+        (rc = upload(e, &e->d_os_grecs, os.grecs)) || (rc = upload(e, &e->d_os_entries, os.entries)))
+      return rc;
+    e->os_ready = true;
+  }
+  const int ns = site_end - site_begin;
+  if (ns > 0) {
+    if ((rc = ensure_layout(e, false))) return rc;   // the plain layout: what pgbp_propagate runs on
+    int64_t ws = 0;   // senders above kLdsMaxDim: one workspace slab per (task, site) of their launch
+    for (const OnSchedule::Launch& ln : os.launches)
+      if (ln.kind == 2) ws = std::max(ws, (int64_t)ln.n * big_ws_doubles(ln.max_mf));
+    if (ws > 0 && (rc = ensure_ws(e, ws * ns))) return rc;
+    if ((rc = reset_fail(e))) return rc;
+    // the range's first site as site 0 of every launch (plain layout: site-major pools and word arrays)
+    DevState S = dev_state(e, opts);
+    S.pool += (int64_t)site_begin * S.pool_stride;
+    S.rpool += (int64_t)site_begin * S.rpool_stride;
+    S.flags += (int64_t)site_begin * S.n_msgs;
+    S.status += (int64_t)site_begin * S.n_msgs;
+    S.fail += site_begin;
+    S.poison += (int64_t)site_begin * S.n_clusters;
+    // Every level runs on every site, failed or not (stop_below = 0): a failure only stops what is downstream of it
+    // (poison), and everything downstream of a message comes later than it in walk order, so the lowest fail key of a
+    // site is the walk's first failure.
+    for (int L = 0; L < os.n_levels; ++L) {
+      launch_regularize_onschedule(S.pool, S.pool_stride, e->d_bdim, e->d_os_a_cl, os.level_a_off[L],
+                                   os.level_a_off[L + 1] - os.level_a_off[L], e->d_os_ed_off, e->d_os_ed_msg, e->d_msgs,
+                                   e->d_idx, ns, e->st);
+      for (int q = os.level_launch_off[L]; q < os.level_launch_off[L + 1]; ++q) {
+        const OnSchedule::Launch& ln = os.launches[q];
+        if (ln.kind == 0)
+          launch_level_generic(S, e->d_os_grecs, ln.first, ln.n, ns, 0, 0, ln.max_mf, false, e->st);
+        else
+          launch_level_big(S, e->d_os_task_off, e->d_os_entries, ln.first, ln.n, ns, 0, 0, ln.max_mf, e->d_ws, e->st);
+      }
+    }
+    e->sym_known = false;
+  }
+  std::vector<unsigned long long> keys(std::max(1, ns), kNoFail);
+  if (ns > 0)
+    HIPCHK(e, hipMemcpyAsync(keys.data(), e->d_fail + site_begin, sizeof(unsigned long long) * ns, hipMemcpyDeviceToHost,
+                             e->st));
+  HIPCHK(e, hipStreamSynchronize(e->st));
+  HIPCHK(e, hipGetLastError());
+  for (int s = 0; s < p.n_sites; ++s) {
+    const unsigned long long key = s >= site_begin && s < site_end ? keys[s - site_begin] : kNoFail;
+    const bool failed = is_failure_key(key);
+    if (fail_msg) fail_msg[s] = failed ? os.walk_msg[(size_t)(key >> kInfoBits)] : -1;
+    if (fail_info) fail_info[s] = failed ? (int32_t)(key & ((1ull << kInfoBits) - 1)) : 0;
+  }
   return PGBP_OK;
 }
 

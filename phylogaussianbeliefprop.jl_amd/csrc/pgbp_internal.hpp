@@ -131,6 +131,7 @@ constexpr int kGenericMaxDim = 64;    // largest sender the wave-per-task generi
 // a message of the large-belief kernel (bp_level_big: descriptors with 32-bit dimensions): its sender is beyond the wave-per-task
 // kernel's lane grids, or its receiver beyond the byte fields of a GRec
 inline bool big_msg(const MsgDesc& m) { return m.mf > kGenericMaxDim || m.mt > 254; }
+constexpr int kLdsMaxDim = 128;   // largest working matrix [J | h] that fits a CU's LDS (128 x 129 doubles = 132 KB of 160)
 constexpr int kChunkMaxTasks = 2400;  // a level joins a chunk of fused levels if it is all fast-class and has at most this many RECORDS (messages):
                                       // with the trees of a chunk's forest packed into at most kChunkBins workgroups (round 4) a pass of the loop
                                       // kernel holds up to 8 records per CU and the chip 2 048 per pass -- 7.6 us per fused level at that width
@@ -234,6 +235,38 @@ struct Tree {
   std::vector<FPro> tail_pros;
 };
 
+// regularizebeliefs_onschedule! (src/clustergraphbeliefs.jl:376-403) as a LEVELLED plan (plan_onschedule): the walk visits the
+// clusters in index order; cluster ci adds eps = max(max|J_ci|, sqrt(eps)) at the scope of every sepset to a later neighbour
+// (and on that sepset's diagonal), then sends to those neighbours in sepset order.  A cluster's step waits for every message
+// into it (cluster_level = 1 + the largest level of those); a message ci -> nj runs at max(cluster_level[ci], the level of
+// the previous message into nj), so the messages into one receiver keep the walk's order (same level: one task, in order).
+// Level L = phase A (the eps edits of the clusters whose step is at L: regularize_onschedule_kernel) then phase B (the
+// level's tasks on the kernels of pgbp_propagate: bp_level_generic / bp_level_big, one launch per class and ROUND -- a task
+// whose messages change class is cut into runs, run r of every task going out in round r, so that every message runs on
+// exactly the instance pgbp_propagate would pick for it).
+struct OnSchedule {
+  bool built = false;
+  int32_t n_levels = 0;
+  std::vector<int32_t> cluster_level;  // [n_clusters]
+  std::vector<int32_t> msg_level;      // [n_msgs] -1: not sent
+  std::vector<int32_t> walk_pos;       // [n_msgs] position in the walk's order of sends (the first-failure key), -1: not sent
+  std::vector<int32_t> walk_msg;       // [messages sent] the inverse of walk_pos
+  std::vector<int32_t> ed_off, ed_msg; // [n_clusters + 1] -> per cluster the messages it sends through the sepsets it edits (keep_map =
+                                       //   the sepset's scope in the cluster), in sepset order
+  std::vector<int32_t> a_cl;           // phase A: the clusters with edits, level by level
+  std::vector<int32_t> level_a_off;    // [n_levels + 1] -> a_cl
+  struct Launch {
+    int32_t kind;    // 0: bp_level_generic (first = record in grecs), 1: bp_level_big in LDS, 2: bp_level_big with the
+                     // workspace (first = task in task_off)
+    int32_t first, n, max_mf;
+  };
+  std::vector<Launch> launches;        // phase B, level after level, round after round
+  std::vector<int32_t> level_launch_off;  // [n_levels + 1] -> launches
+  std::vector<GRec> grecs;             // per generic launch: the first records of its tasks, then their later records (`next`)
+  std::vector<int32_t> task_off;       // big launches: tasks -> entries
+  std::vector<Entry> entries;
+};
+
 struct Plan {
   int32_t n_clusters = 0, n_sepsets = 0, n_sites = 1, device = 0;
   std::vector<int32_t> dims;
@@ -252,6 +285,7 @@ struct Plan {
   Tuning tune;         // PGBP_TUNING as read when the plan was built
   int32_t fast_p = 0;  // sepset dimension the register-resident kernel is instantiated for (0: none)
   bool all_fast = false;  // every task of every scheduled traversal runs on the register-resident kernel
+  mutable OnSchedule onsched;  // built on first use (plan_onschedule): a function of the graph alone
   std::string err;
 
   int32_t n_beliefs() const { return n_clusters + n_sepsets; }
@@ -266,6 +300,7 @@ GRec make_grec(const Plan& p, const Entry& en, int32_t next);  // the record of 
 int plan_set_schedule(Plan& p, int32_t n_trees, const int32_t* tree_off, const int32_t* pa_j,
                       const int32_t* ch_j);
 double plan_bytes_per_calibrate(const Plan& p, int64_t* n_messages);
+const OnSchedule& plan_onschedule(const Plan& p);  // the levelled walk of regularizebeliefs_onschedule! (built once)
 
 }  // namespace pgbp
 

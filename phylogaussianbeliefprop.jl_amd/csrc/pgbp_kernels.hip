@@ -2312,6 +2312,57 @@ void launch_regularize_bycluster(double* pool, int64_t pool_stride, const int64_
                      pool_stride, d_boff, d_dim, d_sepcl, d_eps, n_clusters, n_sepsets);
 }
 
+// ---- regularizebeliefs_onschedule!, phase A of a level (src/clustergraphbeliefs.jl:376-403; OnSchedule in pgbp_internal.hpp)
+// One wavefront per (cluster of the level, site): eps = max(max|J|, sqrt(eps(T))) BEFORE any edit, by a wave max-reduction
+// (a NaN anywhere in J makes eps NaN, as Julia's maximum and Python's max do); then for every sepset to a later neighbour,
+// in sepset order: J[i,i] += eps at the sepset's scope in the cluster (keep_map of the message the cluster sends through it;
+// one lane per diagonal entry, a barrier between sepsets so that an entry several scopes share takes its adds in that
+// order), and diag(J_sepset) += eps.  The sepsets of different clusters are distinct: no two wavefronts write one word.
+// Plain layout; pool / the site index are those of the first site of the call's range.
+constexpr double kSqrtEps = 1.4901161193847656e-08;   // sqrt(eps(Float64)) = 2^-26, exact
+__global__ __launch_bounds__(64) void regularize_onschedule_kernel(double* __restrict__ pool, int64_t pool_stride,
+                                                                   const int32_t* __restrict__ dim,
+                                                                   const int32_t* __restrict__ a_cl, int a0,
+                                                                   const int32_t* __restrict__ ed_off,
+                                                                   const int32_t* __restrict__ ed_msg,
+                                                                   const MsgDesc* __restrict__ msgs,
+                                                                   const int32_t* __restrict__ idx) {
+  const int lane = threadIdx.x, c = a_cl[a0 + blockIdx.x], site = blockIdx.y;
+  const int m = dim[c];
+  const int q0 = ed_off[c], q1 = ed_off[c + 1];
+  double* __restrict__ base = pool + (int64_t)site * pool_stride;
+  double* __restrict__ J = base + msgs[ed_msg[q0]].from_off;
+  double mx = 0.0;
+  int nan = 0;
+  for (int i = lane; i < m * m; i += kWave) {
+    const double a = fabs(J[i]);
+    nan |= a != a;
+    mx = fmax(mx, a);
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) mx = fmax(mx, __shfl_xor(mx, o));
+  const double eps = __any(nan) ? __builtin_nan("") : fmax(mx, kSqrtEps);
+  __syncthreads();   // (every lane has read J before the first add)
+  for (int q = q0; q < q1; ++q) {
+    const MsgDesc md = msgs[ed_msg[q]];
+    double* __restrict__ Js = base + md.sep_off;
+    for (int t = lane; t < md.s; t += kWave) {
+      const int i = idx[md.keep_map + t];
+      J[i + (int64_t)i * m] += eps;
+      Js[t + (int64_t)t * md.s] += eps;
+    }
+    __syncthreads();
+  }
+}
+
+void launch_regularize_onschedule(double* pool, int64_t pool_stride, const int32_t* d_dim, const int32_t* d_a_cl, int a0,
+                                  int n, const int32_t* d_ed_off, const int32_t* d_ed_msg, const MsgDesc* d_msgs,
+                                  const int32_t* d_idx, int n_sites, hipStream_t st) {
+  if (n <= 0 || n_sites <= 0) return;
+  hipLaunchKernelGGL(regularize_onschedule_kernel, dim3(n, n_sites), dim3(kWave), 0, st, pool, pool_stride, d_dim, d_a_cl, a0,
+                     d_ed_off, d_ed_msg, d_msgs, d_idx);
+}
+
 // ---- record gather/scatter between the ABI's packed layout and the padded device records
 __global__ void records_kernel(const double* __restrict__ src, int64_t src_stride,
                                const int64_t* __restrict__ src_off, double* __restrict__ dst, int64_t dst_stride,

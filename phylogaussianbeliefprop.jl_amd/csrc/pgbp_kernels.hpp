@@ -106,7 +106,6 @@ void launch_chunk_generic(const DevState& S, const GRec* d_recs, const int32_t* 
 void launch_level_big(const DevState& S, const int32_t* d_task_off, const Entry* d_entries, int task0, int ntasks,
                       int n_sites, unsigned long long seq_base, unsigned long long stop_below, int max_mf, double* d_ws,
                       hipStream_t st);
-constexpr int kLdsMaxDim = 128;   // largest working matrix [J | h] that fits a CU's LDS (128 x 129 doubles = 132 KB of 160)
 int64_t big_ws_doubles(int max_mf);   // doubles of one workspace slab for a working matrix of dimension max_mf (0: fits LDS)
 
 // thread-per-(site, task) kernel for graphs whose beliefs all have dimension <= 2 (univariate batches)
@@ -256,6 +255,10 @@ void launch_regularize_bycluster(double* pool, int64_t pool_stride, const int64_
                                  const int32_t* d_nb_off, const int32_t* d_nb_msg, const MsgDesc* d_msgs,
                                  const int32_t* d_idx, const int32_t* d_sepcl, double* d_eps, int n_clusters,
                                  int n_sepsets, int n_sites, hipStream_t st);
+// regularizebeliefs_onschedule!, phase A of one level (OnSchedule): the n clusters d_a_cl[a0 ..], plain layout
+void launch_regularize_onschedule(double* pool, int64_t pool_stride, const int32_t* d_dim, const int32_t* d_a_cl, int a0,
+                                  int n, const int32_t* d_ed_off, const int32_t* d_ed_msg, const MsgDesc* d_msgs,
+                                  const int32_t* d_idx, int n_sites, hipStream_t st);
 void launch_reduce_flags(const int32_t* flags, int n_msgs, int n_sites, int32_t* d_iscal, hipStream_t st, int sm = 0);
 // iscal[site] = notcal[site] == 0 (DevState::notcal)
 void launch_iscal_from_notcal(const int32_t* d_notcal, int32_t* d_iscal, int n_sites, hipStream_t st);

@@ -9,6 +9,7 @@
 //   * postorder = edges in reverse, child -> parent, residual key (pa, ch);
 //     preorder = edges in order, parent -> child, key (ch, pa) (src/calibration.jl:121-151).
 #include <algorithm>
+#include <array>
 #include <cstdlib>
 #include <cstring>
 #include <map>
@@ -1269,6 +1270,141 @@ double plan_bytes_per_calibrate(const Plan& p, int64_t* n_messages) {
   return bytes * p.n_sites;
 }
 
+// ---- regularizebeliefs_onschedule! as a levelled plan (OnSchedule, pgbp_internal.hpp) ----------------------------------
+// The reference's walk (src/clustergraphbeliefs.jl:376-403): clusters in index order, each one's neighbours in sepset order;
+// cluster ci edits the sepsets to the neighbours it has not heard from and sends to the ones it has not sent to -- the
+// neighbours of higher index, every message going from the lower cluster of its sepset to the higher one.
+const OnSchedule& plan_onschedule(const Plan& p) {
+  OnSchedule& o = p.onsched;
+  if (o.built) return o;
+  const int nc = p.n_clusters, nm = p.n_msgs();
+  std::vector<std::vector<std::pair<int32_t, int32_t>>> nb(nc);   // (neighbour, the message this cluster sends to it)
+  for (int k = 0; k < p.n_sepsets; ++k) {
+    const int a = p.sepset_clusters[2 * k], b = p.sepset_clusters[2 * k + 1];
+    nb[a].push_back({b, 2 * k + 1});   // (message 2k + 1 is received by b)
+    nb[b].push_back({a, 2 * k});
+  }
+  o.cluster_level.assign(nc, 0);
+  o.msg_level.assign(nm, -1);
+  o.walk_pos.assign(nm, -1);
+  o.walk_msg.clear();
+  o.ed_off.assign(nc + 1, 0);
+  o.ed_msg.clear();
+  std::vector<int32_t> last_into(nc, -1);   // level of the last message into each cluster so far
+  std::set<std::pair<int32_t, int32_t>> sent;   // (sender, receiver): the reference's `sent` (keyed by cluster pairs)
+  std::vector<std::pair<int32_t, int32_t>> sends;
+  for (int ci = 0; ci < nc; ++ci) {
+    const int L = o.cluster_level[ci];   // final: every message into ci comes from a lower cluster
+    sends.clear();
+    for (const auto& [nj, msg] : nb[ci]) {
+      if (sent.insert({nj, ci}).second) o.ed_msg.push_back(msg);
+      if (sent.insert({ci, nj}).second) sends.push_back({nj, msg});
+    }
+    o.ed_off[ci + 1] = (int32_t)o.ed_msg.size();
+    for (const auto& [nj, msg] : sends) {
+      const int ml = std::max(L, last_into[nj]);
+      o.msg_level[msg] = ml;
+      o.walk_pos[msg] = (int32_t)o.walk_msg.size();
+      o.walk_msg.push_back(msg);
+      last_into[nj] = ml;
+      o.cluster_level[nj] = std::max(o.cluster_level[nj], ml + 1);
+    }
+  }
+  int nl = 0;
+  for (int c = 0; c < nc; ++c) nl = std::max(nl, o.cluster_level[c] + 1);
+  o.n_levels = nl;
+  // phase A: the clusters with something to add, level by level
+  o.level_a_off.assign(nl + 1, 0);
+  std::vector<std::vector<int32_t>> acl(nl);
+  for (int c = 0; c < nc; ++c) {
+    bool any = false;
+    for (int q = o.ed_off[c]; q < o.ed_off[c + 1]; ++q) any |= p.msgs[o.ed_msg[q]].s > 0;
+    if (any) acl[o.cluster_level[c]].push_back(c);
+  }
+  o.a_cl.clear();
+  for (int L = 0; L < nl; ++L) {
+    o.a_cl.insert(o.a_cl.end(), acl[L].begin(), acl[L].end());
+    o.level_a_off[L + 1] = (int32_t)o.a_cl.size();
+  }
+  // phase B: per level one task per receiver (its messages in walk order), cut into runs of one kernel instance each
+  auto kind_of = [&](int msg) {
+    const MsgDesc& m = p.msgs[msg];
+    return !big_msg(m) ? 0 : (m.mf > kLdsMaxDim ? 2 : 1);
+  };
+  std::vector<std::vector<std::vector<int32_t>>> tasks(nl);
+  std::vector<int32_t> cur_task(nc, -1), cur_level(nc, -1);
+  for (int32_t msg : o.walk_msg) {
+    const int L = o.msg_level[msg], to = p.msgs[msg].to_b;
+    if (cur_level[to] != L) {
+      cur_level[to] = L;
+      cur_task[to] = (int32_t)tasks[L].size();
+      tasks[L].emplace_back();
+    }
+    tasks[L][cur_task[to]].push_back(msg);
+  }
+  o.launches.clear();
+  o.level_launch_off.assign(nl + 1, 0);
+  o.grecs.clear();
+  o.task_off.assign(1, 0);
+  o.entries.clear();
+  auto entry = [&](int msg) {
+    Entry en{};
+    en.msg = msg;
+    en.seq = o.walk_pos[msg];
+    return en;
+  };
+  for (int L = 0; L < nl; ++L) {
+    // runs[t] = (kind, first, one past the last message of the run) of task t
+    std::vector<std::vector<std::array<int, 3>>> runs(tasks[L].size());
+    size_t max_runs = 0;
+    for (size_t t = 0; t < tasks[L].size(); ++t) {
+      const std::vector<int32_t>& ms = tasks[L][t];
+      for (size_t i = 0; i < ms.size(); ++i) {
+        const int kd = kind_of(ms[i]);
+        if (runs[t].empty() || runs[t].back()[0] != kd) runs[t].push_back({kd, (int)i, (int)i + 1});
+        else runs[t].back()[2] = (int)i + 1;
+      }
+      max_runs = std::max(max_runs, runs[t].size());
+    }
+    for (size_t r = 0; r < max_runs; ++r) {
+      for (int kd = 0; kd < 3; ++kd) {
+        std::vector<std::pair<size_t, int>> sel;   // (task, run index)
+        for (size_t t = 0; t < tasks[L].size(); ++t)
+          if (r < runs[t].size() && runs[t][r][0] == kd) sel.push_back({t, (int)r});
+        if (sel.empty()) continue;
+        OnSchedule::Launch ln{kd, 0, (int32_t)sel.size(), 0};
+        if (kd == 0) {
+          ln.first = (int32_t)o.grecs.size();
+          int32_t later = ln.first + (int32_t)sel.size();   // where the runs' later records go
+          for (const auto& [t, ri] : sel) {
+            const auto& rn = runs[t][ri];
+            o.grecs.push_back(make_grec(p, entry(tasks[L][t][rn[1]]), rn[2] - rn[1] > 1 ? later : -1));
+            later += rn[2] - rn[1] - 1;
+          }
+          for (const auto& [t, ri] : sel) {
+            const auto& rn = runs[t][ri];
+            for (int i = rn[1] + 1; i < rn[2]; ++i)
+              o.grecs.push_back(make_grec(p, entry(tasks[L][t][i]), i + 1 < rn[2] ? (int32_t)o.grecs.size() + 1 : -1));
+          }
+        } else {
+          ln.first = (int32_t)o.task_off.size() - 1;
+          for (const auto& [t, ri] : sel) {
+            const auto& rn = runs[t][ri];
+            for (int i = rn[1]; i < rn[2]; ++i) o.entries.push_back(entry(tasks[L][t][i]));
+            o.task_off.push_back((int32_t)o.entries.size());
+          }
+        }
+        for (const auto& [t, ri] : sel)
+          for (int i = runs[t][ri][1]; i < runs[t][ri][2]; ++i) ln.max_mf = std::max(ln.max_mf, p.msgs[tasks[L][t][i]].mf);
+        o.launches.push_back(ln);
+      }
+    }
+    o.level_launch_off[L + 1] = (int32_t)o.launches.size();
+  }
+  o.built = true;
+  return o;
+}
+
 }  // namespace pgbp
 
 // ------------------------------------------------------------------ C ABI (host-only part)
@@ -1446,6 +1582,17 @@ int pgbp_plan_rows(const pgbp_plan* p, int32_t tree, int32_t dir, int64_t* n_row
   if (level_row0) std::copy(tr->level_rowbase.begin(), tr->level_rowbase.end(), level_row0);
   if (level_nrows) std::copy(tr->level_nrows.begin(), tr->level_nrows.end(), level_nrows);
   if (rowmap) std::copy(tr->rowmap.begin(), tr->rowmap.end(), rowmap);
+  return PGBP_OK;
+}
+
+int pgbp_plan_onschedule(const pgbp_plan* p, int32_t* n_levels, int32_t* cluster_level, int32_t* msg_level,
+                         int32_t* walk_pos) {
+  if (!p || p->p.msgs.size() != (size_t)p->p.n_msgs() || p->p.n_clusters <= 0) return PGBP_ERR_INVALID;
+  const pgbp::OnSchedule& o = pgbp::plan_onschedule(p->p);
+  if (n_levels) *n_levels = o.n_levels;
+  if (cluster_level) std::copy(o.cluster_level.begin(), o.cluster_level.end(), cluster_level);
+  if (msg_level) std::copy(o.msg_level.begin(), o.msg_level.end(), msg_level);
+  if (walk_pos) std::copy(o.walk_pos.begin(), o.walk_pos.end(), walk_pos);
   return PGBP_OK;
 }
 

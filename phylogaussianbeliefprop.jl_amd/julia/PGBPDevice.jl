@@ -254,6 +254,26 @@ function PGBP.regularizebeliefs_bycluster!(o::DeviceClusterGraphBelief, _cluster
     pull!(o)
 end
 
+"""
+    regularizebeliefs_onschedule!(beliefs, clustergraph)
+
+src/clustergraphbeliefs.jl:343-403 on the device (the graph is the engine's): the walk levelled once per graph, a few
+launches per level, bit for bit the sequential walk.  Throws the BPPosDefException of the first failing message in walk
+order, as the reference does.
+"""
+function PGBP.regularizebeliefs_onschedule!(o::DeviceClusterGraphBelief, _cg=nothing)
+    fail_msg = Ref(Int32(-1)); fail_info = Ref(Int32(0))
+    check(o.handle, @ccall LIB.pgbp_regularize_onschedule(o.handle::Ptr{Cvoid}, Int32(0)::Int32, Int32(1)::Int32,
+        Ref(Opts(0, 1, 0, 0, 1e-5))::Ref{Opts}, fail_msg::Ref{Int32}, fail_info::Ref{Int32})::Cint)
+    pull!(o)
+    fail_msg[] < 0 && return nothing
+    j = o.cgb.nclusters + fail_msg[] ÷ 2 + 1                # message 2(k-1) + dir - 1 is received by the sepset's end `dir`
+    lab = o.cgb.belief[j].metadata[fail_msg[] % 2 == 0 ? 2 : 1]
+    from = PGBP.clusterindex(lab, o.cgb)
+    integ = setdiff(1:length(o.cgb.belief[from].h), PGBP.scopeindex(o.cgb.belief[j], o.cgb.belief[from]))
+    throw(PGBP.BPPosDefException("belief $(o.cgb.belief[from].metadata), integrating $(integ)", fail_info[]))
+end
+
 "free_energy(beliefs) -> (average energy, approximate entropy, free energy) (src/score.jl:162-182)"
 function PGBP.free_energy(o::DeviceClusterGraphBelief)
     out = zeros(3); info = Ref(Int32(0))

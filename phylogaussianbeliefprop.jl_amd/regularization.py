@@ -3,9 +3,13 @@
 All three add positive values to diagonal entries of cluster and sepset precisions so that every belief
 becomes non-degenerate while the graphical model (product of cluster beliefs / product of sepset beliefs)
 is unchanged.  `regularizebeliefs_bycluster_` is the one inside the optimisation loop of
-calibrate_optimize_clustergraph! (src/calibration.jl:335-343) and runs entirely on the device; the other two
-are graph walks on the host that edit single beliefs through pgbp_get_belief / pgbp_set_belief and send the
-real messages of `regularizebeliefs_onschedule!` with pgbp_propagate."""
+calibrate_optimize_clustergraph! (src/calibration.jl:335-343) and runs entirely on the device;
+`regularizebeliefs_onschedule_` runs on the device as a levelled plan (pgbp_regularize_onschedule) -- its host walk,
+which edits single beliefs through pgbp_get_belief / pgbp_set_belief and sends every real message with its own
+pgbp_propagate, is kept for an engine of several sites regularised at `beliefs.site` alone; the node-subtree
+regulariser is a graph walk on the host."""
+import ctypes as C
+
 import numpy as np
 
 from . import _lib as L
@@ -174,11 +178,37 @@ def _scopeindex_node(node_lab, sep, clu):
             np.nonzero(c_insc.T.reshape(-1)[clu.inscope.T.reshape(-1)])[0])
 
 
-def regularizebeliefs_onschedule_(beliefs, clustergraph=None):
+def regularizebeliefs_onschedule_(beliefs, clustergraph=None, *, all_sites=False):
+    """regularizebeliefs_onschedule!(beliefs, clustergraph) (src/clustergraphbeliefs.jl:343-403) on the device
+    (pgbp_regularize_onschedule): clusters in label order; each first receives the default message eps*I
+    (eps = max(max|J|, sqrt(eps(T)))) on every edge it has not heard from, then sends its real message on every edge it
+    has not yet used -- levelled once per graph, a few launches per level, bit for bit the sequential walk.
+    An engine of one site, or `all_sites=True`: every site.  Several sites without `all_sites`: the host walk at
+    `beliefs.site` (eps edits on that site, messages on every site), as before.  A failing message raises the
+    BPPosDefException of the walk's first failure (with `all_sites`: of the lowest failing site)."""
+    if beliefs.n_sites > 1 and not all_sites:
+        _regularizebeliefs_onschedule_host(beliefs, clustergraph)
+        return
+    ns = beliefs.n_sites
+    fail_msg = np.full(ns, -1, dtype=np.int32)
+    fail_info = np.zeros(ns, dtype=np.int32)
+    o = beliefs._opts()
+    _check(beliefs._lib.pgbp_regularize_onschedule(beliefs._eng, 0, ns, C.byref(o), L.i32p(fail_msg),
+                                                   L.i32p(fail_info)), beliefs._eng)
+    beliefs._invalidate()
+    for site in range(ns):
+        if fail_msg[site] >= 0:
+            k, d = divmod(int(fail_msg[site]), 2)
+            sender = int(beliefs._sepcl[k][0 if d == 1 else 1])   # message 2k + d is received by cluster d of sepset k
+            raise beliefs._exception_for(sender, k, int(fail_info[site]))
+
+
+def _regularizebeliefs_onschedule_host(beliefs, clustergraph=None):
     """regularizebeliefs_onschedule!(beliefs, clustergraph) (src/clustergraphbeliefs.jl:376-403): clusters in
     label order; each first receives the default message eps*I (eps = max(max|J|, sqrt(eps(T)))) on every
     edge it has not heard from, then sends its real message (propagate_belief! on the device) on every edge
-    it has not yet used.  One site (beliefs.site)."""
+    it has not yet used.  The eps edits on one site (beliefs.site), the messages on every site: the walk on the host,
+    one pgbp_propagate per message."""
     nb = _neighbors(beliefs)
     nc = beliefs.nclusters
     lib, eng, site = beliefs._lib, beliefs._eng, beliefs.site
