@@ -156,23 +156,19 @@ constexpr size_t kMixedLevelFastMinNarrow = (size_t)1 << 30;  // ... where the s
 // PGBP_TUNING -- comma-separated `key` or `key=value` tokens -- and carried in the plan: what the differential fuzz of the
 // launch modes switches (tests/test_gpu_parity.py), plus the few numeric thresholds worth re-sweeping on other trees.
 // Everything else that used to be an environment switch of a finished experiment is gone (DESIGN.md section 4 keeps
-// the measurements).  Unknown tokens are an error of pgbp_create / pgbp_plan_create.
+// the measurements).  An unknown token, or a value its key does not accept, is an error of pgbp_create / pgbp_plan_create.
 struct Tuning {
   bool tail = true;            // no_tail: no single-workgroup tail and no chunks: one launch per level
   bool chunks = true;          // no_chunks: no chunks of fused levels
   bool prologues = true;       // no_prologue: Bethe graphs of trees on the two-level schedule (no prologue fusion)
-  bool chain_fusion = false;   // chain_fusion: unary clusters passed through inside one task of the wave-per-task kernel (opt-in)
   bool pair2 = true;           // pair=0: chunks of small messages on bp_chunk_generic (one wavefront per task) instead of bp_chunk_pair
   bool loop2 = true;           // loop=0: tail and chunks of the packed layout on bp_fast16's own loop mode (one wavefront per record)
   bool packed_layouts = true;  // plain_layout: keep the ABI's record layout on the device (no BS16, no site-minor)
   long long mixed_fast_min = -1;   // mixed_fast_min=n: a level with both task classes splits from n fast-class tasks on (-1: default)
   int small4_min = kSmall4MinTasksDefault;   // small4_min=n: four tasks per wavefront from n tasks on (-1: never)
   int chunk_bins = -1;         // chunk_bins=n: workgroups of a chunk launch at most (0: one per tree of its forest; -1: kChunkBins)
-  int chunk_max_recs = -1, chunk_max_tasks = -1;   // chunk_max_recs / chunk_max_tasks=n: widest fused level (-1: defaults)
-  long long chunk_uni_max = -1;   // chunk_uni_max=n: site batches: a level joins a chunk while tasks x sites <= n
-  int chunk_depth = -1, chunk_depth_generic = -1;   // chunk_depth / chunk_depth_generic=n: levels per chunk (-1: kChunkDepth / kChunkGenericDepth)
 };
-// parses PGBP_TUNING; false + message on an unknown token
+// parses PGBP_TUNING; false + message on an unknown token or a bad value
 bool read_tuning(Tuning& t, std::string& err);
 
 struct Traversal {

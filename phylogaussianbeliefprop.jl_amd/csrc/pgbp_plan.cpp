@@ -10,6 +10,8 @@
 //     preorder = edges in order, parent -> child, key (ch, pa) (src/calibration.jl:121-151).
 #include <algorithm>
 #include <array>
+#include <cerrno>
+#include <climits>
 #include <cstdlib>
 #include <cstring>
 #include <map>
@@ -37,25 +39,29 @@ bool read_tuning(Tuning& t, std::string& err) {
     while (!tok.empty() && tok.back() == ' ') tok.pop_back();
     if (tok.empty()) continue;
     const size_t eq = tok.find('=');
-    const std::string key = tok.substr(0, eq), val = eq == std::string::npos ? "" : tok.substr(eq + 1);
-    const long long num = val.empty() ? 0 : atoll(val.c_str());
-    if (key == "no_tail") t.tail = false;
-    else if (key == "no_chunks") t.chunks = false;
-    else if (key == "no_prologue") t.prologues = false;
-    else if (key == "chain_fusion") t.chain_fusion = true;
-    else if (key == "pair") t.pair2 = num != 0;
-    else if (key == "loop") t.loop2 = num != 0;
-    else if (key == "plain_layout") t.packed_layouts = false;
-    else if (key == "mixed_fast_min") t.mixed_fast_min = num;
-    else if (key == "small4_min") t.small4_min = (int)num;
-    else if (key == "chunk_bins") t.chunk_bins = (int)num;
-    else if (key == "chunk_max_recs") t.chunk_max_recs = (int)num;
-    else if (key == "chunk_max_tasks") t.chunk_max_tasks = (int)num;
-    else if (key == "chunk_uni_max") t.chunk_uni_max = num;
-    else if (key == "chunk_depth") t.chunk_depth = (int)num;
-    else if (key == "chunk_depth_generic") t.chunk_depth_generic = (int)num;
-    else {
-      err = "PGBP_TUNING: unknown token '" + tok + "'";
+    const std::string key = tok.substr(0, eq);
+    const bool flag = eq == std::string::npos;   // a flag-only key takes no value, a valued key one whole number in its range
+    long long num = 0;
+    bool numeric = false;
+    if (!flag) {
+      char* stop = nullptr;
+      errno = 0;
+      num = strtoll(tok.c_str() + eq + 1, &stop, 10);
+      numeric = stop != tok.c_str() + eq + 1 && *stop == '\0' && errno == 0;
+    }
+    auto within = [&](long long lo, long long hi) { return numeric && num >= lo && num <= hi; };
+    bool ok = false;
+    if (key == "no_tail") { ok = flag; t.tail = false; }
+    else if (key == "no_chunks") { ok = flag; t.chunks = false; }
+    else if (key == "no_prologue") { ok = flag; t.prologues = false; }
+    else if (key == "plain_layout") { ok = flag; t.packed_layouts = false; }
+    else if (key == "pair") { ok = within(0, 1); t.pair2 = num != 0; }
+    else if (key == "loop") { ok = within(0, 1); t.loop2 = num != 0; }
+    else if (key == "mixed_fast_min") { ok = within(-1, LLONG_MAX); t.mixed_fast_min = num; }
+    else if (key == "small4_min") { ok = within(-1, INT_MAX); t.small4_min = (int)num; }
+    else if (key == "chunk_bins") { ok = within(0, INT_MAX); t.chunk_bins = (int)num; }
+    if (!ok) {
+      err = "PGBP_TUNING: unknown key or bad value in token '" + tok + "'";
       return false;
     }
   }
@@ -236,7 +242,7 @@ static bool prologue_pair(const MsgDesc& light, const MsgDesc& heavy, int P) {
 // Can the whole task run as ONE workgroup of the register-resident kernel, one wave per message?
 static bool fast_task(const Plan& p, const Traversal& tr, int t, bool postorder, int* block_up0, int* block_mt) {
   const int e0 = tr.task_off[t], e1 = tr.task_off[t + 1];
-  int up0 = -1, mt = -1, first_main = -1, mains = 0;
+  int up0 = -1, mt = -1, mains = 0;
   for (int e = e0; e < e1; ++e) {
     const MsgDesc& m = p.msgs[tr.entries[e].msg];
     if (!fast_msg(m, p.fast_p)) return false;
@@ -244,11 +250,7 @@ static bool fast_task(const Plan& p, const Traversal& tr, int t, bool postorder,
       if (e + 1 >= e1 || tr.entries[e + 1].pro || !prologue_pair(m, p.msgs[tr.entries[e + 1].msg], p.fast_p)) return false;
       continue;
     }
-    if (first_main < 0) first_main = e;
     if (++mains > kFastMaxWaves) return false;
-    // a fused chain (build_traversals) passes through several receivers / senders: generic kernel
-    const MsgDesc& m0 = p.msgs[tr.entries[first_main].msg];
-    if (postorder ? m.to_b != m0.to_b : m.from_b != m0.from_b) return false;
     if (postorder && m.s > 0) {  // all deltas must land on the same receiver block
       if (up0 >= 0 && (m.up0 != up0 || m.mt != mt)) return false;
       up0 = m.up0;
@@ -524,7 +526,7 @@ static void finalize_traversal(const Plan& p, Traversal& tr, bool postorder) {
         // one after the other at several microseconds each, and on the narrow levels that latency is the level's time.
         // (Not in the univariate site-minor engines, whose tasks are spread over sites, not over messages.)
         bool split = grp == &slow && !postorder && !task_is_big && p.max_dim > 2;
-        for (int e = e0 + 1; e < e1; ++e)   // (a chain-fused task passes through several senders: its messages depend on each other)
+        for (int e = e0 + 1; e < e1; ++e)   // (behind a prologue entry, whose sender is another cluster, the task's own message depends on it)
           split = split && p.msgs[tr.entries[e].msg].from_b == p.msgs[tr.entries[e0].msg].from_b;
         for (int e = e0; e < e1; ++e) {
           Entry en = tr.entries[e];
@@ -674,14 +676,8 @@ static void build_chunks(const Plan& p, Traversal& tr, bool postorder) {
   tr.centries.clear();
   tr.cpros.clear();
   tr.cgroups.clear();
-  // (chain fusion makes tasks that pass through several receivers: the forest below assumes one receiver / sender per task)
-  const bool off = !p.tune.chunks || !p.tune.tail || p.tune.chain_fusion;
-  const int depth_fast = p.tune.chunk_depth >= 2 ? p.tune.chunk_depth : kChunkDepth;
-  const int depth_generic = p.tune.chunk_depth_generic >= 2 ? p.tune.chunk_depth_generic : kChunkGenericDepth;
-  const int max_tasks = p.tune.chunk_max_recs > 0 ? p.tune.chunk_max_recs : kChunkMaxTasks;
-  const int max_tasks_generic = p.tune.chunk_max_tasks > 0 ? p.tune.chunk_max_tasks : kChunkGenericMaxTasks;
   const int nlev = (int)tr.level_off.size() - 1;
-  if (off || nlev <= 0) return;
+  if (!p.tune.chunks || !p.tune.tail || nlev <= 0) return;
   const int ntasks = (int)tr.task_off.size() - 1;
   std::vector<int32_t> task_level(ntasks, 0);
   for (int L = 0; L < nlev; ++L)
@@ -708,10 +704,10 @@ static void build_chunks(const Plan& p, Traversal& tr, bool postorder) {
     // (a level of a site batch joins a chunk while its launch could not fill the chip: tasks x sites threads)
     // (measured, three repetitions each: 65 536 threads best for 2 000 and 8 000 sites; 262 144 another 2 % for 1 000 -- the
     // fewer the sites, the less a level's own launch has to do)
-    const long long uni_max = p.tune.chunk_uni_max >= 0 ? p.tune.chunk_uni_max : (long long)kChunkUniMaxThreads * (p.n_sites <= 1024 ? 4 : 1);
+    const long long uni_max = (long long)kChunkUniMaxThreads * (p.n_sites <= 1024 ? 4 : 1);
     if (uni) return nt > 0 && (long long)nt * p.n_sites <= uni_max;
     // (register-resident levels are measured in RECORDS -- wavefront pairs of a pass --, wave-per-task ones in tasks)
-    return nt > 0 && (all_fast(L) ? tr.level_nrecs[L] <= max_tasks : nt <= max_tasks_generic) && tr.level_nbig[L] == 0 &&
+    return nt > 0 && (all_fast(L) ? tr.level_nrecs[L] <= kChunkMaxTasks : nt <= kChunkGenericMaxTasks) && tr.level_nbig[L] == 0 &&
            (all_fast(L) || (tr.level_nfast[L] == 0 && level_mf[L] <= kChunkGenericMaxMf));   // (a generic chunk walks message
            // records, which the fast-class tasks of a mixed level do not have)
   };
@@ -727,7 +723,7 @@ static void build_chunks(const Plan& p, Traversal& tr, bool postorder) {
     int R = L;
     while (R < hi && eligible(R) && all_fast(R) == all_fast(L)) ++R;   // one kernel class per run (and per chunk)
     // the run [L, R): cut into chunks from the root end, so that the odd short chunk is the wide one
-    const int depth = (all_fast(L) || uni) ? depth_fast : depth_generic;   // (wave-per-task chunks only: the thread-per-site ones keep 4)
+    const int depth = (all_fast(L) || uni) ? kChunkDepth : kChunkGenericDepth;   // (wave-per-task chunks only: the thread-per-site ones keep 4)
     if (postorder) {
       for (int b = R; b > L;) {
         int a = b - 1;
@@ -900,21 +896,18 @@ static void build_chunks(const Plan& p, Traversal& tr, bool postorder) {
   }
 }
 
-// Level-synchronous schedules of one spanning tree.
-// fuse = 1: CHAIN FUSION (opt-in).  A cluster with exactly one child in the schedule tree receives one message and can send
-// at once: the wave that delivered the message goes on with the cluster's own message(s) instead of leaving them to the
-// next level (= the next kernel launch).  Postorder: the single message into a unary cluster X is prepended to the
-// entry X -> parent(X) of the task of parent(X); preorder: the task of a cluster S whose parent has no other child is
-// appended to the parent's task.  Message order into every receiver, sequence numbers and arithmetic are unchanged;
-// only the grouping into waves and levels is: Bethe graphs (factor clusters are unary) lose half of their levels.
-// Fused tasks run on the generic kernel (entries of a task are executed in order by one wavefront).
-// fuse = 2: PROLOGUE FUSION (default where it applies).  Only the pairs the register-resident kernel runs as one record
-// (prologue_pair): F has one child C and a parent Y; its one incoming message of a traversal (postorder: C -> F,
-// preorder: Y -> F) integrates nothing and lands on the block its own message (F -> Y / F -> C) integrates out: the
-// incoming message becomes the PROLOGUE entry (Entry::pro) in front of F's own.  Every factor cluster of a tree's Bethe
-// graph is such an F: half of the levels go, and the tasks stay on the register-resident kernel.
+// Level-synchronous schedules of one spanning tree: a postorder (a message goes out at the height
+// of its sender, the messages into one receiver are one task) and its mirror image, a preorder as late as possible (the
+// messages of one sender are one task).  Message order into every receiver, sequence numbers and arithmetic are the
+// sequential loop's; only the grouping into tasks and levels is the planner's.  Two schedules:
+// PLAIN LEVELS (prologues = false): one level per unit of height, every message an entry of its own.
+// PROLOGUE FUSION (prologues = true; plan_set_schedule keeps it where the register-resident kernel runs the whole tree).
+// Only the pairs that kernel runs as one record (prologue_pair): F has one child C and a parent Y; its one incoming
+// message of a traversal (postorder: C -> F, preorder: Y -> F) integrates nothing and lands on the block its own message
+// (F -> Y / F -> C) integrates out: the incoming message becomes the PROLOGUE entry (Entry::pro) in front of F's own.
+// Every factor cluster of a tree's Bethe graph is such an F: half of the levels go.
 static bool tree_all_fast(const Tree& t);
-static void build_traversals(const Plan& p, Tree& t, int fuse) {
+static void build_traversals(const Plan& p, Tree& t, bool prologues) {
   const int n = (int)t.pa.size();
   // message id of edge i in each direction: sepset k = (a, b); dir 0 is received by a
   auto msg_to = [&](int i, int receiver) {
@@ -927,13 +920,9 @@ static void build_traversals(const Plan& p, Tree& t, int fuse) {
     if (++nchild[t.pa[i]] == 1) only_child_edge[t.pa[i]] = i;
     parent_edge[t.ch[i]] = i;
   }
-  auto unary = [&](int cluster) {
-    auto it = nchild.find(cluster);
-    return fuse == 1 && it != nchild.end() && it->second == 1;
-  };
-  // fuse = 2: is F's one incoming message of the postorder / preorder the prologue of its own?
+  // is F's one incoming message of the postorder / preorder the prologue of its own?
   auto pro_cluster = [&](int F, bool post) {
-    if (fuse != 2) return false;
+    if (!prologues) return false;
     auto ic = nchild.find(F);
     auto ip = parent_edge.find(F);
     if (ic == nchild.end() || ic->second != 1 || ip == parent_edge.end()) return false;
@@ -942,14 +931,13 @@ static void build_traversals(const Plan& p, Tree& t, int fuse) {
     const int heavy = post ? msg_to(ep, t.pa[ep]) : msg_to(ec, t.ch[ec]);
     return prologue_pair(p.msgs[light], p.msgs[heavy], p.fast_p);
   };
-  // ---- postorder: level = height of the child in the schedule tree (chains collapsed)
+  // ---- postorder: level = height of the child in the schedule tree (a prologue does not add to it)
   std::unordered_map<int, int> hnode;  // cluster -> level at which it can send (its height; leaves are absent: 0)
   int post_levels = 0;
   {
     std::vector<int> lvl(n);
-    std::vector<uint8_t> chained_edge(n, 0);  // the message of edge i rides in front of the edge above its receiver
-    for (int i = 0; i < n; ++i)
-      chained_edge[i] = (unary(t.pa[i]) && parent_edge.count(t.pa[i])) || pro_cluster(t.pa[i], true);
+    std::vector<uint8_t> pro_edge(n, 0);  // the message of edge i is the prologue of the edge above its receiver
+    for (int i = 0; i < n; ++i) pro_edge[i] = pro_cluster(t.pa[i], true);
     int nlev = 0;
     for (int i = n - 1; i >= 0; --i) {
       int h = 0;
@@ -957,14 +945,14 @@ static void build_traversals(const Plan& p, Tree& t, int fuse) {
       if (it != hnode.end()) h = it->second;
       lvl[i] = h;
       int& hp = hnode[t.pa[i]];
-      // a unary parent that has an edge above it sends in the same level, right after this message
-      hp = std::max(hp, chained_edge[i] ? h : h + 1);
+      // (behind a prologue the parent sends in the same level)
+      hp = std::max(hp, pro_edge[i] ? h : h + 1);
       nlev = std::max(nlev, h + 1);
     }
     // tasks: group by (level, target parent); entries in reference order (decreasing i)
     std::vector<std::vector<int>> bylevel(nlev);
     for (int i = n - 1; i >= 0; --i)
-      if (!chained_edge[i]) bylevel[lvl[i]].push_back(i);  // chained edges ride in front of the edge above their receiver
+      if (!pro_edge[i]) bylevel[lvl[i]].push_back(i);
     Traversal& tr = t.post;
     tr = Traversal{};
     tr.level_off.push_back(0);
@@ -984,10 +972,9 @@ static void build_traversals(const Plan& p, Tree& t, int fuse) {
       }
       for (auto& tk : tasks) {
         for (int top : tk) {
-          // the chain below `top`: single child edges of unary / prologue clusters, deepest first
+          // the chain below `top`: single child edges of prologue clusters, deepest first
           chain.assign(1, top);
-          while (unary(t.ch[chain.back()]) || pro_cluster(t.ch[chain.back()], true))
-            chain.push_back(only_child_edge[t.ch[chain.back()]]);
+          while (pro_cluster(t.ch[chain.back()], true)) chain.push_back(only_child_edge[t.ch[chain.back()]]);
           for (int q = (int)chain.size() - 1; q >= 0; --q) {
             const int i = chain[q];
             Entry e{};
@@ -995,37 +982,29 @@ static void build_traversals(const Plan& p, Tree& t, int fuse) {
             e.edge = i;
             e.reuse = 0;
             e.seq = n - 1 - i;
-            e.pro = (fuse == 2 && q > 0) ? 1 : 0;
+            e.pro = q > 0 ? 1 : 0;
             tr.entries.push_back(e);
             tr.max_mf = std::max(tr.max_mf, p.msgs[e.msg].mf);
           }
         }
         tr.task_off.push_back((int)tr.entries.size());
       }
-      if (!tasks.empty() || !fuse) tr.level_off.push_back((int)tr.task_off.size() - 1);
+      if (!tasks.empty()) tr.level_off.push_back((int)tr.task_off.size() - 1);   // (prologues can take every edge of a level)
     }
     post_levels = nlev;
     finalize_traversal(p, tr, true);
   }
   // ---- preorder; tasks group by sender.  A sender may send as soon as it has received from its own parent (level =
   // its depth: as soon as possible) and no later than its height allows (level = tree height - its height: as late as
-  // possible); both take as many levels as the tree is deep.  Default: AS LATE AS POSSIBLE, the mirror image of the
+  // possible); both take as many levels as the tree is deep.  The planner sends AS LATE AS POSSIBLE, the mirror image of the
   // postorder -- the levels near the root are then as narrow as the postorder's last ones (they join the single-workgroup
   // tail launch), and the bulk of the messages sits in a few very wide levels at the leaf end, instead of a bell of
-  // mid-sized levels that each pay a full launch latency.  Chain fusion keeps the depth order (a fused chain starts where its
-  // first message may).
+  // mid-sized levels that each pay a full launch latency.
   {
-    const bool alap = fuse != 1;
-    auto height = [&](int cluster) {
-      auto it = hnode.find(cluster);
-      return it == hnode.end() ? 0 : it->second;
-    };
-    std::unordered_map<int, int> dnode;   // cluster -> level at which it sends
-    std::unordered_map<int, int> head;    // cluster -> the cluster whose task carries its messages
     std::vector<int> lvl(n);
-    std::vector<uint8_t> pro_edge(n, 0);  // fuse = 2: the message of edge i is the prologue of its receiver's own task
+    std::vector<uint8_t> pro_edge(n, 0);  // the message of edge i is the prologue of its receiver's own task
     int nlev = 0;
-    if (fuse == 2) {
+    if (prologues) {
       // Levels from the dependencies themselves (the postorder's heights do not carry over: there a prologue shortens the
       // path through F, here it moves X -> F from X's task into F's).  The task of a sender S waits for the task that
       // delivered into S -- its parent's -- or, where parent(S) -> S is S's prologue, for the one that delivered into
@@ -1058,24 +1037,13 @@ static void build_traversals(const Plan& p, Tree& t, int fuse) {
       }
       for (int i = 0; i < n; ++i) {
         const int S = t.pa[i];
-        lvl[i] = alap ? maxdepth - ph[S] : depth[S];
+        lvl[i] = maxdepth - ph[S];
       }
       // (levels of prologue edges are not used: they follow their receiver's task)
       nlev = maxdepth + 1;
     } else {
-      for (int i = 0; i < n; ++i) {
-        int dpt = 0;
-        auto it = dnode.find(t.pa[i]);
-        if (it != dnode.end()) dpt = it->second;
-        if (alap) dpt = post_levels - height(t.pa[i]);
-        lvl[i] = dpt;
-        const bool chained = unary(t.pa[i]);   // the child's task follows this message in the same wave
-        dnode[t.ch[i]] = chained ? dpt : dpt + 1;
-        auto ih = head.find(t.pa[i]);
-        const int hp = ih == head.end() ? t.pa[i] : ih->second;
-        head[t.ch[i]] = chained ? hp : t.ch[i];
-        nlev = std::max(nlev, dpt + 1);
-      }
+      for (int i = 0; i < n; ++i) lvl[i] = post_levels - hnode.at(t.pa[i]);   // (a sender has a height: it is some edge's parent)
+      nlev = post_levels;
     }
     std::vector<std::vector<int>> bylevel(nlev);
     for (int i = 0; i < n; ++i)
@@ -1087,12 +1055,10 @@ static void build_traversals(const Plan& p, Tree& t, int fuse) {
     for (int L = 0; L < nlev; ++L) {
       std::unordered_map<int, int> task_of_sender;
       std::vector<std::vector<int>> tasks;
-      for (int i : bylevel[L]) {   // increasing i: a chained child's edges come after the edge into it
-        auto ih = head.find(t.pa[i]);
-        const int key = ih == head.end() ? t.pa[i] : ih->second;
-        auto it = task_of_sender.find(key);
+      for (int i : bylevel[L]) {
+        auto it = task_of_sender.find(t.pa[i]);
         if (it == task_of_sender.end()) {
-          task_of_sender[key] = (int)tasks.size();
+          task_of_sender[t.pa[i]] = (int)tasks.size();
           tasks.push_back({i});
         } else {
           tasks[it->second].push_back(i);
@@ -1100,20 +1066,18 @@ static void build_traversals(const Plan& p, Tree& t, int fuse) {
       }
       for (auto& tk : tasks) {
         int prev_msg = -1;
-        if (fuse == 2) {
-          // the prologue of this sender's task: the message its parent sends into it
-          auto ip = parent_edge.find(t.pa[tk[0]]);
-          if (ip != parent_edge.end() && pro_edge[ip->second]) {
-            const int i = ip->second;
-            Entry e{};
-            e.msg = msg_to(i, t.ch[i]);
-            e.edge = i;
-            e.seq = n + i;
-            e.reuse = 0;
-            e.pro = 1;
-            tr.entries.push_back(e);
-            tr.max_mf = std::max(tr.max_mf, p.msgs[e.msg].mf);
-          }
+        // the prologue of this sender's task: the message its parent sends into it
+        auto ip = parent_edge.find(t.pa[tk[0]]);
+        if (ip != parent_edge.end() && pro_edge[ip->second]) {
+          const int i = ip->second;
+          Entry e{};
+          e.msg = msg_to(i, t.ch[i]);
+          e.edge = i;
+          e.seq = n + i;
+          e.reuse = 0;
+          e.pro = 1;
+          tr.entries.push_back(e);
+          tr.max_mf = std::max(tr.max_mf, p.msgs[e.msg].mf);
         }
         for (int i : tk) {
           Entry e{};
@@ -1135,7 +1099,7 @@ static void build_traversals(const Plan& p, Tree& t, int fuse) {
         }
         tr.task_off.push_back((int)tr.entries.size());
       }
-      if (!tasks.empty() || !fuse) tr.level_off.push_back((int)tr.task_off.size() - 1);
+      if (!tasks.empty()) tr.level_off.push_back((int)tr.task_off.size() - 1);   // (prologues can take every edge of a level)
     }
     finalize_traversal(p, tr, false);
   }
@@ -1192,16 +1156,15 @@ int plan_set_schedule(Plan& p, int32_t n_trees, const int32_t* tree_off, const i
       }
       T.sep[i] = it->second;
     }
-    build_traversals(p, T, 0);
-    // Prologue fusion (fuse = 2) where some cluster qualifies (every factor cluster of a tree's Bethe graph) AND the
+    build_traversals(p, T, false);
+    // Prologue fusion where some cluster qualifies (every factor cluster of a tree's Bethe graph) AND the
     // register-resident kernel runs the whole tree: on a mixed schedule (cfg5's Bethe graph: hybrid families beside
     // tree edges in every level) the levels go to the wave-per-task kernel whole, where a prologue is one more message
     // for the same wavefront -- half the levels at twice the time each (measured: 1.86 against 1.78 ms per iteration).
     // The univariate site batches run on the thread-per-site kernel and keep the plain levels.  (PGBP_TUNING no_prologue: A/B.)
     if (tree_all_fast(T)) {
-      const bool no_pro = !p.tune.prologues || p.tune.chain_fusion;
       const bool uni = p.max_dim <= 2 && p.n_sites >= 8;
-      if (!no_pro && !uni && p.fast_p > 0) {
+      if (p.tune.prologues && !uni && p.fast_p > 0) {
         std::unordered_map<int, int> nch, par, only;
         for (int i = 0; i < n; ++i) {
           if (++nch[T.pa[i]] == 1) only[T.pa[i]] = i;
@@ -1222,19 +1185,11 @@ int plan_set_schedule(Plan& p, int32_t n_trees, const int32_t* tree_off, const i
           }
         }
         if (any) {
-          build_traversals(p, T, 2);
-          if (!tree_all_fast(T)) build_traversals(p, T, 0);
+          build_traversals(p, T, true);
+          if (!tree_all_fast(T)) build_traversals(p, T, false);
         }
       }
     }
-    // Chain fusion is OPT-IN (PGBP_TUNING chain_fusion): measured on the cfg5 network (Bethe graph, 20 000 tips) it trades
-    // 398 launches for 152 but a fused level lasts as long as its longest chain (about 5 us per message inside a wave
-    // against about 10 us per launch): 4.8 ms per iteration against 3.9 ms.  It pays on path-like
-    // schedule trees (nodesubtree_clusterlist schedules).  Schedules that the register-resident kernel runs whole and
-    // the thread-per-site kernel of univariate batches always keep the plain levels.
-    const bool fuse_on = p.tune.chain_fusion;
-    const bool uni_batch = p.max_dim <= 2 && p.n_sites >= 8;
-    if (fuse_on && !uni_batch && !tree_all_fast(T)) build_traversals(p, T, 1);
     // the tail launch walks the postorder's last levels and the preorder's first ones as ONE sequence of passes
     T.tail = T.post.tentries;
     T.tail.insert(T.tail.end(), T.pre.tentries.begin(), T.pre.tentries.end());

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Child process of tests/test_plan_cpu.py::test_planner_under_address_and_undefined_sanitizers: drives the host-only
 planning API (pgbp_plan_* of include/pgbp.h) of an ASan + UBSan build of csrc/pgbp_plan.cpp over trees, Bethe graphs,
-network graphs (several schedule trees, node-subtree schedules, fused chains) and malformed inputs.  Any sanitizer
+network graphs (several schedule trees, node-subtree schedules) and malformed inputs.  Any sanitizer
 report aborts the process (halt_on_error)."""
 import ctypes as C
 import os

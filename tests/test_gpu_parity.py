@@ -1295,20 +1295,6 @@ def test_calibration_level3_joingraph_loopy_run_on_device(P, caplog, variant):
     assert np.allclose(mu6[:len(want)], want, rtol=1.5e-8, atol=0)
 
 
-def test_chain_fusion_opt_in_differential_fuzz(P):
-    """PGBP_TUNING=chain_fusion (opt-in, read when an engine is created; a child process keeps the variable out of this one): unary clusters of a schedule tree are
-    passed through inside one task of the generic kernel (pgbp_plan.cpp build_traversals).  The differential fuzz
-    against the plain-C sequential engine (beliefs 1e-8, flags, first failure) must hold unchanged."""
-    import os
-    import subprocess
-    import sys
-    here = os.path.dirname(os.path.abspath(__file__))
-    env = dict(os.environ, PGBP_TUNING="chain_fusion")
-    out = subprocess.run([sys.executable, os.path.join(here, "fuzz_gpu_vs_c_oracle.py"), "80", "77"], env=env,
-                         capture_output=True, text=True, timeout=600)
-    assert out.returncode == 0 and "80 cases ok" in out.stdout, (out.stdout[-1500:], out.stderr[-1500:])
-
-
 @pytest.mark.parametrize("env", [
     {"PGBP_TUNING": "no_tail"},
     {"PGBP_TUNING": "no_prologue"},

@@ -164,12 +164,23 @@ def test_plan_rejects_bad_input():
     lib, pl, code, keep = _plan(p2)
     assert code == L.ERR_INVALID and b"strictly increasing" in lib.pgbp_plan_last_error(pl)
     lib.pgbp_plan_destroy(pl)
-    # an unknown token of PGBP_TUNING is an error of the create call, not a silently ignored typo
-    os.environ["PGBP_TUNING"] = "no_tail,chunk_binz=3"
+    # an unknown token of PGBP_TUNING is an error of the create call, not a silently ignored typo; so are the keys that
+    # were removed, a value its key does not accept, a value on a flag and a missing value
+    removed = ["chain_fusion", "chunk_max_recs", "chunk_max_tasks", "chunk_uni_max", "chunk_depth", "chunk_depth_generic"]
+    bad = ["chunk_binz=3"] + removed + [k + "=2" for k in removed] + ["pair=on", "loop=", "no_tail=1", "chunk_bins=-2",
+                                                                    "small4_min=x", "pair=2"]
+    good = ["no_tail,chunk_bins=3", "loop=0,no_prologue", "small4_min=-1", "pair=1", " no_chunks , pair=0 "]
     try:
-        lib, pl, code, keep = _plan(S.cliquetree_of_tree(tr, 2))
-        assert code == L.ERR_INVALID and b"chunk_binz=3" in lib.pgbp_plan_last_error(pl)
-        lib.pgbp_plan_destroy(pl)
+        for tok in bad:
+            os.environ["PGBP_TUNING"] = "no_tail," + tok
+            lib, pl, code, keep = _plan(S.cliquetree_of_tree(tr, 2))
+            assert code == L.ERR_INVALID and tok.encode() in lib.pgbp_plan_last_error(pl), tok
+            lib.pgbp_plan_destroy(pl)
+        for tuning in good:
+            os.environ["PGBP_TUNING"] = tuning
+            lib, pl, code, keep = _plan(S.cliquetree_of_tree(tr, 2))
+            assert code == 0, (tuning, lib.pgbp_plan_last_error(pl))
+            lib.pgbp_plan_destroy(pl)
     finally:
         del os.environ["PGBP_TUNING"]
     # dimension above PGBP_MAX_DIM is refused, not silently mishandled
@@ -432,16 +443,16 @@ def test_nodesubtree_clusterlist_equals_the_oracle():
         assert (o[2], o[3]) == (q[2], q[3])
 
 
-# ----------------------------------------------------------------------------- fused chains (generic-kernel schedules)
+# ----------------------------------------------------------------------------- level schedules of generic-kernel graphs
 
 def _check_traversal(lo, to, em, ee, pa, ch, sepcl, d):
-    """Invariants of one traversal (dir d) that make the level-synchronous, chain-fused execution equal to the
+    """Invariants of one traversal (dir d) that make the level-synchronous execution equal to the
     reference's sequential loop: every edge once; the messages of a task are executed in order by one wave, tasks of a
     level run concurrently, levels in sequence.  (1) a message is sent only after every message into its sender (of this
     traversal) has been delivered: in an earlier level or earlier in the same task; (2) two tasks of one level touch
     disjoint beliefs, except that they may READ a common cluster nobody writes; (3) the messages a task delivers into one
     receiver are applied in the reference's order (postorder: decreasing edge index; siblings of different heights
-    arrive in different levels, as without fusion: sums then differ from the sequential loop in the last bits only)."""
+    arrive in different levels: sums then differ from the sequential loop in the last bits only)."""
     n = len(pa)
     assert sorted(ee.tolist()) == list(range(n))
     when = {}
@@ -476,28 +487,13 @@ def _check_traversal(lo, to, em, ee, pa, ch, sepcl, d):
                 assert sorted(same, key=lambda i: when[i]) == sorted(same, reverse=True), rcv
 
 
-def test_fused_chain_schedule_invariants_subprocess():
-    """Chain fusion is opt-in through PGBP_TUNING=chain_fusion (read when a plan is built): the checks run in a child process."""
-    import subprocess
-    import sys
-    env = dict(os.environ, PGBP_TUNING="chain_fusion")
-    code = ("import sys; sys.path.insert(0, %r); sys.path.insert(0, %r); import test_plan_cpu as T\n"
-            "for g, s in [('bethe_tree', 1), ('bethe_net', 2), ('join_net', 3), ('bethe_net', 4), ('nodesubtrees', 5), ('path', 6)]:\n"
-            "    T._fused_chain_schedule_invariants(g, s, True)\n"
-            "print('fused ok')" % (ROOT, os.path.join(ROOT, "tests")))
-    out = subprocess.run([sys.executable, "-c", code], env=env, capture_output=True, text=True, timeout=600)
-    assert out.returncode == 0 and "fused ok" in out.stdout, (out.stdout[-2000:], out.stderr[-2000:])
-
-
 @pytest.mark.parametrize("graph,seed", [("bethe_tree", 1), ("bethe_net", 2), ("join_net", 3), ("nodesubtrees", 5), ("path", 6)])
 def test_generic_schedule_invariants(graph, seed):
-    """The same invariants on the default (unfused) level schedules of generic-kernel graphs."""
-    _fused_chain_schedule_invariants(graph, seed, False)
+    """The invariants of _check_traversal on the level schedules (pgbp_plan.cpp build_traversals) of generic-kernel graphs."""
+    _generic_schedule_invariants(graph, seed)
 
 
-def _fused_chain_schedule_invariants(graph, seed, fused):
-    """Chain fusion (pgbp_plan.cpp build_traversals): unary clusters of the schedule tree are passed through inside one
-    task; Bethe graphs lose about half of their levels."""
+def _generic_schedule_invariants(graph, seed):
     import pgbp_amd as P
     rng = np.random.default_rng(seed)
     if graph == "bethe_tree":
@@ -516,7 +512,7 @@ def _fused_chain_schedule_invariants(graph, seed, fused):
             sched = [x for x in (P.nodesubtree_clusterlist(cn, ed, sn, v) for v in range(1, net.nnodes + 1)) if x[0]]
         elif graph == "path":
             full = P.spanningtrees_clusterlist(len(cn), ed, cn, net.is_leaf)[0]
-            # one root-to-leaf path of the spanning tree: every cluster unary -> one level per direction
+            # one root-to-leaf path of the spanning tree: every cluster unary -> one level per message
             pa_l, ch_l = list(full[2]), list(full[3])
             node = ch_l[-1]
             path = []
@@ -536,25 +532,19 @@ def _fused_chain_schedule_invariants(graph, seed, fused):
     assert _set_sched(lib, pl, sched) == 0, lib.pgbp_plan_last_error(pl)
     sepcl = np.asarray(sepcl).reshape(-1, 2)
     for t, (pa, ch) in enumerate(sched):
-        depth = {int(pa[0]): 0} if len(pa) else {}
-        for a, c in zip(pa, ch):
-            depth[int(c)] = depth[int(a)] + 1
         for d in (0, 1):
             lo, to, em, ee, er = _traversal(lib, pl, t, d)
             _check_traversal(lo, to, em, ee, pa, ch, sepcl, d)
             nlev = len(lo) - 1
-            if fused and graph in ("bethe_tree", "bethe_net") and len(pa) > 20:
-                assert nlev <= 0.65 * max(depth.values())
             if graph == "path":
-                assert (nlev == 1 and to[1] - to[0] == len(pa)) if fused else nlev == len(pa)
+                assert nlev == len(pa)
     lib.pgbp_plan_destroy(pl)
 
 
 def test_planner_under_address_and_undefined_sanitizers(tmp_path):
-    """csrc/pgbp_plan.cpp (layout, message table, level schedules, chain fusion: host-only code) built with
+    """csrc/pgbp_plan.cpp (layout, message table, level schedules: host-only code) built with
     -fsanitize=address,undefined and driven through the pgbp_plan_* API over trees, Bethe and join graphs of networks,
-    node-subtree schedules and malformed inputs, once with and once without chain fusion.  GPU sanitizers are not
-    available on the pool; this is the host half."""
+    node-subtree schedules and malformed inputs.  GPU sanitizers are not available on the pool; this is the host half."""
     import subprocess
     import sys
     so = str(tmp_path / "libpgbp_plan_asan.so")
@@ -562,15 +552,12 @@ def test_planner_under_address_and_undefined_sanitizers(tmp_path):
     subprocess.check_call(["g++", "-O1", "-g", "-std=c++17", "-fPIC", "-fsanitize=address,undefined",
                            "-fno-omit-frame-pointer", "-fno-sanitize-recover=undefined", "-shared", "-o", so, src])
     asan = subprocess.check_output(["gcc", "-print-file-name=libasan.so"], text=True).strip()
-    for fuse in (False, True):
-        env = dict(os.environ, LD_PRELOAD=asan, ASAN_OPTIONS="detect_leaks=0:halt_on_error=1",
-                   UBSAN_OPTIONS="halt_on_error=1:print_stacktrace=1")
-        env.pop("PGBP_TUNING", None)
-        if fuse:
-            env["PGBP_TUNING"] = "chain_fusion"
-        out = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "sanitize_plan.py"), so], env=env,
-                             capture_output=True, text=True, timeout=600)
-        assert out.returncode == 0 and "sanitized planner ok" in out.stdout, (out.stdout[-1500:], out.stderr[-3000:])
+    env = dict(os.environ, LD_PRELOAD=asan, ASAN_OPTIONS="detect_leaks=0:halt_on_error=1",
+               UBSAN_OPTIONS="halt_on_error=1:print_stacktrace=1")
+    env.pop("PGBP_TUNING", None)
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "sanitize_plan.py"), so], env=env,
+                         capture_output=True, text=True, timeout=600)
+    assert out.returncode == 0 and "sanitized planner ok" in out.stdout, (out.stdout[-1500:], out.stderr[-3000:])
 
 
 def test_cliquetree_on_arrays_is_a_clique_tree_with_the_oracles_cliques():
@@ -1238,8 +1225,7 @@ def test_message_records_of_the_wave_per_task_kernels(ntips, p, kind, graph):
                 seen_generic += 1
                 msgs = [int(m) for m in em[to[t]:to[t + 1]]]
                 if d == 1 and int(dims.max()) > 2:
-                    senders = {int(sc[m // 2][1 - m % 2]) for m in msgs}
-                    assert len(msgs) == 1 or len(senders) > 1, "a generic preorder task = one message (unless chain-fused)"
+                    assert len(msgs) == 1, "a generic preorder task = one message"
                 q, chain = int(tf[t]), []
                 while q >= 0:
                     assert not used[q]
@@ -1304,7 +1290,7 @@ def test_residual_norm_thresholds_are_exact():
 
 @pytest.mark.parametrize("ntips,p", [(300, 8), (57, 5), (200, 16)])
 def test_bethe_graph_of_a_tree_is_scheduled_with_prologues(ntips, p):
-    """Prologue fusion (build_traversals, fuse = 2): in the Bethe graph of a tree every factor cluster F = {v, pa(v)} has
+    """Prologue fusion (build_traversals with prologues): in the Bethe graph of a tree every factor cluster F = {v, pa(v)} has
     one child and one parent in the schedule tree, and the one message it receives in a traversal (from a variable
     cluster: nothing integrated) lands on the block its own message integrates out.  That message is planned as the
     PROLOGUE of F's own -- the entry in front of it in the same task (entry_reuse = 2), the 7th word of its record -- in
