@@ -273,6 +273,45 @@ int  pgbp_calibrate(pgbp_engine* e, int32_t niter, const pgbp_opts* opts, pgbp_r
  * every site: mu[n_sites * m] (may be NULL), norm[n_sites], info[n_sites] (0 ok, >0 not PD, may be NULL).
  * An all-zero belief gives mu = Inf, norm = g (src/beliefupdates.jl:189-191). */
 int  pgbp_integrate(pgbp_engine* e, int32_t belief, double* mu, double* norm, int32_t* info);
+/* integratebelief! (src/beliefupdates.jl:168-200) for MANY beliefs at once, with the covariance: one launch per dimension
+ * class over a grid of (belief, site) -- at most 16 variables: four beliefs per wavefront, one per row of 16 lanes, in
+ * registers; 17 .. 64: one wavefront per belief, the working matrix in LDS; 65 .. 128: a workgroup of 256 threads, the
+ * working matrix in up to 133 KB of LDS, the inverse formed in place from the elimination's factor (csrc/pgbp_moments.hip).
+ * beliefs[n]: belief indices (NULL: all clusters, n ignored); sites [site_begin, site_end).
+ * Per (site, listed belief) of dimension m, back to back in list order, site-major:
+ *   out    : Sigma = J^-1 (m*m, column-major, symmetric, both triangles written), then mu (m), then norm (1)
+ *            -- the layout of a belief record (pgbp_get_belief), so pgbp_packed_beliefs_size gives the size;
+ *   with want_cov == 0 only mu (m) then norm (1) are written.
+ * info[(site - site_begin) * n + i] (may be NULL): 0, or the PosDefException.info of that belief (its outputs are NaN).
+ * An all-zero belief gives mu = Inf, norm = g (src/beliefupdates.jl:189-191), info 0; the reference defines no
+ * covariance there, so Sigma is all NaN.  A belief of dimension 0 gives norm = g.
+ * mu and norm are bit-identical to pgbp_integrate's in every class (the same operations on every entry, in the same
+ * order), on the plain and on the packed (BS16) layout.  A univariate batch in the site-minor layout is first converted
+ * to the plain one (as pgbp_free_energy does); pgbp_integrate has a closed form of its own there (dimension <= 2), so
+ * on such an engine the two agree to rounding (1e-12 relative), not bit for bit.
+ * A listed belief of more than 128 variables, or an index out of range, fails with PGBP_ERR_INVALID (the message names
+ * the belief) before anything is launched.  Read-only on the beliefs; no atomics: a second call returns the same bytes.
+ * The outputs and the info words come back as two copies behind one stream synchronisation (the call's scratch buffers are
+ * allocated and freed per call, which synchronises the device as well).
+ * pgbp_moments_size: doubles per site of `out` (-1: a bad list). */
+int pgbp_moments(pgbp_engine* e, int32_t n, const int32_t* beliefs, int32_t site_begin, int32_t site_end,
+                 int32_t want_cov, double* out, int32_t* info);
+int64_t pgbp_moments_size(pgbp_engine* e, int32_t n, const int32_t* beliefs, int32_t want_cov);
+/* The loop of calibrate_exact_cliquetree! (src/calibration.jl:442-499) over the families given to pgbp_lg_setup, on the
+ * CURRENT beliefs (calibrated under R = I and an improper root prior), for sites [site_begin, site_end):
+ * num[(site - site_begin) * p*p ...] (column-major p x p) and den[site - site_begin]; R_hat = num / den.
+ * One workgroup per (family, site) computes the moments of the family's cluster in LDS (the solve of pgbp_moments; only the
+ * family's diffExp, t = sum gamma^2 length and 1 - diffVar / t leave it, into a per-family slot), a second pass adds the
+ * slots in family order by a fixed tree: no atomics on doubles, the same bytes on every call.  Line by line the reference:
+ * a family with t == 0, a root-prior family, a tip whose parent (an internal child that itself) has nothing in scope and a
+ * tip without data are skipped; a tip's denominator term reads the cluster's FIRST variable (vv[1, 1], :478), which must
+ * be its parent's first trait (checked); an internal family reads J^-1 at the first trait of the child and of each parent.
+ * Fails before any launch with PGBP_ERR_STATE without a family table, with PGBP_ERR_INVALID for a family whose parent is
+ * the fixed root (the sweep is defined on the improper-root engine), for partial scopes ("some leaf must have partial
+ * data: cluster ... has partial traits in scope", :416-421) and for a cluster of more than 128 variables.
+ * info[site - site_begin] (may be NULL) as pgbp_free_energy: 0, or 1-based index of the first cluster that is not positive
+ * definite (num and den of that site are NaN). */
+int pgbp_bm_exact_stats(pgbp_engine* e, int32_t site_begin, int32_t site_end, double* num, double* den, int32_t* info);
 
 /* ---- scores (second "next" row: SURVEY.md section 8(f)-2) -------------------------------------- */
 /* free_energy(beliefs) (src/score.jl:162-182) for every site: out3[3*site + {0,1,2}] = (average energy,

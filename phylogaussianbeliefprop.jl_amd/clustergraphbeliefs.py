@@ -415,6 +415,48 @@ class ClusterGraphBelief:
             self._objs[j].mu = mu[0].copy()
         return mu[self.site].copy(), float(norm[self.site])
 
+    def moments_(self, beliefs=None, cov=True, all_sites=False):
+        """Posterior moments of many beliefs in ONE device call (pgbp_moments): per listed belief (beliefs=None: every
+        cluster) the tuple (mu, Sigma, norm) with Sigma = J^-1 (None when cov is false); mu and norm are
+        integratebelief!'s (src/beliefupdates.jl:168-200), bit for bit those of integratebelief_.  all_sites: the arrays
+        gain a leading site axis and a fourth element, info [n_sites] (0, or PosDefException.info: that site's entries
+        are NaN); otherwise the current site's values, and a belief of the current site that is not positive definite
+        raises integratebelief_'s LinAlgError."""
+        if beliefs is None:
+            lst = np.arange(self.nclusters, dtype=np.int32)
+            ptr, n = None, 0
+        else:
+            lst = np.ascontiguousarray(beliefs, dtype=np.int32).reshape(-1)
+            keep = lst if lst.size else np.zeros(1, dtype=np.int32)
+            ptr, n = L.i32p(keep), int(lst.size)
+        per = int(self._lib.pgbp_moments_size(self._eng, n, ptr, int(bool(cov))))
+        if per < 0:
+            # (the call itself reports which index is bad / which belief is too large)
+            _check(self._lib.pgbp_moments(self._eng, n, ptr, 0, 0, int(bool(cov)), None, None), self._eng)
+            raise L.PgbpError(L.ERR_INVALID, "pgbp_moments_size failed")
+        s0, s1 = (0, self.n_sites) if all_sites else (self.site, self.site + 1)
+        out = np.zeros((s1 - s0, max(1, per)))
+        info = np.zeros((s1 - s0, max(1, lst.size)), dtype=np.int32)
+        _check(self._lib.pgbp_moments(self._eng, n, ptr, s0, s1, int(bool(cov)), L.f64p(out), L.i32p(info)), self._eng)
+        res, at = [], 0
+        for i, b in enumerate(lst):
+            m = int(self._dims[b])
+            Sig = None
+            if cov:
+                Sig = out[:, at: at + m * m].reshape(-1, m, m).transpose(0, 2, 1)   # (column-major records)
+                at += m * m
+            mu = out[:, at: at + m]
+            norm = out[:, at + m]
+            at += m + 1
+            if all_sites:
+                res.append((mu.copy(), None if Sig is None else Sig.copy(), norm.copy(), info[:, i].copy()))
+                continue
+            if info[0, i] != 0:
+                raise np.linalg.LinAlgError(
+                    f"PosDefException: matrix is not positive definite; Cholesky factorization failed (info={info[0, i]}).")
+            res.append((mu[0].copy(), None if Sig is None else Sig[0].copy(), float(norm[0])))
+        return res
+
     def default_sepset1(self):
         """default_sepset1 (src/clustergraphbeliefs.jl:197-202)."""
         for j in range(self.nclusters, self.nbeliefs):

@@ -2110,4 +2110,27 @@ int engine_pack_records_device(pgbp_engine* e, int32_t site, int32_t n, const in
 int engine_fail(pgbp_engine* e, int code, const std::string& msg) { return e->fail(code, msg); }
 int engine_device(const pgbp_engine* e) { return e->plan.device; }
 int engine_n_sites(const pgbp_engine* e) { return e->plan.n_sites; }
+// pgbp_moments.hip: the belief state in the plain site-major layout (a univariate batch leaves its site-minor buffers first)
+int engine_view(pgbp_engine* e, EngineView* v) {
+  DeviceScope device_scope(e);
+  if (e->layout_sm) {
+    const int rc = ensure_site_minor(e, false);
+    if (rc) return rc;
+  }
+  *v = engine_peek(e);
+  return PGBP_OK;
+}
+EngineView engine_peek(pgbp_engine* e) {
+  EngineView v;
+  v.plan = &e->plan;
+  v.st = e->st;
+  v.pool = e->d_pool;
+  v.boff = e->d_boff;
+  v.bdim = e->d_bdim;
+  v.bs16 = e->layout_bs16 ? 1 : 0;
+  v.lg = &e->lg;
+  v.lg_ready = e->lg_ready ? 1 : 0;
+  return v;
+}
+const Plan* engine_plan(const pgbp_engine* e) { return &e->plan; }
 }  // namespace pgbp

@@ -275,5 +275,19 @@ int engine_pack_records_device(pgbp_engine* e, int32_t site, int32_t n, const in
 int engine_fail(pgbp_engine* e, int code, const std::string& msg);
 int engine_device(const pgbp_engine* e);
 int engine_n_sites(const pgbp_engine* e);
+// what pgbp_moments.hip reads of an engine: its plan, stream and the belief pool in the plain (site-major) layout
+struct EngineView {
+  const Plan* plan;
+  hipStream_t st;
+  const double* pool;     // [n_sites][plan->pool_stride()]
+  const int64_t* boff;    // device copies of Plan::boff / Plan::dims
+  const int32_t* bdim;
+  int bs16;               // beliefs of dimension P / 2P are in the packed layout (pgbp_bs16.hpp)
+  const LgStatic* lg;     // the family table of pgbp_lg_setup (device pointers); lg_ready == 0: none
+  int lg_ready;
+};
+int engine_view(pgbp_engine* e, EngineView* v);
+EngineView engine_peek(pgbp_engine* e);          // the same words without touching the layout, the device or the last error
+const Plan* engine_plan(const pgbp_engine* e);
 
 }  // namespace pgbp

@@ -201,6 +201,48 @@ function PGBP.integratebelief!(o::DeviceClusterGraphBelief, j::Integer)
     return (mu[1:m], norm[])
 end
 
+"""
+    moments!(obj, beliefs = 1:nclusters; cov = true) -> Vector of (mu, Sigma, norm)
+
+Posterior mean, covariance `inv(J)` and normalisation constant of many beliefs in one device call (pgbp_moments):
+`integratebelief!` of every listed belief, bit for bit, plus the covariance the reference gets from `inv(b.J)`
+(src/calibration.jl:464).  A belief that is not positive definite throws its PosDefException.
+"""
+function moments!(o::DeviceClusterGraphBelief, beliefs::AbstractVector{<:Integer} = 1:PGBP.nclusters(o.cgb); cov::Bool = true)
+    lst = Int32.(beliefs .- 1); n = Int32(length(lst)); wc = Int32(cov)
+    per = @ccall LIB.pgbp_moments_size(o.handle::Ptr{Cvoid}, n::Int32, lst::Ptr{Int32}, wc::Int32)::Int64
+    per >= 0 || error("pgbp_moments: bad belief list (an index out of range, or a belief of more than 128 variables)")
+    out = zeros(max(per, 1)); info = zeros(Int32, max(n, 1))
+    check(o.handle, @ccall LIB.pgbp_moments(o.handle::Ptr{Cvoid}, n::Int32, lst::Ptr{Int32}, Int32(0)::Int32, Int32(1)::Int32, wc::Int32, out::Ptr{Float64}, info::Ptr{Int32})::Cint)
+    res = Vector{Tuple{Vector{Float64},Union{Nothing,Matrix{Float64}},Float64}}(); at = 0
+    for (i, j) in enumerate(beliefs)
+        info[i] == 0 || throw(PGBP.LA.PosDefException(info[i]))
+        m = length(o.cgb.belief[j].h)
+        S = cov ? reshape(out[at+1:at+m*m], m, m) : nothing
+        at += cov ? m * m : 0
+        push!(res, (out[at+1:at+m], S, out[at+m+1])); at += m + 1
+    end
+    return res
+end
+
+"""
+    calibrate_exact_cliquetree!(obj, spt, rootcluster, rootpos, p) -> (R_hat, mu_hat)
+
+The sequence of `calibrate_exact_cliquetree!` (src/calibration.jl:404-517) on the device, for an engine `obj` built under the
+improper root prior whose factors were assigned with R = I, mu = 0 (pgbp_lg_assignfactors): calibrate, the root's posterior
+mean from `moments!`, the family sweep (pgbp_bm_exact_stats), `R_hat = num / den`.  The score of the returned fixed-root
+model is one `pgbp_lg_assignfactors` + log-likelihood evaluation on a second engine built with a fixed root (the reference
+re-allocates the root's scope in place, :507-511).
+"""
+function calibrate_exact_cliquetree!(o::DeviceClusterGraphBelief, spt, rootcluster::Integer, rootpos::Integer, p::Integer)
+    PGBP.calibrate!(o, [spt])
+    mu, _, _ = moments!(o, [rootcluster]; cov = false)[1]
+    num = zeros(p * p); den = Ref(0.0); info = Ref(Int32(0))
+    check(o.handle, @ccall LIB.pgbp_bm_exact_stats(o.handle::Ptr{Cvoid}, Int32(0)::Int32, Int32(1)::Int32, num::Ptr{Float64}, den::Ref{Float64}, info::Ref{Int32})::Cint)
+    info[] == 0 || throw(PGBP.LA.PosDefException(info[]))
+    return (reshape(num, p, p) ./ den[], mu[rootpos:rootpos+p-1])
+end
+
 "the reference's error line for a failed message (src/beliefupdates.jl:69-76): belief metadata + integrated indices"
 function report_failure(o::DeviceClusterGraphBelief, spt, res::Result, verbose::Bool)
     i = res.fail_edge + 1
