@@ -312,6 +312,40 @@ int64_t pgbp_moments_size(pgbp_engine* e, int32_t n, const int32_t* beliefs, int
  * info[site - site_begin] (may be NULL) as pgbp_free_energy: 0, or 1-based index of the first cluster that is not positive
  * definite (num and den of that site are NaN). */
 int pgbp_bm_exact_stats(pgbp_engine* e, int32_t site_begin, int32_t site_end, double* num, double* den, int32_t* info);
+/* The exact gradient of the log-likelihood with respect to every model parameter, from the CURRENT beliefs, for sites
+ * [site_begin, site_end): Fisher's identity d loglik / d theta = sum_f E[d log phi_f / d theta | data] over the families
+ * given to pgbp_lg_setup, the expectation under the belief of the family's cluster, with the parameters the engine kept from
+ * the last pgbp_lg_assignfactors (shared or per site: a per-site engine returns each site's own gradient).
+ * THE RESULT IS THE EXACT GRADIENT ONLY WHEN THE BELIEFS ARE CALIBRATED (postorder AND preorder) ON A CLIQUE TREE UNDER THE
+ * PARAMETERS OF THE LAST pgbp_lg_assignfactors; the call does not verify that.  On a loopy cluster graph the same sweep on
+ * the beliefs of a CONVERGED calibration is the gradient of the factored energy (the Bethe free energy is stationary in the
+ * beliefs at a fixed point); before convergence it is neither.
+ * Per family (notation of pgbp_lg_params: residual r = x_child - sum_k qc_k x_k - w, variance V = sum_k vc_k R[colour_k]
+ * restricted to the kept components O = child_mask, j = V_OO^-1; blocks in scope random with the cluster's J^-1 h and J^-1,
+ * a tip's data row and the fixed root's mean constants): e = E[r], M = Cov(r) + e e', G_V = (j M j - j) / 2, g_w = j e,
+ * g_qk = E[r' j x_k].  Outputs, site-major:
+ *   dR     [sites][n_rates][p*p] column-major, symmetric: dR[c] = sum_f sum_{k: colour_k = c} vc_k G_V(f) (a root-prior
+ *          family: G_V itself), so that d loglik = tr(dR[c] dR_c): entry (a, b) is the derivative along (E_ab + E_ba) / 2;
+ *   dmu    [sites][p]: j e of the root-prior family plus qc_k j e of the families whose parent k is the fixed root (zero
+ *          for an improper root);
+ *   dtheta [sites][p], dalpha [sites] (OU; NULL allowed for a BM engine, zeros are written when given there):
+ *          dtheta = sum wc_k g_w,  dalpha = sum_k (dvc_k/dalpha tr(G_V R[colour_k]) + dwc_k/dalpha theta' g_w +
+ *          dqc_k/dalpha g_qk), R the stationary variance.
+ * Families the factor fill skips (child_mask == 0) contribute nothing.
+ * Device (csrc/pgbp_grad.hip): one workgroup per (family, site) solves the family's cluster in LDS (the solve of
+ * pgbp_moments) and writes a slot of p*p + p + 3 + n_rates doubles; the slots are added in a fixed order (256 consecutive
+ * families per workgroup, then a fixed tree): no atomics on doubles, two calls return the same bytes.  The slots of a chunk
+ * of sites at a time (256 MB at most).  Read-only on the beliefs; every layout (a site-minor univariate batch is converted
+ * to the plain layout first, as pgbp_bm_exact_stats does).
+ * Fails before any launch with PGBP_ERR_STATE without a family table or before the first pgbp_lg_assignfactors, with
+ * PGBP_ERR_INVALID for a site range out of bounds, for dalpha / dtheta NULL on an OU engine, for a family whose cluster has
+ * more than 128 variables, and when that cluster's working matrix plus the p x p scratch exceed the 160 KB of LDS (p > 16
+ * with clusters near 128 variables).  Fixed, random and improper roots, hybrid families, several colours and scope masks
+ * are all accepted.
+ * info[site - site_begin] (may be NULL): 0, or the 1-based index of the first cluster that is not positive definite (or
+ * whose family variance is not): that site's outputs are NaN. */
+int pgbp_lg_gradient(pgbp_engine* e, int32_t site_begin, int32_t site_end, double* dR, double* dmu, double* dalpha,
+                     double* dtheta, int32_t* info);
 
 /* ---- scores (second "next" row: SURVEY.md section 8(f)-2) -------------------------------------- */
 /* free_energy(beliefs) (src/score.jl:162-182) for every site: out3[3*site + {0,1,2}] = (average energy,
@@ -427,6 +461,12 @@ int  pgbp_enqueue_calibrate(pgbp_engine* e, int32_t reps, int32_t reset_each, co
  * may still hold an earlier evaluation's values where the engine skipped their reset.  Other sites are unaffected.) */
 int  pgbp_enqueue_loglik(pgbp_engine* e, int32_t reps, const pgbp_opts* opts);
 int  pgbp_fetch_loglik(pgbp_engine* e, double* norm, int32_t* info);
+/* Enqueue integratebelief! of one belief on the CURRENT beliefs (nothing is reset, no message is passed): its per-site
+ * constants stay on the device until pgbp_fetch_loglik, like those of pgbp_enqueue_loglik.  No host synchronisation. */
+int  pgbp_enqueue_integrate(pgbp_engine* e, int32_t belief);
+/* The layout the belief pool is in right now: bit 0 = packed (BS16) records, bit 1 = site-minor univariate batch; 0 = plain.
+ * Every call converts as it needs; this only reports (tests of layout independence). */
+int32_t pgbp_layout(const pgbp_engine* e);
 /* The whole body of score(theta) (src/calibration.jl:195-221) on the device: pgbp_bm_tree_assignfactors with
  * the parameters uploaded by the LAST pgbp_bm_tree_assignfactors call, postorder of tree 0, root integrate. */
 int  pgbp_enqueue_loglik_bm(pgbp_engine* e, int32_t reps, const pgbp_opts* opts);

@@ -121,6 +121,7 @@ SYMBOLS = {
     "pgbp_moments": (C.c_int, [_P, C.c_int32, _I32P, C.c_int32, C.c_int32, C.c_int32, _F64P, _I32P]),
     "pgbp_moments_size": (C.c_int64, [_P, C.c_int32, _I32P, C.c_int32]),
     "pgbp_bm_exact_stats": (C.c_int, [_P, C.c_int32, C.c_int32, _F64P, _F64P, _I32P]),
+    "pgbp_lg_gradient": (C.c_int, [_P, C.c_int32, C.c_int32, _F64P, _F64P, _F64P, _F64P, _I32P]),
     "pgbp_free_energy": (C.c_int, [_P, _F64P, _I32P]),
     "pgbp_bm_tree_setup": (C.c_int, [_P, C.POINTER(BmTree)]),
     "pgbp_bm_tree_assignfactors": (C.c_int, [_P, _F64P, _F64P, _F64P, C.c_int32]),
@@ -133,6 +134,8 @@ SYMBOLS = {
     "pgbp_fetch_kernel_time": (C.c_int, [_P, C.POINTER(C.c_float), _I32P]),
     "pgbp_enqueue_loglik": (C.c_int, [_P, C.c_int32, C.POINTER(Opts)]),
     "pgbp_fetch_loglik": (C.c_int, [_P, _F64P, _I32P]),
+    "pgbp_enqueue_integrate": (C.c_int, [_P, C.c_int32]),
+    "pgbp_layout": (C.c_int32, [_P]),
     "pgbp_sync": (C.c_int, [_P]),
     "pgbp_time_enqueued": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, C.POINTER(Opts), C.POINTER(C.c_float)]),
     "pgbp_time_message_kernels": (C.c_int, [_P, C.c_int32, C.POINTER(Opts), C.POINTER(C.c_float), _I32P]),

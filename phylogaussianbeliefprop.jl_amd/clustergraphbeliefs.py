@@ -571,6 +571,59 @@ class ClusterGraphBelief:
         _check(self._lib.pgbp_fetch_loglik(self._eng, L.f64p(norm), L.i32p(info)), self._eng)
         return norm, info
 
+    def gradient_lg(self, all_sites=False):
+        """pgbp_lg_gradient on the current beliefs: the gradient of the log-likelihood with respect to every parameter
+        of the last assignfactors_lg_, by Fisher's identity -- one sweep over the node families.  EXACT ONLY when the
+        beliefs are calibrated (postorder and preorder) on a clique tree under those parameters (not verified); on a
+        loopy cluster graph, at a converged calibration, it is the gradient of the factored energy.
+        Returns a dict: dR [n_rates, p, p] (symmetric; d loglik = sum_c tr(dR[c] dR_c)), dmu [p], dalpha (scalar) and
+        dtheta [p] (zero for a Brownian motion), info; with a leading site axis when all_sites.  A site whose info is
+        not 0 (1-based index of a cluster that is not positive definite) holds NaN; for the current site that raises."""
+        p, nr = self._lg_p, self._lg_nrates
+        s0, s1 = (0, self.n_sites) if all_sites else (self.site, self.site + 1)
+        n = s1 - s0
+        dR = np.zeros((n, nr, p, p))
+        dmu = np.zeros((n, p))
+        dalpha = np.zeros(n)
+        dtheta = np.zeros((n, p))
+        info = np.zeros(n, dtype=np.int32)
+        _check(self._lib.pgbp_lg_gradient(self._eng, s0, s1, L.f64p(dR), L.f64p(dmu), L.f64p(dalpha), L.f64p(dtheta),
+                                          L.i32p(info)), self._eng)
+        dR = dR.transpose(0, 1, 3, 2)   # (column-major blocks; symmetric)
+        d = dict(dR=dR, dmu=dmu, dalpha=dalpha, dtheta=dtheta, info=info)
+        return d if all_sites else self._gradient_of_site(d, 0)
+
+    @staticmethod
+    def _gradient_of_site(d, s):
+        if d["info"][s]:
+            raise np.linalg.LinAlgError(f"PosDefException: belief {d['info'][s] - 1} is not positive definite")
+        return dict(dR=d["dR"][s].copy(), dmu=d["dmu"][s].copy(), dalpha=float(d["dalpha"][s]), dtheta=d["dtheta"][s].copy(),
+                    info=0)
+
+    def loglik_and_gradient_lg(self, schedule_tree, all_sites=False):
+        """Log-likelihood and its exact gradient under the parameters of the last assignfactors_lg_ on a clique tree:
+        beliefs reset from the factors that call filled -> one calibrate (postorder + preorder of `schedule_tree`) ->
+        integratebelief! at the tree's root cluster -> the family sweep (gradient_lg).  The reset, the traversals and the
+        root integration are enqueued without host synchronisation; the sweep's fetch is the one wait (the root's constants
+        are then copied from a stream that is already idle).  Like loglik_lg, the host mirrors of the beliefs are not
+        refreshed.  Returns (loglik, gradient dict): the current site's values, or arrays over the sites (info of a failed
+        site is not 0 and its values are NaN) when all_sites."""
+        self._ensure_schedule([schedule_tree])
+        o = self._opts()
+        pa = np.asarray(schedule_tree[-2]).reshape(-1)
+        root = int(pa[0]) if pa.size else 0
+        _check(self._lib.pgbp_enqueue_calibrate(self._eng, 1, 1, C.byref(o)), self._eng)
+        _check(self._lib.pgbp_enqueue_integrate(self._eng, root), self._eng)
+        grad = self.gradient_lg(all_sites=True)
+        norm = np.zeros(self.n_sites)
+        info = np.zeros(self.n_sites, dtype=np.int32)
+        _check(self._lib.pgbp_fetch_loglik(self._eng, L.f64p(norm), L.i32p(info)), self._eng)
+        grad["info"] = np.where(grad["info"] != 0, grad["info"], info)
+        norm = np.where(grad["info"] != 0, np.nan, norm)
+        if all_sites:
+            return norm, grad
+        return float(norm[self.site]), self._gradient_of_site(grad, self.site)
+
     def traffic_model(self):
         b = C.c_double()
         n = C.c_int64()

@@ -1979,6 +1979,16 @@ int pgbp_enqueue_loglik(pgbp_engine* e, int32_t reps, const pgbp_opts* opts) {
   return e->take_enqueue_rc();
 }
 
+int32_t pgbp_layout(const pgbp_engine* e) { return e ? (e->layout_bs16 ? 1 : 0) | (e->layout_sm ? 2 : 0) : -1; }
+
+int pgbp_enqueue_integrate(pgbp_engine* e, int32_t belief) {
+  DeviceScope device_scope(e);
+  if (!e) return PGBP_ERR_INVALID;
+  if (belief < 0 || belief >= e->plan.n_beliefs()) return e->fail(PGBP_ERR_INVALID, "belief index out of range");
+  integrate_async(e, belief, nullptr);
+  return e->take_enqueue_rc();
+}
+
 int pgbp_fetch_loglik(pgbp_engine* e, double* norm, int32_t* info) {
   DeviceScope device_scope(e);
   if (!e || !norm) return PGBP_ERR_INVALID;
@@ -2133,4 +2143,9 @@ EngineView engine_peek(pgbp_engine* e) {
   return v;
 }
 const Plan* engine_plan(const pgbp_engine* e) { return &e->plan; }
+bool engine_lg_params(const pgbp_engine* e, LgParams* out) {
+  if (!e->lg_ready || !e->lg_have_params) return false;
+  *out = e->lgp;
+  return true;
+}
 }  // namespace pgbp

@@ -1,0 +1,495 @@
+// Exact gradient of the log-likelihood from calibrated beliefs (pgbp_lg_gradient of include/pgbp.h).
+//
+// Fisher's identity: d loglik / d theta = sum_f E[ d log phi_f / d theta | data ], a sum over the node families given to
+// pgbp_lg_setup of an expectation under the posterior of the family's variables -- the calibrated belief of the family's
+// cluster.  Notation of pgbp_lgfill.hip: child coefficient c_0 = 1, parent k c_k = -qc_k, V = sum_k vc_k R[colour_k],
+// w = sum_k wc_k theta (root-prior family: r = x_root - mu, V = R[colour]); O = child_mask[f] the components the factor
+// keeps, j = (V_OO)^-1.  With r = sum_a c_a x_a - w, a block in scope random with the posterior moments (m_a, Sigma_ab) of
+// the cluster's J^-1 h and J^-1, a tip's data row and the fixed root's mean constants:
+//   e = E[r],  M = Cov(r) + e e',   G_V = (j M j - j) / 2   (d loglik = tr(G_V dV)),   g_w = j e   (d loglik = g_w' dw),
+//   g_qk = E[r' j x_k] = tr(j (sum_a c_a Sigma_ak + e m_k'))                          (d loglik = g_qk dqc_k),
+// and the chain rule through the edge coefficients (lg_coefs) gives dR[colour], dmu, dtheta and dalpha.
+//
+// Stage 1 (grad_family): one workgroup per (family, site) solves the family's cluster in LDS (mom_solve: Sigma never leaves
+// the LDS) and writes the family's slot [G_V (p*p) | g_w (p) | dalpha term | c_mu | c_theta | c_R[n_rates]]: the matrices once
+// and the scalar chain-rule coefficients beside them, so that the slot does not grow with the number of rates.
+// Stage 2 (grad_reduce_blocks, grad_reduce_final): the slots are added in a FIXED order -- 256 consecutive families per
+// workgroup, four lanes of 64 families each in family order, the four lanes added in lane order, then the block partials by a
+// fixed tree -- no floating-point atomics: two calls return the same bytes.  The slots of a chunk of sites at a time
+// (256 MB at most), as pgbp_bm_exact_stats bounds its scratch.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cmath>
+#include <string>
+#include <vector>
+
+#include "pgbp_bs16.hpp"
+#include "pgbp_kernels.hpp"
+#include "pgbp_mom_dev.hpp"
+
+namespace pgbp {
+
+extern __shared__ double grad_lds[];
+
+constexpr int kGradFamBlock = 256;   // families per workgroup of the first reduction
+
+// edge coefficients of a parent edge and their derivatives in alpha (lg_coefs of pgbp_lgfill.hip; a = exp(-alpha t))
+__device__ __forceinline__ void grad_coefs(int model, double alpha, double t, double gam, double& qc, double& vc, double& wc,
+                                           double& dqc, double& dvc, double& dwc) {
+#pragma clang fp contract(off)
+  if (model == PGBP_LG_OU) {
+    const double a = exp(-alpha * t);
+    qc = gam * a;
+    vc = gam * gam * (1.0 - a * a);
+    wc = gam * (1.0 - a);
+    dqc = -(gam * t) * a;
+    dvc = 2.0 * (gam * gam) * t * (a * a);
+    dwc = (gam * t) * a;
+  } else {
+    qc = gam;
+    vc = gam * gam * t;
+    wc = 0.0;
+    dqc = dvc = dwc = 0.0;
+  }
+}
+
+__device__ __forceinline__ int grad_rank(unsigned long long mask, int t) { return __popcll(mask & ((1ull << t) - 1ull)); }
+
+// Gauss-Jordan on the mo x 2mo system [V | I] (row stride ld) in LDS by NT threads: the right half becomes V^-1; false when
+// a pivot is not positive (uniform: every thread reads the same pivot)
+template <int NT>
+__device__ __forceinline__ bool grad_invert(double* __restrict__ A, int mo, int ld, int t) {
+#pragma clang fp contract(off)
+  const int nc = 2 * mo;
+  for (int k = 0; k < mo; ++k) {
+    __syncthreads();
+    const double d = A[k * ld + k];
+    if (!(d > 0.0)) return false;
+    const double rd = 1.0 / d;
+    __syncthreads();
+    for (int j = k + 1 + t; j < nc; j += NT) A[k * ld + j] = A[k * ld + j] * rd;
+    __syncthreads();
+    const int ncol = nc - (k + 1);
+    for (int idx = t; idx < (mo - 1) * ncol; idx += NT) {
+      int i = idx / ncol;
+      const int j = k + 1 + (idx - i * ncol);
+      if (i >= k) ++i;
+      A[i * ld + j] = A[i * ld + j] - A[i * ld + k] * A[k * ld + j];
+    }
+  }
+  __syncthreads();
+  return true;
+}
+
+// LDS of grad_family beyond mom_solve's: doubles, then ints
+__host__ __device__ inline int grad_ldv(int p) { return (2 * p) | 1; }
+__host__ __device__ inline size_t grad_extra_doubles(int p, int K) {
+  return (size_t)p * grad_ldv(p) + 2 * (size_t)p * p + 2 * (size_t)p + (size_t)(K + 1) * p + 6 * (size_t)K + 1;
+}
+__host__ __device__ inline size_t grad_extra_ints(int p, int K) { return (size_t)(K + 1) + (size_t)p + (size_t)(K + 1) * p; }
+
+template <int NT>
+__global__ __launch_bounds__(NT) void grad_family(const double* __restrict__ pool, int64_t pool_stride,
+                                                  const int64_t* __restrict__ boff, const int32_t* __restrict__ bdim, int bs,
+                                                  int fp, LgStatic F, LgParams M, const int32_t* __restrict__ fam_cluster,
+                                                  int n_fam, int site0, int n_sites, double* __restrict__ slots,
+                                                  int32_t* __restrict__ info, int info0) {
+#pragma clang fp contract(off)
+  const int t = threadIdx.x, f = blockIdx.x;
+  const int p = F.p, K = F.K, np = F.n_parents[f], nn = np + 1, nr = F.n_rates;
+  const int c = fam_cluster[f], m = bdim[c], ld = (m + 1) | 1;
+  const unsigned long long full = p >= 64 ? ~0ull : ((1ull << p) - 1ull);
+  const unsigned long long O = F.child_mask ? (F.child_mask[f] & full) : full;
+  const int mo = __popcll(O);
+  const int cpos = F.child_pos[f];
+  const int sl = p * p + p + 3 + nr;
+  const int DA = p * p + p, CMU = DA + 1, CTH = DA + 2, CR = DA + 3;
+  // LDS: [W | dv] of mom_solve, then this kernel's arrays
+  double* __restrict__ W = grad_lds;
+  double* __restrict__ dv = grad_lds + m * ld;
+  double* __restrict__ A = grad_lds + mom_lds_doubles(m);   // [V_OO | I] -> [.. | j], mo x ldv
+  const int ldv = grad_ldv(p);
+  double* __restrict__ Mx = A + p * ldv;        // M = Cov(r) + e e'  (mo x mo)
+  double* __restrict__ Tx = Mx + p * p;         // j M
+  double* __restrict__ ev = Tx + p * p;         // e
+  double* __restrict__ ge = ev + p;             // j e
+  double* __restrict__ xm = ge + p;             // [a][i]: posterior mean of block a (or its constant value) at kept trait i
+  double* __restrict__ cz = xm + (K + 1) * p;   // c_a (K + 1)
+  double* __restrict__ vcs = cz + (K + 1);      // vc, wc, dqc, dvc, dwc (K each)
+  double* __restrict__ wcs = vcs + K;
+  double* __restrict__ dqs = wcs + K;
+  double* __restrict__ dvs = dqs + K;
+  double* __restrict__ dws = dvs + K;
+  int* __restrict__ ipos = reinterpret_cast<int*>(grad_lds + mom_lds_doubles(m) + ((grad_extra_doubles(p, K) + 1) & ~(size_t)1));
+  int* __restrict__ oidx = ipos + (K + 1);
+  int* __restrict__ vi = oidx + p;              // [a][i]: the variable's index in the cluster, -1: a constant
+  bool any_scope = cpos >= 0;
+  for (int k = 0; k < np; ++k) any_scope |= F.parent_pos[(size_t)f * K + k] >= 0;
+  // families the factor fill skips contribute nothing (and a root-prior family of a fixed root, which has no factor)
+  const bool skip = mo == 0 || (np == 0 && cpos < 0);
+  const bool packed = bs && bs16::applies(m, fp);
+  const bool ou = M.model == PGBP_LG_OU;
+  for (int site = blockIdx.y; site < n_sites; site += gridDim.y) {
+    double* __restrict__ o = slots + ((int64_t)site * n_fam + f) * sl;
+    if (skip) {
+      for (int a = t; a < sl; a += NT) o[a] = 0.0;
+      continue;
+    }
+    const int64_t as = site0 + site, ps = M.per_site ? as : 0;
+    const double* __restrict__ R = M.R + ps * nr * p * p;
+    const double* __restrict__ mu = M.mu + ps * p;
+    const double* __restrict__ theta = (ou && M.theta) ? M.theta + ps * p : nullptr;
+    const double alpha = ou ? M.alpha[ps] : 0.0;
+    int st = 0;
+    if (any_scope) {
+      const double* __restrict__ rec = pool + as * pool_stride + boff[c];
+      double mant, quad;
+      int expo;
+      st = mom_solve<NT, true>(rec, m, packed, fp, W, dv, t, mant, expo, quad);
+    } else {
+      __syncthreads();   // (the previous site's arrays have been read)
+    }
+    if (st != 0) {   // not positive definite (the constant belief J = 0 included: no moments): the site's sums are NaN
+      for (int a = t; a < sl; a += NT) o[a] = NAN;
+      if (t == 0) atomicMin(info + info0 + site, c + 1);
+      continue;
+    }
+    // coefficients, positions, kept traits
+    for (int a = t; a <= np; a += NT) {
+      if (a == 0) {
+        cz[0] = 1.0;
+        ipos[0] = cpos;
+      } else {
+        const int k = a - 1;
+        double qc, vc, wc, dq, dvv, dw;
+        grad_coefs(M.model, alpha, F.length[(size_t)f * K + k], F.gamma[(size_t)f * K + k], qc, vc, wc, dq, dvv, dw);
+        cz[a] = -qc;
+        vcs[k] = vc; wcs[k] = wc; dqs[k] = dq; dvs[k] = dvv; dws[k] = dw;
+        ipos[a] = F.parent_pos[(size_t)f * K + k];
+      }
+    }
+    for (int tr = t; tr < p; tr += NT)
+      if ((O >> tr) & 1ull) oidx[grad_rank(O, tr)] = tr;
+    __syncthreads();
+    // where each block's kept traits sit in the cluster, and their posterior mean (or constant value)
+    for (int idx = t; idx < nn * mo; idx += NT) {
+      const int a = idx / mo, i = idx - a * mo, tr = oidx[i];
+      const int pa = ipos[a];
+      if (pa >= 0) {
+        const unsigned long long ma = a == 0 ? O : (F.parent_mask ? F.parent_mask[(size_t)f * K + a - 1] : full);
+        const int v = pa + grad_rank(ma, tr);
+        vi[a * p + i] = v;
+        xm[a * p + i] = W[v * ld + m];
+      } else {
+        vi[a * p + i] = -1;
+        xm[a * p + i] = a == 0 ? F.data[(as * F.n_rows + F.data_row[f]) * p + tr] : mu[tr];   // tip / fixed root
+      }
+    }
+    // V_OO and the identity
+    for (int idx = t; idx < mo * mo; idx += NT) {
+      const int j = idx / mo, i = idx - j * mo;
+      const int e = oidx[i] + oidx[j] * p;
+      double v = 0.0;
+      if (np == 0) {
+        v = R[(int64_t)F.color[(size_t)f * K] * p * p + e];
+      } else {
+        for (int k = 0; k < np; ++k) v = v + vcs[k] * R[(int64_t)F.color[(size_t)f * K + k] * p * p + e];
+      }
+      A[i * ldv + j] = v;
+      A[i * ldv + mo + j] = (i == j) ? 1.0 : 0.0;
+    }
+    __syncthreads();
+    // e = E[r]
+    for (int i = t; i < mo; i += NT) {
+      const int tr = oidx[i];
+      double e = 0.0;
+      for (int a = 0; a < nn; ++a) e = e + cz[a] * xm[a * p + i];
+      double w = 0.0;
+      if (np == 0) {
+        w = mu[tr];
+      } else if (theta) {
+        for (int k = 0; k < np; ++k) w = w + wcs[k] * theta[tr];
+      }
+      ev[i] = e - w;
+    }
+    __syncthreads();
+    // M = Cov(r) + e e'
+    for (int idx = t; idx < mo * mo; idx += NT) {
+      const int j = idx / mo, i = idx - j * mo;
+      double s = 0.0;
+      for (int a = 0; a < nn; ++a) {
+        const int va = vi[a * p + i];
+        if (va < 0) continue;
+        for (int b = 0; b < nn; ++b) {
+          const int vb = vi[b * p + j];
+          if (vb < 0) continue;
+          s = s + cz[a] * cz[b] * (va >= vb ? W[va * ld + vb] : W[vb * ld + va]);
+        }
+      }
+      Mx[i * mo + j] = s + ev[i] * ev[j];
+    }
+    if (!grad_invert<NT>(A, mo, ldv, t)) {   // a variance that is not positive definite: the fill made this cluster's g NaN
+      for (int a = t; a < sl; a += NT) o[a] = NAN;
+      if (t == 0) atomicMin(info + info0 + site, c + 1);
+      continue;
+    }
+    // j(i, k): the upper triangle mirrored, exactly symmetric (as the fill reads it)
+    auto jj = [&](int i, int k) -> double { return i <= k ? A[i * ldv + mo + k] : A[k * ldv + mo + i]; };
+    for (int idx = t; idx < mo * mo; idx += NT) {
+      const int k = idx / mo, i = idx - k * mo;
+      double s = 0.0;
+      for (int l = 0; l < mo; ++l) s = s + jj(i, l) * Mx[l * mo + k];
+      Tx[i * mo + k] = s;
+    }
+    for (int i = t; i < mo; i += NT) {
+      double s = 0.0;
+      for (int l = 0; l < mo; ++l) s = s + jj(i, l) * ev[l];
+      ge[i] = s;
+    }
+    for (int a = t; a < DA; a += NT) o[a] = 0.0;   // (the entries outside O)
+    __syncthreads();
+    // G_V = (j M j - j) / 2 embedded into p x p (upper triangle computed, mirrored), g_w = j e
+    for (int idx = t; idx < mo * mo; idx += NT) {
+      const int k = idx / mo, i = idx - k * mo;
+      if (i > k) continue;
+      double s = 0.0;
+      for (int l = 0; l < mo; ++l) s = s + Tx[i * mo + l] * jj(l, k);
+      const double g = 0.5 * (s - jj(i, k));
+      o[oidx[i] + oidx[k] * p] = g;
+      o[oidx[k] + oidx[i] * p] = g;
+      Mx[i * mo + k] = g;   // (M has been consumed: T = j M is complete) -- kept for the alpha term
+      Mx[k * mo + i] = g;
+    }
+    for (int i = t; i < mo; i += NT) o[p * p + oidx[i]] = ge[i];
+    __syncthreads();
+    if (t == 0) {
+      double cmu = 0.0, cth = 0.0, da = 0.0;
+      if (np == 0) {
+        cmu = 1.0;
+      } else {
+        for (int k = 0; k < np; ++k) {
+          if (ipos[k + 1] < 0) cmu = cmu - cz[k + 1];   // qc_k: the parent is the fixed root
+          cth = cth + wcs[k];
+        }
+        if (ou) {
+          for (int k = 0; k < np; ++k) {
+            const double* __restrict__ Rk = R + (int64_t)F.color[(size_t)f * K + k] * p * p;
+            double trGR = 0.0, thg = 0.0, gq = 0.0;
+            for (int i = 0; i < mo; ++i) {
+              for (int l = 0; l < mo; ++l) {
+                trGR = trGR + Mx[i * mo + l] * Rk[oidx[l] + oidx[i] * p];
+                // E[r x_k'](i, l) = sum_a c_a Sigma(a_i, k_l) + e_i m_k(l)
+                double ex = ev[i] * xm[(k + 1) * p + l];
+                const int vk = vi[(k + 1) * p + l];
+                if (vk >= 0) {
+                  for (int a = 0; a < nn; ++a) {
+                    const int va = vi[a * p + i];
+                    if (va >= 0) ex = ex + cz[a] * (va >= vk ? W[va * ld + vk] : W[vk * ld + va]);
+                  }
+                }
+                gq = gq + jj(l, i) * ex;
+              }
+              if (theta) thg = thg + theta[oidx[i]] * ge[i];
+            }
+            da = da + dvs[k] * trGR + dws[k] * thg + dqs[k] * gq;
+          }
+        }
+      }
+      o[DA] = da;
+      o[CMU] = cmu;
+      o[CTH] = cth;
+    }
+    for (int r = t; r < nr; r += NT) {
+      double cr = 0.0;
+      if (np == 0) {
+        cr = F.color[(size_t)f * K] == r ? 1.0 : 0.0;
+      } else {
+        for (int k = 0; k < np; ++k)
+          if (F.color[(size_t)f * K + k] == r) cr = cr + vcs[k];
+      }
+      o[CR + r] = cr;
+    }
+  }
+}
+
+// entry en of a site's gradient [dR (n_rates * p*p) | dmu (p) | dtheta (p) | dalpha] as this family's slot gives it
+__device__ __forceinline__ double grad_entry(const double* __restrict__ o, int en, int p, int nr) {
+#pragma clang fp contract(off)
+  const int pp = p * p, DA = pp + p;
+  if (en < nr * pp) {
+    const int r = en / pp;
+    return o[en - r * pp] * o[DA + 3 + r];
+  }
+  en -= nr * pp;
+  if (en < p) return o[pp + en] * o[DA + 1];
+  en -= p;
+  if (en < p) return o[pp + en] * o[DA + 2];
+  return o[DA];
+}
+
+// partial[site][block][entry]: kGradFamBlock consecutive families, lane q = t / 64 adds its 64 families in family order,
+// the four lanes are added in lane order
+__global__ __launch_bounds__(256) void grad_reduce_blocks(const double* __restrict__ slots, int n_fam, int p, int nr,
+                                                          int n_ent, int n_sites, double* __restrict__ partial) {
+#pragma clang fp contract(off)
+  __shared__ double part[256];
+  const int t = threadIdx.x, el = t & 63, q = t >> 6;
+  const int en = blockIdx.x * 64 + el, fb = blockIdx.y, nfb = gridDim.y;
+  const int sl = p * p + p + 3 + nr;
+  for (int site = blockIdx.z; site < n_sites; site += gridDim.z) {
+    double acc = 0.0;
+    if (en < n_ent) {
+      const int f0 = fb * kGradFamBlock + q * 64;
+      const int f1 = min(f0 + 64, n_fam);
+      for (int f = f0; f < f1; ++f) acc = acc + grad_entry(slots + ((int64_t)site * n_fam + f) * sl, en, p, nr);
+    }
+    __syncthreads();
+    part[t] = acc;
+    __syncthreads();
+    if (q == 0 && en < n_ent)
+      partial[((int64_t)site * nfb + fb) * n_ent + en] = ((part[el] + part[64 + el]) + part[128 + el]) + part[192 + el];
+  }
+}
+
+__global__ __launch_bounds__(256) void grad_reduce_final(const double* __restrict__ partial, int nfb, int n_ent, int n_sites,
+                                                         double* __restrict__ out, int out0) {
+#pragma clang fp contract(off)
+  __shared__ double part[256];
+  const int t = threadIdx.x, en = blockIdx.x;
+  for (int site = blockIdx.y; site < n_sites; site += gridDim.y) {
+    double acc = 0.0;
+    for (int b = t; b < nfb; b += 256) acc = acc + partial[((int64_t)site * nfb + b) * n_ent + en];
+    __syncthreads();
+    part[t] = acc;
+    __syncthreads();
+    for (int w = 128; w > 0; w >>= 1) {
+      if (t < w) part[t] = part[t] + part[t + w];
+      __syncthreads();
+    }
+    if (t == 0) out[(int64_t)(out0 + site) * n_ent + en] = part[0];
+  }
+}
+
+}  // namespace pgbp
+
+using namespace pgbp;
+
+extern "C" int pgbp_lg_gradient(pgbp_engine* e, int32_t site_begin, int32_t site_end, double* dR, double* dmu, double* dalpha,
+                                double* dtheta, int32_t* info) {
+  if (!e) return PGBP_ERR_INVALID;
+  LgParams M{};
+  {
+    const EngineView v0 = engine_peek(e);
+    if (!v0.lg_ready)
+      return engine_fail(e, PGBP_ERR_STATE, "pgbp_lg_gradient: no family table (call pgbp_lg_setup first)");
+    if (!engine_lg_params(e, &M))
+      return engine_fail(e, PGBP_ERR_STATE, "pgbp_lg_gradient: no parameters yet (call pgbp_lg_assignfactors first)");
+    if (site_begin < 0 || site_end < site_begin || site_end > v0.plan->n_sites)
+      return engine_fail(e, PGBP_ERR_INVALID, "pgbp_lg_gradient: site range outside the engine's sites");
+    if (!dR || !dmu) return engine_fail(e, PGBP_ERR_INVALID, "pgbp_lg_gradient: no output buffer");
+    if (M.model == PGBP_LG_OU && (!dalpha || !dtheta))
+      return engine_fail(e, PGBP_ERR_INVALID, "pgbp_lg_gradient: the OU model needs dalpha and dtheta");
+  }
+  EngineView v;
+  int rc = engine_view(e, &v);
+  if (rc) return rc;
+  // (as in pgbp_bm_exact_stats, what follows runs on the caller's current device: an engine of a multi-device group is
+  // swept from the thread that has its device current)
+  const Plan& pl = *v.plan;
+  const LgStatic& F = *v.lg;
+  const int nc = pl.n_clusters, p = F.p, K = F.K, nr = F.n_rates;
+  // which cluster each family sits in (the CSR of pgbp_lg_setup back from the device: a word per family)
+  std::vector<int32_t> off(nc + 1);
+  hipError_t herr = hipMemcpy(off.data(), F.cl_off, sizeof(int32_t) * (nc + 1), hipMemcpyDeviceToHost);
+  const int nf = herr == hipSuccess ? off[nc] : 0;
+  std::vector<int32_t> cfam(std::max(nf, 1));
+  if (herr == hipSuccess && nf > 0) herr = hipMemcpy(cfam.data(), F.cl_fam, sizeof(int32_t) * nf, hipMemcpyDeviceToHost);
+  if (herr != hipSuccess) return engine_fail(e, PGBP_ERR_HIP, std::string("pgbp_lg_gradient (family table): ") + hipGetErrorString(herr));
+  std::vector<int32_t> fcl(std::max(nf, 1), 0);
+  int max_m = 1;
+  for (int c = 0; c < nc; ++c)
+    for (int q = off[c]; q < off[c + 1]; ++q) {
+      fcl[cfam[q]] = c;
+      if (pl.dims[c] > kLdsMaxDim)
+        return engine_fail(e, PGBP_ERR_INVALID, "pgbp_lg_gradient: family " + std::to_string(cfam[q]) + " (cluster " +
+                                                    std::to_string(c) + "): the cluster has more than " +
+                                                    std::to_string(kLdsMaxDim) + " variables");
+      max_m = std::max(max_m, (int)pl.dims[c]);
+    }
+  const size_t lds_bytes = sizeof(double) * (mom_lds_doubles(max_m) + ((grad_extra_doubles(p, K) + 1) & ~(size_t)1)) +
+                           sizeof(int) * grad_extra_ints(p, K);
+  if (lds_bytes > 160 * 1024)
+    return engine_fail(e, PGBP_ERR_INVALID, "pgbp_lg_gradient: a cluster of " + std::to_string(max_m) + " variables with " +
+                                                std::to_string(p) + " traits needs " + std::to_string(lds_bytes) +
+                                                " bytes of LDS, more than the 160 KB of a compute unit");
+  const int ns = site_end - site_begin;
+  if (ns == 0) return PGBP_OK;
+  const bool ou = M.model == PGBP_LG_OU;
+  const int pp = p * p, n_ent = nr * pp + 2 * p + 1;
+  auto scatter = [&](const double* src, const int32_t* inf) {   // a site's [dR | dmu | dtheta | dalpha] to the caller's arrays
+    for (int s = 0; s < ns; ++s) {
+      const bool bad = inf && inf[s] != 0;
+      const double* g = src ? src + (size_t)s * n_ent : nullptr;
+      for (int a = 0; a < nr * pp; ++a) dR[(size_t)s * nr * pp + a] = bad ? NAN : (g ? g[a] : 0.0);
+      for (int a = 0; a < p; ++a) dmu[(size_t)s * p + a] = bad ? NAN : (g ? g[nr * pp + a] : 0.0);
+      if (dtheta)
+        for (int a = 0; a < p; ++a) dtheta[(size_t)s * p + a] = bad ? NAN : ((g && ou) ? g[nr * pp + p + a] : 0.0);
+      if (dalpha) dalpha[s] = bad ? NAN : ((g && ou) ? g[nr * pp + 2 * p] : 0.0);
+      if (info) info[s] = inf ? inf[s] : 0;
+    }
+  };
+  if (nf == 0) {
+    scatter(nullptr, nullptr);
+    return PGBP_OK;
+  }
+  const int sl = pp + p + 3 + nr;
+  const int64_t per_site = (int64_t)nf * sl;
+  const int chunk = (int)std::max<int64_t>(1, std::min<int64_t>(ns, ((int64_t)32 << 20) / per_site));
+  const int nfb = (nf + kGradFamBlock - 1) / kGradFamBlock;
+  int32_t* d_fcl = nullptr;
+  double *d_slots = nullptr, *d_part = nullptr, *d_out = nullptr;
+  int32_t* d_info = nullptr;
+  std::vector<int32_t> inf(ns, 0x7fffffff);
+  std::vector<double> out((size_t)ns * n_ent);
+  herr = hipMalloc(reinterpret_cast<void**>(&d_fcl), sizeof(int32_t) * nf);
+  if (herr == hipSuccess) herr = hipMalloc(reinterpret_cast<void**>(&d_slots), sizeof(double) * (size_t)per_site * chunk);
+  if (herr == hipSuccess) herr = hipMalloc(reinterpret_cast<void**>(&d_part), sizeof(double) * (size_t)chunk * nfb * n_ent);
+  if (herr == hipSuccess) herr = hipMalloc(reinterpret_cast<void**>(&d_out), sizeof(double) * (size_t)ns * n_ent);
+  if (herr == hipSuccess) herr = hipMalloc(reinterpret_cast<void**>(&d_info), sizeof(int32_t) * (size_t)ns);
+  if (herr == hipSuccess) herr = hipMemcpyAsync(d_fcl, fcl.data(), sizeof(int32_t) * nf, hipMemcpyHostToDevice, v.st);
+  if (herr == hipSuccess) herr = hipMemcpyAsync(d_info, inf.data(), sizeof(int32_t) * ns, hipMemcpyHostToDevice, v.st);
+  if (herr != hipSuccess) {
+    for (void* q : {(void*)d_fcl, (void*)d_slots, (void*)d_part, (void*)d_out, (void*)d_info})
+      if (q) (void)hipFree(q);
+    return engine_fail(e, PGBP_ERR_HIP, std::string("pgbp_lg_gradient (scratch): ") + hipGetErrorString(herr));
+  }
+  (void)hipGetLastError();   // (an error an earlier asynchronous call left behind is that call's to report)
+  {
+    const void* kern = max_m <= 64 ? reinterpret_cast<const void*>(grad_family<64>) : reinterpret_cast<const void*>(grad_family<256>);
+    if (lds_bytes > 64 * 1024) herr = hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
+    for (int s0 = 0; herr == hipSuccess && s0 < ns; s0 += chunk) {
+      const int n = std::min(chunk, ns - s0), gy = std::min(n, 65535);
+      if (max_m <= 64)
+        hipLaunchKernelGGL(grad_family<64>, dim3(nf, gy), dim3(64), lds_bytes, v.st, v.pool, pl.pool_stride(), v.boff, v.bdim,
+                           v.bs16, pl.fast_p, F, M, d_fcl, nf, site_begin + s0, n, d_slots, d_info, s0);
+      else
+        hipLaunchKernelGGL(grad_family<256>, dim3(nf, gy), dim3(256), lds_bytes, v.st, v.pool, pl.pool_stride(), v.boff, v.bdim,
+                           v.bs16, pl.fast_p, F, M, d_fcl, nf, site_begin + s0, n, d_slots, d_info, s0);
+      hipLaunchKernelGGL(grad_reduce_blocks, dim3((n_ent + 63) / 64, nfb, gy), dim3(256), 0, v.st, d_slots, nf, p, nr, n_ent, n,
+                         d_part);
+      hipLaunchKernelGGL(grad_reduce_final, dim3(n_ent, gy), dim3(256), 0, v.st, d_part, nfb, n_ent, n, d_out, s0);
+    }
+    if (herr == hipSuccess) herr = hipGetLastError();
+  }
+  if (herr == hipSuccess) herr = hipMemcpyAsync(out.data(), d_out, sizeof(double) * out.size(), hipMemcpyDeviceToHost, v.st);
+  if (herr == hipSuccess) herr = hipMemcpyAsync(inf.data(), d_info, sizeof(int32_t) * (size_t)ns, hipMemcpyDeviceToHost, v.st);
+  const hipError_t serr = hipStreamSynchronize(v.st);
+  if (herr == hipSuccess) herr = serr;
+  for (void* q : {(void*)d_fcl, (void*)d_slots, (void*)d_part, (void*)d_out, (void*)d_info})
+    if (q) (void)hipFree(q);
+  if (herr != hipSuccess) return engine_fail(e, PGBP_ERR_HIP, std::string("pgbp_lg_gradient: ") + hipGetErrorString(herr));
+  for (int s = 0; s < ns; ++s) inf[s] = inf[s] == 0x7fffffff ? 0 : inf[s];
+  scatter(out.data(), inf.data());
+  return PGBP_OK;
+}

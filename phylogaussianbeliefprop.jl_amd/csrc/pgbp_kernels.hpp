@@ -289,5 +289,7 @@ struct EngineView {
 int engine_view(pgbp_engine* e, EngineView* v);
 EngineView engine_peek(pgbp_engine* e);          // the same words without touching the layout, the device or the last error
 const Plan* engine_plan(const pgbp_engine* e);
+// the parameters the engine kept from the last pgbp_lg_assignfactors (device pointers); false: none yet
+bool engine_lg_params(const pgbp_engine* e, LgParams* out);
 
 }  // namespace pgbp

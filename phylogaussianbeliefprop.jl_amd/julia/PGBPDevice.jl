@@ -243,6 +243,21 @@ function calibrate_exact_cliquetree!(o::DeviceClusterGraphBelief, spt, rootclust
     return (reshape(num, p, p) ./ den[], mu[rootpos:rootpos+p-1])
 end
 
+"""
+    lg_gradient(obj, p, nrates; ou = false) -> (dR, dmu, dalpha, dtheta)
+
+The exact gradient of the log-likelihood with respect to the parameters of the last pgbp_lg_assignfactors, from the current
+beliefs (pgbp_lg_gradient: Fisher's identity, one sweep over the node families).  Exact only when the beliefs are calibrated
+(postorder and preorder) on a clique tree under those parameters; on a loopy graph, at a converged calibration, the gradient of
+the factored energy.  `dR[:, :, c]` is symmetric with d loglik = tr(dR[:, :, c] * dR_c); dalpha, dtheta are zero unless `ou`.
+"""
+function lg_gradient(o::DeviceClusterGraphBelief, p::Integer, nrates::Integer; ou::Bool = false)
+    dR = zeros(p * p * nrates); dmu = zeros(p); dalpha = Ref(0.0); dtheta = zeros(p); info = Ref(Int32(0))
+    check(o.handle, @ccall LIB.pgbp_lg_gradient(o.handle::Ptr{Cvoid}, Int32(0)::Int32, Int32(1)::Int32, dR::Ptr{Float64}, dmu::Ptr{Float64}, dalpha::Ref{Float64}, dtheta::Ptr{Float64}, info::Ref{Int32})::Cint)
+    info[] == 0 || throw(PGBP.LA.PosDefException(info[]))
+    return (reshape(dR, p, p, nrates), dmu, dalpha[], dtheta)
+end
+
 "the reference's error line for a failed message (src/beliefupdates.jl:69-76): belief metadata + integrated indices"
 function report_failure(o::DeviceClusterGraphBelief, spt, res::Result, verbose::Bool)
     i = res.fail_edge + 1

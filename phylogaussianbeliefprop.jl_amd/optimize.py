@@ -43,17 +43,35 @@ class _BMTransform:
                 U[i, j] = theta[k]; k += 1
         return U.T @ U, np.asarray(theta[k:k + p], float)
 
+    def pullback(self, theta, dR, dmu):
+        """Chain rule through `back`: the gradient in theta of a function whose gradient in (R, mu) is (dR, dmu), dR
+        symmetric with d f = tr(dR dR_) (what gradient_lg returns).  Diagonal: R_ii = exp(theta_i).  Full: R = U'U, so
+        d f / d U = 2 U dR on the upper triangle, the diagonal entries times U_ii for theta = log U_ii."""
+        p = self.p
+        dR = np.atleast_2d(np.asarray(dR, float))
+        dR = (dR + dR.T) / 2
+        dmu = np.asarray(dmu, float).reshape(p)
+        if self.diagonal:
+            return np.concatenate([np.diag(dR) * np.exp(np.asarray(theta[:p], float)), dmu])
+        R, _ = self.back(theta)
+        U = np.linalg.cholesky(R).T
+        dU = 2.0 * U @ dR
+        return np.array([dU[i, i] * U[i, i] for i in range(p)] + [dU[i, j] for j in range(1, p) for i in range(j)]
+                        + list(dmu))
 
-def _minimise(score, x0, maxiter):
+
+def _minimise(score, x0, maxiter, grad=None):
     from scipy.optimize import minimize
 
-    def grad(x):
+    def central(x):
         g = np.zeros_like(x)
         for i in range(len(x)):
             h = 1e-6 * max(1.0, abs(x[i]))
             e = np.zeros_like(x); e[i] = h
             g[i] = (score(x + e) - score(x - e)) / (2 * h)
         return g
+    if grad is None:
+        grad = central
     # L-BFGS-B, restarted from its own end point while it still improves (its line search gives up early on badly scaled
     # starts, e.g. rates two orders of magnitude off), then a Nelder-Mead polish when a restart stalls above the tolerance
     best = minimize(score, x0, jac=grad, method="L-BFGS-B", options={"maxiter": maxiter, "ftol": 1e-15, "gtol": 1e-9})
@@ -77,16 +95,48 @@ def _minimise(score, x0, maxiter):
     return best
 
 
-def calibrate_optimize_cliquetree_(beliefs, schedule_tree, R0, mu0, extra_rates=(), maxiter=200, diagonal=False):
+def _check_gradient_mode(gradient):
+    if gradient not in ("central", "analytic"):
+        raise ValueError(f"gradient must be 'central' or 'analytic', not {gradient!r}")
+
+
+def calibrate_optimize_cliquetree_(beliefs, schedule_tree, R0, mu0, extra_rates=(), maxiter=200, diagonal=False,
+                                   gradient="central"):
     """calibrate_optimize_cliquetree! (src/calibration.jl:183-221) for a homogeneous Brownian motion (univariate or full
     rate matrix): maximise the log-likelihood over (R, mu); the root prior variance, if the root is random, stays fixed
     (`extra_rates`: the matrices that follow R in the rate table of lg_setup, e.g. the root prior variance).
     Each evaluation = assignfactors! + postorder of `schedule_tree` + integratebelief! at its root, on the device.
     diagonal: MvDiagBrownianMotion (independent traits: only the diagonal of R is estimated).
+    gradient: "central" (default) -- central differences, 2 n_theta evaluations per gradient; "analytic" -- value and
+    exact gradient from ONE calibration and one sweep over the node families (loglik_and_gradient_lg), pulled back
+    through the transform.  `opt.n_device_evals` counts the device evaluations either way.
     Returns (R, mu, loglik, scipy result)."""
+    _check_gradient_mode(gradient)
     p = beliefs._lg_p
     tf = _BMTransform(p, diagonal)
     beliefs._ensure_schedule([schedule_tree])
+    count = [0]
+    memo = {}
+
+    def value_and_grad(theta):
+        key = np.asarray(theta, float).tobytes()
+        if key not in memo:
+            memo.clear()
+            R, mu = tf.back(theta)
+            try:
+                np.linalg.cholesky(R)
+            except np.linalg.LinAlgError:
+                memo[key] = (np.inf, np.zeros(len(theta)))
+                return memo[key]
+            rates = np.stack([R] + [np.atleast_2d(np.asarray(x, float)) for x in extra_rates])
+            beliefs.assignfactors_lg_(rates, mu)
+            count[0] += 1
+            ll, g = beliefs.loglik_and_gradient_lg(schedule_tree, all_sites=True)
+            if g["info"][0] or not np.isfinite(ll[0]):
+                memo[key] = (np.inf, np.zeros(len(theta)))
+            else:
+                memo[key] = (-float(ll[0]), -tf.pullback(theta, g["dR"][0, 0], g["dmu"][0]))
+        return memo[key]
 
     def score(theta):
         R, mu = tf.back(theta)
@@ -96,23 +146,33 @@ def calibrate_optimize_cliquetree_(beliefs, schedule_tree, R0, mu0, extra_rates=
             return np.inf
         rates = np.stack([R] + [np.atleast_2d(np.asarray(x, float)) for x in extra_rates])
         beliefs.assignfactors_lg_(rates, mu)
+        count[0] += 1
         ll, info = beliefs.loglik_lg()
         return np.inf if (info[0] or not np.isfinite(ll[0])) else -float(ll[0])
-    opt = _minimise(score, tf.forward(R0, mu0), maxiter)
+    if gradient == "analytic":
+        opt = _minimise(lambda x: value_and_grad(x)[0], tf.forward(R0, mu0), maxiter, grad=lambda x: value_and_grad(x)[1])
+    else:
+        opt = _minimise(score, tf.forward(R0, mu0), maxiter)
+    opt.n_device_evals = count[0]
     R, mu = tf.back(opt.x)
     return R, mu, -float(opt.fun), opt
 
 
 def calibrate_optimize_clustergraph_(beliefs, schedule, R0, mu0, extra_rates=(), maxiter_calibration=100, maxiter=200,
-                                     diagonal=False):
+                                     diagonal=False, gradient="central"):
     """calibrate_optimize_clustergraph! (src/calibration.jl:309-359): maximise the factored energy (= minus the Bethe free
     energy; the log-likelihood on a clique tree) over (R, mu).  Each evaluation = assignfactors! + factors from beliefs +
     regularizebeliefs_bycluster! + calibrate!(schedule, maxiter_calibration; auto=true) + free_energy, on the device.
+    gradient: "central" (default), or "analytic": the family sweep (gradient_lg) on the beliefs the calibration left.
+    That is the gradient of the factored energy ONLY at a converged calibration (the Bethe free energy is stationary in
+    the beliefs at a fixed point); where calibrate! stops at maxiter_calibration before convergence it is approximate.
     Returns (R, mu, factored energy, scipy result)."""
     from .calibration import calibrate_
+    _check_gradient_mode(gradient)
     p = beliefs._lg_p
     tf = _BMTransform(p, diagonal)
     lib = beliefs._lib
+    count = [0]
 
     def score(theta):
         R, mu = tf.back(theta)
@@ -122,6 +182,7 @@ def calibrate_optimize_clustergraph_(beliefs, schedule, R0, mu0, extra_rates=(),
             return np.inf
         rates = np.stack([R] + [np.atleast_2d(np.asarray(x, float)) for x in extra_rates])
         beliefs.assignfactors_lg_(rates, mu)               # also snapshots the factors and resets the flags
+        count[0] += 1
         if lib.pgbp_regularize_bycluster(beliefs._eng) != L.PGBP_OK:
             return np.inf
         succ, _ = calibrate_(beliefs, schedule, maxiter_calibration, auto=True, verbose=False, sync=False)
@@ -129,6 +190,26 @@ def calibrate_optimize_clustergraph_(beliefs, schedule, R0, mu0, extra_rates=(),
             return np.inf
         out, info = beliefs.free_energy(all_sites=True)
         return np.inf if info[0] or not np.isfinite(out[0, 2]) else float(out[0, 2])
-    opt = _minimise(score, tf.forward(R0, mu0), maxiter)
+    memo = {}
+
+    def value_and_grad(theta):
+        key = np.asarray(theta, float).tobytes()
+        if key not in memo:
+            memo.clear()
+            f = score(theta)
+            g = np.zeros(len(theta))
+            if np.isfinite(f):
+                d = beliefs.gradient_lg(all_sites=True)    # (on the beliefs the calibration inside score() left)
+                if d["info"][0]:
+                    f = np.inf
+                else:
+                    g = -tf.pullback(theta, d["dR"][0, 0], d["dmu"][0])
+            memo[key] = (f, g)
+        return memo[key]
+    if gradient == "analytic":
+        opt = _minimise(lambda x: value_and_grad(x)[0], tf.forward(R0, mu0), maxiter, grad=lambda x: value_and_grad(x)[1])
+    else:
+        opt = _minimise(score, tf.forward(R0, mu0), maxiter)
+    opt.n_device_evals = count[0]
     R, mu = tf.back(opt.x)
     return R, mu, -float(opt.fun), opt
