@@ -346,6 +346,52 @@ int pgbp_bm_exact_stats(pgbp_engine* e, int32_t site_begin, int32_t site_end, do
  * whose family variance is not): that site's outputs are NaN. */
 int pgbp_lg_gradient(pgbp_engine* e, int32_t site_begin, int32_t site_end, double* dR, double* dmu, double* dalpha,
                      double* dtheta, int32_t* info);
+/* JOINT posterior draws of every cluster variable from CALIBRATED beliefs on a clique tree, for sites [site_begin, site_end):
+ * the joint is prod clusters / prod sepsets, and one preorder sweep of schedule tree `tree` (an index into the schedule given to
+ * pgbp_set_schedule, as pgbp_traverse's) that conditions each cluster on the sepset to its parent turns standard normals z
+ * into exact joint draws x.  The call knows nothing of the evolutionary model: beliefs, scopes and the schedule tree only.
+ * Layout: z and x are host pointers, [n_draws][site_end - site_begin][pgbp_sample_size]; cluster i's dims[i] variables sit at
+ * the cumulative offset of the cluster dimensions, clusters in index order, variables in the belief's own order
+ * (pgbp_sample_size: doubles per (draw, site) = the sum of the cluster dimensions; -1: no engine).
+ * Semantics: the parent -> child edges of the tree in its (preorder) order; for the root cluster S is empty; for a child
+ * cluster S = the child's variables the sepset to its parent maps to (the child side of that sepset's scope_idx), R = the
+ * rest of the child's variables in the child's order; x_S is copied from the parent's already drawn values (read through the
+ * parent side of the same scope_idx) and
+ *     x_R = J_RR^-1 (h_R - J_RS x_S) + L^-T z_R,     J_RR = L L', L LOWER triangular with a positive diagonal
+ * (the Cholesky factor of the R block in the child's variable order; the upper triangle of J is read), z_R = the entries of z
+ * at the positions of R: a caller can reproduce a draw from z.  Entries of z at S positions are ignored; a cluster of
+ * dimension 0 writes nothing; a sepset of dimension 0 makes the child an independent draw.
+ * Consequences: with z = 0 the result is the joint posterior mean; a variable held by several clusters has the same bits in all
+ * of them; THE RESULT IS A DRAW FROM THE JOINT POSTERIOR ONLY IF THE BELIEFS ARE CALIBRATED (postorder AND preorder) ON A CLIQUE
+ * TREE -- the call does not verify that, as pgbp_lg_gradient does not; the call is read-only on the beliefs and uses no
+ * atomics: two calls with the same z return the same bytes; the result for a (draw, site) does not depend on which other draws
+ * or sites are in the call.
+ * Device (csrc/pgbp_sample.hip): a FACTOR phase, one grid over (cluster, site), eliminates [J_RR | J_RS | h_R] in LDS with the
+ * arithmetic of pgbp_moments (at most 16 variables: four clusters per wavefront; 17 .. 64: a wavefront; 65 .. 128: a workgroup
+ * of 256 threads) and leaves a = J_RR^-1 h_R, G = J_RR^-1 J_RS and L^-T in a scratch pool no larger than the beliefs, for a chunk
+ * of sites at a time (256 MB at most) -- once, however many draws; an APPLY phase, one launch per preorder level over (cluster
+ * of the level, draw, variable) x site, x_R = a - G x_S + L^-T z_R with every sum in index order.  z goes up and x comes down
+ * as one copy each per chunk, behind one stream synchronisation.  Every layout (a site-minor univariate batch is converted to
+ * the plain one first, as pgbp_moments does).
+ * Fails before any launch with PGBP_ERR_STATE when no schedule has been set, with PGBP_ERR_INVALID when `tree` is out of range,
+ * when the tree does not span every cluster or the graph has a cycle (n_sepsets != n_clusters - 1: the sweep is exact on a
+ * clique tree only), for a cluster of more than 128 variables (the message names it, as pgbp_moments'), for n_draws < 1, a bad
+ * site range, z or x NULL.
+ * info[site - site_begin] (may be NULL): 0, or the 1-based index of the first cluster in preorder whose J_RR is not positive
+ * definite: all draws of that site are NaN; other sites are unaffected.  There is no random number generator on the device:
+ * the caller supplies z. */
+int     pgbp_sample_posterior(pgbp_engine* e, int32_t tree, int32_t site_begin, int32_t site_end, int32_t n_draws,
+                              const double* z, double* x, int32_t* info);
+int64_t pgbp_sample_size(pgbp_engine* e);
+/* Bounds of the scratch of pgbp_sample_posterior, process-wide, in doubles: the factor pool of a chunk of sites (default
+ * 32 Mi doubles = 256 MB) and the device copies of z and of x of a chunk of draws (default 128 Mi doubles = 1 GB each); a value
+ * <= 0 restores the default.  At least one site and one draw are always taken.  The results do not depend on the chunks (the
+ * tests cut a small batch into several to show it). */
+void    pgbp_sample_scratch_limits(int64_t factor_doubles, int64_t draw_doubles);
+/* The same call with the stream drained after each phase (measurement only: tools/time_sample.py): ms4[0 .. 3] = wall
+ * milliseconds of {factor phase, copy of z to the device, apply phase, copy of x to the host}, summed over the chunks. */
+int     pgbp_sample_posterior_timed(pgbp_engine* e, int32_t tree, int32_t site_begin, int32_t site_end, int32_t n_draws,
+                                    const double* z, double* x, int32_t* info, double* ms4);
 
 /* ---- scores (second "next" row: SURVEY.md section 8(f)-2) -------------------------------------- */
 /* free_energy(beliefs) (src/score.jl:162-182) for every site: out3[3*site + {0,1,2}] = (average energy,

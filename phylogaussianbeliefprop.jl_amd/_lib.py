@@ -122,6 +122,10 @@ SYMBOLS = {
     "pgbp_moments_size": (C.c_int64, [_P, C.c_int32, _I32P, C.c_int32]),
     "pgbp_bm_exact_stats": (C.c_int, [_P, C.c_int32, C.c_int32, _F64P, _F64P, _I32P]),
     "pgbp_lg_gradient": (C.c_int, [_P, C.c_int32, C.c_int32, _F64P, _F64P, _F64P, _F64P, _I32P]),
+    "pgbp_sample_posterior": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _F64P, _F64P, _I32P]),
+    "pgbp_sample_size": (C.c_int64, [_P]),
+    "pgbp_sample_scratch_limits": (None, [C.c_int64, C.c_int64]),
+    "pgbp_sample_posterior_timed": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _F64P, _F64P, _I32P, _F64P]),
     "pgbp_free_energy": (C.c_int, [_P, _F64P, _I32P]),
     "pgbp_bm_tree_setup": (C.c_int, [_P, C.POINTER(BmTree)]),
     "pgbp_bm_tree_assignfactors": (C.c_int, [_P, _F64P, _F64P, _F64P, C.c_int32]),

@@ -457,6 +457,53 @@ class ClusterGraphBelief:
             res.append((mu[0].copy(), None if Sig is None else Sig[0].copy(), float(norm[0])))
         return res
 
+    def sample_posterior_(self, n_draws=1, z=None, rng=None, schedule_tree=0, all_sites=False):
+        """Joint posterior draws of every cluster variable in ONE device call (pgbp_sample_posterior): a preorder sweep of
+        schedule tree `schedule_tree` (an index into the schedule that was set, as pgbp_traverse's `tree`) that conditions
+        each cluster on the sepset to its parent.  A draw from the joint posterior only if the beliefs are calibrated
+        (postorder and preorder) on a clique tree; the call does not verify that.
+        z: standard normals [n_draws, n_sites or 1, size] (size = the sum of the cluster dimensions); None: drawn with
+        numpy.random.default_rng(rng).  z = 0 gives the joint posterior mean.
+        Returns (x, info, views): x [n_draws, n_sites or 1, size] (all_sites: every site, otherwise the current one),
+        info [n_sites or 1] (0, or the 1-based index of the first cluster in preorder whose conditional precision is not
+        positive definite: that site's draws are NaN) and views[i] = x[:, :, cluster i's variables]."""
+        size = int(self._lib.pgbp_sample_size(self._eng))
+        s0, s1 = (0, self.n_sites) if all_sites else (self.site, self.site + 1)
+        n_draws = int(n_draws)
+        shape = (max(n_draws, 0), s1 - s0, size)
+        if z is None:
+            z = np.random.default_rng(rng).standard_normal(shape)
+        z = np.ascontiguousarray(z, dtype=np.float64)
+        if z.shape != shape:
+            raise ValueError(f"z has shape {z.shape}, expected {shape}")
+        x = np.zeros(shape)
+        info = np.zeros(s1 - s0, dtype=np.int32)
+        keep = z if z.size else np.zeros(1)
+        out = x if x.size else np.zeros(1)
+        _check(self._lib.pgbp_sample_posterior(self._eng, int(schedule_tree), s0, s1, n_draws, L.f64p(keep), L.f64p(out),
+                                               L.i32p(info)), self._eng)
+        off = np.concatenate([[0], np.cumsum(self._dims[: self.nclusters].astype(np.int64))])
+        return x, info, [x[:, :, off[i]: off[i + 1]] for i in range(self.nclusters)]
+
+    def node_samples(self, draws, site=0):
+        """The draws of sample_posterior_ by node, for an object built from labelled beliefs: {node label: [n_draws, p]},
+        the traits of a node that are out of scope NaN, the values taken from the first cluster that holds the node.
+        draws: x [n_draws, sites, size]; site: which of its site columns."""
+        if self._objs is None:
+            raise ValueError("node_samples needs labelled beliefs (an object built from CanonicalBelief objects)")
+        draws = np.asarray(draws)
+        out, at = {}, 0
+        for b in self._objs[: self.nclusters]:
+            insc = np.asarray(b.inscope, dtype=bool)
+            for k, lab in enumerate(b.nodelabel):
+                n = int(insc[:, k].sum())
+                if lab not in out:
+                    v = np.full((draws.shape[0], insc.shape[0]), np.nan)
+                    v[:, insc[:, k]] = draws[:, site, at: at + n]
+                    out[lab] = v
+                at += n
+        return out
+
     def default_sepset1(self):
         """default_sepset1 (src/clustergraphbeliefs.jl:197-202)."""
         for j in range(self.nclusters, self.nbeliefs):

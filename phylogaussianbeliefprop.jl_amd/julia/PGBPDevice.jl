@@ -258,6 +258,32 @@ function lg_gradient(o::DeviceClusterGraphBelief, p::Integer, nrates::Integer; o
     return (reshape(dR, p, p, nrates), dmu, dalpha[], dtheta)
 end
 
+"""
+    sample_size(obj) -> Int
+
+Doubles per draw of `sample_posterior!`: the sum of the cluster dimensions (pgbp_sample_size).
+"""
+sample_size(o::DeviceClusterGraphBelief) = Int(@ccall LIB.pgbp_sample_size(o.handle::Ptr{Cvoid})::Int64)
+
+"""
+    sample_posterior!(obj, ndraws = 1; z = randn(sample_size(obj), ndraws), tree = 1) -> x
+
+Joint posterior draws of every cluster variable from the current beliefs (pgbp_sample_posterior): one preorder sweep of schedule
+tree `tree` (1-based, into the schedule given to `set_schedule!`) that conditions each cluster on the sepset to its parent.
+Column d of `x` is draw d: cluster i's variables at the cumulative offset of the cluster dimensions, in the belief's own order;
+`z = 0` gives the joint posterior mean.  A draw from the joint posterior only when the beliefs are calibrated (postorder and
+preorder) on a clique tree; the call does not verify that.  A cluster whose conditional precision is not positive definite
+throws its PosDefException (info = the cluster's index).
+"""
+function sample_posterior!(o::DeviceClusterGraphBelief, ndraws::Integer = 1;
+                           z::AbstractMatrix{Float64} = randn(sample_size(o), ndraws), tree::Integer = 1)
+    size(z) == (sample_size(o), ndraws) || error("z must be sample_size(obj) x ndraws")
+    zz = Matrix{Float64}(z); x = zeros(max(sample_size(o), 1), ndraws); info = Ref(Int32(0))
+    check(o.handle, @ccall LIB.pgbp_sample_posterior(o.handle::Ptr{Cvoid}, (tree-1)::Int32, Int32(0)::Int32, Int32(1)::Int32, ndraws::Int32, zz::Ptr{Float64}, x::Ptr{Float64}, info::Ref{Int32})::Cint)
+    info[] == 0 || throw(PGBP.LA.PosDefException(info[]))
+    return x[1:sample_size(o), :]
+end
+
 "the reference's error line for a failed message (src/beliefupdates.jl:69-76): belief metadata + integrated indices"
 function report_failure(o::DeviceClusterGraphBelief, spt, res::Result, verbose::Bool)
     i = res.fail_edge + 1
