@@ -47,6 +47,13 @@ def main():
           + ("" if exact else "  (loopy graph: approximations)"))
     if exact:
         assert abs(norm - g["ll"]) <= 1e-9 * abs(g["ll"])
+        # leave-one-out cross-validation from the same calibration: how well do the other tips predict each tip?
+        loo = cgb.loo_lg()
+        z = P.loo_zscores(loo)[:, 0]
+        worst = int(np.nanargmax(np.abs(z)))
+        tip = g["taxa"][int(cgb._lg["data_row"][loo["families"][worst]])]
+        print(f"leave-one-out: summed log predictive density {loo['total']:.6f}; largest |z| {abs(z[worst]):.3f} at tip {tip} "
+              f"(observed {loo['y'][worst, 0]:.4f}, predicted {loo['mean'][worst, 0]:.4f} +- {np.sqrt(loo['cov'][worst, 0, 0]):.4f})")
 
 
 if __name__ == "__main__":

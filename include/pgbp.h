@@ -346,6 +346,49 @@ int pgbp_bm_exact_stats(pgbp_engine* e, int32_t site_begin, int32_t site_end, do
  * whose family variance is not): that site's outputs are NaN. */
 int pgbp_lg_gradient(pgbp_engine* e, int32_t site_begin, int32_t site_end, double* dR, double* dmu, double* dalpha,
                      double* dtheta, int32_t* info);
+/* LEAVE-ONE-OUT predictive moments of every tip from the CURRENT beliefs, for sites [site_begin, site_end): for each tip family
+ * of the table given to pgbp_lg_setup (child_pos < 0, data_row >= 0, at least one observed trait: O = child_mask, o = |O|), the
+ * distribution of the tip's observed values y_O given the data of all OTHER tips, with the parameters the engine kept from the
+ * last pgbp_lg_assignfactors (shared or per site: a per-site engine returns each site's own prediction).
+ * THE RESULT IS THE EXACT LEAVE-ONE-OUT PREDICTIVE ONLY WHEN THE BELIEFS ARE CALIBRATED (postorder AND preorder) ON A CLIQUE TREE
+ * UNDER THE PARAMETERS OF THE LAST pgbp_lg_assignfactors; the call does not verify that.  On a loopy cluster graph the same sweep
+ * on the beliefs of a CONVERGED calibration is the Bethe approximation of it; before convergence it is neither.
+ * Per tip family (notation of pgbp_lg_params): the tip's factor is N(y_O; u + w, V) with u = (sum_k qc_k x_k)_O the parents'
+ * contribution (a fixed-root parent: its constant), w = (sum_k wc_k theta)_O, V = (sum_k vc_k R[colour_k])_OO.  With
+ * m_u = E[u], S = Cov(u) from the cluster's J^-1 h and J^-1 (S = 0 when no parent is in scope) and r = y_O - w - m_u:
+ *     D = V - S,   cov = V D^-1 V,   mean = y_O - V D^-1 r,
+ *     lpd = -(o log 2pi + 2 log det V - log det D + r' D^-1 r) / 2      (the log predictive density of y_O).
+ * pgbp_lg_loo_count: the number n_tip of tip families (-1: no family table); pgbp_lg_loo_families: their indices into the
+ * family table, in order -- the order of every output.  Outputs, site-major:
+ *   mean  [sites][n_tip][p]    NaN at the unobserved traits; may be NULL;
+ *   cov   [sites][n_tip][p*p]  column-major, symmetric, both triangles written, NaN rows / columns at the unobserved traits;
+ *                              may be NULL;
+ *   lpd   [sites][n_tip];
+ *   total [sites]: the sum of lpd in tip-family order (thread r of 256 adds the tips r, r + 256, ... in order, the partial sums
+ *         are added by a fixed tree); may be NULL;
+ *   info  [sites][n_tip] (may be NULL): 0; 1 when D (or V) is not positive definite -- the other data leave u undetermined: an
+ *         improper root with no other informative tip, an improper cavity; a pivot of D's factorisation that is not above
+ *         2^-40 times V's diagonal entry counts as not positive (D is formed by cancellation: below that it is rounding
+ *         noise), as does a cluster whose belief is the constant 1 --; or 1 + PosDefException.info of the cluster.  Where
+ *         info is not 0 that tip's mean, cov and lpd are NaN and so is the site's total; other tips and sites are unaffected.
+ * Device (csrc/pgbp_loo.hip): one workgroup per (tip family, site) solves the family's cluster in LDS (the solve of
+ * pgbp_moments), forms V, D and the right-hand sides [V | r], factorises D and V by Cholesky and writes its outputs; a second
+ * kernel adds the site's total.  No atomics, every sum in index order: two calls return the same bytes, and the result for a
+ * site does not depend on which other sites are in the call.  The device copies of the outputs of a chunk of sites at a time
+ * (256 MB at most; pgbp_loo_scratch_limit: that bound in doubles, process-wide, <= 0 restores the default -- the results do
+ * not depend on the chunks).  Read-only on the beliefs; every layout (a site-minor univariate batch is converted to the plain
+ * layout first, as pgbp_bm_exact_stats does); one stream synchronisation per call.
+ * Fails before any launch with PGBP_ERR_STATE without a family table or before the first pgbp_lg_assignfactors, with
+ * PGBP_ERR_INVALID for a site range out of bounds, for lpd NULL, for a family whose cluster has more than 128 variables
+ * (the message names the family and the cluster), and when the largest cluster's working matrix plus the 3 p x p scratch
+ * exceed the 160 KB of LDS -- the limits of pgbp_lg_gradient, taken as there over the clusters of ALL families of the table:
+ * an engine serves both sweeps or neither (the tip families' own clusters are small; the limit is conservative for them).
+ * A table without tip families returns PGBP_OK and writes only total = 0. */
+int32_t pgbp_lg_loo_count(pgbp_engine* e);
+int     pgbp_lg_loo_families(pgbp_engine* e, int32_t* fam);
+int     pgbp_lg_loo(pgbp_engine* e, int32_t site_begin, int32_t site_end, double* mean, double* cov, double* lpd,
+                    double* total, int32_t* info);
+void    pgbp_loo_scratch_limit(int64_t doubles);
 /* JOINT posterior draws of every cluster variable from CALIBRATED beliefs on a clique tree, for sites [site_begin, site_end):
  * the joint is prod clusters / prod sepsets, and one preorder sweep of schedule tree `tree` (an index into the schedule given to
  * pgbp_set_schedule, as pgbp_traverse's) that conditions each cluster on the sepset to its parent turns standard normals z

@@ -671,11 +671,81 @@ class ClusterGraphBelief:
             return norm, grad
         return float(norm[self.site]), self._gradient_of_site(grad, self.site)
 
+    def loo_lg(self, all_sites=False):
+        """pgbp_lg_loo on the current beliefs: the leave-one-out predictive distribution of every tip that has data, given
+        the data of all other tips, under the parameters of the last assignfactors_lg_ -- one sweep over the tip families.
+        EXACT ONLY when the beliefs are calibrated (postorder and preorder) on a clique tree under those parameters (not
+        verified); on a loopy cluster graph, at a converged calibration, it is the Bethe approximation.
+        Returns a dict: families [n_tip] (indices into the family table given to lg_setup, the order of every other entry),
+        mean [n_tip, p] and cov [n_tip, p, p] (NaN at unobserved traits), lpd [n_tip] (log predictive density of the tip's
+        observed values), total (their sum in family order), info [n_tip] (0; 1: the other data do not determine the
+        prediction; 1 + PosDefException.info of the cluster -- that tip's entries and total are NaN, nothing raises) and
+        y [n_tip, p] (the tip's data row, for loo_zscores); with a leading site axis when all_sites."""
+        p = self._lg_p
+        nt = int(self._lib.pgbp_lg_loo_count(self._eng))
+        if nt < 0:
+            _check(self._lib.pgbp_lg_loo(self._eng, 0, 0, None, None, None, None, None), self._eng)
+            raise L.PgbpError(L.ERR_STATE, "pgbp_lg_loo_count failed")
+        fam = np.zeros(max(nt, 1), dtype=np.int32)
+        _check(self._lib.pgbp_lg_loo_families(self._eng, L.i32p(fam)), self._eng)
+        fam = fam[:nt]
+        s0, s1 = (0, self.n_sites) if all_sites else (self.site, self.site + 1)
+        n = s1 - s0
+        mean = np.zeros((n, max(nt, 1), p))
+        cov = np.zeros((n, max(nt, 1), p, p))
+        lpd = np.zeros((n, max(nt, 1)))
+        total = np.zeros(n)
+        info = np.zeros((n, max(nt, 1)), dtype=np.int32)
+        _check(self._lib.pgbp_lg_loo(self._eng, s0, s1, L.f64p(mean), L.f64p(cov), L.f64p(lpd), L.f64p(total), L.i32p(info)),
+               self._eng)
+        y = self._lg["data"][s0:s1][:, self._lg["data_row"][fam]]
+        d = dict(families=fam, mean=mean[:, :nt], cov=cov[:, :nt].transpose(0, 1, 3, 2), lpd=lpd[:, :nt], total=total,
+                 info=info[:, :nt], y=y)
+        if all_sites:
+            return d
+        return {k: (v if k == "families" else (float(v[0]) if k == "total" else v[0].copy())) for k, v in d.items()}
+
+    def loo_and_loglik_lg(self, schedule_tree, all_sites=False):
+        """Log-likelihood and the leave-one-out predictions of every tip under the parameters of the last assignfactors_lg_
+        on a clique tree: beliefs reset from the factors that call filled -> one calibrate (postorder + preorder of
+        `schedule_tree`) -> integratebelief! at the tree's root cluster -> the sweep over the tip families (loo_lg), as
+        loglik_and_gradient_lg does for the gradient.  Returns (loglik, loo dict): the current site's values, or arrays over
+        the sites when all_sites (loglik of a site whose calibration failed is NaN)."""
+        self._ensure_schedule([schedule_tree])
+        o = self._opts()
+        pa = np.asarray(schedule_tree[-2]).reshape(-1)
+        root = int(pa[0]) if pa.size else 0
+        _check(self._lib.pgbp_enqueue_calibrate(self._eng, 1, 1, C.byref(o)), self._eng)
+        _check(self._lib.pgbp_enqueue_integrate(self._eng, root), self._eng)
+        loo = self.loo_lg(all_sites=True)
+        norm = np.zeros(self.n_sites)
+        info = np.zeros(self.n_sites, dtype=np.int32)
+        _check(self._lib.pgbp_fetch_loglik(self._eng, L.f64p(norm), L.i32p(info)), self._eng)
+        norm = np.where(info != 0, np.nan, norm)
+        if all_sites:
+            return norm, loo
+        s = self.site
+        return float(norm[s]), {k: (v if k == "families" else (float(v[s]) if k == "total" else v[s].copy()))
+                                for k, v in loo.items()}
+
     def traffic_model(self):
         b = C.c_double()
         n = C.c_int64()
         _check(self._lib.pgbp_traffic_model(self._eng, C.byref(b), C.byref(n)), self._eng)
         return b.value, n.value
+
+
+def loo_zscores(d):
+    """Standardised leave-one-out residuals of the dict loo_lg returns: per tip z = L^-1 (y - mean) over its observed traits,
+    cov = L L' (L lower triangular), so that z is standard normal under the model; NaN at unobserved traits and for a tip
+    whose info is not 0.  Shape of d["mean"].  On the host."""
+    mean, cov, y = np.asarray(d["mean"]), np.asarray(d["cov"]), np.asarray(d["y"])
+    z = np.full(mean.shape, np.nan)
+    for ix in np.ndindex(mean.shape[:-1]):
+        o = np.isfinite(mean[ix])
+        if o.any():
+            z[ix][o] = np.linalg.solve(np.linalg.cholesky(cov[ix][np.ix_(o, o)]), (y[ix] - mean[ix])[o])
+    return z
 
 
 class _ResidualDict:

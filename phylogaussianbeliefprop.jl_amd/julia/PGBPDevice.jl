@@ -259,6 +259,38 @@ function lg_gradient(o::DeviceClusterGraphBelief, p::Integer, nrates::Integer; o
 end
 
 """
+    lg_loo_families(obj) -> Vector{Int}
+
+The tip families of the table given to pgbp_lg_setup (1-based indices into it), in the order of `lg_loo`'s outputs
+(pgbp_lg_loo_count, pgbp_lg_loo_families).
+"""
+function lg_loo_families(o::DeviceClusterGraphBelief)
+    n = @ccall LIB.pgbp_lg_loo_count(o.handle::Ptr{Cvoid})::Int32
+    n >= 0 || error("pgbp_lg_loo_count: no family table (call pgbp_lg_setup first)")
+    fam = zeros(Int32, max(n, 1))
+    check(o.handle, @ccall LIB.pgbp_lg_loo_families(o.handle::Ptr{Cvoid}, fam::Ptr{Int32})::Cint)
+    return Int.(fam[1:n]) .+ 1
+end
+
+"""
+    lg_loo(obj, p) -> (mean, cov, lpd, total, info)
+
+Leave-one-out predictive moments of every tip with data, given the data of all other tips, from the current beliefs
+(pgbp_lg_loo: one sweep over the tip families).  Exact only when the beliefs are calibrated (postorder and preorder) on a clique
+tree under the parameters of the last pgbp_lg_assignfactors; on a loopy graph, at a converged calibration, the Bethe
+approximation.  `mean[:, i]` and `cov[:, :, i]` of tip family i (`lg_loo_families`) are NaN at its unobserved traits; `lpd[i]` is
+the log predictive density of its observed values, `total` their sum; `info[i]` is 0, 1 when the other data do not determine
+the prediction, or 1 + PosDefException.info of the cluster (that tip's values are NaN; nothing is thrown).
+"""
+function lg_loo(o::DeviceClusterGraphBelief, p::Integer)
+    n = length(lg_loo_families(o))
+    mean = zeros(p, max(n, 1)); cov = zeros(p, p, max(n, 1)); lpd = zeros(max(n, 1)); total = Ref(0.0)
+    info = zeros(Int32, max(n, 1))
+    check(o.handle, @ccall LIB.pgbp_lg_loo(o.handle::Ptr{Cvoid}, Int32(0)::Int32, Int32(1)::Int32, mean::Ptr{Float64}, cov::Ptr{Float64}, lpd::Ptr{Float64}, total::Ref{Float64}, info::Ptr{Int32})::Cint)
+    return (mean[:, 1:n], cov[:, :, 1:n], lpd[1:n], total[], info[1:n])
+end
+
+"""
     sample_size(obj) -> Int
 
 Doubles per draw of `sample_posterior!`: the sum of the cluster dimensions (pgbp_sample_size).
