@@ -23,6 +23,7 @@
 #include <thread>
 #include <vector>
 
+#include "pgbp_devmem.hpp"
 #include "pgbp_internal.hpp"
 #include "pgbp_kernels.hpp"
 
@@ -448,9 +449,9 @@ thread_local std::string g_comm_create_error;
 struct pgbp_comm {
   ncclComm_t comm = nullptr;
   int32_t n_ranks = 1, rank = 0, device = 0;
-  double* d_recv = nullptr;
+  pgbp::DevBuf<double> d_recv;
   int64_t recv_cap = 0;
-  double* d_send = nullptr;    // send slot of pgbp_comm_exchange_beliefs
+  pgbp::DevBuf<double> d_send;    // send slot of pgbp_comm_exchange_beliefs
   int64_t send_cap = 0;
   std::vector<double> h_recv;
   std::string err;
@@ -545,8 +546,8 @@ int pgbp_comm_create(const uint8_t* id128, int32_t n_ranks, int32_t rank, int32_
 void pgbp_comm_destroy(pgbp_comm* c) {
   if (!c) return;
   (void)hipSetDevice(c->device);
-  if (c->d_recv) (void)hipFree(c->d_recv);
-  if (c->d_send) (void)hipFree(c->d_send);
+  c->d_recv.reset();   // (ahead of the communicator, as ever)
+  c->d_send.reset();
   if (c->comm) (void)rccl().comm_destroy(c->comm);
   delete c;
 }
@@ -568,10 +569,8 @@ int pgbp_comm_gather_loglik(pgbp_comm* c, pgbp_engine* e, int32_t slot_sites, do
   }
   const int64_t slot = 2 * (int64_t)slot_sites + 2, total = slot * c->n_ranks;
   if (total > c->recv_cap) {
-    if (c->d_recv) (void)hipFree(c->d_recv);
-    c->d_recv = nullptr;
     c->recv_cap = 0;
-    if (hipMalloc(reinterpret_cast<void**>(&c->d_recv), sizeof(double) * (size_t)total) != hipSuccess) {
+    if (c->d_recv.alloc((size_t)total) != 0) {
       c->err = "hipMalloc of the gather buffer failed";
       return PGBP_ERR_HIP;
     }
@@ -579,13 +578,13 @@ int pgbp_comm_gather_loglik(pgbp_comm* c, pgbp_engine* e, int32_t slot_sites, do
   }
   // THE collective of the site-sharded path: one all-gather on the engine's stream, behind the kernels that produced
   // the log-likelihoods (no host synchronisation in between)
-  const ncclResult_t nrc = rccl().all_gather(d_slot, c->d_recv, (size_t)slot, ncclFloat64, c->comm, st);
+  const ncclResult_t nrc = rccl().all_gather(d_slot, c->d_recv.get(), (size_t)slot, ncclFloat64, c->comm, st);
   if (nrc != ncclSuccess) {
     c->err = std::string("ncclAllGather: ") + rccl().error_string(nrc);
     return PGBP_ERR_HIP;
   }
   c->h_recv.resize((size_t)total);
-  if (hipMemcpyAsync(c->h_recv.data(), c->d_recv, sizeof(double) * (size_t)total, hipMemcpyDeviceToHost, st) != hipSuccess ||
+  if (hipMemcpyAsync(c->h_recv.data(), c->d_recv.get(), sizeof(double) * (size_t)total, hipMemcpyDeviceToHost, st) != hipSuccess ||
       hipStreamSynchronize(st) != hipSuccess) {
     c->err = "copy of the gathered log-likelihoods failed";
     return PGBP_ERR_HIP;
@@ -622,27 +621,25 @@ int pgbp_comm_exchange_beliefs(pgbp_comm* c, pgbp_engine* e, int32_t site, const
   }
   if (slot == 0) return PGBP_OK;
   (void)hipSetDevice(c->device);
-  auto grow = [&](double** buf, int64_t* cap, int64_t need) {
+  auto grow = [&](pgbp::DevBuf<double>& buf, int64_t* cap, int64_t need) {
     if (need <= *cap) return true;
-    if (*buf) (void)hipFree(*buf);
-    *buf = nullptr;
     *cap = 0;
-    if (hipMalloc(reinterpret_cast<void**>(buf), sizeof(double) * (size_t)need) != hipSuccess) return false;
+    if (buf.alloc((size_t)need) != 0) return false;
     *cap = need;
     return true;
   };
-  if (!grow(&c->d_send, &c->send_cap, slot) || !grow(&c->d_recv, &c->recv_cap, slot * c->n_ranks)) {
+  if (!grow(c->d_send, &c->send_cap, slot) || !grow(c->d_recv, &c->recv_cap, slot * c->n_ranks)) {
     c->err = "hipMalloc of the exchange buffers failed";
     return PGBP_ERR_HIP;
   }
   hipStream_t st = nullptr;
   int rc = pgbp::engine_pack_records_device(e, site, list_off[c->rank + 1] - list_off[c->rank], lists + list_off[c->rank],
-                                            c->d_send, 1, &st, nullptr);
+                                            c->d_send.get(), 1, &st, nullptr);
   if (rc) {
     c->err = pgbp_last_error(e);
     return rc;
   }
-  const ncclResult_t nrc = rccl().all_gather(c->d_send, c->d_recv, (size_t)slot, ncclFloat64, c->comm, st);
+  const ncclResult_t nrc = rccl().all_gather(c->d_send.get(), c->d_recv.get(), (size_t)slot, ncclFloat64, c->comm, st);
   if (nrc != ncclSuccess) {
     c->err = std::string("ncclAllGather: ") + rccl().error_string(nrc);
     return PGBP_ERR_HIP;
@@ -650,7 +647,7 @@ int pgbp_comm_exchange_beliefs(pgbp_comm* c, pgbp_engine* e, int32_t site, const
   for (int r = 0; r < c->n_ranks; ++r) {
     if ((r == c->rank && !include_self) || size[r] == 0) continue;
     rc = pgbp::engine_pack_records_device(e, site, list_off[r + 1] - list_off[r], lists + list_off[r],
-                                          c->d_recv + (int64_t)r * slot, 0, nullptr, nullptr);
+                                          c->d_recv.get() + (int64_t)r * slot, 0, nullptr, nullptr);
     if (rc) {
       c->err = pgbp_last_error(e);
       return rc;

@@ -13,6 +13,7 @@
 #include <string>
 #include <vector>
 
+#include "pgbp_devmem.hpp"
 #include "pgbp_internal.hpp"
 #include "pgbp_kernels.hpp"
 
@@ -31,110 +32,153 @@ thread_local std::string g_create_error;  // (per thread: pgbp_group creates its
 __attribute__((constructor(101))) void pgbp_default_environment() { setenv("HIP_FORCE_DEV_KERNARG", "1", 0); }
 
 struct DevTraversal {
-  int32_t* d_task_off = nullptr;
-  Entry* d_entries = nullptr;
-  URec* d_urecs = nullptr;           // the entries as self-contained records (plans of univariate site batches: bp_level_uni1)
-  FEntry* d_fentries = nullptr;
-  FPro* d_fpros = nullptr;           // Traversal::fpros / cpros (null: no record of the traversal has a prologue)
-  FPro* d_cpros = nullptr;
-  FEntry* d_centries = nullptr;      // Traversal::centries: the groups of the chunks of fused levels
-  int32_t* d_chunk_wg_off = nullptr; // Traversal::chunk_wg_off
-  int32_t* d_cgroups = nullptr;      // Traversal::cgroups as first records of the tasks (Traversal::task_grec)
-  int32_t* d_cgroups_task = nullptr; // Traversal::cgroups as they are (task ids): the thread-per-site chunk kernel
-  GRec* d_grecs = nullptr;           // Traversal::grecs
-  int32_t* d_rowmap = nullptr;       // Traversal::rowmap
+  DevBuf<int32_t> d_task_off;
+  DevBuf<Entry> d_entries;
+  DevBuf<URec> d_urecs;           // the entries as self-contained records (plans of univariate site batches: bp_level_uni1)
+  DevBuf<FEntry> d_fentries;
+  DevBuf<FPro> d_fpros;           // Traversal::fpros / cpros (null: no record of the traversal has a prologue)
+  DevBuf<FPro> d_cpros;
+  DevBuf<FEntry> d_centries;      // Traversal::centries: the groups of the chunks of fused levels
+  DevBuf<int32_t> d_chunk_wg_off; // Traversal::chunk_wg_off
+  DevBuf<int32_t> d_cgroups;      // Traversal::cgroups as first records of the tasks (Traversal::task_grec)
+  DevBuf<int32_t> d_cgroups_task; // Traversal::cgroups as they are (task ids): the thread-per-site chunk kernel
+  DevBuf<GRec> d_grecs;           // Traversal::grecs
+  DevBuf<int32_t> d_rowmap;       // Traversal::rowmap
   // residual_kldiv! of sepsets beyond the LDS instance (kKlLdsMaxS): the entries concerned, ascending (device copy + host copy)
-  int32_t* d_kl_big = nullptr;
+  DevBuf<int32_t> d_kl_big;
   std::vector<int32_t> kl_big;
 };
 
+// The engine's stream.  Declared ahead of every buffer of pgbp_engine, so that it is destroyed after all of them.
+struct StreamOwner {
+  hipStream_t s = nullptr;
+  StreamOwner() = default;
+  StreamOwner(const StreamOwner&) = delete;
+  StreamOwner& operator=(const StreamOwner&) = delete;
+  ~StreamOwner() { if (s) (void)hipStreamDestroy(s); }
+  operator hipStream_t() const { return s; }
+};
+
+// Buffers that exist together or not at all: a set-up fills a local group and the engine takes it whole.
+// the site-minor copies of the pools and the twins of the per-message / per-cluster word arrays
+struct SmBufs {
+  DevBuf<double> pool, fpool, rpool, kldiv;
+  DevBuf<int32_t> flags, status, klflags, poison;
+};
+// pgbp_bm_tree; data_sm: [row][site] copy of data (p = 1, else null); ithl: [n_clusters] (1 / t, (p / 2) log t) of launch_bm_ithl
+struct BmBufs {
+  DevBuf<int32_t> kind, row;
+  DevBuf<double> length, data, data_sm, Rinv, logdet, mu;
+  DevBuf<double2> ithl;
+};
+// the levelled walk of pgbp_regularize_onschedule (OnSchedule)
+struct OsBufs {
+  DevBuf<int32_t> a_cl, ed_off, ed_msg, task_off;
+  DevBuf<GRec> grecs;
+  DevBuf<Entry> entries;
+};
+// what LgStatic points at: the family table of pgbp_lg_setup and the parameter slots pgbp_lg_assignfactors fills
+struct LgBufs {
+  DevBuf<int32_t> off, fam, np, cp, row, pp, col;
+  DevBuf<double> len, gam, data, data_sm;
+  DevBuf<unsigned long long> cm, pm;
+  DevBuf<LgSimpleFam> simple;
+  DevBuf<double> R, alpha, theta, mu;
+};
+
+hipEvent_t hip_event(void* ev) { return static_cast<hipEvent_t>(ev); }
+
 }  // namespace
+
+// the two doors of pgbp_devmem.hpp to device memory, and the two to events
+int pgbp::dev_malloc_bytes(void** p, size_t bytes) { return (int)hipMalloc(p, bytes); }
+void pgbp::dev_free_bytes(void* p) { (void)hipFree(p); }
+int pgbp::dev_event_create(void** ev) {
+  hipEvent_t h = nullptr;
+  const hipError_t rc = hipEventCreate(&h);
+  *ev = rc == hipSuccess ? h : nullptr;
+  return (int)rc;
+}
+void pgbp::dev_event_destroy(void* ev) { (void)hipEventDestroy(hip_event(ev)); }
 
 struct pgbp_engine {
   Plan plan;
-  hipStream_t st = nullptr;
+  StreamOwner st;   // (first: see StreamOwner)
   // the KL flags and divergences are as the last reset left them (nothing computed a KL residual since): the next reset of
   // the message flags leaves them alone (two of its three arrays; cfg4: 2.6 GB a call)
   bool kl_flags_clean = false, kl_div_clean = false;
   // device state
-  double* d_pool = nullptr;    // [n_sites][pool_stride] beliefs
-  double* d_fpool = nullptr;   // [n_sites][cluster_stride] factors
-  double* d_rpool = nullptr;   // [n_sites][rpool_stride] residuals
-  MsgDesc* d_msgs = nullptr;
-  int32_t* d_idx = nullptr;
-  int32_t* d_flags = nullptr;
-  int32_t* d_status = nullptr;
-  double* d_kldiv = nullptr;
-  int32_t* d_klflags = nullptr;     // [n_sites][n_msgs] iscalibrated_kl
-  int32_t* d_nb_off = nullptr;      // [n_clusters+1] -> d_nb_msg: the messages each cluster sends (regularisers)
-  int32_t* d_nb_msg = nullptr;
-  int32_t* d_sepcl = nullptr;       // [2*n_sepsets] sepset -> its two clusters
-  double* d_eps = nullptr;          // [n_sites][n_clusters] regularisation scratch
-  double* d_thr = nullptr;          // DevState::thr: residual-norm thresholds of the current tolerance
-  double* d_logtab = nullptr;       // DevState::logtab
+  DevBuf<double> d_pool;    // [n_sites][pool_stride] beliefs
+  DevBuf<double> d_fpool;   // [n_sites][cluster_stride] factors
+  DevBuf<double> d_rpool;   // [n_sites][rpool_stride] residuals
+  DevBuf<MsgDesc> d_msgs;
+  DevBuf<int32_t> d_idx;
+  DevBuf<int32_t> d_flags;
+  DevBuf<int32_t> d_status;
+  DevBuf<double> d_kldiv;
+  DevBuf<int32_t> d_klflags;     // [n_sites][n_msgs] iscalibrated_kl
+  DevBuf<int32_t> d_nb_off;      // [n_clusters+1] -> d_nb_msg: the messages each cluster sends (regularisers)
+  DevBuf<int32_t> d_nb_msg;
+  DevBuf<int32_t> d_sepcl;       // [2*n_sepsets] sepset -> its two clusters
+  DevBuf<double> d_eps;          // [n_sites][n_clusters] regularisation scratch
+  DevBuf<double> d_thr;          // DevState::thr: residual-norm thresholds of the current tolerance
+  DevBuf<double> d_logtab;       // DevState::logtab
   std::vector<double> h_thr;
   double thr_atol = 0.0;
   bool thr_valid = false;
-  unsigned long long* d_fail = nullptr;
-  int32_t* d_poison = nullptr;      // [n_sites][n_clusters]
-  int32_t* d_iscal = nullptr;       // [n_sites]
-  int32_t* d_notcal = nullptr;      // [n_sites] DevState::notcal
-  int32_t* d_iscal_hist = nullptr;  // [hist_cap][n_sites]
+  DevBuf<unsigned long long> d_fail;
+  DevBuf<int32_t> d_poison;      // [n_sites][n_clusters]
+  DevBuf<int32_t> d_iscal;       // [n_sites]
+  DevBuf<int32_t> d_notcal;      // [n_sites] DevState::notcal
+  DevBuf<int32_t> d_iscal_hist;  // [hist_cap][n_sites]
   int64_t hist_cap = 0;
-  int64_t* d_boff = nullptr;        // record offset tables for pack/unpack
-  int64_t* d_packed_off = nullptr;
-  int64_t* d_roff = nullptr;
-  int64_t* d_rpacked_off = nullptr;
-  double* d_mu = nullptr;    // [n_sites][max_dim]
-  double* d_norm = nullptr;  // [n_sites]
-  int32_t* d_info = nullptr; // [n_sites]
-  int32_t* d_bdim = nullptr;        // [n_beliefs] dims (layout conversion)
-  int32_t* d_rdim = nullptr;        // [n_msgs] sepset dim of every directed message
-  int32_t* d_symflag = nullptr;     // != 0: some precision matrix is not symmetric
+  DevBuf<int64_t> d_boff;        // record offset tables for pack/unpack
+  DevBuf<int64_t> d_packed_off;
+  DevBuf<int64_t> d_roff;
+  DevBuf<int64_t> d_rpacked_off;
+  DevBuf<double> d_mu;    // [n_sites][max_dim]
+  DevBuf<double> d_norm;  // [n_sites]
+  DevBuf<int32_t> d_info; // [n_sites]
+  DevBuf<int32_t> d_bdim;        // [n_beliefs] dims (layout conversion)
+  DevBuf<int32_t> d_rdim;        // [n_msgs] sepset dim of every directed message
+  DevBuf<int32_t> d_symflag;     // != 0: some precision matrix is not symmetric
   int32_t max_s = 0;                // largest sepset dimension
-  // site-minor copies of the pools (univariate batches: every dimension <= 2), allocated at first use
-  double *d_pool_sm = nullptr, *d_fpool_sm = nullptr, *d_rpool_sm = nullptr;
-  // second copies of the per-message / per-cluster word arrays: a layout switch transposes into them and swaps
-  int32_t *d_flags_alt = nullptr, *d_status_alt = nullptr, *d_klflags_alt = nullptr, *d_poison_alt = nullptr;
-  double* d_kldiv_alt = nullptr;
+  // site-minor copies of the pools (univariate batches: every dimension <= 2), allocated at first use, and second copies of
+  // the per-message / per-cluster word arrays: a layout switch transposes into them and swaps
+  SmBufs sm;
   bool layout_sm = false;           // the live state is in the site-minor buffers
   bool layout_bs16 = false;         // current device layout of 16/32-dim beliefs and 16-dim residuals
   bool sym_known = false, sym_ok = false;
   // pgbp_regularize_onschedule: the levelled walk (OnSchedule) on the device, uploaded at its first call
   bool os_ready = false;
-  int32_t *d_os_a_cl = nullptr, *d_os_ed_off = nullptr, *d_os_ed_msg = nullptr, *d_os_task_off = nullptr;
-  GRec* d_os_grecs = nullptr;
-  Entry* d_os_entries = nullptr;
-  int32_t* d_one_task_off = nullptr;  // single-message task for pgbp_propagate
-  Entry* d_one_entry = nullptr;
-  GRec* d_one_rec = nullptr;
+  OsBufs os;
+  DevBuf<int32_t> d_one_task_off;  // single-message task for pgbp_propagate
+  DevBuf<Entry> d_one_entry;
+  DevBuf<GRec> d_one_rec;
   std::vector<DevTraversal> dpost, dpre;
-  std::vector<FEntry*> d_tail;   // per tree: the tail groups of its postorder followed by those of its preorder
-  std::vector<FPro*> d_tail_pros;  // ... and their prologues (null: none)
+  std::vector<DevBuf<FEntry>> d_tail;   // per tree: the tail groups of its postorder followed by those of its preorder
+  std::vector<DevBuf<FPro>> d_tail_pros;  // ... and their prologues (null: none)
   // HIP events of the last pgbp_enqueue_calibrate_timed call (resolved by pgbp_fetch_kernel_time)
-  std::vector<std::pair<hipEvent_t, hipEvent_t>> kernel_events;
+  std::vector<EventPair> kernel_events;
   int32_t kernel_launches = 0;
-  double* d_ws = nullptr;        // workspace of the kernels whose working matrix exceeds the LDS (beliefs above kLdsMaxDim)
+  DevBuf<double> d_ws;        // workspace of the kernels whose working matrix exceeds the LDS (beliefs above kLdsMaxDim)
   int64_t ws_cap = 0;
-  double* d_gather = nullptr;    // send slot of pgbp_comm_gather_loglik: [norm | info | succ, iscal]
+  DevBuf<double> d_gather;    // send slot of pgbp_comm_gather_loglik: [norm | info | succ, iscal]
   int64_t gather_cap = 0;
-  double* d_xbuf = nullptr;      // exchange buffer of pgbp_pack_beliefs / pgbp_unpack_beliefs
+  DevBuf<double> d_xbuf;      // exchange buffer of pgbp_pack_beliefs / pgbp_unpack_beliefs
   int64_t xbuf_cap = 0;
-  int64_t* d_xoff = nullptr;     // ... its record offsets: [n] in the pool, [n + 1] in the buffer
+  DevBuf<int64_t> d_xoff;     // ... its record offsets: [n] in the pool, [n + 1] in the buffer
   int64_t xoff_cap = 0;
   bool have_factors = false;
   // pgbp_bm_tree: static description + last parameters of the device factor fill
+  bool bm_ready = false;
   int32_t bm_p = 0, bm_rows = 0, bm_per_site = 0;
-  int32_t *d_bm_kind = nullptr, *d_bm_row = nullptr;
-  double* d_bm_data_sm = nullptr;   // [row][site] copy of d_bm_data (p = 1)
-  double *d_bm_length = nullptr, *d_bm_data = nullptr, *d_bm_Rinv = nullptr, *d_bm_logdet = nullptr, *d_bm_mu = nullptr;
-  double2* d_bm_ithl = nullptr;    // [n_clusters] (1 / t, (p / 2) log t): launch_bm_ithl at set-up
+  BmBufs bm;
   // pgbp_lg_families: static description + last parameters of the general linear-Gaussian factor fill
   LgStatic lg{};                  // device pointers (owned: lg_bufs)
   LgParams lgp{};
-  std::vector<void*> lg_bufs;
+  LgBufs lg_bufs;
   bool lg_ready = false, lg_have_params = false, lg_uni_ok = false;
-  double *d_lg_R = nullptr, *d_lg_alpha = nullptr, *d_lg_theta = nullptr, *d_lg_mu = nullptr;
   std::string err;
   // a step of an asynchronous enqueue that could not be issued (a workspace that could not be allocated: ensure_ws has
   // set `err`): the launches that needed it were skipped; every entry point that enqueued, and the next pgbp_sync /
@@ -173,18 +217,19 @@ struct DeviceScope {
 int reset_fail(pgbp_engine* e);
 
 template <class T>
-int dev_alloc(pgbp_engine* e, T** p, size_t n) {
-  *p = nullptr;
-  if (n == 0) n = 1;
-  HIPCHK(e, hipMalloc(reinterpret_cast<void**>(p), n * sizeof(T)));
+int dev_alloc(pgbp_engine* e, DevBuf<T>& p, size_t n) {
+  HIPCHK(e, hipError_t(p.alloc(n)));
   return PGBP_OK;
 }
 
+// `p` takes the new buffer only once the copy has succeeded: a failure leaves it as it was
 template <class T>
-int upload(pgbp_engine* e, T** p, const std::vector<T>& v) {
-  int rc = dev_alloc(e, p, v.size());
+int upload(pgbp_engine* e, DevBuf<T>& p, const std::vector<T>& v) {
+  DevBuf<T> b;
+  int rc = dev_alloc(e, b, v.size());
   if (rc) return rc;
-  if (!v.empty()) HIPCHK(e, hipMemcpy(*p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
+  if (!v.empty()) HIPCHK(e, hipMemcpy(b.get(), v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
+  p = std::move(b);
   return PGBP_OK;
 }
 
@@ -208,7 +253,7 @@ int ensure_thresholds(pgbp_engine* e, double atol) {
     e->h_thr[s] = quotient_threshold(std::sqrt((double)s), atol);
     e->h_thr[PGBP_MAX_DIM + 1 + s] = quotient_threshold(std::sqrt((double)s * (double)s), atol);
   }
-  HIPCHK(e, hipMemcpyAsync(e->d_thr, e->h_thr.data(), sizeof(double) * e->h_thr.size(), hipMemcpyHostToDevice, e->st));
+  HIPCHK(e, hipMemcpyAsync(e->d_thr.get(), e->h_thr.data(), sizeof(double) * e->h_thr.size(), hipMemcpyHostToDevice, e->st));
   e->thr_atol = atol;
   e->thr_valid = true;
   return PGBP_OK;
@@ -216,23 +261,23 @@ int ensure_thresholds(pgbp_engine* e, double atol) {
 
 DevState dev_state(pgbp_engine* e, const pgbp_opts* o) {
   DevState S;
-  S.pool = e->d_pool;
+  S.pool = e->d_pool.get();
   S.pool_stride = e->plan.pool_stride();
-  S.rpool = e->d_rpool;
+  S.rpool = e->d_rpool.get();
   S.rpool_stride = e->plan.rpool_stride();
-  S.msgs = e->d_msgs;
-  S.idx = e->d_idx;
-  S.flags = e->d_flags;
-  S.status = e->d_status;
-  S.fail = e->d_fail;
-  S.poison = e->d_poison;
+  S.msgs = e->d_msgs.get();
+  S.idx = e->d_idx.get();
+  S.flags = e->d_flags.get();
+  S.status = e->d_status.get();
+  S.fail = e->d_fail.get();
+  S.poison = e->d_poison.get();
   S.n_clusters = e->plan.n_clusters;
   S.n_msgs = e->plan.n_msgs();
   S.update_resnorm = o ? o->update_residualnorm : 1;
   S.atol = o ? o->atol : 1e-5;
   // (DevState::thr belongs to this tolerance: every entry point went through check_opts -> ensure_thresholds first)
-  S.thr = e->d_thr;
-  S.logtab = reinterpret_cast<const double2*>(e->d_logtab);
+  S.thr = e->d_thr.get();
+  S.logtab = reinterpret_cast<const double2*>(e->d_logtab.get());
   const int sp = e->plan.fast_p > 0 ? e->plan.fast_p : 0;
   S.thr_h_p = e->h_thr.empty() ? 0.0 : e->h_thr[sp];
   S.thr_J_p = e->h_thr.empty() ? 0.0 : e->h_thr[PGBP_MAX_DIM + 1 + sp];
@@ -240,13 +285,13 @@ DevState dev_state(pgbp_engine* e, const pgbp_opts* o) {
   S.fast_p = e->plan.fast_p;
   S.sm = e->layout_sm ? 1 : 0;
   S.n_sites = e->plan.n_sites;
-  S.packed_off = e->d_packed_off;
-  S.rpacked_off = e->d_rpacked_off;
+  S.packed_off = e->d_packed_off.get();
+  S.rpacked_off = e->d_rpacked_off.get();
   S.sep_zero = 0;
   S.notcal = nullptr;
   if (e->layout_sm) {
-    S.pool = e->d_pool_sm;
-    S.rpool = e->d_rpool_sm;
+    S.pool = e->sm.pool.get();
+    S.rpool = e->sm.rpool.get();
   }
   return S;
 }
@@ -275,7 +320,7 @@ __global__ __launch_bounds__(256) void clear_poison_if_failed(const unsigned lon
 // init_messagecalibrationflags_reset! on the device (src/clustergraphbeliefs.jl:190-202); reset_kl: the KL divergences too
 void reset_message_flags(pgbp_engine* e, int reset_kl) {
   const int mode = ((reset_kl && !e->kl_div_clean) ? 1 : 0) | (e->kl_flags_clean ? 0 : 2);
-  launch_reset_flags(e->d_msgs, e->d_flags, e->d_klflags, e->d_kldiv, e->plan.n_msgs(), e->plan.n_sites, mode, e->st,
+  launch_reset_flags(e->d_msgs.get(), e->d_flags.get(), e->d_klflags.get(), e->d_kldiv.get(), e->plan.n_msgs(), e->plan.n_sites, mode, e->st,
                      e->layout_sm ? 1 : 0);
   e->kl_flags_clean = true;
   if (reset_kl) e->kl_div_clean = true;
@@ -287,8 +332,8 @@ int reset_fail(pgbp_engine* e) {
   const int64_t n_words = (int64_t)sm_row(e->plan.n_sites) * (int64_t)e->plan.n_clusters;
   const int64_t want = (n_words / 4 + 255) / 256;
   const int grid = (int)std::max<int64_t>(1, std::min<int64_t>(want, 2048));
-  hipLaunchKernelGGL(clear_poison_if_failed, dim3(grid), dim3(256), 0, e->st, e->d_fail, (int)ns, e->d_poison, n_words);
-  HIPCHK(e, hipMemsetAsync(e->d_fail, 0xFF, sizeof(unsigned long long) * ns, e->st));
+  hipLaunchKernelGGL(clear_poison_if_failed, dim3(grid), dim3(256), 0, e->st, e->d_fail.get(), (int)ns, e->d_poison.get(), n_words);
+  HIPCHK(e, hipMemsetAsync(e->d_fail.get(), 0xFF, sizeof(unsigned long long) * ns, e->st));
   return PGBP_OK;
 }
 
@@ -303,33 +348,35 @@ int ensure_site_minor(pgbp_engine* e, bool want) {
   const Plan& p = e->plan;
   if (want == e->layout_sm) return PGBP_OK;
   const size_t ns = (size_t)sm_row(p.n_sites);   // (rows of the site-minor buffers: padded)
-  if (want && !e->d_pool_sm) {
+  if (want && !e->sm.pool) {
+    SmBufs B;
     int rc;
-    if ((rc = dev_alloc(e, &e->d_pool_sm, ns * (size_t)p.packed_off.back()))) return rc;
-    if ((rc = dev_alloc(e, &e->d_fpool_sm, ns * (size_t)p.packed_off[p.n_clusters]))) return rc;
-    if ((rc = dev_alloc(e, &e->d_rpool_sm, ns * (size_t)p.rpacked_off.back()))) return rc;
+    if ((rc = dev_alloc(e, B.pool, ns * (size_t)p.packed_off.back()))) return rc;
+    if ((rc = dev_alloc(e, B.fpool, ns * (size_t)p.packed_off[p.n_clusters]))) return rc;
+    if ((rc = dev_alloc(e, B.rpool, ns * (size_t)p.rpacked_off.back()))) return rc;
     const size_t nm = (size_t)p.n_msgs();
-    if ((rc = dev_alloc(e, &e->d_flags_alt, ns * nm))) return rc;
-    if ((rc = dev_alloc(e, &e->d_status_alt, ns * nm))) return rc;
-    if ((rc = dev_alloc(e, &e->d_klflags_alt, ns * nm))) return rc;
-    if ((rc = dev_alloc(e, &e->d_kldiv_alt, ns * nm))) return rc;
-    if ((rc = dev_alloc(e, &e->d_poison_alt, ns * (size_t)std::max(1, p.n_clusters)))) return rc;
+    if ((rc = dev_alloc(e, B.flags, ns * nm))) return rc;
+    if ((rc = dev_alloc(e, B.status, ns * nm))) return rc;
+    if ((rc = dev_alloc(e, B.klflags, ns * nm))) return rc;
+    if ((rc = dev_alloc(e, B.kldiv, ns * nm))) return rc;
+    if ((rc = dev_alloc(e, B.poison, ns * (size_t)std::max(1, p.n_clusters)))) return rc;
+    e->sm = std::move(B);
   }
   const int to = want ? 1 : 0;
   // flags, status, KL words and poison marks: [site][index] <-> [index][site]
-  launch_transpose_words_i32(e->d_flags, e->d_flags_alt, p.n_msgs(), p.n_sites, to, e->st);
-  launch_transpose_words_i32(e->d_status, e->d_status_alt, p.n_msgs(), p.n_sites, to, e->st);
-  launch_transpose_words_i32(e->d_klflags, e->d_klflags_alt, p.n_msgs(), p.n_sites, to, e->st);
-  launch_transpose_words_f64(e->d_kldiv, e->d_kldiv_alt, p.n_msgs(), p.n_sites, to, e->st);
-  launch_transpose_words_i32(e->d_poison, e->d_poison_alt, p.n_clusters, p.n_sites, to, e->st);
-  std::swap(e->d_flags, e->d_flags_alt);
-  std::swap(e->d_status, e->d_status_alt);
-  std::swap(e->d_klflags, e->d_klflags_alt);
-  std::swap(e->d_kldiv, e->d_kldiv_alt);
-  std::swap(e->d_poison, e->d_poison_alt);
-  launch_site_minor(e->d_pool, p.pool_stride(), e->d_pool_sm, e->d_boff, e->d_packed_off, p.n_beliefs(), p.n_sites, to, e->st);
-  launch_site_minor(e->d_fpool, p.cluster_stride(), e->d_fpool_sm, e->d_boff, e->d_packed_off, p.n_clusters, p.n_sites, to, e->st);
-  launch_site_minor(e->d_rpool, p.rpool_stride(), e->d_rpool_sm, e->d_roff, e->d_rpacked_off, p.n_msgs(), p.n_sites, to, e->st);
+  launch_transpose_words_i32(e->d_flags.get(), e->sm.flags.get(), p.n_msgs(), p.n_sites, to, e->st);
+  launch_transpose_words_i32(e->d_status.get(), e->sm.status.get(), p.n_msgs(), p.n_sites, to, e->st);
+  launch_transpose_words_i32(e->d_klflags.get(), e->sm.klflags.get(), p.n_msgs(), p.n_sites, to, e->st);
+  launch_transpose_words_f64(e->d_kldiv.get(), e->sm.kldiv.get(), p.n_msgs(), p.n_sites, to, e->st);
+  launch_transpose_words_i32(e->d_poison.get(), e->sm.poison.get(), p.n_clusters, p.n_sites, to, e->st);
+  e->d_flags.swap(e->sm.flags);
+  e->d_status.swap(e->sm.status);
+  e->d_klflags.swap(e->sm.klflags);
+  e->d_kldiv.swap(e->sm.kldiv);
+  e->d_poison.swap(e->sm.poison);
+  launch_site_minor(e->d_pool.get(), p.pool_stride(), e->sm.pool.get(), e->d_boff.get(), e->d_packed_off.get(), p.n_beliefs(), p.n_sites, to, e->st);
+  launch_site_minor(e->d_fpool.get(), p.cluster_stride(), e->sm.fpool.get(), e->d_boff.get(), e->d_packed_off.get(), p.n_clusters, p.n_sites, to, e->st);
+  launch_site_minor(e->d_rpool.get(), p.rpool_stride(), e->sm.rpool.get(), e->d_roff.get(), e->d_rpacked_off.get(), p.n_msgs(), p.n_sites, to, e->st);
   e->layout_sm = want;
   return PGBP_OK;
 }
@@ -347,11 +394,11 @@ int ensure_layout(pgbp_engine* e, bool want_bs16, bool want_sm = false) {
   if (want_bs16 == e->layout_bs16) return PGBP_OK;
   if (want_bs16) {
     if (!e->sym_known) {
-      HIPCHK(e, hipMemsetAsync(e->d_symflag, 0, sizeof(int32_t), e->st));
-      launch_check_symmetry(e->d_pool, p.pool_stride(), e->d_boff, e->d_bdim, p.n_beliefs(), p.n_sites, e->d_symflag, p.fast_p, e->st);
-      launch_check_symmetry(e->d_fpool, p.cluster_stride(), e->d_boff, e->d_bdim, p.n_clusters, p.n_sites, e->d_symflag, p.fast_p, e->st);
+      HIPCHK(e, hipMemsetAsync(e->d_symflag.get(), 0, sizeof(int32_t), e->st));
+      launch_check_symmetry(e->d_pool.get(), p.pool_stride(), e->d_boff.get(), e->d_bdim.get(), p.n_beliefs(), p.n_sites, e->d_symflag.get(), p.fast_p, e->st);
+      launch_check_symmetry(e->d_fpool.get(), p.cluster_stride(), e->d_boff.get(), e->d_bdim.get(), p.n_clusters, p.n_sites, e->d_symflag.get(), p.fast_p, e->st);
       int32_t flag = 0;
-      HIPCHK(e, hipMemcpyAsync(&flag, e->d_symflag, sizeof(flag), hipMemcpyDeviceToHost, e->st));
+      HIPCHK(e, hipMemcpyAsync(&flag, e->d_symflag.get(), sizeof(flag), hipMemcpyDeviceToHost, e->st));
       HIPCHK(e, hipStreamSynchronize(e->st));
       e->sym_known = true;
       e->sym_ok = flag == 0;
@@ -359,9 +406,9 @@ int ensure_layout(pgbp_engine* e, bool want_bs16, bool want_sm = false) {
     if (!e->sym_ok) return PGBP_OK;  // stay plain: exact reference semantics for asymmetric input
   }
   const int to = want_bs16 ? 1 : 0;
-  launch_convert_layout(e->d_pool, p.pool_stride(), e->d_boff, e->d_bdim, p.n_beliefs(), p.n_sites, to, 0, p.fast_p, e->st);
-  launch_convert_layout(e->d_fpool, p.cluster_stride(), e->d_boff, e->d_bdim, p.n_clusters, p.n_sites, to, 0, p.fast_p, e->st);
-  launch_convert_layout(e->d_rpool, p.rpool_stride(), e->d_roff, e->d_rdim, p.n_msgs(), p.n_sites, to, 1, p.fast_p, e->st);
+  launch_convert_layout(e->d_pool.get(), p.pool_stride(), e->d_boff.get(), e->d_bdim.get(), p.n_beliefs(), p.n_sites, to, 0, p.fast_p, e->st);
+  launch_convert_layout(e->d_fpool.get(), p.cluster_stride(), e->d_boff.get(), e->d_bdim.get(), p.n_clusters, p.n_sites, to, 0, p.fast_p, e->st);
+  launch_convert_layout(e->d_rpool.get(), p.rpool_stride(), e->d_roff.get(), e->d_rdim.get(), p.n_msgs(), p.n_sites, to, 1, p.fast_p, e->st);
   e->layout_bs16 = want_bs16;
   return PGBP_OK;
 }
@@ -381,29 +428,9 @@ bool want_bs16(const pgbp_engine* e) {
 }
 
 void free_traversals(pgbp_engine* e) {
-  for (auto* v : {&e->dpost, &e->dpre}) {
-    for (auto& d : *v) {
-      if (d.d_task_off) (void)hipFree(d.d_task_off);
-      if (d.d_entries) (void)hipFree(d.d_entries);
-      if (d.d_urecs) (void)hipFree(d.d_urecs);
-      if (d.d_fentries) (void)hipFree(d.d_fentries);
-      if (d.d_fpros) (void)hipFree(d.d_fpros);
-      if (d.d_cpros) (void)hipFree(d.d_cpros);
-      if (d.d_centries) (void)hipFree(d.d_centries);
-      if (d.d_chunk_wg_off) (void)hipFree(d.d_chunk_wg_off);
-      if (d.d_cgroups) (void)hipFree(d.d_cgroups);
-      if (d.d_cgroups_task) (void)hipFree(d.d_cgroups_task);
-      if (d.d_grecs) (void)hipFree(d.d_grecs);
-      if (d.d_rowmap) (void)hipFree(d.d_rowmap);
-      if (d.d_kl_big) (void)hipFree(d.d_kl_big);
-    }
-    v->clear();
-  }
-  for (FEntry* t : e->d_tail)
-    if (t) (void)hipFree(t);
+  e->dpost.clear();
+  e->dpre.clear();
   e->d_tail.clear();
-  for (FPro* t : e->d_tail_pros)
-    if (t) (void)hipFree(t);
   e->d_tail_pros.clear();
 }
 
@@ -411,10 +438,9 @@ void free_traversals(pgbp_engine* e) {
 int ensure_ws(pgbp_engine* e, int64_t doubles) {
   if (doubles <= e->ws_cap) return PGBP_OK;
   HIPCHK(e, hipStreamSynchronize(e->st));
-  if (e->d_ws) (void)hipFree(e->d_ws);
-  e->d_ws = nullptr;
   e->ws_cap = 0;
-  HIPCHK(e, hipMalloc(reinterpret_cast<void**>(&e->d_ws), sizeof(double) * (size_t)doubles));
+  const int rc = dev_alloc(e, e->d_ws, (size_t)doubles);
+  if (rc) return rc;
   e->ws_cap = doubles;
   return PGBP_OK;
 }
@@ -465,15 +491,15 @@ void enqueue_levels(pgbp_engine* e, const DevState& S, const Traversal& tr, cons
       while (next_chunk < tr.chunks.size() && tr.chunks[next_chunk].level0 < L) ++next_chunk;
       if (next_chunk < tr.chunks.size() && tr.chunks[next_chunk].level0 == L && tr.chunks[next_chunk].level1 <= L1) {
         const Traversal::Chunk& ch = tr.chunks[next_chunk];
-        if (uni && d.d_urecs)   // (the planner builds chunks of tasks for such plans: pgbp_plan.cpp, plan_uni)
-          launch_chunk_uni1(S, d.d_task_off, d.d_urecs, d.d_cgroups_task + ch.group0 * kTailWaves, d.d_chunk_wg_off + ch.wg0,
+        if (uni && d.d_urecs.get())   // (the planner builds chunks of tasks for such plans: pgbp_plan.cpp, plan_uni)
+          launch_chunk_uni1(S, d.d_task_off.get(), d.d_urecs.get(), d.d_cgroups_task.get() + ch.group0 * kTailWaves, d.d_chunk_wg_off.get() + ch.wg0,
                             ch.n_wg, e->plan.n_sites, seq_base, stop_below, e->st);
         else if (ch.generic)
-          launch_chunk_generic(S, d.d_grecs, d.d_cgroups + ch.group0 * kTailWaves, d.d_chunk_wg_off + ch.wg0, ch.n_wg,
+          launch_chunk_generic(S, d.d_grecs.get(), d.d_cgroups.get() + ch.group0 * kTailWaves, d.d_chunk_wg_off.get() + ch.wg0, ch.n_wg,
                                e->plan.n_sites, seq_base, stop_below, ch.max_mf, ch.small_only != 0, e->plan.tune.pair2, e->st);
         else
-          launch_loop_or_tail(e, S, d.d_centries + ch.group0 * kTailWaves, d.d_cpros ? d.d_cpros + ch.group0 * kTailWaves : nullptr,
-                              ch.n_groups, INT32_MAX, seq_base, stop_below, stop_below, d.d_chunk_wg_off + ch.wg0, ch.n_wg);
+          launch_loop_or_tail(e, S, d.d_centries.get() + ch.group0 * kTailWaves, d.d_cpros.get() ? d.d_cpros.get() + ch.group0 * kTailWaves : nullptr,
+                              ch.n_groups, INT32_MAX, seq_base, stop_below, stop_below, d.d_chunk_wg_off.get() + ch.wg0, ch.n_wg);
         if (launches) *launches += 1;
         L = ch.level1 - 1;
         continue;
@@ -481,21 +507,21 @@ void enqueue_levels(pgbp_engine* e, const DevState& S, const Traversal& tr, cons
     }
     const int t0 = tr.level_off[L], nt = tr.level_off[L + 1] - t0;
     const int nf = tr.level_nfast[L], ng = tr.level_ngroups[L];
-    launch_fast16(S, d.d_fentries + tr.level_fbase[L], d.d_fpros ? d.d_fpros + tr.level_fbase[L] : nullptr, kFastLevel, ng, ng,
+    launch_fast16(S, d.d_fentries.get() + tr.level_fbase[L], d.d_fpros.get() ? d.d_fpros.get() + tr.level_fbase[L] : nullptr, kFastLevel, ng, ng,
                   e->plan.n_sites, seq_base, stop_below, stop_below, e->st);
     const int nbig = tr.level_nbig[L];
     if (uni)
-      launch_level_uni(S, d.d_task_off, d.d_entries, d.d_urecs, t0 + nf, nt - nf, e->plan.n_sites, seq_base, stop_below, e->max_s, e->st);
+      launch_level_uni(S, d.d_task_off.get(), d.d_entries.get(), d.d_urecs.get(), t0 + nf, nt - nf, e->plan.n_sites, seq_base, stop_below, e->max_s, e->st);
     else {
-      const bool rows = d.d_rowmap && !tr.level_nrows.empty() && tr.level_nrows[L] > 0;
-      launch_level_generic(S, d.d_grecs, tr.level_gbase[L], nt - nf - nbig, e->plan.n_sites, seq_base, stop_below,
+      const bool rows = d.d_rowmap.get() && !tr.level_nrows.empty() && tr.level_nrows[L] > 0;
+      launch_level_generic(S, d.d_grecs.get(), tr.level_gbase[L], nt - nf - nbig, e->plan.n_sites, seq_base, stop_below,
                            tr.max_mf, nbig == 0 && tr.level_small[L] != 0, e->st,
-                           rows ? d.d_rowmap + 2 * tr.level_rowbase[L] : nullptr, rows ? tr.level_nrows[L] : 0,
+                           rows ? d.d_rowmap.get() + 2 * tr.level_rowbase[L] : nullptr, rows ? tr.level_nrows[L] : 0,
                            e->plan.tune.small4_min);
       if (nbig > 0) {
         if (ensure_ws(e, (int64_t)nbig * e->plan.n_sites * big_ws_doubles(tr.max_mf_big)) == PGBP_OK)
-          launch_level_big(S, d.d_task_off, d.d_entries, t0 + nt - nbig, nbig, e->plan.n_sites, seq_base, stop_below,
-                           tr.max_mf_big, e->d_ws, e->st);
+          launch_level_big(S, d.d_task_off.get(), d.d_entries.get(), t0 + nt - nbig, nbig, e->plan.n_sites, seq_base, stop_below,
+                           tr.max_mf_big, e->d_ws.get(), e->st);
         else
           e->enqueue_rc = PGBP_ERR_HIP;   // (these messages never ran: the entry point reports it)
       }
@@ -510,8 +536,8 @@ void enqueue_levels(pgbp_engine* e, const DevState& S, const Traversal& tr, cons
       const int n_big = (int)(b1 - b0);
       e->kl_flags_clean = e->kl_div_clean = false;
       if (n_big == 0 || ensure_ws(e, (int64_t)n_big * e->plan.n_sites * kldiv_ws_doubles(level_s)) == PGBP_OK)
-        launch_residual_kldiv(S, d.d_entries, e0, e1 - e0, level_s, e->d_kldiv, e->d_klflags, e->plan.n_sites, stop_below, e->st,
-                              d.d_kl_big + (b0 - d.kl_big.begin()), n_big, e->d_ws);
+        launch_residual_kldiv(S, d.d_entries.get(), e0, e1 - e0, level_s, e->d_kldiv.get(), e->d_klflags.get(), e->plan.n_sites, stop_below, e->st,
+                              d.d_kl_big.get() + (b0 - d.kl_big.begin()), n_big, e->d_ws.get());
       else
         e->enqueue_rc = PGBP_ERR_HIP;
     }
@@ -536,7 +562,7 @@ void enqueue_tree(pgbp_engine* e, const DevState& S, int tree, int dirs, unsigne
   if (np + nq > 0) {
     // d_tail = the postorder's tail groups followed by the preorder's
     const size_t first = (size_t)(np > 0 ? 0 : T.post.tail_levels) * kTailWaves;
-    launch_loop_or_tail(e, S, e->d_tail[tree] + first, e->d_tail_pros[tree] ? e->d_tail_pros[tree] + first : nullptr, np + nq,
+    launch_loop_or_tail(e, S, e->d_tail[tree].get() + first, e->d_tail_pros[tree] ? e->d_tail_pros[tree].get() + first : nullptr, np + nq,
                         np, seq_base, stop_post, stop_pre, nullptr, 0);
     if (n_launches) *n_launches += 1;
   }
@@ -552,14 +578,14 @@ void enqueue_pair_and_iscal(pgbp_engine* e, const DevState& S, int tree, unsigne
   const Plan& p = e->plan;
   const bool fused = e->layout_sm && !kl && S.update_resnorm != 0 && (int)p.trees[tree].pa.size() == p.n_sepsets;
   if (fused) {
-    (void)hipMemsetAsync(e->d_notcal, 0, sizeof(int32_t) * (size_t)p.n_sites, e->st);
+    (void)hipMemsetAsync(e->d_notcal.get(), 0, sizeof(int32_t) * (size_t)p.n_sites, e->st);
     DevState S1 = S;
-    S1.notcal = e->d_notcal;
+    S1.notcal = e->d_notcal.get();
     enqueue_tree(e, S1, tree, 3, pair, kl, n_launches);
-    launch_iscal_from_notcal(e->d_notcal, d_out, p.n_sites, e->st);
+    launch_iscal_from_notcal(e->d_notcal.get(), d_out, p.n_sites, e->st);
   } else {
     enqueue_tree(e, S, tree, 3, pair, kl, n_launches);
-    launch_reduce_flags(e->d_flags, p.n_msgs(), p.n_sites, d_out, e->st, e->layout_sm ? 1 : 0);
+    launch_reduce_flags(e->d_flags.get(), p.n_msgs(), p.n_sites, d_out, e->st, e->layout_sm ? 1 : 0);
   }
 }
 
@@ -567,11 +593,11 @@ void enqueue_pair_and_iscal(pgbp_engine* e, const DevState& S, int tree, unsigne
 void integrate_async(pgbp_engine* e, int belief, double* d_mu) {
   const Plan& p = e->plan;
   if (e->layout_sm)
-    launch_integrate_sm(e->d_pool_sm, p.packed_off[belief], p.dims[belief], d_mu, std::max(1, p.max_dim), e->d_norm,
-                        e->d_info, p.n_sites, e->st);
+    launch_integrate_sm(e->sm.pool.get(), p.packed_off[belief], p.dims[belief], d_mu, std::max(1, p.max_dim), e->d_norm.get(),
+                        e->d_info.get(), p.n_sites, e->st);
   else if (ensure_ws(e, (int64_t)p.n_sites * big_ws_doubles(p.dims[belief])) == PGBP_OK)
-    launch_integrate(e->d_pool, p.pool_stride(), p.boff[belief], p.dims[belief], e->layout_bs16 ? 1 : 0, p.fast_p, d_mu,
-                     std::max(1, p.max_dim), e->d_norm, e->d_info, p.n_sites, e->d_ws, e->st);
+    launch_integrate(e->d_pool.get(), p.pool_stride(), p.boff[belief], p.dims[belief], e->layout_bs16 ? 1 : 0, p.fast_p, d_mu,
+                     std::max(1, p.max_dim), e->d_norm.get(), e->d_info.get(), p.n_sites, e->d_ws.get(), e->st);
   else
     e->enqueue_rc = PGBP_ERR_HIP;   // (e->err is set; the entry point returns the code)
 }
@@ -582,17 +608,17 @@ int reset_from_factors_async(pgbp_engine* e, bool skip_sepsets = false) {
   const Plan& p = e->plan;
   if (e->layout_sm) {  // cluster elements come first and are contiguous over sites
     const int64_t nc = p.packed_off[p.n_clusters] * sm_row(p.n_sites), nall = p.packed_off.back() * sm_row(p.n_sites);
-    HIPCHK(e, hipMemcpyAsync(e->d_pool_sm, e->d_fpool_sm, sizeof(double) * (size_t)nc, hipMemcpyDeviceToDevice, e->st));
-    if (!skip_sepsets) HIPCHK(e, hipMemsetAsync(e->d_pool_sm + nc, 0, sizeof(double) * (size_t)(nall - nc), e->st));
+    HIPCHK(e, hipMemcpyAsync(e->sm.pool.get(), e->sm.fpool.get(), sizeof(double) * (size_t)nc, hipMemcpyDeviceToDevice, e->st));
+    if (!skip_sepsets) HIPCHK(e, hipMemsetAsync(e->sm.pool.get() + nc, 0, sizeof(double) * (size_t)(nall - nc), e->st));
     return PGBP_OK;
   }
   if (e->layout_bs16)  // packed records use about half of their slots: copy what is in use
-    launch_copy_records(e->d_fpool, p.cluster_stride(), e->d_pool, p.pool_stride(), e->d_boff, e->d_bdim, p.n_clusters, 1,
+    launch_copy_records(e->d_fpool.get(), p.cluster_stride(), e->d_pool.get(), p.pool_stride(), e->d_boff.get(), e->d_bdim.get(), p.n_clusters, 1,
                         p.fast_p, p.n_sites, e->st);
   else
-    launch_copy_strided(e->d_fpool, p.cluster_stride(), e->d_pool, p.pool_stride(), p.cluster_stride(), p.n_sites, e->st);
+    launch_copy_strided(e->d_fpool.get(), p.cluster_stride(), e->d_pool.get(), p.pool_stride(), p.cluster_stride(), p.n_sites, e->st);
   if (!skip_sepsets)
-    launch_zero_strided(e->d_pool + p.cluster_stride(), p.pool_stride(), p.pool_stride() - p.cluster_stride(),
+    launch_zero_strided(e->d_pool.get() + p.cluster_stride(), p.pool_stride(), p.pool_stride() - p.cluster_stride(),
                         p.n_sites, e->st);
   return PGBP_OK;
 }
@@ -624,34 +650,7 @@ const char* pgbp_last_error(const pgbp_engine* e) { return e ? e->err.c_str() : 
 void pgbp_destroy(pgbp_engine* e) {
   if (!e) return;
   (void)hipSetDevice(e->plan.device);
-  free_traversals(e);
-  for (auto& pr : e->kernel_events) {
-    (void)hipEventDestroy(pr.first);
-    (void)hipEventDestroy(pr.second);
-  }
-  for (void* p : {(void*)e->d_pool, (void*)e->d_fpool, (void*)e->d_rpool, (void*)e->d_msgs, (void*)e->d_idx,
-                  (void*)e->d_flags, (void*)e->d_status, (void*)e->d_kldiv, (void*)e->d_klflags, (void*)e->d_nb_off, (void*)e->d_nb_msg, (void*)e->d_sepcl, (void*)e->d_eps, (void*)e->d_thr, (void*)e->d_logtab, (void*)e->d_pool_sm, (void*)e->d_fpool_sm, (void*)e->d_rpool_sm, (void*)e->d_flags_alt, (void*)e->d_status_alt,
-                  (void*)e->d_klflags_alt, (void*)e->d_poison_alt, (void*)e->d_kldiv_alt, (void*)e->d_fail, (void*)e->d_poison,
-                  (void*)e->d_iscal, (void*)e->d_notcal,
-                  (void*)e->d_iscal_hist, (void*)e->d_boff, (void*)e->d_packed_off, (void*)e->d_roff,
-                  (void*)e->d_rpacked_off, (void*)e->d_mu, (void*)e->d_norm, (void*)e->d_info,
-                  (void*)e->d_one_task_off, (void*)e->d_one_entry, (void*)e->d_one_rec, (void*)e->d_bdim, (void*)e->d_rdim,
-                  (void*)e->d_symflag, (void*)e->d_bm_kind, (void*)e->d_bm_row, (void*)e->d_bm_length, (void*)e->d_bm_ithl,
-                  (void*)e->d_bm_data, (void*)e->d_bm_Rinv, (void*)e->d_bm_logdet, (void*)e->d_bm_mu,
-                  (void*)e->d_os_a_cl, (void*)e->d_os_ed_off, (void*)e->d_os_ed_msg, (void*)e->d_os_task_off,
-                  (void*)e->d_os_grecs, (void*)e->d_os_entries})
-    if (p) (void)hipFree(p);
-  for (void* p : e->lg_bufs)
-    if (p) (void)hipFree(p);
-  for (void* p : {(void*)e->d_lg_R, (void*)e->d_lg_alpha, (void*)e->d_lg_theta, (void*)e->d_lg_mu})
-    if (p) (void)hipFree(p);
-  if (e->d_gather) (void)hipFree(e->d_gather);
-  if (e->d_ws) (void)hipFree(e->d_ws);
-  if (e->d_xbuf) (void)hipFree(e->d_xbuf);
-  if (e->d_xoff) (void)hipFree(e->d_xoff);
-  if (e->d_bm_data_sm) (void)hipFree(e->d_bm_data_sm);
-  if (e->st) (void)hipStreamDestroy(e->st);
-  delete e;
+  delete e;   // (the first release waits for the device, as hipFree does; the buffers go before the stream)
 }
 
 int pgbp_create(const pgbp_desc* desc, pgbp_engine** out) {
@@ -679,7 +678,7 @@ int pgbp_create(const pgbp_desc* desc, pgbp_engine** out) {
     e->err = "hipSetDevice failed";
     return bail(PGBP_ERR_HIP);
   }
-  if (hipStreamCreateWithFlags(&e->st, hipStreamNonBlocking) != hipSuccess) {
+  if (hipStreamCreateWithFlags(&e->st.s, hipStreamNonBlocking) != hipSuccess) {
     e->err = "hipStreamCreate failed";
     return bail(PGBP_ERR_HIP);
   }
@@ -688,15 +687,15 @@ int pgbp_create(const pgbp_desc* desc, pgbp_engine** out) {
   const size_t nm = (size_t)p.n_msgs();
   const size_t nsw = (size_t)sm_row(p.n_sites);   // the per-message / per-cluster word arrays serve both layouts (a switch swaps
                                                    // them with their twins): sized for the padded rows of the site-minor one
-  if ((rc = dev_alloc(e, &e->d_pool, ns * p.pool_stride()))) return bail(rc);
-  if ((rc = dev_alloc(e, &e->d_fpool, ns * p.cluster_stride()))) return bail(rc);
-  if ((rc = dev_alloc(e, &e->d_rpool, ns * p.rpool_stride()))) return bail(rc);
-  if ((rc = upload(e, &e->d_msgs, p.msgs))) return bail(rc);
-  if ((rc = upload(e, &e->d_idx, p.idxpool))) return bail(rc);
-  if ((rc = dev_alloc(e, &e->d_flags, nsw * nm))) return bail(rc);
-  if ((rc = dev_alloc(e, &e->d_status, nsw * nm))) return bail(rc);
-  if ((rc = dev_alloc(e, &e->d_kldiv, nsw * nm))) return bail(rc);
-  if ((rc = dev_alloc(e, &e->d_klflags, nsw * nm))) return bail(rc);
+  if ((rc = dev_alloc(e, e->d_pool, ns * p.pool_stride()))) return bail(rc);
+  if ((rc = dev_alloc(e, e->d_fpool, ns * p.cluster_stride()))) return bail(rc);
+  if ((rc = dev_alloc(e, e->d_rpool, ns * p.rpool_stride()))) return bail(rc);
+  if ((rc = upload(e, e->d_msgs, p.msgs))) return bail(rc);
+  if ((rc = upload(e, e->d_idx, p.idxpool))) return bail(rc);
+  if ((rc = dev_alloc(e, e->d_flags, nsw * nm))) return bail(rc);
+  if ((rc = dev_alloc(e, e->d_status, nsw * nm))) return bail(rc);
+  if ((rc = dev_alloc(e, e->d_kldiv, nsw * nm))) return bail(rc);
+  if ((rc = dev_alloc(e, e->d_klflags, nsw * nm))) return bail(rc);
   {
     std::vector<int32_t> nb_off(p.n_clusters + 1, 0), nb_msg(nm);
     for (int k = 0; k < p.n_sepsets; ++k) {
@@ -709,12 +708,12 @@ int pgbp_create(const pgbp_desc* desc, pgbp_engine** out) {
       nb_msg[fill[p.sepset_clusters[2 * k]]++] = 2 * k + 1;
       nb_msg[fill[p.sepset_clusters[2 * k + 1]]++] = 2 * k;
     }
-    if ((rc = upload(e, &e->d_nb_off, nb_off))) return bail(rc);
-    if ((rc = upload(e, &e->d_nb_msg, nb_msg))) return bail(rc);
-    if ((rc = upload(e, &e->d_sepcl, p.sepset_clusters))) return bail(rc);
-    if ((rc = dev_alloc(e, &e->d_eps, ns * (size_t)std::max(1, p.n_clusters)))) return bail(rc);
-    if ((rc = dev_alloc(e, &e->d_thr, 2 * (size_t)(PGBP_MAX_DIM + 1)))) return bail(rc);
-    if ((rc = dev_alloc(e, &e->d_logtab, 256))) return bail(rc);
+    if ((rc = upload(e, e->d_nb_off, nb_off))) return bail(rc);
+    if ((rc = upload(e, e->d_nb_msg, nb_msg))) return bail(rc);
+    if ((rc = upload(e, e->d_sepcl, p.sepset_clusters))) return bail(rc);
+    if ((rc = dev_alloc(e, e->d_eps, ns * (size_t)std::max(1, p.n_clusters)))) return bail(rc);
+    if ((rc = dev_alloc(e, e->d_thr, 2 * (size_t)(PGBP_MAX_DIM + 1)))) return bail(rc);
+    if ((rc = dev_alloc(e, e->d_logtab, 256))) return bail(rc);
     {
       // DevState::logtab, in the host's extended precision
       double tab[256];
@@ -724,42 +723,42 @@ int pgbp_create(const pgbp_desc* desc, pgbp_engine** out) {
         tab[2 * i] = inv;
         tab[2 * i + 1] = (double)(-logl((long double)inv));
       }
-      if (hipMemcpy(e->d_logtab, tab, sizeof(tab), hipMemcpyHostToDevice) != hipSuccess) return bail(PGBP_ERR_HIP);
+      if (hipMemcpy(e->d_logtab.get(), tab, sizeof(tab), hipMemcpyHostToDevice) != hipSuccess) return bail(PGBP_ERR_HIP);
     }
   }
-  if ((rc = dev_alloc(e, &e->d_fail, ns))) return bail(rc);
-  if ((rc = dev_alloc(e, &e->d_poison, nsw * (size_t)p.n_clusters))) return bail(rc);
-  if ((rc = dev_alloc(e, &e->d_iscal, ns))) return bail(rc);
-  if ((rc = dev_alloc(e, &e->d_notcal, ns))) return bail(rc);
-  if ((rc = upload(e, &e->d_boff, p.boff))) return bail(rc);
-  if ((rc = upload(e, &e->d_packed_off, p.packed_off))) return bail(rc);
-  if ((rc = upload(e, &e->d_roff, p.roff))) return bail(rc);
-  if ((rc = upload(e, &e->d_rpacked_off, p.rpacked_off))) return bail(rc);
-  if ((rc = dev_alloc(e, &e->d_mu, ns * (size_t)std::max(1, p.max_dim)))) return bail(rc);
-  if ((rc = dev_alloc(e, &e->d_norm, ns))) return bail(rc);
-  if ((rc = dev_alloc(e, &e->d_info, ns))) return bail(rc);
+  if ((rc = dev_alloc(e, e->d_fail, ns))) return bail(rc);
+  if ((rc = dev_alloc(e, e->d_poison, nsw * (size_t)p.n_clusters))) return bail(rc);
+  if ((rc = dev_alloc(e, e->d_iscal, ns))) return bail(rc);
+  if ((rc = dev_alloc(e, e->d_notcal, ns))) return bail(rc);
+  if ((rc = upload(e, e->d_boff, p.boff))) return bail(rc);
+  if ((rc = upload(e, e->d_packed_off, p.packed_off))) return bail(rc);
+  if ((rc = upload(e, e->d_roff, p.roff))) return bail(rc);
+  if ((rc = upload(e, e->d_rpacked_off, p.rpacked_off))) return bail(rc);
+  if ((rc = dev_alloc(e, e->d_mu, ns * (size_t)std::max(1, p.max_dim)))) return bail(rc);
+  if ((rc = dev_alloc(e, e->d_norm, ns))) return bail(rc);
+  if ((rc = dev_alloc(e, e->d_info, ns))) return bail(rc);
   {
     std::vector<int32_t> rdim(nm);
     for (size_t d = 0; d < nm; ++d) rdim[d] = p.dims[p.n_clusters + d / 2];
     for (int32_t v : rdim) e->max_s = std::max(e->max_s, v);
-    if ((rc = upload(e, &e->d_bdim, p.dims))) return bail(rc);
-    if ((rc = upload(e, &e->d_rdim, rdim))) return bail(rc);
-    if ((rc = dev_alloc(e, &e->d_symflag, 1))) return bail(rc);
+    if ((rc = upload(e, e->d_bdim, p.dims))) return bail(rc);
+    if ((rc = upload(e, e->d_rdim, rdim))) return bail(rc);
+    if ((rc = dev_alloc(e, e->d_symflag, 1))) return bail(rc);
   }
-  if ((rc = dev_alloc(e, &e->d_one_task_off, 2))) return bail(rc);
-  if ((rc = dev_alloc(e, &e->d_one_entry, 1))) return bail(rc);
-  if ((rc = dev_alloc(e, &e->d_one_rec, 1))) return bail(rc);
+  if ((rc = dev_alloc(e, e->d_one_task_off, 2))) return bail(rc);
+  if ((rc = dev_alloc(e, e->d_one_entry, 1))) return bail(rc);
+  if ((rc = dev_alloc(e, e->d_one_rec, 1))) return bail(rc);
   // beliefs = constant function 1 (h, J, g all 0: src/beliefs.jl:108-132); residuals 0;
   // flags false / kldiv -1, empty messages born calibrated (src/beliefs.jl:914-924)
-  if (hipMemsetAsync(e->d_pool, 0, ns * p.pool_stride() * sizeof(double), e->st) != hipSuccess ||
-      hipMemsetAsync(e->d_fpool, 0, ns * p.cluster_stride() * sizeof(double), e->st) != hipSuccess ||
-      hipMemsetAsync(e->d_rpool, 0, ns * p.rpool_stride() * sizeof(double), e->st) != hipSuccess ||
-      hipMemsetAsync(e->d_status, 0, nsw * nm * sizeof(int32_t), e->st) != hipSuccess ||
-      hipMemsetAsync(e->d_flags, 0, nsw * nm * sizeof(int32_t), e->st) != hipSuccess ||
-      hipMemsetAsync(e->d_klflags, 0, nsw * nm * sizeof(int32_t), e->st) != hipSuccess ||
-      hipMemsetAsync(e->d_kldiv, 0, nsw * nm * sizeof(double), e->st) != hipSuccess ||
-      hipMemsetAsync(e->d_poison, 0, nsw * (size_t)p.n_clusters * sizeof(int32_t), e->st) != hipSuccess ||
-      hipMemsetAsync(e->d_fail, 0xFF, ns * sizeof(unsigned long long), e->st) != hipSuccess) {
+  if (hipMemsetAsync(e->d_pool.get(), 0, ns * p.pool_stride() * sizeof(double), e->st) != hipSuccess ||
+      hipMemsetAsync(e->d_fpool.get(), 0, ns * p.cluster_stride() * sizeof(double), e->st) != hipSuccess ||
+      hipMemsetAsync(e->d_rpool.get(), 0, ns * p.rpool_stride() * sizeof(double), e->st) != hipSuccess ||
+      hipMemsetAsync(e->d_status.get(), 0, nsw * nm * sizeof(int32_t), e->st) != hipSuccess ||
+      hipMemsetAsync(e->d_flags.get(), 0, nsw * nm * sizeof(int32_t), e->st) != hipSuccess ||
+      hipMemsetAsync(e->d_klflags.get(), 0, nsw * nm * sizeof(int32_t), e->st) != hipSuccess ||
+      hipMemsetAsync(e->d_kldiv.get(), 0, nsw * nm * sizeof(double), e->st) != hipSuccess ||
+      hipMemsetAsync(e->d_poison.get(), 0, nsw * (size_t)p.n_clusters * sizeof(int32_t), e->st) != hipSuccess ||
+      hipMemsetAsync(e->d_fail.get(), 0xFF, ns * sizeof(unsigned long long), e->st) != hipSuccess) {
     e->err = "hipMemsetAsync failed";
     return bail(PGBP_ERR_HIP);
   }
@@ -794,10 +793,10 @@ int pgbp_init_factors_frombeliefs(pgbp_engine* e) {
   if (!e) return PGBP_ERR_INVALID;
   const Plan& p = e->plan;
   if (e->layout_sm)
-    HIPCHK(e, hipMemcpyAsync(e->d_fpool_sm, e->d_pool_sm, sizeof(double) * (size_t)p.packed_off[p.n_clusters] * (size_t)sm_row(p.n_sites),
+    HIPCHK(e, hipMemcpyAsync(e->sm.fpool.get(), e->sm.pool.get(), sizeof(double) * (size_t)p.packed_off[p.n_clusters] * (size_t)sm_row(p.n_sites),
                              hipMemcpyDeviceToDevice, e->st));
   else
-    launch_copy_strided(e->d_pool, p.pool_stride(), e->d_fpool, p.cluster_stride(), p.cluster_stride(), p.n_sites,
+    launch_copy_strided(e->d_pool.get(), p.pool_stride(), e->d_fpool.get(), p.cluster_stride(), p.cluster_stride(), p.n_sites,
                         e->st);
   e->have_factors = true;
   return pgbp_sync(e);
@@ -813,15 +812,14 @@ int pgbp_set_beliefs(pgbp_engine* e, const double* packed, int32_t snapshot_fact
     e->sym_known = false;
   }
   const int64_t psz = p.packed_off.back();
-  double* stage = nullptr;
-  HIPCHK(e, hipMalloc((void**)&stage, sizeof(double) * (size_t)psz * p.n_sites));
-  hipError_t rc = hipMemcpyAsync(stage, packed, sizeof(double) * (size_t)psz * p.n_sites, hipMemcpyHostToDevice, e->st);
+  DevBuf<double> stage;
+  if (int rc0 = dev_alloc(e, stage, (size_t)psz * p.n_sites)) return rc0;
+  hipError_t rc = hipMemcpyAsync(stage.get(), packed, sizeof(double) * (size_t)psz * p.n_sites, hipMemcpyHostToDevice, e->st);
   if (rc == hipSuccess) {
-    launch_records(stage, psz, e->d_packed_off, e->d_pool, p.pool_stride(), e->d_boff, e->d_packed_off,
+    launch_records(stage.get(), psz, e->d_packed_off.get(), e->d_pool.get(), p.pool_stride(), e->d_boff.get(), e->d_packed_off.get(),
                    p.n_beliefs(), p.n_sites, e->st);
     rc = hipStreamSynchronize(e->st);
   }
-  (void)hipFree(stage);
   if (rc != hipSuccess) return e->fail(PGBP_ERR_HIP, std::string("pgbp_set_beliefs: ") + hipGetErrorString(rc));
   if (snapshot_factors) return pgbp_init_factors_frombeliefs(e);
   return PGBP_OK;
@@ -836,13 +834,12 @@ int pgbp_get_beliefs(pgbp_engine* e, double* packed) {
     if (rc0) return rc0;
   }
   const int64_t psz = p.packed_off.back();
-  double* stage = nullptr;
-  HIPCHK(e, hipMalloc((void**)&stage, sizeof(double) * (size_t)psz * p.n_sites));
-  launch_records(e->d_pool, p.pool_stride(), e->d_boff, stage, psz, e->d_packed_off, e->d_packed_off, p.n_beliefs(),
+  DevBuf<double> stage;
+  if (int rc0 = dev_alloc(e, stage, (size_t)psz * p.n_sites)) return rc0;
+  launch_records(e->d_pool.get(), p.pool_stride(), e->d_boff.get(), stage.get(), psz, e->d_packed_off.get(), e->d_packed_off.get(), p.n_beliefs(),
                  p.n_sites, e->st);
-  hipError_t rc = hipMemcpyAsync(packed, stage, sizeof(double) * (size_t)psz * p.n_sites, hipMemcpyDeviceToHost, e->st);
+  hipError_t rc = hipMemcpyAsync(packed, stage.get(), sizeof(double) * (size_t)psz * p.n_sites, hipMemcpyDeviceToHost, e->st);
   if (rc == hipSuccess) rc = hipStreamSynchronize(e->st);
-  (void)hipFree(stage);
   if (rc != hipSuccess) return e->fail(PGBP_ERR_HIP, std::string("pgbp_get_beliefs: ") + hipGetErrorString(rc));
   return PGBP_OK;
 }
@@ -857,13 +854,12 @@ int pgbp_get_site_beliefs(pgbp_engine* e, int32_t site, double* packed) {
     if (rc0) return rc0;
   }
   const int64_t psz = p.packed_off.back();
-  double* stage = nullptr;
-  HIPCHK(e, hipMalloc((void**)&stage, sizeof(double) * (size_t)std::max<int64_t>(1, psz)));
-  launch_records(e->d_pool + (int64_t)site * p.pool_stride(), p.pool_stride(), e->d_boff, stage, psz, e->d_packed_off,
-                 e->d_packed_off, p.n_beliefs(), 1, e->st);
-  hipError_t rc = hipMemcpyAsync(packed, stage, sizeof(double) * (size_t)psz, hipMemcpyDeviceToHost, e->st);
+  DevBuf<double> stage;
+  if (int rc0 = dev_alloc(e, stage, (size_t)psz)) return rc0;
+  launch_records(e->d_pool.get() + (int64_t)site * p.pool_stride(), p.pool_stride(), e->d_boff.get(), stage.get(), psz, e->d_packed_off.get(),
+                 e->d_packed_off.get(), p.n_beliefs(), 1, e->st);
+  hipError_t rc = hipMemcpyAsync(packed, stage.get(), sizeof(double) * (size_t)psz, hipMemcpyDeviceToHost, e->st);
   if (rc == hipSuccess) rc = hipStreamSynchronize(e->st);
-  (void)hipFree(stage);
   if (rc != hipSuccess) return e->fail(PGBP_ERR_HIP, std::string("pgbp_get_site_beliefs: ") + hipGetErrorString(rc));
   return PGBP_OK;
 }
@@ -872,7 +868,7 @@ static int belief_rec(pgbp_engine* e, int32_t site, int32_t b, double** dptr, in
   const Plan& p = e->plan;
   if (site < 0 || site >= p.n_sites || b < 0 || b >= p.n_beliefs())
     return e->fail(PGBP_ERR_INVALID, "site or belief index out of range");
-  *dptr = e->d_pool + (int64_t)site * p.pool_stride() + p.boff[b];
+  *dptr = e->d_pool.get() + (int64_t)site * p.pool_stride() + p.boff[b];
   *len = p.packed_off[b + 1] - p.packed_off[b];
   return PGBP_OK;
 }
@@ -922,20 +918,16 @@ static int xbuf_prepare(pgbp_engine* e, int32_t site, int32_t n, const int32_t* 
   if (rc) return rc;
   if ((int64_t)off.size() > e->xoff_cap || at > e->xbuf_cap) HIPCHK(e, hipStreamSynchronize(e->st));
   if ((int64_t)off.size() > e->xoff_cap) {
-    if (e->d_xoff) (void)hipFree(e->d_xoff);
-    e->d_xoff = nullptr;
     e->xoff_cap = 0;
-    HIPCHK(e, hipMalloc(reinterpret_cast<void**>(&e->d_xoff), sizeof(int64_t) * off.size()));
+    if ((rc = dev_alloc(e, e->d_xoff, off.size()))) return rc;
     e->xoff_cap = (int64_t)off.size();
   }
   if (at > e->xbuf_cap) {
-    if (e->d_xbuf) (void)hipFree(e->d_xbuf);
-    e->d_xbuf = nullptr;
     e->xbuf_cap = 0;
-    HIPCHK(e, hipMalloc(reinterpret_cast<void**>(&e->d_xbuf), sizeof(double) * (size_t)std::max<int64_t>(at, 1)));
+    if ((rc = dev_alloc(e, e->d_xbuf, (size_t)at))) return rc;
     e->xbuf_cap = std::max<int64_t>(at, 1);
   }
-  HIPCHK(e, hipMemcpyAsync(e->d_xoff, off.data(), sizeof(int64_t) * off.size(), hipMemcpyHostToDevice, e->st));
+  HIPCHK(e, hipMemcpyAsync(e->d_xoff.get(), off.data(), sizeof(int64_t) * off.size(), hipMemcpyHostToDevice, e->st));
   HIPCHK(e, hipStreamSynchronize(e->st));   // (`off` is a local)
   return PGBP_OK;
 }
@@ -957,9 +949,9 @@ int pgbp_pack_beliefs(pgbp_engine* e, int32_t site, int32_t n, const int32_t* be
   int64_t total = 0;
   int rc = xbuf_prepare(e, site, n, beliefs, &total);
   if (rc || n == 0) return rc;
-  launch_pack_records(e->d_pool + (int64_t)site * e->plan.pool_stride(), e->d_xoff, e->d_xoff + n, n, e->d_xbuf, 1, e->st);
+  launch_pack_records(e->d_pool.get() + (int64_t)site * e->plan.pool_stride(), e->d_xoff.get(), e->d_xoff.get() + n, n, e->d_xbuf.get(), 1, e->st);
   HIPCHK(e, hipGetLastError());
-  HIPCHK(e, hipMemcpyAsync(buf, e->d_xbuf, sizeof(double) * (size_t)total, hipMemcpyDeviceToHost, e->st));
+  HIPCHK(e, hipMemcpyAsync(buf, e->d_xbuf.get(), sizeof(double) * (size_t)total, hipMemcpyDeviceToHost, e->st));
   return pgbp_sync(e);
 }
 
@@ -970,8 +962,8 @@ int pgbp_unpack_beliefs(pgbp_engine* e, int32_t site, int32_t n, const int32_t* 
   int rc = xbuf_prepare(e, site, n, beliefs, &total);
   if (rc || n == 0) return rc;
   e->sym_known = false;
-  HIPCHK(e, hipMemcpyAsync(e->d_xbuf, buf, sizeof(double) * (size_t)total, hipMemcpyHostToDevice, e->st));
-  launch_pack_records(e->d_pool + (int64_t)site * e->plan.pool_stride(), e->d_xoff, e->d_xoff + n, n, e->d_xbuf, 0, e->st);
+  HIPCHK(e, hipMemcpyAsync(e->d_xbuf.get(), buf, sizeof(double) * (size_t)total, hipMemcpyHostToDevice, e->st));
+  launch_pack_records(e->d_pool.get() + (int64_t)site * e->plan.pool_stride(), e->d_xoff.get(), e->d_xoff.get() + n, n, e->d_xbuf.get(), 0, e->st);
   HIPCHK(e, hipGetLastError());
   return pgbp_sync(e);
 }
@@ -1003,20 +995,19 @@ int pgbp_get_residuals(pgbp_engine* e, double* packed, int32_t* iscalibrated_res
   const size_t ns = (size_t)p.n_sites, nm = (size_t)p.n_msgs();
   if (packed) {
     const int64_t rsz = p.rpacked_off.back();
-    double* stage = nullptr;
-    HIPCHK(e, hipMalloc((void**)&stage, sizeof(double) * (size_t)std::max<int64_t>(1, rsz) * ns));
-    launch_records(e->d_rpool, p.rpool_stride(), e->d_roff, stage, rsz, e->d_rpacked_off, e->d_rpacked_off,
+    DevBuf<double> stage;
+    if (int rc0 = dev_alloc(e, stage, (size_t)std::max<int64_t>(1, rsz) * ns)) return rc0;
+    launch_records(e->d_rpool.get(), p.rpool_stride(), e->d_roff.get(), stage.get(), rsz, e->d_rpacked_off.get(), e->d_rpacked_off.get(),
                    (int)nm, p.n_sites, e->st);
-    hipError_t rc = hipMemcpyAsync(packed, stage, sizeof(double) * (size_t)rsz * ns, hipMemcpyDeviceToHost, e->st);
+    hipError_t rc = hipMemcpyAsync(packed, stage.get(), sizeof(double) * (size_t)rsz * ns, hipMemcpyDeviceToHost, e->st);
     if (rc == hipSuccess) rc = hipStreamSynchronize(e->st);
-    (void)hipFree(stage);
     if (rc != hipSuccess) return e->fail(PGBP_ERR_HIP, std::string("pgbp_get_residuals: ") + hipGetErrorString(rc));
   }
   if (iscalibrated_resid)
-    HIPCHK(e, hipMemcpyAsync(iscalibrated_resid, e->d_flags, sizeof(int32_t) * ns * nm, hipMemcpyDeviceToHost, e->st));
-  if (kldiv) HIPCHK(e, hipMemcpyAsync(kldiv, e->d_kldiv, sizeof(double) * ns * nm, hipMemcpyDeviceToHost, e->st));
+    HIPCHK(e, hipMemcpyAsync(iscalibrated_resid, e->d_flags.get(), sizeof(int32_t) * ns * nm, hipMemcpyDeviceToHost, e->st));
+  if (kldiv) HIPCHK(e, hipMemcpyAsync(kldiv, e->d_kldiv.get(), sizeof(double) * ns * nm, hipMemcpyDeviceToHost, e->st));
   if (iscalibrated_kl)
-    HIPCHK(e, hipMemcpyAsync(iscalibrated_kl, e->d_klflags, sizeof(int32_t) * ns * nm, hipMemcpyDeviceToHost, e->st));
+    HIPCHK(e, hipMemcpyAsync(iscalibrated_kl, e->d_klflags.get(), sizeof(int32_t) * ns * nm, hipMemcpyDeviceToHost, e->st));
   return pgbp_sync(e);
 }
 
@@ -1032,11 +1023,11 @@ int pgbp_get_residual(pgbp_engine* e, int32_t site, int32_t msg, double* rec, in
   const size_t w = (size_t)site * (size_t)p.n_msgs() + (size_t)msg;
   const int64_t len = p.rpacked_off[msg + 1] - p.rpacked_off[msg];
   if (rec && len > 0)
-    HIPCHK(e, hipMemcpyAsync(rec, e->d_rpool + (int64_t)site * p.rpool_stride() + p.roff[msg], sizeof(double) * (size_t)len,
+    HIPCHK(e, hipMemcpyAsync(rec, e->d_rpool.get() + (int64_t)site * p.rpool_stride() + p.roff[msg], sizeof(double) * (size_t)len,
                              hipMemcpyDeviceToHost, e->st));
-  if (iscalibrated_resid) HIPCHK(e, hipMemcpyAsync(iscalibrated_resid, e->d_flags + w, sizeof(int32_t), hipMemcpyDeviceToHost, e->st));
-  if (kldiv) HIPCHK(e, hipMemcpyAsync(kldiv, e->d_kldiv + w, sizeof(double), hipMemcpyDeviceToHost, e->st));
-  if (iscalibrated_kl) HIPCHK(e, hipMemcpyAsync(iscalibrated_kl, e->d_klflags + w, sizeof(int32_t), hipMemcpyDeviceToHost, e->st));
+  if (iscalibrated_resid) HIPCHK(e, hipMemcpyAsync(iscalibrated_resid, e->d_flags.get() + w, sizeof(int32_t), hipMemcpyDeviceToHost, e->st));
+  if (kldiv) HIPCHK(e, hipMemcpyAsync(kldiv, e->d_kldiv.get() + w, sizeof(double), hipMemcpyDeviceToHost, e->st));
+  if (iscalibrated_kl) HIPCHK(e, hipMemcpyAsync(iscalibrated_kl, e->d_klflags.get() + w, sizeof(int32_t), hipMemcpyDeviceToHost, e->st));
   return pgbp_sync(e);
 }
 
@@ -1053,9 +1044,9 @@ int pgbp_set_schedule(pgbp_engine* e, int32_t n_trees, const int32_t* tree_off, 
   for (int t = 0; t < n_trees && rc == PGBP_OK; ++t) {
     for (int dir = 0; dir < 2 && rc == PGBP_OK; ++dir) {
       const Traversal& tr = dir == 0 ? e->plan.trees[t].post : e->plan.trees[t].pre;
-      DevTraversal& d = dir == 0 ? e->dpost[t] : e->dpre[t];
-      if ((rc = upload(e, &d.d_task_off, tr.task_off))) break;
-      if ((rc = upload(e, &d.d_entries, tr.entries))) break;
+      DevTraversal d;   // (moved into the engine once every buffer of it exists)
+      if ((rc = upload(e, d.d_task_off, tr.task_off))) break;
+      if ((rc = upload(e, d.d_entries, tr.entries))) break;
       if (e->plan.max_dim <= 2 && e->plan.n_sites >= 8 && e->max_s <= 1) {
         // thread-per-site kernel for sepsets of at most one variable: every entry as ONE record (URec)
         const Plan& pl = e->plan;
@@ -1075,34 +1066,33 @@ int pgbp_set_schedule(pgbp_engine* e, int32_t n_trees, const int32_t* tree_off, 
           r.from_p = pl.packed_off[m.from_b]; r.sep_p = pl.packed_off[m.sep_b]; r.to_p = pl.packed_off[m.to_b];
           r.res_p = pl.rpacked_off[en.msg];
         }
-        if ((rc = upload(e, &d.d_urecs, ur))) break;
+        if ((rc = upload(e, d.d_urecs, ur))) break;
       }
-      if ((rc = upload(e, &d.d_fentries, tr.fentries))) break;
+      if ((rc = upload(e, d.d_fentries, tr.fentries))) break;
       if (tr.has_pro) {
-        if ((rc = upload(e, &d.d_fpros, tr.fpros))) break;
-        if ((rc = upload(e, &d.d_cpros, tr.cpros))) break;
+        if ((rc = upload(e, d.d_fpros, tr.fpros))) break;
+        if ((rc = upload(e, d.d_cpros, tr.cpros))) break;
       }
-      if ((rc = upload(e, &d.d_centries, tr.centries))) break;
-      if ((rc = upload(e, &d.d_chunk_wg_off, tr.chunk_wg_off))) break;
+      if ((rc = upload(e, d.d_centries, tr.centries))) break;
+      if ((rc = upload(e, d.d_chunk_wg_off, tr.chunk_wg_off))) break;
       std::vector<int32_t> grp_recs(tr.cgroups);
       for (int32_t& t : grp_recs)
         if (t >= 0) t = tr.task_grec[t];
-      if ((rc = upload(e, &d.d_cgroups, grp_recs))) break;
-      if ((rc = upload(e, &d.d_cgroups_task, tr.cgroups))) break;
-      if ((rc = upload(e, &d.d_grecs, tr.grecs))) break;
-      if ((rc = upload(e, &d.d_rowmap, tr.rowmap))) break;
-      d.kl_big.clear();
+      if ((rc = upload(e, d.d_cgroups, grp_recs))) break;
+      if ((rc = upload(e, d.d_cgroups_task, tr.cgroups))) break;
+      if ((rc = upload(e, d.d_grecs, tr.grecs))) break;
+      if ((rc = upload(e, d.d_rowmap, tr.rowmap))) break;
       for (size_t q = 0; q < tr.entries.size(); ++q)
         if (e->plan.msgs[tr.entries[q].msg].s > kKlLdsMaxS) d.kl_big.push_back((int32_t)q);
-      if ((rc = upload(e, &d.d_kl_big, d.kl_big))) break;
+      if ((rc = upload(e, d.d_kl_big, d.kl_big))) break;
+      (dir == 0 ? e->dpost[t] : e->dpre[t]) = std::move(d);
     }
     if (rc == PGBP_OK) {
       const Tree& T = e->plan.trees[t];
-      FEntry* dt = nullptr;
-      if ((rc = upload(e, &dt, T.tail)) == PGBP_OK) e->d_tail.push_back(dt);
-      FPro* dp = nullptr;   // (null unless a traversal of this tree has prologues)
-      if (rc == PGBP_OK && (T.post.has_pro || T.pre.has_pro)) rc = upload(e, &dp, T.tail_pros);
-      if (rc == PGBP_OK) e->d_tail_pros.push_back(dp);
+      e->d_tail.emplace_back();
+      e->d_tail_pros.emplace_back();   // (null unless a traversal of this tree has prologues)
+      rc = upload(e, e->d_tail.back(), T.tail);
+      if (rc == PGBP_OK && (T.post.has_pro || T.pre.has_pro)) rc = upload(e, e->d_tail_pros.back(), T.tail_pros);
     }
   }
   if (rc) {  // out of device memory half way: leave the engine without a schedule rather than with half of one
@@ -1133,20 +1123,20 @@ int pgbp_propagate(pgbp_engine* e, int32_t cluster_to, int32_t sepset, int32_t c
   if ((rc = ensure_layout(e, false))) return rc;  // single messages run on the generic kernel
   const int32_t toff[2] = {0, 1};
   Entry en{2 * k + dir, 0, 0, 0};
-  HIPCHK(e, hipMemcpyAsync(e->d_one_task_off, toff, sizeof(toff), hipMemcpyHostToDevice, e->st));
-  HIPCHK(e, hipMemcpyAsync(e->d_one_entry, &en, sizeof(en), hipMemcpyHostToDevice, e->st));
+  HIPCHK(e, hipMemcpyAsync(e->d_one_task_off.get(), toff, sizeof(toff), hipMemcpyHostToDevice, e->st));
+  HIPCHK(e, hipMemcpyAsync(e->d_one_entry.get(), &en, sizeof(en), hipMemcpyHostToDevice, e->st));
   if ((rc = reset_fail(e))) return rc;
   DevState S = dev_state(e, opts);
   if (big_msg(p.msgs[en.msg])) {
     if ((rc = ensure_ws(e, (int64_t)p.n_sites * big_ws_doubles(p.msgs[en.msg].mf)))) return rc;
-    launch_level_big(S, e->d_one_task_off, e->d_one_entry, 0, 1, p.n_sites, 0, 0, p.msgs[en.msg].mf, e->d_ws, e->st);
+    launch_level_big(S, e->d_one_task_off.get(), e->d_one_entry.get(), 0, 1, p.n_sites, 0, 0, p.msgs[en.msg].mf, e->d_ws.get(), e->st);
   } else {
     const GRec rec = make_grec(p, en, -1);
-    HIPCHK(e, hipMemcpyAsync(e->d_one_rec, &rec, sizeof(rec), hipMemcpyHostToDevice, e->st));
-    launch_level_generic(S, e->d_one_rec, 0, 1, p.n_sites, 0, 0, p.msgs[en.msg].mf, false, e->st);
+    HIPCHK(e, hipMemcpyAsync(e->d_one_rec.get(), &rec, sizeof(rec), hipMemcpyHostToDevice, e->st));
+    launch_level_generic(S, e->d_one_rec.get(), 0, 1, p.n_sites, 0, 0, p.msgs[en.msg].mf, false, e->st);
   }
   std::vector<unsigned long long> keys(p.n_sites);
-  HIPCHK(e, hipMemcpyAsync(keys.data(), e->d_fail, sizeof(unsigned long long) * p.n_sites, hipMemcpyDeviceToHost, e->st));
+  HIPCHK(e, hipMemcpyAsync(keys.data(), e->d_fail.get(), sizeof(unsigned long long) * p.n_sites, hipMemcpyDeviceToHost, e->st));
   HIPCHK(e, hipStreamSynchronize(e->st));
   HIPCHK(e, hipGetLastError());
   if (info)
@@ -1175,8 +1165,8 @@ int pgbp_residual_kldiv(pgbp_engine* e, int32_t cluster_to, int32_t sepset, int3
   Entry en{2 * k + dir, 0, 0, 0};
   const int s_msg = p.msgs[en.msg].s;
   const int32_t toff[2] = {0, 1};   // (d_one_task_off[0] = 0 doubles as the list "entry 0" of the workspace instance)
-  HIPCHK(e, hipMemcpyAsync(e->d_one_task_off, toff, sizeof(toff), hipMemcpyHostToDevice, e->st));
-  HIPCHK(e, hipMemcpyAsync(e->d_one_entry, &en, sizeof(en), hipMemcpyHostToDevice, e->st));
+  HIPCHK(e, hipMemcpyAsync(e->d_one_task_off.get(), toff, sizeof(toff), hipMemcpyHostToDevice, e->st));
+  HIPCHK(e, hipMemcpyAsync(e->d_one_entry.get(), &en, sizeof(en), hipMemcpyHostToDevice, e->st));
   HIPCHK(e, hipStreamSynchronize(e->st));   // (toff, en: locals)
   const bool kl_ws = s_msg > kKlLdsMaxS;
   if (kl_ws && (rc = ensure_ws(e, (int64_t)p.n_sites * kldiv_ws_doubles(s_msg)))) return rc;
@@ -1184,11 +1174,11 @@ int pgbp_residual_kldiv(pgbp_engine* e, int32_t cluster_to, int32_t sepset, int3
   DevState S = dev_state(e, opts);
   // a standalone call always computes (stop_below = 0; the status of the last attempt of this message still gates)
   e->kl_flags_clean = e->kl_div_clean = false;
-  launch_residual_kldiv(S, e->d_one_entry, 0, 1, s_msg, e->d_kldiv, e->d_klflags, p.n_sites, 0, e->st,
-                        kl_ws ? e->d_one_task_off : nullptr, kl_ws ? 1 : 0, e->d_ws);
+  launch_residual_kldiv(S, e->d_one_entry.get(), 0, 1, s_msg, e->d_kldiv.get(), e->d_klflags.get(), p.n_sites, 0, e->st,
+                        kl_ws ? e->d_one_task_off.get() : nullptr, kl_ws ? 1 : 0, e->d_ws.get());
   if (iscalibrated_kl) {
     std::vector<int32_t> all((size_t)p.n_sites * std::max(1, p.n_msgs()));
-    HIPCHK(e, hipMemcpyAsync(all.data(), e->d_klflags, sizeof(int32_t) * (size_t)p.n_sites * p.n_msgs(),
+    HIPCHK(e, hipMemcpyAsync(all.data(), e->d_klflags.get(), sizeof(int32_t) * (size_t)p.n_sites * p.n_msgs(),
                              hipMemcpyDeviceToHost, e->st));
     HIPCHK(e, hipStreamSynchronize(e->st));
     for (int s = 0; s < p.n_sites; ++s) iscalibrated_kl[s] = all[(size_t)s * p.n_msgs() + en.msg];
@@ -1204,8 +1194,8 @@ int pgbp_regularize_bycluster(pgbp_engine* e) {
   const Plan& p = e->plan;
   int rc = ensure_layout(e, false);
   if (rc) return rc;
-  launch_regularize_bycluster(e->d_pool, p.pool_stride(), e->d_boff, e->d_bdim, e->d_nb_off, e->d_nb_msg, e->d_msgs,
-                              e->d_idx, e->d_sepcl, e->d_eps, p.n_clusters, p.n_sepsets, p.n_sites, e->st);
+  launch_regularize_bycluster(e->d_pool.get(), p.pool_stride(), e->d_boff.get(), e->d_bdim.get(), e->d_nb_off.get(), e->d_nb_msg.get(), e->d_msgs.get(),
+                              e->d_idx.get(), e->d_sepcl.get(), e->d_eps.get(), p.n_clusters, p.n_sepsets, p.n_sites, e->st);
   e->sym_known = false;
   HIPCHK(e, hipGetLastError());
   return PGBP_OK;
@@ -1222,10 +1212,11 @@ int pgbp_regularize_onschedule(pgbp_engine* e, int32_t site_begin, int32_t site_
   if (rc) return rc;
   const OnSchedule& os = plan_onschedule(p);
   if (!e->os_ready) {
-    if ((rc = upload(e, &e->d_os_a_cl, os.a_cl)) || (rc = upload(e, &e->d_os_ed_off, os.ed_off)) ||
-        (rc = upload(e, &e->d_os_ed_msg, os.ed_msg)) || (rc = upload(e, &e->d_os_task_off, os.task_off)) ||
-        (rc = upload(e, &e->d_os_grecs, os.grecs)) || (rc = upload(e, &e->d_os_entries, os.entries)))
+    OsBufs B;
+    if ((rc = upload(e, B.a_cl, os.a_cl)) || (rc = upload(e, B.ed_off, os.ed_off)) || (rc = upload(e, B.ed_msg, os.ed_msg)) ||
+        (rc = upload(e, B.task_off, os.task_off)) || (rc = upload(e, B.grecs, os.grecs)) || (rc = upload(e, B.entries, os.entries)))
       return rc;
+    e->os = std::move(B);
     e->os_ready = true;
   }
   const int ns = site_end - site_begin;
@@ -1248,22 +1239,22 @@ int pgbp_regularize_onschedule(pgbp_engine* e, int32_t site_begin, int32_t site_
     // (poison), and everything downstream of a message comes later than it in walk order, so the lowest fail key of a
     // site is the walk's first failure.
     for (int L = 0; L < os.n_levels; ++L) {
-      launch_regularize_onschedule(S.pool, S.pool_stride, e->d_bdim, e->d_os_a_cl, os.level_a_off[L],
-                                   os.level_a_off[L + 1] - os.level_a_off[L], e->d_os_ed_off, e->d_os_ed_msg, e->d_msgs,
-                                   e->d_idx, ns, e->st);
+      launch_regularize_onschedule(S.pool, S.pool_stride, e->d_bdim.get(), e->os.a_cl.get(), os.level_a_off[L],
+                                   os.level_a_off[L + 1] - os.level_a_off[L], e->os.ed_off.get(), e->os.ed_msg.get(), e->d_msgs.get(),
+                                   e->d_idx.get(), ns, e->st);
       for (int q = os.level_launch_off[L]; q < os.level_launch_off[L + 1]; ++q) {
         const OnSchedule::Launch& ln = os.launches[q];
         if (ln.kind == 0)
-          launch_level_generic(S, e->d_os_grecs, ln.first, ln.n, ns, 0, 0, ln.max_mf, false, e->st);
+          launch_level_generic(S, e->os.grecs.get(), ln.first, ln.n, ns, 0, 0, ln.max_mf, false, e->st);
         else
-          launch_level_big(S, e->d_os_task_off, e->d_os_entries, ln.first, ln.n, ns, 0, 0, ln.max_mf, e->d_ws, e->st);
+          launch_level_big(S, e->os.task_off.get(), e->os.entries.get(), ln.first, ln.n, ns, 0, 0, ln.max_mf, e->d_ws.get(), e->st);
       }
     }
     e->sym_known = false;
   }
   std::vector<unsigned long long> keys(std::max(1, ns), kNoFail);
   if (ns > 0)
-    HIPCHK(e, hipMemcpyAsync(keys.data(), e->d_fail + site_begin, sizeof(unsigned long long) * ns, hipMemcpyDeviceToHost,
+    HIPCHK(e, hipMemcpyAsync(keys.data(), e->d_fail.get() + site_begin, sizeof(unsigned long long) * ns, hipMemcpyDeviceToHost,
                              e->st));
   HIPCHK(e, hipStreamSynchronize(e->st));
   HIPCHK(e, hipGetLastError());
@@ -1287,8 +1278,8 @@ static int collect_results(pgbp_engine* e, pgbp_result* results, const std::vect
   const int ns = p.n_sites;
   std::vector<unsigned long long> keys(ns);
   std::vector<int32_t> iscal(ns);
-  HIPCHK(e, hipMemcpyAsync(keys.data(), e->d_fail, sizeof(unsigned long long) * ns, hipMemcpyDeviceToHost, e->st));
-  HIPCHK(e, hipMemcpyAsync(iscal.data(), e->d_iscal, sizeof(int32_t) * ns, hipMemcpyDeviceToHost, e->st));
+  HIPCHK(e, hipMemcpyAsync(keys.data(), e->d_fail.get(), sizeof(unsigned long long) * ns, hipMemcpyDeviceToHost, e->st));
+  HIPCHK(e, hipMemcpyAsync(iscal.data(), e->d_iscal.get(), sizeof(int32_t) * ns, hipMemcpyDeviceToHost, e->st));
   HIPCHK(e, hipStreamSynchronize(e->st));
   HIPCHK(e, hipGetLastError());
   if (const int erc = e->take_enqueue_rc()) return erc;
@@ -1329,7 +1320,7 @@ int pgbp_traverse(pgbp_engine* e, int32_t tree, int32_t dir, const pgbp_opts* op
   if ((rc = ensure_layout(e, want_bs16(e), want_site_minor(e) && !(opts && opts->update_residualkldiv)))) return rc;
   DevState S = dev_state(e, opts);
   enqueue_tree(e, S, tree, dir == 0 ? 1 : 2, (unsigned long long)tree, opts && opts->update_residualkldiv);
-  launch_reduce_flags(e->d_flags, p.n_msgs(), p.n_sites, e->d_iscal, e->st, e->layout_sm ? 1 : 0);
+  launch_reduce_flags(e->d_flags.get(), p.n_msgs(), p.n_sites, e->d_iscal.get(), e->st, e->layout_sm ? 1 : 0);
   return collect_results(e, results, nullptr, 0);
 }
 
@@ -1352,14 +1343,12 @@ int pgbp_calibrate(pgbp_engine* e, int32_t niter, const pgbp_opts* opts, pgbp_re
   const bool kl = opts && opts->update_residualkldiv;
   const int64_t n_pairs_max = (int64_t)niter * nt;
   if (n_pairs_max > e->hist_cap) {
-    if (e->d_iscal_hist) (void)hipFree(e->d_iscal_hist);
-    e->d_iscal_hist = nullptr;
     e->hist_cap = 0;
-    if ((rc = dev_alloc(e, &e->d_iscal_hist, (size_t)n_pairs_max * ns))) return rc;
+    if ((rc = dev_alloc(e, e->d_iscal_hist, (size_t)n_pairs_max * ns))) return rc;
     e->hist_cap = n_pairs_max;
   }
   if ((rc = reset_fail(e))) return rc;
-  HIPCHK(e, hipMemsetAsync(e->d_iscal, 0, sizeof(int32_t) * ns, e->st));
+  HIPCHK(e, hipMemsetAsync(e->d_iscal.get(), 0, sizeof(int32_t) * ns, e->st));
   if ((rc = ensure_layout(e, want_bs16(e), want_site_minor(e) && !(opts && opts->update_residualkldiv)))) return rc;
   DevState S = dev_state(e, opts);
   int pairs_done = 0;
@@ -1379,16 +1368,16 @@ int pgbp_calibrate(pgbp_engine* e, int32_t niter, const pgbp_opts* opts, pgbp_re
   for (int i = 0; i < niter && !stop; ++i) {
     for (int j = 0; j < nt && !stop; ++j) {
       const unsigned long long pair = (unsigned long long)i * nt + j;
-      enqueue_pair_and_iscal(e, S, j, pair, kl, e->d_iscal_hist + pair * ns);
+      enqueue_pair_and_iscal(e, S, j, pair, kl, e->d_iscal_hist.get() + pair * ns);
       ++pairs_done;
       if (!auto_stop) continue;
-      launch_halt_if_calibrated(e->d_iscal_hist + pair * ns, e->d_fail, ((pair + 1) * stride - 1) << kInfoBits, ns, e->st);
+      launch_halt_if_calibrated(e->d_iscal_hist.get() + pair * ns, e->d_fail.get(), ((pair + 1) * stride - 1) << kInfoBits, ns, e->st);
       const bool last = (i == niter - 1 && j == nt - 1);
       if (pairs_done - batch_first < kAhead && !last) continue;
       const int nb = pairs_done - batch_first;
       now.resize((size_t)nb * ns);
-      HIPCHK(e, hipMemcpyAsync(now.data(), e->d_iscal_hist + (size_t)batch_first * ns, sizeof(int32_t) * now.size(), hipMemcpyDeviceToHost, e->st));
-      HIPCHK(e, hipMemcpyAsync(keys.data(), e->d_fail, sizeof(unsigned long long) * ns, hipMemcpyDeviceToHost, e->st));
+      HIPCHK(e, hipMemcpyAsync(now.data(), e->d_iscal_hist.get() + (size_t)batch_first * ns, sizeof(int32_t) * now.size(), hipMemcpyDeviceToHost, e->st));
+      HIPCHK(e, hipMemcpyAsync(keys.data(), e->d_fail.get(), sizeof(unsigned long long) * ns, hipMemcpyDeviceToHost, e->st));
       HIPCHK(e, hipStreamSynchronize(e->st));
       for (int s = 0; s < ns; ++s) {
         if (site_done[s]) continue;
@@ -1411,8 +1400,8 @@ int pgbp_calibrate(pgbp_engine* e, int32_t niter, const pgbp_opts* opts, pgbp_re
   }
   std::vector<int32_t> hist((size_t)std::max(1, pairs_done) * ns, 0);
   if (pairs_done > 0) {
-    HIPCHK(e, hipMemcpyAsync(hist.data(), e->d_iscal_hist, sizeof(int32_t) * (size_t)pairs_done * ns, hipMemcpyDeviceToHost, e->st));
-    HIPCHK(e, hipMemcpyAsync(e->d_iscal, e->d_iscal_hist + (size_t)(pairs_done - 1) * ns, sizeof(int32_t) * ns, hipMemcpyDeviceToDevice, e->st));
+    HIPCHK(e, hipMemcpyAsync(hist.data(), e->d_iscal_hist.get(), sizeof(int32_t) * (size_t)pairs_done * ns, hipMemcpyDeviceToHost, e->st));
+    HIPCHK(e, hipMemcpyAsync(e->d_iscal.get(), e->d_iscal_hist.get() + (size_t)(pairs_done - 1) * ns, sizeof(int32_t) * ns, hipMemcpyDeviceToDevice, e->st));
   }
   return collect_results(e, results, &hist, pairs_done);
 }
@@ -1424,15 +1413,15 @@ int pgbp_integrate(pgbp_engine* e, int32_t belief, double* mu, double* norm, int
   if (belief < 0 || belief >= p.n_beliefs()) return e->fail(PGBP_ERR_INVALID, "belief index out of range");
   const int m = p.dims[belief];
   const int ns = p.n_sites;
-  integrate_async(e, belief, mu ? e->d_mu : nullptr);
-  HIPCHK(e, hipMemcpyAsync(norm, e->d_norm, sizeof(double) * ns, hipMemcpyDeviceToHost, e->st));
+  integrate_async(e, belief, mu ? e->d_mu.get() : nullptr);
+  HIPCHK(e, hipMemcpyAsync(norm, e->d_norm.get(), sizeof(double) * ns, hipMemcpyDeviceToHost, e->st));
   std::vector<double> mus;
   if (mu && m > 0) {
     mus.resize((size_t)ns * std::max(1, p.max_dim));
-    HIPCHK(e, hipMemcpyAsync(mus.data(), e->d_mu, sizeof(double) * mus.size(), hipMemcpyDeviceToHost, e->st));
+    HIPCHK(e, hipMemcpyAsync(mus.data(), e->d_mu.get(), sizeof(double) * mus.size(), hipMemcpyDeviceToHost, e->st));
   }
   std::vector<int32_t> inf(ns);
-  HIPCHK(e, hipMemcpyAsync(inf.data(), e->d_info, sizeof(int32_t) * ns, hipMemcpyDeviceToHost, e->st));
+  HIPCHK(e, hipMemcpyAsync(inf.data(), e->d_info.get(), sizeof(int32_t) * ns, hipMemcpyDeviceToHost, e->st));
   HIPCHK(e, hipStreamSynchronize(e->st));
   HIPCHK(e, hipGetLastError());
   if (const int erc = e->take_enqueue_rc()) return erc;
@@ -1460,29 +1449,27 @@ int pgbp_free_energy(pgbp_engine* e, double* out3, int32_t* info) {
   std::vector<int32_t> big;
   for (int b = 0; b < p.n_beliefs(); ++b)
     if (p.dims[b] > kFreeEnergyLdsMaxDim) big.push_back(b);
-  double *d_contrib = nullptr, *d_out = nullptr;
-  int32_t *d_inf = nullptr, *d_big = nullptr;
+  DevBuf<double> d_contrib, d_out;
+  DevBuf<int32_t> d_inf, d_big;
   int rc;
   if (!big.empty()) {
     if ((rc = ensure_ws(e, (int64_t)big.size() * ns * free_energy_ws_doubles(p.max_dim)))) return rc;
-    if ((rc = upload(e, &d_big, big))) return rc;
+    if ((rc = upload(e, d_big, big))) return rc;
   }
-  if ((rc = dev_alloc(e, &d_contrib, (size_t)2 * ns * p.n_beliefs()))) { if (d_big) (void)hipFree(d_big); return rc; }
-  if ((rc = dev_alloc(e, &d_out, (size_t)3 * ns))) { (void)hipFree(d_contrib); if (d_big) (void)hipFree(d_big); return rc; }
-  if ((rc = dev_alloc(e, &d_inf, (size_t)ns))) { (void)hipFree(d_contrib); (void)hipFree(d_out); if (d_big) (void)hipFree(d_big); return rc; }
+  if ((rc = dev_alloc(e, d_contrib, (size_t)2 * ns * p.n_beliefs()))) return rc;
+  if ((rc = dev_alloc(e, d_out, (size_t)3 * ns))) return rc;
+  if ((rc = dev_alloc(e, d_inf, (size_t)ns))) return rc;
   std::vector<int32_t> inf(ns, 0x7fffffff);
-  hipError_t herr = hipMemcpyAsync(d_inf, inf.data(), sizeof(int32_t) * ns, hipMemcpyHostToDevice, e->st);
+  hipError_t herr = hipMemcpyAsync(d_inf.get(), inf.data(), sizeof(int32_t) * ns, hipMemcpyHostToDevice, e->st);
   if (herr == hipSuccess) {
-    launch_free_energy(e->d_pool, p.pool_stride(), e->d_fpool, p.cluster_stride(), e->d_boff, e->d_bdim, p.n_clusters,
-                       p.n_beliefs(), p.max_dim, e->layout_bs16 ? 1 : 0, p.fast_p, d_contrib, d_out, d_inf, ns, e->st, d_big,
-                       (int)big.size(), e->d_ws);
-    herr = hipMemcpyAsync(out3, d_out, sizeof(double) * 3 * ns, hipMemcpyDeviceToHost, e->st);
+    launch_free_energy(e->d_pool.get(), p.pool_stride(), e->d_fpool.get(), p.cluster_stride(), e->d_boff.get(), e->d_bdim.get(), p.n_clusters,
+                       p.n_beliefs(), p.max_dim, e->layout_bs16 ? 1 : 0, p.fast_p, d_contrib.get(), d_out.get(), d_inf.get(), ns, e->st,
+                       d_big.get(), (int)big.size(), e->d_ws.get());
+    herr = hipMemcpyAsync(out3, d_out.get(), sizeof(double) * 3 * ns, hipMemcpyDeviceToHost, e->st);
   }
-  if (herr == hipSuccess) herr = hipMemcpyAsync(inf.data(), d_inf, sizeof(int32_t) * ns, hipMemcpyDeviceToHost, e->st);
+  if (herr == hipSuccess) herr = hipMemcpyAsync(inf.data(), d_inf.get(), sizeof(int32_t) * ns, hipMemcpyDeviceToHost, e->st);
   if (herr == hipSuccess) herr = hipStreamSynchronize(e->st);
   if (herr == hipSuccess) herr = hipGetLastError();
-  (void)hipFree(d_contrib); (void)hipFree(d_out); (void)hipFree(d_inf);
-  if (d_big) (void)hipFree(d_big);
   if (herr != hipSuccess) return e->fail(PGBP_ERR_HIP, std::string("pgbp_free_energy: ") + hipGetErrorString(herr));
   if (info)
     for (int s = 0; s < ns; ++s) info[s] = inf[s] == 0x7fffffff ? 0 : inf[s];
@@ -1506,34 +1493,28 @@ int pgbp_bm_tree_setup(pgbp_engine* e, const pgbp_bm_tree* t) {
       return e->fail(PGBP_ERR_INVALID, "pgbp_bm_tree_setup: cluster " + std::to_string(c) + ": kind, dimension, branch length or data row inconsistent");
   }
   if (t->n_rows > 0 && !t->data) return e->fail(PGBP_ERR_INVALID, "pgbp_bm_tree_setup: data missing");
-  for (void* q : {(void*)e->d_bm_kind, (void*)e->d_bm_row, (void*)e->d_bm_length, (void*)e->d_bm_data, (void*)e->d_bm_Rinv,
-                  (void*)e->d_bm_logdet, (void*)e->d_bm_mu})
-    if (q) (void)hipFree(q);
-  e->d_bm_kind = e->d_bm_row = nullptr;
-  e->d_bm_length = e->d_bm_data = e->d_bm_Rinv = e->d_bm_logdet = e->d_bm_mu = nullptr;
+  BmBufs B;   // (a failure leaves the previous set-up in force)
   int rc;
-  if ((rc = upload(e, &e->d_bm_kind, std::vector<int32_t>(t->kind, t->kind + nc)))) return rc;
-  if ((rc = upload(e, &e->d_bm_row, std::vector<int32_t>(t->data_row, t->data_row + nc)))) return rc;
-  if ((rc = upload(e, &e->d_bm_length, std::vector<double>(t->length, t->length + nc)))) return rc;
-  if (e->d_bm_ithl) (void)hipFree(e->d_bm_ithl);
-  e->d_bm_ithl = nullptr;
-  if ((rc = dev_alloc(e, &e->d_bm_ithl, (size_t)nc))) return rc;
-  launch_bm_ithl(e->d_bm_length, e->d_bm_kind, t->p, e->d_bm_ithl, nc, e->st);
+  if ((rc = upload(e, B.kind, std::vector<int32_t>(t->kind, t->kind + nc)))) return rc;
+  if ((rc = upload(e, B.row, std::vector<int32_t>(t->data_row, t->data_row + nc)))) return rc;
+  if ((rc = upload(e, B.length, std::vector<double>(t->length, t->length + nc)))) return rc;
+  if ((rc = dev_alloc(e, B.ithl, (size_t)nc))) return rc;
+  launch_bm_ithl(B.length.get(), B.kind.get(), t->p, B.ithl.get(), nc, e->st);
   const size_t nd = (size_t)p.n_sites * t->n_rows * t->p;
-  if ((rc = dev_alloc(e, &e->d_bm_data, nd))) return rc;
-  if (nd) HIPCHK(e, hipMemcpy(e->d_bm_data, t->data, nd * sizeof(double), hipMemcpyHostToDevice));
-  if (e->d_bm_data_sm) (void)hipFree(e->d_bm_data_sm);
-  e->d_bm_data_sm = nullptr;
+  if ((rc = dev_alloc(e, B.data, nd))) return rc;
+  if (nd) HIPCHK(e, hipMemcpy(B.data.get(), t->data, nd * sizeof(double), hipMemcpyHostToDevice));
   if (t->p == 1 && t->n_rows > 0) {   // univariate batches: [row][site] copy for the thread-per-site fill
-    if ((rc = dev_alloc(e, &e->d_bm_data_sm, (size_t)t->n_rows * (size_t)sm_row(p.n_sites)))) return rc;
-    launch_transpose_words_f64(e->d_bm_data, e->d_bm_data_sm, t->n_rows, p.n_sites, 1, e->st);
+    if ((rc = dev_alloc(e, B.data_sm, (size_t)t->n_rows * (size_t)sm_row(p.n_sites)))) return rc;
+    launch_transpose_words_f64(B.data.get(), B.data_sm.get(), t->n_rows, p.n_sites, 1, e->st);
     HIPCHK(e, hipStreamSynchronize(e->st));
   }
-  if ((rc = dev_alloc(e, &e->d_bm_Rinv, (size_t)p.n_sites * t->p * t->p))) return rc;
-  if ((rc = dev_alloc(e, &e->d_bm_logdet, (size_t)p.n_sites))) return rc;
-  if ((rc = dev_alloc(e, &e->d_bm_mu, (size_t)p.n_sites * t->p))) return rc;
+  if ((rc = dev_alloc(e, B.Rinv, (size_t)p.n_sites * t->p * t->p))) return rc;
+  if ((rc = dev_alloc(e, B.logdet, (size_t)p.n_sites))) return rc;
+  if ((rc = dev_alloc(e, B.mu, (size_t)p.n_sites * t->p))) return rc;
+  e->bm = std::move(B);
   e->bm_p = t->p;
   e->bm_rows = t->n_rows;
+  e->bm_ready = true;
   return PGBP_OK;
 }
 
@@ -1542,11 +1523,11 @@ int pgbp_bm_tree_setup(pgbp_engine* e, const pgbp_bm_tree* t) {
 static int bm_fill_async(pgbp_engine* e, bool also_factors, bool skip_sepsets = false) {
   const Plan& p = e->plan;
   if (e->layout_sm && e->bm_p == 1) {  // univariate batch, site-minor state
-    launch_bm_tree_fill_uni_sm(e->d_pool_sm, also_factors ? e->d_fpool_sm : nullptr, e->d_packed_off, e->d_bdim,
-                               e->d_bm_kind, e->d_bm_length, e->d_bm_row, e->d_bm_data_sm, e->bm_rows, e->d_bm_Rinv,
-                               e->d_bm_logdet, e->d_bm_mu, e->bm_per_site, p.n_clusters, p.n_sites, e->st);
+    launch_bm_tree_fill_uni_sm(e->sm.pool.get(), also_factors ? e->sm.fpool.get() : nullptr, e->d_packed_off.get(), e->d_bdim.get(),
+                               e->bm.kind.get(), e->bm.length.get(), e->bm.row.get(), e->bm.data_sm.get(), e->bm_rows, e->bm.Rinv.get(),
+                               e->bm.logdet.get(), e->bm.mu.get(), e->bm_per_site, p.n_clusters, p.n_sites, e->st);
     const int64_t nc = p.packed_off[p.n_clusters] * sm_row(p.n_sites), nall = p.packed_off.back() * sm_row(p.n_sites);
-    if (!skip_sepsets) HIPCHK(e, hipMemsetAsync(e->d_pool_sm + nc, 0, sizeof(double) * (size_t)(nall - nc), e->st));  // sepsets = 1
+    if (!skip_sepsets) HIPCHK(e, hipMemsetAsync(e->sm.pool.get() + nc, 0, sizeof(double) * (size_t)(nall - nc), e->st));  // sepsets = 1
     reset_message_flags(e, also_factors ? 1 : 0);
     if (also_factors) e->have_factors = true;
     return PGBP_OK;
@@ -1555,21 +1536,21 @@ static int bm_fill_async(pgbp_engine* e, bool also_factors, bool skip_sepsets = 
     const int rc0 = ensure_site_minor(e, false);
     if (rc0) return rc0;
   }
-  double* fp = also_factors ? e->d_fpool : nullptr;
+  double* fp = also_factors ? e->d_fpool.get() : nullptr;
   bool done = false;
   if (e->bm_p == p.fast_p)  // lane-blocked instance: every cluster has dimension 0, p or 2p (checked at setup)
-    done = launch_bm_tree_fill_fast(e->d_pool, p.pool_stride(), fp, p.cluster_stride(), e->d_boff, e->d_bdim, e->d_bm_kind,
-                                    e->d_bm_ithl, e->d_bm_row, e->d_bm_data, e->bm_rows, e->bm_p, e->d_bm_Rinv,
-                                    e->d_bm_logdet, e->d_bm_mu, e->bm_per_site, e->layout_bs16 ? 1 : 0, p.n_clusters,
+    done = launch_bm_tree_fill_fast(e->d_pool.get(), p.pool_stride(), fp, p.cluster_stride(), e->d_boff.get(), e->d_bdim.get(), e->bm.kind.get(),
+                                    e->bm.ithl.get(), e->bm.row.get(), e->bm.data.get(), e->bm_rows, e->bm_p, e->bm.Rinv.get(),
+                                    e->bm.logdet.get(), e->bm.mu.get(), e->bm_per_site, e->layout_bs16 ? 1 : 0, p.n_clusters,
                                     p.n_sites, e->st);
   if (!done) {
-    launch_bm_tree_fill(e->d_pool, p.pool_stride(), e->d_fpool, p.cluster_stride(), e->d_boff, e->d_bdim, e->d_bm_kind,
-                        e->d_bm_length, e->d_bm_row, e->d_bm_data, e->bm_rows, e->bm_p, e->d_bm_Rinv, e->d_bm_logdet,
-                        e->d_bm_mu, e->bm_per_site, e->layout_bs16 ? 1 : 0, p.fast_p, p.n_clusters, p.n_sites, e->st);
+    launch_bm_tree_fill(e->d_pool.get(), p.pool_stride(), e->d_fpool.get(), p.cluster_stride(), e->d_boff.get(), e->d_bdim.get(), e->bm.kind.get(),
+                        e->bm.length.get(), e->bm.row.get(), e->bm.data.get(), e->bm_rows, e->bm_p, e->bm.Rinv.get(), e->bm.logdet.get(),
+                        e->bm.mu.get(), e->bm_per_site, e->layout_bs16 ? 1 : 0, p.fast_p, p.n_clusters, p.n_sites, e->st);
     also_factors = true;  // the general kernel always writes both
   }
   if (!skip_sepsets)
-    launch_zero_strided(e->d_pool + p.cluster_stride(), p.pool_stride(), p.pool_stride() - p.cluster_stride(),
+    launch_zero_strided(e->d_pool.get() + p.cluster_stride(), p.pool_stride(), p.pool_stride() - p.cluster_stride(),
                         p.n_sites, e->st);  // sepsets = 1 (init_beliefs_reset!)
   reset_message_flags(e, also_factors ? 1 : 0);
   if (also_factors) e->have_factors = true;
@@ -1580,11 +1561,11 @@ int pgbp_bm_tree_assignfactors(pgbp_engine* e, const double* Rinv, const double*
                                int32_t per_site) {
   DeviceScope device_scope(e);
   if (!e || !Rinv || !logdetR || !mu) return PGBP_ERR_INVALID;
-  if (!e->d_bm_kind) return e->fail(PGBP_ERR_STATE, "pgbp_bm_tree_assignfactors: call pgbp_bm_tree_setup first");
+  if (!e->bm_ready) return e->fail(PGBP_ERR_STATE, "pgbp_bm_tree_assignfactors: call pgbp_bm_tree_setup first");
   const size_t n = per_site ? (size_t)e->plan.n_sites : 1, pp = (size_t)e->bm_p;
-  HIPCHK(e, hipMemcpyAsync(e->d_bm_Rinv, Rinv, n * pp * pp * sizeof(double), hipMemcpyHostToDevice, e->st));
-  HIPCHK(e, hipMemcpyAsync(e->d_bm_logdet, logdetR, n * sizeof(double), hipMemcpyHostToDevice, e->st));
-  HIPCHK(e, hipMemcpyAsync(e->d_bm_mu, mu, n * pp * sizeof(double), hipMemcpyHostToDevice, e->st));
+  HIPCHK(e, hipMemcpyAsync(e->bm.Rinv.get(), Rinv, n * pp * pp * sizeof(double), hipMemcpyHostToDevice, e->st));
+  HIPCHK(e, hipMemcpyAsync(e->bm.logdet.get(), logdetR, n * sizeof(double), hipMemcpyHostToDevice, e->st));
+  HIPCHK(e, hipMemcpyAsync(e->bm.mu.get(), mu, n * pp * sizeof(double), hipMemcpyHostToDevice, e->st));
   e->bm_per_site = per_site ? 1 : 0;
   // R^-1 is symmetric and the fill writes symmetric blocks: the layout the traversals want can be kept
   e->sym_known = true;
@@ -1602,7 +1583,7 @@ int pgbp_enqueue_loglik_bm(pgbp_engine* e, int32_t reps, const pgbp_opts* opts) 
   int rc = check_opts(e, opts);
   if (rc) return rc;
   if ((rc = need_schedule(e, 0))) return rc;
-  if (!e->d_bm_kind) return e->fail(PGBP_ERR_STATE, "pgbp_enqueue_loglik_bm: call pgbp_bm_tree_setup / assignfactors first");
+  if (!e->bm_ready) return e->fail(PGBP_ERR_STATE, "pgbp_enqueue_loglik_bm: call pgbp_bm_tree_setup / assignfactors first");
   if ((rc = reset_fail(e))) return rc;
   if ((rc = ensure_layout(e, want_bs16(e), want_site_minor(e)))) return rc;
   DevState S = dev_state(e, opts);
@@ -1690,65 +1671,51 @@ int pgbp_lg_setup(pgbp_engine* e, const pgbp_lg_families* f) {
     std::vector<int32_t> at(count.begin(), count.end() - 1);
     for (int i = 0; i < f->n_families; ++i) fam[at[f->cluster[i]]++] = i;  // stable: the reference's loop order
   }
-  for (void* q : e->lg_bufs)
-    if (q) (void)hipFree(q);
-  e->lg_bufs.clear();
-  for (double** q : {&e->d_lg_R, &e->d_lg_alpha, &e->d_lg_theta, &e->d_lg_mu}) {
-    if (*q) (void)hipFree(*q);
-    *q = nullptr;
-  }
-  e->lg_ready = e->lg_have_params = false;
   const size_t nf = (size_t)f->n_families, nfk = nf * K;
   int rc;
-  int32_t *d_off = nullptr, *d_fam = nullptr, *d_np = nullptr, *d_cp = nullptr, *d_row = nullptr, *d_pp = nullptr, *d_col = nullptr;
-  double *d_len = nullptr, *d_gam = nullptr, *d_data = nullptr;
-  auto keep = [&](void* q) { e->lg_bufs.push_back(q); };
-  if ((rc = upload(e, &d_off, count))) return rc; keep(d_off);
-  if ((rc = upload(e, &d_fam, fam))) return rc; keep(d_fam);
-  if ((rc = upload(e, &d_np, std::vector<int32_t>(f->n_parents, f->n_parents + nf)))) return rc; keep(d_np);
-  if ((rc = upload(e, &d_cp, std::vector<int32_t>(f->child_pos, f->child_pos + nf)))) return rc; keep(d_cp);
-  if ((rc = upload(e, &d_row, std::vector<int32_t>(f->data_row, f->data_row + nf)))) return rc; keep(d_row);
-  if ((rc = upload(e, &d_pp, std::vector<int32_t>(f->parent_pos, f->parent_pos + nfk)))) return rc; keep(d_pp);
-  if ((rc = upload(e, &d_col, std::vector<int32_t>(f->color, f->color + nfk)))) return rc; keep(d_col);
-  if ((rc = upload(e, &d_len, std::vector<double>(f->length, f->length + nfk)))) return rc; keep(d_len);
-  if ((rc = upload(e, &d_gam, std::vector<double>(f->gamma, f->gamma + nfk)))) return rc; keep(d_gam);
+  LgBufs B;   // the whole table into a local: the engine takes it once the last buffer exists
+  if ((rc = upload(e, B.off, count))) return rc;
+  if ((rc = upload(e, B.fam, fam))) return rc;
+  if ((rc = upload(e, B.np, std::vector<int32_t>(f->n_parents, f->n_parents + nf)))) return rc;
+  if ((rc = upload(e, B.cp, std::vector<int32_t>(f->child_pos, f->child_pos + nf)))) return rc;
+  if ((rc = upload(e, B.row, std::vector<int32_t>(f->data_row, f->data_row + nf)))) return rc;
+  if ((rc = upload(e, B.pp, std::vector<int32_t>(f->parent_pos, f->parent_pos + nfk)))) return rc;
+  if ((rc = upload(e, B.col, std::vector<int32_t>(f->color, f->color + nfk)))) return rc;
+  if ((rc = upload(e, B.len, std::vector<double>(f->length, f->length + nfk)))) return rc;
+  if ((rc = upload(e, B.gam, std::vector<double>(f->gamma, f->gamma + nfk)))) return rc;
   const size_t nd = (size_t)p.n_sites * f->n_rows * pp;
-  if ((rc = dev_alloc(e, &d_data, nd))) return rc; keep(d_data);
-  unsigned long long *d_cm = nullptr, *d_pm = nullptr;
+  if ((rc = dev_alloc(e, B.data, nd))) return rc;
   if (f->child_mask) {
     std::vector<unsigned long long> v(nf);
     for (size_t i = 0; i < nf; ++i) v[i] = cmask((int)i);
-    if ((rc = upload(e, &d_cm, v))) return rc; keep(d_cm);
+    if ((rc = upload(e, B.cm, v))) return rc;
   }
   if (f->parent_mask) {
     std::vector<unsigned long long> v(nfk);
     for (size_t i = 0; i < nf; ++i)
       for (int k = 0; k < K; ++k) v[i * K + k] = pmask((int)i, k);
-    if ((rc = upload(e, &d_pm, v))) return rc; keep(d_pm);
+    if ((rc = upload(e, B.pm, v))) return rc;
   }
-  if (d_data && nd) {
+  if (nd) {
     if (!f->child_mask) {  // complete data: checked finite above
-      HIPCHK(e, hipMemcpy(d_data, f->data, nd * sizeof(double), hipMemcpyHostToDevice));
+      HIPCHK(e, hipMemcpy(B.data.get(), f->data, nd * sizeof(double), hipMemcpyHostToDevice));
     } else {               // masked-out entries may be NaN on the host: never let them reach arithmetic
       std::vector<double> clean(f->data, f->data + nd);
       for (double& x : clean) if (!std::isfinite(x)) x = 0.0;
-      HIPCHK(e, hipMemcpy(d_data, clean.data(), nd * sizeof(double), hipMemcpyHostToDevice));
+      HIPCHK(e, hipMemcpy(B.data.get(), clean.data(), nd * sizeof(double), hipMemcpyHostToDevice));
     }
   }
   const size_t ns = (size_t)p.n_sites;
-  if ((rc = dev_alloc(e, &e->d_lg_R, ns * f->n_rates * pp * pp))) return rc;
-  if ((rc = dev_alloc(e, &e->d_lg_alpha, ns))) return rc;
-  if ((rc = dev_alloc(e, &e->d_lg_theta, ns * pp))) return rc;
-  if ((rc = dev_alloc(e, &e->d_lg_mu, ns * pp))) return rc;
-  double* d_data_sm = nullptr;
+  if ((rc = dev_alloc(e, B.R, ns * f->n_rates * pp * pp))) return rc;
+  if ((rc = dev_alloc(e, B.alpha, ns))) return rc;
+  if ((rc = dev_alloc(e, B.theta, ns * pp))) return rc;
+  if ((rc = dev_alloc(e, B.mu, ns * pp))) return rc;
   if (uni_ok && f->n_rows > 0) {   // the thread-per-site fill reads the tip data with lanes = sites: keep a [row][site] copy
-    if ((rc = dev_alloc(e, &d_data_sm, (size_t)f->n_rows * (size_t)sm_row(p.n_sites)))) return rc;
-    keep(d_data_sm);
-    launch_transpose_words_f64(d_data, d_data_sm, f->n_rows, p.n_sites, 1, e->st);
+    if ((rc = dev_alloc(e, B.data_sm, (size_t)f->n_rows * (size_t)sm_row(p.n_sites)))) return rc;
+    launch_transpose_words_f64(B.data.get(), B.data_sm.get(), f->n_rows, p.n_sites, 1, e->st);
     HIPCHK(e, hipStreamSynchronize(e->st));
   }
   // one record per cluster where every cluster holds exactly one family with at most one parent and there are no scope masks
-  LgSimpleFam* d_simple = nullptr;
   if (uni_ok && !f->child_mask && !f->parent_mask && f->n_families == nc) {
     std::vector<LgSimpleFam> sf(nc);
     bool simple = true;
@@ -1766,14 +1733,14 @@ int pgbp_lg_setup(pgbp_engine* e, const pgbp_lg_families* f) {
       if (r.cpos > 1 || r.ppos > 1) { simple = false; break; }
       sf[c] = r;
     }
-    if (simple) {
-      if ((rc = upload(e, &d_simple, sf))) return rc;
-      keep(d_simple);
-    }
+    if (simple && (rc = upload(e, B.simple, sf))) return rc;
   }
-  e->lg = LgStatic{pp, K, f->n_rates, f->n_rows, d_off, d_fam, d_np, d_cp, d_row, d_pp, d_len, d_gam, d_col, d_data, d_cm, d_pm,
-                   d_data_sm, d_simple};
+  e->lg_bufs = std::move(B);
+  const LgBufs& L = e->lg_bufs;
+  e->lg = LgStatic{pp, K, f->n_rates, f->n_rows, L.off.get(), L.fam.get(), L.np.get(), L.cp.get(), L.row.get(), L.pp.get(), L.len.get(),
+                   L.gam.get(), L.col.get(), L.data.get(), L.cm.get(), L.pm.get(), L.data_sm.get(), L.simple.get()};
   e->lg_ready = true;
+  e->lg_have_params = false;
   e->lg_uni_ok = uni_ok;
   return PGBP_OK;
 }
@@ -1783,19 +1750,19 @@ int pgbp_lg_setup(pgbp_engine* e, const pgbp_lg_families* f) {
 static int lg_fill_async(pgbp_engine* e, bool also_factors, bool skip_sepsets = false) {
   const Plan& p = e->plan;
   if (e->layout_sm && e->lg_uni_ok) {
-    launch_lg_fill_uni_sm(e->lg, e->lgp, e->d_pool_sm, also_factors ? e->d_fpool_sm : nullptr, e->d_packed_off, e->d_bdim,
+    launch_lg_fill_uni_sm(e->lg, e->lgp, e->sm.pool.get(), also_factors ? e->sm.fpool.get() : nullptr, e->d_packed_off.get(), e->d_bdim.get(),
                           p.n_clusters, p.n_sites, e->st);
     const int64_t nc = p.packed_off[p.n_clusters] * sm_row(p.n_sites), nall = p.packed_off.back() * sm_row(p.n_sites);
-    if (!skip_sepsets) HIPCHK(e, hipMemsetAsync(e->d_pool_sm + nc, 0, sizeof(double) * (size_t)(nall - nc), e->st));  // sepsets = 1
+    if (!skip_sepsets) HIPCHK(e, hipMemsetAsync(e->sm.pool.get() + nc, 0, sizeof(double) * (size_t)(nall - nc), e->st));  // sepsets = 1
   } else {
     if (e->layout_sm) {
       const int rc0 = ensure_site_minor(e, false);
       if (rc0) return rc0;
     }
-    launch_lg_fill(e->lg, e->lgp, e->d_pool, p.pool_stride(), also_factors ? e->d_fpool : nullptr, p.cluster_stride(),
-                   e->d_boff, e->d_bdim, e->layout_bs16 ? 1 : 0, p.fast_p, p.max_dim, p.n_clusters, p.n_sites, e->st);
+    launch_lg_fill(e->lg, e->lgp, e->d_pool.get(), p.pool_stride(), also_factors ? e->d_fpool.get() : nullptr, p.cluster_stride(),
+                   e->d_boff.get(), e->d_bdim.get(), e->layout_bs16 ? 1 : 0, p.fast_p, p.max_dim, p.n_clusters, p.n_sites, e->st);
     if (!skip_sepsets)
-      launch_zero_strided(e->d_pool + p.cluster_stride(), p.pool_stride(), p.pool_stride() - p.cluster_stride(),
+      launch_zero_strided(e->d_pool.get() + p.cluster_stride(), p.pool_stride(), p.pool_stride() - p.cluster_stride(),
                           p.n_sites, e->st);  // sepsets = 1 (init_beliefs_reset!)
   }
   reset_message_flags(e, also_factors ? 1 : 0);
@@ -1811,12 +1778,12 @@ int pgbp_lg_assignfactors(pgbp_engine* e, const pgbp_lg_params* m) {
   if (m->model == PGBP_LG_OU && (!m->alpha || !m->theta))
     return e->fail(PGBP_ERR_INVALID, "pgbp_lg_assignfactors: the OU model needs alpha and theta");
   const size_t n = m->per_site ? (size_t)e->plan.n_sites : 1, pp = (size_t)e->lg.p;
-  HIPCHK(e, hipMemcpyAsync(e->d_lg_R, m->R, n * e->lg.n_rates * pp * pp * sizeof(double), hipMemcpyHostToDevice, e->st));
-  HIPCHK(e, hipMemcpyAsync(e->d_lg_mu, m->mu, n * pp * sizeof(double), hipMemcpyHostToDevice, e->st));
-  if (m->alpha) HIPCHK(e, hipMemcpyAsync(e->d_lg_alpha, m->alpha, n * sizeof(double), hipMemcpyHostToDevice, e->st));
-  if (m->theta) HIPCHK(e, hipMemcpyAsync(e->d_lg_theta, m->theta, n * pp * sizeof(double), hipMemcpyHostToDevice, e->st));
+  HIPCHK(e, hipMemcpyAsync(e->lg_bufs.R.get(), m->R, n * e->lg.n_rates * pp * pp * sizeof(double), hipMemcpyHostToDevice, e->st));
+  HIPCHK(e, hipMemcpyAsync(e->lg_bufs.mu.get(), m->mu, n * pp * sizeof(double), hipMemcpyHostToDevice, e->st));
+  if (m->alpha) HIPCHK(e, hipMemcpyAsync(e->lg_bufs.alpha.get(), m->alpha, n * sizeof(double), hipMemcpyHostToDevice, e->st));
+  if (m->theta) HIPCHK(e, hipMemcpyAsync(e->lg_bufs.theta.get(), m->theta, n * pp * sizeof(double), hipMemcpyHostToDevice, e->st));
   HIPCHK(e, hipStreamSynchronize(e->st));  // the host buffers may go away
-  e->lgp = LgParams{m->model, m->per_site ? 1 : 0, e->d_lg_R, e->d_lg_alpha, m->theta ? e->d_lg_theta : nullptr, e->d_lg_mu};
+  e->lgp = LgParams{m->model, m->per_site ? 1 : 0, e->lg_bufs.R.get(), e->lg_bufs.alpha.get(), m->theta ? e->lg_bufs.theta.get() : nullptr, e->lg_bufs.mu.get()};
   e->lg_have_params = true;
   // the fill writes exactly symmetric blocks: the layout the traversals want can be kept
   e->sym_known = true;
@@ -1857,8 +1824,8 @@ int pgbp_enqueue_loglik_lg(pgbp_engine* e, int32_t reps, const pgbp_opts* opts) 
 
 // one iteration of calibrate! over every schedule tree.  ev != null: one HIP event pair around the message launches of
 // each tree (they run back to back on the stream), *n_launches += their number
-static int enqueue_calibrate_once(pgbp_engine* e, const DevState& S, int reset_each,
-                                  std::vector<std::pair<hipEvent_t, hipEvent_t>>* ev, int* n_launches = nullptr) {
+static int enqueue_calibrate_once(pgbp_engine* e, const DevState& S, int reset_each, std::vector<EventPair>* ev,
+                                  int* n_launches = nullptr) {
   const Plan& p = e->plan;
   if (reset_each) {
     int rc = reset_from_factors_async(e);
@@ -1866,16 +1833,15 @@ static int enqueue_calibrate_once(pgbp_engine* e, const DevState& S, int reset_e
     reset_message_flags(e, 1);
   }
   for (int j = 0; j < (int)p.trees.size(); ++j) {
-    hipEvent_t a = nullptr, b = nullptr;
+    EventPair pr;
     if (ev) {
-      HIPCHK(e, hipEventCreate(&a));
-      HIPCHK(e, hipEventCreate(&b));
-      HIPCHK(e, hipEventRecord(a, e->st));
+      HIPCHK(e, hipError_t(pr.create()));
+      HIPCHK(e, hipEventRecord(hip_event(pr.first()), e->st));
     }
-    enqueue_pair_and_iscal(e, S, j, (unsigned long long)j, false, e->d_iscal, n_launches);
+    enqueue_pair_and_iscal(e, S, j, (unsigned long long)j, false, e->d_iscal.get(), n_launches);
     if (ev) {
-      HIPCHK(e, hipEventRecord(b, e->st));
-      ev->push_back({a, b});
+      HIPCHK(e, hipEventRecord(hip_event(pr.second()), e->st));
+      ev->push_back(std::move(pr));
     }
   }
   return PGBP_OK;
@@ -1896,10 +1862,6 @@ int pgbp_enqueue_calibrate(pgbp_engine* e, int32_t reps, int32_t reset_each, con
 }
 
 static void drop_kernel_events(pgbp_engine* e) {
-  for (auto& pr : e->kernel_events) {
-    (void)hipEventDestroy(pr.first);
-    (void)hipEventDestroy(pr.second);
-  }
   e->kernel_events.clear();
   e->kernel_launches = 0;
 }
@@ -1922,10 +1884,10 @@ int pgbp_enqueue_calibrate_timed(pgbp_engine* e, int32_t reps, int32_t reset_eac
   } else {
     // nothing but message launches (and the flag reduction behind each tree) in the region: ONE pair around all of it
     // -- an event record is a barrier packet on the stream, and two of them per repetition cost 4 % of a cfg3 calibrate
-    hipEvent_t a = nullptr, b = nullptr;
-    HIPCHK(e, hipEventCreate(&a));
-    HIPCHK(e, hipEventCreate(&b));
-    e->kernel_events.push_back({a, b});
+    EventPair pr;
+    HIPCHK(e, hipError_t(pr.create()));
+    const hipEvent_t a = hip_event(pr.first()), b = hip_event(pr.second());
+    e->kernel_events.push_back(std::move(pr));
     HIPCHK(e, hipEventRecord(a, e->st));
     for (int r = 0; r < reps; ++r)
       if ((rc = enqueue_calibrate_once(e, S, 0, nullptr, &launches))) return rc;
@@ -1943,7 +1905,7 @@ int pgbp_fetch_kernel_time(pgbp_engine* e, float* ms_kernels, int32_t* n_launche
   double total = 0;
   for (auto& pr : e->kernel_events) {
     float ms = 0;
-    HIPCHK(e, hipEventElapsedTime(&ms, pr.first, pr.second));
+    HIPCHK(e, hipEventElapsedTime(&ms, hip_event(pr.first()), hip_event(pr.second())));
     total += ms;
   }
   *ms_kernels = (float)total;
@@ -1993,15 +1955,15 @@ int pgbp_fetch_loglik(pgbp_engine* e, double* norm, int32_t* info) {
   DeviceScope device_scope(e);
   if (!e || !norm) return PGBP_ERR_INVALID;
   const int ns = e->plan.n_sites;
-  HIPCHK(e, hipMemcpyAsync(norm, e->d_norm, sizeof(double) * ns, hipMemcpyDeviceToHost, e->st));
-  if (info) HIPCHK(e, hipMemcpyAsync(info, e->d_info, sizeof(int32_t) * ns, hipMemcpyDeviceToHost, e->st));
+  HIPCHK(e, hipMemcpyAsync(norm, e->d_norm.get(), sizeof(double) * ns, hipMemcpyDeviceToHost, e->st));
+  if (info) HIPCHK(e, hipMemcpyAsync(info, e->d_info.get(), sizeof(int32_t) * ns, hipMemcpyDeviceToHost, e->st));
   HIPCHK(e, hipStreamSynchronize(e->st));
   HIPCHK(e, hipGetLastError());
   if (const int erc = e->take_enqueue_rc()) return erc;
   if (info) {
     // a failed postorder message also invalidates the likelihood
     std::vector<unsigned long long> keys(ns);
-    HIPCHK(e, hipMemcpy(keys.data(), e->d_fail, sizeof(unsigned long long) * ns, hipMemcpyDeviceToHost));
+    HIPCHK(e, hipMemcpy(keys.data(), e->d_fail.get(), sizeof(unsigned long long) * ns, hipMemcpyDeviceToHost));
     for (int s = 0; s < ns; ++s)
       if (is_failure_key(keys[s]) && info[s] == 0) info[s] = (int32_t)(keys[s] & ((1ull << kInfoBits) - 1));
   }
@@ -2012,9 +1974,9 @@ int pgbp_time_enqueued(pgbp_engine* e, int32_t kind, int32_t reps, int32_t reset
                        float* ms_total) {
   DeviceScope device_scope(e);
   if (!e || !ms_total || kind < 0 || kind > 3) return PGBP_ERR_INVALID;
-  hipEvent_t a, b;
-  HIPCHK(e, hipEventCreate(&a));
-  HIPCHK(e, hipEventCreate(&b));
+  EventPair pr;
+  HIPCHK(e, hipError_t(pr.create()));
+  const hipEvent_t a = hip_event(pr.first()), b = hip_event(pr.second());
   HIPCHK(e, hipStreamSynchronize(e->st));
   HIPCHK(e, hipEventRecord(a, e->st));
   int rc = kind == 0 ? pgbp_enqueue_calibrate(e, reps, reset_each, opts)
@@ -2025,8 +1987,6 @@ int pgbp_time_enqueued(pgbp_engine* e, int32_t kind, int32_t reps, int32_t reset
     HIPCHK(e, hipEventSynchronize(b));
     HIPCHK(e, hipEventElapsedTime(ms_total, a, b));
   }
-  (void)hipEventDestroy(a);
-  (void)hipEventDestroy(b);
   return rc;
 }
 
@@ -2084,17 +2044,15 @@ int engine_pack_gather_slot(pgbp_engine* e, int32_t slot_sites, double** d_slot,
   if (slot_sites < ns) return e->fail(PGBP_ERR_INVALID, "gather slot smaller than this rank's number of sites");
   const int64_t need = 2 * (int64_t)slot_sites + 2;
   if (need > e->gather_cap) {
-    if (e->d_gather) (void)hipFree(e->d_gather);
-    e->d_gather = nullptr;
     e->gather_cap = 0;
-    int rc = dev_alloc(e, &e->d_gather, (size_t)need);
+    int rc = dev_alloc(e, e->d_gather, (size_t)need);
     if (rc) return rc;
     e->gather_cap = need;
   }
-  hipLaunchKernelGGL(pack_gather_slot, dim3(1), dim3(256), 0, e->st, e->d_norm, e->d_info, e->d_fail, e->d_iscal, ns,
-                     slot_sites, e->d_gather);
+  hipLaunchKernelGGL(pack_gather_slot, dim3(1), dim3(256), 0, e->st, e->d_norm.get(), e->d_info.get(), e->d_fail.get(), e->d_iscal.get(), ns,
+                     slot_sites, e->d_gather.get());
   HIPCHK(e, hipGetLastError());
-  *d_slot = e->d_gather;
+  *d_slot = e->d_gather.get();
   *st = e->st;
   if (n_sites) *n_sites = ns;
   return PGBP_OK;
@@ -2110,7 +2068,7 @@ int engine_pack_records_device(pgbp_engine* e, int32_t site, int32_t n, const in
   if (rc) return rc;
   if (n > 0) {
     if (!to_buf) e->sym_known = false;
-    launch_pack_records(e->d_pool + (int64_t)site * e->plan.pool_stride(), e->d_xoff, e->d_xoff + n, n, d_buf, to_buf, e->st);
+    launch_pack_records(e->d_pool.get() + (int64_t)site * e->plan.pool_stride(), e->d_xoff.get(), e->d_xoff.get() + n, n, d_buf, to_buf, e->st);
     HIPCHK(e, hipGetLastError());
   }
   if (st) *st = e->st;
@@ -2134,9 +2092,9 @@ EngineView engine_peek(pgbp_engine* e) {
   EngineView v;
   v.plan = &e->plan;
   v.st = e->st;
-  v.pool = e->d_pool;
-  v.boff = e->d_boff;
-  v.bdim = e->d_bdim;
+  v.pool = e->d_pool.get();
+  v.boff = e->d_boff.get();
+  v.bdim = e->d_bdim.get();
   v.bs16 = e->layout_bs16 ? 1 : 0;
   v.lg = &e->lg;
   v.lg_ready = e->lg_ready ? 1 : 0;

@@ -25,6 +25,7 @@
 #include <vector>
 
 #include "pgbp_bs16.hpp"
+#include "pgbp_devmem.hpp"
 #include "pgbp_kernels.hpp"
 #include "pgbp_mom_dev.hpp"
 
@@ -447,23 +448,18 @@ extern "C" int pgbp_lg_gradient(pgbp_engine* e, int32_t site_begin, int32_t site
   const int64_t per_site = (int64_t)nf * sl;
   const int chunk = (int)std::max<int64_t>(1, std::min<int64_t>(ns, ((int64_t)32 << 20) / per_site));
   const int nfb = (nf + kGradFamBlock - 1) / kGradFamBlock;
-  int32_t* d_fcl = nullptr;
-  double *d_slots = nullptr, *d_part = nullptr, *d_out = nullptr;
-  int32_t* d_info = nullptr;
-  std::vector<int32_t> inf(ns, 0x7fffffff);
+  std::vector<int32_t> inf(ns, 0x7fffffff);   // (ahead of the buffers: they are released, which drains the uploads, first)
   std::vector<double> out((size_t)ns * n_ent);
-  herr = hipMalloc(reinterpret_cast<void**>(&d_fcl), sizeof(int32_t) * nf);
-  if (herr == hipSuccess) herr = hipMalloc(reinterpret_cast<void**>(&d_slots), sizeof(double) * (size_t)per_site * chunk);
-  if (herr == hipSuccess) herr = hipMalloc(reinterpret_cast<void**>(&d_part), sizeof(double) * (size_t)chunk * nfb * n_ent);
-  if (herr == hipSuccess) herr = hipMalloc(reinterpret_cast<void**>(&d_out), sizeof(double) * (size_t)ns * n_ent);
-  if (herr == hipSuccess) herr = hipMalloc(reinterpret_cast<void**>(&d_info), sizeof(int32_t) * (size_t)ns);
-  if (herr == hipSuccess) herr = hipMemcpyAsync(d_fcl, fcl.data(), sizeof(int32_t) * nf, hipMemcpyHostToDevice, v.st);
-  if (herr == hipSuccess) herr = hipMemcpyAsync(d_info, inf.data(), sizeof(int32_t) * ns, hipMemcpyHostToDevice, v.st);
-  if (herr != hipSuccess) {
-    for (void* q : {(void*)d_fcl, (void*)d_slots, (void*)d_part, (void*)d_out, (void*)d_info})
-      if (q) (void)hipFree(q);
-    return engine_fail(e, PGBP_ERR_HIP, std::string("pgbp_lg_gradient (scratch): ") + hipGetErrorString(herr));
-  }
+  DevBuf<int32_t> d_fcl, d_info;
+  DevBuf<double> d_slots, d_part, d_out;
+  herr = (hipError_t)d_fcl.alloc(nf);
+  if (herr == hipSuccess) herr = (hipError_t)d_slots.alloc((size_t)per_site * chunk);
+  if (herr == hipSuccess) herr = (hipError_t)d_part.alloc((size_t)chunk * nfb * n_ent);
+  if (herr == hipSuccess) herr = (hipError_t)d_out.alloc((size_t)ns * n_ent);
+  if (herr == hipSuccess) herr = (hipError_t)d_info.alloc((size_t)ns);
+  if (herr == hipSuccess) herr = hipMemcpyAsync(d_fcl.get(), fcl.data(), sizeof(int32_t) * nf, hipMemcpyHostToDevice, v.st);
+  if (herr == hipSuccess) herr = hipMemcpyAsync(d_info.get(), inf.data(), sizeof(int32_t) * ns, hipMemcpyHostToDevice, v.st);
+  if (herr != hipSuccess) return engine_fail(e, PGBP_ERR_HIP, std::string("pgbp_lg_gradient (scratch): ") + hipGetErrorString(herr));
   (void)hipGetLastError();   // (an error an earlier asynchronous call left behind is that call's to report)
   {
     const void* kern = max_m <= 64 ? reinterpret_cast<const void*>(grad_family<64>) : reinterpret_cast<const void*>(grad_family<256>);
@@ -472,22 +468,20 @@ extern "C" int pgbp_lg_gradient(pgbp_engine* e, int32_t site_begin, int32_t site
       const int n = std::min(chunk, ns - s0), gy = std::min(n, 65535);
       if (max_m <= 64)
         hipLaunchKernelGGL(grad_family<64>, dim3(nf, gy), dim3(64), lds_bytes, v.st, v.pool, pl.pool_stride(), v.boff, v.bdim,
-                           v.bs16, pl.fast_p, F, M, d_fcl, nf, site_begin + s0, n, d_slots, d_info, s0);
+                           v.bs16, pl.fast_p, F, M, d_fcl.get(), nf, site_begin + s0, n, d_slots.get(), d_info.get(), s0);
       else
         hipLaunchKernelGGL(grad_family<256>, dim3(nf, gy), dim3(256), lds_bytes, v.st, v.pool, pl.pool_stride(), v.boff, v.bdim,
-                           v.bs16, pl.fast_p, F, M, d_fcl, nf, site_begin + s0, n, d_slots, d_info, s0);
-      hipLaunchKernelGGL(grad_reduce_blocks, dim3((n_ent + 63) / 64, nfb, gy), dim3(256), 0, v.st, d_slots, nf, p, nr, n_ent, n,
-                         d_part);
-      hipLaunchKernelGGL(grad_reduce_final, dim3(n_ent, gy), dim3(256), 0, v.st, d_part, nfb, n_ent, n, d_out, s0);
+                           v.bs16, pl.fast_p, F, M, d_fcl.get(), nf, site_begin + s0, n, d_slots.get(), d_info.get(), s0);
+      hipLaunchKernelGGL(grad_reduce_blocks, dim3((n_ent + 63) / 64, nfb, gy), dim3(256), 0, v.st, d_slots.get(), nf, p, nr, n_ent, n,
+                         d_part.get());
+      hipLaunchKernelGGL(grad_reduce_final, dim3(n_ent, gy), dim3(256), 0, v.st, d_part.get(), nfb, n_ent, n, d_out.get(), s0);
     }
     if (herr == hipSuccess) herr = hipGetLastError();
   }
-  if (herr == hipSuccess) herr = hipMemcpyAsync(out.data(), d_out, sizeof(double) * out.size(), hipMemcpyDeviceToHost, v.st);
-  if (herr == hipSuccess) herr = hipMemcpyAsync(inf.data(), d_info, sizeof(int32_t) * (size_t)ns, hipMemcpyDeviceToHost, v.st);
+  if (herr == hipSuccess) herr = hipMemcpyAsync(out.data(), d_out.get(), sizeof(double) * out.size(), hipMemcpyDeviceToHost, v.st);
+  if (herr == hipSuccess) herr = hipMemcpyAsync(inf.data(), d_info.get(), sizeof(int32_t) * (size_t)ns, hipMemcpyDeviceToHost, v.st);
   const hipError_t serr = hipStreamSynchronize(v.st);
   if (herr == hipSuccess) herr = serr;
-  for (void* q : {(void*)d_fcl, (void*)d_slots, (void*)d_part, (void*)d_out, (void*)d_info})
-    if (q) (void)hipFree(q);
   if (herr != hipSuccess) return engine_fail(e, PGBP_ERR_HIP, std::string("pgbp_lg_gradient: ") + hipGetErrorString(herr));
   for (int s = 0; s < ns; ++s) inf[s] = inf[s] == 0x7fffffff ? 0 : inf[s];
   scatter(out.data(), inf.data());

@@ -25,6 +25,7 @@
 #include <vector>
 
 #include "pgbp_bs16.hpp"
+#include "pgbp_devmem.hpp"
 #include "pgbp_kernels.hpp"
 #include "pgbp_mom_dev.hpp"
 
@@ -421,26 +422,19 @@ extern "C" int pgbp_lg_loo(pgbp_engine* e, int32_t site_begin, int32_t site_end,
   const int pp = p * p;
   const int64_t per_site = (int64_t)nt * (1 + (mean ? p : 0) + (cov ? pp : 0));
   const int chunk = (int)std::max<int64_t>(1, std::min<int64_t>(ns, g_loo_limit.load() / per_site));
-  int32_t *d_tips = nullptr, *d_tcl = nullptr, *d_info = nullptr;
-  double *d_mean = nullptr, *d_cov = nullptr, *d_lpd = nullptr, *d_total = nullptr;
+  DevBuf<int32_t> d_tips, d_tcl, d_info;
+  DevBuf<double> d_mean, d_cov, d_lpd, d_total;
   const size_t cn = (size_t)chunk * nt;
-  hipError_t herr = hipMalloc(reinterpret_cast<void**>(&d_tips), sizeof(int32_t) * nt);
-  if (herr == hipSuccess) herr = hipMalloc(reinterpret_cast<void**>(&d_tcl), sizeof(int32_t) * nt);
-  if (herr == hipSuccess) herr = hipMalloc(reinterpret_cast<void**>(&d_info), sizeof(int32_t) * cn);
-  if (herr == hipSuccess && mean) herr = hipMalloc(reinterpret_cast<void**>(&d_mean), sizeof(double) * cn * p);
-  if (herr == hipSuccess && cov) herr = hipMalloc(reinterpret_cast<void**>(&d_cov), sizeof(double) * cn * pp);
-  if (herr == hipSuccess) herr = hipMalloc(reinterpret_cast<void**>(&d_lpd), sizeof(double) * cn);
-  if (herr == hipSuccess) herr = hipMalloc(reinterpret_cast<void**>(&d_total), sizeof(double) * (size_t)ns);
-  if (herr == hipSuccess) herr = hipMemcpyAsync(d_tips, tips.data(), sizeof(int32_t) * nt, hipMemcpyHostToDevice, v.st);
-  if (herr == hipSuccess) herr = hipMemcpyAsync(d_tcl, tcl.data(), sizeof(int32_t) * nt, hipMemcpyHostToDevice, v.st);
-  auto release = [&]() {
-    for (void* q : {(void*)d_tips, (void*)d_tcl, (void*)d_info, (void*)d_mean, (void*)d_cov, (void*)d_lpd, (void*)d_total})
-      if (q) (void)hipFree(q);
-  };
-  if (herr != hipSuccess) {
-    release();
-    return engine_fail(e, PGBP_ERR_HIP, std::string("pgbp_lg_loo (scratch): ") + hipGetErrorString(herr));
-  }
+  hipError_t herr = (hipError_t)d_tips.alloc(nt);
+  if (herr == hipSuccess) herr = (hipError_t)d_tcl.alloc(nt);
+  if (herr == hipSuccess) herr = (hipError_t)d_info.alloc(cn);
+  if (herr == hipSuccess && mean) herr = (hipError_t)d_mean.alloc(cn * p);
+  if (herr == hipSuccess && cov) herr = (hipError_t)d_cov.alloc(cn * pp);
+  if (herr == hipSuccess) herr = (hipError_t)d_lpd.alloc(cn);
+  if (herr == hipSuccess) herr = (hipError_t)d_total.alloc((size_t)ns);
+  if (herr == hipSuccess) herr = hipMemcpyAsync(d_tips.get(), tips.data(), sizeof(int32_t) * nt, hipMemcpyHostToDevice, v.st);
+  if (herr == hipSuccess) herr = hipMemcpyAsync(d_tcl.get(), tcl.data(), sizeof(int32_t) * nt, hipMemcpyHostToDevice, v.st);
+  if (herr != hipSuccess) return engine_fail(e, PGBP_ERR_HIP, std::string("pgbp_lg_loo (scratch): ") + hipGetErrorString(herr));
   (void)hipGetLastError();   // (an error an earlier asynchronous call left behind is that call's to report)
   {
     const void* kern = max_m <= 64 ? reinterpret_cast<const void*>(loo_family<64>) : reinterpret_cast<const void*>(loo_family<256>);
@@ -449,23 +443,22 @@ extern "C" int pgbp_lg_loo(pgbp_engine* e, int32_t site_begin, int32_t site_end,
       const int n = std::min(chunk, ns - s0), gy = std::min(n, 65535);
       if (max_m <= 64)
         hipLaunchKernelGGL(loo_family<64>, dim3(nt, gy), dim3(64), lds_bytes, v.st, v.pool, pl.pool_stride(), v.boff, v.bdim,
-                           v.bs16, pl.fast_p, F, M, d_tips, d_tcl, nt, site_begin + s0, n, d_mean, d_cov, d_lpd, d_info);
+                           v.bs16, pl.fast_p, F, M, d_tips.get(), d_tcl.get(), nt, site_begin + s0, n, d_mean.get(), d_cov.get(), d_lpd.get(), d_info.get());
       else
         hipLaunchKernelGGL(loo_family<256>, dim3(nt, gy), dim3(256), lds_bytes, v.st, v.pool, pl.pool_stride(), v.boff, v.bdim,
-                           v.bs16, pl.fast_p, F, M, d_tips, d_tcl, nt, site_begin + s0, n, d_mean, d_cov, d_lpd, d_info);
-      hipLaunchKernelGGL(loo_reduce, dim3(gy), dim3(256), 0, v.st, d_lpd, nt, n, d_total, s0);
+                           v.bs16, pl.fast_p, F, M, d_tips.get(), d_tcl.get(), nt, site_begin + s0, n, d_mean.get(), d_cov.get(), d_lpd.get(), d_info.get());
+      hipLaunchKernelGGL(loo_reduce, dim3(gy), dim3(256), 0, v.st, d_lpd.get(), nt, n, d_total.get(), s0);
       herr = hipGetLastError();
       const size_t o = (size_t)s0 * nt, len = (size_t)n * nt;
-      if (herr == hipSuccess) herr = hipMemcpyAsync(lpd + o, d_lpd, sizeof(double) * len, hipMemcpyDeviceToHost, v.st);
-      if (herr == hipSuccess && mean) herr = hipMemcpyAsync(mean + o * p, d_mean, sizeof(double) * len * p, hipMemcpyDeviceToHost, v.st);
-      if (herr == hipSuccess && cov) herr = hipMemcpyAsync(cov + o * pp, d_cov, sizeof(double) * len * pp, hipMemcpyDeviceToHost, v.st);
-      if (herr == hipSuccess && info) herr = hipMemcpyAsync(info + o, d_info, sizeof(int32_t) * len, hipMemcpyDeviceToHost, v.st);
+      if (herr == hipSuccess) herr = hipMemcpyAsync(lpd + o, d_lpd.get(), sizeof(double) * len, hipMemcpyDeviceToHost, v.st);
+      if (herr == hipSuccess && mean) herr = hipMemcpyAsync(mean + o * p, d_mean.get(), sizeof(double) * len * p, hipMemcpyDeviceToHost, v.st);
+      if (herr == hipSuccess && cov) herr = hipMemcpyAsync(cov + o * pp, d_cov.get(), sizeof(double) * len * pp, hipMemcpyDeviceToHost, v.st);
+      if (herr == hipSuccess && info) herr = hipMemcpyAsync(info + o, d_info.get(), sizeof(int32_t) * len, hipMemcpyDeviceToHost, v.st);
     }
   }
-  if (herr == hipSuccess && total) herr = hipMemcpyAsync(total, d_total, sizeof(double) * (size_t)ns, hipMemcpyDeviceToHost, v.st);
+  if (herr == hipSuccess && total) herr = hipMemcpyAsync(total, d_total.get(), sizeof(double) * (size_t)ns, hipMemcpyDeviceToHost, v.st);
   const hipError_t serr = hipStreamSynchronize(v.st);
   if (herr == hipSuccess) herr = serr;
-  release();
   if (herr != hipSuccess) return engine_fail(e, PGBP_ERR_HIP, std::string("pgbp_lg_loo: ") + hipGetErrorString(herr));
   return PGBP_OK;
 }

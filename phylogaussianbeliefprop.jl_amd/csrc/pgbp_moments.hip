@@ -25,6 +25,7 @@
 #include <vector>
 
 #include "pgbp_bs16.hpp"
+#include "pgbp_devmem.hpp"
 #include "pgbp_kernels.hpp"
 #include "pgbp_mom_dev.hpp"
 
@@ -444,36 +445,32 @@ extern "C" int pgbp_moments(pgbp_engine* e, int32_t n, const int32_t* beliefs, i
   const int64_t out_stride = at;
   std::vector<MomItem> all;
   for (int c = 0; c < 3; ++c) all.insert(all.end(), items[c].begin(), items[c].end());
-  MomItem* d_items = nullptr;
-  double* d_out = nullptr;
-  int32_t* d_info = nullptr;
-  hipError_t herr = hipMalloc(reinterpret_cast<void**>(&d_items), sizeof(MomItem) * all.size());
-  if (herr == hipSuccess) herr = hipMalloc(reinterpret_cast<void**>(&d_out), sizeof(double) * (size_t)out_stride * ns);
-  if (herr == hipSuccess) herr = hipMalloc(reinterpret_cast<void**>(&d_info), sizeof(int32_t) * (size_t)nl * ns);
-  if (herr == hipSuccess) herr = hipMemcpyAsync(d_items, all.data(), sizeof(MomItem) * all.size(), hipMemcpyHostToDevice, v.st);
+  DevBuf<MomItem> d_items;
+  DevBuf<double> d_out;
+  DevBuf<int32_t> d_info;
+  hipError_t herr = (hipError_t)d_items.alloc(all.size());
+  if (herr == hipSuccess) herr = (hipError_t)d_out.alloc((size_t)out_stride * ns);
+  if (herr == hipSuccess) herr = (hipError_t)d_info.alloc((size_t)nl * ns);
+  if (herr == hipSuccess) herr = hipMemcpyAsync(d_items.get(), all.data(), sizeof(MomItem) * all.size(), hipMemcpyHostToDevice, v.st);
   if (herr == hipSuccess) {
     const int grid_y = std::min(ns, 65535);
     const int n0 = (int)items[0].size(), n1 = (int)items[1].size(), n2 = (int)items[2].size();
     if (n0 > 0) {
       if (want_cov)
         hipLaunchKernelGGL(moments_small4<true>, dim3((n0 + 3) / 4, grid_y), dim3(64), 0, v.st, v.pool, p.pool_stride(), v.boff,
-                           v.bdim, v.bs16, p.fast_p, d_items, n0, site_begin, ns, nl, d_out, out_stride, d_info);
+                           v.bdim, v.bs16, p.fast_p, d_items.get(), n0, site_begin, ns, nl, d_out.get(), out_stride, d_info.get());
       else
         hipLaunchKernelGGL(moments_small4<false>, dim3((n0 + 3) / 4, grid_y), dim3(64), 0, v.st, v.pool, p.pool_stride(), v.boff,
-                           v.bdim, v.bs16, p.fast_p, d_items, n0, site_begin, ns, nl, d_out, out_stride, d_info);
+                           v.bdim, v.bs16, p.fast_p, d_items.get(), n0, site_begin, ns, nl, d_out.get(), out_stride, d_info.get());
     }
-    if (n1 > 0) launch_moments_lds<64>(want_cov != 0, n1, max_m[1], grid_y, v, d_items + n0, site_begin, ns, nl, d_out, out_stride, d_info);
-    if (n2 > 0) launch_moments_lds<256>(want_cov != 0, n2, max_m[2], grid_y, v, d_items + n0 + n1, site_begin, ns, nl, d_out, out_stride, d_info);
+    if (n1 > 0) launch_moments_lds<64>(want_cov != 0, n1, max_m[1], grid_y, v, d_items.get() + n0, site_begin, ns, nl, d_out.get(), out_stride, d_info.get());
+    if (n2 > 0) launch_moments_lds<256>(want_cov != 0, n2, max_m[2], grid_y, v, d_items.get() + n0 + n1, site_begin, ns, nl, d_out.get(), out_stride, d_info.get());
     herr = hipGetLastError();
   }
-  std::vector<int32_t> inf;
-  if (herr == hipSuccess) herr = hipMemcpyAsync(out, d_out, sizeof(double) * (size_t)out_stride * ns, hipMemcpyDeviceToHost, v.st);
-  if (herr == hipSuccess && info) herr = hipMemcpyAsync(info, d_info, sizeof(int32_t) * (size_t)nl * ns, hipMemcpyDeviceToHost, v.st);
+  if (herr == hipSuccess) herr = hipMemcpyAsync(out, d_out.get(), sizeof(double) * (size_t)out_stride * ns, hipMemcpyDeviceToHost, v.st);
+  if (herr == hipSuccess && info) herr = hipMemcpyAsync(info, d_info.get(), sizeof(int32_t) * (size_t)nl * ns, hipMemcpyDeviceToHost, v.st);
   const hipError_t serr = hipStreamSynchronize(v.st);   // (also when something failed: `all` is a local the upload reads)
   if (herr == hipSuccess) herr = serr;
-  if (d_items) (void)hipFree(d_items);
-  if (d_out) (void)hipFree(d_out);
-  if (d_info) (void)hipFree(d_info);
   if (herr != hipSuccess) return engine_fail(e, PGBP_ERR_HIP, std::string("pgbp_moments: ") + hipGetErrorString(herr));
   return PGBP_OK;
 }
@@ -558,17 +555,16 @@ extern "C" int pgbp_bm_exact_stats(pgbp_engine* e, int32_t site_begin, int32_t s
   // slots of a chunk of sites at a time (256 MB at most: cfg4's 8 000 sites x 40 000 families would be 7.7 GB at once)
   const int64_t per_site = (int64_t)nf * (p + 2);
   const int chunk = (int)std::max<int64_t>(1, std::min<int64_t>(ns, ((int64_t)32 << 20) / per_site));
-  int32_t* d_fcl = nullptr;
-  double *d_slots = nullptr, *d_num = nullptr, *d_den = nullptr;
-  int32_t* d_info = nullptr;
-  std::vector<int32_t> inf(ns, 0x7fffffff);
-  herr = hipMalloc(reinterpret_cast<void**>(&d_fcl), sizeof(int32_t) * nf);
-  if (herr == hipSuccess) herr = hipMalloc(reinterpret_cast<void**>(&d_slots), sizeof(double) * (size_t)per_site * chunk);
-  if (herr == hipSuccess) herr = hipMalloc(reinterpret_cast<void**>(&d_num), sizeof(double) * (size_t)ns * p * p);
-  if (herr == hipSuccess) herr = hipMalloc(reinterpret_cast<void**>(&d_den), sizeof(double) * (size_t)ns);
-  if (herr == hipSuccess) herr = hipMalloc(reinterpret_cast<void**>(&d_info), sizeof(int32_t) * (size_t)ns);
-  if (herr == hipSuccess) herr = hipMemcpyAsync(d_fcl, fcl.data(), sizeof(int32_t) * nf, hipMemcpyHostToDevice, v.st);
-  if (herr == hipSuccess) herr = hipMemcpyAsync(d_info, inf.data(), sizeof(int32_t) * ns, hipMemcpyHostToDevice, v.st);
+  std::vector<int32_t> inf(ns, 0x7fffffff);   // (ahead of the buffers: they are released, which drains the uploads, first)
+  DevBuf<int32_t> d_fcl, d_info;
+  DevBuf<double> d_slots, d_num, d_den;
+  herr = (hipError_t)d_fcl.alloc(nf);
+  if (herr == hipSuccess) herr = (hipError_t)d_slots.alloc((size_t)per_site * chunk);
+  if (herr == hipSuccess) herr = (hipError_t)d_num.alloc((size_t)ns * p * p);
+  if (herr == hipSuccess) herr = (hipError_t)d_den.alloc((size_t)ns);
+  if (herr == hipSuccess) herr = (hipError_t)d_info.alloc((size_t)ns);
+  if (herr == hipSuccess) herr = hipMemcpyAsync(d_fcl.get(), fcl.data(), sizeof(int32_t) * nf, hipMemcpyHostToDevice, v.st);
+  if (herr == hipSuccess) herr = hipMemcpyAsync(d_info.get(), inf.data(), sizeof(int32_t) * ns, hipMemcpyHostToDevice, v.st);
   if (herr == hipSuccess) {
     const size_t bytes = moments_lds_bytes(max_m);
     const void* kern = max_m <= 64 ? reinterpret_cast<const void*>(bm_exact_family<64>) : reinterpret_cast<const void*>(bm_exact_family<256>);
@@ -577,21 +573,19 @@ extern "C" int pgbp_bm_exact_stats(pgbp_engine* e, int32_t site_begin, int32_t s
       const int n = std::min(chunk, ns - s0), gy = std::min(n, 65535);
       if (max_m <= 64)
         hipLaunchKernelGGL(bm_exact_family<64>, dim3(nf, gy), dim3(64), bytes, v.st, v.pool, pl.pool_stride(), v.boff, v.bdim,
-                           v.bs16, pl.fast_p, F, d_fcl, nf, site_begin + s0, n, d_slots, d_info, s0);
+                           v.bs16, pl.fast_p, F, d_fcl.get(), nf, site_begin + s0, n, d_slots.get(), d_info.get(), s0);
       else
         hipLaunchKernelGGL(bm_exact_family<256>, dim3(nf, gy), dim3(256), bytes, v.st, v.pool, pl.pool_stride(), v.boff, v.bdim,
-                           v.bs16, pl.fast_p, F, d_fcl, nf, site_begin + s0, n, d_slots, d_info, s0);
-      hipLaunchKernelGGL(bm_exact_reduce, dim3(p * p + 1, gy), dim3(256), 0, v.st, d_slots, nf, p, n, d_num, d_den, s0);
+                           v.bs16, pl.fast_p, F, d_fcl.get(), nf, site_begin + s0, n, d_slots.get(), d_info.get(), s0);
+      hipLaunchKernelGGL(bm_exact_reduce, dim3(p * p + 1, gy), dim3(256), 0, v.st, d_slots.get(), nf, p, n, d_num.get(), d_den.get(), s0);
     }
     herr = hipGetLastError();
   }
-  if (herr == hipSuccess) herr = hipMemcpyAsync(num, d_num, sizeof(double) * (size_t)ns * p * p, hipMemcpyDeviceToHost, v.st);
-  if (herr == hipSuccess) herr = hipMemcpyAsync(den, d_den, sizeof(double) * (size_t)ns, hipMemcpyDeviceToHost, v.st);
-  if (herr == hipSuccess) herr = hipMemcpyAsync(inf.data(), d_info, sizeof(int32_t) * (size_t)ns, hipMemcpyDeviceToHost, v.st);
+  if (herr == hipSuccess) herr = hipMemcpyAsync(num, d_num.get(), sizeof(double) * (size_t)ns * p * p, hipMemcpyDeviceToHost, v.st);
+  if (herr == hipSuccess) herr = hipMemcpyAsync(den, d_den.get(), sizeof(double) * (size_t)ns, hipMemcpyDeviceToHost, v.st);
+  if (herr == hipSuccess) herr = hipMemcpyAsync(inf.data(), d_info.get(), sizeof(int32_t) * (size_t)ns, hipMemcpyDeviceToHost, v.st);
   const hipError_t serr = hipStreamSynchronize(v.st);
   if (herr == hipSuccess) herr = serr;
-  for (void* q : {(void*)d_fcl, (void*)d_slots, (void*)d_num, (void*)d_den, (void*)d_info})
-    if (q) (void)hipFree(q);
   if (herr != hipSuccess) return engine_fail(e, PGBP_ERR_HIP, std::string("pgbp_bm_exact_stats: ") + hipGetErrorString(herr));
   if (info)
     for (int s2 = 0; s2 < ns; ++s2) info[s2] = inf[s2] == 0x7fffffff ? 0 : inf[s2];

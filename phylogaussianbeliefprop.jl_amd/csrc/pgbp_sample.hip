@@ -24,6 +24,7 @@
 #include <vector>
 
 #include "pgbp_bs16.hpp"
+#include "pgbp_devmem.hpp"
 #include "pgbp_kernels.hpp"
 #include "pgbp_mom_dev.hpp"
 
@@ -290,23 +291,23 @@ static int sample_posterior(pgbp_engine* e, int32_t tree, int32_t site_begin, in
   const int chunk = (int)std::max<int64_t>(1, std::min<int64_t>(ns, g_factor_limit.load() / std::max<int64_t>(1, f_stride)));
   const int dchunk = (int)std::max<int64_t>(1, std::min<int64_t>(n_draws, g_draw_limit.load() / ((int64_t)chunk * size)));
   const size_t n_items = by_class.size();
-  SampItem* d_items = nullptr;   // by class, then by level
-  int32_t *d_idx = nullptr, *d_order = nullptr, *d_stat = nullptr, *d_info = nullptr;
-  double *d_f = nullptr, *d_z = nullptr, *d_x = nullptr;
+  DevBuf<SampItem> d_items;   // by class, then by level
+  DevBuf<int32_t> d_idx, d_order, d_stat, d_info;
+  DevBuf<double> d_f, d_z, d_x;
   if (idx.empty()) idx.push_back(0);
-  hipError_t herr = hipMalloc(reinterpret_cast<void**>(&d_items), sizeof(SampItem) * 2 * n_items);
-  if (herr == hipSuccess) herr = hipMalloc(reinterpret_cast<void**>(&d_idx), sizeof(int32_t) * idx.size());
-  if (herr == hipSuccess) herr = hipMalloc(reinterpret_cast<void**>(&d_order), sizeof(int32_t) * nc);
-  if (herr == hipSuccess) herr = hipMalloc(reinterpret_cast<void**>(&d_stat), sizeof(int32_t) * (size_t)chunk * nc);
-  if (herr == hipSuccess) herr = hipMalloc(reinterpret_cast<void**>(&d_info), sizeof(int32_t) * (size_t)ns);
-  if (herr == hipSuccess) herr = hipMalloc(reinterpret_cast<void**>(&d_f), sizeof(double) * (size_t)std::max<int64_t>(1, f_stride) * chunk);
-  if (herr == hipSuccess) herr = hipMalloc(reinterpret_cast<void**>(&d_z), sizeof(double) * (size_t)dchunk * chunk * size);
-  if (herr == hipSuccess) herr = hipMalloc(reinterpret_cast<void**>(&d_x), sizeof(double) * (size_t)dchunk * chunk * size);
-  if (herr == hipSuccess) herr = hipMemcpyAsync(d_items, by_class.data(), sizeof(SampItem) * n_items, hipMemcpyHostToDevice, v.st);
-  if (herr == hipSuccess) herr = hipMemcpyAsync(d_items + n_items, by_level.data(), sizeof(SampItem) * n_items, hipMemcpyHostToDevice, v.st);
-  if (herr == hipSuccess) herr = hipMemcpyAsync(d_idx, idx.data(), sizeof(int32_t) * idx.size(), hipMemcpyHostToDevice, v.st);
-  if (herr == hipSuccess) herr = hipMemcpyAsync(d_order, order.data(), sizeof(int32_t) * nc, hipMemcpyHostToDevice, v.st);
-  if (herr == hipSuccess) herr = hipMemsetAsync(d_stat, 0, sizeof(int32_t) * (size_t)chunk * nc, v.st);   // (clusters without variables)
+  hipError_t herr = (hipError_t)d_items.alloc(2 * n_items);
+  if (herr == hipSuccess) herr = (hipError_t)d_idx.alloc(idx.size());
+  if (herr == hipSuccess) herr = (hipError_t)d_order.alloc(nc);
+  if (herr == hipSuccess) herr = (hipError_t)d_stat.alloc((size_t)chunk * nc);
+  if (herr == hipSuccess) herr = (hipError_t)d_info.alloc((size_t)ns);
+  if (herr == hipSuccess) herr = (hipError_t)d_f.alloc((size_t)std::max<int64_t>(1, f_stride) * chunk);
+  if (herr == hipSuccess) herr = (hipError_t)d_z.alloc((size_t)dchunk * chunk * size);
+  if (herr == hipSuccess) herr = (hipError_t)d_x.alloc((size_t)dchunk * chunk * size);
+  if (herr == hipSuccess) herr = hipMemcpyAsync(d_items.get(), by_class.data(), sizeof(SampItem) * n_items, hipMemcpyHostToDevice, v.st);
+  if (herr == hipSuccess) herr = hipMemcpyAsync(d_items.get() + n_items, by_level.data(), sizeof(SampItem) * n_items, hipMemcpyHostToDevice, v.st);
+  if (herr == hipSuccess) herr = hipMemcpyAsync(d_idx.get(), idx.data(), sizeof(int32_t) * idx.size(), hipMemcpyHostToDevice, v.st);
+  if (herr == hipSuccess) herr = hipMemcpyAsync(d_order.get(), order.data(), sizeof(int32_t) * nc, hipMemcpyHostToDevice, v.st);
+  if (herr == hipSuccess) herr = hipMemsetAsync(d_stat.get(), 0, sizeof(int32_t) * (size_t)chunk * nc, v.st);   // (clusters without variables)
   auto t_last = std::chrono::steady_clock::now();
   auto phase = [&](int k) {   // timed variant only
     if (!ms) return;
@@ -326,50 +327,48 @@ static int sample_posterior(pgbp_engine* e, int32_t tree, int32_t site_begin, in
     const size_t row = sizeof(double) * size;
     for (int s0 = 0; herr == hipSuccess && s0 < ns; s0 += chunk) {
       const int n = std::min(chunk, ns - s0), gy = std::min(n, 65535);
-      const SampItem* it = d_items;
+      const SampItem* it = d_items.get();
       if (n_class[0] > 0)
         hipLaunchKernelGGL((sample_factor<64, 16>), dim3((n_class[0] + 3) / 4, gy), dim3(64), sizeof(double) * 4 * kSampSmallRegion,
-                           v.st, v.pool, p.pool_stride(), v.bs16, p.fast_p, it, n_class[0], d_idx, kSampSmallRegion,
-                           site_begin + s0, n, d_f, f_stride, d_stat, nc);
+                           v.st, v.pool, p.pool_stride(), v.bs16, p.fast_p, it, n_class[0], d_idx.get(), kSampSmallRegion,
+                           site_begin + s0, n, d_f.get(), f_stride, d_stat.get(), nc);
       it += n_class[0];
       if (n_class[1] > 0)
         hipLaunchKernelGGL((sample_factor<64, 64>), dim3(n_class[1], gy), dim3(64), b1, v.st, v.pool, p.pool_stride(), v.bs16,
-                           p.fast_p, it, n_class[1], d_idx, 0, site_begin + s0, n, d_f, f_stride, d_stat, nc);
+                           p.fast_p, it, n_class[1], d_idx.get(), 0, site_begin + s0, n, d_f.get(), f_stride, d_stat.get(), nc);
       it += n_class[1];
       if (n_class[2] > 0)
         hipLaunchKernelGGL((sample_factor<256, 256>), dim3(n_class[2], gy), dim3(256), b2, v.st, v.pool, p.pool_stride(), v.bs16,
-                           p.fast_p, it, n_class[2], d_idx, 0, site_begin + s0, n, d_f, f_stride, d_stat, nc);
-      hipLaunchKernelGGL(sample_info, dim3(gy), dim3(256), 0, v.st, d_stat, d_order, nc, n, d_info + s0);
+                           p.fast_p, it, n_class[2], d_idx.get(), 0, site_begin + s0, n, d_f.get(), f_stride, d_stat.get(), nc);
+      hipLaunchKernelGGL(sample_info, dim3(gy), dim3(256), 0, v.st, d_stat.get(), d_order.get(), nc, n, d_info.get() + s0);
       phase(0);
       for (int d0 = 0; herr == hipSuccess && d0 < n_draws; d0 += dchunk) {
         const int nd = std::min(dchunk, n_draws - d0);
         // rows = draws: [nd][n][size] on the device, [n_draws][ns][size] on the host
         if (n == ns)
-          herr = hipMemcpyAsync(d_z, z + (size_t)d0 * ns * size, row * n * nd, hipMemcpyHostToDevice, v.st);
+          herr = hipMemcpyAsync(d_z.get(), z + (size_t)d0 * ns * size, row * n * nd, hipMemcpyHostToDevice, v.st);
         else
-          herr = hipMemcpy2DAsync(d_z, row * n, z + ((size_t)d0 * ns + s0) * size, row * ns, row * n, nd, hipMemcpyHostToDevice, v.st);
+          herr = hipMemcpy2DAsync(d_z.get(), row * n, z + ((size_t)d0 * ns + s0) * size, row * ns, row * n, nd, hipMemcpyHostToDevice, v.st);
         phase(1);
         for (size_t l = 0; herr == hipSuccess && l + 1 < level_off.size(); ++l) {
           const int ni = level_off[l + 1] - level_off[l], mp = level_mpad[l];
           const int64_t threads = (int64_t)ni * nd * mp;
           hipLaunchKernelGGL(sample_apply, dim3((unsigned)((threads + 255) / 256), gy), dim3(256), 0, v.st,
-                             d_items + n_items + level_off[l], ni, mp, nd, n, d_idx, d_f, f_stride, d_info + s0, d_z, d_x, size);
+                             d_items.get() + n_items + level_off[l], ni, mp, nd, n, d_idx.get(), d_f.get(), f_stride, d_info.get() + s0, d_z.get(), d_x.get(), size);
         }
         if (herr == hipSuccess) herr = hipGetLastError();
         phase(2);
         if (herr == hipSuccess && n == ns)
-          herr = hipMemcpyAsync(x + (size_t)d0 * ns * size, d_x, row * n * nd, hipMemcpyDeviceToHost, v.st);
+          herr = hipMemcpyAsync(x + (size_t)d0 * ns * size, d_x.get(), row * n * nd, hipMemcpyDeviceToHost, v.st);
         else if (herr == hipSuccess)
-          herr = hipMemcpy2DAsync(x + ((size_t)d0 * ns + s0) * size, row * ns, d_x, row * n, row * n, nd, hipMemcpyDeviceToHost, v.st);
+          herr = hipMemcpy2DAsync(x + ((size_t)d0 * ns + s0) * size, row * ns, d_x.get(), row * n, row * n, nd, hipMemcpyDeviceToHost, v.st);
         phase(3);
       }
     }
   }
-  if (herr == hipSuccess && info) herr = hipMemcpyAsync(info, d_info, sizeof(int32_t) * (size_t)ns, hipMemcpyDeviceToHost, v.st);
+  if (herr == hipSuccess && info) herr = hipMemcpyAsync(info, d_info.get(), sizeof(int32_t) * (size_t)ns, hipMemcpyDeviceToHost, v.st);
   const hipError_t serr = hipStreamSynchronize(v.st);   // (also when something failed: the uploads read this call's locals)
   if (herr == hipSuccess) herr = serr;
-  for (void* q : {(void*)d_items, (void*)d_idx, (void*)d_order, (void*)d_stat, (void*)d_info, (void*)d_f, (void*)d_z, (void*)d_x})
-    if (q) (void)hipFree(q);
   if (herr != hipSuccess) return engine_fail(e, PGBP_ERR_HIP, fn + hipGetErrorString(herr));
   return PGBP_OK;
 }

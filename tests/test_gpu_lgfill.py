@@ -619,3 +619,87 @@ def test_exact_reml_with_fully_missing_sisters(P):
     cgb2.assignfactors_lg_(np.array([[[g["sigma2"]]]]), [g["mu"]])
     ll2, info = cgb2.loglik_lg()
     assert not info.any() and abs(ll2[0] - g["ll"]) <= 1e-10 * abs(g["ll"])
+
+
+@pytest.mark.parametrize("fill", ["bm_tree", "lg"])
+@pytest.mark.parametrize("p,ns", [(1, 64), (1, 65), (2, 1)], ids=["p1-ns64", "p1-ns65", "p2-ns1"])
+def test_reused_engine_equals_a_fresh_one_bit_for_bit(P, fill, p, ns):
+    """One engine through every path that acquires, swaps or replaces device buffers, against a fresh engine given only
+    the final inputs: set-up, assign factors, log-likelihood, pgbp_get_beliefs (back to the plain layout), log-likelihood
+    again (into the site-minor twins that exist by then), set-up again with other tip data, schedule again,
+    log-likelihood.  64 sites: the smallest batch in the site-minor layout; 65: its rows are padded, so the row length is
+    not the number of sites; p = 2 on one site: no site-minor layout at all.  The second set-up replaces the parameter
+    slots, so the parameters are assigned again behind it (the device fill has nothing to read otherwise).
+    Log-likelihood, info and every belief: the same bits."""
+    import ctypes as C
+    from pgbp_amd import _lib as L
+    from pgbp_amd import synth as S
+    rng = np.random.default_rng(7 * p + ns)
+    tr = S.random_tree(4, rng)
+    prob = S.cliquetree_of_tree(tr, p)
+    psz = int(prob.packed_off[-1])
+
+    def inputs():
+        X = np.zeros((ns, tr.nnodes, p))
+        X[:, tr.is_leaf] = rng.normal(size=(ns, tr.ntips, p))
+        R = np.stack([(lambda r: (r + r.T) / 2)(S.random_rate_matrix(p, rng)) for _ in range(ns)])
+        return X, R, rng.normal(size=(ns, p))
+
+    def setup(eng, X):
+        if fill == "bm_tree":
+            eng.bm_tree_setup(*S.bm_tree_table(tr, prob), X)
+        else:
+            eng.lg_setup(S.lg_tree_table(tr, prob, p), X)
+
+    def assign(eng, R, mu):
+        if fill == "bm_tree":
+            eng.assignfactors_bm_(R, mu)
+        else:
+            eng.assignfactors_lg_(R[:, None], mu)
+
+    def loglik(eng):
+        o = eng._opts()
+        enqueue = eng._lib.pgbp_enqueue_loglik_bm if fill == "bm_tree" else eng._lib.pgbp_enqueue_loglik_lg
+        assert enqueue(eng._eng, 1, C.byref(o)) == 0, eng._lib.pgbp_last_error(eng._eng)
+
+    def beliefs(eng):
+        out = np.zeros((ns, psz))
+        assert eng._lib.pgbp_get_beliefs(eng._eng, L.f64p(out)) == 0, eng._lib.pgbp_last_error(eng._eng)
+        return out
+
+    def results(eng):
+        norm, info = np.zeros(ns), np.zeros(ns, np.int32)
+        assert eng._lib.pgbp_fetch_loglik(eng._eng, L.f64p(norm), L.i32p(info)) == 0
+        return norm, info, beliefs(eng)
+
+    def engine():
+        eng = P.ClusterGraphBelief.from_arrays(prob.dims, prob.sepset_clusters, prob.scope_off, prob.scope_idx,
+                                               np.zeros((ns, psz)), n_sites=ns)
+        eng.set_schedule(prob.schedule)
+        return eng
+
+    site_minor = p == 1 and ns >= 64
+    first, last = inputs(), inputs()
+    eng = engine()
+    setup(eng, first[0])
+    assign(eng, *first[1:])
+    loglik(eng)
+    assert bool(eng._lib.pgbp_layout(eng._eng) & 2) == site_minor
+    beliefs(eng)
+    assert eng._lib.pgbp_layout(eng._eng) & 2 == 0
+    loglik(eng)
+    assert bool(eng._lib.pgbp_layout(eng._eng) & 2) == site_minor
+    setup(eng, last[0])
+    eng.set_schedule(prob.schedule)
+    assign(eng, *last[1:])
+    loglik(eng)
+    got = results(eng)
+
+    fresh = engine()
+    setup(fresh, last[0])
+    assign(fresh, *last[1:])
+    loglik(fresh)
+    want = results(fresh)
+    assert not want[1].any() and np.all(np.isfinite(want[0]))
+    for g, w in zip(got, want):
+        assert g.tobytes() == w.tobytes()
