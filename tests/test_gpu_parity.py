@@ -1742,8 +1742,10 @@ def test_first_failure_in_the_wave_per_task_kernels(P, p, where):
     """A clique tree of a network (generic-class tasks: the register-resident small-message body for p = 3, 4, the in-LDS
     body for p = 20; level launches at the leaf end, chunks of fused levels at the root end): clusters whose J is made
     negative definite fail at their first pivot.  The engine reports the failure the reference's sequential postorder
-    meets first (the largest edge index, src/calibration.jl:121) with its PosDefException.info, from whichever launch
-    mode ran the message; without the damage the same engine calibrates."""
+    meets first (the largest edge index, src/calibration.jl:121), from whichever launch mode ran the message; without
+    the damage the same engine calibrates.  Every pivot candidate is negative here, so the only PosDefException.info this
+    test sees is 1: info at a chosen pivot k > 1 is tests/test_gpu_message_shapes.py (test_info_at_a_chosen_pivot and,
+    through a traversal, test_kernels_that_only_a_traversal_reaches)."""
     import ctypes as C
     from pgbp_amd import _lib as L
     rng = np.random.default_rng(300 + p)
