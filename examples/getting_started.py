@@ -54,6 +54,17 @@ def main():
         tip = g["taxa"][int(cgb._lg["data_row"][loo["families"][worst]])]
         print(f"leave-one-out: summed log predictive density {loo['total']:.6f}; largest |z| {abs(z[worst]):.3f} at tip {tip} "
               f"(observed {loo['y'][worst, 0]:.4f}, predicted {loo['mean'][worst, 0]:.4f} +- {np.sqrt(loo['cov'][worst, 0, 0]):.4f})")
+        # derivatives in every edge from the same calibration: where would a shift of the mean help most, and which
+        # inheritance do the traits pull at?  (no root-prior family here: family f is the family of node f + 1)
+        dg = cgb.edge_gradient_lg()
+        f = int(np.argmax(np.abs(dg["dshift"][:, 0])))
+        parents = [names[q - 1] for q in net.node2family[f + 1][1:]]
+        print(f"edge gradient: largest |dshift| {dg['dshift'][f, 0]:.4f} on the edge(s) {parents} -> {names[f + 1]}")
+        hyb = np.nonzero(fam["n_parents"] == 2)[0]
+        if len(hyb):
+            h = int(hyb[0])
+            print(f"first hybrid {names[h + 1]}: dgamma {dg['dgamma'][h]} (free partials; with gamma_2 = 1 - gamma_1: "
+                  f"{dg['dgamma'][h, 0] - dg['dgamma'][h, 1]:.4f}), dlength {dg['dlength'][h]}")
 
 
 if __name__ == "__main__":

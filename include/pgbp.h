@@ -346,6 +346,45 @@ int pgbp_bm_exact_stats(pgbp_engine* e, int32_t site_begin, int32_t site_end, do
  * whose family variance is not): that site's outputs are NaN. */
 int pgbp_lg_gradient(pgbp_engine* e, int32_t site_begin, int32_t site_end, double* dR, double* dmu, double* dalpha,
                      double* dtheta, int32_t* info);
+/* DERIVATIVES OF THE LOG-LIKELIHOOD IN EVERY EDGE -- its length, its inheritance and a shift of the mean on it -- from the
+ * CURRENT beliefs and the parameters the engine kept from the last pgbp_lg_assignfactors (shared or per site), for sites
+ * [site_begin, site_end).  The same Fisher's-identity sweep as pgbp_lg_gradient, without its sum over the families, and exact
+ * under the same condition: beliefs calibrated (postorder AND preorder) on a clique tree under those parameters; not verified.
+ * Per family f, with O = child_mask, j = V_OO^-1 and e, M, G_V = (j M j - j) / 2, g_w = j e, g_qk = E[r' j x_k] as documented
+ * for pgbp_lg_gradient, per parent edge k < n_parents[f]:
+ *     dX_k = dvc_k/dX tr(G_V R[colour_k]_OO) + dwc_k/dX theta_O' g_w + dqc_k/dX g_qk,     X in {length t, inheritance gamma},
+ *     BM:                    d/dt: dqc = 0, dvc = gamma^2, dwc = 0;                      d/dgamma: dqc = 1, dvc = 2 gamma t, dwc = 0;
+ *     OU, a = exp(-alpha t): d/dt: dqc = -gamma alpha a, dvc = 2 gamma^2 alpha a^2, dwc = gamma alpha a;
+ *                            d/dgamma: dqc = a, dvc = 2 gamma (1 - a^2), dwc = 1 - a.
+ * Outputs, site-major; any of the three may be NULL, not all three:
+ *   dlength [sites][n_families][K], dgamma [sites][n_families][K] (K = max_parents): entry k in the per-parent order given to
+ *       pgbp_lg_setup.  dgamma is the FREE partial in each gamma_k; that a hybrid's gamma sum to 1 is the caller's constraint:
+ *       d/dgamma_major at gamma_minor = 1 - gamma_major is dgamma[major] - dgamma[minor].  Entries k >= n_parents[f] are NaN
+ *       (no such edge), every entry of a root-prior family included.  A family the factor fill skips (child_mask == 0)
+ *       writes 0 for its real edges.
+ *   dshift [sites][n_families][p]: the derivative in an additive displacement s of the child's conditional mean
+ *       (r = x_child - sum_k qc_k x_k - w - s), that is g_w embedded into the p traits, 0 outside O.  For a tree edge this is
+ *       the score of a mean shift on that edge; for a root-prior family it is the family's dmu term.  Skipped families: 0.
+ *   info [sites] (may be NULL): as pgbp_lg_gradient's; that site's outputs are all NaN, other sites are unaffected.
+ * Device (csrc/pgbp_edge.hip): one workgroup per (family, site) -- 64 threads while every family's cluster has at most 64
+ * variables, else 256 -- solves the cluster in LDS (the solve of pgbp_moments), forms the family quantities and writes its
+ * own K + K + p outputs: no reduction, no atomics on doubles, every sum in a fixed index order.  What a (family, site)
+ * writes depends on nothing else in the call; two calls return the same bytes.  Device copies of the outputs of a chunk of
+ * sites at a time (256 MB at most), one stream synchronisation per call.  Read-only on the beliefs; every layout, as
+ * pgbp_lg_gradient.
+ * Fails before any launch with PGBP_ERR_STATE without a family table or before the first pgbp_lg_assignfactors, with
+ * PGBP_ERR_INVALID for a site range out of bounds, for all three outputs NULL, for a family whose cluster has more than 128
+ * variables (the message names the family and the cluster), and when the LDS need -- the largest cluster's working matrix
+ * plus p x (2p + 1) + 3 p x p doubles of family scratch -- exceeds 160 KB. */
+int pgbp_lg_edge_gradient(pgbp_engine* e, int32_t site_begin, int32_t site_end, double* dlength, double* dgamma,
+                          double* dshift, int32_t* info);
+/* Replace the lengths and / or the inheritances of the family table on the device without a new pgbp_lg_setup: length and
+ * gamma are [n_families * max_parents] as in pgbp_lg_families, either may be NULL (left as it is).  The per-cluster records
+ * the thread-per-site fill keeps are rewritten too.  The checks of pgbp_lg_setup apply (lengths of real edges positive and
+ * finite, inheritances finite): PGBP_ERR_INVALID with NOTHING changed.  Data, masks and parameters are left alone; beliefs
+ * and factors are not refilled: the next pgbp_lg_assignfactors or pgbp_enqueue_loglik_lg uses the new values.
+ * PGBP_ERR_STATE without a family table.  Two small copies and one stream synchronisation. */
+int pgbp_lg_set_edges(pgbp_engine* e, const double* length, const double* gamma);
 /* LEAVE-ONE-OUT predictive moments of every tip from the CURRENT beliefs, for sites [site_begin, site_end): for each tip family
  * of the table given to pgbp_lg_setup (child_pos < 0, data_row >= 0, at least one observed trait: O = child_mask, o = |O|), the
  * distribution of the tip's observed values y_O given the data of all OTHER tips, with the parameters the engine kept from the

@@ -671,6 +671,71 @@ class ClusterGraphBelief:
             return norm, grad
         return float(norm[self.site]), self._gradient_of_site(grad, self.site)
 
+    def edge_gradient_lg(self, all_sites=False):
+        """pgbp_lg_edge_gradient on the current beliefs: the derivative of the log-likelihood in every edge length, in every
+        inheritance and in a shift of the mean on every edge, under the parameters of the last assignfactors_lg_ -- one sweep
+        over the node families, each family writing its own numbers.  EXACT ONLY when the beliefs are calibrated (postorder
+        and preorder) on a clique tree under those parameters (not verified), as gradient_lg.
+        Returns a dict: dlength, dgamma [n_families, K] (K = max_parents, the per-parent order of the family table given to
+        lg_setup; NaN where a family has no such edge; dgamma is the FREE partial in each gamma: at gamma_minor =
+        1 - gamma_major the derivative in gamma_major is dgamma[major] - dgamma[minor]), dshift [n_families, p] (the score of
+        an additive shift of the child's conditional mean; a root-prior family: its dmu term) and info; with a leading site
+        axis when all_sites.  A site whose info is not 0 holds NaN; for the current site that raises."""
+        p = self._lg_p
+        nf = len(self._lg["cluster"])
+        K = self._lg["length"].size // nf if nf else 1
+        s0, s1 = (0, self.n_sites) if all_sites else (self.site, self.site + 1)
+        n = s1 - s0
+        dlength = np.zeros((n, nf, K))
+        dgamma = np.zeros((n, nf, K))
+        dshift = np.zeros((n, nf, p))
+        info = np.zeros(n, dtype=np.int32)
+        _check(self._lib.pgbp_lg_edge_gradient(self._eng, s0, s1, L.f64p(dlength), L.f64p(dgamma), L.f64p(dshift),
+                                               L.i32p(info)), self._eng)
+        d = dict(dlength=dlength, dgamma=dgamma, dshift=dshift, info=info)
+        return d if all_sites else self._edge_gradient_of_site(d, 0)
+
+    @staticmethod
+    def _edge_gradient_of_site(d, s):
+        if d["info"][s]:
+            raise np.linalg.LinAlgError(f"PosDefException: belief {d['info'][s] - 1} is not positive definite")
+        return dict(dlength=d["dlength"][s].copy(), dgamma=d["dgamma"][s].copy(), dshift=d["dshift"][s].copy(), info=0)
+
+    def loglik_and_edge_gradient_lg(self, schedule_tree, all_sites=False):
+        """Log-likelihood and its derivatives in every edge under the parameters of the last assignfactors_lg_ on a clique
+        tree: the steps of loglik_and_gradient_lg with the edge sweep (edge_gradient_lg) in place of the parameter sweep.
+        Returns (loglik, edge-gradient dict): the current site's values, or arrays over the sites (info of a failed site is
+        not 0 and its values are NaN) when all_sites."""
+        self._ensure_schedule([schedule_tree])
+        o = self._opts()
+        pa = np.asarray(schedule_tree[-2]).reshape(-1)
+        root = int(pa[0]) if pa.size else 0
+        _check(self._lib.pgbp_enqueue_calibrate(self._eng, 1, 1, C.byref(o)), self._eng)
+        _check(self._lib.pgbp_enqueue_integrate(self._eng, root), self._eng)
+        grad = self.edge_gradient_lg(all_sites=True)
+        norm = np.zeros(self.n_sites)
+        info = np.zeros(self.n_sites, dtype=np.int32)
+        _check(self._lib.pgbp_fetch_loglik(self._eng, L.f64p(norm), L.i32p(info)), self._eng)
+        grad["info"] = np.where(grad["info"] != 0, grad["info"], info)
+        norm = np.where(grad["info"] != 0, np.nan, norm)
+        if all_sites:
+            return norm, grad
+        return float(norm[self.site]), self._edge_gradient_of_site(grad, self.site)
+
+    def set_edges_lg(self, length=None, gamma=None):
+        """pgbp_lg_set_edges: replace the edge lengths and / or inheritances of the family table given to lg_setup
+        ([n_families * K] each, the table's own layout; None: left as it is) on the device, without uploading the data
+        again.  The next assignfactors_lg_ or loglik_lg uses them; beliefs and factors are not refilled by this call."""
+        nk = self._lg["length"].size
+        arr = {}
+        for name, v in (("length", length), ("gamma", gamma)):
+            if v is not None:
+                arr[name] = np.ascontiguousarray(np.asarray(v, np.float64).reshape(-1))
+                assert arr[name].size == nk, name
+        _check(self._lib.pgbp_lg_set_edges(self._eng, L.f64p(arr["length"]) if "length" in arr else None,
+                                           L.f64p(arr["gamma"]) if "gamma" in arr else None), self._eng)
+        self._lg.update(arr)
+
     def loo_lg(self, all_sites=False):
         """pgbp_lg_loo on the current beliefs: the leave-one-out predictive distribution of every tip that has data, given
         the data of all other tips, under the parameters of the last assignfactors_lg_ -- one sweep over the tip families.

@@ -179,6 +179,11 @@ struct pgbp_engine {
   LgParams lgp{};
   LgBufs lg_bufs;
   bool lg_ready = false, lg_have_params = false, lg_uni_ok = false;
+  // host side of the table for pgbp_lg_set_edges: families, parents of each, and -- where LgStatic::simple exists -- its
+  // records with the family each was made from
+  int32_t lg_nf = 0;
+  std::vector<int32_t> lg_h_np, lg_h_simple_fam;
+  std::vector<LgSimpleFam> lg_h_simple;
   std::string err;
   // a step of an asynchronous enqueue that could not be issued (a workspace that could not be allocated: ensure_ws has
   // set `err`): the launches that needed it were skipped; every entry point that enqueued, and the next pgbp_sync /
@@ -1716,8 +1721,11 @@ int pgbp_lg_setup(pgbp_engine* e, const pgbp_lg_families* f) {
     HIPCHK(e, hipStreamSynchronize(e->st));
   }
   // one record per cluster where every cluster holds exactly one family with at most one parent and there are no scope masks
+  std::vector<LgSimpleFam> h_simple;
+  std::vector<int32_t> h_simple_fam;
   if (uni_ok && !f->child_mask && !f->parent_mask && f->n_families == nc) {
     std::vector<LgSimpleFam> sf(nc);
+    std::vector<int32_t> sfam(nc);
     bool simple = true;
     for (int c = 0; c < nc && simple; ++c) {
       if (count[c + 1] - count[c] != 1) { simple = false; break; }
@@ -1732,10 +1740,19 @@ int pgbp_lg_setup(pgbp_engine* e, const pgbp_lg_families* f) {
       r.gamma = np > 0 ? f->gamma[(size_t)i * K] : 0.0;
       if (r.cpos > 1 || r.ppos > 1) { simple = false; break; }
       sf[c] = r;
+      sfam[c] = i;
     }
     if (simple && (rc = upload(e, B.simple, sf))) return rc;
+    if (simple) {
+      h_simple = std::move(sf);
+      h_simple_fam = std::move(sfam);
+    }
   }
   e->lg_bufs = std::move(B);
+  e->lg_nf = f->n_families;
+  e->lg_h_np.assign(f->n_parents, f->n_parents + nf);
+  e->lg_h_simple = std::move(h_simple);
+  e->lg_h_simple_fam = std::move(h_simple_fam);
   const LgBufs& L = e->lg_bufs;
   e->lg = LgStatic{pp, K, f->n_rates, f->n_rows, L.off.get(), L.fam.get(), L.np.get(), L.cp.get(), L.row.get(), L.pp.get(), L.len.get(),
                    L.gam.get(), L.col.get(), L.data.get(), L.cm.get(), L.pm.get(), L.data_sm.get(), L.simple.get()};
@@ -1795,6 +1812,39 @@ int pgbp_lg_assignfactors(pgbp_engine* e, const pgbp_lg_params* m) {
     if (rc) return rc;
   }
   return lg_fill_async(e, true);
+}
+
+int pgbp_lg_set_edges(pgbp_engine* e, const double* length, const double* gamma) {
+  DeviceScope device_scope(e);
+  if (!e) return PGBP_ERR_INVALID;
+  if (!e->lg_ready) return e->fail(PGBP_ERR_STATE, "pgbp_lg_set_edges: no family table (call pgbp_lg_setup first)");
+  const int K = e->lg.K, nf = e->lg_nf;
+  // the checks of pgbp_lg_setup, all of them before anything changes
+  for (int i = 0; i < nf; ++i)
+    for (int k = 0; k < e->lg_h_np[i]; ++k) {
+      const size_t o = (size_t)i * K + k;
+      const bool bad_length = length && (!(length[o] > 0.0) || !std::isfinite(length[o]));
+      if (bad_length || (gamma && !std::isfinite(gamma[o])))
+        return e->fail(PGBP_ERR_INVALID, "pgbp_lg_set_edges: family " + std::to_string(i) + ": " +
+                                             (bad_length ? "parent edge length must be positive (degenerate families are out of scope)"
+                                                         : "inheritance not finite"));
+    }
+  const size_t bytes = (size_t)nf * K * sizeof(double);
+  if (length && bytes) HIPCHK(e, hipMemcpyAsync(e->lg_bufs.len.get(), length, bytes, hipMemcpyHostToDevice, e->st));
+  if (gamma && bytes) HIPCHK(e, hipMemcpyAsync(e->lg_bufs.gam.get(), gamma, bytes, hipMemcpyHostToDevice, e->st));
+  if (!e->lg_h_simple.empty()) {   // the per-cluster records of the thread-per-site fill carry their own copies
+    for (size_t c = 0; c < e->lg_h_simple.size(); ++c) {
+      LgSimpleFam& r = e->lg_h_simple[c];
+      if (r.np == 0) continue;
+      const size_t o = (size_t)e->lg_h_simple_fam[c] * K;
+      if (length) r.length = length[o];
+      if (gamma) r.gamma = gamma[o];
+    }
+    HIPCHK(e, hipMemcpyAsync(e->lg_bufs.simple.get(), e->lg_h_simple.data(), e->lg_h_simple.size() * sizeof(LgSimpleFam),
+                             hipMemcpyHostToDevice, e->st));
+  }
+  HIPCHK(e, hipStreamSynchronize(e->st));  // the host buffers may go away
+  return PGBP_OK;
 }
 
 int pgbp_enqueue_loglik_lg(pgbp_engine* e, int32_t reps, const pgbp_opts* opts) {

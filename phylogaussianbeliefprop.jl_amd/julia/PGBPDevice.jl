@@ -291,6 +291,39 @@ function lg_loo(o::DeviceClusterGraphBelief, p::Integer)
 end
 
 """
+    lg_edge_gradient(obj, p, nfamilies, K) -> (dlength, dgamma, dshift)
+
+Derivatives of the log-likelihood in every edge from the current beliefs (pgbp_lg_edge_gradient: one sweep over the node
+families, each writing its own numbers): `dlength[k, f]` and `dgamma[k, f]` for parent edge k of family f of the table given to
+pgbp_lg_setup (`K` = its max_parents; NaN where the family has no such edge; `dgamma` is the free partial in each inheritance:
+with gamma_minor = 1 - gamma_major the derivative in gamma_major is `dgamma[major] - dgamma[minor]`), `dshift[:, f]` the score of
+an additive shift of the child's conditional mean (a root-prior family: its dmu term).  Exact under the condition of
+`lg_gradient`.  A cluster that is not positive definite throws its PosDefException.
+"""
+function lg_edge_gradient(o::DeviceClusterGraphBelief, p::Integer, nfamilies::Integer, K::Integer)
+    dlength = zeros(K, max(nfamilies, 1)); dgamma = zeros(K, max(nfamilies, 1)); dshift = zeros(p, max(nfamilies, 1))
+    info = Ref(Int32(0))
+    check(o.handle, @ccall LIB.pgbp_lg_edge_gradient(o.handle::Ptr{Cvoid}, Int32(0)::Int32, Int32(1)::Int32, dlength::Ptr{Float64}, dgamma::Ptr{Float64}, dshift::Ptr{Float64}, info::Ref{Int32})::Cint)
+    info[] == 0 || throw(PGBP.LA.PosDefException(info[]))
+    return (dlength[:, 1:nfamilies], dgamma[:, 1:nfamilies], dshift[:, 1:nfamilies])
+end
+
+"""
+    lg_set_edges!(obj; length = nothing, gamma = nothing)
+
+New edge lengths and / or inheritances for the family table given to pgbp_lg_setup (pgbp_lg_set_edges): `K x nfamilies`
+matrices (or vectors in that order), `nothing` leaves the values as they are.  The next pgbp_lg_assignfactors or
+pgbp_enqueue_loglik_lg uses them; a length that is not positive and finite is an error and nothing changes.
+"""
+function lg_set_edges!(o::DeviceClusterGraphBelief; length::Union{Nothing,AbstractArray{Float64}} = nothing,
+                       gamma::Union{Nothing,AbstractArray{Float64}} = nothing)
+    len = length === nothing ? C_NULL : Array{Float64}(length)   # (the call keeps what it converts alive)
+    gam = gamma === nothing ? C_NULL : Array{Float64}(gamma)
+    check(o.handle, @ccall LIB.pgbp_lg_set_edges(o.handle::Ptr{Cvoid}, len::Ptr{Float64}, gam::Ptr{Float64})::Cint)
+    return nothing
+end
+
+"""
     sample_size(obj) -> Int
 
 Doubles per draw of `sample_posterior!`: the sum of the cluster dimensions (pgbp_sample_size).
