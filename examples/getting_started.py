@@ -65,6 +65,22 @@ def main():
             h = int(hyb[0])
             print(f"first hybrid {names[h + 1]}: dgamma {dg['dgamma'][h]} (free partials; with gamma_2 = 1 - gamma_1: "
                   f"{dg['dgamma'][h, 0] - dg['dgamma'][h, 1]:.4f}), dlength {dg['dlength'][h]}")
+        # imputation: hide two values, set an engine up on the incomplete table and predict them from everything else
+        x = np.array(g["x"], float)[:, None]
+        hidden = [1, len(x) - 2]
+        xm = x.copy()
+        xm[hidden] = np.nan
+        fam_m = P.lg_families(st.clusters, st.node2cluster, net.node2family, st.node2fixed,
+                              [list(zip(net.length[i], net.gamma[i], net.color[i])) for i in range(net.nnodes)],
+                              [row.get(names[i], -1) for i in range(net.nnodes)], 1, data=xm)
+        cgm = P.ClusterGraphBelief.from_arrays(st.dims, st.sepset_clusters, st.scope_off, st.scope_idx, None)
+        cgm.lg_setup(fam_m, xm)
+        cgm.assignfactors_lg_(np.array([[[g["model"]["sigma2"]]]], float), [g["model"]["mu"]])
+        ll_m, imp = cgm.impute_and_loglik_lg(sched[0])
+        filled = P.imputed_data(imp, xm)
+        for i, r in enumerate(imp["rows"]):
+            print(f"imputed {g['taxa'][int(r)]}: {filled[int(r), 0]:.4f} +- {np.sqrt(imp['cov'][i, 0, 0]):.4f} "
+                  f"(hidden value {x[int(r), 0]:.4f}); log-likelihood of the remaining data {ll_m:.6f}")
 
 
 if __name__ == "__main__":

@@ -428,6 +428,48 @@ int     pgbp_lg_loo_families(pgbp_engine* e, int32_t* fam);
 int     pgbp_lg_loo(pgbp_engine* e, int32_t site_begin, int32_t site_end, double* mean, double* cov, double* lpd,
                     double* total, int32_t* info);
 void    pgbp_loo_scratch_limit(int64_t doubles);
+/* IMPUTATION of the missing tip values from CALIBRATED beliefs, for sites [site_begin, site_end): the posterior mean and
+ * covariance of the traits a tip does not observe, given ALL the data (the tip's own observed traits included) -- the
+ * leave-NOTHING-out complement of pgbp_lg_loo, with the parameters the engine kept from the last pgbp_lg_assignfactors (shared
+ * or per site).  EXACT ONLY WHEN THE BELIEFS ARE CALIBRATED (postorder AND preorder) ON A CLIQUE TREE UNDER THOSE PARAMETERS;
+ * the call does not verify that.  On a loopy cluster graph, at a converged calibration, it is the Bethe approximation.
+ * A family of the table given to pgbp_lg_setup is LISTED when it is a tip family (child_pos < 0, data_row >= 0, n_parents >= 1)
+ * whose set M of missing traits (the complement of O = child_mask) is not empty; with NULL masks (complete data) nothing is
+ * listed.  Parent k is the FIXED ROOT when parent_pos < 0 and parent_mask is full (its constant qc_k mu enters); any other
+ * parent is a CLUSTER parent with scope parent_mask (possibly empty).  The PREDICTED traits are
+ *     P = M  intersected with the parent_mask of every cluster parent:
+ * a missing trait that some parent does not hold in scope is observed by no tip below that parent, its posterior is in no
+ * belief of the graph (it would take a sweep over the ancestors): it is NOT predicted -- NaN in the outputs, visible in the
+ * static mask `predicted`.  With Z = O u P, u = sum_k qc_k x_k, w = sum_k wc_k theta, V = sum_k vc_k R[colour_k] (the full
+ * p x p matrix; qc, vc, wc as in pgbp_lg_loo), m = J^-1 h and S = J^-1 of the family's cluster:
+ *     B = V_PO V_OO^-1 (empty when O is),   mean = E[u_P] + w_P + B (y_O - w_O - E[u_O]),
+ *     cov = [-B I] Cov(u_Z) [-B I]' + V_PP - B V_OP,
+ *     E[u_T] = sum_k qc_k m[idx_k(T)] (+ qc_k mu_T of the fixed root),  Cov(u_A, u_B) = sum_{a,b} qc_a qc_b S[idx_a(A), idx_b(B)]
+ * over the cluster parents, idx_k(t) = parent_pos + popcount(parent_mask below t).  (Given the parents, the tip's noise is
+ * independent of every other datum: its observed part is pinned by y_O, the rest is the Gaussian conditional.)
+ * pgbp_lg_impute_count: the number n of listed families (-1: no family table); pgbp_lg_impute_families: their indices into
+ * the table, in table order -- the order of every output -- and the mask P of each (bit t = trait t); either pointer may be
+ * NULL.  Outputs, site-major; either of mean and cov may be NULL, not both:
+ *   mean  [sites][n][p]    NaN outside P;
+ *   cov   [sites][n][p*p]  column-major, symmetric, both triangles written, NaN in the rows / columns outside P;
+ *   info  [sites][n]       (may be NULL) 0; -1: the family's P is empty (all NaN, no solve); 1: V_OO or the conditional variance
+ *         V_PP - B V_OP is not positive definite, or the cluster's belief is the constant 1 while a cluster parent is needed;
+ *         or 1 + PosDefException.info of the cluster.  Where info is not 0 that (family, site) is all NaN; others are unaffected.
+ * Device (csrc/pgbp_impute.hip): one workgroup per (listed family, site) solves the family's cluster in LDS (the solve of
+ * pgbp_moments; skipped when no parent is in a cluster) and writes its own p + p*p numbers.  No atomics, no reduction, every
+ * sum in index order: two calls return the same bytes, and a site's result does not depend on the other sites of the call.
+ * The device copies of the outputs of a chunk of sites at a time (256 MB at most; pgbp_impute_scratch_limit: that bound in
+ * doubles, process-wide, <= 0 restores the default -- the results do not depend on the chunks).  Read-only on the beliefs;
+ * every layout (a site-minor univariate batch is converted to the plain layout first); one stream synchronisation per call.
+ * Fails before any launch, as pgbp_lg_loo: PGBP_ERR_STATE without a family table or before the first pgbp_lg_assignfactors;
+ * PGBP_ERR_INVALID for a bad site range, when mean and cov are both NULL, for a family whose cluster has more than 128
+ * variables (the family and the cluster are named) or when mom_solve's matrix plus five p x p blocks exceed the 160 KB of
+ * LDS -- both taken over the clusters of ALL families of the table, before anything else is decided.
+ * A table with nothing listed returns PGBP_OK and writes nothing. */
+int32_t pgbp_lg_impute_count(pgbp_engine* e);
+int     pgbp_lg_impute_families(pgbp_engine* e, int32_t* fam, uint64_t* predicted);
+int     pgbp_lg_impute(pgbp_engine* e, int32_t site_begin, int32_t site_end, double* mean, double* cov, int32_t* info);
+void    pgbp_impute_scratch_limit(int64_t doubles);
 /* JOINT posterior draws of every cluster variable from CALIBRATED beliefs on a clique tree, for sites [site_begin, site_end):
  * the joint is prod clusters / prod sepsets, and one preorder sweep of schedule tree `tree` (an index into the schedule given to
  * pgbp_set_schedule, as pgbp_traverse's) that conditions each cluster on the sepset to its parent turns standard normals z

@@ -128,6 +128,10 @@ SYMBOLS = {
     "pgbp_lg_loo_families": (C.c_int, [_P, _I32P]),
     "pgbp_lg_loo": (C.c_int, [_P, C.c_int32, C.c_int32, _F64P, _F64P, _F64P, _F64P, _I32P]),
     "pgbp_loo_scratch_limit": (None, [C.c_int64]),
+    "pgbp_lg_impute_count": (C.c_int32, [_P]),
+    "pgbp_lg_impute_families": (C.c_int, [_P, _I32P, C.POINTER(C.c_uint64)]),
+    "pgbp_lg_impute": (C.c_int, [_P, C.c_int32, C.c_int32, _F64P, _F64P, _I32P]),
+    "pgbp_impute_scratch_limit": (None, [C.c_int64]),
     "pgbp_sample_posterior": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _F64P, _F64P, _I32P]),
     "pgbp_sample_size": (C.c_int64, [_P]),
     "pgbp_sample_scratch_limits": (None, [C.c_int64, C.c_int64]),

@@ -793,6 +793,62 @@ class ClusterGraphBelief:
         return float(norm[s]), {k: (v if k == "families" else (float(v[s]) if k == "total" else v[s].copy()))
                                 for k, v in loo.items()}
 
+    def impute_lg(self, all_sites=False):
+        """pgbp_lg_impute on the current beliefs: the posterior mean and covariance of the MISSING values of every tip, given
+        all the data (the tip's own observed traits included), under the parameters of the last assignfactors_lg_ -- one
+        sweep over the tip families that miss a trait.  EXACT ONLY when the beliefs are calibrated (postorder and preorder)
+        on a clique tree under those parameters (not verified); on a loopy cluster graph, at a converged calibration, it is
+        the Bethe approximation.  A missing trait that a parent of the tip does not hold in scope (no tip below that parent
+        observes it) is NOT predicted: NaN, predicted False -- the documented limit of the call.
+        Returns a dict: families [n] (indices into the family table given to lg_setup, the order of every other entry),
+        rows [n] (the data row of each tip), predicted [n, p] (bool, the same for every site), mean [n, p] and cov [n, p, p]
+        (NaN outside predicted), info [n] (0; -1: nothing of this tip is predicted; 1: the tip's variance is not positive
+        definite or its cluster's belief is still the constant 1; 1 + PosDefException.info of the cluster -- that tip's
+        entries are NaN, nothing raises); mean, cov and info with a leading site axis when all_sites."""
+        p = self._lg_p
+        n = int(self._lib.pgbp_lg_impute_count(self._eng))
+        if n < 0:
+            _check(self._lib.pgbp_lg_impute(self._eng, 0, 0, None, None, None), self._eng)
+            raise L.PgbpError(L.ERR_STATE, "pgbp_lg_impute_count failed")
+        fam = np.zeros(max(n, 1), dtype=np.int32)
+        pred = np.zeros(max(n, 1), dtype=np.uint64)
+        _check(self._lib.pgbp_lg_impute_families(self._eng, L.i32p(fam), pred.ctypes.data_as(C.POINTER(C.c_uint64))), self._eng)
+        fam, pred = fam[:n], pred[:n]
+        s0, s1 = (0, self.n_sites) if all_sites else (self.site, self.site + 1)
+        ns = s1 - s0
+        mean = np.full((ns, max(n, 1), p), np.nan)
+        cov = np.full((ns, max(n, 1), p, p), np.nan)
+        info = np.zeros((ns, max(n, 1)), dtype=np.int32)
+        _check(self._lib.pgbp_lg_impute(self._eng, s0, s1, L.f64p(mean), L.f64p(cov), L.i32p(info)), self._eng)
+        predicted = ((pred[:, None] >> np.arange(p, dtype=np.uint64)[None, :]) & np.uint64(1)).astype(bool).reshape(n, p)
+        d = dict(families=fam, rows=self._lg["data_row"][fam], predicted=predicted, mean=mean[:, :n],
+                 cov=cov[:, :n].transpose(0, 1, 3, 2), info=info[:, :n])
+        if all_sites:
+            return d
+        return {k: (v[0].copy() if k in ("mean", "cov", "info") else v) for k, v in d.items()}
+
+    def impute_and_loglik_lg(self, schedule_tree, all_sites=False):
+        """Log-likelihood and the imputed values of every tip under the parameters of the last assignfactors_lg_ on a clique
+        tree: beliefs reset from the factors that call filled -> one calibrate (postorder + preorder of `schedule_tree`) ->
+        integratebelief! at the tree's root cluster -> the sweep over the listed tip families (impute_lg), as
+        loo_and_loglik_lg does for the leave-one-out predictions.  Returns (loglik, impute dict): the current site's values,
+        or arrays over the sites when all_sites (loglik of a site whose calibration failed is NaN)."""
+        self._ensure_schedule([schedule_tree])
+        o = self._opts()
+        pa = np.asarray(schedule_tree[-2]).reshape(-1)
+        root = int(pa[0]) if pa.size else 0
+        _check(self._lib.pgbp_enqueue_calibrate(self._eng, 1, 1, C.byref(o)), self._eng)
+        _check(self._lib.pgbp_enqueue_integrate(self._eng, root), self._eng)
+        imp = self.impute_lg(all_sites=True)
+        norm = np.zeros(self.n_sites)
+        info = np.zeros(self.n_sites, dtype=np.int32)
+        _check(self._lib.pgbp_fetch_loglik(self._eng, L.f64p(norm), L.i32p(info)), self._eng)
+        norm = np.where(info != 0, np.nan, norm)
+        if all_sites:
+            return norm, imp
+        s = self.site
+        return float(norm[s]), {k: (v[s].copy() if k in ("mean", "cov", "info") else v) for k, v in imp.items()}
+
     def traffic_model(self):
         b = C.c_double()
         n = C.c_int64()
@@ -811,6 +867,18 @@ def loo_zscores(d):
         if o.any():
             z[ix][o] = np.linalg.solve(np.linalg.cholesky(cov[ix][np.ix_(o, o)]), (y[ix] - mean[ix])[o])
     return z
+
+
+def imputed_data(d, data):
+    """A copy of the data table [n_rows, p] (NaN where missing) with the entries the dict impute_lg returns predicts filled
+    by their posterior mean (d["mean"] [n, p]: one site); every other missing entry stays NaN, and so does a tip whose info
+    is not 0.  On the host."""
+    out = np.array(data, dtype=np.float64, copy=True)
+    mean, pred = np.asarray(d["mean"]), np.asarray(d["predicted"], bool)
+    assert out.ndim == 2 and mean.ndim == 2, "one site: data [n_rows, p], d['mean'] [n, p]"
+    for i, r in enumerate(np.asarray(d["rows"])):
+        out[int(r), pred[i]] = mean[i, pred[i]]
+    return out
 
 
 class _ResidualDict:

@@ -291,6 +291,39 @@ function lg_loo(o::DeviceClusterGraphBelief, p::Integer)
 end
 
 """
+    lg_impute_families(obj) -> (families::Vector{Int}, predicted::Vector{UInt64})
+
+The tip families of the table given to pgbp_lg_setup that miss a trait (1-based indices into it), in the order of `lg_impute`'s
+outputs, and per family the mask of the traits that are predicted (bit t-1 = trait t): the missing traits that every parent in a
+cluster holds in scope (pgbp_lg_impute_count, pgbp_lg_impute_families).
+"""
+function lg_impute_families(o::DeviceClusterGraphBelief)
+    n = @ccall LIB.pgbp_lg_impute_count(o.handle::Ptr{Cvoid})::Int32
+    n >= 0 || error("pgbp_lg_impute_count: no family table (call pgbp_lg_setup first)")
+    fam = zeros(Int32, max(n, 1)); pred = zeros(UInt64, max(n, 1))
+    check(o.handle, @ccall LIB.pgbp_lg_impute_families(o.handle::Ptr{Cvoid}, fam::Ptr{Int32}, pred::Ptr{UInt64})::Cint)
+    return (Int.(fam[1:n]) .+ 1, pred[1:n])
+end
+
+"""
+    lg_impute(obj, p) -> (mean, cov, info)
+
+Posterior moments of the missing values of every tip, given all the data, from the current beliefs (pgbp_lg_impute: one sweep
+over the tip families that miss a trait).  Exact under the condition of `lg_loo`.  `mean[:, i]` and `cov[:, :, i]` of listed
+family i (`lg_impute_families`) are NaN outside its predicted traits; `info[i]` is 0, -1 when nothing of the tip is predicted, 1
+when its variance is not positive definite, or 1 + PosDefException.info of the cluster (that tip's values are NaN; nothing is
+thrown).  `pgbp_impute_scratch_limit` bounds the device copies of the outputs, as `pgbp_loo_scratch_limit` does.
+"""
+function lg_impute(o::DeviceClusterGraphBelief, p::Integer)
+    n = length(lg_impute_families(o)[1])
+    mean = fill(NaN, p, max(n, 1)); cov = fill(NaN, p, p, max(n, 1)); info = zeros(Int32, max(n, 1))
+    check(o.handle, @ccall LIB.pgbp_lg_impute(o.handle::Ptr{Cvoid}, Int32(0)::Int32, Int32(1)::Int32, mean::Ptr{Float64}, cov::Ptr{Float64}, info::Ptr{Int32})::Cint)
+    return (mean[:, 1:n], cov[:, :, 1:n], info[1:n])
+end
+
+impute_scratch_limit(doubles::Integer) = @ccall LIB.pgbp_impute_scratch_limit(Int64(doubles)::Int64)::Cvoid
+
+"""
     lg_edge_gradient(obj, p, nfamilies, K) -> (dlength, dgamma, dshift)
 
 Derivatives of the log-likelihood in every edge from the current beliefs (pgbp_lg_edge_gradient: one sweep over the node
