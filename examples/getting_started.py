@@ -65,6 +65,14 @@ def main():
             h = int(hyb[0])
             print(f"first hybrid {names[h + 1]}: dgamma {dg['dgamma'][h]} (free partials; with gamma_2 = 1 - gamma_1: "
                   f"{dg['dgamma'][h, 0] - dg['dgamma'][h, 1]:.4f}), dlength {dg['dlength'][h]}")
+        # the engine can hold such a shift: fit the jump on that edge (the exact ML value at these parameters, from
+        # n p + 2 = 3 calibrations -- at 0, at the unit shift, and one that leaves the engine at the estimate: the
+        # log-likelihood is quadratic in the shifts) and see what it buys
+        fit = P.fit_shifts_lg(cgb, sched[0], [(f, 0)])
+        print(f"fitted shift on {parents[0]} -> {names[f + 1]}: {fit['shifts'][0, 0]:.4f} +- {fit['se'][0, 0]:.4f}; "
+              f"log-likelihood {norm:.6f} -> {fit['loglik']:.6f} (gain {fit['loglik'] - norm:.6f})")
+        assert fit["loglik"] >= norm
+        cgb.clear_shifts_lg()
         # imputation: hide two values, set an engine up on the incomplete table and predict them from everything else
         x = np.array(g["x"], float)[:, None]
         hidden = [1, len(x) - 2]

@@ -385,6 +385,33 @@ int pgbp_lg_edge_gradient(pgbp_engine* e, int32_t site_begin, int32_t site_end, 
  * and factors are not refilled: the next pgbp_lg_assignfactors or pgbp_enqueue_loglik_lg uses the new values.
  * PGBP_ERR_STATE without a family table.  Two small copies and one stream synchronisation. */
 int pgbp_lg_set_edges(pgbp_engine* e, const double* length, const double* gamma);
+/* MEAN SHIFTS ON EDGES: the reference's HeterogeneousShiftedBrownianMotion (src/evomodels/heterogeneousmodels.jl:152-179) and
+ * the displacement its generic factor code carries through tree edges and hybrid nodes (src/evomodels/evomodels.jl:208-245,
+ * :314-330).  A shift s_k (a p-vector) on parent edge k of family f makes the child's conditional mean
+ *     sum_k gamma_k (a_k x_k + (1 - a_k) theta + s_k),   a_k = 1 for BM, exp(-alpha t_k) for OU:
+ * in the notation of pgbp_lg_params the family's offset gains d = sum_k gamma_k s_k, the residual is
+ * r = x_child - sum_k qc_k x_k - w - d.  The coefficient of a shift is gamma_k under both models.  Variances, J and qc, vc, wc
+ * are untouched; the factor keeps the components O = child_mask[f] of d: a component of a shift outside O has no effect (not
+ * an error).
+ *   edge  [n_shifts]: edge[i] = f * max_parents + k, the index used by length and gamma of pgbp_lg_families; the list is sparse
+ *         (the device keeps a dense int32 slot map [n_families * max_parents], -1 for none, and the values);
+ *   value [n_shifts][p], or with per_site != 0 [n_sites][n_shifts][p] (allowed whether the parameters are shared or per site);
+ *   n_shifts = 0 clears the shifts (edge and value may be NULL).  The call REPLACES the previous list, it does not add to it.
+ * Takes effect as pgbp_lg_set_edges does: the next pgbp_lg_assignfactors or pgbp_enqueue_loglik_lg uses the shifts (every fill is
+ * followed by a correction of h and g of the clusters that hold a shifted family, csrc/pgbp_shift.hip: nothing is launched
+ * when none is set); beliefs and factors are not refilled by this call.  pgbp_lg_gradient, pgbp_lg_edge_gradient, pgbp_lg_loo and
+ * pgbp_lg_impute read the CURRENT shifts, as they read the current parameters: call them on beliefs calibrated under both.
+ * There dgamma[f][k] gains s_k,O' g_w; dshift keeps its meaning: the derivative in s_k is gamma_k * dshift[f].  pgbp_moments and
+ * pgbp_sample_posterior read beliefs only.  Shifts survive pgbp_lg_set_edges (gamma is read when the factors are filled); a new
+ * pgbp_lg_setup clears them.  An engine borrowed from a pgbp_group or pgbp_patterns (pgbp_group_engine, pgbp_patterns_engine)
+ * takes the call like any other; there is no group-level call.
+ * PGBP_ERR_STATE without a family table.  PGBP_ERR_INVALID with NOTHING changed (the previous shifts stay in force) and a text
+ * that names the entry for: an index out of range, k >= n_parents[f], a root-prior family (it has no edge), an edge listed
+ * twice, a value that is not finite.  Up to four copies (the slot map, the cluster list, the values -- n_sites * n_shifts * p
+ * doubles with per_site -- and, for a univariate per-site batch, their [shift][site] copy) and one stream synchronisation.
+ * pgbp_lg_shift_count: the number of shifts in force (0: none; -1: no family table). */
+int pgbp_lg_set_shifts(pgbp_engine* e, int32_t n_shifts, const int32_t* edge, const double* value, int32_t per_site);
+int32_t pgbp_lg_shift_count(pgbp_engine* e);
 /* LEAVE-ONE-OUT predictive moments of every tip from the CURRENT beliefs, for sites [site_begin, site_end): for each tip family
  * of the table given to pgbp_lg_setup (child_pos < 0, data_row >= 0, at least one observed trait: O = child_mask, o = |O|), the
  * distribution of the tip's observed values y_O given the data of all OTHER tips, with the parameters the engine kept from the

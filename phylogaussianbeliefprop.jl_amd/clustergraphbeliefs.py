@@ -586,6 +586,8 @@ class ClusterGraphBelief:
                          k["parent_mask"].ctypes.data_as(C.POINTER(C.c_uint64)) if k["parent_mask"] is not None else None)
         _check(self._lib.pgbp_lg_setup(self._eng, C.byref(t)), self._eng)
         self._lg_p, self._lg_nrates = int(fam["p"]), int(fam["n_rates"])
+        self._lg_shift_edges = np.zeros(0, np.int32)   # a new table clears the shifts (pgbp_lg_setup)
+        self._lg_last = None                           # ... and has no parameters yet
 
     def assignfactors_lg_(self, R, mu, model="bm", alpha=None, theta=None, sync=False):
         """assignfactors!(beliefs, model, ...) (src/beliefs.jl:786-861) on the device for a Brownian motion
@@ -605,6 +607,7 @@ class ClusterGraphBelief:
         m = L.LgParams(L.LG_OU if ou else L.LG_BM, int(per_site), L.f64p(R), L.f64p(al) if ou else None,
                        L.f64p(th) if ou else None, L.f64p(mu))
         _check(self._lib.pgbp_lg_assignfactors(self._eng, C.byref(m)), self._eng)
+        self._lg_last = (m, (R, mu, al, th))   # what loglik_and_shift_gradient_lg fills again (keeps the arrays alive)
         if sync:
             self._invalidate()
 
@@ -735,6 +738,81 @@ class ClusterGraphBelief:
         _check(self._lib.pgbp_lg_set_edges(self._eng, L.f64p(arr["length"]) if "length" in arr else None,
                                            L.f64p(arr["gamma"]) if "gamma" in arr else None), self._eng)
         self._lg.update(arr)
+
+    def _shift_edges(self, edges):
+        """(family, k) pairs or flat indices family * K + k -> flat int32 indices."""
+        nf = len(self._lg["cluster"])
+        K = self._lg["length"].size // nf if nf else 1
+        e = np.asarray(edges, np.int64)
+        if e.ndim == 2:
+            if e.shape[1] != 2:
+                raise ValueError("edges: (family, k) pairs or flat indices family * K + k")
+            if e.size and (e[:, 1].min() < 0 or e[:, 1].max() >= K):
+                raise ValueError(f"edges: k must be in 0 .. {K - 1}")
+            e = e[:, 0] * K + e[:, 1]
+        return np.ascontiguousarray(e.reshape(-1), np.int32)
+
+    def set_shifts_lg(self, edges, values):
+        """pgbp_lg_set_shifts: mean shifts on edges (the reference's HeterogeneousShiftedBrownianMotion, and the same
+        displacement under OU).  edges: (family, k) pairs -- k the parent edge in the per-parent order of the family table
+        given to lg_setup -- or flat indices family * K + k; values: [n, p], or [n_sites, n, p] for one set per site.  The
+        child's conditional mean gains sum_k gamma_k s_k; a component of a shift outside the family's child_mask has no
+        effect.  The call REPLACES the previous shifts (an empty list clears them); the next assignfactors_lg_ or loglik_lg
+        uses them, beliefs and factors are not refilled by this call.  The four sweeps (gradient_lg, edge_gradient_lg,
+        loo_lg, impute_lg) read the current shifts: call them on beliefs calibrated under them.  An invalid entry raises
+        and leaves the previous shifts in force."""
+        e = self._shift_edges(edges)
+        p = self._lg_p
+        v = np.asarray(values, np.float64)
+        per_site = v.ndim == 3
+        v = np.ascontiguousarray(v.reshape((self.n_sites, e.size, p) if per_site else (e.size, p)))
+        _check(self._lib.pgbp_lg_set_shifts(self._eng, int(e.size), L.i32p(e) if e.size else None,
+                                            L.f64p(v) if e.size else None, int(per_site)), self._eng)
+        self._lg_shift_edges = e
+
+    def clear_shifts_lg(self):
+        """Remove every mean shift (pgbp_lg_set_shifts with an empty list)."""
+        _check(self._lib.pgbp_lg_set_shifts(self._eng, 0, None, None, 0), self._eng)
+        self._lg_shift_edges = np.zeros(0, np.int32)
+
+    def shift_count_lg(self):
+        """pgbp_lg_shift_count: the number of shifts in force (0: none)."""
+        return int(self._lib.pgbp_lg_shift_count(self._eng))
+
+    def _shift_gradient_from(self, d):
+        e = getattr(self, "_lg_shift_edges", np.zeros(0, np.int32))
+        nf = len(self._lg["cluster"])
+        K = self._lg["length"].size // nf if nf else 1
+        gam = self._lg["gamma"].reshape(-1)[e]
+        return gam[None, :, None] * d["dshift"][:, e // K, :]
+
+    def shift_gradient_lg(self, all_sites=False):
+        """The derivative of the log-likelihood in every shift that is set: gamma_k * dshift[f] of edge_gradient_lg for the
+        edges given to set_shifts_lg, in their order: [n, p], or [n_sites, n, p] when all_sites.  EXACT ONLY when the beliefs
+        are calibrated on a clique tree under the current parameters and shifts, as edge_gradient_lg."""
+        d = self.edge_gradient_lg(all_sites=True)
+        s0 = 0 if all_sites else self.site
+        if not all_sites and d["info"][s0]:
+            raise np.linalg.LinAlgError(f"PosDefException: belief {d['info'][s0] - 1} is not positive definite")
+        g = self._shift_gradient_from(d)
+        return g if all_sites else g[s0].copy()
+
+    def loglik_and_shift_gradient_lg(self, schedule_tree, all_sites=False):
+        """Log-likelihood and its derivative in the shifts that are set, on a clique tree: the factors are filled again
+        with the parameters of the last assignfactors_lg_ (so that shifts set since then are in), then the steps of
+        loglik_and_edge_gradient_lg.  Returns (loglik, gradient [n, p]) of the current site, or arrays over the sites (NaN
+        where a site failed) when all_sites."""
+        if getattr(self, "_lg_last", None) is None:
+            raise L.PgbpError(L.ERR_STATE, "loglik_and_shift_gradient_lg: no parameters yet (call assignfactors_lg_ first)")
+        m, _keep = self._lg_last
+        _check(self._lib.pgbp_lg_assignfactors(self._eng, C.byref(m)), self._eng)
+        ll, d = self.loglik_and_edge_gradient_lg(schedule_tree, all_sites=True)
+        g = self._shift_gradient_from(d)
+        if all_sites:
+            return ll, g
+        if d["info"][self.site]:
+            raise np.linalg.LinAlgError(f"PosDefException: belief {d['info'][self.site] - 1} is not positive definite")
+        return float(ll[self.site]), g[self.site].copy()
 
     def loo_lg(self, all_sites=False):
         """pgbp_lg_loo on the current beliefs: the leave-one-out predictive distribution of every tip that has data, given

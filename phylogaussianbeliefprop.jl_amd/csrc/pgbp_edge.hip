@@ -28,6 +28,7 @@
 #include "pgbp_devmem.hpp"
 #include "pgbp_kernels.hpp"
 #include "pgbp_mom_dev.hpp"
+#include "pgbp_shift_dev.hpp"
 
 namespace pgbp {
 
@@ -106,7 +107,7 @@ __host__ __device__ inline size_t edge_extra_ints(int p, int K) { return (size_t
 template <int NT>
 __global__ __launch_bounds__(NT) void edge_family(const double* __restrict__ pool, int64_t pool_stride,
                                                   const int64_t* __restrict__ boff, const int32_t* __restrict__ bdim, int bs,
-                                                  int fp, LgStatic F, LgParams M, const int32_t* __restrict__ fam_cluster,
+                                                  int fp, LgStatic F, LgParams M, LgShifts Sh, const int32_t* __restrict__ fam_cluster,
                                                   int n_fam, int site0, int n_sites, double* __restrict__ dlen,
                                                   double* __restrict__ dgam, double* __restrict__ dshift,
                                                   int32_t* __restrict__ info, int info0) {
@@ -231,6 +232,7 @@ __global__ __launch_bounds__(NT) void edge_family(const double* __restrict__ poo
       } else if (theta) {
         for (int k = 0; k < np; ++k) w = w + cf[2 * K + k] * theta[tr];
       }
+      if (Sh.slot) w = w + lg_shift_d(Sh, F.gamma, f, K, np, tr, p, as);   // a shift of the mean on a parent edge
       ev[i] = e - w;
     }
     __syncthreads();
@@ -322,7 +324,15 @@ __global__ __launch_bounds__(NT) void edge_family(const double* __restrict__ poo
           if (theta) thg = thg + theta[oidx[i]] * ge[i];
         }
         if (dlen) dlen[fo * K + k] = cf[4 * K + k] * trGR + cf[5 * K + k] * thg + cf[3 * K + k] * gq;
-        if (dgam) dgam[fo * K + k] = cf[7 * K + k] * trGR + cf[8 * K + k] * thg + cf[6 * K + k] * gq;
+        if (dgam) {
+          double dg = cf[7 * K + k] * trGR + cf[8 * K + k] * thg + cf[6 * K + k] * gq;
+          if (Sh.slot && Sh.slot[(size_t)f * K + k] >= 0) {   // the shift's coefficient is gamma_k: + s_k,O' g_w
+            double sg = 0.0;
+            for (int i = 0; i < mo; ++i) sg = sg + lg_shift_value(Sh, (int64_t)f * K + k, oidx[i], p, as) * ge[i];
+            dg = dg + sg;
+          }
+          dgam[fo * K + k] = dg;
+        }
       }
     }
   }
@@ -352,6 +362,7 @@ extern "C" int pgbp_lg_edge_gradient(pgbp_engine* e, int32_t site_begin, int32_t
   // (as in pgbp_lg_gradient, what follows runs on the caller's current device)
   const Plan& pl = *v.plan;
   const LgStatic& F = *v.lg;
+  const LgShifts Sh = engine_lg_shifts(e);
   const int nc = pl.n_clusters, p = F.p, K = F.K;
   // which cluster each family sits in (the CSR of pgbp_lg_setup back from the device: a word per family)
   std::vector<int32_t> off(nc + 1);
@@ -407,11 +418,11 @@ extern "C" int pgbp_lg_edge_gradient(pgbp_engine* e, int32_t site_begin, int32_t
       const int n = std::min(chunk, ns - s0), gy = std::min(n, 65535);
       if (max_m <= 64)
         hipLaunchKernelGGL(edge_family<64>, dim3(nf, gy), dim3(64), lds_bytes, v.st, v.pool, pl.pool_stride(), v.boff, v.bdim,
-                           v.bs16, pl.fast_p, F, M, d_fcl.get(), nf, site_begin + s0, n, d_len.get(), d_gam.get(), d_shift.get(),
+                           v.bs16, pl.fast_p, F, M, Sh, d_fcl.get(), nf, site_begin + s0, n, d_len.get(), d_gam.get(), d_shift.get(),
                            d_info.get(), s0);
       else
         hipLaunchKernelGGL(edge_family<256>, dim3(nf, gy), dim3(256), lds_bytes, v.st, v.pool, pl.pool_stride(), v.boff, v.bdim,
-                           v.bs16, pl.fast_p, F, M, d_fcl.get(), nf, site_begin + s0, n, d_len.get(), d_gam.get(), d_shift.get(),
+                           v.bs16, pl.fast_p, F, M, Sh, d_fcl.get(), nf, site_begin + s0, n, d_len.get(), d_gam.get(), d_shift.get(),
                            d_info.get(), s0);
       herr = hipGetLastError();
       const size_t nk = (size_t)n * nf * K, np_ = (size_t)n * nf * p, ok = (size_t)s0 * nf * K, op = (size_t)s0 * nf * p;

@@ -85,6 +85,11 @@ struct LgBufs {
   DevBuf<LgSimpleFam> simple;
   DevBuf<double> R, alpha, theta, mu;
 };
+// what LgShifts points at (pgbp_lg_set_shifts), and the clusters the correction kernel visits
+struct LgShiftBufs {
+  DevBuf<int32_t> slot, cl;
+  DevBuf<double> value, value_sm;
+};
 
 hipEvent_t hip_event(void* ev) { return static_cast<hipEvent_t>(ev); }
 
@@ -184,6 +189,12 @@ struct pgbp_engine {
   int32_t lg_nf = 0;
   std::vector<int32_t> lg_h_np, lg_h_simple_fam;
   std::vector<LgSimpleFam> lg_h_simple;
+  // pgbp_lg_set_shifts: mean shifts on edges (device pointers owned by lg_shift_bufs; slot == null: none), the number of
+  // clusters that hold a shifted family, and the cluster of every family (host side, for that list)
+  LgShifts lgs{};
+  LgShiftBufs lg_shift_bufs;
+  int32_t lg_n_shift_cl = 0;
+  std::vector<int32_t> lg_h_cluster;
   std::string err;
   // a step of an asynchronous enqueue that could not be issued (a workspace that could not be allocated: ensure_ws has
   // set `err`): the launches that needed it were skipped; every entry point that enqueued, and the next pgbp_sync /
@@ -1753,6 +1764,10 @@ int pgbp_lg_setup(pgbp_engine* e, const pgbp_lg_families* f) {
   e->lg_h_np.assign(f->n_parents, f->n_parents + nf);
   e->lg_h_simple = std::move(h_simple);
   e->lg_h_simple_fam = std::move(h_simple_fam);
+  e->lg_h_cluster.assign(f->cluster, f->cluster + nf);
+  e->lg_shift_bufs = LgShiftBufs{};   // a new table: no shifts
+  e->lgs = LgShifts{};
+  e->lg_n_shift_cl = 0;
   const LgBufs& L = e->lg_bufs;
   e->lg = LgStatic{pp, K, f->n_rates, f->n_rows, L.off.get(), L.fam.get(), L.np.get(), L.cp.get(), L.row.get(), L.pp.get(), L.len.get(),
                    L.gam.get(), L.col.get(), L.data.get(), L.cm.get(), L.pm.get(), L.data_sm.get(), L.simple.get()};
@@ -1769,6 +1784,8 @@ static int lg_fill_async(pgbp_engine* e, bool also_factors, bool skip_sepsets = 
   if (e->layout_sm && e->lg_uni_ok) {
     launch_lg_fill_uni_sm(e->lg, e->lgp, e->sm.pool.get(), also_factors ? e->sm.fpool.get() : nullptr, e->d_packed_off.get(), e->d_bdim.get(),
                           p.n_clusters, p.n_sites, e->st);
+    launch_lg_shift_uni_sm(e->lg, e->lgp, e->lgs, e->lg_shift_bufs.cl.get(), e->lg_n_shift_cl, e->sm.pool.get(),
+                           also_factors ? e->sm.fpool.get() : nullptr, e->d_packed_off.get(), e->d_bdim.get(), p.n_sites, e->st);
     const int64_t nc = p.packed_off[p.n_clusters] * sm_row(p.n_sites), nall = p.packed_off.back() * sm_row(p.n_sites);
     if (!skip_sepsets) HIPCHK(e, hipMemsetAsync(e->sm.pool.get() + nc, 0, sizeof(double) * (size_t)(nall - nc), e->st));  // sepsets = 1
   } else {
@@ -1778,6 +1795,9 @@ static int lg_fill_async(pgbp_engine* e, bool also_factors, bool skip_sepsets = 
     }
     launch_lg_fill(e->lg, e->lgp, e->d_pool.get(), p.pool_stride(), also_factors ? e->d_fpool.get() : nullptr, p.cluster_stride(),
                    e->d_boff.get(), e->d_bdim.get(), e->layout_bs16 ? 1 : 0, p.fast_p, p.max_dim, p.n_clusters, p.n_sites, e->st);
+    launch_lg_shift(e->lg, e->lgp, e->lgs, e->lg_shift_bufs.cl.get(), e->lg_n_shift_cl, e->d_pool.get(), p.pool_stride(),
+                    also_factors ? e->d_fpool.get() : nullptr, p.cluster_stride(), e->d_boff.get(), e->d_bdim.get(),
+                    e->layout_bs16 ? 1 : 0, p.fast_p, p.max_dim, p.n_sites, e->st);
     if (!skip_sepsets)
       launch_zero_strided(e->d_pool.get() + p.cluster_stride(), p.pool_stride(), p.pool_stride() - p.cluster_stride(),
                           p.n_sites, e->st);  // sepsets = 1 (init_beliefs_reset!)
@@ -1845,6 +1865,80 @@ int pgbp_lg_set_edges(pgbp_engine* e, const double* length, const double* gamma)
   }
   HIPCHK(e, hipStreamSynchronize(e->st));  // the host buffers may go away
   return PGBP_OK;
+}
+
+int pgbp_lg_set_shifts(pgbp_engine* e, int32_t n_shifts, const int32_t* edge, const double* value, int32_t per_site) {
+  DeviceScope device_scope(e);
+  if (!e) return PGBP_ERR_INVALID;
+  if (!e->lg_ready) return e->fail(PGBP_ERR_STATE, "pgbp_lg_set_shifts: no family table (call pgbp_lg_setup first)");
+  if (n_shifts < 0 || (n_shifts > 0 && (!edge || !value)))
+    return e->fail(PGBP_ERR_INVALID, "pgbp_lg_set_shifts: a negative count or a missing array");
+  const int K = e->lg.K, nf = e->lg_nf, pp = e->lg.p;
+  const size_t ns = per_site ? (size_t)e->plan.n_sites : 1, n = (size_t)n_shifts;
+  // every check before anything changes
+  std::vector<int32_t> slot(std::max<size_t>(1, (size_t)nf * K), -1);
+  for (int i = 0; i < n_shifts; ++i) {
+    const std::string where = "pgbp_lg_set_shifts: entry " + std::to_string(i) + " (edge " + std::to_string(edge[i]) + "): ";
+    if (edge[i] < 0 || (int64_t)edge[i] >= (int64_t)nf * K) return e->fail(PGBP_ERR_INVALID, where + "edge index out of range");
+    const int fam = edge[i] / K, k = edge[i] - fam * K;
+    if (e->lg_h_np[fam] == 0)
+      return e->fail(PGBP_ERR_INVALID, where + "family " + std::to_string(fam) + " is a root prior, it has no edge");
+    if (k >= e->lg_h_np[fam])
+      return e->fail(PGBP_ERR_INVALID, where + "family " + std::to_string(fam) + " has " + std::to_string(e->lg_h_np[fam]) +
+                                           " parent edges, no edge " + std::to_string(k));
+    if (slot[edge[i]] >= 0)
+      return e->fail(PGBP_ERR_INVALID, where + "the edge is listed twice (entry " + std::to_string(slot[edge[i]]) + " has it too)");
+    slot[edge[i]] = i;
+    for (size_t s = 0; s < ns; ++s)
+      for (int t = 0; t < pp; ++t)
+        if (!std::isfinite(value[(s * n + i) * pp + t]))
+          return e->fail(PGBP_ERR_INVALID, where + "the value of trait " + std::to_string(t) + " is not finite");
+  }
+  if (n_shifts == 0) {   // clear (kernels already enqueued may still read the old shifts)
+    HIPCHK(e, hipStreamSynchronize(e->st));
+    e->lg_shift_bufs = LgShiftBufs{};
+    e->lgs = LgShifts{};
+    e->lg_n_shift_cl = 0;
+    return PGBP_OK;
+  }
+  // the clusters that hold a shifted family, in index order
+  std::vector<int32_t> cl;
+  for (int i = 0; i < n_shifts; ++i) cl.push_back(e->lg_h_cluster[edge[i] / K]);
+  std::sort(cl.begin(), cl.end());
+  cl.erase(std::unique(cl.begin(), cl.end()), cl.end());
+  // univariate per-site batches: the values once more as [shift][site], what the thread-per-site correction reads
+  std::vector<double> vsm;
+  if (per_site && e->lg_uni_ok) {
+    const size_t row = (size_t)sm_row(e->plan.n_sites);
+    vsm.assign(n * row, 0.0);
+    for (size_t s = 0; s < ns; ++s)
+      for (size_t i = 0; i < n; ++i) vsm[i * row + s] = value[s * n + i];
+  }
+  LgShiftBufs B;   // into a local: the engine takes it once every copy has been made
+  int rc;
+  if ((rc = dev_alloc(e, B.slot, slot.size()))) return rc;
+  if ((rc = dev_alloc(e, B.cl, cl.size()))) return rc;
+  if ((rc = dev_alloc(e, B.value, ns * n * pp))) return rc;
+  if (!vsm.empty() && (rc = dev_alloc(e, B.value_sm, vsm.size()))) return rc;
+  // every buffer exists: the copies, then ONE synchronisation whatever they returned (none may outlive the host vectors)
+  hipError_t herr = hipMemcpyAsync(B.slot.get(), slot.data(), slot.size() * sizeof(int32_t), hipMemcpyHostToDevice, e->st);
+  if (herr == hipSuccess) herr = hipMemcpyAsync(B.cl.get(), cl.data(), cl.size() * sizeof(int32_t), hipMemcpyHostToDevice, e->st);
+  if (herr == hipSuccess) herr = hipMemcpyAsync(B.value.get(), value, ns * n * pp * sizeof(double), hipMemcpyHostToDevice, e->st);
+  if (herr == hipSuccess && !vsm.empty())
+    herr = hipMemcpyAsync(B.value_sm.get(), vsm.data(), vsm.size() * sizeof(double), hipMemcpyHostToDevice, e->st);
+  const hipError_t serr = hipStreamSynchronize(e->st);  // the host buffers may go away; kernels that read the old shifts have finished
+  if (herr == hipSuccess) herr = serr;
+  if (herr != hipSuccess) return e->fail(PGBP_ERR_HIP, std::string("pgbp_lg_set_shifts (upload): ") + hipGetErrorString(herr));
+  e->lg_shift_bufs = std::move(B);
+  const LgShiftBufs& S = e->lg_shift_bufs;
+  e->lgs = LgShifts{S.slot.get(), S.value.get(), per_site ? 1 : 0, n_shifts, S.value_sm.get()};
+  e->lg_n_shift_cl = (int32_t)cl.size();
+  return PGBP_OK;
+}
+
+int32_t pgbp_lg_shift_count(pgbp_engine* e) {
+  if (!e || !e->lg_ready) return -1;
+  return e->lgs.slot ? e->lgs.n : 0;
 }
 
 int pgbp_enqueue_loglik_lg(pgbp_engine* e, int32_t reps, const pgbp_opts* opts) {
@@ -2156,4 +2250,5 @@ bool engine_lg_params(const pgbp_engine* e, LgParams* out) {
   *out = e->lgp;
   return true;
 }
+LgShifts engine_lg_shifts(const pgbp_engine* e) { return e->lg_ready ? e->lgs : LgShifts{}; }
 }  // namespace pgbp

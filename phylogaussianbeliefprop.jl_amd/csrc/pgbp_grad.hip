@@ -28,6 +28,7 @@
 #include "pgbp_devmem.hpp"
 #include "pgbp_kernels.hpp"
 #include "pgbp_mom_dev.hpp"
+#include "pgbp_shift_dev.hpp"
 
 namespace pgbp {
 
@@ -93,7 +94,7 @@ __host__ __device__ inline size_t grad_extra_ints(int p, int K) { return (size_t
 template <int NT>
 __global__ __launch_bounds__(NT) void grad_family(const double* __restrict__ pool, int64_t pool_stride,
                                                   const int64_t* __restrict__ boff, const int32_t* __restrict__ bdim, int bs,
-                                                  int fp, LgStatic F, LgParams M, const int32_t* __restrict__ fam_cluster,
+                                                  int fp, LgStatic F, LgParams M, LgShifts Sh, const int32_t* __restrict__ fam_cluster,
                                                   int n_fam, int site0, int n_sites, double* __restrict__ slots,
                                                   int32_t* __restrict__ info, int info0) {
 #pragma clang fp contract(off)
@@ -212,6 +213,7 @@ __global__ __launch_bounds__(NT) void grad_family(const double* __restrict__ poo
       } else if (theta) {
         for (int k = 0; k < np; ++k) w = w + wcs[k] * theta[tr];
       }
+      if (Sh.slot) w = w + lg_shift_d(Sh, F.gamma, f, K, np, tr, p, as);   // a shift of the mean on a parent edge
       ev[i] = e - w;
     }
     __syncthreads();
@@ -399,6 +401,7 @@ extern "C" int pgbp_lg_gradient(pgbp_engine* e, int32_t site_begin, int32_t site
   // swept from the thread that has its device current)
   const Plan& pl = *v.plan;
   const LgStatic& F = *v.lg;
+  const LgShifts Sh = engine_lg_shifts(e);
   const int nc = pl.n_clusters, p = F.p, K = F.K, nr = F.n_rates;
   // which cluster each family sits in (the CSR of pgbp_lg_setup back from the device: a word per family)
   std::vector<int32_t> off(nc + 1);
@@ -468,10 +471,10 @@ extern "C" int pgbp_lg_gradient(pgbp_engine* e, int32_t site_begin, int32_t site
       const int n = std::min(chunk, ns - s0), gy = std::min(n, 65535);
       if (max_m <= 64)
         hipLaunchKernelGGL(grad_family<64>, dim3(nf, gy), dim3(64), lds_bytes, v.st, v.pool, pl.pool_stride(), v.boff, v.bdim,
-                           v.bs16, pl.fast_p, F, M, d_fcl.get(), nf, site_begin + s0, n, d_slots.get(), d_info.get(), s0);
+                           v.bs16, pl.fast_p, F, M, Sh, d_fcl.get(), nf, site_begin + s0, n, d_slots.get(), d_info.get(), s0);
       else
         hipLaunchKernelGGL(grad_family<256>, dim3(nf, gy), dim3(256), lds_bytes, v.st, v.pool, pl.pool_stride(), v.boff, v.bdim,
-                           v.bs16, pl.fast_p, F, M, d_fcl.get(), nf, site_begin + s0, n, d_slots.get(), d_info.get(), s0);
+                           v.bs16, pl.fast_p, F, M, Sh, d_fcl.get(), nf, site_begin + s0, n, d_slots.get(), d_info.get(), s0);
       hipLaunchKernelGGL(grad_reduce_blocks, dim3((n_ent + 63) / 64, nfb, gy), dim3(256), 0, v.st, d_slots.get(), nf, p, nr, n_ent, n,
                          d_part.get());
       hipLaunchKernelGGL(grad_reduce_final, dim3(n_ent, gy), dim3(256), 0, v.st, d_part.get(), nfb, n_ent, n, d_out.get(), s0);

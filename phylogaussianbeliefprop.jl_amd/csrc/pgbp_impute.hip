@@ -32,6 +32,7 @@
 #include "pgbp_devmem.hpp"
 #include "pgbp_kernels.hpp"
 #include "pgbp_mom_dev.hpp"
+#include "pgbp_shift_dev.hpp"
 
 namespace pgbp {
 
@@ -78,7 +79,7 @@ __host__ __device__ inline size_t impute_lds_doubles(int max_m, int p, int K, si
 template <int NT>
 __global__ __launch_bounds__(NT) void impute_family(const double* __restrict__ pool, int64_t pool_stride,
                                                     const int64_t* __restrict__ boff, const int32_t* __restrict__ bdim, int bs,
-                                                    int fp, LgStatic F, LgParams M, const int32_t* __restrict__ fam,
+                                                    int fp, LgStatic F, LgParams M, LgShifts Sh, const int32_t* __restrict__ fam,
                                                     const int32_t* __restrict__ fcl, const unsigned long long* __restrict__ pred,
                                                     int n_fam, int site0, int n_sites, double* __restrict__ mean,
                                                     double* __restrict__ cov, int32_t* __restrict__ info) {
@@ -214,6 +215,7 @@ __global__ __launch_bounds__(NT) void impute_family(const double* __restrict__ p
       double w = 0.0;
       if (theta)
         for (int k = 0; k < np; ++k) w = w + wcs[k] * theta[zidx[i]];
+      if (Sh.slot) w = w + lg_shift_d(Sh, F.gamma, f, K, np, zidx[i], p, as);   // a shift of the mean: the full p-vector of d
       eu[i] = e;
       wv[i] = w;
       if (i < no) rv[i] = (yv[i] - w) - e;
@@ -422,6 +424,7 @@ extern "C" int pgbp_lg_impute(pgbp_engine* e, int32_t site_begin, int32_t site_e
   // (as in pgbp_lg_loo, what follows runs on the caller's current device)
   const Plan& pl = *v.plan;
   const LgStatic& F = *v.lg;
+  const LgShifts Sh = engine_lg_shifts(e);
   const int p = F.p, K = F.K, n = (int)fams.size();
   // the limits are pgbp_lg_loo's, over the clusters of ALL families of the table: an engine serves every sweep or none
   int max_m = 0;
@@ -471,11 +474,11 @@ extern "C" int pgbp_lg_impute(pgbp_engine* e, int32_t site_begin, int32_t site_e
       const int nsc = std::min(chunk, ns - s0), gy = std::min(nsc, 65535);
       if (max_m <= 64)
         hipLaunchKernelGGL(impute_family<64>, dim3(n, gy), dim3(64), lds_bytes, v.st, v.pool, pl.pool_stride(), v.boff, v.bdim,
-                           v.bs16, pl.fast_p, F, M, d_fams.get(), d_cls.get(), d_pred.get(), n, site_begin + s0, nsc,
+                           v.bs16, pl.fast_p, F, M, Sh, d_fams.get(), d_cls.get(), d_pred.get(), n, site_begin + s0, nsc,
                            d_mean.get(), d_cov.get(), d_info.get());
       else
         hipLaunchKernelGGL(impute_family<256>, dim3(n, gy), dim3(256), lds_bytes, v.st, v.pool, pl.pool_stride(), v.boff, v.bdim,
-                           v.bs16, pl.fast_p, F, M, d_fams.get(), d_cls.get(), d_pred.get(), n, site_begin + s0, nsc,
+                           v.bs16, pl.fast_p, F, M, Sh, d_fams.get(), d_cls.get(), d_pred.get(), n, site_begin + s0, nsc,
                            d_mean.get(), d_cov.get(), d_info.get());
       herr = hipGetLastError();
       const size_t o = (size_t)s0 * n, len = (size_t)nsc * n;

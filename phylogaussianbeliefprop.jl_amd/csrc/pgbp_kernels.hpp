@@ -206,6 +206,22 @@ struct LgParams {
   int32_t model, per_site;
   const double *R, *alpha, *theta, *mu;  // device pointers
 };
+// Mean shifts on edges (pgbp_lg_set_shifts): a struct of its own, so that the kernel arguments of the fill kernels -- LgStatic
+// and LgParams -- stay as they are.  slot == null: no shift is set.
+struct LgShifts {
+  const int32_t* slot;     // [n_families * K]: index into value of the shift on that parent edge, -1: none
+  const double* value;     // [n][p], per_site: [n_sites][n][p]
+  int32_t per_site, n;
+  const double* value_sm;  // univariate per-site batches: the values once more as [n][site] (rows padded: sm_row), else null
+};
+// the correction of a fill for the shifts (pgbp_shift.hip), launched right after it: one workgroup per (cluster of d_shcl, site)
+// adds Delta h and Delta g to the records in pool and, when not null, fpool (current layout)
+void launch_lg_shift(const LgStatic& F, const LgParams& M, const LgShifts& S, const int32_t* d_shcl, int n_shcl, double* pool,
+                     int64_t pool_stride, double* fpool, int64_t fpool_stride, const int64_t* d_boff, const int32_t* d_dim,
+                     int bs16, int fast_p, int max_dim, int n_sites, hipStream_t st);
+void launch_lg_shift_uni_sm(const LgStatic& F, const LgParams& M, const LgShifts& S, const int32_t* d_shcl, int n_shcl,
+                            double* pool_sm, double* fpool_sm, const int64_t* d_poff, const int32_t* d_dim, int n_sites,
+                            hipStream_t st);
 // one workgroup per (cluster, site); pool / fpool in the current layout (fpool may be null: beliefs only)
 void launch_lg_fill(const LgStatic& F, const LgParams& M, double* pool, int64_t pool_stride, double* fpool,
                     int64_t fpool_stride, const int64_t* d_boff, const int32_t* d_dim, int bs16, int fast_p, int max_dim,
@@ -291,5 +307,7 @@ EngineView engine_peek(pgbp_engine* e);          // the same words without touch
 const Plan* engine_plan(const pgbp_engine* e);
 // the parameters the engine kept from the last pgbp_lg_assignfactors (device pointers); false: none yet
 bool engine_lg_params(const pgbp_engine* e, LgParams* out);
+// the shifts of pgbp_lg_set_shifts (device pointers); slot == null: none set
+LgShifts engine_lg_shifts(const pgbp_engine* e);
 
 }  // namespace pgbp

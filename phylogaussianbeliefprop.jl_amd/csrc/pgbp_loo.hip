@@ -28,6 +28,7 @@
 #include "pgbp_devmem.hpp"
 #include "pgbp_kernels.hpp"
 #include "pgbp_mom_dev.hpp"
+#include "pgbp_shift_dev.hpp"
 
 namespace pgbp {
 
@@ -77,7 +78,7 @@ __host__ __device__ inline size_t loo_extra_ints(int p, int K) { return (size_t)
 template <int NT>
 __global__ __launch_bounds__(NT) void loo_family(const double* __restrict__ pool, int64_t pool_stride,
                                                  const int64_t* __restrict__ boff, const int32_t* __restrict__ bdim, int bs,
-                                                 int fp, LgStatic F, LgParams M, const int32_t* __restrict__ tip_fam,
+                                                 int fp, LgStatic F, LgParams M, LgShifts Sh, const int32_t* __restrict__ tip_fam,
                                                  const int32_t* __restrict__ tip_cluster, int n_tip, int site0, int n_sites,
                                                  double* __restrict__ mean, double* __restrict__ cov,
                                                  double* __restrict__ lpd, int32_t* __restrict__ info) {
@@ -202,6 +203,7 @@ __global__ __launch_bounds__(NT) void loo_family(const double* __restrict__ pool
       double w = 0.0;
       if (theta)
         for (int k = 0; k < np; ++k) w = w + wcs[k] * theta[oidx[i]];
+      if (Sh.slot) w = w + lg_shift_d(Sh, F.gamma, f, K, np, oidx[i], p, as);   // a shift of the mean on a parent edge
       Ym[i * ldy + mo] = (yv[i] - w) - mu_u;
     }
     // D = V - S, S = Cov(u): the lower triangle
@@ -390,6 +392,7 @@ extern "C" int pgbp_lg_loo(pgbp_engine* e, int32_t site_begin, int32_t site_end,
   // (as in pgbp_lg_gradient, what follows runs on the caller's current device)
   const Plan& pl = *v.plan;
   const LgStatic& F = *v.lg;
+  const LgShifts Sh = engine_lg_shifts(e);
   const int p = F.p, K = F.K, nt = (int)tips.size();
   // the limits are pgbp_lg_gradient's, over the clusters of ALL families of the table: an engine either serves both sweeps
   // or neither, and the dimension class of the launch is the gradient's
@@ -443,10 +446,10 @@ extern "C" int pgbp_lg_loo(pgbp_engine* e, int32_t site_begin, int32_t site_end,
       const int n = std::min(chunk, ns - s0), gy = std::min(n, 65535);
       if (max_m <= 64)
         hipLaunchKernelGGL(loo_family<64>, dim3(nt, gy), dim3(64), lds_bytes, v.st, v.pool, pl.pool_stride(), v.boff, v.bdim,
-                           v.bs16, pl.fast_p, F, M, d_tips.get(), d_tcl.get(), nt, site_begin + s0, n, d_mean.get(), d_cov.get(), d_lpd.get(), d_info.get());
+                           v.bs16, pl.fast_p, F, M, Sh, d_tips.get(), d_tcl.get(), nt, site_begin + s0, n, d_mean.get(), d_cov.get(), d_lpd.get(), d_info.get());
       else
         hipLaunchKernelGGL(loo_family<256>, dim3(nt, gy), dim3(256), lds_bytes, v.st, v.pool, pl.pool_stride(), v.boff, v.bdim,
-                           v.bs16, pl.fast_p, F, M, d_tips.get(), d_tcl.get(), nt, site_begin + s0, n, d_mean.get(), d_cov.get(), d_lpd.get(), d_info.get());
+                           v.bs16, pl.fast_p, F, M, Sh, d_tips.get(), d_tcl.get(), nt, site_begin + s0, n, d_mean.get(), d_cov.get(), d_lpd.get(), d_info.get());
       hipLaunchKernelGGL(loo_reduce, dim3(gy), dim3(256), 0, v.st, d_lpd.get(), nt, n, d_total.get(), s0);
       herr = hipGetLastError();
       const size_t o = (size_t)s0 * nt, len = (size_t)n * nt;

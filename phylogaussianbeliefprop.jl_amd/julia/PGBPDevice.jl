@@ -357,6 +357,31 @@ function lg_set_edges!(o::DeviceClusterGraphBelief; length::Union{Nothing,Abstra
 end
 
 """
+    lg_set_shifts!(obj, edges, values)
+
+Mean shifts on edges (pgbp_lg_set_shifts): `edges` holds the 0-based indices `f * K + k` of the family table given to
+pgbp_lg_setup (family `f`, parent edge `k`, `K` = max_parents), `values` is `p x length(edges)` (one shift per column) or
+`p x length(edges) x n_sites` for one set per site.  The child's conditional mean gains `sum_k gamma_k s_k`.  An empty
+`edges` clears the shifts; the call replaces the previous list.  The next pgbp_lg_assignfactors or pgbp_enqueue_loglik_lg
+uses them; an invalid entry is an error and nothing changes.
+"""
+function lg_set_shifts!(o::DeviceClusterGraphBelief, edges::AbstractVector{<:Integer}, values::AbstractArray{Float64})
+    ed = Vector{Int32}(edges)
+    val = Array{Float64}(values)
+    per_site = ndims(val) == 3 ? Int32(1) : Int32(0)
+    check(o.handle, @ccall LIB.pgbp_lg_set_shifts(o.handle::Ptr{Cvoid}, Int32(Base.length(ed))::Int32, ed::Ptr{Int32},
+                                                  val::Ptr{Float64}, per_site::Int32)::Cint)
+    return nothing
+end
+
+"""
+    lg_shift_count(obj) -> Int
+
+Number of mean shifts in force (pgbp_lg_shift_count): 0 when none is set, -1 without a family table.
+"""
+lg_shift_count(o::DeviceClusterGraphBelief) = Int(@ccall LIB.pgbp_lg_shift_count(o.handle::Ptr{Cvoid})::Int32)
+
+"""
     sample_size(obj) -> Int
 
 Doubles per draw of `sample_posterior!`: the sum of the cluster dimensions (pgbp_sample_size).

@@ -213,3 +213,71 @@ def calibrate_optimize_clustergraph_(beliefs, schedule, R0, mu0, extra_rates=(),
     opt.n_device_evals = count[0]
     R, mu = tf.back(opt.x)
     return R, mu, -float(opt.fun), opt
+
+
+def fit_shifts_lg(beliefs, schedule_tree, edges, all_sites=False):
+    """The exact maximum-likelihood mean shifts on a GIVEN set of edges, at the parameters of the last assignfactors_lg_.
+    The log-likelihood is quadratic in the shifts, its score linear: g(s) = g(0) - H s.  One evaluation of
+    loglik_and_shift_gradient_lg at s = 0 and one per unit vector (step 1: exact up to rounding, no step size to choose)
+    give g(0) and the columns of H -- n p + 1 evaluations for n edges of p traits; H is symmetrised and H s = g(0) solved
+    by Cholesky on the host; one more evaluation at the solution leaves the engine (shifts, factors and calibrated beliefs)
+    at it and gives its log-likelihood: n p + 2 evaluations (fill + calibrate + edge sweep each) in all.  EXACT ON A CLIQUE TREE ONLY, as the sweeps it calls; not verified.
+    edges: (family, k) pairs or flat indices, as set_shifts_lg.  all_sites: one fit per site (the engine is left with one
+    set of shifts per site), else the current site's fit, set for all sites.
+    Returns a dict: shifts [n, p], loglik, H [n p, n p] (the observed information of the shifts, entries ordered edge-major,
+    trait-minor: H^-1 is their covariance) and se [n, p]; with a leading site axis when all_sites.
+    If H is not positive definite the shifts are not identified from these data (two shifts with the same tips below them,
+    a trait that no tip below observes): ValueError names the (edge, trait) of the failing pivot."""
+    e = beliefs._shift_edges(edges)
+    n, p = int(e.size), beliefs._lg_p
+    if n == 0:
+        raise ValueError("fit_shifts_lg: no edge given")
+    nf = len(beliefs._lg["cluster"])
+    K = beliefs._lg["length"].size // nf
+    sites = list(range(beliefs.n_sites)) if all_sites else [beliefs.site]
+
+    def evaluate(values):
+        beliefs.set_shifts_lg(e, values)
+        ll, g = beliefs.loglik_and_shift_gradient_lg(schedule_tree, all_sites=True)
+        if not np.all(np.isfinite(ll[sites])):
+            raise np.linalg.LinAlgError("fit_shifts_lg: the calibration failed (a belief is not positive definite)")
+        return ll, g.reshape(beliefs.n_sites, n * p)
+
+    _, g0 = evaluate(np.zeros((n, p)))
+    H = np.zeros((beliefs.n_sites, n * p, n * p))
+    for j in range(n * p):
+        unit = np.zeros(n * p)
+        unit[j] = 1.0
+        _, gj = evaluate(unit.reshape(n, p))
+        H[:, :, j] = g0 - gj
+    H = (H + H.transpose(0, 2, 1)) / 2
+    shat = np.zeros((beliefs.n_sites, n * p))
+    se = np.zeros((beliefs.n_sites, n * p))
+    for s in sites:
+        Lc = _cholesky_or_name(H[s], e, K, p)
+        shat[s] = np.linalg.solve(Lc.T, np.linalg.solve(Lc, g0[s]))
+        Li = np.linalg.solve(Lc, np.eye(n * p))
+        se[s] = np.sqrt(np.sum(Li * Li, axis=0))   # diag(H^-1) = column norms of L^-1
+    if all_sites:
+        ll, _ = evaluate(shat.reshape(beliefs.n_sites, n, p))
+        return dict(shifts=shat.reshape(-1, n, p), loglik=ll, H=H, se=se.reshape(-1, n, p))
+    s = beliefs.site
+    ll, _ = evaluate(shat[s].reshape(n, p))
+    return dict(shifts=shat[s].reshape(n, p), loglik=float(ll[s]), H=H[s], se=se[s].reshape(n, p))
+
+
+def _cholesky_or_name(H, edges, K, p):
+    """Lower Cholesky factor of H, or ValueError naming the (edge, trait) of the first pivot that is not positive.  A pivot
+    at or below 1e-10 of its own diagonal entry counts as not positive: H is made of differences of scores that are exact
+    to about 1e-13 relative, below that a pivot is rounding noise."""
+    m = H.shape[0]
+    Lc = np.zeros_like(H)
+    for j in range(m):
+        d = H[j, j] - Lc[j, :j] @ Lc[j, :j]
+        if not (d > 1e-10 * abs(H[j, j])) or not np.isfinite(d):
+            f, k = int(edges[j // p]) // K, int(edges[j // p]) % K
+            raise ValueError(f"fit_shifts_lg: the shifts are not identified from these data: pivot {j} (edge (family {f}, "
+                             f"parent {k}), trait {j % p}) of the information matrix is not positive ({d:.3g})")
+        Lc[j, j] = np.sqrt(d)
+        Lc[j + 1:, j] = (H[j + 1:, j] - Lc[j + 1:, :j] @ Lc[j, :j]) / Lc[j, j]
+    return Lc
