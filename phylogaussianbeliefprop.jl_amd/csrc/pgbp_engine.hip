@@ -401,12 +401,25 @@ bool want_site_minor(const pgbp_engine* e) {
   return e->plan.tune.packed_layouts && e->plan.max_dim <= 2 && e->plan.n_sites >= 64;
 }
 
+// many tiny problems (every belief <= 2 variables, at least 8 sites): every task of a traversal runs on the thread-per-site
+// kernels (bp_level_uni / uni1, lanes = sites), whatever class the planner gave it
+bool uni_engine(const pgbp_engine* e) { return e->plan.max_dim <= 2 && e->plan.n_sites >= 8; }
+
+static int ensure_bs16(pgbp_engine* e, bool want_bs16);
+
+// The BS16 conversion works on the plain pools: the site-minor layout is left before it and entered after it, and excludes
+// BS16 (its buffers hold plain records, element by element).
 int ensure_layout(pgbp_engine* e, bool want_bs16, bool want_sm = false) {
+  int rc;
+  if (want_sm) want_bs16 = false;
+  if (e->layout_sm && !want_sm && (rc = ensure_site_minor(e, false))) return rc;
+  if ((rc = ensure_bs16(e, want_bs16))) return rc;
+  if (want_sm && !e->layout_sm && (rc = ensure_site_minor(e, true))) return rc;
+  return PGBP_OK;
+}
+
+static int ensure_bs16(pgbp_engine* e, bool want_bs16) {
   const Plan& p = e->plan;
-  if (want_sm != e->layout_sm) {
-    const int rc = ensure_site_minor(e, want_sm);
-    if (rc) return rc;
-  }
   if (want_bs16 == e->layout_bs16) return PGBP_OK;
   if (want_bs16) {
     if (!e->sym_known) {
@@ -440,7 +453,9 @@ bool fresh_sepsets_shortcut(const pgbp_engine* e) {
 }
 
 bool want_bs16(const pgbp_engine* e) {
-  return e->plan.tune.packed_layouts && e->plan.all_fast && e->plan.fast_p > 0 && e->plan.fast_p % 2 == 0;  // packed tiles: even P
+  // (packed tiles: even P; not for the thread-per-site engines, whose kernels read plain records -- a clique tree whose
+  // sepsets all hold 2 variables is all fast-class with P = 2)
+  return e->plan.tune.packed_layouts && e->plan.all_fast && e->plan.fast_p > 0 && e->plan.fast_p % 2 == 0 && !uni_engine(e);
 }
 
 void free_traversals(pgbp_engine* e) {
@@ -480,7 +495,7 @@ unsigned long long seq_stride(const pgbp_engine* e) {
 // how many levels at the root end of a traversal the tail launch takes over (0: none)
 int tail_levels(const pgbp_engine* e, const Traversal& tr, bool kl) {
   // residual_kldiv! runs between levels; the site-minor layout belongs to the thread-per-site kernel
-  if (kl || e->layout_sm || !e->plan.tune.tail) return 0;
+  if (kl || e->layout_sm || uni_engine(e) || !e->plan.tune.tail) return 0;
   return tr.tail_levels;
 }
 
@@ -497,7 +512,7 @@ void launch_loop_or_tail(pgbp_engine* e, const DevState& S, const FEntry* recs, 
 // levels [L0, L1) of one traversal: one launch per level (two where a level mixes fast-class and generic tasks)
 void enqueue_levels(pgbp_engine* e, const DevState& S, const Traversal& tr, const DevTraversal& d, int L0, int L1,
                     unsigned long long seq_base, unsigned long long stop_below, bool kl, int* launches) {
-  const bool uni = e->plan.max_dim <= 2 && e->plan.n_sites >= 8;  // many tiny problems: lanes = sites (bp_level_uni / uni1)
+  const bool uni = uni_engine(e);  // many tiny problems: lanes = sites (bp_level_uni / uni1)
   // (the loop mode of the thread-per-site kernels exists for sepsets of at most one variable: bp_chunk_uni1)
   const bool chunks_on = !kl && e->plan.tune.tail && (uni ? e->max_s <= 1 : !e->layout_sm);
   size_t next_chunk = 0;
@@ -522,12 +537,14 @@ void enqueue_levels(pgbp_engine* e, const DevState& S, const Traversal& tr, cons
       }
     }
     const int t0 = tr.level_off[L], nt = tr.level_off[L + 1] - t0;
-    const int nf = tr.level_nfast[L], ng = tr.level_ngroups[L];
+    // (a thread-per-site engine: the level's fast-class tasks too -- with 2-variable sepsets the planner finds some, and the
+    // register-resident kernel knows nothing of the site-minor layout)
+    const int nf = uni ? 0 : tr.level_nfast[L], ng = uni ? 0 : tr.level_ngroups[L];
     launch_fast16(S, d.d_fentries.get() + tr.level_fbase[L], d.d_fpros.get() ? d.d_fpros.get() + tr.level_fbase[L] : nullptr, kFastLevel, ng, ng,
                   e->plan.n_sites, seq_base, stop_below, stop_below, e->st);
     const int nbig = tr.level_nbig[L];
     if (uni)
-      launch_level_uni(S, d.d_task_off.get(), d.d_entries.get(), d.d_urecs.get(), t0 + nf, nt - nf, e->plan.n_sites, seq_base, stop_below, e->max_s, e->st);
+      launch_level_uni(S, d.d_task_off.get(), d.d_entries.get(), d.d_urecs.get(), t0, nt, e->plan.n_sites, seq_base, stop_below, e->max_s, e->st);
     else {
       const bool rows = d.d_rowmap.get() && !tr.level_nrows.empty() && tr.level_nrows[L] > 0;
       launch_level_generic(S, d.d_grecs.get(), tr.level_gbase[L], nt - nf - nbig, e->plan.n_sites, seq_base, stop_below,

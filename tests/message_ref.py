@@ -296,9 +296,10 @@ def _belief(rng, n, J=None):
 Built = namedtuple("Built", "case keep up senders sepsets receivers dims sepcl scope_off scope_idx packed i_from i_to")
 
 
-def build_case(case):
+def build_case(case, n_sites=2):
     """The float64 inputs of a case: per site (J, h, g) of sender, sepset and receiver, the index maps, and the engine
-    description with its packed beliefs [2, packed_size]."""
+    description with its packed beliefs [n_sites, packed_size].  Sites beyond the first two are drawn after them
+    (_site_inputs), so the first two are the same bytes whatever n_sites is."""
     rng = _rng_of(case.name)
     mf, s, mt = case.mf, case.s, case.mt
     keep = index_pattern(case.keep_kind, mf, s, rng)
@@ -330,6 +331,11 @@ def build_case(case):
         senders.append(snd)
         sepsets.append(sep)
         receivers.append(rcv)
+    for site in range(2, n_sites):
+        snd, sep, rcv = _site_inputs(case, rng, site, keep, integ, n_sites)
+        senders.append(snd)
+        sepsets.append(sep)
+        receivers.append(rcv)
     i_from, i_to = (1, 0) if case.flip else (0, 1)
     dims = np.zeros(3, np.int32)
     dims[i_from], dims[i_to], dims[2] = mf, mt, s
@@ -338,7 +344,7 @@ def build_case(case):
     scope_off = np.array([0, s, 2 * s], np.int64)
     scope_idx = np.concatenate(sides).astype(np.int32)
     packed = []
-    for site in range(2):
+    for site in range(n_sites):
         recs = [None, None, sepsets[site]]
         recs[i_from], recs[i_to] = senders[site], receivers[site]
         packed.append(np.concatenate([pack_record(*r) for r in recs]))
@@ -437,3 +443,226 @@ def c_engine_integrate(dims, sepcl, scope_off, scope_idx, packed_site):
     norm = C.c_double()
     info = cengine.lib().orc_integrate(ce.h, 0, mu.ctypes.data_as(C.POINTER(C.c_double)), C.byref(norm))
     return mu[:m], norm.value, int(info)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the tiny shapes of the thread-per-site kernels (bp_level_uni, bp_level_uni1, bp_chunk_uni1: every belief <= 2 variables,
+# lanes = sites), many sites.  Shared by tests/test_uni_cases_cpu.py and tests/test_gpu_uni_message_shapes.py.
+# ---------------------------------------------------------------------------------------------------------------------
+
+UNI_SITES = (8, 64, 65)      # thread-per-site in the plain layout / the smallest site-minor batch / a padded site-minor row
+UNI_MAX_SITES = max(UNI_SITES)
+SEP_KINDS = ("zero", "below", "near")
+
+
+def _maps(n, s):
+    """every strictly increasing map of s positions into n (n <= 2) by its pattern name"""
+    return ("lead", "trail") if (s == 1 and n == 2) else ("lead",)
+
+
+def uni_shape_cases():
+    """Every (mf, s, mt) with mf, mt in {0, 1, 2} and s <= min(mf, mt), every strictly increasing keep map and up map, all
+    three sepset kinds, both directions: 19 shapes-with-maps x 3 x 2 = 114 cases."""
+    out = []
+    for mf in range(3):
+        for mt in range(3):
+            for s in range(min(mf, mt) + 1):
+                for kk in _maps(mf, s):
+                    for uk in _maps(mt, s):
+                        for sep_kind in SEP_KINDS:
+                            for flip in (False, True):
+                                out.append(Case(f"u-{mf}-{s}-{mt}-{kk}-{uk}-{sep_kind}-{int(flip)}", mf, s, mt, kk, uk, sep_kind,
+                                                flip, None))
+    return out
+
+
+# the sites that carry a placed event: not lane 0 of their wavefront, and site 64 (the one site of the padded row of a
+# 65-site batch)
+UNI_EVENT_SITES = {8: (5,), 64: (37,), 65: (37, 64)}
+_UNI_EXIT_SHAPES = ((1, 1), (1, 0), (2, 0))        # (ni, s)
+
+
+def uni_exit2_cases():
+    """The all-zero exit at c = eps and no exit at c = 2 eps, for (ni, s) = (1, 1), (1, 0), (2, 0); placed in site 0 (as
+    exit2_cases) and in the event sites."""
+    return [Case(f"ub-{ni}-{s}-{c / EPS:.0f}eps", ni + s, s, 2, "trail" if s else "lead", "trail" if s else "lead", "below",
+                 bool(ni % 2), ("exit2", c))
+            for ni, s in _UNI_EXIT_SHAPES for c in (EPS, 2 * EPS)]
+
+
+def uni_failure_cases():
+    """A failure at pivot 1 (ni = 1, 2) and at pivot 2 (ni = 2) of the event sites, both generators, s = 0 and s = 1 where
+    the shape allows (mf <= 2)."""
+    out = []
+    for ni, s in ((1, 0), (1, 1), (2, 0)):
+        for k in range(1, ni + 1):
+            for kind in ("sign", "zero"):
+                out.append(Case(f"uc-{ni}-{s}-k{k}-{kind}", ni + s, s, 2, "lead", "trail" if s else "lead", "below", bool(k % 2),
+                                ("sites", k, kind)))
+    return out
+
+
+def _site_inputs(case, rng, site, keep, integ, n_sites):
+    """(sender, sepset, receiver) of one site beyond the first two of build_case: the same construction, with the
+    eigenvalue range of every matrix drawn per site (a 1 x 1 spd() is always 10)."""
+    mf, s, mt = case.mf, case.s, case.mt
+    lo = rng.uniform(0.5, 2.0)
+    hi = lo * rng.uniform(2.0, 10.0)
+    snd = (spd(rng, mf, lo, hi), rng.standard_normal(mf), float(rng.standard_normal()))
+    f = case.fail
+    events = UNI_EVENT_SITES.get(n_sites, ())
+    if f is not None and site in events:
+        J = snd[0]
+        if f[0] == "exit2":
+            J[np.ix_(integ, integ)] = f[1] * np.eye(integ.size)
+            J[np.ix_(keep, integ)] = 0.0
+            J[np.ix_(integ, keep)] = 0.0
+            snd[1][integ] = 0.0
+        elif f[0] == "sites":
+            J[np.ix_(integ, integ)] = ldl_failure(rng, integ.size, f[1], f[2])
+    rcv = (spd(rng, mt, lo, hi), rng.standard_normal(mt), float(rng.standard_normal()))
+    Jm, hm, gm, info, _ = marginalize_ld(*snd, keep)
+    if case.sep_kind == "zero" or info:
+        sep = (np.zeros((s, s)), np.zeros(s), 0.0)
+    else:
+        q = 0.5 if case.sep_kind == "below" else 1.0 - 1e-9
+        sep = ((q * Jm).astype(np.float64), (q * hm).astype(np.float64) + (0.0 if q > 0.9 else 0.1), float(rng.standard_normal()))
+    return snd, sep, rcv
+
+
+Msg = namedtuple("Msg", "i_from i_to k keep up")     # k: the sepset's number (belief index n_clusters + k)
+UniBuilt = namedtuple("UniBuilt", "case kind n_sites dims sepcl scope_off scope_idx packed msgs pa ch nc fail_sites")
+UNI_KINDS = ("pair", "chain2", "chain1")
+# pair:   sender -(s)- receiver                                   rooted at the receiver: one message
+# chain2: sender -(s)- receiver -(2)- extra(2)                    (mt = 2); for mt < 2 one more link carries the 2-variable
+#         sender -(s)- receiver -(mt)- extra(2) -(2)- extra(2)    sepset.  The engine's largest sepset is 2 whatever s is.
+# chain1: sender -(s)- receiver -(min(1, mt))- extra(2)           s <= 1: every sepset <= 1 and two levels (a chunk)
+# chains are rooted at their last cluster: the postorder sends sender -> receiver first, then the message OUT OF the receiver.
+
+
+def build_uni(case, kind="pair", n_sites=2):
+    """A case on an engine of n_sites sites (sites 0 and 1: build_case's bytes; further sites drawn after them)."""
+    b = build_case(case, n_sites)
+    fail_sites = tuple(x for x in UNI_EVENT_SITES.get(n_sites, ()) if case.fail is not None and case.fail[0] == "sites")
+    first = Msg(b.i_from, b.i_to, 0, b.keep, b.up)
+    if kind == "pair":
+        return UniBuilt(case, kind, n_sites, b.dims, b.sepcl, b.scope_off, b.scope_idx, b.packed, [first],
+                        np.array([b.i_to], np.int32), np.array([b.i_from], np.int32), 2, fail_sites)
+    rng = _rng_of(case.name + "-" + kind)
+    mt = case.mt
+    if kind == "chain2":
+        links = [(2, 2)] if mt == 2 else [(mt, 2), (2, 2)]      # (sepset dimension, next cluster's dimension)
+    else:
+        assert case.s <= 1
+        links = [(min(1, mt), 2)]
+    nc = 2 + len(links)
+    cdims = [int(b.dims[0]), int(b.dims[1])] + [d for _, d in links]
+    sdims = [case.s] + [s2 for s2, _ in links]
+    sepcl = [0, 1]
+    sides = [b.scope_idx[b.scope_off[0]:b.scope_off[1]], b.scope_idx[b.scope_off[1]:b.scope_off[2]]]
+    msgs = [first]
+    prev = b.i_to
+    for j, (s2, d) in enumerate(links):
+        nxt = 2 + j
+        dp = cdims[prev]
+        kp = np.arange(s2, dtype=np.int32)                                    # every variable of a receiver of mt < 2
+        un = np.arange(d - s2, d, dtype=np.int32)                             # the trailing variables of the next cluster
+        if (j + int(case.flip)) % 2:
+            sepcl += [nxt, prev]
+            sides += [un, kp]
+        else:
+            sepcl += [prev, nxt]
+            sides += [kp, un]
+        assert s2 <= dp
+        msgs.append(Msg(prev, nxt, 1 + j, kp, un))
+        prev = nxt
+    scope_off = np.concatenate([[0], np.cumsum([len(x) for x in sides])]).astype(np.int64)
+    scope_idx = np.concatenate(sides).astype(np.int32)
+    dims = np.array(cdims + sdims, np.int32)
+    off0 = record_offsets(b.dims)
+    packed = []
+    for site in range(n_sites):
+        recs = [b.packed[site][off0[0]:off0[1]], b.packed[site][off0[1]:off0[2]]]
+        lo = rng.uniform(0.5, 2.0)
+        for _, d in links:
+            recs.append(pack_record(spd(rng, d, lo, 8.0 * lo), rng.standard_normal(d), float(rng.standard_normal())))
+        recs.append(b.packed[site][off0[2]:off0[3]])
+        for s2, _ in links:
+            if case.sep_kind == "zero":
+                recs.append(np.zeros(s2 * s2 + s2 + 1))
+            else:
+                recs.append(pack_record(spd(rng, s2, 0.1 * lo, 0.4 * lo), 0.1 * rng.standard_normal(s2), float(rng.standard_normal())))
+        packed.append(np.concatenate(recs))
+    pa = np.array([m.i_to for m in reversed(msgs)], np.int32)      # preorder from the root = the last cluster
+    ch = np.array([m.i_from for m in reversed(msgs)], np.int32)
+    return UniBuilt(case, kind, n_sites, dims, np.array(sepcl, np.int32), scope_off, scope_idx, np.stack(packed), msgs, pa, ch,
+                    nc, fail_sites)
+
+
+def uni_records(ub, packed_site):
+    """every belief record (J, h, g) of one site's packed beliefs"""
+    off = record_offsets(ub.dims)
+    return [unpack_record(packed_site[off[i]:off[i + 1]], int(ub.dims[i])) for i in range(len(ub.dims))]
+
+
+def uni_reference(ub, packed_site):
+    """The postorder of ub in longdouble on one site's float64 beliefs: per message (new sepset, new receiver, residual,
+    info, exit) or None for a message that is not sent (its sender received no message because of a failure upstream).
+    The sender of a later message is the previous receiver ROUNDED to float64: what an engine holds."""
+    recs = uni_records(ub, packed_site)
+    out, dead = [], set()
+    for m in ub.msgs:
+        if m.i_from in dead:
+            dead.add(m.i_to)
+            out.append(None)
+            continue
+        r = propagate_ld(recs[m.i_from], recs[ub.nc + m.k], recs[m.i_to], m.keep, m.up)
+        out.append(r)
+        if r[3]:
+            dead.add(m.i_to)
+            continue
+        recs[ub.nc + m.k] = tuple(np.asarray(x, dtype=LD).astype(np.float64) for x in r[0])
+        recs[m.i_to] = tuple(np.asarray(x, dtype=LD).astype(np.float64) for x in r[1])
+    return out
+
+
+def uni_c_engine(ub, packed_site):
+    """The plain-C engine on the same postorder of one site: (packed beliefs, residual records, flags, infos)."""
+    from oracle import cengine
+    ce = cengine.Engine(ub.dims, ub.sepcl, ub.scope_off, ub.scope_idx, packed_site)
+    infos, dead = [], set()
+    for m in ub.msgs:
+        if m.i_from in dead:
+            dead.add(m.i_to)
+            infos.append(None)
+            continue
+        infos.append(ce.propagate(m.i_to, m.k, m.i_from))
+        if infos[-1]:
+            dead.add(m.i_to)
+    res, flags = ce.residuals()
+    return ce.packed(), res, flags, infos
+
+
+def residual_of(ub, m, res_site):
+    """(dJ, dh) of message m in one site's residual records, and the message's id (2 k + direction)"""
+    sd = np.repeat(ub.dims[ub.nc:].astype(np.int64), 2)
+    roff = np.concatenate([[0], np.cumsum(sd * sd + sd)])
+    d = 2 * m.k + (1 if ub.sepcl[2 * m.k + 1] == m.i_to else 0)
+    s = int(ub.dims[ub.nc + m.k])
+    r = res_site[roff[d]:roff[d + 1]]
+    return (r[:s * s].reshape(s, s, order="F"), r[s * s:]), d
+
+
+def uni_integrate_inputs(m, n_sites):
+    """n_sites beliefs of m <= 2 variables for pgbp_integrate beside a one-variable neighbour (integrate_inputs' engine);
+    the event sites hold a failure at pivot m ("sign")."""
+    rng = _rng_of(f"uint-{m}-{n_sites}")
+    beliefs = []
+    for site in range(n_sites):
+        lo = rng.uniform(0.5, 2.0)
+        J = ldl_failure(rng, m, m, "sign") if site in UNI_EVENT_SITES[n_sites] else spd(rng, m, lo, 9.0 * lo)
+        beliefs.append((J, rng.standard_normal(m), float(rng.standard_normal())))
+    dims = np.array([m, 1, 1], np.int32)
+    one = (np.ones((1, 1)), np.zeros(1), 0.0)
+    packed = np.stack([np.concatenate([pack_record(*b), pack_record(*one), pack_record(*one)]) for b in beliefs])
+    return beliefs, dims, np.array([0, 1], np.int32), np.array([0, 1, 2], np.int64), np.array([m - 1, 0], np.int32), packed
