@@ -720,7 +720,11 @@ int pgbp_create(const pgbp_desc* desc, pgbp_engine** out) {
   const size_t nm = (size_t)p.n_msgs();
   const size_t nsw = (size_t)sm_row(p.n_sites);   // the per-message / per-cluster word arrays serve both layouts (a switch swaps
                                                    // them with their twins): sized for the padded rows of the site-minor one
-  if ((rc = dev_alloc(e, e->d_pool, ns * p.pool_stride()))) return bail(rc);
+  // (kPoolTail: the loop-launch kernel issues every sender load whatever the record is; for a constant's one-double record
+  // the right-hand planes of a packed tile lie up to 130 doubles behind its start -- past the end of the last site's pool if
+  // little follows it there.  The values are ignored; the addresses must be valid.)
+  constexpr size_t kPoolTail = 256;
+  if ((rc = dev_alloc(e, e->d_pool, ns * p.pool_stride() + kPoolTail))) return bail(rc);
   if ((rc = dev_alloc(e, e->d_fpool, ns * p.cluster_stride()))) return bail(rc);
   if ((rc = dev_alloc(e, e->d_rpool, ns * p.rpool_stride()))) return bail(rc);
   if ((rc = upload(e, e->d_msgs, p.msgs))) return bail(rc);

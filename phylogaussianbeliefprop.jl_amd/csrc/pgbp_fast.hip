@@ -1,7 +1,7 @@
 // Register-resident message kernel for gfx950 (wave64), sepsets of dimension P (2 .. 16; described for P = 16).
 //
 // One wavefront = one message; the waves of a workgroup = the messages of a few tasks (ordered lists of messages
-// sharing a receiver or a sender); every HBM access a 16- or 32-byte-per-lane coalesced vector access issued up front.
+// sharing a receiver or a sender); every HBM access a 16-byte-per-lane coalesced vector access issued up front.
 //
 // Lane geometry: lane = 8*b + a, a = row group, b = column group (0..7 each).
 // A 32 x 32 sender precision, re-indexed so that the 16 integrated variables come first
@@ -114,6 +114,7 @@ __global__ __launch_bounds__(MODE == kTail ? kTailWaves * 64 : kFastMaxWaves * 6
   const int site = blockIdx.y;
   constexpr int PR = P - (ODD ? 1 : 0);  // the real sepset dimension
   constexpr int G = P / 2;               // lane grid G x G (all 64 lanes for P = 16)
+  constexpr int PL = BS ? bs16::sym_plane(P) : 0, PLT = bs16::full_plane(P);   // plane strides of the packed tiles (pgbp_bs16.hpp)
   // STREAMING accesses (round 4, last session): what a calibrate touches once -- the residual and the sepset it writes, the old
   // sepset and a leaf's belief it reads, a postorder's 2P-dim sender -- goes past the caches with the non-temporal hint, so
   // that what IS read again (the receiver blocks: the next level's senders) stays in them: cfg3 0.838 -> 0.796 ms per
@@ -149,7 +150,7 @@ __global__ __launch_bounds__(MODE == kTail ? kTailWaves * 64 : kFastMaxWaves * 6
     const bool act = lane < G * G;  // lanes beyond the grid shadow lane (0, 0) and never store
     const int a = act ? lane % G : 0, b = act ? lane / G : 0;
     const bool up = act && a <= b;               // this lane's block is stored in the packed layout
-    const int kidx = (b * (b + 1) / 2 + a) * 4;  // its offset inside a packed symmetric tile
+    const int kidx = (b * (b + 1) / 2 + a) * 2;  // its offset inside a plane of a packed symmetric tile
 
     const bool has_next = MODE != kLevel && g + gstride < ngroups;
     // kTail: the whole next record is requested here as a VECTOR load (lanes 0 .. 3 fetch 16 bytes each): the compiler
@@ -218,14 +219,14 @@ __global__ __launch_bounds__(MODE == kTail ? kTailWaves * 64 : kFastMaxWaves * 6
       auto load_sep_to = [&]() {
         if (!S.sep_zero) {
           if (has_block) {
-            sJ = load_blk<BS, ODD, kStream>(sep, PR, a, b, up, kidx, PR);
+            sJ = load_blk<BS, ODD, kStream, PL>(sep, PR, a, b, up, kidx, PR);
             if (b == 0) sh = load_pair<ODD>(sep + sepH, a, PR);
           }
           sg = sep[sepG];
         }
         if (own) {
           if (recv_blk) {
-            tJ = load_blk<BS, ODD>(to + tJ0, mt, a, b, up, kidx, PR);
+            tJ = load_blk<BS, ODD, false, PL>(to + tJ0, mt, a, b, up, kidx, PR);
             if (b == 0) {
               const double2 t2 = load_pair<ODD>(to + tH0, a, PR);
               th[0] = t2.x; th[1] = t2.y;
@@ -243,7 +244,7 @@ __global__ __launch_bounds__(MODE == kTail ? kTailWaves * 64 : kFastMaxWaves * 6
           load_sep_to();
         } else if (en.mf == PR && has_block) {
           // nothing to integrate: the message is the sender's belief (src/beliefupdates.jl:56)
-          mJ = load_blk<BS, ODD, kStream>(from, PR, a, b, up, kidx, PR);
+          mJ = load_blk<BS, ODD, kStream, PL>(from, PR, a, b, up, kidx, PR);
           const double2 ch = load_pair<ODD>(from + (BS ? bs16::h1(P) : PR * PR), a, PR);
           mh[0] = ch.x; mh[1] = ch.y;
           gmsg = from[BS ? bs16::g1(P) : PR * PR + PR];
@@ -256,7 +257,7 @@ __global__ __launch_bounds__(MODE == kTail ? kTailWaves * 64 : kFastMaxWaves * 6
             for (int j = 0; j < 4; ++j) f.w[i][j] = 0.0;
           if (en.mf == PR) {
             // everything is integrated (dimension-0 sepset): the 16 x 16 precision is the integrated block
-            const Blk v = load_blk<BS, ODD>(from, PR, a, b, up, kidx, PR);
+            const Blk v = load_blk<BS, ODD, false, PL>(from, PR, a, b, up, kidx, PR);
             const double2 vh = load_pair<ODD>(from + (BS ? bs16::h1(P) : PR * PR), a, PR);
             f.w[0][0] = v.x; f.w[1][0] = v.y; f.w[0][1] = v.z; f.w[1][1] = v.w;
             if (ODD && a == G - 1 && b == G - 1) f.w[1][1] = 1.0;  // the phantom variable: decoupled, unit precision
@@ -293,26 +294,26 @@ __global__ __launch_bounds__(MODE == kTail ? kTailWaves * 64 : kFastMaxWaves * 6
             // (postorder: the sender is read by this message alone and not again before the preorder comes back to it as a
             // receiver -- a streaming load; preorder: the siblings' messages read the same sender -- a plain one)
             Blk ii{0, 0, 0, 0}, ss{0, 0, 0, 0};
-            double4 t;
+            double2 t0, t1;   // left and right column of the T10 block
             if (itrail || !kStream) {
-              ii = load_blk<true>(from + (itrail ? bs16::t11(P) : 0), P, a, b, up, kidx);
-              ss = load_blk<true>(from + (itrail ? 0 : bs16::t11(P)), P, a, b, up, kidx);
+              ii = load_blk<true, false, false, PL>(from + (itrail ? bs16::t11(P) : 0), P, a, b, up, kidx);
+              ss = load_blk<true, false, false, PL>(from + (itrail ? 0 : bs16::t11(P)), P, a, b, up, kidx);
               // J_SI block (rows of S = my a, cols of I = my b): block (a, b) of T10, or block (b, a) transposed
-              t = *reinterpret_cast<const double4*>(from + bs16::t10(P) + (itrail ? (b + G * a) : (a + G * b)) * 4);
+              const double* __restrict__ tp = from + bs16::t10(P) + (itrail ? (b + G * a) : (a + G * b)) * 2;
+              t0 = *reinterpret_cast<const double2*>(tp);
+              t1 = *reinterpret_cast<const double2*>(tp + PLT);
             } else {
-              if (up) {
-                const pgbp_d4v vi = __builtin_nontemporal_load(reinterpret_cast<const pgbp_d4v*>(from + kidx));
-                const pgbp_d4v vs = __builtin_nontemporal_load(reinterpret_cast<const pgbp_d4v*>(from + bs16::t11(P) + kidx));
-                ii = Blk{vi.x, vi.y, vi.z, vi.w};
-                ss = Blk{vs.x, vs.y, vs.z, vs.w};
-              }
+              ii = load_blk<true, false, true, PL>(from, P, a, b, up, kidx);
+              ss = load_blk<true, false, true, PL>(from + bs16::t11(P), P, a, b, up, kidx);
               // ... block (a, b) of T10
-              const pgbp_d4v tv = __builtin_nontemporal_load(reinterpret_cast<const pgbp_d4v*>(from + bs16::t10(P) + (a + G * b) * 4));
-              t = make_double4(tv.x, tv.y, tv.z, tv.w);
+              const pgbp_d2v* __restrict__ tp = reinterpret_cast<const pgbp_d2v*>(from + bs16::t10(P) + (a + G * b) * 2);
+              const pgbp_d2v u0 = __builtin_nontemporal_load(tp), u1 = __builtin_nontemporal_load(tp + PLT / 2);
+              t0 = make_double2(u0.x, u0.y);
+              t1 = make_double2(u1.x, u1.y);
             }
             f.w[0][0] = ii.x; f.w[1][0] = ii.y; f.w[0][1] = ii.z; f.w[1][1] = ii.w;
             f.w[2][2] = ss.x; f.w[3][2] = ss.y; f.w[2][3] = ss.z; f.w[3][3] = ss.w;
-            f.w[2][0] = t.x; f.w[3][0] = itrail ? t.z : t.y; f.w[2][1] = itrail ? t.y : t.z; f.w[3][1] = t.w;
+            f.w[2][0] = t0.x; f.w[3][0] = itrail ? t1.x : t0.y; f.w[2][1] = itrail ? t0.y : t1.x; f.w[3][1] = t1.y;
             const double2 hi = *reinterpret_cast<const double2*>(from + bs16::h2(P) + (itrail ? P : 0) + 2 * a);
             const double2 hs = *reinterpret_cast<const double2*>(from + bs16::h2(P) + (itrail ? 0 : P) + 2 * a);
             f.h[0] = hi.x; f.h[1] = hi.y; f.h[2] = hs.x; f.h[3] = hs.y;
@@ -344,14 +345,14 @@ __global__ __launch_bounds__(MODE == kTail ? kTailWaves * 64 : kFastMaxWaves * 6
             double* __restrict__ sep2 = pool + pr.sep_off;
             double* __restrict__ res2 = rpool + pr.res_off;
             constexpr int xH = BS ? bs16::h1(P) : PR * PR, xG = BS ? bs16::g1(P) : PR * PR + PR;
-            const Blk xJ = load_blk<BS, ODD>(xfrom, PR, a, b, up, kidx, PR);
+            const Blk xJ = load_blk<BS, ODD, false, PL>(xfrom, PR, a, b, up, kidx, PR);
             const double2 xh = load_pair<ODD>(xfrom + xH, a, PR);
             const double xg = xfrom[xG];
             Blk s2{0, 0, 0, 0};
             double2 s2h = make_double2(0.0, 0.0);
             double s2g = 0.0;
             if (!S.sep_zero) {
-              s2 = load_blk<BS, ODD>(sep2, PR, a, b, up, kidx, PR);
+              s2 = load_blk<BS, ODD, false, PL>(sep2, PR, a, b, up, kidx, PR);
               s2h = load_pair<ODD>(sep2 + xH, a, PR);
               s2g = sep2[xG];
             }
@@ -360,8 +361,8 @@ __global__ __launch_bounds__(MODE == kTail ? kTailWaves * 64 : kFastMaxWaves * 6
               // divide! (src/beliefupdates.jl:579-587)
               const Blk d2{xJ.x - s2.x, xJ.y - s2.y, xJ.z - s2.z, xJ.w - s2.w};
               const double d2h0 = xh.x - s2h.x, d2h1 = xh.y - s2h.y, d2g = xg - s2g;
-              store_blk<BS, ODD>(sep2, PR, a, b, up, act, kidx, xJ, PR);
-              store_blk<BS, ODD, true>(res2, PR, a, b, up, act, kidx, d2, PR);
+              store_blk<BS, ODD, false, PL>(sep2, PR, a, b, up, act, kidx, xJ, PR);
+              store_blk<BS, ODD, true, PL>(res2, PR, a, b, up, act, kidx, d2, PR);
               double maxJ2 = 0.0, maxh2 = 0.0;
               if (BS ? up : act) {
                 maxJ2 = fmax(fmax(fabs(d2.x), fabs(d2.y)), fmax(fabs(d2.z), fabs(d2.w)));
@@ -391,7 +392,7 @@ __global__ __launch_bounds__(MODE == kTail ? kTailWaves * 64 : kFastMaxWaves * 6
               double* __restrict__ iH = BS ? fw + bs16::h2(P) + (en.keep0 == 0 ? P : 0) : fw + 4 * PR * PR + i0;
               double* __restrict__ iG = BS ? fw + bs16::g2(P) : fw + 4 * PR * PR + 2 * PR;
               // (ODD: the phantom corner holds the unit pivot in registers only: store_blk skips indices >= PR)
-              store_blk<BS, ODD>(iJ, 2 * PR, a, b, up, act, kidx, Blk{f.w[0][0], f.w[1][0], f.w[0][1], f.w[1][1]}, PR);
+              store_blk<BS, ODD, false, PL>(iJ, 2 * PR, a, b, up, act, kidx, Blk{f.w[0][0], f.w[1][0], f.w[0][1], f.w[1][1]}, PR);
               if (act && b == 0) store_pair<ODD>(iH, a, f.h[0], f.h[1], PR);
               if (lane == 0) iG[0] = gmsg;
             }
@@ -471,8 +472,8 @@ __global__ __launch_bounds__(MODE == kTail ? kTailWaves * 64 : kFastMaxWaves * 6
       double maxJ = 0.0, maxh = 0.0;
       if (has_block) {
         dJ = Blk{mJ.x - sJ.x, mJ.y - sJ.y, mJ.z - sJ.z, mJ.w - sJ.w};
-        store_blk<BS, ODD, kStream>(sep, PR, a, b, up, act, kidx, mJ, PR);
-        store_blk<BS, ODD, true>(res, PR, a, b, up, act, kidx, dJ, PR);
+        store_blk<BS, ODD, kStream, PL>(sep, PR, a, b, up, act, kidx, mJ, PR);
+        store_blk<BS, ODD, true, PL>(res, PR, a, b, up, act, kidx, dJ, PR);
         if (BS ? up : act) {
           maxJ = fmax(fmax(fabs(dJ.x), fabs(dJ.y)), fmax(fabs(dJ.z), fabs(dJ.w)));
           if (dJ.x != dJ.x || dJ.y != dJ.y || dJ.z != dJ.z || dJ.w != dJ.w) maxJ = INFINITY;
@@ -563,7 +564,7 @@ __global__ __launch_bounds__(MODE == kTail ? kTailWaves * 64 : kFastMaxWaves * 6
       }
       if (own) {
         if (recv_blk) {
-          store_blk<BS, ODD>(to + tJ0, mt, a, b, up, act, kidx, tJ, PR);
+          store_blk<BS, ODD, false, PL>(to + tJ0, mt, a, b, up, act, kidx, tJ, PR);
           if (act && b == 0) store_pair<ODD>(to + tH0, a, th[0], th[1], PR);
         }
         if (lane == 0) to[tG0] = tg;
@@ -631,7 +632,7 @@ void launch_fast_p(const DevState& S, const FEntry* d_recs, const FPro* d_pros, 
 // ---- assignfactors! for MvFullBrownianMotion on a tree (pgbp_bm_tree of include/pgbp.h), lane-blocked ---------------
 // One wavefront per cluster, same lane geometry as the message kernel: lane (a, b) holds the 2 x 2 block
 // R^-1[2a..2a+1][2b..2b+1] for the whole launch and writes it, scaled by 1/t and signed, into the tiles of the record
-// (32-byte stores, whole lines), h = R^-1 v / t by a butterfly over b, g from v'R^-1 v / t by a butterfly over a.
+// (two 16-byte stores per tile, one per plane: pgbp_bs16.hpp), h = R^-1 v / t by a butterfly over b, g from v'R^-1 v / t by a butterfly over a.
 // Formulas: pgbp_kernels.hip, bm_tree_fill_kernel (the general-dimension version of the same fill).
 // clusters per wavefront of bm_tree_fill_fast (1 / 2 / 3 / 4 / 8 / 16 / 32 / 64: 1 970 / 1 990 / 2 000 / 1 990 / 1 968 / 1 953 / 1 949 /
 // 1 893 log-likelihood evaluations per second on cfg3: the records want many wavefronts more than they want their descriptions
@@ -658,7 +659,8 @@ __global__ __launch_bounds__(256) void bm_tree_fill_fast(double* __restrict__ po
   const bool act = lane < G * G;
   const int a = act ? lane % G : 0, b = act ? lane / G : 0;
   const bool up = act && a <= b;
-  const int kidx = (b * (b + 1) / 2 + a) * 4;
+  const int kidx = (b * (b + 1) / 2 + a) * 2;
+  constexpr int PL = bs16::sym_plane(P), PLT = bs16::full_plane(P);
   const double* __restrict__ Rinv = Rinv_all + (per_site ? (int64_t)site * PR * PR : 0);
   const double* __restrict__ mu = mu_all + (per_site ? (int64_t)site * PR : 0);
   const double g_base = -0.5 * ((double)PR * PGBP_LOG2PI + logdetR_all[per_site ? site : 0]);
@@ -735,13 +737,19 @@ __global__ __launch_bounds__(256) void bm_tree_fill_fast(double* __restrict__ po
       // The packed record is put together in LDS and goes out as ONE contiguous stream of 16 bytes per lane: every store
       // instruction then covers whole 128-byte lines.  (A lane's 2 x 2 block is 32 bytes = two 16-byte stores at a stride of
       // 32 bytes between lanes: each instruction left half of every line it touched to the other, the L2 took twice the write
-      // requests, and the kernel ran at 3.3 TB/s where a plain fill of the same 292 MB reaches 6.1.)
+      // requests, and the kernel ran at 3.3 TB/s where a plain fill of the same 292 MB reaches 6.1.  The tiles have since been
+      // split into planes, pgbp_bs16.hpp, so a direct store would cover whole lines of the tiles too; the staging stays for the
+      // record as a whole -- tiles, h and g in one stream -- and the LDS image simply comes out in the new order.)
       double* r = obuf[wave];
       int rl = 1;
       if (k == 0) {  // 2P x 2P: [j -j; -j j], h = 0
-        store_blk<true>(r, P, a, b, up, act, kidx, Jp);
-        store_blk<true>(r + bs16::t11(P), P, a, b, up, act, kidx, Jp);
-        if (act) *reinterpret_cast<double4*>(r + bs16::t10(P) + (a + G * b) * 4) = make_double4(Jm.x, Jm.y, Jm.z, Jm.w);
+        store_blk<true, false, false, PL>(r, P, a, b, up, act, kidx, Jp);
+        store_blk<true, false, false, PL>(r + bs16::t11(P), P, a, b, up, act, kidx, Jp);
+        if (act) {
+          double* tp = r + bs16::t10(P) + (a + G * b) * 2;
+          *reinterpret_cast<double2*>(tp) = make_double2(Jm.x, Jm.y);
+          *reinterpret_cast<double2*>(tp + PLT) = make_double2(Jm.z, Jm.w);
+        }
         if (act && b == 0) {
           *reinterpret_cast<double2*>(r + bs16::h2(P) + 2 * a) = make_double2(0.0, 0.0);
           *reinterpret_cast<double2*>(r + bs16::h2(P) + P + 2 * a) = make_double2(0.0, 0.0);
@@ -749,7 +757,7 @@ __global__ __launch_bounds__(256) void bm_tree_fill_fast(double* __restrict__ po
         if (lane == 0) r[bs16::g2(P)] = g;
         rl = bs16::g2(P) + 1;
       } else if (k <= 2) {  // P x P block j on the kept variables, h = +j v
-        store_blk<true>(r, P, a, b, up, act, kidx, Jp);
+        store_blk<true, false, false, PL>(r, P, a, b, up, act, kidx, Jp);
         if (act && b == 0) *reinterpret_cast<double2*>(r + bs16::h1(P) + 2 * a) = make_double2(jv0, jv1);
         if (lane == 0) r[bs16::g1(P)] = g;
         rl = bs16::g1(P) + 1;
@@ -776,9 +784,13 @@ __global__ __launch_bounds__(256) void bm_tree_fill_fast(double* __restrict__ po
       double* __restrict__ r = which ? frec : rec;
       if (k == 0) {  // 2P x 2P: [j -j; -j j], h = 0
         if constexpr (BS) {
-          store_blk<true>(r, P, a, b, up, act, kidx, Jp);
-          store_blk<true>(r + bs16::t11(P), P, a, b, up, act, kidx, Jp);
-          if (act) *reinterpret_cast<double4*>(r + bs16::t10(P) + (a + G * b) * 4) = make_double4(Jm.x, Jm.y, Jm.z, Jm.w);
+          store_blk<true, false, false, PL>(r, P, a, b, up, act, kidx, Jp);
+          store_blk<true, false, false, PL>(r + bs16::t11(P), P, a, b, up, act, kidx, Jp);
+          if (act) {
+            double* tp = r + bs16::t10(P) + (a + G * b) * 2;
+            *reinterpret_cast<double2*>(tp) = make_double2(Jm.x, Jm.y);
+            *reinterpret_cast<double2*>(tp + PLT) = make_double2(Jm.z, Jm.w);
+          }
           if (act && b == 0) {
             *reinterpret_cast<double2*>(r + bs16::h2(P) + 2 * a) = make_double2(0.0, 0.0);
             *reinterpret_cast<double2*>(r + bs16::h2(P) + P + 2 * a) = make_double2(0.0, 0.0);
@@ -796,7 +808,7 @@ __global__ __launch_bounds__(256) void bm_tree_fill_fast(double* __restrict__ po
           if (lane == 0) r[4 * PR * PR + 2 * PR] = g;
         }
       } else if (k <= 2) {  // P x P block j on the kept variables, h = +j v
-        store_blk<BS, ODD>(r, PR, a, b, up, act, kidx, Jp, PR);
+        store_blk<BS, ODD, false, PL>(r, PR, a, b, up, act, kidx, Jp, PR);
         if (act && b == 0) store_pair<ODD>(r + (BS ? bs16::h1(P) : PR * PR), a, jv0, jv1, PR);
         if (lane == 0) r[BS ? bs16::g1(P) : PR * PR + PR] = g;
       } else {  // everything absorbed: a constant

@@ -275,23 +275,28 @@ struct Blk { double x, y, z, w; };
 
 // Load / store the lane's block of a 16 x 16 symmetric quantity (sepset J, residual dJ, receiver sub-block,
 // a 16-dim sender).  Plain layout: column-major with leading dimension ld, all 64 lanes (two double2).
-// BS16: packed upper blocks, lanes a <= b only (one double4), pgbp_bs16.hpp.
+// BS16: packed upper blocks, lanes a <= b only, pgbp_bs16.hpp: the block's left column at base + kidx (kidx = 2k), its right
+// column PL doubles behind it (PL = bs16::sym_plane(P), a constant: two 16-byte accesses off one address, each
+// wave-instruction one contiguous plane of the tile).
 // ODD (plain layout only): the quantity really is n x n with n = P - 1 odd; the lane grid is the one of P, index n is
 // a phantom (reads 0, is never stored), and the accesses are element-wise because rows no longer pair up on 16 bytes.
-typedef double pgbp_d4v __attribute__((ext_vector_type(4)));
+typedef double pgbp_d2v __attribute__((ext_vector_type(2)));
 // NT: a streaming load (an operand this calibrate reads once: a sepset, a leaf's belief)
-template <bool BS, bool ODD = false, bool NT = false>
+template <bool BS, bool ODD = false, bool NT = false, int PL = 0>
 __device__ __forceinline__ Blk load_blk(const double* __restrict__ base, int ld, int a, int b, bool up, int kidx,
                                         int n = 0) {
   Blk r{0.0, 0.0, 0.0, 0.0};
   if constexpr (BS) {
+    static_assert(PL > 0, "a packed tile access names its plane stride");
     if (up) {
       if constexpr (NT) {
-        const pgbp_d4v v = __builtin_nontemporal_load(reinterpret_cast<const pgbp_d4v*>(base + kidx));
-        r = Blk{v.x, v.y, v.z, v.w};
+        const pgbp_d2v v = __builtin_nontemporal_load(reinterpret_cast<const pgbp_d2v*>(base + kidx));
+        const pgbp_d2v u = __builtin_nontemporal_load(reinterpret_cast<const pgbp_d2v*>(base + kidx + PL));
+        r = Blk{v.x, v.y, u.x, u.y};
       } else {
-        const double4 v = *reinterpret_cast<const double4*>(base + kidx);
-        r = Blk{v.x, v.y, v.z, v.w};
+        const double2 v = *reinterpret_cast<const double2*>(base + kidx);
+        const double2 u = *reinterpret_cast<const double2*>(base + kidx + PL);
+        r = Blk{v.x, v.y, u.x, u.y};
       }
     }
   } else if constexpr (ODD) {
@@ -308,13 +313,20 @@ __device__ __forceinline__ Blk load_blk(const double* __restrict__ base, int ld,
   return r;
 }
 // NT: a streaming store (the residuals: written by every message, read by nobody before the next reset)
-template <bool BS, bool ODD = false, bool NT = false>
+template <bool BS, bool ODD = false, bool NT = false, int PL = 0>
 __device__ __forceinline__ void store_blk(double* __restrict__ base, int ld, int a, int b, bool up, bool act, int kidx,
                                           const Blk& v, int n = 0) {
   if constexpr (BS) {
+    static_assert(PL > 0, "a packed tile access names its plane stride");
     if constexpr (NT) {
-      if (up) __builtin_nontemporal_store(pgbp_d4v{v.x, v.y, v.z, v.w}, reinterpret_cast<pgbp_d4v*>(base + kidx));
-    } else if (up) *reinterpret_cast<double4*>(base + kidx) = make_double4(v.x, v.y, v.z, v.w);
+      if (up) {
+        __builtin_nontemporal_store(pgbp_d2v{v.x, v.y}, reinterpret_cast<pgbp_d2v*>(base + kidx));
+        __builtin_nontemporal_store(pgbp_d2v{v.z, v.w}, reinterpret_cast<pgbp_d2v*>(base + kidx + PL));
+      }
+    } else if (up) {
+      *reinterpret_cast<double2*>(base + kidx) = make_double2(v.x, v.y);
+      *reinterpret_cast<double2*>(base + kidx + PL) = make_double2(v.z, v.w);
+    }
   } else if constexpr (ODD) {
     if (act) {
       const int r0 = 2 * a, r1 = 2 * a + 1, c0 = 2 * b, c1 = 2 * b + 1;
@@ -334,7 +346,6 @@ __device__ __forceinline__ double2 load_pair(const double* __restrict__ v, int a
   if constexpr (ODD) return make_double2(2 * a < n ? v[2 * a] : 0.0, 2 * a + 1 < n ? v[2 * a + 1] : 0.0);
   else return *reinterpret_cast<const double2*>(v + 2 * a);
 }
-typedef double pgbp_d2v __attribute__((ext_vector_type(2)));
 template <bool ODD, bool NT = false>
 __device__ __forceinline__ void store_pair(double* __restrict__ v, int a, double x, double y, int n) {
   if constexpr (ODD) {

@@ -48,7 +48,7 @@ constexpr int kLoopWaves = 2 * kTailWaves;
 // or a copy of a loaded register is a wait for that load, and these loads are in flight across half a pass)
 struct SndOps {
   Blk ii, ss;       // 2P sender: its integrated and kept tiles; P-dim sender: ii = its tile
-  double4 t;        // 2P sender: the block of T10 this lane needs
+  double2 t0, t1;   // 2P sender: the block of T10 this lane needs, left and right column
   double2 hi, hs;   // h of the integrated / kept variables (P-dim sender: hi = its h)
   double g;
   Blk xJ, s2;       // prologue: X's tile, the sepset (X, F)
@@ -73,6 +73,7 @@ __global__ __launch_bounds__(kLoopWaves * 64) void bp_loop16(DevState S_arg, con
                                                              unsigned long long stop_b_arg,
                                                              const int32_t* __restrict__ wg_off) {
   constexpr int W = kTailWaves, G = P / 2;
+  constexpr int PL = bs16::sym_plane(P), PLT = bs16::full_plane(P);   // plane strides of the packed tiles (pgbp_bs16.hpp)
   DevState S = S_arg;
   const FEntry* __restrict__ recs = recs_arg;
   int ngroups = ngroups_arg, split = split_arg;
@@ -95,14 +96,14 @@ __global__ __launch_bounds__(kLoopWaves * 64) void bp_loop16(DevState S_arg, con
   bool act = lane < G * G;
   int a = act ? lane % G : 0, b = act ? lane / G : 0;
   bool up = act && a <= b;
-  int kidx = (b * (b + 1) / 2 + a) * 4;
+  int kidx = (b * (b + 1) / 2 + a) * 2;
   auto lane_geometry = [&]() {
     asm volatile("; lane geometry" : "+v"(lane));
     act = lane < G * G;
     a = act ? lane % G : 0;
     b = act ? lane / G : 0;
     up = act && a <= b;
-    kidx = (b * (b + 1) / 2 + a) * 4;
+    kidx = (b * (b + 1) / 2 + a) * 2;
   };
   double* __restrict__ pool = S.pool + (int64_t)site * S.pool_stride;
   double* __restrict__ rpool = S.rpool + (int64_t)site * S.rpool_stride;
@@ -129,14 +130,18 @@ __global__ __launch_bounds__(kLoopWaves * 64) void bp_loop16(DevState S_arg, con
     const int o_hs = heavy ? bs16::h2(P) + (itrail ? 0 : P) : 0;
     const int o_g = heavy ? bs16::g2(P) : (none ? 0 : bs16::g1(P));
     const int lk = none ? 0 : kidx, la = none ? 0 : 2 * a;                  // (a constant's record is one double long)
-    const int lt = none ? 0 : (itrail ? (b + G * a) : (a + G * b)) * 4;
-    {   // (every lane loads: a lane below the diagonal fetches some other block of the tile, zeroed where it is used)
-      const double4 v = *reinterpret_cast<const double4*>(from + o_ii + lk);
-      const double4 u = *reinterpret_cast<const double4*>(from + o_ss + lk);
-      s.ii = Blk{v.x, v.y, v.z, v.w};
-      s.ss = Blk{u.x, u.y, u.z, u.w};
+    const int lt = none ? 0 : (itrail ? (b + G * a) : (a + G * b)) * 2;
+    {   // (every lane loads: a lane below the diagonal fetches some other block of the tile, zeroed where it is used; the
+        // right columns of a constant's one-double record come from whatever follows it in the pool, pgbp_engine.hip: kPoolTail)
+      const double2 v0 = *reinterpret_cast<const double2*>(from + o_ii + lk);
+      const double2 v1 = *reinterpret_cast<const double2*>(from + o_ii + lk + PL);
+      const double2 u0 = *reinterpret_cast<const double2*>(from + o_ss + lk);
+      const double2 u1 = *reinterpret_cast<const double2*>(from + o_ss + lk + PL);
+      s.ii = Blk{v0.x, v0.y, v1.x, v1.y};
+      s.ss = Blk{u0.x, u0.y, u1.x, u1.y};
     }
-    s.t = *reinterpret_cast<const double4*>(from + o_t + lt);
+    s.t0 = *reinterpret_cast<const double2*>(from + o_t + lt);
+    s.t1 = *reinterpret_cast<const double2*>(from + o_t + lt + PLT);
     s.hi = *reinterpret_cast<const double2*>(from + o_hi + la);
     s.hs = *reinterpret_cast<const double2*>(from + o_hs + la);
     s.g = from[o_g];
@@ -149,10 +154,12 @@ __global__ __launch_bounds__(kLoopWaves * 64) void bp_loop16(DevState S_arg, con
       const double* __restrict__ xfrom = pool + qp.from_off;   // (no prologue: offsets 0, the start of the pool)
       const double* __restrict__ sep2 = pool + qp.sep_off;
       {
-        const double4 v = *reinterpret_cast<const double4*>(xfrom + kidx);
-        const double4 u = *reinterpret_cast<const double4*>(sep2 + kidx);
-        s.xJ = Blk{v.x, v.y, v.z, v.w};
-        s.s2 = Blk{u.x, u.y, u.z, u.w};
+        const double2 v0 = *reinterpret_cast<const double2*>(xfrom + kidx);
+        const double2 v1 = *reinterpret_cast<const double2*>(xfrom + kidx + PL);
+        const double2 u0 = *reinterpret_cast<const double2*>(sep2 + kidx);
+        const double2 u1 = *reinterpret_cast<const double2*>(sep2 + kidx + PL);
+        s.xJ = Blk{v0.x, v0.y, v1.x, v1.y};
+        s.s2 = Blk{u0.x, u0.y, u1.x, u1.y};
       }
       s.xh = *reinterpret_cast<const double2*>(xfrom + bs16::h1(P) + 2 * a);
       s.s2h = *reinterpret_cast<const double2*>(sep2 + bs16::h1(P) + 2 * a);
@@ -276,7 +283,7 @@ __global__ __launch_bounds__(kLoopWaves * 64) void bp_loop16(DevState S_arg, con
           if (up) {
             f.w[2][2] = cs.ss.x; f.w[3][2] = cs.ss.y; f.w[2][3] = cs.ss.z; f.w[3][3] = cs.ss.w;
           }
-          f.w[2][0] = cs.t.x; f.w[3][0] = itrail ? cs.t.z : cs.t.y; f.w[2][1] = itrail ? cs.t.y : cs.t.z; f.w[3][1] = cs.t.w;
+          f.w[2][0] = cs.t0.x; f.w[3][0] = itrail ? cs.t1.x : cs.t0.y; f.w[2][1] = itrail ? cs.t0.y : cs.t1.x; f.w[3][1] = cs.t1.y;
           f.h[2] = cs.hs.x; f.h[3] = cs.hs.y;
         }
         gmsg = cs.g;
@@ -443,14 +450,14 @@ __global__ __launch_bounds__(kLoopWaves * 64) void bp_loop16(DevState S_arg, con
       if (live) {
         if (!sepz) {
           if (has_block) {
-            sJ = load_blk<true, false, !PRO>(sep, P, a, b, up, kidx);
+            sJ = load_blk<true, false, !PRO, PL>(sep, P, a, b, up, kidx);
             if (b == 0) sh = load_pair<false>(sep + bs16::h1(P), a, P);
           }
           sg = sep[sepG];
         }
         if (own) {
           if (recv_blk) {
-            tJ = load_blk<true>(to + tJ0, mt, a, b, up, kidx);
+            tJ = load_blk<true, false, false, PL>(to + tJ0, mt, a, b, up, kidx);
             if (b == 0) {
               const double2 t2 = load_pair<false>(to + tH0, a, P);
               th0 = t2.x; th1 = t2.y;
@@ -474,16 +481,16 @@ __global__ __launch_bounds__(kLoopWaves * 64) void bp_loop16(DevState S_arg, con
             p_xg = src[kLSlotG];
             if ((int)src[kLSlotStatus] != 1) poison_p = 1;
           } else {
-            p_x = load_blk<true>(xfrom, P, a, b, up, kidx);
+            p_x = load_blk<true, false, false, PL>(xfrom, P, a, b, up, kidx);
             xh = load_pair<false>(xfrom + bs16::h1(P), a, P);
             p_xg = xfrom[bs16::g1(P)];
           }
           if (!sepz) {
-            s2 = load_blk<true>(sep2, P, a, b, up, kidx);
+            s2 = load_blk<true, false, false, PL>(sep2, P, a, b, up, kidx);
             s2h = load_pair<false>(sep2 + bs16::h1(P), a, P);
             s2g = sep2[bs16::g1(P)];
           }
-          const Blk fi = load_blk<true>(fw + f_ii, P, a, b, up, kidx);
+          const Blk fi = load_blk<true, false, false, PL>(fw + f_ii, P, a, b, up, kidx);
           const double2 fh = load_pair<false>(fw + f_hi, a, P);
           const double fg = fw[bs16::g2(P)];
           // the message X -> F as bp_fast16 forms it: divide! by the sepset (X, F), mult! onto F's record
@@ -592,8 +599,8 @@ __global__ __launch_bounds__(kLoopWaves * 64) void bp_loop16(DevState S_arg, con
         double* __restrict__ res2 = rpool + pr.res_off;
         double* __restrict__ fw = pool + en.from_off;
         constexpr int xH = bs16::h1(P), xG = bs16::g1(P);
-        store_blk<true>(sep2, P, a, b, up, act, kidx, p_x);
-        store_blk<true, false, true>(res2, P, a, b, up, act, kidx, p_d);
+        store_blk<true, false, false, PL>(sep2, P, a, b, up, act, kidx, p_x);
+        store_blk<true, false, true, PL>(res2, P, a, b, up, act, kidx, p_d);
         double maxJ2 = 0.0, maxh2 = 0.0;
         if (up) {
           maxJ2 = fmax(fmax(fabs(p_d.x), fabs(p_d.y)), fmax(fabs(p_d.z), fabs(p_d.w)));
@@ -612,15 +619,15 @@ __global__ __launch_bounds__(kLoopWaves * 64) void bp_loop16(DevState S_arg, con
           const bool all_ok2 = __all(maxh2 <= S.thr_h_p && maxJ2 <= S.thr_J_p);
           if (lane == 0) S.flags[(int64_t)site * S.n_msgs + pr.msg] = all_ok2 ? 1 : 0;
         }
-        store_blk<true>(fw + f_ii, P, a, b, up, act, kidx, p_ii);
+        store_blk<true, false, false, PL>(fw + f_ii, P, a, b, up, act, kidx, p_ii);
         if (act && b == 0) store_pair<false>(fw + f_hi, a, p_h0, p_h1, P);
         if (lane == 0) fw[bs16::g2(P)] = p_g;
       }
       if (state == 1) {
         if (has_block) {
           // (streaming stores, as in bp_fast16: nothing reads the residual, and the sepset not before the other traversal)
-          store_blk<true, false, !PRO>(sep, P, a, b, up, act, kidx, mJ);
-          store_blk<true, false, true>(res, P, a, b, up, act, kidx, dJ);
+          store_blk<true, false, !PRO, PL>(sep, P, a, b, up, act, kidx, mJ);
+          store_blk<true, false, true, PL>(res, P, a, b, up, act, kidx, dJ);
           if (act && b == 0) {
             store_pair<false, !PRO>(sep + bs16::h1(P), a, mh0, mh1, P);
             store_pair<false, true>(res + bs16::h1(P), a, dh0, dh1, P);
@@ -638,7 +645,7 @@ __global__ __launch_bounds__(kLoopWaves * 64) void bp_loop16(DevState S_arg, con
         }
         if (own) {
           if (recv_blk) {
-            store_blk<true>(to + tJ0, mt, a, b, up, act, kidx, tJ);
+            store_blk<true, false, false, PL>(to + tJ0, mt, a, b, up, act, kidx, tJ);
             if (act && b == 0) store_pair<false>(to + tH0, a, th0, th1, P);
           }
           if (lane == 0) to[tG0] = tg;
