@@ -3,13 +3,14 @@
 //
 // Fisher's identity as in pgbp_grad.hip, without the sum over the families: the length t_k and the inheritance gamma_k of
 // parent edge k enter the likelihood through the factor of their own family only, and there through the edge coefficients
-// (qc_k, vc_k, wc_k) of lg_coefs (pgbp_lgfill.hip).  With the family quantities of pgbp_grad.hip -- O = child_mask[f],
+// (qc_k, vc_k, wc_k) of lg_coefs (pgbp_fam_dev.hpp; their derivatives: lg_coefs_dedge).  With the family quantities that
+// fam_score_T and fam_score_gv of that header form for this kernel and grad_family alike -- O = child_mask[f],
 // j = (V_OO)^-1, r = x_child - sum_k qc_k x_k - w, e = E[r], M = Cov(r) + e e', G_V = (j M j - j) / 2, g_w = j e,
 // g_qk = E[r' j x_k] under the belief of the family's cluster --
 //   dX_k = dvc_k/dX tr(G_V R[colour_k]_OO) + dwc_k/dX theta_O' g_w + dqc_k/dX g_qk,    X in {t, gamma},
 //   BM:  dqc/dt = 0,            dvc/dt = gamma^2,               dwc/dt = 0;
 //        dqc/dgamma = 1,        dvc/dgamma = 2 gamma t,         dwc/dgamma = 0;
-//   OU (a = exp(-alpha t)):
+//   OU (a = e^(-alpha t)):
 //        dqc/dt = -gamma alpha a,  dvc/dt = 2 gamma^2 alpha a^2,  dwc/dt = gamma alpha a;
 //        dqc/dgamma = a,           dvc/dgamma = 2 gamma (1 - a^2), dwc/dgamma = 1 - a,
 // and the score of an additive displacement s of the child's conditional mean (r = ... - w - s) is g_w.
@@ -26,82 +27,17 @@
 
 #include "pgbp_bs16.hpp"
 #include "pgbp_devmem.hpp"
+#include "pgbp_fam_dev.hpp"
 #include "pgbp_kernels.hpp"
-#include "pgbp_mom_dev.hpp"
-#include "pgbp_shift_dev.hpp"
 
 namespace pgbp {
 
 extern __shared__ double edge_lds[];
 
-// edge coefficients of a parent edge (lg_coefs of pgbp_lgfill.hip; a = exp(-alpha t)) and their partial derivatives in the
-// length (q_t, v_t, w_t) and in the inheritance (q_g, v_g, w_g)
-struct EdgeCoefs {
-  double qc, vc, wc, q_t, v_t, w_t, q_g, v_g, w_g;
-};
-__device__ __forceinline__ EdgeCoefs edge_coefs(int model, double alpha, double t, double gam) {
-#pragma clang fp contract(off)
-  EdgeCoefs c;
-  if (model == PGBP_LG_OU) {
-    const double a = exp(-alpha * t);
-    c.qc = gam * a;
-    c.vc = gam * gam * (1.0 - a * a);
-    c.wc = gam * (1.0 - a);
-    c.q_t = -(gam * alpha) * a;
-    c.v_t = 2.0 * (gam * gam) * alpha * (a * a);
-    c.w_t = (gam * alpha) * a;
-    c.q_g = a;
-    c.v_g = 2.0 * gam * (1.0 - a * a);
-    c.w_g = 1.0 - a;
-  } else {
-    c.qc = gam;
-    c.vc = gam * gam * t;
-    c.wc = 0.0;
-    c.q_t = 0.0;
-    c.v_t = gam * gam;
-    c.w_t = 0.0;
-    c.q_g = 1.0;
-    c.v_g = 2.0 * gam * t;
-    c.w_g = 0.0;
-  }
-  return c;
-}
-
-__device__ __forceinline__ int edge_rank(unsigned long long mask, int t) { return __popcll(mask & ((1ull << t) - 1ull)); }
-
-// Gauss-Jordan on the mo x 2mo system [V | I] (row stride ld) in LDS by NT threads: the right half becomes V^-1; false when
-// a pivot is not positive (uniform: every thread reads the same pivot)
-template <int NT>
-__device__ __forceinline__ bool edge_invert(double* __restrict__ A, int mo, int ld, int t) {
-#pragma clang fp contract(off)
-  const int nc = 2 * mo;
-  for (int k = 0; k < mo; ++k) {
-    __syncthreads();
-    const double d = A[k * ld + k];
-    if (!(d > 0.0)) return false;
-    const double rd = 1.0 / d;
-    __syncthreads();
-    for (int j = k + 1 + t; j < nc; j += NT) A[k * ld + j] = A[k * ld + j] * rd;
-    __syncthreads();
-    const int ncol = nc - (k + 1);
-    for (int idx = t; idx < (mo - 1) * ncol; idx += NT) {
-      int i = idx / ncol;
-      const int j = k + 1 + (idx - i * ncol);
-      if (i >= k) ++i;
-      A[i * ld + j] = A[i * ld + j] - A[i * ld + k] * A[k * ld + j];
-    }
-  }
-  __syncthreads();
-  return true;
-}
-
-// LDS of edge_family beyond mom_solve's: doubles, then ints
-constexpr int kEdgeCoefs = 9;   // the members of EdgeCoefs, K of each
-__host__ __device__ inline int edge_ldv(int p) { return (2 * p) | 1; }
-__host__ __device__ inline size_t edge_extra_doubles(int p, int K) {
-  return (size_t)p * edge_ldv(p) + 3 * (size_t)p * p + 4 * (size_t)p + (size_t)(K + 1) * p + (size_t)kEdgeCoefs * K;
-}
-__host__ __device__ inline size_t edge_extra_ints(int p, int K) { return (size_t)(K + 1) + (size_t)p + (size_t)(K + 1) * p; }
+// LDS of edge_family: fam_score's arrays with six more rows of coefficients (LgEdgeDerivs: q_t, v_t, w_t, q_g, v_g, w_g), and
+// of its own Px (p x p) and the row sums rq, rr (p each)
+constexpr int kEdgeRows = 9;
+__host__ __device__ inline size_t edge_extra_doubles(int p) { return (size_t)p * p + 2 * (size_t)p; }
 
 // dlen / dgam [n_sites][n_fam][K], dshift [n_sites][n_fam][p] of the sites site0 .. site0 + n_sites (any may be null)
 template <int NT>
@@ -119,29 +55,18 @@ __global__ __launch_bounds__(NT) void edge_family(const double* __restrict__ poo
   const unsigned long long O = F.child_mask ? (F.child_mask[f] & full) : full;
   const int mo = __popcll(O);
   const int cpos = F.child_pos[f];
-  // LDS: [W | dv] of mom_solve, then this kernel's arrays
-  double* __restrict__ W = edge_lds;
-  double* __restrict__ dv = edge_lds + m * ld;
-  double* __restrict__ A = edge_lds + mom_lds_doubles(m);   // [V_OO | I] -> [.. | j], mo x ldv
-  const int ldv = edge_ldv(p);
-  double* __restrict__ Mx = A + p * ldv;        // M = Cov(r) + e e', then G_V  (mo x mo)
-  double* __restrict__ Tx = Mx + p * p;         // j M, then the terms of tr(G_V R[colour_k])
-  double* __restrict__ Px = Tx + p * p;         // the terms of g_qk = sum_il j(l, i) E[r x_k'](i, l)
-  double* __restrict__ ev = Px + p * p;         // e
-  double* __restrict__ ge = ev + p;             // j e
-  double* __restrict__ rq = ge + p;             // row sums of Px, of Tx
+  const FamLds L = fam_carve(edge_lds, m, p, K, kEdgeRows, edge_extra_doubles(p));
+  const int ldv = fam_ldv(p);
+  double* cf = L.cf;                            // rows of K: qc, vc, wc, then LgEdgeDerivs
+  double* __restrict__ Tx = L.Tx;               // j M, then the terms of tr(G_V R[colour_k])
+  double* __restrict__ Px = L.extra;            // the terms of g_qk = sum_il j(l, i) E[r x_k'](i, l)
+  double* __restrict__ rq = Px + p * p;         // row sums of Px, of Tx
   double* __restrict__ rr = rq + p;
-  double* __restrict__ xm = rr + p;             // [a][i]: posterior mean of block a (or its constant value) at kept trait i
-  double* __restrict__ cf = xm + (K + 1) * p;   // [kEdgeCoefs][K]
-  int* __restrict__ ipos = reinterpret_cast<int*>(edge_lds + mom_lds_doubles(m) + ((edge_extra_doubles(p, K) + 1) & ~(size_t)1));
-  int* __restrict__ oidx = ipos + (K + 1);
-  int* __restrict__ vi = oidx + p;              // [a][i]: the variable's index in the cluster, -1: a constant
   bool any_scope = cpos >= 0;
   for (int k = 0; k < np; ++k) any_scope |= F.parent_pos[(size_t)f * K + k] >= 0;
   // families the factor fill skips (and a root-prior family of a fixed root, which has no factor)
   const bool skip = mo == 0 || (np == 0 && cpos < 0);
   const bool packed = bs && bs16::applies(m, fp);
-  const bool ou = M.model == PGBP_LG_OU;
   for (int site = blockIdx.y; site < n_sites; site += gridDim.y) {
     const int64_t fo = (int64_t)site * n_fam + f;
     // every entry of the family: `edge` at its real edges, NaN where there is no edge, `shift` at the p traits
@@ -157,132 +82,36 @@ __global__ __launch_bounds__(NT) void edge_family(const double* __restrict__ poo
       write_all(0.0, 0.0);
       continue;
     }
-    const int64_t as = site0 + site, ps = M.per_site ? as : 0;
-    const double* __restrict__ R = M.R + ps * F.n_rates * p * p;
-    const double* __restrict__ mu = M.mu + ps * p;
-    const double* __restrict__ theta = (ou && M.theta) ? M.theta + ps * p : nullptr;
-    const double alpha = ou ? M.alpha[ps] : 0.0;
+    const int64_t as = site0 + site;
+    const LgSite S = lg_site(M, F.n_rates, p, as);
     int st = 0;
     if (any_scope) {
       const double* __restrict__ rec = pool + as * pool_stride + boff[c];
       double mant, quad;
       int expo;
-      st = mom_solve<NT, true>(rec, m, packed, fp, W, dv, t, mant, expo, quad);
+      st = mom_solve<NT, true>(rec, m, packed, fp, L.W, L.dv, t, mant, expo, quad);
     } else {
       __syncthreads();   // (the previous site's arrays have been read)
     }
-    if (st != 0) {   // not positive definite (the constant belief J = 0 included: no moments)
+    // the cluster is not positive definite (the constant belief J = 0 included: no moments), or the family's variance is not
+    // (the fill made this cluster's g NaN)
+    if (st == 0) {
+      for (int k = t; k < np; k += NT) {
+        const LgEdgeDerivs d = lg_coefs_dedge(M.model, S.alpha, F.length[(size_t)f * K + k], F.gamma[(size_t)f * K + k]);
+        cf[3 * K + k] = d.q_t; cf[4 * K + k] = d.v_t; cf[5 * K + k] = d.w_t;
+        cf[6 * K + k] = d.q_g; cf[7 * K + k] = d.v_g; cf[8 * K + k] = d.w_g;
+      }
+      if (!fam_score_T<NT>(L, F, M, Sh, S, f, m, O, as, t)) st = 1;
+    }
+    if (st != 0) {
       write_all(NAN, NAN);
       if (t == 0) atomicMin(info + info0 + site, c + 1);
       continue;
     }
-    // coefficients, positions, kept traits
-    for (int a = t; a <= np; a += NT) {
-      if (a == 0) {
-        ipos[0] = cpos;
-      } else {
-        const int k = a - 1;
-        const EdgeCoefs e = edge_coefs(M.model, alpha, F.length[(size_t)f * K + k], F.gamma[(size_t)f * K + k]);
-        cf[0 * K + k] = e.qc; cf[1 * K + k] = e.vc; cf[2 * K + k] = e.wc;
-        cf[3 * K + k] = e.q_t; cf[4 * K + k] = e.v_t; cf[5 * K + k] = e.w_t;
-        cf[6 * K + k] = e.q_g; cf[7 * K + k] = e.v_g; cf[8 * K + k] = e.w_g;
-        ipos[a] = F.parent_pos[(size_t)f * K + k];
-      }
-    }
-    for (int tr = t; tr < p; tr += NT)
-      if ((O >> tr) & 1ull) oidx[edge_rank(O, tr)] = tr;
-    __syncthreads();
-    auto cz = [&](int a) -> double { return a == 0 ? 1.0 : -cf[a - 1]; };   // c_0 = 1, c_k = -qc_k
-    // where each block's kept traits sit in the cluster, and their posterior mean (or constant value)
-    for (int idx = t; idx < nn * mo; idx += NT) {
-      const int a = idx / mo, i = idx - a * mo, tr = oidx[i];
-      const int pa = ipos[a];
-      if (pa >= 0) {
-        const unsigned long long ma = a == 0 ? O : (F.parent_mask ? F.parent_mask[(size_t)f * K + a - 1] : full);
-        const int v = pa + edge_rank(ma, tr);
-        vi[a * p + i] = v;
-        xm[a * p + i] = W[v * ld + m];
-      } else {
-        vi[a * p + i] = -1;
-        xm[a * p + i] = a == 0 ? F.data[(as * F.n_rows + F.data_row[f]) * p + tr] : mu[tr];   // tip / fixed root
-      }
-    }
-    // V_OO and the identity
-    for (int idx = t; idx < mo * mo; idx += NT) {
-      const int j = idx / mo, i = idx - j * mo;
-      const int e = oidx[i] + oidx[j] * p;
-      double v = 0.0;
-      if (np == 0) {
-        v = R[(int64_t)F.color[(size_t)f * K] * p * p + e];
-      } else {
-        for (int k = 0; k < np; ++k) v = v + cf[1 * K + k] * R[(int64_t)F.color[(size_t)f * K + k] * p * p + e];
-      }
-      A[i * ldv + j] = v;
-      A[i * ldv + mo + j] = (i == j) ? 1.0 : 0.0;
-    }
-    __syncthreads();
-    // e = E[r]
-    for (int i = t; i < mo; i += NT) {
-      const int tr = oidx[i];
-      double e = 0.0;
-      for (int a = 0; a < nn; ++a) e = e + cz(a) * xm[a * p + i];
-      double w = 0.0;
-      if (np == 0) {
-        w = mu[tr];
-      } else if (theta) {
-        for (int k = 0; k < np; ++k) w = w + cf[2 * K + k] * theta[tr];
-      }
-      if (Sh.slot) w = w + lg_shift_d(Sh, F.gamma, f, K, np, tr, p, as);   // a shift of the mean on a parent edge
-      ev[i] = e - w;
-    }
-    __syncthreads();
-    // M = Cov(r) + e e'
-    for (int idx = t; idx < mo * mo; idx += NT) {
-      const int j = idx / mo, i = idx - j * mo;
-      double s = 0.0;
-      for (int a = 0; a < nn; ++a) {
-        const int va = vi[a * p + i];
-        if (va < 0) continue;
-        for (int b = 0; b < nn; ++b) {
-          const int vb = vi[b * p + j];
-          if (vb < 0) continue;
-          s = s + cz(a) * cz(b) * (va >= vb ? W[va * ld + vb] : W[vb * ld + va]);
-        }
-      }
-      Mx[i * mo + j] = s + ev[i] * ev[j];
-    }
-    if (!edge_invert<NT>(A, mo, ldv, t)) {   // a variance that is not positive definite: the fill made this cluster's g NaN
-      write_all(NAN, NAN);
-      if (t == 0) atomicMin(info + info0 + site, c + 1);
-      continue;
-    }
-    // j(i, k): the upper triangle mirrored, exactly symmetric (as the fill reads it)
-    auto jj = [&](int i, int k) -> double { return i <= k ? A[i * ldv + mo + k] : A[k * ldv + mo + i]; };
-    for (int idx = t; idx < mo * mo; idx += NT) {
-      const int k = idx / mo, i = idx - k * mo;
-      double s = 0.0;
-      for (int l = 0; l < mo; ++l) s = s + jj(i, l) * Mx[l * mo + k];
-      Tx[i * mo + k] = s;
-    }
-    for (int i = t; i < mo; i += NT) {
-      double s = 0.0;
-      for (int l = 0; l < mo; ++l) s = s + jj(i, l) * ev[l];
-      ge[i] = s;
-    }
-    __syncthreads();
-    // G_V = (j M j - j) / 2 (upper triangle computed, mirrored) over M, which T = j M has consumed
-    for (int idx = t; idx < mo * mo; idx += NT) {
-      const int k = idx / mo, i = idx - k * mo;
-      if (i > k) continue;
-      double s = 0.0;
-      for (int l = 0; l < mo; ++l) s = s + Tx[i * mo + l] * jj(l, k);
-      const double g = 0.5 * (s - jj(i, k));
-      Mx[i * mo + k] = g;
-      Mx[k * mo + i] = g;
-    }
+    fam_score_gv<NT>(L, p, mo, nullptr, t);   // G_V over M
     // the shift: g_w embedded into the p traits
     if (dshift)
-      for (int tr = t; tr < p; tr += NT) dshift[fo * p + tr] = ((O >> tr) & 1ull) ? ge[edge_rank(O, tr)] : 0.0;
+      for (int tr = t; tr < p; tr += NT) dshift[fo * p + tr] = ((O >> tr) & 1ull) ? L.ge[mask_rank(O, tr)] : 0.0;
     for (int k = np + t; k < K; k += NT) {   // no such edge (every entry of a root-prior family)
       if (dlen) dlen[fo * K + k] = NAN;
       if (dgam) dgam[fo * K + k] = NAN;
@@ -290,20 +119,20 @@ __global__ __launch_bounds__(NT) void edge_family(const double* __restrict__ poo
     if (!dlen && !dgam) continue;
     for (int k = 0; k < np; ++k) {
       __syncthreads();   // (G_V is complete and T read; the previous edge's row sums have been read)
-      const double* __restrict__ Rk = R + (int64_t)F.color[(size_t)f * K + k] * p * p;
+      const double* __restrict__ Rk = S.R + (int64_t)F.color[(size_t)f * K + k] * p * p;
       for (int idx = t; idx < mo * mo; idx += NT) {
         const int i = idx / mo, l = idx - i * mo;
         // E[r x_k'](i, l) = sum_a c_a Sigma(a_i, k_l) + e_i m_k(l)
-        double ex = ev[i] * xm[(k + 1) * p + l];
-        const int vk = vi[(k + 1) * p + l];
+        double ex = L.ev[i] * L.xm[(k + 1) * p + l];
+        const int vk = L.vi[(k + 1) * p + l];
         if (vk >= 0) {
           for (int a = 0; a < nn; ++a) {
-            const int va = vi[a * p + i];
-            if (va >= 0) ex = ex + cz(a) * (va >= vk ? W[va * ld + vk] : W[vk * ld + va]);
+            const int va = L.vi[a * p + i];
+            if (va >= 0) ex = ex + fam_c(cf, a) * (va >= vk ? L.W[va * ld + vk] : L.W[vk * ld + va]);
           }
         }
-        Px[idx] = jj(l, i) * ex;
-        Tx[idx] = Mx[idx] * Rk[oidx[l] + oidx[i] * p];
+        Px[idx] = fam_j(L.A, ldv, mo, l, i) * ex;
+        Tx[idx] = L.Mx[idx] * Rk[L.oidx[l] + L.oidx[i] * p];
       }
       __syncthreads();
       for (int i = t; i < mo; i += NT) {   // row i in column order
@@ -321,14 +150,14 @@ __global__ __launch_bounds__(NT) void edge_family(const double* __restrict__ poo
         for (int i = 0; i < mo; ++i) {
           gq = gq + rq[i];
           trGR = trGR + rr[i];
-          if (theta) thg = thg + theta[oidx[i]] * ge[i];
+          if (S.theta) thg = thg + S.theta[L.oidx[i]] * L.ge[i];
         }
         if (dlen) dlen[fo * K + k] = cf[4 * K + k] * trGR + cf[5 * K + k] * thg + cf[3 * K + k] * gq;
         if (dgam) {
           double dg = cf[7 * K + k] * trGR + cf[8 * K + k] * thg + cf[6 * K + k] * gq;
           if (Sh.slot && Sh.slot[(size_t)f * K + k] >= 0) {   // the shift's coefficient is gamma_k: + s_k,O' g_w
             double sg = 0.0;
-            for (int i = 0; i < mo; ++i) sg = sg + lg_shift_value(Sh, (int64_t)f * K + k, oidx[i], p, as) * ge[i];
+            for (int i = 0; i < mo; ++i) sg = sg + lg_shift_value(Sh, (int64_t)f * K + k, L.oidx[i], p, as) * L.ge[i];
             dg = dg + sg;
           }
           dgam[fo * K + k] = dg;
@@ -363,28 +192,13 @@ extern "C" int pgbp_lg_edge_gradient(pgbp_engine* e, int32_t site_begin, int32_t
   const Plan& pl = *v.plan;
   const LgStatic& F = *v.lg;
   const LgShifts Sh = engine_lg_shifts(e);
-  const int nc = pl.n_clusters, p = F.p, K = F.K;
-  // which cluster each family sits in (the CSR of pgbp_lg_setup back from the device: a word per family)
-  std::vector<int32_t> off(nc + 1);
-  hipError_t herr = hipMemcpy(off.data(), F.cl_off, sizeof(int32_t) * (nc + 1), hipMemcpyDeviceToHost);
-  const int nf = herr == hipSuccess ? off[nc] : 0;
-  std::vector<int32_t> cfam(std::max(nf, 1));
-  if (herr == hipSuccess && nf > 0) herr = hipMemcpy(cfam.data(), F.cl_fam, sizeof(int32_t) * nf, hipMemcpyDeviceToHost);
-  if (herr != hipSuccess)
-    return engine_fail(e, PGBP_ERR_HIP, std::string("pgbp_lg_edge_gradient (family table): ") + hipGetErrorString(herr));
-  std::vector<int32_t> fcl(std::max(nf, 1), 0);
-  int max_m = 1;
-  for (int c = 0; c < nc; ++c)
-    for (int q = off[c]; q < off[c + 1]; ++q) {
-      fcl[cfam[q]] = c;
-      if (pl.dims[c] > kLdsMaxDim)
-        return engine_fail(e, PGBP_ERR_INVALID, "pgbp_lg_edge_gradient: family " + std::to_string(cfam[q]) + " (cluster " +
-                                                    std::to_string(c) + "): the cluster has more than " +
-                                                    std::to_string(kLdsMaxDim) + " variables");
-      max_m = std::max(max_m, (int)pl.dims[c]);
-    }
-  const size_t lds_bytes = sizeof(double) * (mom_lds_doubles(max_m) + ((edge_extra_doubles(p, K) + 1) & ~(size_t)1)) +
-                           sizeof(int) * edge_extra_ints(p, K);
+  const int p = F.p, K = F.K;
+  std::vector<int32_t> fcl;   // which cluster each family sits in
+  int max_m = 0;
+  rc = lg_family_clusters(e, "pgbp_lg_edge_gradient", v, true, &fcl, &max_m);
+  if (rc) return rc;
+  const int nf = (int)fcl.size();
+  const size_t lds_bytes = fam_score_lds_bytes(max_m, p, K, kEdgeRows, edge_extra_doubles(p));
   if (lds_bytes > 160 * 1024)
     return engine_fail(e, PGBP_ERR_INVALID, "pgbp_lg_edge_gradient: a cluster of " + std::to_string(max_m) + " variables with " +
                                                 std::to_string(p) + " traits needs " + std::to_string(lds_bytes) +
@@ -401,7 +215,7 @@ extern "C" int pgbp_lg_edge_gradient(pgbp_engine* e, int32_t site_begin, int32_t
   std::vector<int32_t> inf(ns, 0x7fffffff);   // (ahead of the buffers: they are released, which drains the uploads, first)
   DevBuf<int32_t> d_fcl, d_info;
   DevBuf<double> d_len, d_gam, d_shift;
-  herr = (hipError_t)d_fcl.alloc(nf);
+  hipError_t herr = (hipError_t)d_fcl.alloc(nf);
   if (herr == hipSuccess && dlength) herr = (hipError_t)d_len.alloc((size_t)chunk * nf * K);
   if (herr == hipSuccess && dgamma) herr = (hipError_t)d_gam.alloc((size_t)chunk * nf * K);
   if (herr == hipSuccess && dshift) herr = (hipError_t)d_shift.alloc((size_t)chunk * nf * p);

@@ -8,7 +8,9 @@
 // the cluster's J^-1 h and J^-1, a tip's data row and the fixed root's mean constants:
 //   e = E[r],  M = Cov(r) + e e',   G_V = (j M j - j) / 2   (d loglik = tr(G_V dV)),   g_w = j e   (d loglik = g_w' dw),
 //   g_qk = E[r' j x_k] = tr(j (sum_a c_a Sigma_ak + e m_k'))                          (d loglik = g_qk dqc_k),
-// and the chain rule through the edge coefficients (lg_coefs) gives dR[colour], dmu, dtheta and dalpha.
+// and the chain rule through the edge coefficients (lg_coefs, lg_coefs_dalpha of pgbp_fam_dev.hpp) gives dR[colour], dmu,
+// dtheta and dalpha.  e, M, j, G_V and g_w are formed by fam_score_T and fam_score_gv of that header, the body this kernel
+// shares with edge_family (pgbp_edge.hip); the slot, the alpha term and the chain-rule coefficients are this kernel's own.
 //
 // Stage 1 (grad_family): one workgroup per (family, site) solves the family's cluster in LDS (mom_solve: Sigma never leaves
 // the LDS) and writes the family's slot [G_V (p*p) | g_w (p) | dalpha term | c_mu | c_theta | c_R[n_rates]]: the matrices once
@@ -26,9 +28,8 @@
 
 #include "pgbp_bs16.hpp"
 #include "pgbp_devmem.hpp"
+#include "pgbp_fam_dev.hpp"
 #include "pgbp_kernels.hpp"
-#include "pgbp_mom_dev.hpp"
-#include "pgbp_shift_dev.hpp"
 
 namespace pgbp {
 
@@ -36,60 +37,8 @@ extern __shared__ double grad_lds[];
 
 constexpr int kGradFamBlock = 256;   // families per workgroup of the first reduction
 
-// edge coefficients of a parent edge and their derivatives in alpha (lg_coefs of pgbp_lgfill.hip; a = exp(-alpha t))
-__device__ __forceinline__ void grad_coefs(int model, double alpha, double t, double gam, double& qc, double& vc, double& wc,
-                                           double& dqc, double& dvc, double& dwc) {
-#pragma clang fp contract(off)
-  if (model == PGBP_LG_OU) {
-    const double a = exp(-alpha * t);
-    qc = gam * a;
-    vc = gam * gam * (1.0 - a * a);
-    wc = gam * (1.0 - a);
-    dqc = -(gam * t) * a;
-    dvc = 2.0 * (gam * gam) * t * (a * a);
-    dwc = (gam * t) * a;
-  } else {
-    qc = gam;
-    vc = gam * gam * t;
-    wc = 0.0;
-    dqc = dvc = dwc = 0.0;
-  }
-}
-
-__device__ __forceinline__ int grad_rank(unsigned long long mask, int t) { return __popcll(mask & ((1ull << t) - 1ull)); }
-
-// Gauss-Jordan on the mo x 2mo system [V | I] (row stride ld) in LDS by NT threads: the right half becomes V^-1; false when
-// a pivot is not positive (uniform: every thread reads the same pivot)
-template <int NT>
-__device__ __forceinline__ bool grad_invert(double* __restrict__ A, int mo, int ld, int t) {
-#pragma clang fp contract(off)
-  const int nc = 2 * mo;
-  for (int k = 0; k < mo; ++k) {
-    __syncthreads();
-    const double d = A[k * ld + k];
-    if (!(d > 0.0)) return false;
-    const double rd = 1.0 / d;
-    __syncthreads();
-    for (int j = k + 1 + t; j < nc; j += NT) A[k * ld + j] = A[k * ld + j] * rd;
-    __syncthreads();
-    const int ncol = nc - (k + 1);
-    for (int idx = t; idx < (mo - 1) * ncol; idx += NT) {
-      int i = idx / ncol;
-      const int j = k + 1 + (idx - i * ncol);
-      if (i >= k) ++i;
-      A[i * ld + j] = A[i * ld + j] - A[i * ld + k] * A[k * ld + j];
-    }
-  }
-  __syncthreads();
-  return true;
-}
-
-// LDS of grad_family beyond mom_solve's: doubles, then ints
-__host__ __device__ inline int grad_ldv(int p) { return (2 * p) | 1; }
-__host__ __device__ inline size_t grad_extra_doubles(int p, int K) {
-  return (size_t)p * grad_ldv(p) + 2 * (size_t)p * p + 2 * (size_t)p + (size_t)(K + 1) * p + 6 * (size_t)K + 1;
-}
-__host__ __device__ inline size_t grad_extra_ints(int p, int K) { return (size_t)(K + 1) + (size_t)p + (size_t)(K + 1) * p; }
+// LDS of grad_family: fam_score's arrays with three more rows of coefficients, the alpha-derivatives dqc, dvc, dwc
+constexpr int kGradRows = 6;
 
 template <int NT>
 __global__ __launch_bounds__(NT) void grad_family(const double* __restrict__ pool, int64_t pool_stride,
@@ -107,25 +56,9 @@ __global__ __launch_bounds__(NT) void grad_family(const double* __restrict__ poo
   const int cpos = F.child_pos[f];
   const int sl = p * p + p + 3 + nr;
   const int DA = p * p + p, CMU = DA + 1, CTH = DA + 2, CR = DA + 3;
-  // LDS: [W | dv] of mom_solve, then this kernel's arrays
-  double* __restrict__ W = grad_lds;
-  double* __restrict__ dv = grad_lds + m * ld;
-  double* __restrict__ A = grad_lds + mom_lds_doubles(m);   // [V_OO | I] -> [.. | j], mo x ldv
-  const int ldv = grad_ldv(p);
-  double* __restrict__ Mx = A + p * ldv;        // M = Cov(r) + e e'  (mo x mo)
-  double* __restrict__ Tx = Mx + p * p;         // j M
-  double* __restrict__ ev = Tx + p * p;         // e
-  double* __restrict__ ge = ev + p;             // j e
-  double* __restrict__ xm = ge + p;             // [a][i]: posterior mean of block a (or its constant value) at kept trait i
-  double* __restrict__ cz = xm + (K + 1) * p;   // c_a (K + 1)
-  double* __restrict__ vcs = cz + (K + 1);      // vc, wc, dqc, dvc, dwc (K each)
-  double* __restrict__ wcs = vcs + K;
-  double* __restrict__ dqs = wcs + K;
-  double* __restrict__ dvs = dqs + K;
-  double* __restrict__ dws = dvs + K;
-  int* __restrict__ ipos = reinterpret_cast<int*>(grad_lds + mom_lds_doubles(m) + ((grad_extra_doubles(p, K) + 1) & ~(size_t)1));
-  int* __restrict__ oidx = ipos + (K + 1);
-  int* __restrict__ vi = oidx + p;              // [a][i]: the variable's index in the cluster, -1: a constant
+  const FamLds L = fam_carve(grad_lds, m, p, K, kGradRows, 0);
+  const int ldv = fam_ldv(p);
+  double* cf = L.cf;   // rows of K: qc, vc, wc, dqc, dvc, dwc
   bool any_scope = cpos >= 0;
   for (int k = 0; k < np; ++k) any_scope |= F.parent_pos[(size_t)f * K + k] >= 0;
   // families the factor fill skips contribute nothing (and a root-prior family of a fixed root, which has no factor)
@@ -138,133 +71,34 @@ __global__ __launch_bounds__(NT) void grad_family(const double* __restrict__ poo
       for (int a = t; a < sl; a += NT) o[a] = 0.0;
       continue;
     }
-    const int64_t as = site0 + site, ps = M.per_site ? as : 0;
-    const double* __restrict__ R = M.R + ps * nr * p * p;
-    const double* __restrict__ mu = M.mu + ps * p;
-    const double* __restrict__ theta = (ou && M.theta) ? M.theta + ps * p : nullptr;
-    const double alpha = ou ? M.alpha[ps] : 0.0;
+    const int64_t as = site0 + site;
+    const LgSite S = lg_site(M, nr, p, as);
     int st = 0;
     if (any_scope) {
       const double* __restrict__ rec = pool + as * pool_stride + boff[c];
       double mant, quad;
       int expo;
-      st = mom_solve<NT, true>(rec, m, packed, fp, W, dv, t, mant, expo, quad);
+      st = mom_solve<NT, true>(rec, m, packed, fp, L.W, L.dv, t, mant, expo, quad);
     } else {
       __syncthreads();   // (the previous site's arrays have been read)
     }
-    if (st != 0) {   // not positive definite (the constant belief J = 0 included: no moments): the site's sums are NaN
+    // the cluster is not positive definite (the constant belief J = 0 included: no moments), or the family's variance is not
+    // (the fill made this cluster's g NaN): the site's sums are NaN
+    if (st == 0) {
+      for (int k = t; k < np; k += NT)
+        lg_coefs_dalpha(M.model, S.alpha, F.length[(size_t)f * K + k], F.gamma[(size_t)f * K + k], cf[3 * K + k], cf[4 * K + k],
+                        cf[5 * K + k]);
+      if (!fam_score_T<NT>(L, F, M, Sh, S, f, m, O, as, t)) st = 1;
+    }
+    if (st != 0) {
       for (int a = t; a < sl; a += NT) o[a] = NAN;
       if (t == 0) atomicMin(info + info0 + site, c + 1);
       continue;
-    }
-    // coefficients, positions, kept traits
-    for (int a = t; a <= np; a += NT) {
-      if (a == 0) {
-        cz[0] = 1.0;
-        ipos[0] = cpos;
-      } else {
-        const int k = a - 1;
-        double qc, vc, wc, dq, dvv, dw;
-        grad_coefs(M.model, alpha, F.length[(size_t)f * K + k], F.gamma[(size_t)f * K + k], qc, vc, wc, dq, dvv, dw);
-        cz[a] = -qc;
-        vcs[k] = vc; wcs[k] = wc; dqs[k] = dq; dvs[k] = dvv; dws[k] = dw;
-        ipos[a] = F.parent_pos[(size_t)f * K + k];
-      }
-    }
-    for (int tr = t; tr < p; tr += NT)
-      if ((O >> tr) & 1ull) oidx[grad_rank(O, tr)] = tr;
-    __syncthreads();
-    // where each block's kept traits sit in the cluster, and their posterior mean (or constant value)
-    for (int idx = t; idx < nn * mo; idx += NT) {
-      const int a = idx / mo, i = idx - a * mo, tr = oidx[i];
-      const int pa = ipos[a];
-      if (pa >= 0) {
-        const unsigned long long ma = a == 0 ? O : (F.parent_mask ? F.parent_mask[(size_t)f * K + a - 1] : full);
-        const int v = pa + grad_rank(ma, tr);
-        vi[a * p + i] = v;
-        xm[a * p + i] = W[v * ld + m];
-      } else {
-        vi[a * p + i] = -1;
-        xm[a * p + i] = a == 0 ? F.data[(as * F.n_rows + F.data_row[f]) * p + tr] : mu[tr];   // tip / fixed root
-      }
-    }
-    // V_OO and the identity
-    for (int idx = t; idx < mo * mo; idx += NT) {
-      const int j = idx / mo, i = idx - j * mo;
-      const int e = oidx[i] + oidx[j] * p;
-      double v = 0.0;
-      if (np == 0) {
-        v = R[(int64_t)F.color[(size_t)f * K] * p * p + e];
-      } else {
-        for (int k = 0; k < np; ++k) v = v + vcs[k] * R[(int64_t)F.color[(size_t)f * K + k] * p * p + e];
-      }
-      A[i * ldv + j] = v;
-      A[i * ldv + mo + j] = (i == j) ? 1.0 : 0.0;
-    }
-    __syncthreads();
-    // e = E[r]
-    for (int i = t; i < mo; i += NT) {
-      const int tr = oidx[i];
-      double e = 0.0;
-      for (int a = 0; a < nn; ++a) e = e + cz[a] * xm[a * p + i];
-      double w = 0.0;
-      if (np == 0) {
-        w = mu[tr];
-      } else if (theta) {
-        for (int k = 0; k < np; ++k) w = w + wcs[k] * theta[tr];
-      }
-      if (Sh.slot) w = w + lg_shift_d(Sh, F.gamma, f, K, np, tr, p, as);   // a shift of the mean on a parent edge
-      ev[i] = e - w;
-    }
-    __syncthreads();
-    // M = Cov(r) + e e'
-    for (int idx = t; idx < mo * mo; idx += NT) {
-      const int j = idx / mo, i = idx - j * mo;
-      double s = 0.0;
-      for (int a = 0; a < nn; ++a) {
-        const int va = vi[a * p + i];
-        if (va < 0) continue;
-        for (int b = 0; b < nn; ++b) {
-          const int vb = vi[b * p + j];
-          if (vb < 0) continue;
-          s = s + cz[a] * cz[b] * (va >= vb ? W[va * ld + vb] : W[vb * ld + va]);
-        }
-      }
-      Mx[i * mo + j] = s + ev[i] * ev[j];
-    }
-    if (!grad_invert<NT>(A, mo, ldv, t)) {   // a variance that is not positive definite: the fill made this cluster's g NaN
-      for (int a = t; a < sl; a += NT) o[a] = NAN;
-      if (t == 0) atomicMin(info + info0 + site, c + 1);
-      continue;
-    }
-    // j(i, k): the upper triangle mirrored, exactly symmetric (as the fill reads it)
-    auto jj = [&](int i, int k) -> double { return i <= k ? A[i * ldv + mo + k] : A[k * ldv + mo + i]; };
-    for (int idx = t; idx < mo * mo; idx += NT) {
-      const int k = idx / mo, i = idx - k * mo;
-      double s = 0.0;
-      for (int l = 0; l < mo; ++l) s = s + jj(i, l) * Mx[l * mo + k];
-      Tx[i * mo + k] = s;
-    }
-    for (int i = t; i < mo; i += NT) {
-      double s = 0.0;
-      for (int l = 0; l < mo; ++l) s = s + jj(i, l) * ev[l];
-      ge[i] = s;
     }
     for (int a = t; a < DA; a += NT) o[a] = 0.0;   // (the entries outside O)
-    __syncthreads();
-    // G_V = (j M j - j) / 2 embedded into p x p (upper triangle computed, mirrored), g_w = j e
-    for (int idx = t; idx < mo * mo; idx += NT) {
-      const int k = idx / mo, i = idx - k * mo;
-      if (i > k) continue;
-      double s = 0.0;
-      for (int l = 0; l < mo; ++l) s = s + Tx[i * mo + l] * jj(l, k);
-      const double g = 0.5 * (s - jj(i, k));
-      o[oidx[i] + oidx[k] * p] = g;
-      o[oidx[k] + oidx[i] * p] = g;
-      Mx[i * mo + k] = g;   // (M has been consumed: T = j M is complete) -- kept for the alpha term
-      Mx[k * mo + i] = g;
-    }
-    for (int i = t; i < mo; i += NT) o[p * p + oidx[i]] = ge[i];
+    // G_V embedded into p x p, and kept in Mx for the alpha term; g_w = j e
+    fam_score_gv<NT>(L, p, mo, o, t);
+    for (int i = t; i < mo; i += NT) o[p * p + L.oidx[i]] = L.ge[i];
     __syncthreads();
     if (t == 0) {
       double cmu = 0.0, cth = 0.0, da = 0.0;
@@ -272,30 +106,30 @@ __global__ __launch_bounds__(NT) void grad_family(const double* __restrict__ poo
         cmu = 1.0;
       } else {
         for (int k = 0; k < np; ++k) {
-          if (ipos[k + 1] < 0) cmu = cmu - cz[k + 1];   // qc_k: the parent is the fixed root
-          cth = cth + wcs[k];
+          if (L.ipos[k + 1] < 0) cmu = cmu - fam_c(cf, k + 1);   // qc_k: the parent is the fixed root
+          cth = cth + cf[2 * K + k];
         }
         if (ou) {
           for (int k = 0; k < np; ++k) {
-            const double* __restrict__ Rk = R + (int64_t)F.color[(size_t)f * K + k] * p * p;
+            const double* __restrict__ Rk = S.R + (int64_t)F.color[(size_t)f * K + k] * p * p;
             double trGR = 0.0, thg = 0.0, gq = 0.0;
             for (int i = 0; i < mo; ++i) {
               for (int l = 0; l < mo; ++l) {
-                trGR = trGR + Mx[i * mo + l] * Rk[oidx[l] + oidx[i] * p];
+                trGR = trGR + L.Mx[i * mo + l] * Rk[L.oidx[l] + L.oidx[i] * p];
                 // E[r x_k'](i, l) = sum_a c_a Sigma(a_i, k_l) + e_i m_k(l)
-                double ex = ev[i] * xm[(k + 1) * p + l];
-                const int vk = vi[(k + 1) * p + l];
+                double ex = L.ev[i] * L.xm[(k + 1) * p + l];
+                const int vk = L.vi[(k + 1) * p + l];
                 if (vk >= 0) {
                   for (int a = 0; a < nn; ++a) {
-                    const int va = vi[a * p + i];
-                    if (va >= 0) ex = ex + cz[a] * (va >= vk ? W[va * ld + vk] : W[vk * ld + va]);
+                    const int va = L.vi[a * p + i];
+                    if (va >= 0) ex = ex + fam_c(cf, a) * (va >= vk ? L.W[va * ld + vk] : L.W[vk * ld + va]);
                   }
                 }
-                gq = gq + jj(l, i) * ex;
+                gq = gq + fam_j(L.A, ldv, mo, l, i) * ex;
               }
-              if (theta) thg = thg + theta[oidx[i]] * ge[i];
+              if (S.theta) thg = thg + S.theta[L.oidx[i]] * L.ge[i];
             }
-            da = da + dvs[k] * trGR + dws[k] * thg + dqs[k] * gq;
+            da = da + cf[4 * K + k] * trGR + cf[5 * K + k] * thg + cf[3 * K + k] * gq;
           }
         }
       }
@@ -309,7 +143,7 @@ __global__ __launch_bounds__(NT) void grad_family(const double* __restrict__ poo
         cr = F.color[(size_t)f * K] == r ? 1.0 : 0.0;
       } else {
         for (int k = 0; k < np; ++k)
-          if (F.color[(size_t)f * K + k] == r) cr = cr + vcs[k];
+          if (F.color[(size_t)f * K + k] == r) cr = cr + cf[K + k];
       }
       o[CR + r] = cr;
     }
@@ -402,27 +236,13 @@ extern "C" int pgbp_lg_gradient(pgbp_engine* e, int32_t site_begin, int32_t site
   const Plan& pl = *v.plan;
   const LgStatic& F = *v.lg;
   const LgShifts Sh = engine_lg_shifts(e);
-  const int nc = pl.n_clusters, p = F.p, K = F.K, nr = F.n_rates;
-  // which cluster each family sits in (the CSR of pgbp_lg_setup back from the device: a word per family)
-  std::vector<int32_t> off(nc + 1);
-  hipError_t herr = hipMemcpy(off.data(), F.cl_off, sizeof(int32_t) * (nc + 1), hipMemcpyDeviceToHost);
-  const int nf = herr == hipSuccess ? off[nc] : 0;
-  std::vector<int32_t> cfam(std::max(nf, 1));
-  if (herr == hipSuccess && nf > 0) herr = hipMemcpy(cfam.data(), F.cl_fam, sizeof(int32_t) * nf, hipMemcpyDeviceToHost);
-  if (herr != hipSuccess) return engine_fail(e, PGBP_ERR_HIP, std::string("pgbp_lg_gradient (family table): ") + hipGetErrorString(herr));
-  std::vector<int32_t> fcl(std::max(nf, 1), 0);
-  int max_m = 1;
-  for (int c = 0; c < nc; ++c)
-    for (int q = off[c]; q < off[c + 1]; ++q) {
-      fcl[cfam[q]] = c;
-      if (pl.dims[c] > kLdsMaxDim)
-        return engine_fail(e, PGBP_ERR_INVALID, "pgbp_lg_gradient: family " + std::to_string(cfam[q]) + " (cluster " +
-                                                    std::to_string(c) + "): the cluster has more than " +
-                                                    std::to_string(kLdsMaxDim) + " variables");
-      max_m = std::max(max_m, (int)pl.dims[c]);
-    }
-  const size_t lds_bytes = sizeof(double) * (mom_lds_doubles(max_m) + ((grad_extra_doubles(p, K) + 1) & ~(size_t)1)) +
-                           sizeof(int) * grad_extra_ints(p, K);
+  const int p = F.p, K = F.K, nr = F.n_rates;
+  std::vector<int32_t> fcl;   // which cluster each family sits in
+  int max_m = 0;
+  rc = lg_family_clusters(e, "pgbp_lg_gradient", v, true, &fcl, &max_m);
+  if (rc) return rc;
+  const int nf = (int)fcl.size();
+  const size_t lds_bytes = fam_score_lds_bytes(max_m, p, K, kGradRows, 0);
   if (lds_bytes > 160 * 1024)
     return engine_fail(e, PGBP_ERR_INVALID, "pgbp_lg_gradient: a cluster of " + std::to_string(max_m) + " variables with " +
                                                 std::to_string(p) + " traits needs " + std::to_string(lds_bytes) +
@@ -455,7 +275,7 @@ extern "C" int pgbp_lg_gradient(pgbp_engine* e, int32_t site_begin, int32_t site
   std::vector<double> out((size_t)ns * n_ent);
   DevBuf<int32_t> d_fcl, d_info;
   DevBuf<double> d_slots, d_part, d_out;
-  herr = (hipError_t)d_fcl.alloc(nf);
+  hipError_t herr = (hipError_t)d_fcl.alloc(nf);
   if (herr == hipSuccess) herr = (hipError_t)d_slots.alloc((size_t)per_site * chunk);
   if (herr == hipSuccess) herr = (hipError_t)d_part.alloc((size_t)chunk * nfb * n_ent);
   if (herr == hipSuccess) herr = (hipError_t)d_out.alloc((size_t)ns * n_ent);

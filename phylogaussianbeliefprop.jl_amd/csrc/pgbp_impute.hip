@@ -1,7 +1,8 @@
 // Posterior moments of the MISSING values of every tip from calibrated beliefs (pgbp_lg_impute of include/pgbp.h): the
 // complement of pgbp_loo.hip -- there a tip's own data is divided out of its cluster's belief, here nothing is left out.
 //
-// A tip's factor is N(x; u + w, V) in the notation of pgbp_lgfill.hip / pgbp_loo.hip: u = sum_k qc_k x_k the parents'
+// A tip's factor is N(x; u + w, V) in the notation of pgbp_lgfill.hip / pgbp_loo.hip (coefficients, block table, Cov(u_Z), the
+// Cholesky and the staging of a packed record: pgbp_fam_dev.hpp): u = sum_k qc_k x_k the parents'
 // contribution (a fixed-root parent: its constant qc_k mu), w = sum_k wc_k theta, V = sum_k vc_k R[colour_k] (p x p).  With
 // O = child_mask[f] the observed traits, M its complement, the PREDICTED traits are P = M intersected with the scope of every
 // cluster parent (a missing trait a parent does not hold is in no belief of the graph: NaN), Z = O u P.  Given the parents the
@@ -30,38 +31,12 @@
 
 #include "pgbp_bs16.hpp"
 #include "pgbp_devmem.hpp"
+#include "pgbp_fam_dev.hpp"
 #include "pgbp_kernels.hpp"
-#include "pgbp_mom_dev.hpp"
-#include "pgbp_shift_dev.hpp"
 
 namespace pgbp {
 
 extern __shared__ double imp_lds[];
-
-__device__ __forceinline__ int imp_rank(unsigned long long mask, int t) { return __popcll(mask & ((1ull << t) - 1ull)); }
-
-// Left-looking Cholesky of the lower triangle of the leading n x n block of A (row stride ld) in LDS by NT threads: L(i, j),
-// i > j, in place; the diagonal of L in dl (A's diagonal is left as it was).  false when a pivot is not positive (uniform:
-// every thread computes the same pivot).  (loo_cholesky of pgbp_loo.hip without the pivot floor: no matrix here is formed
-// by cancellation against the beliefs.)
-template <int NT>
-__device__ __forceinline__ bool imp_cholesky(double* __restrict__ A, int n, int ld, double* __restrict__ dl, int t) {
-#pragma clang fp contract(off)
-  for (int j = 0; j < n; ++j) {
-    double d = A[j * ld + j];
-    for (int k = 0; k < j; ++k) d = fma(-A[j * ld + k], A[j * ld + k], d);
-    if (!(d > 0.0)) return false;
-    const double l = sqrt(d);
-    for (int i = j + 1 + t; i < n; i += NT) {
-      double s = A[i * ld + j];
-      for (int k = 0; k < j; ++k) s = fma(-A[i * ld + k], A[j * ld + k], s);
-      A[i * ld + j] = s / l;
-    }
-    if (t == 0) dl[j] = l;
-    __syncthreads();
-  }
-  return true;
-}
 
 // LDS of impute_family beyond mom_solve's: doubles (five p x p blocks: V_ZZ, Cov(u_Z), Y / B', C, the copy of C / G; six
 // p-vectors; qc, vc, wc; the parents' means), then ints
@@ -107,23 +82,19 @@ __global__ __launch_bounds__(NT) void impute_family(const double* __restrict__ p
   double* __restrict__ rv = yv + p;                         // y_O - w_O - E[u_O]
   double* __restrict__ dlV = rv + p;                        // diagonal of V_OO's factor
   double* __restrict__ dlC = dlV + p;                       // diagonal of C's factor
-  double* __restrict__ qcs = dlC + p;                       // qc, vc, wc (K each)
-  double* __restrict__ vcs = qcs + K;
-  double* __restrict__ wcs = vcs + K;
-  double* __restrict__ xm = wcs + K;                        // [k][i]: posterior mean of parent k (or its constant) at trait Z_i
+  double* __restrict__ cf = dlC + p;                        // rows of K: qc, vc, wc
+  double* __restrict__ xm = cf + 3 * K;                     // [k][i]: posterior mean of parent k (or its constant) at trait Z_i
   int* __restrict__ ipos = reinterpret_cast<int*>(imp_lds + mom_lds_doubles(m) + ((impute_extra_doubles(p, K) + 1) & ~(size_t)1));
   int* __restrict__ zidx = ipos + K;                        // Z: the observed traits in order, then the predicted ones
   int* __restrict__ vi = zidx + p;                          // [k][i]: the variable's index in the cluster, -1: a constant
-  // a packed (BS16) record is first copied here in the plain layout, the upper triangle mirrored, as loo_family does: read this
-  // way the two layouts give the same bytes
+  // a packed (BS16) record is first copied here in the plain layout (fam_stage_plain)
   double* __restrict__ stage = imp_lds + mom_lds_doubles(m) + ((impute_extra_doubles(p, K) + 1) & ~(size_t)1) +
                                ((impute_extra_ints(p, K) + 1) >> 1);
   bool any_scope = false;
   for (int k = 0; k < np; ++k) any_scope |= F.parent_pos[(size_t)f * K + k] >= 0;
   const bool packed = bs && bs16::applies(m, fp);
-  const bool ou = M.model == PGBP_LG_OU;
   // (every condition of an early `continue` below is the same in all threads of the workgroup: P and any_scope belong to the
-  // family, mom_solve and imp_cholesky return what every thread computed from the same LDS words)
+  // family, mom_solve and lds_cholesky return what every thread computed from the same LDS words)
   for (int site = blockIdx.y; site < n_sites; site += gridDim.y) {
     const int64_t slot = (int64_t)site * n_fam + ti;
     double* __restrict__ om = mean ? mean + slot * p : nullptr;
@@ -134,22 +105,15 @@ __global__ __launch_bounds__(NT) void impute_family(const double* __restrict__ p
       if (t == 0) info[slot] = -1;
       continue;
     }
-    const int64_t as = site0 + site, ps = M.per_site ? as : 0;
-    const double* __restrict__ R = M.R + ps * nr * p * p;
-    const double* __restrict__ mu = M.mu + ps * p;
-    const double* __restrict__ theta = (ou && M.theta) ? M.theta + ps * p : nullptr;
-    const double alpha = ou ? M.alpha[ps] : 0.0;
+    const int64_t as = site0 + site;
+    const LgSite S = lg_site(M, nr, p, as);
     int st = 0;
     if (any_scope) {
       const double* __restrict__ rec = pool + as * pool_stride + boff[c];
       double mant, quad;
       int expo;
-      if (packed) {   // (mom_solve's first barrier publishes the copy; its loads end behind a barrier as well)
-        for (int idx = t; idx < m * m; idx += NT) {
-          const int j = idx / m, i = idx - j * m;
-          stage[idx] = rec[bs16::J_off(m, i < j ? i : j, i < j ? j : i, fp)];
-        }
-        for (int i = t; i < m; i += NT) stage[m * m + i] = rec[bs16::h_off(m, i, fp)];
+      if (packed) {
+        fam_stage_plain<NT>(rec, m, fp, stage, t);
         rec = stage;
       }
       st = mom_solve<NT, true>(rec, m, false, fp, W, dv, t, mant, expo, quad);
@@ -164,57 +128,34 @@ __global__ __launch_bounds__(NT) void impute_family(const double* __restrict__ p
     }
     // coefficients, positions, the traits of Z
     for (int k = t; k < np; k += NT) {
-      double qc, vc, wc;
-      const double tl = F.length[(size_t)f * K + k], gam = F.gamma[(size_t)f * K + k];
-      if (ou) {   // (lg_coefs of pgbp_lgfill.hip)
-        const double a = exp(-alpha * tl);
-        qc = gam * a;
-        vc = gam * gam * (1.0 - a * a);
-        wc = gam * (1.0 - a);
-      } else {
-        qc = gam;
-        vc = gam * gam * tl;
-        wc = 0.0;
-      }
-      qcs[k] = qc; vcs[k] = vc; wcs[k] = wc;
+      lg_coefs<false>(M.model, S.alpha, F.length[(size_t)f * K + k], F.gamma[(size_t)f * K + k], cf[k], cf[K + k], cf[2 * K + k]);
       ipos[k] = F.parent_pos[(size_t)f * K + k];
     }
     for (int tr = t; tr < p; tr += NT) {
-      if ((O >> tr) & 1ull) zidx[imp_rank(O, tr)] = tr;
-      else if ((P >> tr) & 1ull) zidx[no + imp_rank(P, tr)] = tr;
+      if ((O >> tr) & 1ull) zidx[mask_rank(O, tr)] = tr;
+      else if ((P >> tr) & 1ull) zidx[no + mask_rank(P, tr)] = tr;
     }
     __syncthreads();
     // where each cluster parent's traits of Z sit in the cluster, and their posterior mean (or the fixed root's constant)
     // (P is not empty: every cluster parent holds a trait, its parent_pos is not negative; a negative one is the fixed root)
-    for (int idx = t; idx < np * nz; idx += NT) {
-      const int k = idx / nz, i = idx - k * nz, tr = zidx[i];
-      const int pk = ipos[k];
-      if (pk >= 0) {
-        const int v = pk + imp_rank(F.parent_mask[(size_t)f * K + k], tr);
-        vi[k * p + i] = v;
-        xm[k * p + i] = W[v * ld + m];
-      } else {
-        vi[k * p + i] = -1;
-        xm[k * p + i] = mu[tr];
-      }
-    }
+    fam_blocks<NT>(F, f, as, S.mu, 0, np, O, ipos, zidx, nz, W, ld, m, vi, xm, t);
     for (int i = t; i < no; i += NT) yv[i] = F.data[(as * F.n_rows + row) * p + zidx[i]];
     // V_ZZ
     for (int idx = t; idx < nz * nz; idx += NT) {
       const int i = idx / nz, j = idx - i * nz;
       const int e = zidx[i] + zidx[j] * p;
       double v = 0.0;
-      for (int k = 0; k < np; ++k) v = v + vcs[k] * R[(int64_t)F.color[(size_t)f * K + k] * p * p + e];
+      for (int k = 0; k < np; ++k) v = v + cf[K + k] * S.R[(int64_t)F.color[(size_t)f * K + k] * p * p + e];
       Vz[i * nz + j] = v;
     }
     __syncthreads();
     // E[u_Z], w_Z and the residual of the observed traits
     for (int i = t; i < nz; i += NT) {
       double e = 0.0;
-      for (int k = 0; k < np; ++k) e = e + qcs[k] * xm[k * p + i];
+      for (int k = 0; k < np; ++k) e = e + cf[k] * xm[k * p + i];
       double w = 0.0;
-      if (theta)
-        for (int k = 0; k < np; ++k) w = w + wcs[k] * theta[zidx[i]];
+      if (S.theta)
+        for (int k = 0; k < np; ++k) w = w + cf[2 * K + k] * S.theta[zidx[i]];
       if (Sh.slot) w = w + lg_shift_d(Sh, F.gamma, f, K, np, zidx[i], p, as);   // a shift of the mean: the full p-vector of d
       eu[i] = e;
       wv[i] = w;
@@ -224,21 +165,12 @@ __global__ __launch_bounds__(NT) void impute_family(const double* __restrict__ p
     for (int idx = t; idx < nz * nz; idx += NT) {
       const int i = idx / nz, j = idx - i * nz;
       if (j > i) continue;
-      double s = 0.0;
-      for (int a = 0; a < np; ++a) {
-        const int va = vi[a * p + i];
-        if (va < 0) continue;
-        for (int b = 0; b < np; ++b) {
-          const int vb = vi[b * p + j];
-          if (vb < 0) continue;
-          s = s + qcs[a] * qcs[b] * (va >= vb ? W[va * ld + vb] : W[vb * ld + va]);
-        }
-      }
+      const double s = fam_cov(W, ld, vi, p, [&](int k) -> double { return cf[k]; }, np, i, j);
       Cu[i * nz + j] = s;
       Cu[j * nz + i] = s;
     }
     __syncthreads();
-    bool ok = imp_cholesky<NT>(Vz, no, nz, dlV, t);
+    bool ok = lds_cholesky<NT>(Vz, no, nz, dlV, nullptr, t);
     if (ok) {
       // Y = L^-1 V_OP: thread j its own column, rows in order
       for (int j = t; j < nq; j += NT)
@@ -259,7 +191,7 @@ __global__ __launch_bounds__(NT) void impute_family(const double* __restrict__ p
         Dm[a * nq + b] = s;
       }
       __syncthreads();
-      ok = imp_cholesky<NT>(Dm, nq, nq, dlC, t);   // (nq >= 1: it ends behind a barrier)
+      ok = lds_cholesky<NT>(Dm, nq, nq, dlC, nullptr, t);   // (nq >= 1: it ends behind a barrier)
     }
     if (!ok) {   // V_OO or the conditional variance is not positive definite
       if (om) for (int a = t; a < p; a += NT) om[a] = NAN;
@@ -317,25 +249,21 @@ __global__ __launch_bounds__(NT) void impute_family(const double* __restrict__ p
 static std::atomic<int64_t> g_impute_limit{(int64_t)32 << 20};
 
 // the listed families of the table given to pgbp_lg_setup (tip families with a missing trait), in table order, the cluster of
-// each and its mask P (fcl: the cluster of every family of the table)
-static int impute_list(pgbp_engine* e, const EngineView& v, const char* fn, std::vector<int32_t>& fams, std::vector<int32_t>& cls,
-                       std::vector<unsigned long long>& pred, std::vector<int32_t>& fcl) {
-  const Plan& pl = *v.plan;
+// each and its mask P
+// (fcl, check_dims, max_m: lg_family_clusters -- the count and the list are served whatever the clusters' sizes, the sweep is not)
+static int impute_list(pgbp_engine* e, const EngineView& v, const char* fn, bool check_dims, std::vector<int32_t>& fams,
+                       std::vector<int32_t>& cls, std::vector<unsigned long long>& pred, std::vector<int32_t>& fcl, int* max_m) {
   const LgStatic& F = *v.lg;
-  const int nc = pl.n_clusters, K = F.K;
-  std::vector<int32_t> off(nc + 1);
-  hipError_t herr = hipMemcpy(off.data(), F.cl_off, sizeof(int32_t) * (nc + 1), hipMemcpyDeviceToHost);
-  const int nf = herr == hipSuccess ? off[nc] : 0;
+  const int K = F.K;
+  const int rc = lg_family_clusters(e, fn, v, check_dims, &fcl, max_m);
+  if (rc) return rc;
+  const int nf = (int)fcl.size();
   const size_t n1 = (size_t)std::max(nf, 1);
-  std::vector<int32_t> cfam(n1), cpos(n1), drow(n1), npar(n1), ppos(n1 * K);
+  std::vector<int32_t> cpos(n1), drow(n1), npar(n1), ppos(n1 * K);
   std::vector<unsigned long long> cmask, pmask;
-  if (herr == hipSuccess && nf > 0) herr = hipMemcpy(cfam.data(), F.cl_fam, sizeof(int32_t) * nf, hipMemcpyDeviceToHost);
-  fcl.assign(nf, 0);
-  if (herr == hipSuccess)
-    for (int c = 0; c < nc; ++c)
-      for (int q = off[c]; q < off[c + 1]; ++q) fcl[cfam[q]] = c;
+  hipError_t herr = hipSuccess;
   const bool masks = F.child_mask && F.parent_mask;   // complete data: nothing is listed
-  if (herr == hipSuccess && nf > 0 && masks) {
+  if (nf > 0 && masks) {
     cmask.resize(nf);
     pmask.resize((size_t)nf * K);
     herr = hipMemcpy(cpos.data(), F.child_pos, sizeof(int32_t) * nf, hipMemcpyDeviceToHost);
@@ -368,12 +296,13 @@ static int impute_list(pgbp_engine* e, const EngineView& v, const char* fn, std:
 }
 
 static int impute_table(pgbp_engine* e, const char* fn, EngineView* v, std::vector<int32_t>& fams, std::vector<int32_t>& cls,
-                        std::vector<unsigned long long>& pred, std::vector<int32_t>& fcl) {
+                        std::vector<unsigned long long>& pred, std::vector<int32_t>& fcl, bool check_dims = false,
+                        int* max_m = nullptr) {
   if (!engine_peek(e).lg_ready)
     return engine_fail(e, PGBP_ERR_STATE, std::string(fn) + ": no family table (call pgbp_lg_setup first)");
   const int rc = engine_view(e, v);
   if (rc) return rc;
-  return impute_list(e, *v, fn, fams, cls, pred, fcl);
+  return impute_list(e, *v, fn, check_dims, fams, cls, pred, fcl, max_m);
 }
 
 }  // namespace pgbp
@@ -419,22 +348,15 @@ extern "C" int pgbp_lg_impute(pgbp_engine* e, int32_t site_begin, int32_t site_e
   EngineView v;
   std::vector<int32_t> fams, cls, fcl;
   std::vector<unsigned long long> pred;
-  int rc = impute_table(e, "pgbp_lg_impute", &v, fams, cls, pred, fcl);
+  // the limits are pgbp_lg_loo's, over the clusters of ALL families of the table: an engine serves every sweep or none
+  int max_m = 0;
+  int rc = impute_table(e, "pgbp_lg_impute", &v, fams, cls, pred, fcl, true, &max_m);
   if (rc) return rc;
   // (as in pgbp_lg_loo, what follows runs on the caller's current device)
   const Plan& pl = *v.plan;
   const LgStatic& F = *v.lg;
   const LgShifts Sh = engine_lg_shifts(e);
   const int p = F.p, K = F.K, n = (int)fams.size();
-  // the limits are pgbp_lg_loo's, over the clusters of ALL families of the table: an engine serves every sweep or none
-  int max_m = 0;
-  for (int f = 0; f < (int)fcl.size(); ++f) {
-    const int c = fcl[f];
-    if (pl.dims[c] > kLdsMaxDim)
-      return engine_fail(e, PGBP_ERR_INVALID, "pgbp_lg_impute: family " + std::to_string(f) + " (cluster " + std::to_string(c) +
-                                                  "): the cluster has more than " + std::to_string(kLdsMaxDim) + " variables");
-    max_m = std::max(max_m, (int)pl.dims[c]);
-  }
   size_t stage = 0;   // a packed record's plain copy
   for (int i = 0; i < n && v.bs16; ++i) {
     const size_t m = (size_t)pl.dims[cls[i]];

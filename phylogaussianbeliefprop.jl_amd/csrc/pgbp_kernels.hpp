@@ -309,5 +309,11 @@ const Plan* engine_plan(const pgbp_engine* e);
 bool engine_lg_params(const pgbp_engine* e, LgParams* out);
 // the shifts of pgbp_lg_set_shifts (device pointers); slot == null: none set
 LgShifts engine_lg_shifts(const pgbp_engine* e);
+// Which cluster each family of pgbp_lg_setup's table sits in: the table's CSR (LgStatic::cl_off, cl_fam) back from the device, a
+// word per family, inverted to fcl[f] (one entry per family).  max_m (may be null): the largest dimension among the clusters
+// that hold a family, 0 without families.  check_dims: a family in a cluster of more than kLdsMaxDim variables fails the call,
+// "<fn>: family F (cluster C): the cluster has more than 128 variables".  Returns PGBP_OK or engine_fail's code.
+int lg_family_clusters(pgbp_engine* e, const char* fn, const EngineView& v, bool check_dims, std::vector<int32_t>* fcl,
+                       int* max_m);
 
 }  // namespace pgbp

@@ -5,7 +5,7 @@
 //   X_child | parents ~ N( sum_k q_k X_k + w , V ),   q_k = qc_k * I,  V = sum_k vc_k R[color_k],  w = sum_k wc_k theta
 //     Brownian motion (homogeneous / heterogeneous: src/evomodels/homogeneousbrownianmotion.jl:222-351,
 //       heterogeneousmodels.jl:110-150):        qc = gamma, vc = gamma^2 t, wc = 0
-//     Ornstein-Uhlenbeck (homogeneousornsteinuhlenbeck.jl:51-66), a = exp(-alpha t):
+//     Ornstein-Uhlenbeck (homogeneousornsteinuhlenbeck.jl:51-66), a = e^(-alpha t):
 //                                                qc = gamma a, vc = gamma^2 (1 - a^2), wc = gamma (1 - a)
 //     hybrid node: the weighted combination of its parent edges (evomodels.jl:314-330); K = 0: root prior
 //       (factor_root, evomodels.jl:377-396): V = R[color], w = mu.
@@ -19,7 +19,12 @@
 // what absorbleaf! and the partial-scope marginalisation of assignfactors! (src/beliefs.jl:829-857) leave.
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
+#include <string>
+#include <vector>
+
 #include "pgbp_bs16.hpp"
+#include "pgbp_fam_dev.hpp"
 #include "pgbp_kernels.hpp"
 
 namespace pgbp {
@@ -27,20 +32,6 @@ namespace pgbp {
 #define PGBP_LOG2PI 1.8378770664093454835606594728112
 
 extern __shared__ double lg_lds[];
-
-// edge coefficients of parent edge (length t, inheritance gam) under the model
-__device__ __forceinline__ void lg_coefs(int model, double alpha, double t, double gam, double& qc, double& vc, double& wc) {
-  if (model == PGBP_LG_OU) {
-    const double a = exp(-alpha * t);
-    qc = gam * a;
-    vc = gam * gam * (1.0 - a * a);
-    wc = gam * (1.0 - a);
-  } else {
-    qc = gam;
-    vc = gam * gam * t;
-    wc = 0.0;
-  }
-}
 
 // Gauss-Jordan on the p x nc system [V | I | z] (row stride ld) in LDS by one wavefront: the right part becomes
 // [V^-1 | V^-1 z]; false when a pivot is not positive.
@@ -68,11 +59,6 @@ __device__ __forceinline__ bool lg_gauss_jordan(double* W, int p, int nc, int ld
   }
   logdet = log(mant) + (double)expo * 0.69314718055994530941723212145818;
   return true;
-}
-
-// rank of trait t inside a node's block = number of in-scope traits before it
-__device__ __forceinline__ int lg_rank(unsigned long long mask, int t) {
-  return __popcll(mask & ((1ull << t) - 1ull));
 }
 
 __global__ __launch_bounds__(64) void lg_fill_kernel(LgStatic F, LgParams M, double* __restrict__ pool, int64_t pool_stride,
@@ -120,13 +106,13 @@ __global__ __launch_bounds__(64) void lg_fill_kernel(LgStatic F, LgParams M, dou
         ipos[0] = cpos;
       } else {
         double qc, vc, wc;
-        lg_coefs(M.model, alpha, F.length[(int64_t)f * K + lane - 1], F.gamma[(int64_t)f * K + lane - 1], qc, vc, wc);
+        lg_coefs<true>(M.model, alpha, F.length[(int64_t)f * K + lane - 1], F.gamma[(int64_t)f * K + lane - 1], qc, vc, wc);
         cz[lane] = -qc;
         ipos[lane] = F.parent_pos[(int64_t)f * K + lane - 1];
       }
     }
     for (int t = lane; t < p; t += kWave)
-      if ((O >> t) & 1ull) oidx[lg_rank(O, t)] = t;
+      if ((O >> t) & 1ull) oidx[mask_rank(O, t)] = t;
     __syncthreads();
     // V_OO, identity, z_O
     for (int idx = lane; idx < mo * mo; idx += kWave) {
@@ -138,7 +124,7 @@ __global__ __launch_bounds__(64) void lg_fill_kernel(LgStatic F, LgParams M, dou
       } else {
         for (int k = 0; k < np; ++k) {
           double qc, vc, wc;
-          lg_coefs(M.model, alpha, F.length[(int64_t)f * K + k], F.gamma[(int64_t)f * K + k], qc, vc, wc);
+          lg_coefs<true>(M.model, alpha, F.length[(int64_t)f * K + k], F.gamma[(int64_t)f * K + k], qc, vc, wc);
           v += vc * R[(int64_t)F.color[(int64_t)f * K + k] * p * p + e];
         }
       }
@@ -154,7 +140,7 @@ __global__ __launch_bounds__(64) void lg_fill_kernel(LgStatic F, LgParams M, dou
         z = 0.0;
         for (int k = 0; k < np; ++k) {
           double qc, vc, wc;
-          lg_coefs(M.model, alpha, F.length[(int64_t)f * K + k], F.gamma[(int64_t)f * K + k], qc, vc, wc);
+          lg_coefs<true>(M.model, alpha, F.length[(int64_t)f * K + k], F.gamma[(int64_t)f * K + k], qc, vc, wc);
           if (theta) z += wc * theta[t];
           if (F.parent_pos[(int64_t)f * K + k] < 0) z += qc * mu[t];   // - c_k mu, c_k = -q_k: fixed root
         }
@@ -183,13 +169,13 @@ __global__ __launch_bounds__(64) void lg_fill_kernel(LgStatic F, LgParams M, dou
       const unsigned long long ma = (a == 0 || !F.parent_mask) ? (a == 0 ? O : full) : F.parent_mask[(int64_t)f * K + a - 1];
       const unsigned long long mb = (b == 0 || !F.parent_mask) ? (b == 0 ? O : full) : F.parent_mask[(int64_t)f * K + b - 1];
       const double jv = (i <= k) ? W[i * ld + mo + k] : W[k * ld + mo + i];
-      rec[(pa + lg_rank(ma, oidx[i])) + (int64_t)(pb + lg_rank(mb, oidx[k])) * m] += cz[a] * cz[b] * jv;
+      rec[(pa + mask_rank(ma, oidx[i])) + (int64_t)(pb + mask_rank(mb, oidx[k])) * m] += cz[a] * cz[b] * jv;
     }
     for (int idx = lane; idx < nn * mo; idx += kWave) {
       const int a = idx / mo, i = idx - a * mo;
       if (ipos[a] < 0) continue;
       const unsigned long long ma = (a == 0 || !F.parent_mask) ? (a == 0 ? O : full) : F.parent_mask[(int64_t)f * K + a - 1];
-      rec[m * m + ipos[a] + lg_rank(ma, oidx[i])] += cz[a] * W[i * ld + 2 * mo];
+      rec[m * m + ipos[a] + mask_rank(ma, oidx[i])] += cz[a] * W[i * ld + 2 * mo];
     }
     if (lane == 0) rec[m * m + m] += -0.5 * ((double)mo * PGBP_LOG2PI + logdet + q);
   }
@@ -253,7 +239,7 @@ __global__ __launch_bounds__(256) void lg_fill_uni_sm_kernel(LgStatic F, LgParam
       } else {
         for (int k = 0; k < np; ++k) {
           double qc, vc, wc;
-          lg_coefs(M.model, alpha, F.length[(int64_t)f * K + k], F.gamma[(int64_t)f * K + k], qc, vc, wc);
+          lg_coefs<true>(M.model, alpha, F.length[(int64_t)f * K + k], F.gamma[(int64_t)f * K + k], qc, vc, wc);
           V += vc * R[F.color[(int64_t)f * K + k]];
           z += wc * theta;
           if (F.parent_pos[(int64_t)f * K + k] < 0) z += qc * mu;
@@ -267,7 +253,7 @@ __global__ __launch_bounds__(256) void lg_fill_uni_sm_kernel(LgStatic F, LgParam
         if (k == 2) return qk2;
         if (k == 3) return qk3;
         double qc, vc, wc;
-        lg_coefs(M.model, alpha, F.length[(int64_t)f * K + k], F.gamma[(int64_t)f * K + k], qc, vc, wc);
+        lg_coefs<true>(M.model, alpha, F.length[(int64_t)f * K + k], F.gamma[(int64_t)f * K + k], qc, vc, wc);
         return qc;
       };
       const double j = 1.0 / V;
@@ -331,7 +317,7 @@ __global__ __launch_bounds__(256) void lg_fill_uni_simple_sm_kernel(LgStatic F, 
       z = mu;
     } else {
       double qc, vc, wc;
-      lg_coefs(M.model, alpha, f.length, f.gamma, qc, vc, wc);
+      lg_coefs<true>(M.model, alpha, f.length, f.gamma, qc, vc, wc);
       V += vc * R[f.color];
       z += wc * theta;
       if (f.ppos < 0) z += qc * mu;
@@ -425,6 +411,32 @@ void launch_lg_fill_uni_sm(const LgStatic& F, const LgParams& M, double* pool_sm
   }
   hipLaunchKernelGGL(lg_fill_uni_sm_kernel, dim3(gx, (n_sites + bs - 1) / bs), dim3(bs), 0, st, F, M, pool_sm, fpool_sm,
                      d_poff, d_dim, n_clusters, n_sites);
+}
+
+int lg_family_clusters(pgbp_engine* e, const char* fn, const EngineView& v, bool check_dims, std::vector<int32_t>* fcl,
+                       int* max_m) {
+  const Plan& pl = *v.plan;
+  const LgStatic& F = *v.lg;
+  const int nc = pl.n_clusters;
+  std::vector<int32_t> off(nc + 1);
+  hipError_t herr = hipMemcpy(off.data(), F.cl_off, sizeof(int32_t) * (nc + 1), hipMemcpyDeviceToHost);
+  const int nf = herr == hipSuccess ? off[nc] : 0;
+  std::vector<int32_t> cfam(nf);
+  if (herr == hipSuccess && nf > 0) herr = hipMemcpy(cfam.data(), F.cl_fam, sizeof(int32_t) * nf, hipMemcpyDeviceToHost);
+  if (herr != hipSuccess) return engine_fail(e, PGBP_ERR_HIP, std::string(fn) + " (family table): " + hipGetErrorString(herr));
+  fcl->assign(nf, 0);
+  int mm = 0;
+  for (int c = 0; c < nc; ++c)
+    for (int q = off[c]; q < off[c + 1]; ++q) {
+      (*fcl)[cfam[q]] = c;
+      if (check_dims && pl.dims[c] > kLdsMaxDim)
+        return engine_fail(e, PGBP_ERR_INVALID, std::string(fn) + ": family " + std::to_string(cfam[q]) + " (cluster " +
+                                                    std::to_string(c) + "): the cluster has more than " +
+                                                    std::to_string(kLdsMaxDim) + " variables");
+      mm = std::max(mm, (int)pl.dims[c]);
+    }
+  if (max_m) *max_m = mm;
+  return PGBP_OK;
 }
 
 }  // namespace pgbp

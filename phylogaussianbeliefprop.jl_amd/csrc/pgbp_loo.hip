@@ -1,6 +1,7 @@
 // Leave-one-out predictive moments of every tip from calibrated beliefs (pgbp_lg_loo of include/pgbp.h).
 //
-// A tip's data enters the model through one factor, N(y_O; u + w, V) in the notation of pgbp_lgfill.hip / pgbp_grad.hip:
+// A tip's data enters the model through one factor, N(y_O; u + w, V) in the notation of pgbp_lgfill.hip / pgbp_grad.hip
+// (coefficients, block table, Cov(u), the Cholesky and the staging of a packed record: pgbp_fam_dev.hpp):
 // u = (sum_k qc_k x_k)_O the parents' contribution (a fixed-root parent: its constant), w = (sum_k wc_k theta)_O,
 // V = (sum_k vc_k R[colour_k])_OO, O = child_mask[f] the observed traits, o = |O|.  With m_u = E[u], S = Cov(u) under the
 // calibrated belief of the family's cluster and r = y_O - w - m_u, dividing the factor out of the belief leaves the cavity
@@ -26,46 +27,14 @@
 
 #include "pgbp_bs16.hpp"
 #include "pgbp_devmem.hpp"
+#include "pgbp_fam_dev.hpp"
 #include "pgbp_kernels.hpp"
-#include "pgbp_mom_dev.hpp"
-#include "pgbp_shift_dev.hpp"
 
 namespace pgbp {
 
 extern __shared__ double loo_lds[];
 
 #define PGBP_LOO_LOG2PI 1.8378770664093454835606594728112
-
-// D = V - S is formed by cancellation: its entries carry an error of about 2^-52 |V|.  A pivot of its factorisation that is
-// not above 2^-40 of V's diagonal entry is rounding noise (the cavity variance is more than 2^40 times the tip's own): D is
-// then reported as not positive definite.
-constexpr double kLooPivotFloor = 0x1p-40;
-
-__device__ __forceinline__ int loo_rank(unsigned long long mask, int t) { return __popcll(mask & ((1ull << t) - 1ull)); }
-
-// Left-looking Cholesky of the lower triangle of the n x n matrix A (row stride ld) in LDS by NT threads: L(i, j), i > j, in
-// place; the diagonal of L in dl (A's diagonal is left as it was).  floor: null, or per pivot the value the pivot must exceed
-// (floor[j * (ld + 1)] * kLooPivotFloor).  false when a pivot fails (uniform: every thread computes the same pivot).
-template <int NT>
-__device__ __forceinline__ bool loo_cholesky(double* __restrict__ A, int n, int ld, double* __restrict__ dl,
-                                             const double* __restrict__ floor, int t) {
-#pragma clang fp contract(off)
-  for (int j = 0; j < n; ++j) {
-    double d = A[j * ld + j];
-    for (int k = 0; k < j; ++k) d = fma(-A[j * ld + k], A[j * ld + k], d);
-    const double lim = floor ? floor[j * ld + j] * kLooPivotFloor : 0.0;
-    if (!(d > lim)) return false;
-    const double l = sqrt(d);
-    for (int i = j + 1 + t; i < n; i += NT) {
-      double s = A[i * ld + j];
-      for (int k = 0; k < j; ++k) s = fma(-A[i * ld + k], A[j * ld + k], s);
-      A[i * ld + j] = s / l;
-    }
-    if (t == 0) dl[j] = l;
-    __syncthreads();
-  }
-  return true;
-}
 
 // LDS of loo_family beyond mom_solve's: doubles, then ints
 __host__ __device__ inline size_t loo_extra_doubles(int p, int K) {
@@ -100,42 +69,30 @@ __global__ __launch_bounds__(NT) void loo_family(const double* __restrict__ pool
   double* __restrict__ dlD = Ym + p * p + p;                // diagonal of D's factor
   double* __restrict__ dlV = dlD + p;                       // diagonal of V's factor
   double* __restrict__ yv = dlV + p;                        // y_O
-  double* __restrict__ qcs = yv + p;                        // qc, vc, wc (K each)
-  double* __restrict__ vcs = qcs + K;
-  double* __restrict__ wcs = vcs + K;
-  double* __restrict__ xm = wcs + K;                        // [k][i]: posterior mean of parent k (or its constant) at kept trait i
+  double* __restrict__ cf = yv + p;                         // rows of K: qc, vc, wc
+  double* __restrict__ xm = cf + 3 * K;                     // [k][i]: posterior mean of parent k (or its constant) at kept trait i
   int* __restrict__ ipos = reinterpret_cast<int*>(loo_lds + mom_lds_doubles(m) + ((loo_extra_doubles(p, K) + 1) & ~(size_t)1));
   int* __restrict__ oidx = ipos + K;
   int* __restrict__ vi = oidx + p;                          // [k][i]: the variable's index in the cluster, -1: a constant
-  // a packed (BS16) record is first copied here in the plain layout, the upper triangle mirrored (what a plain record gives
-  // mom_solve: PDMat(Symmetric(J))) -- a packed record keeps both triangles of its diagonal 2 x 2 blocks, equal to the last
-  // bit only: read this way the two layouts give the same bytes
+  // a packed (BS16) record is first copied here in the plain layout (fam_stage_plain)
   double* __restrict__ stage = loo_lds + mom_lds_doubles(m) + ((loo_extra_doubles(p, K) + 1) & ~(size_t)1) +
                                ((loo_extra_ints(p, K) + 1) >> 1);
   bool any_scope = false;
   for (int k = 0; k < np; ++k) any_scope |= F.parent_pos[(size_t)f * K + k] >= 0;
   const bool packed = bs && bs16::applies(m, fp);
-  const bool ou = M.model == PGBP_LG_OU;
   for (int site = blockIdx.y; site < n_sites; site += gridDim.y) {
     const int64_t slot = (int64_t)site * n_tip + ti;
     double* __restrict__ om = mean ? mean + slot * p : nullptr;
     double* __restrict__ oc = cov ? cov + slot * p * p : nullptr;
-    const int64_t as = site0 + site, ps = M.per_site ? as : 0;
-    const double* __restrict__ R = M.R + ps * nr * p * p;
-    const double* __restrict__ mu = M.mu + ps * p;
-    const double* __restrict__ theta = (ou && M.theta) ? M.theta + ps * p : nullptr;
-    const double alpha = ou ? M.alpha[ps] : 0.0;
+    const int64_t as = site0 + site;
+    const LgSite S = lg_site(M, nr, p, as);
     int st = 0;
     if (any_scope) {
       const double* __restrict__ rec = pool + as * pool_stride + boff[c];
       double mant, quad;
       int expo;
-      if (packed) {   // (mom_solve's first barrier publishes the copy; its loads end behind a barrier as well)
-        for (int idx = t; idx < m * m; idx += NT) {
-          const int j = idx / m, i = idx - j * m;
-          stage[idx] = rec[bs16::J_off(m, i < j ? i : j, i < j ? j : i, fp)];
-        }
-        for (int i = t; i < m; i += NT) stage[m * m + i] = rec[bs16::h_off(m, i, fp)];
+      if (packed) {
+        fam_stage_plain<NT>(rec, m, fp, stage, t);
         rec = stage;
       }
       st = mom_solve<NT, true>(rec, m, false, fp, W, dv, t, mant, expo, quad);
@@ -153,45 +110,21 @@ __global__ __launch_bounds__(NT) void loo_family(const double* __restrict__ pool
     }
     // coefficients, positions, kept traits
     for (int k = t; k < np; k += NT) {
-      double qc, vc, wc;
-      const double tl = F.length[(size_t)f * K + k], gam = F.gamma[(size_t)f * K + k];
-      if (ou) {   // (lg_coefs of pgbp_lgfill.hip)
-        const double a = exp(-alpha * tl);
-        qc = gam * a;
-        vc = gam * gam * (1.0 - a * a);
-        wc = gam * (1.0 - a);
-      } else {
-        qc = gam;
-        vc = gam * gam * tl;
-        wc = 0.0;
-      }
-      qcs[k] = qc; vcs[k] = vc; wcs[k] = wc;
+      lg_coefs<false>(M.model, S.alpha, F.length[(size_t)f * K + k], F.gamma[(size_t)f * K + k], cf[k], cf[K + k], cf[2 * K + k]);
       ipos[k] = F.parent_pos[(size_t)f * K + k];
     }
     for (int tr = t; tr < p; tr += NT)
-      if ((O >> tr) & 1ull) oidx[loo_rank(O, tr)] = tr;
+      if ((O >> tr) & 1ull) oidx[mask_rank(O, tr)] = tr;
     __syncthreads();
     // where each parent's kept traits sit in the cluster, and their posterior mean (or the fixed root's constant)
-    for (int idx = t; idx < np * mo; idx += NT) {
-      const int k = idx / mo, i = idx - k * mo, tr = oidx[i];
-      const int pk = ipos[k];
-      if (pk >= 0) {
-        const unsigned long long mk = F.parent_mask ? F.parent_mask[(size_t)f * K + k] : full;
-        const int v = pk + loo_rank(mk, tr);
-        vi[k * p + i] = v;
-        xm[k * p + i] = W[v * ld + m];
-      } else {
-        vi[k * p + i] = -1;
-        xm[k * p + i] = mu[tr];
-      }
-    }
+    fam_blocks<NT>(F, f, as, S.mu, 0, np, O, ipos, oidx, mo, W, ld, m, vi, xm, t);
     for (int i = t; i < mo; i += NT) yv[i] = F.data[(as * F.n_rows + row) * p + oidx[i]];
     // V_OO, twice: the matrix to factorise and the right-hand sides
     for (int idx = t; idx < mo * mo; idx += NT) {
       const int i = idx / mo, j = idx - i * mo;
       const int e = oidx[i] + oidx[j] * p;
       double v = 0.0;
-      for (int k = 0; k < np; ++k) v = v + vcs[k] * R[(int64_t)F.color[(size_t)f * K + k] * p * p + e];
+      for (int k = 0; k < np; ++k) v = v + cf[K + k] * S.R[(int64_t)F.color[(size_t)f * K + k] * p * p + e];
       Vm[i * mo + j] = v;
       Ym[i * ldy + j] = v;
     }
@@ -199,10 +132,10 @@ __global__ __launch_bounds__(NT) void loo_family(const double* __restrict__ pool
     // r = y_O - w - m_u, the last right-hand side
     for (int i = t; i < mo; i += NT) {
       double mu_u = 0.0;
-      for (int k = 0; k < np; ++k) mu_u = mu_u + qcs[k] * xm[k * p + i];
+      for (int k = 0; k < np; ++k) mu_u = mu_u + cf[k] * xm[k * p + i];
       double w = 0.0;
-      if (theta)
-        for (int k = 0; k < np; ++k) w = w + wcs[k] * theta[oidx[i]];
+      if (S.theta)
+        for (int k = 0; k < np; ++k) w = w + cf[2 * K + k] * S.theta[oidx[i]];
       if (Sh.slot) w = w + lg_shift_d(Sh, F.gamma, f, K, np, oidx[i], p, as);   // a shift of the mean on a parent edge
       Ym[i * ldy + mo] = (yv[i] - w) - mu_u;
     }
@@ -210,20 +143,10 @@ __global__ __launch_bounds__(NT) void loo_family(const double* __restrict__ pool
     for (int idx = t; idx < mo * mo; idx += NT) {
       const int i = idx / mo, j = idx - i * mo;
       if (j > i) continue;
-      double s = 0.0;
-      for (int a = 0; a < np; ++a) {
-        const int va = vi[a * p + i];
-        if (va < 0) continue;
-        for (int b = 0; b < np; ++b) {
-          const int vb = vi[b * p + j];
-          if (vb < 0) continue;
-          s = s + qcs[a] * qcs[b] * (va >= vb ? W[va * ld + vb] : W[vb * ld + va]);
-        }
-      }
-      Dm[i * mo + j] = Vm[i * mo + j] - s;
+      Dm[i * mo + j] = Vm[i * mo + j] - fam_cov(W, ld, vi, p, [&](int k) -> double { return cf[k]; }, np, i, j);
     }
     __syncthreads();
-    bool ok = loo_cholesky<NT>(Dm, mo, mo, dlD, Vm, t);
+    bool ok = lds_cholesky<NT>(Dm, mo, mo, dlD, Vm, t);
     if (ok) {
       // Y = L^-1 [V | r]: thread j its own column, rows in order
       for (int j = t; j <= mo; j += NT)
@@ -232,7 +155,7 @@ __global__ __launch_bounds__(NT) void loo_family(const double* __restrict__ pool
           for (int k = 0; k < i; ++k) s = fma(-Dm[i * mo + k], Ym[k * ldy + j], s);
           Ym[i * ldy + j] = s / dlD[i];
         }
-      ok = loo_cholesky<NT>(Vm, mo, mo, dlV, nullptr, t);   // (its first barrier publishes Y)
+      ok = lds_cholesky<NT>(Vm, mo, mo, dlV, nullptr, t);   // (its first barrier publishes Y)
     }
     if (!ok) {   // D or V is not positive definite
       if (om) for (int a = t; a < p; a += NT) om[a] = NAN;
@@ -305,28 +228,23 @@ __global__ __launch_bounds__(256) void loo_reduce(const double* __restrict__ lpd
 static std::atomic<int64_t> g_loo_limit{(int64_t)32 << 20};
 
 // the tip families of the table given to pgbp_lg_setup, in order, and the cluster of each
-// (fcl: the cluster of every family of the table)
-static int loo_tips(pgbp_engine* e, const EngineView& v, const char* fn, std::vector<int32_t>& tips, std::vector<int32_t>& tcl,
-                    std::vector<int32_t>& fcl) {
-  const Plan& pl = *v.plan;
+// (fcl, check_dims, max_m: lg_family_clusters -- the count and the list are served whatever the clusters' sizes, the sweep is not)
+static int loo_tips(pgbp_engine* e, const EngineView& v, const char* fn, bool check_dims, std::vector<int32_t>& tips,
+                    std::vector<int32_t>& tcl, std::vector<int32_t>& fcl, int* max_m) {
   const LgStatic& F = *v.lg;
-  const int nc = pl.n_clusters;
-  std::vector<int32_t> off(nc + 1);
-  hipError_t herr = hipMemcpy(off.data(), F.cl_off, sizeof(int32_t) * (nc + 1), hipMemcpyDeviceToHost);
-  const int nf = herr == hipSuccess ? off[nc] : 0;
-  std::vector<int32_t> cfam(std::max(nf, 1)), cpos(std::max(nf, 1)), drow(std::max(nf, 1));
+  const int rc = lg_family_clusters(e, fn, v, check_dims, &fcl, max_m);
+  if (rc) return rc;
+  const int nf = (int)fcl.size();
+  std::vector<int32_t> cpos(std::max(nf, 1)), drow(std::max(nf, 1));
   std::vector<unsigned long long> cmask;
-  if (herr == hipSuccess && nf > 0) herr = hipMemcpy(cfam.data(), F.cl_fam, sizeof(int32_t) * nf, hipMemcpyDeviceToHost);
-  if (herr == hipSuccess && nf > 0) herr = hipMemcpy(cpos.data(), F.child_pos, sizeof(int32_t) * nf, hipMemcpyDeviceToHost);
+  hipError_t herr = hipSuccess;
+  if (nf > 0) herr = hipMemcpy(cpos.data(), F.child_pos, sizeof(int32_t) * nf, hipMemcpyDeviceToHost);
   if (herr == hipSuccess && nf > 0) herr = hipMemcpy(drow.data(), F.data_row, sizeof(int32_t) * nf, hipMemcpyDeviceToHost);
   if (herr == hipSuccess && nf > 0 && F.child_mask) {
     cmask.resize(nf);
     herr = hipMemcpy(cmask.data(), F.child_mask, sizeof(unsigned long long) * nf, hipMemcpyDeviceToHost);
   }
   if (herr != hipSuccess) return engine_fail(e, PGBP_ERR_HIP, std::string(fn) + " (family table): " + hipGetErrorString(herr));
-  fcl.assign(nf, 0);
-  for (int c = 0; c < nc; ++c)
-    for (int q = off[c]; q < off[c + 1]; ++q) fcl[cfam[q]] = c;
   const unsigned long long full = F.p >= 64 ? ~0ull : ((1ull << F.p) - 1ull);
   tips.clear();
   tcl.clear();
@@ -339,12 +257,12 @@ static int loo_tips(pgbp_engine* e, const EngineView& v, const char* fn, std::ve
 }
 
 static int loo_table(pgbp_engine* e, const char* fn, EngineView* v, std::vector<int32_t>& tips, std::vector<int32_t>& tcl,
-                     std::vector<int32_t>& fcl) {
+                     std::vector<int32_t>& fcl, bool check_dims = false, int* max_m = nullptr) {
   if (!engine_peek(e).lg_ready)
     return engine_fail(e, PGBP_ERR_STATE, std::string(fn) + ": no family table (call pgbp_lg_setup first)");
   const int rc = engine_view(e, v);
   if (rc) return rc;
-  return loo_tips(e, *v, fn, tips, tcl, fcl);
+  return loo_tips(e, *v, fn, check_dims, tips, tcl, fcl, max_m);
 }
 
 }  // namespace pgbp
@@ -387,23 +305,16 @@ extern "C" int pgbp_lg_loo(pgbp_engine* e, int32_t site_begin, int32_t site_end,
   }
   EngineView v;
   std::vector<int32_t> tips, tcl, fcl;
-  int rc = loo_table(e, "pgbp_lg_loo", &v, tips, tcl, fcl);
+  // the limits are pgbp_lg_gradient's, over the clusters of ALL families of the table: an engine either serves both sweeps
+  // or neither, and the dimension class of the launch is the gradient's
+  int max_m = 0;
+  int rc = loo_table(e, "pgbp_lg_loo", &v, tips, tcl, fcl, true, &max_m);
   if (rc) return rc;
   // (as in pgbp_lg_gradient, what follows runs on the caller's current device)
   const Plan& pl = *v.plan;
   const LgStatic& F = *v.lg;
   const LgShifts Sh = engine_lg_shifts(e);
   const int p = F.p, K = F.K, nt = (int)tips.size();
-  // the limits are pgbp_lg_gradient's, over the clusters of ALL families of the table: an engine either serves both sweeps
-  // or neither, and the dimension class of the launch is the gradient's
-  int max_m = 0;
-  for (int f = 0; f < (int)fcl.size(); ++f) {
-    const int c = fcl[f];
-    if (pl.dims[c] > kLdsMaxDim)
-      return engine_fail(e, PGBP_ERR_INVALID, "pgbp_lg_loo: family " + std::to_string(f) + " (cluster " + std::to_string(c) +
-                                                  "): the cluster has more than " + std::to_string(kLdsMaxDim) + " variables");
-    max_m = std::max(max_m, (int)pl.dims[c]);
-  }
   size_t stage = 0;   // a packed record's plain copy
   for (int i = 0; i < nt && v.bs16; ++i) {
     const size_t m = (size_t)pl.dims[tcl[i]];

@@ -1,5 +1,5 @@
 // Device helpers shared by the kernels that solve a belief's system [J | h] in LDS (pgbp_moments.hip: pgbp_moments,
-// pgbp_bm_exact_stats; pgbp_grad.hip: pgbp_lg_gradient).  Arithmetic contract: see the head of pgbp_moments.hip.
+// pgbp_bm_exact_stats; the family sweeps pgbp_grad.hip, pgbp_edge.hip, pgbp_loo.hip, pgbp_impute.hip; pgbp_sample.hip).  Arithmetic contract: see the head of pgbp_moments.hip.
 #pragma once
 #include <hip/hip_runtime.h>
 

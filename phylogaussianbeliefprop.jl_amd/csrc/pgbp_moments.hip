@@ -490,16 +490,18 @@ extern "C" int pgbp_bm_exact_stats(pgbp_engine* e, int32_t site_begin, int32_t s
   if (rc) return rc;
   const Plan& pl = *v.plan;
   const LgStatic& F = *v.lg;
-  const int nc = pl.n_clusters, p = F.p, K = F.K;
-  // the family table back from the device (a few words per family) for the checks of src/calibration.jl:416-421 and of this sweep
-  std::vector<int32_t> off(nc + 1);
-  hipError_t herr = hipMemcpy(off.data(), F.cl_off, sizeof(int32_t) * (nc + 1), hipMemcpyDeviceToHost);
-  const int nf = herr == hipSuccess ? off[nc] : 0;
-  std::vector<int32_t> cfam(std::max(nf, 1)), npar(std::max(nf, 1)), cpos(std::max(nf, 1)), ppos((size_t)std::max(nf, 1) * K);
+  const int p = F.p, K = F.K;
+  // the family table back from the device (a few words per family) for the checks of src/calibration.jl:416-421 and of this
+  // sweep; the size of a family's cluster is checked below, family by family, behind the reference's own checks
+  std::vector<int32_t> fcl;
+  rc = lg_family_clusters(e, "pgbp_bm_exact_stats", v, false, &fcl, nullptr);
+  if (rc) return rc;
+  const int nf = (int)fcl.size();
+  std::vector<int32_t> npar(std::max(nf, 1)), cpos(std::max(nf, 1)), ppos((size_t)std::max(nf, 1) * K);
   std::vector<unsigned long long> cmask, pmask;
-  if (herr == hipSuccess && nf > 0) {
-    herr = hipMemcpy(cfam.data(), F.cl_fam, sizeof(int32_t) * nf, hipMemcpyDeviceToHost);
-    if (herr == hipSuccess) herr = hipMemcpy(npar.data(), F.n_parents, sizeof(int32_t) * nf, hipMemcpyDeviceToHost);
+  hipError_t herr = hipSuccess;
+  if (nf > 0) {
+    herr = hipMemcpy(npar.data(), F.n_parents, sizeof(int32_t) * nf, hipMemcpyDeviceToHost);
     if (herr == hipSuccess) herr = hipMemcpy(cpos.data(), F.child_pos, sizeof(int32_t) * nf, hipMemcpyDeviceToHost);
     if (herr == hipSuccess) herr = hipMemcpy(ppos.data(), F.parent_pos, sizeof(int32_t) * (size_t)nf * K, hipMemcpyDeviceToHost);
     if (herr == hipSuccess && F.child_mask) {
@@ -512,9 +514,6 @@ extern "C" int pgbp_bm_exact_stats(pgbp_engine* e, int32_t site_begin, int32_t s
     }
   }
   if (herr != hipSuccess) return engine_fail(e, PGBP_ERR_HIP, std::string("pgbp_bm_exact_stats: ") + hipGetErrorString(herr));
-  std::vector<int32_t> fcl(std::max(nf, 1), 0);
-  for (int c = 0; c < nc; ++c)
-    for (int q = off[c]; q < off[c + 1]; ++q) fcl[cfam[q]] = c;
   const unsigned long long full = p >= 64 ? ~0ull : ((1ull << p) - 1ull);
   int max_m = 1;
   for (int f = 0; f < nf; ++f) {

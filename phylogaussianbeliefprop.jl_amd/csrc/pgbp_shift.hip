@@ -16,28 +16,12 @@
 #include <hip/hip_runtime.h>
 
 #include "pgbp_bs16.hpp"
+#include "pgbp_fam_dev.hpp"
 #include "pgbp_kernels.hpp"
-#include "pgbp_shift_dev.hpp"
 
 namespace pgbp {
 
 extern __shared__ double shift_lds[];
-
-// edge coefficients of parent edge (length t, inheritance gam): lg_coefs of pgbp_lgfill.hip
-__device__ __forceinline__ void shift_coefs(int model, double alpha, double t, double gam, double& qc, double& vc, double& wc) {
-  if (model == PGBP_LG_OU) {
-    const double a = exp(-alpha * t);
-    qc = gam * a;
-    vc = gam * gam * (1.0 - a * a);
-    wc = gam * (1.0 - a);
-  } else {
-    qc = gam;
-    vc = gam * gam * t;
-    wc = 0.0;
-  }
-}
-
-__device__ __forceinline__ int shift_rank(unsigned long long mask, int t) { return __popcll(mask & ((1ull << t) - 1ull)); }
 
 // Gauss-Jordan on the n x nc system [V | z | delta] (row stride ld) in LDS by one wavefront: the right part becomes
 // [V^-1 z | V^-1 delta]; false when a pivot is not positive (the fill made this cluster's g NaN already).
@@ -108,13 +92,13 @@ __global__ __launch_bounds__(64) void shift_kernel(LgStatic F, LgParams M, LgShi
         ipos[0] = cpos;
       } else {
         double qc, vc, wc;
-        shift_coefs(M.model, alpha, F.length[(int64_t)f * K + lane - 1], F.gamma[(int64_t)f * K + lane - 1], qc, vc, wc);
+        lg_coefs<true>(M.model, alpha, F.length[(int64_t)f * K + lane - 1], F.gamma[(int64_t)f * K + lane - 1], qc, vc, wc);
         cz[lane] = -qc;
         ipos[lane] = F.parent_pos[(int64_t)f * K + lane - 1];
       }
     }
     for (int t = lane; t < p; t += kWave)
-      if ((O >> t) & 1ull) oidx[shift_rank(O, t)] = t;
+      if ((O >> t) & 1ull) oidx[mask_rank(O, t)] = t;
     __syncthreads();
     // V_OO
     for (int idx = lane; idx < mo * mo; idx += kWave) {
@@ -123,7 +107,7 @@ __global__ __launch_bounds__(64) void shift_kernel(LgStatic F, LgParams M, LgShi
       double v = 0.0;
       for (int k = 0; k < np; ++k) {
         double qc, vc, wc;
-        shift_coefs(M.model, alpha, F.length[(int64_t)f * K + k], F.gamma[(int64_t)f * K + k], qc, vc, wc);
+        lg_coefs<true>(M.model, alpha, F.length[(int64_t)f * K + k], F.gamma[(int64_t)f * K + k], qc, vc, wc);
         v += vc * R[(int64_t)F.color[(int64_t)f * K + k] * p * p + e];
       }
       W[i * ld + j] = v;
@@ -134,7 +118,7 @@ __global__ __launch_bounds__(64) void shift_kernel(LgStatic F, LgParams M, LgShi
       double z = 0.0;
       for (int k = 0; k < np; ++k) {
         double qc, vc, wc;
-        shift_coefs(M.model, alpha, F.length[(int64_t)f * K + k], F.gamma[(int64_t)f * K + k], qc, vc, wc);
+        lg_coefs<true>(M.model, alpha, F.length[(int64_t)f * K + k], F.gamma[(int64_t)f * K + k], qc, vc, wc);
         if (theta) z += wc * theta[t];
         if (F.parent_pos[(int64_t)f * K + k] < 0) z += qc * mu[t];
       }
@@ -155,7 +139,7 @@ __global__ __launch_bounds__(64) void shift_kernel(LgStatic F, LgParams M, LgShi
       const int a = idx / mo, i = idx - a * mo;
       if (ipos[a] < 0) continue;
       const unsigned long long ma = (a == 0 || !F.parent_mask) ? (a == 0 ? O : full) : F.parent_mask[(int64_t)f * K + a - 1];
-      dh[ipos[a] + shift_rank(ma, oidx[i])] += cz[a] * W[i * ld + mo + 1];
+      dh[ipos[a] + mask_rank(ma, oidx[i])] += cz[a] * W[i * ld + mo + 1];
     }
     if (lane == 0) dh[m] += -q;
   }
@@ -201,7 +185,7 @@ __global__ __launch_bounds__(256) void shift_uni_sm_kernel(LgStatic F, LgParams 
     double V = 0.0, z = 0.0, d = 0.0;
     for (int k = 0; k < np; ++k) {
       double qc, vc, wc;
-      shift_coefs(M.model, alpha, F.length[(int64_t)f * K + k], F.gamma[(int64_t)f * K + k], qc, vc, wc);
+      lg_coefs<true>(M.model, alpha, F.length[(int64_t)f * K + k], F.gamma[(int64_t)f * K + k], qc, vc, wc);
       V += vc * R[F.color[(int64_t)f * K + k]];
       z += wc * theta;
       if (F.parent_pos[(int64_t)f * K + k] < 0) z += qc * mu;
@@ -217,7 +201,7 @@ __global__ __launch_bounds__(256) void shift_uni_sm_kernel(LgStatic F, LgParams 
       double ca = 1.0;
       if (a > 0) {
         double qc, vc, wc;
-        shift_coefs(M.model, alpha, F.length[(int64_t)f * K + a - 1], F.gamma[(int64_t)f * K + a - 1], qc, vc, wc);
+        lg_coefs<true>(M.model, alpha, F.length[(int64_t)f * K + a - 1], F.gamma[(int64_t)f * K + a - 1], qc, vc, wc);
         ca = -qc;
       }
       if (pa == 0) dh0 += ca * j * d; else dh1 += ca * j * d;

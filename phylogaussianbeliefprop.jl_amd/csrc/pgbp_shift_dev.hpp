@@ -1,6 +1,7 @@
 // Mean shifts on edges (pgbp_lg_set_shifts of include/pgbp.h), device side: the displacement d = sum_k gamma_k s_k that a
 // family's offset w gains.  Shared by the correction of the factor fill (pgbp_shift.hip) and by the four post-calibration
-// sweeps (pgbp_grad.hip, pgbp_edge.hip, pgbp_loo.hip, pgbp_impute.hip), which all form w themselves.
+// sweeps, which all form w themselves: pgbp_grad.hip and pgbp_edge.hip in their common body (fam_score_T of
+// pgbp_fam_dev.hpp), pgbp_loo.hip and pgbp_impute.hip in their own kernels.
 #pragma once
 #include <hip/hip_runtime.h>
 
