@@ -73,6 +73,42 @@ def main():
               f"log-likelihood {norm:.6f} -> {fit['loglik']:.6f} (gain {fit['loglik'] - norm:.6f})")
         assert fit["loglik"] >= norm
         cgb.clear_shifts_lg()
+        # which edge carries a jump, how big is it, what does it buy?  Plant a jump of +3 on the edge into an internal node
+        # (every tip gains 3 x the share of its ancestry that passes through that edge), scan EVERY edge from one
+        # calibration -- per edge the exact ML jump, its standard error and the gain 2 (ll(jump) - ll(0)) -- and let the
+        # forward selection pick and refit it
+        x = np.array(g["x"], float)[:, None]
+        n = net.nnodes
+
+        def share(c):   # what a unit displacement of node c adds to the mean of every node (BM: qc = gamma)
+            tau = np.zeros(n)
+            tau[c] = 1.0
+            for i in range(c + 1, n):
+                tau[i] = sum(gk * tau[q - 1] for gk, q in zip(net.gamma[i], net.node2family[i][1:]))
+            return tau
+        inner = [i for i in range(1, n) if not net.is_leaf[i] and len(net.node2family[i]) == 2]
+        ntips = int(np.sum(net.is_leaf))
+        c = min(inner, key=lambda i: abs(sum(1 for q in range(n) if net.is_leaf[q] and share(i)[q] > 0) - ntips / 3))
+        tau = share(c)
+        xj = x.copy()
+        for i in range(n):
+            if net.is_leaf[i] and names[i] in row:
+                xj[row[names[i]], 0] += 3.0 * tau[i]
+        cgb.lg_setup(fam, xj)
+        cgb.assignfactors_lg_(np.array([[[g["model"]["sigma2"]]]], float), [g["model"]["mu"]])
+        ll_j, scan = cgb.loglik_and_shift_scan_lg(sched[0], information=True)
+        print(f"jump of +3 planted on the edge into {names[c]}; scan of {int(np.sum(fam['n_parents']))} edges, log-likelihood {ll_j:.6f}:")
+        for f in np.argsort(-np.nan_to_num(scan["lr"], nan=-1.0))[:3]:
+            k = int(np.argmax(fam["gamma"].reshape(len(scan["lr"]), -1)[f, :fam["n_parents"][f]]))
+            gk = fam["gamma"].reshape(len(scan["lr"]), -1)[f, k]
+            print(f"  {names[net.node2family[f + 1][1 + k] - 1]} -> {names[f + 1]}: jump {scan['edge_jump'][f, k, 0]:.4f} "
+                  f"+- {scan['se'][f, 0] / abs(gk):.4f}, lr {scan['lr'][f]:.4f}")
+        sel = P.select_shifts_lg(cgb, sched[0], 1)
+        (fs, ks), step = sel["edges"][0], sel["path"][0]
+        print(f"selected {names[net.node2family[fs + 1][1 + ks] - 1]} -> {names[fs + 1]}: shift {step['shifts'][0, 0]:.4f} "
+              f"+- {sel['fit']['se'][0, 0]:.4f}, lr at entry {step['lr']:.4f}, log-likelihood {ll_j:.6f} -> {step['loglik']:.6f}")
+        assert abs(2.0 * (step["loglik"] - ll_j) - step["lr"]) <= 1e-8 * step["lr"]
+        cgb.clear_shifts_lg()
         # imputation: hide two values, set an engine up on the incomplete table and predict them from everything else
         x = np.array(g["x"], float)[:, None]
         hidden = [1, len(x) - 2]

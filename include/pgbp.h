@@ -412,6 +412,43 @@ int pgbp_lg_set_edges(pgbp_engine* e, const double* length, const double* gamma)
  * pgbp_lg_shift_count: the number of shifts in force (0: none; -1: no family table). */
 int pgbp_lg_set_shifts(pgbp_engine* e, int32_t n_shifts, const int32_t* edge, const double* value, int32_t per_site);
 int32_t pgbp_lg_shift_count(pgbp_engine* e);
+/* SCAN OF EVERY EDGE FOR A MEAN SHIFT from the CURRENT beliefs, for sites [site_begin, site_end): per family the maximum-
+ * likelihood displacement of the child's conditional mean, its observed information and the likelihood-ratio statistic, under
+ * the parameters the engine kept from the last pgbp_lg_assignfactors and the shifts in force.  EXACT ONLY WHEN THE BELIEFS ARE
+ * CALIBRATED (postorder AND preorder) ON A CLIQUE TREE under those parameters and shifts; the call does not verify that.
+ * The log-likelihood is quadratic in a displacement d (r = x_child - sum_k qc_k x_k - w - d).  In the notation of
+ * pgbp_lg_edge_gradient (O = child_mask[f], mo = |O|, j = V_OO^-1, e = E[r], g_w = j e) and with C = Cov(r | data), the
+ * covariance of the residual under the cluster's belief WITHOUT the e e' term:
+ *     H_f = j - j C j  (mo x mo, the observed information of d: no data value enters it),
+ *     dhat = H_f^-1 g_w,      lr = 2 (ll(dhat) - ll(0)) = g_w' H_f^-1 g_w.
+ * A shift s_k on parent edge k enters as gamma_k s_k: shat_k = dhat / gamma_k, its information is gamma_k^2 H_f and lr is the
+ * same for every parent edge of a hybrid.  With shifts set, e is the residual at the current shifts: dhat is the INCREMENT to
+ * that edge's shift and lr the gain of a jump there while the other shifts stay where they are.
+ * The traits of O are taken in index order by a Cholesky factorisation with a skip: a trait whose pivot, given the kept
+ * traits before it, is not greater than min_info * j_ii is NOT IDENTIFIED (no tip below observes it, or the data leave the
+ * prior untouched) and is dropped, row and column; dhat and lr are then those of the displacement restricted to the kept
+ * traits.  H_f is formed from C itself, not by taking e e' back out of the gradient's M: its bytes do not depend on the data.
+ * Outputs, site-major; any of the four may be NULL, not all four:
+ *   jump        [sites][n_families][p]     dhat embedded in the p traits; NaN at a trait outside O or not identified;
+ *   lr          [sites][n_families]        the gain; 0 when no trait is identified;
+ *   identified  [sites][n_families]        bit t set: trait t is kept;
+ *   information [sites][n_families][p][p]  H_f at the kept traits, symmetric; NaN elsewhere.
+ *   A root-prior family has no edge: jump, lr and information NaN, identified 0.  A family the factor fill skips
+ *   (child_mask == 0): jump and information NaN, lr 0, identified 0.
+ *   info [sites] (may be NULL): as pgbp_lg_edge_gradient's; that site's outputs are all NaN (identified 0), other sites are
+ *   unaffected.
+ * Device (csrc/pgbp_scan.hip): the frame of pgbp_lg_edge_gradient -- one workgroup per (family, site), 64 threads while every
+ * family's cluster has at most 64 variables, else 256, the cluster solved in LDS -- no reduction, no atomics on doubles, every
+ * sum in a fixed index order: the same bytes on every call and for every split of the site range.  Device copies of the
+ * outputs of a chunk of sites at a time (256 MB at most), one stream synchronisation per call.  Read-only on the beliefs;
+ * every layout, as pgbp_lg_edge_gradient.
+ * Fails before any launch, the outputs untouched, with PGBP_ERR_STATE without a family table or before the first
+ * pgbp_lg_assignfactors, with PGBP_ERR_INVALID for p > 64 (as soon as the table is known), for a site range out of bounds, for
+ * all four outputs NULL, for min_info outside [0, 1), for a family whose cluster has more than 128 variables (the message
+ * names the family and the cluster), and when the LDS need -- the largest cluster's working matrix plus p x (2p + 1) +
+ * 3 p x p + 5 p doubles of family scratch and, in the packed layout, the plain copy of a record -- exceeds 160 KB. */
+int pgbp_lg_shift_scan(pgbp_engine* e, int32_t site_begin, int32_t site_end, double min_info, double* jump, double* lr,
+                       uint64_t* identified, double* information, int32_t* info);
 /* LEAVE-ONE-OUT predictive moments of every tip from the CURRENT beliefs, for sites [site_begin, site_end): for each tip family
  * of the table given to pgbp_lg_setup (child_pos < 0, data_row >= 0, at least one observed trait: O = child_mask, o = |O|), the
  * distribution of the tip's observed values y_O given the data of all OTHER tips, with the parameters the engine kept from the

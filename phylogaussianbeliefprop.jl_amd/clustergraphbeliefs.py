@@ -814,6 +814,91 @@ class ClusterGraphBelief:
             raise np.linalg.LinAlgError(f"PosDefException: belief {d['info'][self.site] - 1} is not positive definite")
         return float(ll[self.site]), g[self.site].copy()
 
+    def shift_scan_lg(self, all_sites=False, min_info=1e-8, information=False):
+        """pgbp_lg_shift_scan on the current beliefs: every edge scanned for a mean shift in one sweep over the node families.
+        The log-likelihood is quadratic in a displacement d of a family's conditional mean; from the calibrated belief of the
+        family's cluster the sweep forms the score g_w, the observed information H_f = j - j C j (C the covariance of the
+        family's residual given the data) and returns the ML displacement H_f^-1 g_w and the gain 2 (ll(dhat) - ll(0)) =
+        g_w' H_f^-1 g_w.  With shifts set it gives the INCREMENT to an edge's shift and the gain of a jump there while the
+        other shifts stay where they are.  EXACT ONLY when the beliefs are calibrated (postorder and preorder) on a clique
+        tree under the current parameters and shifts (not verified), as edge_gradient_lg.
+        min_info: a trait whose pivot in H_f, given the kept traits before it (index order), is not above min_info * j_ii is
+        not identified -- no tip below observes it, or the data leave the prior untouched -- and is dropped; the result is the
+        ML displacement restricted to the kept traits.  (Rounding leaves such pivots at <= 2.6e-15 of j_ii on the test
+        networks, identified ones are >= 2.8e-3 there; fit_shifts_lg uses 1e-10 on differences of scores.)
+        Returns a dict, F = n_families, K = max_parents: jump [F, p] (NaN at a trait that is out of the family's child_mask or
+        not identified, and for a root-prior family, which has no edge), lr [F] (0 when no trait is identified, NaN for a
+        root-prior family), dof [F] (the number of kept traits), identified [F, p] (bool), edge_jump [F, K, p] = jump / gamma_k,
+        the ML shift on parent edge k (NaN where there is no such edge or gamma_k = 0; its information is gamma_k^2 H, its lr
+        the family's), info; with information=True also H [F, p, p] (H_f at the kept traits, NaN elsewhere) and se [F, p] =
+        sqrt(diag(H_kept^-1)), the standard error of jump.  With a leading site axis when all_sites.  A site whose info is
+        not 0 holds NaN; for the current site that raises."""
+        p = self._lg_p
+        nf = len(self._lg["cluster"])
+        K = self._lg["length"].size // nf if nf else 1
+        s0, s1 = (0, self.n_sites) if all_sites else (self.site, self.site + 1)
+        n = s1 - s0
+        jump = np.zeros((n, nf, p))
+        lr = np.zeros((n, nf))
+        ident = np.zeros((n, nf), np.uint64)
+        H = np.zeros((n, nf, p, p)) if information else None
+        info = np.zeros(n, dtype=np.int32)
+        _check(self._lib.pgbp_lg_shift_scan(self._eng, s0, s1, float(min_info), L.f64p(jump), L.f64p(lr),
+                                            ident.ctypes.data_as(C.POINTER(C.c_uint64)), L.f64p(H) if information else None,
+                                            L.i32p(info)), self._eng)
+        bits = ((ident[:, :, None] >> np.arange(p, dtype=np.uint64)[None, None, :]) & np.uint64(1)).astype(bool)
+        gam = np.asarray(self._lg["gamma"], np.float64).reshape(nf, K)
+        real = np.arange(K)[None, :] < np.asarray(self._lg["n_parents"]).reshape(nf, 1)
+        inv = np.full((nf, K), np.nan)
+        ok = real & (gam != 0.0)
+        inv[ok] = 1.0 / gam[ok]
+        d = dict(jump=jump, lr=lr, dof=bits.sum(axis=2).astype(np.int32), identified=bits,
+                 edge_jump=jump[:, :, None, :] * inv[None, :, :, None], info=info)
+        if information:
+            se = np.full((n, nf, p), np.nan)
+            flat_id, flat_H, flat_se = ident.reshape(-1), H.reshape(-1, p, p), se.reshape(-1, p)
+            for mask in np.unique(flat_id):
+                idx = [t for t in range(p) if (int(mask) >> t) & 1]
+                if not idx:
+                    continue
+                sel = np.flatnonzero(flat_id == mask)
+                cov = np.linalg.inv(flat_H[np.ix_(sel, idx, idx)])
+                flat_se[np.ix_(sel, idx)] = np.sqrt(np.diagonal(cov, axis1=1, axis2=2))
+            d["H"], d["se"] = H, se
+        return d if all_sites else self._shift_scan_of_site(d, 0)
+
+    @staticmethod
+    def _shift_scan_of_site(d, s):
+        if d["info"][s]:
+            raise np.linalg.LinAlgError(f"PosDefException: belief {d['info'][s] - 1} is not positive definite")
+        return dict({k: v[s].copy() for k, v in d.items() if k != "info"}, info=0)
+
+    def loglik_and_shift_scan_lg(self, schedule_tree, all_sites=False, min_info=1e-8, information=False):
+        """Log-likelihood and the scan of every edge for a mean shift, on a clique tree: the factors are filled again with the
+        parameters of the last assignfactors_lg_ (so that shifts set since then are in), then the steps of
+        loglik_and_edge_gradient_lg with the scan (shift_scan_lg) in place of the edge sweep.  Returns (loglik, scan dict): the
+        current site's values, or arrays over the sites (info of a failed site is not 0 and its values are NaN) when
+        all_sites."""
+        if getattr(self, "_lg_last", None) is None:
+            raise L.PgbpError(L.ERR_STATE, "loglik_and_shift_scan_lg: no parameters yet (call assignfactors_lg_ first)")
+        m, _keep = self._lg_last
+        _check(self._lib.pgbp_lg_assignfactors(self._eng, C.byref(m)), self._eng)
+        self._ensure_schedule([schedule_tree])
+        o = self._opts()
+        pa = np.asarray(schedule_tree[-2]).reshape(-1)
+        root = int(pa[0]) if pa.size else 0
+        _check(self._lib.pgbp_enqueue_calibrate(self._eng, 1, 1, C.byref(o)), self._eng)
+        _check(self._lib.pgbp_enqueue_integrate(self._eng, root), self._eng)
+        scan = self.shift_scan_lg(all_sites=True, min_info=min_info, information=information)
+        norm = np.zeros(self.n_sites)
+        info = np.zeros(self.n_sites, dtype=np.int32)
+        _check(self._lib.pgbp_fetch_loglik(self._eng, L.f64p(norm), L.i32p(info)), self._eng)
+        scan["info"] = np.where(scan["info"] != 0, scan["info"], info)
+        norm = np.where(scan["info"] != 0, np.nan, norm)
+        if all_sites:
+            return norm, scan
+        return float(norm[self.site]), self._shift_scan_of_site(scan, self.site)
+
     def loo_lg(self, all_sites=False):
         """pgbp_lg_loo on the current beliefs: the leave-one-out predictive distribution of every tip that has data, given
         the data of all other tips, under the parameters of the last assignfactors_lg_ -- one sweep over the tip families.

@@ -132,6 +132,37 @@ __device__ __forceinline__ bool lds_cholesky(double* __restrict__ A, int n, int 
   return true;
 }
 
+// lds_cholesky's arithmetic with a skip (pgbp_scan.hip): index j is KEPT when its pivot, given the kept indices before it,
+// exceeds min_info * lim[j * lstride]; otherwise it is dropped from the system -- its row and column take no part in any
+// later pivot or column.  L(i, j) in place below the diagonal for every kept j (all i > j, kept or not: a dropped row is
+// never read), the diagonal of L in dl at the kept indices; A's diagonal and upper triangle are left as they were.  Returns
+// the mask of kept indices (uniform: every thread computes the same pivots; a pivot that is NaN is dropped).  Every kept
+// column ends behind a barrier; the caller's barrier stands before the first.
+template <int NT>
+__device__ __forceinline__ unsigned long long lds_cholesky_skip(double* __restrict__ A, int n, int ld, double* __restrict__ dl,
+                                                                const double* __restrict__ lim, int lstride, double min_info,
+                                                                int t) {
+#pragma clang fp contract(off)
+  unsigned long long kept = 0ull;
+  for (int j = 0; j < n; ++j) {
+    double d = A[j * ld + j];
+    for (int k = 0; k < j; ++k)
+      if ((kept >> k) & 1ull) d = fma(-A[j * ld + k], A[j * ld + k], d);
+    if (!(d > min_info * lim[j * lstride])) continue;
+    const double l = sqrt(d);
+    for (int i = j + 1 + t; i < n; i += NT) {
+      double s = A[i * ld + j];
+      for (int k = 0; k < j; ++k)
+        if ((kept >> k) & 1ull) s = fma(-A[i * ld + k], A[j * ld + k], s);
+      A[i * ld + j] = s / l;
+    }
+    if (t == 0) dl[j] = l;
+    kept |= 1ull << j;
+    __syncthreads();
+  }
+  return kept;
+}
+
 // the parameters of site `as` (absolute): theta is null and alpha 0 unless the model is OU
 struct LgSite {
   const double *R, *mu, *theta;

@@ -382,6 +382,27 @@ Number of mean shifts in force (pgbp_lg_shift_count): 0 when none is set, -1 wit
 lg_shift_count(o::DeviceClusterGraphBelief) = Int(@ccall LIB.pgbp_lg_shift_count(o.handle::Ptr{Cvoid})::Int32)
 
 """
+    lg_shift_scan(obj, p, nfamilies; min_info = 1e-8) -> (jump, lr, identified, information)
+
+Every edge scanned for a mean shift from the current beliefs (pgbp_lg_shift_scan: one sweep over the node families).  Per
+family f of the table given to pgbp_lg_setup: `jump[:, f]` the maximum-likelihood displacement of the child's conditional mean
+(NaN at a trait outside the family's child_mask or not identified, and for a root-prior family), `lr[f]` the gain
+2 (ll(jump) - ll(0)), `identified[f]` the bit mask of kept traits and `information[:, :, f]` the observed information H_f at the
+kept traits (NaN elsewhere).  The shift on parent edge k is `jump / gamma_k`, its information `gamma_k^2 H_f`.  A trait whose
+pivot in H_f is not above `min_info` times its prior precision is not identified and is dropped.  With shifts set the result is
+the increment to an edge's shift, the others held.  Exact under the condition of `lg_gradient`.  A cluster that is not
+positive definite throws its PosDefException.
+"""
+function lg_shift_scan(o::DeviceClusterGraphBelief, p::Integer, nfamilies::Integer; min_info::Real = 1e-8)
+    n = max(nfamilies, 1)
+    jump = zeros(p, n); lr = zeros(n); identified = zeros(UInt64, n); information = zeros(p, p, n)
+    info = Ref(Int32(0))
+    check(o.handle, @ccall LIB.pgbp_lg_shift_scan(o.handle::Ptr{Cvoid}, Int32(0)::Int32, Int32(1)::Int32, Float64(min_info)::Float64, jump::Ptr{Float64}, lr::Ptr{Float64}, identified::Ptr{UInt64}, information::Ptr{Float64}, info::Ref{Int32})::Cint)
+    info[] == 0 || throw(PGBP.LA.PosDefException(info[]))
+    return (jump[:, 1:nfamilies], lr[1:nfamilies], identified[1:nfamilies], information[:, :, 1:nfamilies])
+end
+
+"""
     sample_size(obj) -> Int
 
 Doubles per draw of `sample_posterior!`: the sum of the cluster dimensions (pgbp_sample_size).

@@ -281,3 +281,67 @@ def _cholesky_or_name(H, edges, K, p):
         Lc[j, j] = np.sqrt(d)
         Lc[j + 1:, j] = (H[j + 1:, j] - Lc[j + 1:, :j] @ Lc[j, :j]) / Lc[j, j]
     return Lc
+
+
+def select_shifts_lg(beliefs, schedule_tree, max_shifts, min_lr=0.0, candidates=None, min_info=1e-8):
+    """Greedy forward selection of mean shifts at the current site, on a clique tree, at the parameters of the last
+    assignfactors_lg_.  It starts from no shift (shifts in force are cleared) and repeats:
+      1. loglik_and_shift_scan_lg under the shifts chosen so far: per family the gain lr of a jump there, the others held;
+      2. the candidates are one edge per family -- the parent edge with the largest gamma, ties to the lowest k (every
+         parent edge of a hybrid has the family's lr) -- without the edges already chosen, the families outside `candidates`
+         (family indices) when it is given, root-prior families and families with no identified trait;
+      3. the largest lr (ties to the lowest family) enters, unless it is below min_lr or max_shifts is reached; ALL chosen
+         shifts are then refitted jointly by fit_shifts_lg;
+      4. if that refit raises because the joint information is not positive definite (the new shift is not identified next to
+         the chosen ones), the previous shifts are put back on the engine, with its factors and calibrated beliefs, the
+         candidate is excluded for good and the next one is taken.
+    Returns a dict: path -- per step edge (family, k), lr and dof at entry, loglik after the joint refit and the shifts
+    [step + 1, p] of all chosen edges --, edges [(family, k)] in order of entry, fit (the last fit_shifts_lg dict; None when
+    nothing entered) and loglik0 (the log-likelihood without shifts).  The engine is left at the last fit.
+    min_lr HAS NO STATISTICAL DEFAULT: lr is a maximum over all edges, not one chi-square draw.  Without any jump in the data
+    the largest lr of the 39-node test networks reaches 13.1, so a per-edge rule such as AIC (lr > 2 dof) over-selects; choose
+    min_lr from a null simulation of the network at hand, or fix max_shifts.  p-values are out of scope."""
+    nf = len(beliefs._lg["cluster"])
+    K = beliefs._lg["length"].size // nf
+    p = beliefs._lg_p
+    gam = np.asarray(beliefs._lg["gamma"], np.float64).reshape(nf, K)
+    npar = np.asarray(beliefs._lg["n_parents"]).reshape(nf)
+    best_k = np.array([int(np.argmax(gam[f, :npar[f]])) if npar[f] > 0 else -1 for f in range(nf)])   # (argmax: first of ties)
+    allowed = np.ones(nf, bool) if candidates is None else np.isin(np.arange(nf), np.asarray(list(candidates), np.int64))
+    allowed &= best_k >= 0
+    chosen, values = [], np.zeros((0, p))
+    path, fit, ll0 = [], None, None
+    beliefs.clear_shifts_lg()
+    while len(chosen) < int(max_shifts):
+        ll, scan = beliefs.loglik_and_shift_scan_lg(schedule_tree, min_info=min_info)
+        if ll0 is None:
+            ll0 = ll
+        lr = np.where(allowed & (scan["dof"] > 0) & np.isfinite(scan["lr"]), scan["lr"], -np.inf)
+        for f, k in chosen:
+            if best_k[f] == k:
+                lr[f] = -np.inf
+        entered = False
+        for f in np.argsort(-lr, kind="stable"):
+            if not np.isfinite(lr[f]) or lr[f] < min_lr:
+                break
+            edge = (int(f), int(best_k[f]))
+            try:
+                fit_new = fit_shifts_lg(beliefs, schedule_tree, chosen + [edge])
+            except ValueError:
+                allowed[f] = False
+                if chosen:
+                    beliefs.set_shifts_lg(chosen, values)
+                else:
+                    beliefs.clear_shifts_lg()
+                beliefs.loglik_and_shift_gradient_lg(schedule_tree)   # factors and beliefs under the restored shifts
+                continue
+            fit = fit_new
+            chosen.append(edge)
+            values = fit["shifts"].copy()
+            path.append(dict(edge=edge, lr=float(scan["lr"][f]), dof=int(scan["dof"][f]), loglik=fit["loglik"],
+                             shifts=values.copy()))
+            entered = True
+            break
+        if not entered:
+            break
+    return dict(path=path, edges=list(chosen), fit=fit, loglik0=ll0)
