@@ -125,6 +125,17 @@ def main():
         for i, r in enumerate(imp["rows"]):
             print(f"imputed {g['taxa'][int(r)]}: {filled[int(r), 0]:.4f} +- {np.sqrt(imp['cov'][i, 0, 0]):.4f} "
                   f"(hidden value {x[int(r), 0]:.4f}); log-likelihood of the remaining data {ll_m:.6f}")
+        # measurement error: the same data read as species means with a known standard error of 0.3 (se2 = 0.09 at every
+        # tip; sigma_e = 0: no within-species covariance to scale), fitted with and without it
+        cgb.lg_setup(fam, x)
+        sigma2, mu0 = np.array([[g["model"]["sigma2"]]], float), [g["model"]["mu"]]
+        R_plain, mu_plain, ll_plain, _ = P.calibrate_optimize_cliquetree_(cgb, sched[0], sigma2, mu0, gradient="analytic")
+        tips = [f for f in range(len(fam["cluster"])) if fam["child_pos"][f] < 0 and fam["data_row"][f] >= 0]
+        cgb.set_tip_noise_lg(tips, np.zeros((1, 1)), se2=np.full((len(tips), 1), 0.09))
+        R_se, mu_se, ll_se, _ = P.calibrate_optimize_cliquetree_(cgb, sched[0], sigma2, mu0, gradient="analytic")
+        print(f"fit without standard errors: sigma2 {R_plain[0, 0]:.4f}, mu {mu_plain[0]:.4f}, log-likelihood {ll_plain:.6f}; "
+              f"with se = 0.3 at {len(tips)} tips: sigma2 {R_se[0, 0]:.4f}, mu {mu_se[0]:.4f}, log-likelihood {ll_se:.6f}")
+        cgb.clear_tip_noise_lg()
 
 
 if __name__ == "__main__":

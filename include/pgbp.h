@@ -412,6 +412,44 @@ int pgbp_lg_set_edges(pgbp_engine* e, const double* length, const double* gamma)
  * pgbp_lg_shift_count: the number of shifts in force (0: none; -1: no family table). */
 int pgbp_lg_set_shifts(pgbp_engine* e, int32_t n_shifts, const int32_t* edge, const double* value, int32_t per_site);
 int32_t pgbp_lg_shift_count(pgbp_engine* e);
+/* MEASUREMENT ERROR AT THE TIPS: species means with known standard errors, or means of n_f individuals with a within-species
+ * covariance.  A tip family f (child_pos < 0, a data row, at least one parent edge) that is listed gets the conditional variance
+ *     V_f = sum_k vc_k R[colour_k] + E_f,      E_f = scale_f * Sigma_e + diag(se2_f):
+ * the tip's variable is the OBSERVATION y = x + eps, eps ~ N(0, E_f).  Means, qc, wc and the shifts are untouched; only the
+ * observed block E_OO (O = child_mask[f]) enters the factor.
+ *   family  [n]: the listed tip families; the list is sparse (the device keeps a dense int32 slot map [n_families], -1 for none);
+ *   scale   [n]: scale_f >= 0, for example 1 / n_f;
+ *   sigma_e [p][p] symmetric, diagonal >= 0 (the two triangles may differ by 1e-12 of the largest entry: they are averaged), or
+ *           with per_site != 0 [n_sites][p][p];
+ *   se2     NULL, or [n][p] known sampling variances >= 0, with per_site != 0 [n_sites][n][p];
+ *   n = 0 clears the noise (the arrays may be NULL).  The call REPLACES the previous list, it does not add to it.
+ * Takes effect as pgbp_lg_set_shifts does: the next pgbp_lg_assignfactors or pgbp_enqueue_loglik_lg uses it (every fill, and its
+ * shift correction, is followed by a correction of J, h and g of the clusters that hold a noisy tip family,
+ * csrc/pgbp_noise.hip: nothing is launched when none is set); beliefs and factors are not refilled by this call.  The sweeps
+ * read the CURRENT noise as they read the current parameters and shifts: pgbp_lg_gradient(_noise), pgbp_lg_edge_gradient and
+ * pgbp_lg_shift_scan use V_OO + E_OO for a noisy tip family; pgbp_lg_loo and pgbp_lg_impute then predict the OBSERVATION of a
+ * noisy tip (variance V + E; pgbp_lg_impute uses the blocks E_PP, E_PO of the missing traits as well), not the trait value
+ * under it.  The noise survives pgbp_lg_set_edges and pgbp_lg_set_shifts; a new pgbp_lg_setup clears it.  An engine borrowed
+ * from a pgbp_group or pgbp_patterns takes the call like any other; there is no group-level call.
+ * ACCURACY: the fill writes j = V_OO^-1 and the correction adds D = (V_OO + E_OO)^-1 - j, formed as -j E_OO (V_OO + E_OO)^-1:
+ * the tip's contribution carries a relative error of about 2^-52 (1 + |E| / |V|).  At |E| / |V| = 1e7 about 1e-8 is left;
+ * nothing is lost for |E| <= |V|.
+ * PGBP_ERR_STATE without a family table.  PGBP_ERR_INVALID with NOTHING changed (the previous noise stays in force) and a text
+ * that names the entry for: a family index out of range, a family that is not a tip family, a family listed twice, a value
+ * that is not finite, an asymmetric sigma_e, a negative scale, se2 or diagonal entry of sigma_e; and when the correction of the
+ * largest noisy cluster -- its record plus two p x (2p + 1) systems -- needs more than the 160 KB of LDS.  Up to six copies
+ * (for a univariate per-site batch se2 once more as [entry][site]) and one stream synchronisation.
+ * pgbp_lg_tip_noise_count: the number of noisy tips in force (0: none; -1: no family table). */
+int pgbp_lg_set_tip_noise(pgbp_engine* e, int32_t n, const int32_t* family, const double* scale, const double* sigma_e,
+                          const double* se2, int32_t per_site);
+int32_t pgbp_lg_tip_noise_count(pgbp_engine* e);
+/* pgbp_lg_gradient with one more output (NULL allowed: then exactly pgbp_lg_gradient):
+ *   dsigma_e [sites][p*p] column-major, symmetric: sum over the noisy tip families of scale_f G_V(f), G_V formed with
+ *            j = (V_OO + E_OO)^-1, so that d loglik = tr(dsigma_e dSigma_e); zeros when no noise is set.
+ * It is one more block of the family slot (a coefficient scale_f beside those of the rates), added by the same fixed tree
+ * as dR: no atomics, two calls return the same bytes. */
+int pgbp_lg_gradient_noise(pgbp_engine* e, int32_t site_begin, int32_t site_end, double* dR, double* dmu, double* dalpha,
+                           double* dtheta, double* dsigma_e, int32_t* info);
 /* SCAN OF EVERY EDGE FOR A MEAN SHIFT from the CURRENT beliefs, for sites [site_begin, site_end): per family the maximum-
  * likelihood displacement of the child's conditional mean, its observed information and the likelihood-ratio statistic, under
  * the parameters the engine kept from the last pgbp_lg_assignfactors and the shifts in force.  EXACT ONLY WHEN THE BELIEFS ARE

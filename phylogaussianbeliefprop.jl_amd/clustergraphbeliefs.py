@@ -587,6 +587,7 @@ class ClusterGraphBelief:
         _check(self._lib.pgbp_lg_setup(self._eng, C.byref(t)), self._eng)
         self._lg_p, self._lg_nrates = int(fam["p"]), int(fam["n_rates"])
         self._lg_shift_edges = np.zeros(0, np.int32)   # a new table clears the shifts (pgbp_lg_setup)
+        self._lg_noise = None                          # ... and the tip noise
         self._lg_last = None                           # ... and has no parameters yet
 
     def assignfactors_lg_(self, R, mu, model="bm", alpha=None, theta=None, sync=False):
@@ -628,7 +629,9 @@ class ClusterGraphBelief:
         loopy cluster graph, at a converged calibration, it is the gradient of the factored energy.
         Returns a dict: dR [n_rates, p, p] (symmetric; d loglik = sum_c tr(dR[c] dR_c)), dmu [p], dalpha (scalar) and
         dtheta [p] (zero for a Brownian motion), info; with a leading site axis when all_sites.  A site whose info is
-        not 0 (1-based index of a cluster that is not positive definite) holds NaN; for the current site that raises."""
+        not 0 (1-based index of a cluster that is not positive definite) holds NaN; for the current site that raises.
+        With tip noise set (set_tip_noise_lg) the dict also holds dsigma_e [p, p] (symmetric; d loglik = tr(dsigma_e
+        dSigma_e)): pgbp_lg_gradient_noise."""
         p, nr = self._lg_p, self._lg_nrates
         s0, s1 = (0, self.n_sites) if all_sites else (self.site, self.site + 1)
         n = s1 - s0
@@ -637,18 +640,29 @@ class ClusterGraphBelief:
         dalpha = np.zeros(n)
         dtheta = np.zeros((n, p))
         info = np.zeros(n, dtype=np.int32)
-        _check(self._lib.pgbp_lg_gradient(self._eng, s0, s1, L.f64p(dR), L.f64p(dmu), L.f64p(dalpha), L.f64p(dtheta),
-                                          L.i32p(info)), self._eng)
+        noisy = self.tip_noise_count_lg() > 0
+        if noisy:
+            dsig = np.zeros((n, p, p))
+            _check(self._lib.pgbp_lg_gradient_noise(self._eng, s0, s1, L.f64p(dR), L.f64p(dmu), L.f64p(dalpha),
+                                                    L.f64p(dtheta), L.f64p(dsig), L.i32p(info)), self._eng)
+        else:
+            _check(self._lib.pgbp_lg_gradient(self._eng, s0, s1, L.f64p(dR), L.f64p(dmu), L.f64p(dalpha), L.f64p(dtheta),
+                                              L.i32p(info)), self._eng)
         dR = dR.transpose(0, 1, 3, 2)   # (column-major blocks; symmetric)
         d = dict(dR=dR, dmu=dmu, dalpha=dalpha, dtheta=dtheta, info=info)
+        if noisy:
+            d["dsigma_e"] = dsig.transpose(0, 2, 1)
         return d if all_sites else self._gradient_of_site(d, 0)
 
     @staticmethod
     def _gradient_of_site(d, s):
         if d["info"][s]:
             raise np.linalg.LinAlgError(f"PosDefException: belief {d['info'][s] - 1} is not positive definite")
-        return dict(dR=d["dR"][s].copy(), dmu=d["dmu"][s].copy(), dalpha=float(d["dalpha"][s]), dtheta=d["dtheta"][s].copy(),
-                    info=0)
+        out = dict(dR=d["dR"][s].copy(), dmu=d["dmu"][s].copy(), dalpha=float(d["dalpha"][s]), dtheta=d["dtheta"][s].copy(),
+                   info=0)
+        if "dsigma_e" in d:
+            out["dsigma_e"] = d["dsigma_e"][s].copy()
+        return out
 
     def loglik_and_gradient_lg(self, schedule_tree, all_sites=False):
         """Log-likelihood and its exact gradient under the parameters of the last assignfactors_lg_ on a clique tree:
@@ -778,6 +792,46 @@ class ClusterGraphBelief:
     def shift_count_lg(self):
         """pgbp_lg_shift_count: the number of shifts in force (0: none)."""
         return int(self._lib.pgbp_lg_shift_count(self._eng))
+
+    def set_tip_noise_lg(self, families, sigma_e, scale=None, se2=None):
+        """pgbp_lg_set_tip_noise: measurement error at the tips.  The conditional variance of every listed tip family f
+        (child_pos < 0 with a data row) gains E_f = scale_f * sigma_e + diag(se2_f): the tip's data row is then an
+        observation y = x + eps of the trait.  families: indices into the family table given to lg_setup; sigma_e: [p, p]
+        symmetric (the within-species covariance), or [n_sites, p, p] for one per site; scale: [n] >= 0 (default 1, for
+        example 1 / n_f); se2: None or known sampling variances [n, p] >= 0, [n_sites, n, p] with a per-site sigma_e (a
+        shared se2 is then repeated).  The call REPLACES the previous noise (an empty list clears it); the next
+        assignfactors_lg_ or loglik_lg uses it, beliefs and factors are not refilled by this call.  The sweeps read the
+        current noise: loo_lg and impute_lg then predict the OBSERVATION of a noisy tip (variance V + E).  An invalid
+        entry raises and leaves the previous noise in force.  Accuracy: a relative error of about 2^-52 (1 + |E| / |V|)
+        in a noisy tip's factor (1e-8 at |E| / |V| = 1e7)."""
+        p = self._lg_p
+        fam = np.ascontiguousarray(np.asarray(families, np.int64).reshape(-1), np.int32)
+        n = int(fam.size)
+        sig = np.asarray(sigma_e, np.float64)
+        per_site = sig.ndim == 3
+        sig = np.ascontiguousarray(sig.reshape((self.n_sites, p, p) if per_site else (p, p)))
+        sc = np.ascontiguousarray(np.broadcast_to(np.asarray(1.0 if scale is None else scale, np.float64).reshape(-1), (n,)))
+        s2 = None
+        if se2 is not None:
+            s2 = np.asarray(se2, np.float64)
+            if per_site:
+                s2 = np.broadcast_to(s2.reshape((-1, n, p)), (self.n_sites, n, p))
+            else:
+                s2 = s2.reshape(n, p)
+            s2 = np.ascontiguousarray(s2)
+        _check(self._lib.pgbp_lg_set_tip_noise(self._eng, n, L.i32p(fam) if n else None, L.f64p(sc) if n else None,
+                                               L.f64p(sig) if n else None, L.f64p(s2) if (n and s2 is not None) else None,
+                                               int(per_site)), self._eng)
+        self._lg_noise = dict(families=fam, per_site=per_site, scale=sc, se2=s2) if n else None
+
+    def clear_tip_noise_lg(self):
+        """Remove the tip noise (pgbp_lg_set_tip_noise with an empty list)."""
+        _check(self._lib.pgbp_lg_set_tip_noise(self._eng, 0, None, None, None, None, 0), self._eng)
+        self._lg_noise = None
+
+    def tip_noise_count_lg(self):
+        """pgbp_lg_tip_noise_count: the number of noisy tips in force (0: none)."""
+        return int(self._lib.pgbp_lg_tip_noise_count(self._eng))
 
     def _shift_gradient_from(self, d):
         e = getattr(self, "_lg_shift_edges", np.zeros(0, np.int32))

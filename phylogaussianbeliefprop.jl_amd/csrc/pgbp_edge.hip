@@ -43,7 +43,8 @@ __host__ __device__ inline size_t edge_extra_doubles(int p) { return (size_t)p *
 template <int NT>
 __global__ __launch_bounds__(NT) void edge_family(const double* __restrict__ pool, int64_t pool_stride,
                                                   const int64_t* __restrict__ boff, const int32_t* __restrict__ bdim, int bs,
-                                                  int fp, LgStatic F, LgParams M, LgShifts Sh, const int32_t* __restrict__ fam_cluster,
+                                                  int fp, LgStatic F, LgParams M, LgShifts Sh, LgNoise Nz,
+                                                  const int32_t* __restrict__ fam_cluster,
                                                   int n_fam, int site0, int n_sites, double* __restrict__ dlen,
                                                   double* __restrict__ dgam, double* __restrict__ dshift,
                                                   int32_t* __restrict__ info, int info0) {
@@ -101,7 +102,7 @@ __global__ __launch_bounds__(NT) void edge_family(const double* __restrict__ poo
         cf[3 * K + k] = d.q_t; cf[4 * K + k] = d.v_t; cf[5 * K + k] = d.w_t;
         cf[6 * K + k] = d.q_g; cf[7 * K + k] = d.v_g; cf[8 * K + k] = d.w_g;
       }
-      if (!fam_score_T<NT>(L, F, M, Sh, S, f, m, O, as, t)) st = 1;
+      if (!fam_score_T<NT>(L, F, M, Sh, Nz, S, f, m, O, as, t)) st = 1;
     }
     if (st != 0) {
       write_all(NAN, NAN);
@@ -192,6 +193,7 @@ extern "C" int pgbp_lg_edge_gradient(pgbp_engine* e, int32_t site_begin, int32_t
   const Plan& pl = *v.plan;
   const LgStatic& F = *v.lg;
   const LgShifts Sh = engine_lg_shifts(e);
+  const LgNoise Nz = engine_lg_noise(e);
   const int p = F.p, K = F.K;
   std::vector<int32_t> fcl;   // which cluster each family sits in
   int max_m = 0;
@@ -232,11 +234,11 @@ extern "C" int pgbp_lg_edge_gradient(pgbp_engine* e, int32_t site_begin, int32_t
       const int n = std::min(chunk, ns - s0), gy = std::min(n, 65535);
       if (max_m <= 64)
         hipLaunchKernelGGL(edge_family<64>, dim3(nf, gy), dim3(64), lds_bytes, v.st, v.pool, pl.pool_stride(), v.boff, v.bdim,
-                           v.bs16, pl.fast_p, F, M, Sh, d_fcl.get(), nf, site_begin + s0, n, d_len.get(), d_gam.get(), d_shift.get(),
+                           v.bs16, pl.fast_p, F, M, Sh, Nz, d_fcl.get(), nf, site_begin + s0, n, d_len.get(), d_gam.get(), d_shift.get(),
                            d_info.get(), s0);
       else
         hipLaunchKernelGGL(edge_family<256>, dim3(nf, gy), dim3(256), lds_bytes, v.st, v.pool, pl.pool_stride(), v.boff, v.bdim,
-                           v.bs16, pl.fast_p, F, M, Sh, d_fcl.get(), nf, site_begin + s0, n, d_len.get(), d_gam.get(), d_shift.get(),
+                           v.bs16, pl.fast_p, F, M, Sh, Nz, d_fcl.get(), nf, site_begin + s0, n, d_len.get(), d_gam.get(), d_shift.get(),
                            d_info.get(), s0);
       herr = hipGetLastError();
       const size_t nk = (size_t)n * nf * K, np_ = (size_t)n * nf * p, ok = (size_t)s0 * nf * K, op = (size_t)s0 * nf * p;

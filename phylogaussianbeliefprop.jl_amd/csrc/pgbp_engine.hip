@@ -90,6 +90,11 @@ struct LgShiftBufs {
   DevBuf<int32_t> slot, cl;
   DevBuf<double> value, value_sm;
 };
+// what LgNoise points at (pgbp_lg_set_tip_noise), and the clusters the correction kernel visits
+struct LgNoiseBufs {
+  DevBuf<int32_t> slot, cl;
+  DevBuf<double> scale, sigma_e, se2, se2_sm;
+};
 
 hipEvent_t hip_event(void* ev) { return static_cast<hipEvent_t>(ev); }
 
@@ -195,6 +200,12 @@ struct pgbp_engine {
   LgShiftBufs lg_shift_bufs;
   int32_t lg_n_shift_cl = 0;
   std::vector<int32_t> lg_h_cluster;
+  // pgbp_lg_set_tip_noise: measurement error at the tips (device pointers owned by lg_noise_bufs; slot == null: none), the
+  // clusters that hold a noisy tip family and the largest of them, and which families are tip families (host side)
+  LgNoise lgn{};
+  LgNoiseBufs lg_noise_bufs;
+  int32_t lg_n_noise_cl = 0, lg_noise_max_dim = 0;
+  std::vector<char> lg_h_tip;
   std::string err;
   // a step of an asynchronous enqueue that could not be issued (a workspace that could not be allocated: ensure_ws has
   // set `err`): the launches that needed it were skipped; every entry point that enqueued, and the next pgbp_sync /
@@ -1789,6 +1800,11 @@ int pgbp_lg_setup(pgbp_engine* e, const pgbp_lg_families* f) {
   e->lg_shift_bufs = LgShiftBufs{};   // a new table: no shifts
   e->lgs = LgShifts{};
   e->lg_n_shift_cl = 0;
+  e->lg_noise_bufs = LgNoiseBufs{};   // ... and no tip noise
+  e->lgn = LgNoise{};
+  e->lg_n_noise_cl = e->lg_noise_max_dim = 0;
+  e->lg_h_tip.assign(nf, 0);
+  for (size_t i = 0; i < nf; ++i) e->lg_h_tip[i] = f->child_pos[i] < 0 && f->data_row[i] >= 0 && f->n_parents[i] >= 1;
   const LgBufs& L = e->lg_bufs;
   e->lg = LgStatic{pp, K, f->n_rates, f->n_rows, L.off.get(), L.fam.get(), L.np.get(), L.cp.get(), L.row.get(), L.pp.get(), L.len.get(),
                    L.gam.get(), L.col.get(), L.data.get(), L.cm.get(), L.pm.get(), L.data_sm.get(), L.simple.get()};
@@ -1807,6 +1823,8 @@ static int lg_fill_async(pgbp_engine* e, bool also_factors, bool skip_sepsets = 
                           p.n_clusters, p.n_sites, e->st);
     launch_lg_shift_uni_sm(e->lg, e->lgp, e->lgs, e->lg_shift_bufs.cl.get(), e->lg_n_shift_cl, e->sm.pool.get(),
                            also_factors ? e->sm.fpool.get() : nullptr, e->d_packed_off.get(), e->d_bdim.get(), p.n_sites, e->st);
+    launch_lg_noise_uni_sm(e->lg, e->lgp, e->lgs, e->lgn, e->lg_noise_bufs.cl.get(), e->lg_n_noise_cl, e->sm.pool.get(),
+                           also_factors ? e->sm.fpool.get() : nullptr, e->d_packed_off.get(), e->d_bdim.get(), p.n_sites, e->st);
     const int64_t nc = p.packed_off[p.n_clusters] * sm_row(p.n_sites), nall = p.packed_off.back() * sm_row(p.n_sites);
     if (!skip_sepsets) HIPCHK(e, hipMemsetAsync(e->sm.pool.get() + nc, 0, sizeof(double) * (size_t)(nall - nc), e->st));  // sepsets = 1
   } else {
@@ -1819,6 +1837,9 @@ static int lg_fill_async(pgbp_engine* e, bool also_factors, bool skip_sepsets = 
     launch_lg_shift(e->lg, e->lgp, e->lgs, e->lg_shift_bufs.cl.get(), e->lg_n_shift_cl, e->d_pool.get(), p.pool_stride(),
                     also_factors ? e->d_fpool.get() : nullptr, p.cluster_stride(), e->d_boff.get(), e->d_bdim.get(),
                     e->layout_bs16 ? 1 : 0, p.fast_p, p.max_dim, p.n_sites, e->st);
+    launch_lg_noise(e->lg, e->lgp, e->lgs, e->lgn, e->lg_noise_bufs.cl.get(), e->lg_n_noise_cl, e->d_pool.get(), p.pool_stride(),
+                    also_factors ? e->d_fpool.get() : nullptr, p.cluster_stride(), e->d_boff.get(), e->d_bdim.get(),
+                    e->layout_bs16 ? 1 : 0, p.fast_p, e->lg_noise_max_dim, p.n_sites, e->st);
     if (!skip_sepsets)
       launch_zero_strided(e->d_pool.get() + p.cluster_stride(), p.pool_stride(), p.pool_stride() - p.cluster_stride(),
                           p.n_sites, e->st);  // sepsets = 1 (init_beliefs_reset!)
@@ -1960,6 +1981,120 @@ int pgbp_lg_set_shifts(pgbp_engine* e, int32_t n_shifts, const int32_t* edge, co
 int32_t pgbp_lg_shift_count(pgbp_engine* e) {
   if (!e || !e->lg_ready) return -1;
   return e->lgs.slot ? e->lgs.n : 0;
+}
+
+int pgbp_lg_set_tip_noise(pgbp_engine* e, int32_t n, const int32_t* family, const double* scale, const double* sigma_e,
+                          const double* se2, int32_t per_site) {
+  DeviceScope device_scope(e);
+  if (!e) return PGBP_ERR_INVALID;
+  if (!e->lg_ready) return e->fail(PGBP_ERR_STATE, "pgbp_lg_set_tip_noise: no family table (call pgbp_lg_setup first)");
+  if (n < 0 || (n > 0 && (!family || !scale || !sigma_e)))
+    return e->fail(PGBP_ERR_INVALID, "pgbp_lg_set_tip_noise: a negative count or a missing array");
+  const int nf = e->lg_nf, pp = e->lg.p, K = e->lg.K;
+  const size_t ns = per_site ? (size_t)e->plan.n_sites : 1, nn = (size_t)n;
+  // every check before anything changes
+  std::vector<int32_t> slot(std::max<size_t>(1, (size_t)nf), -1);
+  std::vector<double> sig;   // sigma_e with the two triangles averaged: exactly symmetric on the device
+  if (n > 0) {
+    sig.assign(sigma_e, sigma_e + ns * pp * pp);
+    for (size_t s = 0; s < ns; ++s) {
+      const double* A = sigma_e + s * pp * pp;
+      const std::string where = "pgbp_lg_set_tip_noise: sigma_e" + (per_site ? " of site " + std::to_string(s) : std::string()) + ": ";
+      double big = 0.0;
+      for (int a = 0; a < pp * pp; ++a) {
+        if (!std::isfinite(A[a]))
+          return e->fail(PGBP_ERR_INVALID, where + "entry (" + std::to_string(a / pp) + ", " + std::to_string(a % pp) + ") is not finite");
+        big = std::max(big, std::fabs(A[a]));
+      }
+      for (int i = 0; i < pp; ++i) {
+        if (A[i * pp + i] < 0.0)
+          return e->fail(PGBP_ERR_INVALID, where + "diagonal entry " + std::to_string(i) + " is negative");
+        for (int j = 0; j < i; ++j) {
+          if (std::fabs(A[i * pp + j] - A[j * pp + i]) > 1e-12 * big)
+            return e->fail(PGBP_ERR_INVALID, where + "entries (" + std::to_string(i) + ", " + std::to_string(j) + ") and (" +
+                                                 std::to_string(j) + ", " + std::to_string(i) + ") differ: the matrix is not symmetric");
+          sig[s * pp * pp + i * pp + j] = sig[s * pp * pp + j * pp + i] = 0.5 * (A[i * pp + j] + A[j * pp + i]);
+        }
+      }
+    }
+  }
+  for (int i = 0; i < n; ++i) {
+    const std::string where = "pgbp_lg_set_tip_noise: entry " + std::to_string(i) + " (family " + std::to_string(family[i]) + "): ";
+    if (family[i] < 0 || family[i] >= nf) return e->fail(PGBP_ERR_INVALID, where + "family index out of range");
+    if (!e->lg_h_tip[family[i]])
+      return e->fail(PGBP_ERR_INVALID, where + "not a tip family (child_pos < 0, a data row and a parent edge)");
+    if (slot[family[i]] >= 0)
+      return e->fail(PGBP_ERR_INVALID, where + "the family is listed twice (entry " + std::to_string(slot[family[i]]) + " has it too)");
+    slot[family[i]] = i;
+    if (!std::isfinite(scale[i])) return e->fail(PGBP_ERR_INVALID, where + "the scale is not finite");
+    if (scale[i] < 0.0) return e->fail(PGBP_ERR_INVALID, where + "the scale is negative");
+    for (size_t s = 0; se2 && s < ns; ++s)
+      for (int t = 0; t < pp; ++t) {
+        const double v = se2[(s * nn + i) * pp + t];
+        if (!std::isfinite(v)) return e->fail(PGBP_ERR_INVALID, where + "se2 of trait " + std::to_string(t) + " is not finite");
+        if (v < 0.0) return e->fail(PGBP_ERR_INVALID, where + "se2 of trait " + std::to_string(t) + " is negative");
+      }
+  }
+  // the clusters that hold a noisy tip family, in index order, and what the correction kernel needs for the largest of them
+  std::vector<int32_t> cl;
+  for (int i = 0; i < n; ++i) cl.push_back(e->lg_h_cluster[family[i]]);
+  std::sort(cl.begin(), cl.end());
+  cl.erase(std::unique(cl.begin(), cl.end()), cl.end());
+  int max_dim = 0;
+  for (int32_t c : cl) max_dim = std::max(max_dim, (int)e->plan.dims[c]);
+  if (n > 0) {
+    const size_t bytes = lg_noise_lds_bytes(pp, K, max_dim);
+    if (bytes > 160 * 1024)
+      return e->fail(PGBP_ERR_INVALID, "pgbp_lg_set_tip_noise: a cluster of " + std::to_string(max_dim) + " variables with " +
+                                           std::to_string(pp) + " traits holds a noisy tip; its correction needs " +
+                                           std::to_string(bytes) + " bytes of LDS, more than the 160 KB of a compute unit");
+  }
+  if (n == 0) {   // clear (kernels already enqueued may still read the old noise)
+    HIPCHK(e, hipStreamSynchronize(e->st));
+    e->lg_noise_bufs = LgNoiseBufs{};
+    e->lgn = LgNoise{};
+    e->lg_n_noise_cl = e->lg_noise_max_dim = 0;
+    return PGBP_OK;
+  }
+  // univariate per-site batches: se2 once more as [slot][site], what the thread-per-site correction reads
+  std::vector<double> ssm;
+  if (per_site && se2 && e->lg_uni_ok) {
+    const size_t row = (size_t)sm_row(e->plan.n_sites);
+    ssm.assign(nn * row, 0.0);
+    for (size_t s = 0; s < ns; ++s)
+      for (size_t i = 0; i < nn; ++i) ssm[i * row + s] = se2[s * nn + i];
+  }
+  LgNoiseBufs B;   // into a local: the engine takes it once every copy has been made
+  int rc;
+  if ((rc = dev_alloc(e, B.slot, slot.size()))) return rc;
+  if ((rc = dev_alloc(e, B.cl, cl.size()))) return rc;
+  if ((rc = dev_alloc(e, B.scale, nn))) return rc;
+  if ((rc = dev_alloc(e, B.sigma_e, sig.size()))) return rc;
+  if (se2 && (rc = dev_alloc(e, B.se2, ns * nn * pp))) return rc;
+  if (!ssm.empty() && (rc = dev_alloc(e, B.se2_sm, ssm.size()))) return rc;
+  // every buffer exists: the copies, then ONE synchronisation whatever they returned (none may outlive the host vectors)
+  hipError_t herr = hipMemcpyAsync(B.slot.get(), slot.data(), slot.size() * sizeof(int32_t), hipMemcpyHostToDevice, e->st);
+  if (herr == hipSuccess) herr = hipMemcpyAsync(B.cl.get(), cl.data(), cl.size() * sizeof(int32_t), hipMemcpyHostToDevice, e->st);
+  if (herr == hipSuccess) herr = hipMemcpyAsync(B.scale.get(), scale, nn * sizeof(double), hipMemcpyHostToDevice, e->st);
+  if (herr == hipSuccess) herr = hipMemcpyAsync(B.sigma_e.get(), sig.data(), sig.size() * sizeof(double), hipMemcpyHostToDevice, e->st);
+  if (herr == hipSuccess && se2)
+    herr = hipMemcpyAsync(B.se2.get(), se2, ns * nn * pp * sizeof(double), hipMemcpyHostToDevice, e->st);
+  if (herr == hipSuccess && !ssm.empty())
+    herr = hipMemcpyAsync(B.se2_sm.get(), ssm.data(), ssm.size() * sizeof(double), hipMemcpyHostToDevice, e->st);
+  const hipError_t serr = hipStreamSynchronize(e->st);  // the host buffers may go away; kernels that read the old noise have finished
+  if (herr == hipSuccess) herr = serr;
+  if (herr != hipSuccess) return e->fail(PGBP_ERR_HIP, std::string("pgbp_lg_set_tip_noise (upload): ") + hipGetErrorString(herr));
+  e->lg_noise_bufs = std::move(B);
+  const LgNoiseBufs& S = e->lg_noise_bufs;
+  e->lgn = LgNoise{S.slot.get(), S.scale.get(), S.sigma_e.get(), se2 ? S.se2.get() : nullptr, per_site ? 1 : 0, n, S.se2_sm.get()};
+  e->lg_n_noise_cl = (int32_t)cl.size();
+  e->lg_noise_max_dim = max_dim;
+  return PGBP_OK;
+}
+
+int32_t pgbp_lg_tip_noise_count(pgbp_engine* e) {
+  if (!e || !e->lg_ready) return -1;
+  return e->lgn.slot ? e->lgn.n : 0;
 }
 
 int pgbp_enqueue_loglik_lg(pgbp_engine* e, int32_t reps, const pgbp_opts* opts) {
@@ -2272,4 +2407,5 @@ bool engine_lg_params(const pgbp_engine* e, LgParams* out) {
   return true;
 }
 LgShifts engine_lg_shifts(const pgbp_engine* e) { return e->lg_ready ? e->lgs : LgShifts{}; }
+LgNoise engine_lg_noise(const pgbp_engine* e) { return e->lg_ready ? e->lgn : LgNoise{}; }
 }  // namespace pgbp

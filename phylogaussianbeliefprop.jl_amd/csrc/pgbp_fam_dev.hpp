@@ -10,6 +10,7 @@
 #include "pgbp_bs16.hpp"
 #include "pgbp_kernels.hpp"
 #include "pgbp_mom_dev.hpp"
+#include "pgbp_noise_dev.hpp"
 #include "pgbp_shift_dev.hpp"
 
 namespace pgbp {
@@ -284,11 +285,12 @@ __device__ __forceinline__ double fam_j(const double* __restrict__ A, int ldv, i
 
 // From the moments of the family's cluster (mom_solve has run, or nothing is in scope and a barrier stands behind the previous
 // site's reads) to T = j M: fills cf rows 0 .. 2, ipos, oidx, vi, xm, ev = e, Mx = M, the right half of A = j, Tx = j M,
-// ge = g_w.  false when the variance V_OO is not positive definite.  No barrier stands behind the writes of Tx and ge:
+// ge = g_w.  A noisy tip family (Nz: pgbp_lg_set_tip_noise) has V_OO + E_OO in place of V_OO, and so j = (V_OO + E_OO)^-1
+// in everything formed from it.  false when that variance is not positive definite.  No barrier stands behind the writes of Tx and ge:
 // fam_score_gv begins with it.
 template <int NT>
 __device__ __forceinline__ bool fam_score_T(const FamLds& L, const LgStatic& F, const LgParams& M, const LgShifts& Sh,
-                                            const LgSite& S, int f, int m, unsigned long long O, int64_t as, int t) {
+                                            const LgNoise& Nz, const LgSite& S, int f, int m, unsigned long long O, int64_t as, int t) {
 #pragma clang fp contract(off)
   const int p = F.p, K = F.K, np = F.n_parents[f], nn = np + 1, mo = __popcll(O);
   const int ld = (m + 1) | 1, ldv = fam_ldv(p);
@@ -312,6 +314,7 @@ __device__ __forceinline__ bool fam_score_T(const FamLds& L, const LgStatic& F, 
   __syncthreads();
   fam_blocks<NT>(F, f, as, S.mu, 1, nn, O, L.ipos, oidx, mo, W, ld, m, L.vi, L.xm, t);
   // V_OO and the identity
+  const int sn = lg_noise_slot(Nz, f);
   for (int idx = t; idx < mo * mo; idx += NT) {
     const int j = idx / mo, i = idx - j * mo;
     const int e = oidx[i] + oidx[j] * p;
@@ -321,6 +324,7 @@ __device__ __forceinline__ bool fam_score_T(const FamLds& L, const LgStatic& F, 
     } else {
       for (int k = 0; k < np; ++k) v = v + cf[K + k] * S.R[(int64_t)F.color[(size_t)f * K + k] * p * p + e];
     }
+    if (sn >= 0) v = v + lg_noise_E(Nz, sn, oidx[i], oidx[j], p, as);   // a noisy tip: V_OO + E_OO
     A[i * ldv + j] = v;
     A[i * ldv + mo + j] = (i == j) ? 1.0 : 0.0;
   }

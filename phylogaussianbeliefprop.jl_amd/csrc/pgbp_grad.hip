@@ -14,7 +14,9 @@
 //
 // Stage 1 (grad_family): one workgroup per (family, site) solves the family's cluster in LDS (mom_solve: Sigma never leaves
 // the LDS) and writes the family's slot [G_V (p*p) | g_w (p) | dalpha term | c_mu | c_theta | c_R[n_rates]]: the matrices once
-// and the scalar chain-rule coefficients beside them, so that the slot does not grow with the number of rates.
+// and the scalar chain-rule coefficients beside them, so that the slot does not grow with the number of rates.  With tip noise
+// set (pgbp_lg_set_tip_noise) the slot carries one more coefficient behind c_R: scale_f of a noisy tip family (else 0), and the
+// reduction one more p x p block, dsigma_e = sum_f scale_f G_V(f) (pgbp_lg_gradient_noise): Sigma_e is reduced as one more rate.
 // Stage 2 (grad_reduce_blocks, grad_reduce_final): the slots are added in a FIXED order -- 256 consecutive families per
 // workgroup, four lanes of 64 families each in family order, the four lanes added in lane order, then the block partials by a
 // fixed tree -- no floating-point atomics: two calls return the same bytes.  The slots of a chunk of sites at a time
@@ -43,7 +45,8 @@ constexpr int kGradRows = 6;
 template <int NT>
 __global__ __launch_bounds__(NT) void grad_family(const double* __restrict__ pool, int64_t pool_stride,
                                                   const int64_t* __restrict__ boff, const int32_t* __restrict__ bdim, int bs,
-                                                  int fp, LgStatic F, LgParams M, LgShifts Sh, const int32_t* __restrict__ fam_cluster,
+                                                  int fp, LgStatic F, LgParams M, LgShifts Sh, LgNoise Nz,
+                                                  const int32_t* __restrict__ fam_cluster,
                                                   int n_fam, int site0, int n_sites, double* __restrict__ slots,
                                                   int32_t* __restrict__ info, int info0) {
 #pragma clang fp contract(off)
@@ -54,7 +57,10 @@ __global__ __launch_bounds__(NT) void grad_family(const double* __restrict__ poo
   const unsigned long long O = F.child_mask ? (F.child_mask[f] & full) : full;
   const int mo = __popcll(O);
   const int cpos = F.child_pos[f];
-  const int sl = p * p + p + 3 + nr;
+  // with tip noise set the slot carries one more coefficient behind those of the rates: scale_f of a noisy tip family (else
+  // 0), the weight of G_V in dsigma_e -- Sigma_e is reduced as one more rate
+  const int nrs = nr + (Nz.slot ? 1 : 0);
+  const int sl = p * p + p + 3 + nrs;
   const int DA = p * p + p, CMU = DA + 1, CTH = DA + 2, CR = DA + 3;
   const FamLds L = fam_carve(grad_lds, m, p, K, kGradRows, 0);
   const int ldv = fam_ldv(p);
@@ -88,7 +94,7 @@ __global__ __launch_bounds__(NT) void grad_family(const double* __restrict__ poo
       for (int k = t; k < np; k += NT)
         lg_coefs_dalpha(M.model, S.alpha, F.length[(size_t)f * K + k], F.gamma[(size_t)f * K + k], cf[3 * K + k], cf[4 * K + k],
                         cf[5 * K + k]);
-      if (!fam_score_T<NT>(L, F, M, Sh, S, f, m, O, as, t)) st = 1;
+      if (!fam_score_T<NT>(L, F, M, Sh, Nz, S, f, m, O, as, t)) st = 1;
     }
     if (st != 0) {
       for (int a = t; a < sl; a += NT) o[a] = NAN;
@@ -137,9 +143,12 @@ __global__ __launch_bounds__(NT) void grad_family(const double* __restrict__ poo
       o[CMU] = cmu;
       o[CTH] = cth;
     }
-    for (int r = t; r < nr; r += NT) {
+    for (int r = t; r < nrs; r += NT) {
       double cr = 0.0;
-      if (np == 0) {
+      if (r == nr) {
+        const int sn = Nz.slot[f];
+        cr = sn >= 0 ? Nz.scale[sn] : 0.0;
+      } else if (np == 0) {
         cr = F.color[(size_t)f * K] == r ? 1.0 : 0.0;
       } else {
         for (int k = 0; k < np; ++k)
@@ -212,8 +221,8 @@ __global__ __launch_bounds__(256) void grad_reduce_final(const double* __restric
 
 using namespace pgbp;
 
-extern "C" int pgbp_lg_gradient(pgbp_engine* e, int32_t site_begin, int32_t site_end, double* dR, double* dmu, double* dalpha,
-                                double* dtheta, int32_t* info) {
+static int lg_gradient(pgbp_engine* e, int32_t site_begin, int32_t site_end, double* dR, double* dmu, double* dalpha,
+                       double* dtheta, double* dsigma_e, int32_t* info) {
   if (!e) return PGBP_ERR_INVALID;
   LgParams M{};
   {
@@ -236,7 +245,9 @@ extern "C" int pgbp_lg_gradient(pgbp_engine* e, int32_t site_begin, int32_t site
   const Plan& pl = *v.plan;
   const LgStatic& F = *v.lg;
   const LgShifts Sh = engine_lg_shifts(e);
-  const int p = F.p, K = F.K, nr = F.n_rates;
+  const LgNoise Nz = engine_lg_noise(e);
+  const int p = F.p, K = F.K, nr0 = F.n_rates;
+  const int nr = nr0 + (Nz.slot ? 1 : 0);   // the slots and the reduction carry Sigma_e as one more rate (grad_family)
   std::vector<int32_t> fcl;   // which cluster each family sits in
   int max_m = 0;
   rc = lg_family_clusters(e, "pgbp_lg_gradient", v, true, &fcl, &max_m);
@@ -255,7 +266,9 @@ extern "C" int pgbp_lg_gradient(pgbp_engine* e, int32_t site_begin, int32_t site
     for (int s = 0; s < ns; ++s) {
       const bool bad = inf && inf[s] != 0;
       const double* g = src ? src + (size_t)s * n_ent : nullptr;
-      for (int a = 0; a < nr * pp; ++a) dR[(size_t)s * nr * pp + a] = bad ? NAN : (g ? g[a] : 0.0);
+      for (int a = 0; a < nr0 * pp; ++a) dR[(size_t)s * nr0 * pp + a] = bad ? NAN : (g ? g[a] : 0.0);
+      if (dsigma_e)
+        for (int a = 0; a < pp; ++a) dsigma_e[(size_t)s * pp + a] = bad ? NAN : ((g && nr > nr0) ? g[nr0 * pp + a] : 0.0);
       for (int a = 0; a < p; ++a) dmu[(size_t)s * p + a] = bad ? NAN : (g ? g[nr * pp + a] : 0.0);
       if (dtheta)
         for (int a = 0; a < p; ++a) dtheta[(size_t)s * p + a] = bad ? NAN : ((g && ou) ? g[nr * pp + p + a] : 0.0);
@@ -291,10 +304,10 @@ extern "C" int pgbp_lg_gradient(pgbp_engine* e, int32_t site_begin, int32_t site
       const int n = std::min(chunk, ns - s0), gy = std::min(n, 65535);
       if (max_m <= 64)
         hipLaunchKernelGGL(grad_family<64>, dim3(nf, gy), dim3(64), lds_bytes, v.st, v.pool, pl.pool_stride(), v.boff, v.bdim,
-                           v.bs16, pl.fast_p, F, M, Sh, d_fcl.get(), nf, site_begin + s0, n, d_slots.get(), d_info.get(), s0);
+                           v.bs16, pl.fast_p, F, M, Sh, Nz, d_fcl.get(), nf, site_begin + s0, n, d_slots.get(), d_info.get(), s0);
       else
         hipLaunchKernelGGL(grad_family<256>, dim3(nf, gy), dim3(256), lds_bytes, v.st, v.pool, pl.pool_stride(), v.boff, v.bdim,
-                           v.bs16, pl.fast_p, F, M, Sh, d_fcl.get(), nf, site_begin + s0, n, d_slots.get(), d_info.get(), s0);
+                           v.bs16, pl.fast_p, F, M, Sh, Nz, d_fcl.get(), nf, site_begin + s0, n, d_slots.get(), d_info.get(), s0);
       hipLaunchKernelGGL(grad_reduce_blocks, dim3((n_ent + 63) / 64, nfb, gy), dim3(256), 0, v.st, d_slots.get(), nf, p, nr, n_ent, n,
                          d_part.get());
       hipLaunchKernelGGL(grad_reduce_final, dim3(n_ent, gy), dim3(256), 0, v.st, d_part.get(), nfb, n_ent, n, d_out.get(), s0);
@@ -309,4 +322,14 @@ extern "C" int pgbp_lg_gradient(pgbp_engine* e, int32_t site_begin, int32_t site
   for (int s = 0; s < ns; ++s) inf[s] = inf[s] == 0x7fffffff ? 0 : inf[s];
   scatter(out.data(), inf.data());
   return PGBP_OK;
+}
+
+extern "C" int pgbp_lg_gradient(pgbp_engine* e, int32_t site_begin, int32_t site_end, double* dR, double* dmu, double* dalpha,
+                                double* dtheta, int32_t* info) {
+  return lg_gradient(e, site_begin, site_end, dR, dmu, dalpha, dtheta, nullptr, info);
+}
+
+extern "C" int pgbp_lg_gradient_noise(pgbp_engine* e, int32_t site_begin, int32_t site_end, double* dR, double* dmu,
+                                      double* dalpha, double* dtheta, double* dsigma_e, int32_t* info) {
+  return lg_gradient(e, site_begin, site_end, dR, dmu, dalpha, dtheta, dsigma_e, info);
 }

@@ -13,6 +13,8 @@
 //   cov  = [-B  I] Cov(u_Z) [-B  I]' + V_PP - B V_OP
 //   E[u_T] = sum_k qc_k m[idx_k(T)] (+ qc_k mu_T of a fixed-root parent),  Cov(u_A, u_B) = sum_{a, b} qc_a qc_b S[idx_a(A), idx_b(B)]
 // over the cluster parents, idx_k(t) = parent_pos + popcount(parent_mask below t).
+// With tip noise set (pgbp_lg_set_tip_noise) V is V + E for a noisy tip at all of Z (the blocks E_PP and E_PO as well as E_OO):
+// the moments are those of the missing entries of the OBSERVATION y = x + eps, not of the trait value under it.
 //
 // impute_family: one workgroup per (listed family, site) solves the family's cluster in LDS (mom_solve: Sigma never leaves the
 // LDS; skipped when no parent is in a cluster: a star tree under a fixed root), forms V_ZZ (Z ordered O first, then P),
@@ -54,7 +56,8 @@ __host__ __device__ inline size_t impute_lds_doubles(int max_m, int p, int K, si
 template <int NT>
 __global__ __launch_bounds__(NT) void impute_family(const double* __restrict__ pool, int64_t pool_stride,
                                                     const int64_t* __restrict__ boff, const int32_t* __restrict__ bdim, int bs,
-                                                    int fp, LgStatic F, LgParams M, LgShifts Sh, const int32_t* __restrict__ fam,
+                                                    int fp, LgStatic F, LgParams M, LgShifts Sh, LgNoise Nz,
+                                                    const int32_t* __restrict__ fam,
                                                     const int32_t* __restrict__ fcl, const unsigned long long* __restrict__ pred,
                                                     int n_fam, int site0, int n_sites, double* __restrict__ mean,
                                                     double* __restrict__ cov, int32_t* __restrict__ info) {
@@ -68,6 +71,7 @@ __global__ __launch_bounds__(NT) void impute_family(const double* __restrict__ p
   const unsigned long long P = pred[ti] & full & ~O;
   const int no = __popcll(O), nq = __popcll(P), nz = no + nq;
   const int row = F.data_row[f];
+  const int sn = lg_noise_slot(Nz, f);
   // LDS: [W | dv] of mom_solve, then this kernel's arrays
   double* __restrict__ W = imp_lds;
   double* __restrict__ dv = imp_lds + m * ld;
@@ -146,6 +150,7 @@ __global__ __launch_bounds__(NT) void impute_family(const double* __restrict__ p
       const int e = zidx[i] + zidx[j] * p;
       double v = 0.0;
       for (int k = 0; k < np; ++k) v = v + cf[K + k] * S.R[(int64_t)F.color[(size_t)f * K + k] * p * p + e];
+      if (sn >= 0) v = v + lg_noise_E(Nz, sn, zidx[i], zidx[j], p, as);   // a noisy tip: the observation's V + E, blocks E_PP, E_PO included
       Vz[i * nz + j] = v;
     }
     __syncthreads();
@@ -356,6 +361,7 @@ extern "C" int pgbp_lg_impute(pgbp_engine* e, int32_t site_begin, int32_t site_e
   const Plan& pl = *v.plan;
   const LgStatic& F = *v.lg;
   const LgShifts Sh = engine_lg_shifts(e);
+  const LgNoise Nz = engine_lg_noise(e);
   const int p = F.p, K = F.K, n = (int)fams.size();
   size_t stage = 0;   // a packed record's plain copy
   for (int i = 0; i < n && v.bs16; ++i) {
@@ -396,11 +402,11 @@ extern "C" int pgbp_lg_impute(pgbp_engine* e, int32_t site_begin, int32_t site_e
       const int nsc = std::min(chunk, ns - s0), gy = std::min(nsc, 65535);
       if (max_m <= 64)
         hipLaunchKernelGGL(impute_family<64>, dim3(n, gy), dim3(64), lds_bytes, v.st, v.pool, pl.pool_stride(), v.boff, v.bdim,
-                           v.bs16, pl.fast_p, F, M, Sh, d_fams.get(), d_cls.get(), d_pred.get(), n, site_begin + s0, nsc,
+                           v.bs16, pl.fast_p, F, M, Sh, Nz, d_fams.get(), d_cls.get(), d_pred.get(), n, site_begin + s0, nsc,
                            d_mean.get(), d_cov.get(), d_info.get());
       else
         hipLaunchKernelGGL(impute_family<256>, dim3(n, gy), dim3(256), lds_bytes, v.st, v.pool, pl.pool_stride(), v.boff, v.bdim,
-                           v.bs16, pl.fast_p, F, M, Sh, d_fams.get(), d_cls.get(), d_pred.get(), n, site_begin + s0, nsc,
+                           v.bs16, pl.fast_p, F, M, Sh, Nz, d_fams.get(), d_cls.get(), d_pred.get(), n, site_begin + s0, nsc,
                            d_mean.get(), d_cov.get(), d_info.get());
       herr = hipGetLastError();
       const size_t o = (size_t)s0 * n, len = (size_t)nsc * n;

@@ -222,6 +222,26 @@ void launch_lg_shift(const LgStatic& F, const LgParams& M, const LgShifts& S, co
 void launch_lg_shift_uni_sm(const LgStatic& F, const LgParams& M, const LgShifts& S, const int32_t* d_shcl, int n_shcl,
                             double* pool_sm, double* fpool_sm, const int64_t* d_poff, const int32_t* d_dim, int n_sites,
                             hipStream_t st);
+// Measurement error at the tips (pgbp_lg_set_tip_noise): the variance of a noisy tip family gains
+// E_f = scale_f Sigma_e + diag(se2_f).  A struct of its own, as LgShifts is.  slot == null: no noise is set.
+struct LgNoise {
+  const int32_t* slot;     // [n_families]: index into scale / se2 of that tip family, -1: none
+  const double* scale;     // [n]
+  const double* sigma_e;   // [p][p] (symmetric), per_site: [n_sites][p][p]
+  const double* se2;       // null, or [n][p], per_site: [n_sites][n][p]
+  int32_t per_site, n;
+  const double* se2_sm;    // univariate per-site batches: se2 once more as [n][site] (rows padded: sm_row), else null
+};
+// the correction of a fill for the tip noise (pgbp_noise.hip), launched after it and after the shift correction: one workgroup
+// per (cluster of d_ncl, site) adds Delta J, Delta h and Delta g to the records in pool and, when not null, fpool (current
+// layout).  max_dim_ncl: the largest dimension among the clusters of d_ncl (lg_noise_lds_bytes: what the kernel needs for it)
+size_t lg_noise_lds_bytes(int p, int K, int max_dim_ncl);
+void launch_lg_noise(const LgStatic& F, const LgParams& M, const LgShifts& S, const LgNoise& Nz, const int32_t* d_ncl, int n_ncl,
+                     double* pool, int64_t pool_stride, double* fpool, int64_t fpool_stride, const int64_t* d_boff,
+                     const int32_t* d_dim, int bs16, int fast_p, int max_dim_ncl, int n_sites, hipStream_t st);
+void launch_lg_noise_uni_sm(const LgStatic& F, const LgParams& M, const LgShifts& S, const LgNoise& Nz, const int32_t* d_ncl,
+                            int n_ncl, double* pool_sm, double* fpool_sm, const int64_t* d_poff, const int32_t* d_dim,
+                            int n_sites, hipStream_t st);
 // one workgroup per (cluster, site); pool / fpool in the current layout (fpool may be null: beliefs only)
 void launch_lg_fill(const LgStatic& F, const LgParams& M, double* pool, int64_t pool_stride, double* fpool,
                     int64_t fpool_stride, const int64_t* d_boff, const int32_t* d_dim, int bs16, int fast_p, int max_dim,
@@ -309,6 +329,8 @@ const Plan* engine_plan(const pgbp_engine* e);
 bool engine_lg_params(const pgbp_engine* e, LgParams* out);
 // the shifts of pgbp_lg_set_shifts (device pointers); slot == null: none set
 LgShifts engine_lg_shifts(const pgbp_engine* e);
+// the tip noise of pgbp_lg_set_tip_noise (device pointers); slot == null: none set
+LgNoise engine_lg_noise(const pgbp_engine* e);
 // Which cluster each family of pgbp_lg_setup's table sits in: the table's CSR (LgStatic::cl_off, cl_fam) back from the device, a
 // word per family, inverted to fcl[f] (one entry per family).  max_m (may be null): the largest dimension among the clusters
 // that hold a family, 0 without families.  check_dims: a family in a cluster of more than kLdsMaxDim variables fails the call,

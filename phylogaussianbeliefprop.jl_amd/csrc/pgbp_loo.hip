@@ -9,6 +9,8 @@
 //   D = V - S,   P = V D^-1 V (covariance),   d = V D^-1 r = y_O - mean,
 //   lpd = -(o log 2pi + 2 log det V - log det D + r' D^-1 r) / 2          (d' P^-1 d = r' D^-1 r).
 // D is positive definite unless the other data leave u undetermined.
+// With tip noise set (pgbp_lg_set_tip_noise) the tip's variable is the OBSERVATION y = x + eps: V is V + E_OO for a noisy tip,
+// here as in the factor, and the moments are those of the predicted observation.
 //
 // Stage 1 (loo_family): one workgroup per (tip family, site) solves the family's cluster in LDS (mom_solve: Sigma never leaves
 // the LDS), forms V, D = V - S and the right-hand sides [V | r], factorises D = L L' (left-looking Cholesky, the lower
@@ -47,7 +49,8 @@ __host__ __device__ inline size_t loo_extra_ints(int p, int K) { return (size_t)
 template <int NT>
 __global__ __launch_bounds__(NT) void loo_family(const double* __restrict__ pool, int64_t pool_stride,
                                                  const int64_t* __restrict__ boff, const int32_t* __restrict__ bdim, int bs,
-                                                 int fp, LgStatic F, LgParams M, LgShifts Sh, const int32_t* __restrict__ tip_fam,
+                                                 int fp, LgStatic F, LgParams M, LgShifts Sh, LgNoise Nz,
+                                                 const int32_t* __restrict__ tip_fam,
                                                  const int32_t* __restrict__ tip_cluster, int n_tip, int site0, int n_sites,
                                                  double* __restrict__ mean, double* __restrict__ cov,
                                                  double* __restrict__ lpd, int32_t* __restrict__ info) {
@@ -60,6 +63,7 @@ __global__ __launch_bounds__(NT) void loo_family(const double* __restrict__ pool
   const unsigned long long O = F.child_mask ? (F.child_mask[f] & full) : full;
   const int mo = __popcll(O), ldy = mo + 1;
   const int row = F.data_row[f];
+  const int sn = lg_noise_slot(Nz, f);
   // LDS: [W | dv] of mom_solve, then this kernel's arrays
   double* __restrict__ W = loo_lds;
   double* __restrict__ dv = loo_lds + m * ld;
@@ -125,6 +129,7 @@ __global__ __launch_bounds__(NT) void loo_family(const double* __restrict__ pool
       const int e = oidx[i] + oidx[j] * p;
       double v = 0.0;
       for (int k = 0; k < np; ++k) v = v + cf[K + k] * S.R[(int64_t)F.color[(size_t)f * K + k] * p * p + e];
+      if (sn >= 0) v = v + lg_noise_E(Nz, sn, oidx[i], oidx[j], p, as);   // a noisy tip: the observation's variance V + E
       Vm[i * mo + j] = v;
       Ym[i * ldy + j] = v;
     }
@@ -314,6 +319,7 @@ extern "C" int pgbp_lg_loo(pgbp_engine* e, int32_t site_begin, int32_t site_end,
   const Plan& pl = *v.plan;
   const LgStatic& F = *v.lg;
   const LgShifts Sh = engine_lg_shifts(e);
+  const LgNoise Nz = engine_lg_noise(e);
   const int p = F.p, K = F.K, nt = (int)tips.size();
   size_t stage = 0;   // a packed record's plain copy
   for (int i = 0; i < nt && v.bs16; ++i) {
@@ -357,10 +363,10 @@ extern "C" int pgbp_lg_loo(pgbp_engine* e, int32_t site_begin, int32_t site_end,
       const int n = std::min(chunk, ns - s0), gy = std::min(n, 65535);
       if (max_m <= 64)
         hipLaunchKernelGGL(loo_family<64>, dim3(nt, gy), dim3(64), lds_bytes, v.st, v.pool, pl.pool_stride(), v.boff, v.bdim,
-                           v.bs16, pl.fast_p, F, M, Sh, d_tips.get(), d_tcl.get(), nt, site_begin + s0, n, d_mean.get(), d_cov.get(), d_lpd.get(), d_info.get());
+                           v.bs16, pl.fast_p, F, M, Sh, Nz, d_tips.get(), d_tcl.get(), nt, site_begin + s0, n, d_mean.get(), d_cov.get(), d_lpd.get(), d_info.get());
       else
         hipLaunchKernelGGL(loo_family<256>, dim3(nt, gy), dim3(256), lds_bytes, v.st, v.pool, pl.pool_stride(), v.boff, v.bdim,
-                           v.bs16, pl.fast_p, F, M, Sh, d_tips.get(), d_tcl.get(), nt, site_begin + s0, n, d_mean.get(), d_cov.get(), d_lpd.get(), d_info.get());
+                           v.bs16, pl.fast_p, F, M, Sh, Nz, d_tips.get(), d_tcl.get(), nt, site_begin + s0, n, d_mean.get(), d_cov.get(), d_lpd.get(), d_info.get());
       hipLaunchKernelGGL(loo_reduce, dim3(gy), dim3(256), 0, v.st, d_lpd.get(), nt, n, d_total.get(), s0);
       herr = hipGetLastError();
       const size_t o = (size_t)s0 * nt, len = (size_t)n * nt;

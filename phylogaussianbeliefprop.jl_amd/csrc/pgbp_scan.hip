@@ -52,7 +52,8 @@ __host__ __device__ inline size_t scan_stage_offset(int m, int p, int K) {
 template <int NT>
 __global__ __launch_bounds__(NT) void scan_family(const double* __restrict__ pool, int64_t pool_stride,
                                                   const int64_t* __restrict__ boff, const int32_t* __restrict__ bdim, int bs,
-                                                  int fp, LgStatic F, LgParams M, LgShifts Sh, const int32_t* __restrict__ fam_cluster,
+                                                  int fp, LgStatic F, LgParams M, LgShifts Sh, LgNoise Nz,
+                                                  const int32_t* __restrict__ fam_cluster,
                                                   int n_fam, int site0, int n_sites, double min_info, double* __restrict__ jump,
                                                   double* __restrict__ lr, unsigned long long* __restrict__ ident,
                                                   double* __restrict__ hinf, int32_t* __restrict__ info, int info0) {
@@ -110,7 +111,7 @@ __global__ __launch_bounds__(NT) void scan_family(const double* __restrict__ poo
       __syncthreads();   // (the previous site's arrays have been read)
     }
     // a root-prior family has no edge; its cluster's failure is reported as the edge sweep reports it
-    if (st == 0 && np > 0 && !fam_score_T<NT>(L, F, M, Sh, S, f, m, O, as, t)) st = 1;
+    if (st == 0 && np > 0 && !fam_score_T<NT>(L, F, M, Sh, Nz, S, f, m, O, as, t)) st = 1;
     if (st != 0) {
       write_none(NAN);
       if (t == 0) atomicMin(info + info0 + site, c + 1);
@@ -232,6 +233,7 @@ extern "C" int pgbp_lg_shift_scan(pgbp_engine* e, int32_t site_begin, int32_t si
   const Plan& pl = *v.plan;
   const LgStatic& F = *v.lg;
   const LgShifts Sh = engine_lg_shifts(e);
+  const LgNoise Nz = engine_lg_noise(e);
   const int p = F.p, K = F.K;
   std::vector<int32_t> fcl;   // which cluster each family sits in
   int max_m = 0;
@@ -280,11 +282,11 @@ extern "C" int pgbp_lg_shift_scan(pgbp_engine* e, int32_t site_begin, int32_t si
       const int n = std::min(chunk, ns - s0), gy = std::min(n, 65535);
       if (max_m <= 64)
         hipLaunchKernelGGL(scan_family<64>, dim3(nf, gy), dim3(64), lds_bytes, v.st, v.pool, pl.pool_stride(), v.boff, v.bdim,
-                           v.bs16, pl.fast_p, F, M, Sh, d_fcl.get(), nf, site_begin + s0, n, min_info, d_jump.get(), d_lr.get(),
+                           v.bs16, pl.fast_p, F, M, Sh, Nz, d_fcl.get(), nf, site_begin + s0, n, min_info, d_jump.get(), d_lr.get(),
                            d_id.get(), d_hinf.get(), d_info.get(), s0);
       else
         hipLaunchKernelGGL(scan_family<256>, dim3(nf, gy), dim3(256), lds_bytes, v.st, v.pool, pl.pool_stride(), v.boff, v.bdim,
-                           v.bs16, pl.fast_p, F, M, Sh, d_fcl.get(), nf, site_begin + s0, n, min_info, d_jump.get(), d_lr.get(),
+                           v.bs16, pl.fast_p, F, M, Sh, Nz, d_fcl.get(), nf, site_begin + s0, n, min_info, d_jump.get(), d_lr.get(),
                            d_id.get(), d_hinf.get(), d_info.get(), s0);
       herr = hipGetLastError();
       const size_t n1 = (size_t)n * nf, o1 = (size_t)s0 * nf;

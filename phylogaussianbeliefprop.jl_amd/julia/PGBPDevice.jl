@@ -382,6 +382,37 @@ Number of mean shifts in force (pgbp_lg_shift_count): 0 when none is set, -1 wit
 lg_shift_count(o::DeviceClusterGraphBelief) = Int(@ccall LIB.pgbp_lg_shift_count(o.handle::Ptr{Cvoid})::Int32)
 
 """
+    lg_set_tip_noise!(obj, families, sigma_e; scale = ones(length(families)), se2 = nothing)
+
+Measurement error at the tips (pgbp_lg_set_tip_noise): the conditional variance of every listed tip family (0-based indices
+into the family table given to pgbp_lg_setup) gains `scale[f] * sigma_e + Diagonal(se2[:, f])`.  `sigma_e` is `p x p`
+symmetric, or `p x p x n_sites` for one per site (`se2` is then `p x length(families) x n_sites`); `se2` may be `nothing`.
+An empty `families` clears the noise; the call replaces the previous list.  The next pgbp_lg_assignfactors or
+pgbp_enqueue_loglik_lg uses it; the sweeps read the current noise (lg_loo and lg_impute then predict the observation of a
+noisy tip).  An invalid entry is an error and nothing changes.
+"""
+function lg_set_tip_noise!(o::DeviceClusterGraphBelief, families::AbstractVector{<:Integer}, sigma_e::AbstractArray{Float64};
+                           scale::AbstractVector{<:Real} = ones(Base.length(families)),
+                           se2::Union{Nothing,AbstractArray{Float64}} = nothing)
+    fam = Vector{Int32}(families)
+    sc = Vector{Float64}(scale)
+    sig = Array{Float64}(sigma_e)
+    per_site = ndims(sig) == 3 ? Int32(1) : Int32(0)
+    s2 = se2 === nothing ? Ptr{Float64}(C_NULL) : Array{Float64}(se2)
+    check(o.handle, @ccall LIB.pgbp_lg_set_tip_noise(o.handle::Ptr{Cvoid}, Int32(Base.length(fam))::Int32, fam::Ptr{Int32},
+                                                     sc::Ptr{Float64}, sig::Ptr{Float64}, s2::Ptr{Float64},
+                                                     per_site::Int32)::Cint)
+    return nothing
+end
+
+"""
+    lg_tip_noise_count(obj) -> Int
+
+Number of noisy tips in force (pgbp_lg_tip_noise_count): 0 when none is set, -1 without a family table.
+"""
+lg_tip_noise_count(o::DeviceClusterGraphBelief) = Int(@ccall LIB.pgbp_lg_tip_noise_count(o.handle::Ptr{Cvoid})::Int32)
+
+"""
     lg_shift_scan(obj, p, nfamilies; min_info = 1e-8) -> (jump, lr, identified, information)
 
 Every edge scanned for a mean shift from the current beliefs (pgbp_lg_shift_scan: one sweep over the node families).  Per

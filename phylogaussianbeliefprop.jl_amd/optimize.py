@@ -101,7 +101,7 @@ def _check_gradient_mode(gradient):
 
 
 def calibrate_optimize_cliquetree_(beliefs, schedule_tree, R0, mu0, extra_rates=(), maxiter=200, diagonal=False,
-                                   gradient="central"):
+                                   gradient="central", sigma_e0=None):
     """calibrate_optimize_cliquetree! (src/calibration.jl:183-221) for a homogeneous Brownian motion (univariate or full
     rate matrix): maximise the log-likelihood over (R, mu); the root prior variance, if the root is random, stays fixed
     (`extra_rates`: the matrices that follow R in the rate table of lg_setup, e.g. the root prior variance).
@@ -110,11 +110,17 @@ def calibrate_optimize_cliquetree_(beliefs, schedule_tree, R0, mu0, extra_rates=
     gradient: "central" (default) -- central differences, 2 n_theta evaluations per gradient; "analytic" -- value and
     exact gradient from ONE calibration and one sweep over the node families (loglik_and_gradient_lg), pulled back
     through the transform.  `opt.n_device_evals` counts the device evaluations either way.
+    sigma_e0: None (default: nothing below applies), or the start value of the within-species covariance Sigma_e of the tip
+    noise in force (set_tip_noise_lg: its families, scale and se2 stay as they are, shared over the sites).  Sigma_e is then
+    estimated jointly with R and mu, through the same transform as R (log-Cholesky; its diagonal when `diagonal`), with
+    either gradient mode ("analytic": dsigma_e of gradient_lg).  The estimate is returned as `opt.sigma_e` and left in force.
     Returns (R, mu, loglik, scipy result)."""
     _check_gradient_mode(gradient)
     p = beliefs._lg_p
     tf = _BMTransform(p, diagonal)
     beliefs._ensure_schedule([schedule_tree])
+    if sigma_e0 is not None:
+        return _optimize_with_sigma_e(beliefs, schedule_tree, tf, R0, mu0, extra_rates, maxiter, gradient, sigma_e0)
     count = [0]
     memo = {}
 
@@ -155,6 +161,66 @@ def calibrate_optimize_cliquetree_(beliefs, schedule_tree, R0, mu0, extra_rates=
         opt = _minimise(score, tf.forward(R0, mu0), maxiter)
     opt.n_device_evals = count[0]
     R, mu = tf.back(opt.x)
+    return R, mu, -float(opt.fun), opt
+
+
+def _optimize_with_sigma_e(beliefs, schedule_tree, tf, R0, mu0, extra_rates, maxiter, gradient, sigma_e0):
+    """calibrate_optimize_cliquetree_ over (R, mu, Sigma_e): theta = [transform of (R, mu) | transform of Sigma_e]."""
+    p = tf.p
+    noise = getattr(beliefs, "_lg_noise", None)
+    if noise is None:
+        raise ValueError("calibrate_optimize_cliquetree_: sigma_e0 given but no tip noise is set (call set_tip_noise_lg first)")
+    if noise["per_site"]:
+        raise ValueError("calibrate_optimize_cliquetree_: sigma_e0 needs a shared sigma_e, the noise in force is per site")
+    nt = len(tf.forward(R0, mu0))
+    zero = np.zeros(p)
+    count = [0]
+    memo = {}
+
+    def unpack(theta):
+        R, mu = tf.back(theta[:nt])
+        S, _ = tf.back(np.concatenate([theta[nt:], zero]))
+        return R, mu, S
+
+    def fill(theta):
+        """The factors under theta; False where R or Sigma_e is not positive definite."""
+        R, mu, S = unpack(theta)
+        try:
+            np.linalg.cholesky(R)
+            np.linalg.cholesky(S)
+        except np.linalg.LinAlgError:
+            return False
+        beliefs.set_tip_noise_lg(noise["families"], S, noise["scale"], noise["se2"])
+        beliefs.assignfactors_lg_(np.stack([R] + [np.atleast_2d(np.asarray(x, float)) for x in extra_rates]), mu)
+        count[0] += 1
+        return True
+
+    def score(theta):
+        if not fill(theta):
+            return np.inf
+        ll, info = beliefs.loglik_lg()
+        return np.inf if (info[0] or not np.isfinite(ll[0])) else -float(ll[0])
+
+    def value_and_grad(theta):
+        key = np.asarray(theta, float).tobytes()
+        if key not in memo:
+            memo.clear()
+            memo[key] = (np.inf, np.zeros(len(theta)))
+            if fill(theta):
+                ll, g = beliefs.loglik_and_gradient_lg(schedule_tree, all_sites=True)
+                if not g["info"][0] and np.isfinite(ll[0]):
+                    gs = tf.pullback(np.concatenate([theta[nt:], zero]), g["dsigma_e"][0], zero)[:len(theta) - nt]
+                    memo[key] = (-float(ll[0]), -np.concatenate([tf.pullback(theta[:nt], g["dR"][0, 0], g["dmu"][0]), gs]))
+        return memo[key]
+    x0 = np.concatenate([tf.forward(R0, mu0), tf.forward(sigma_e0, zero)[:-p]])
+    if gradient == "analytic":
+        opt = _minimise(lambda x: value_and_grad(x)[0], x0, maxiter, grad=lambda x: value_and_grad(x)[1])
+    else:
+        opt = _minimise(score, x0, maxiter)
+    opt.n_device_evals = count[0]
+    R, mu, S = unpack(opt.x)
+    fill(opt.x)
+    opt.sigma_e = S
     return R, mu, -float(opt.fun), opt
 
 
