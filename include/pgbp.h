@@ -619,6 +619,77 @@ void    pgbp_sample_scratch_limits(int64_t factor_doubles, int64_t draw_doubles)
 int     pgbp_sample_posterior_timed(pgbp_engine* e, int32_t tree, int32_t site_begin, int32_t site_end, int32_t n_draws,
                                     const double* z, double* x, int32_t* info, double* ms4);
 
+/* ---- the model run forwards: simulated traits, and tip data without a new set-up ------------------ */
+/* NODE TOPOLOGY of the family table.  pgbp_lg_families names a family's parents by their position in a cluster, which is not
+ * enough to walk the network; this call adds who they are:
+ *   parent_family [n_families * max_parents]: entry f * K + k = the family whose CHILD is parent k of family f; -1: the fixed
+ *                 root (its value is mu); -2: a root without a proper prior (pgbp_lg_simulate is then refused); entries with
+ *                 k >= n_parents[f] are not read.
+ * Every entry must be in range and < f (families are in preorder: parents come first).  The host levels the table -- the root
+ * and a root-prior family have level 0, every other family 1 + the largest level of its parents -- and keeps the families
+ * grouped by level on the device.  PGBP_ERR_STATE without a family table; PGBP_ERR_INVALID with NOTHING changed and a text that
+ * names the entry ("family F, parent K: ...") otherwise.  A new pgbp_lg_setup clears the topology; pgbp_lg_set_edges,
+ * pgbp_lg_set_shifts and pgbp_lg_set_tip_noise leave it alone. */
+int     pgbp_lg_set_topology(pgbp_engine* e, const int32_t* parent_family);
+/* TIP DATA in and out without a new pgbp_lg_setup, for sites [site_begin, site_end): data [sites][n_rows][p], the set-up's
+ * layout.  The missing-data pattern (child_mask) stays the set-up's: an entry outside a tip's mask is stored as the set-up
+ * stores it (as given; not finite: 0) and ignored; an entry inside it that is not finite is PGBP_ERR_INVALID with NOTHING
+ * changed (the text names the family).  The [row][site] copy of a univariate batch is kept in step.  Takes effect as
+ * pgbp_lg_set_shifts does -- at the next pgbp_lg_assignfactors or pgbp_enqueue_loglik_lg; nothing is refilled by the setter --
+ * and after that fill the engine's state is bit for bit the state of a fresh engine set up with that data.
+ * PGBP_ERR_STATE without a family table, PGBP_ERR_INVALID for a bad site range or a NULL buffer.  One copy (and one transpose
+ * launch for a univariate batch) and one stream synchronisation. */
+int     pgbp_lg_set_data(pgbp_engine* e, int32_t site_begin, int32_t site_end, const double* data);
+int     pgbp_lg_get_data(pgbp_engine* e, int32_t site_begin, int32_t site_end, double* data);
+/* SIMULATE every node of the network from the CURRENT model -- the parameters of the last pgbp_lg_assignfactors, the edges,
+ * shifts and tip noise in force -- for sites [site_begin, site_end).  Sites are replicates: an engine with B sites yields B data
+ * sets (with per-site parameters, shifts or noise each under its own).
+ * Semantics.  Families in index order; family f with parents pf(k) = parent_family[f * K + k], the coefficients qc_k, vc_k, wc_k
+ * the sweeps use (OU: a = exp(-alpha t), qc = gamma a, vc = gamma^2 (1 - a^2), wc = gamma (1 - a); BM: gamma, gamma^2 t, 0), the
+ * shifts s_k and the noise E_f of the site.  The child's state, ALL p traits whatever the scope masks, is
+ *     x_f = sum_{k: pf(k) >= 0} qc_k x_pf(k)  +  off_f  +  L_f z_f,
+ *     off_f = (sum_k wc_k) theta + sum_k gamma_k s_k + sum_{k: pf(k) = -1} qc_k mu        (the terms in this order),
+ *     V_f = sum_k vc_k R[colour_k] (+ E_f) = L_f L_f',   L_f LOWER triangular with a positive diagonal, traits in index order
+ * (the lower triangle of V_f is read; (L_f z_f)_t = sum_{j <= t} L_f(t, j) z_f[j] in the order of j).  E_f, all p x p of it, is
+ * added for a listed noisy tip: the value is then the OBSERVATION; tips have no children, so the joint law of the tips is the
+ * model's.  A root-prior family (no parents) has x = mu + chol(R[colour]) z.  z = 0 gives the prior mean of every node.
+ * Layout: z, x and z_out are host pointers, [sites][n_families][p]; x and z_out may be NULL.
+ * z == NULL: the device generates the normals itself, from `seed`, and z_out (when not NULL) receives them:
+ *     (r0, r1, r2, r3) = Philox4x32-10(counter = (f, t / 2, absolute site, 0), key = (seed & 0xffffffff, seed >> 32))
+ *     (Salmon et al. 2011: multipliers 0xD2511F53 on counter word 0 and 0xCD9E8D57 on word 2, key increments 0x9E3779B9 and
+ *     0xBB67AE85, ten rounds);
+ *     u1 = (((r0 >> 5) << 26 | (r1 >> 6)) + 0.5) * 2^-53,   u2 = the same of (r2, r3)   (doubles; the sum rounded to nearest);
+ *     z[t] = sqrt(-2 log u1) cos(2 pi u2) for the even trait t of the pair, z[t + 1] = sqrt(-2 log u1) sin(2 pi u2) for the odd
+ *     one (dropped when t + 1 = p), 2 pi = 6.283185307179586.
+ * The generator is stateless: the value of a (site, family, trait) does not depend on the site range, on the chunks, or on what
+ * else is in the call.  With z != NULL the seed is not read.
+ * write_data != 0: every tip family with a data row (child_pos < 0, a data row, a parent edge) writes its child_mask traits into
+ * the engine's data (and into the [row][site] copy of a univariate batch) for those sites, as pgbp_lg_set_data would; entries
+ * outside the mask keep their bytes; pgbp_lg_get_data then returns exactly x restricted to the tips.  Nothing is refilled.
+ * info[site - site_begin] (may be NULL): 0, or the 1-based index of the first family whose V_f is not positive definite: that
+ * site's x is NaN and its data are left as they were (with shared parameters, shifts and noise every site then has the same
+ * info); other sites are unaffected.
+ * Fails before any launch with PGBP_ERR_STATE without a family table, without a topology or before the first
+ * pgbp_lg_assignfactors; with PGBP_ERR_INVALID for a -2 parent in the topology (the text names the entry), a bad site range,
+ * x and z_out NULL with write_data 0, or p > 64.  Zero-length edges are out of scope, as for the fill.
+ * Device (csrc/pgbp_simulate.hip): a FACTOR phase, one grid over (family, parameter set) -- one set when parameters, shifts and
+ * noise are all shared (the phase then runs once however many sites), else one per site -- forms V_f in LDS, factors it and
+ * leaves [L_f packed | qc | off]; an APPLY phase, one launch per topology level over (family of the level, site, trait).  No
+ * atomics, every sum in index order with contraction off: two calls return the same bytes.  Sites are cut into chunks
+ * (pgbp_simulate_scratch_limits); with x == NULL the states of a chunk are scratch only.  An engine borrowed from a pgbp_group
+ * or pgbp_patterns takes these calls like any other; there is no group-level call. */
+int     pgbp_lg_simulate(pgbp_engine* e, int32_t site_begin, int32_t site_end, const double* z, uint64_t seed, double* x,
+                         double* z_out, int32_t write_data, int32_t* info);
+/* Bounds of the scratch of pgbp_lg_simulate, process-wide, in doubles: the factor records of a chunk of sites (default 32 Mi
+ * doubles; one set only when everything is shared) and the states of a chunk, the normals as much again (default 128 Mi
+ * doubles each); a value <= 0 restores the default.  At least one site is always taken.  The results do not depend on the
+ * chunks. */
+void    pgbp_simulate_scratch_limits(int64_t factor_doubles, int64_t state_doubles);
+/* The same call with the stream drained after each phase (measurement only: tools/time_simulate.py): ms4[0 .. 3] = wall
+ * milliseconds of {factor phase, normals generated or copied up, apply phase, copies to the host}, summed over the chunks. */
+int     pgbp_lg_simulate_timed(pgbp_engine* e, int32_t site_begin, int32_t site_end, const double* z, uint64_t seed, double* x,
+                               double* z_out, int32_t write_data, int32_t* info, double* ms4);
+
 /* ---- scores (second "next" row: SURVEY.md section 8(f)-2) -------------------------------------- */
 /* free_energy(beliefs) (src/score.jl:162-182) for every site: out3[3*site + {0,1,2}] = (average energy,
  * approximate entropy, free energy = energy - entropy); factored_energy (src/score.jl:151-154) = the same

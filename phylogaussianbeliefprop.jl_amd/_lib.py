@@ -142,6 +142,12 @@ SYMBOLS = {
     "pgbp_sample_size": (C.c_int64, [_P]),
     "pgbp_sample_scratch_limits": (None, [C.c_int64, C.c_int64]),
     "pgbp_sample_posterior_timed": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _F64P, _F64P, _I32P, _F64P]),
+    "pgbp_lg_set_topology": (C.c_int, [_P, _I32P]),
+    "pgbp_lg_set_data": (C.c_int, [_P, C.c_int32, C.c_int32, _F64P]),
+    "pgbp_lg_get_data": (C.c_int, [_P, C.c_int32, C.c_int32, _F64P]),
+    "pgbp_lg_simulate": (C.c_int, [_P, C.c_int32, C.c_int32, _F64P, C.c_uint64, _F64P, _F64P, C.c_int32, _I32P]),
+    "pgbp_lg_simulate_timed": (C.c_int, [_P, C.c_int32, C.c_int32, _F64P, C.c_uint64, _F64P, _F64P, C.c_int32, _I32P, _F64P]),
+    "pgbp_simulate_scratch_limits": (None, [C.c_int64, C.c_int64]),
     "pgbp_free_energy": (C.c_int, [_P, _F64P, _I32P]),
     "pgbp_bm_tree_setup": (C.c_int, [_P, C.POINTER(BmTree)]),
     "pgbp_bm_tree_assignfactors": (C.c_int, [_P, _F64P, _F64P, _F64P, C.c_int32]),

@@ -586,6 +586,10 @@ class ClusterGraphBelief:
                          k["parent_mask"].ctypes.data_as(C.POINTER(C.c_uint64)) if k["parent_mask"] is not None else None)
         _check(self._lib.pgbp_lg_setup(self._eng, C.byref(t)), self._eng)
         self._lg_p, self._lg_nrates = int(fam["p"]), int(fam["n_rates"])
+        if fam.get("parent_family") is not None:       # who the parents are (pgbp_lg_set_topology): simulate_lg needs it
+            k["parent_family"] = np.ascontiguousarray(fam["parent_family"], np.int32).reshape(-1)
+            assert k["parent_family"].size == nf * K, "parent_family"
+            _check(self._lib.pgbp_lg_set_topology(self._eng, L.i32p(k["parent_family"])), self._eng)
         self._lg_shift_edges = np.zeros(0, np.int32)   # a new table clears the shifts (pgbp_lg_setup)
         self._lg_noise = None                          # ... and the tip noise
         self._lg_last = None                           # ... and has no parameters yet
@@ -832,6 +836,64 @@ class ClusterGraphBelief:
     def tip_noise_count_lg(self):
         """pgbp_lg_tip_noise_count: the number of noisy tips in force (0: none)."""
         return int(self._lib.pgbp_lg_tip_noise_count(self._eng))
+
+    def set_data_lg(self, data, all_sites=True):
+        """pgbp_lg_set_data: replace the tip data given to lg_setup -- [n_sites, n_rows, p] (or [n_rows, p] on a one-site
+        object; all_sites=False: [n_rows, p] or [1, n_rows, p] for the current site) -- without a new set-up.  The
+        missing-data pattern stays the set-up's: an entry outside a tip's mask is ignored (NaN allowed), one inside it that is
+        not finite raises and leaves the data as they were.  The next assignfactors_lg_ or loglik_lg uses the new data;
+        beliefs and factors are not refilled by this call."""
+        s0, s1 = (0, self.n_sites) if all_sites else (self.site, self.site + 1)
+        rows = int(self._lg["data"].shape[1])
+        d = np.ascontiguousarray(np.asarray(data, np.float64).reshape(s1 - s0, rows, self._lg_p))
+        _check(self._lib.pgbp_lg_set_data(self._eng, s0, s1, L.f64p(d if d.size else np.zeros(1))), self._eng)
+
+    def get_data_lg(self):
+        """pgbp_lg_get_data: the tip data the device holds, [n_sites, n_rows, p] (what lg_setup, set_data_lg or
+        simulate_lg(write_data=True) left; an entry outside a tip's mask that was not finite reads 0)."""
+        rows = int(self._lg["data"].shape[1])
+        d = np.zeros((self.n_sites, rows, self._lg_p))
+        _check(self._lib.pgbp_lg_get_data(self._eng, 0, self.n_sites, L.f64p(d if d.size else np.zeros(1))), self._eng)
+        return d
+
+    def simulate_lg(self, z=None, seed=None, write_data=False, all_sites=False, return_z=False):
+        """pgbp_lg_simulate: every node of the network drawn from the CURRENT model -- the parameters of the last
+        assignfactors_lg_, the edges, shifts and tip noise in force -- in one device sweep; sites are replicates.
+        Exactly one of z and seed: z = standard normals [n_sites or 1, n_families, p] (z = 0 gives the prior means, a
+        caller can reproduce a draw from z: include/pgbp.h has the recipe), or seed = an integer < 2^64 for the device's own
+        stateless generator (Philox4x32-10 + Box-Muller: the draw of a (site, family, trait) depends on nothing else).
+        write_data: the tips' observed traits go straight into the engine's data, as set_data_lg would put them; the next
+        assignfactors_lg_ or loglik_lg uses them.  Needs the family table's `parent_family` (factors.lg_families gives it)
+        and a fixed root or a proper root prior.
+        Returns (x, info) -- with return_z (x, info, z) --: x [n_sites or 1, n_families, p], family order (a noisy tip's row
+        is its OBSERVATION); info [n_sites or 1]: 0, or the 1-based index of the first family whose conditional variance is
+        not positive definite (that site's x is NaN, its data untouched)."""
+        if (z is None) == (seed is None):
+            raise ValueError("simulate_lg takes exactly one of z and seed")
+        s0, s1 = (0, self.n_sites) if all_sites else (self.site, self.site + 1)
+        shape = (s1 - s0, len(self._lg["cluster"]), self._lg_p)
+        if z is not None:
+            z = np.ascontiguousarray(z, dtype=np.float64)
+            if z.shape != shape:
+                raise ValueError(f"z has shape {z.shape}, expected {shape}")
+        x = np.zeros(shape)
+        zo = np.zeros(shape) if return_z else None
+        info = np.zeros(s1 - s0, dtype=np.int32)
+        ptr = lambda a: None if a is None else L.f64p(a if a.size else np.zeros(1))
+        _check(self._lib.pgbp_lg_simulate(self._eng, s0, s1, ptr(z), int(seed or 0), ptr(x), ptr(zo), int(bool(write_data)),
+                                          L.i32p(info)), self._eng)
+        if return_z:
+            return x, info, (zo if z is None else z.copy())
+        return x, info
+
+    def simulated_nodes(self, x, site=0):
+        """The states of simulate_lg by node, for an object built from labelled beliefs: {node label: [p]} for every node
+        that has a family (the fixed root has none: its value is mu).  x: [sites, n_families, p]; site: which row."""
+        if self._objs is None or self.node2family is None:
+            raise ValueError("simulated_nodes needs labelled beliefs (an object built from CanonicalBelief objects)")
+        x = np.asarray(x)
+        skip = len(self.node2family) - x.shape[1]   # the root has no family unless it has a proper prior
+        return {self.node2family[skip + f][0]: x[site, f].copy() for f in range(x.shape[1])}
 
     def _shift_gradient_from(self, d):
         e = getattr(self, "_lg_shift_edges", np.zeros(0, np.int32))

@@ -16,6 +16,7 @@
 #include "pgbp_devmem.hpp"
 #include "pgbp_internal.hpp"
 #include "pgbp_kernels.hpp"
+#include "pgbp_topology.hpp"
 
 using namespace pgbp;
 
@@ -206,6 +207,14 @@ struct pgbp_engine {
   LgNoiseBufs lg_noise_bufs;
   int32_t lg_n_noise_cl = 0, lg_noise_max_dim = 0;
   std::vector<char> lg_h_tip;
+  // pgbp_lg_set_data: what its checks read of the table (host side): data row and child_mask (empty: none) of every family
+  std::vector<int32_t> lg_h_row;
+  std::vector<unsigned long long> lg_h_cmask;
+  // pgbp_lg_set_topology: parents by family and the families grouped by level (pgbp_topology.hpp)
+  bool lg_topo = false;
+  int32_t lg_topo_improper = -1;
+  std::vector<int32_t> lg_h_level_off;
+  DevBuf<int32_t> d_lg_pf, d_lg_level_fam;
   std::string err;
   // a step of an asynchronous enqueue that could not be issued (a workspace that could not be allocated: ensure_ws has
   // set `err`): the launches that needed it were skipped; every entry point that enqueued, and the next pgbp_sync /
@@ -1805,6 +1814,15 @@ int pgbp_lg_setup(pgbp_engine* e, const pgbp_lg_families* f) {
   e->lg_n_noise_cl = e->lg_noise_max_dim = 0;
   e->lg_h_tip.assign(nf, 0);
   for (size_t i = 0; i < nf; ++i) e->lg_h_tip[i] = f->child_pos[i] < 0 && f->data_row[i] >= 0 && f->n_parents[i] >= 1;
+  e->lg_h_row.assign(f->data_row, f->data_row + nf);
+  e->lg_h_cmask.clear();
+  if (f->child_mask)
+    for (size_t i = 0; i < nf; ++i) e->lg_h_cmask.push_back(cmask((int)i));
+  e->lg_topo = false;                 // ... and no topology
+  e->lg_topo_improper = -1;
+  e->lg_h_level_off.clear();
+  e->d_lg_pf.reset();
+  e->d_lg_level_fam.reset();
   const LgBufs& L = e->lg_bufs;
   e->lg = LgStatic{pp, K, f->n_rates, f->n_rows, L.off.get(), L.fam.get(), L.np.get(), L.cp.get(), L.row.get(), L.pp.get(), L.len.get(),
                    L.gam.get(), L.col.get(), L.data.get(), L.cm.get(), L.pm.get(), L.data_sm.get(), L.simple.get()};
@@ -2095,6 +2113,98 @@ int pgbp_lg_set_tip_noise(pgbp_engine* e, int32_t n, const int32_t* family, cons
 int32_t pgbp_lg_tip_noise_count(pgbp_engine* e) {
   if (!e || !e->lg_ready) return -1;
   return e->lgn.slot ? e->lgn.n : 0;
+}
+
+int pgbp_lg_set_topology(pgbp_engine* e, const int32_t* parent_family) {
+  DeviceScope device_scope(e);
+  if (!e) return PGBP_ERR_INVALID;
+  if (!e->lg_ready) return e->fail(PGBP_ERR_STATE, "pgbp_lg_set_topology: no family table (call pgbp_lg_setup first)");
+  const int K = e->lg.K, nf = e->lg_nf;
+  if (nf > 0 && !parent_family) return e->fail(PGBP_ERR_INVALID, "pgbp_lg_set_topology: no table");
+  // every check before anything changes
+  std::vector<int32_t> level_off, level_fam;
+  int32_t improper = -1;
+  std::string why;
+  if (!lg_topology_levels(nf, K, e->lg_h_np.data(), parent_family, level_off, level_fam, &improper, why))
+    return e->fail(PGBP_ERR_INVALID, "pgbp_lg_set_topology: " + why);
+  std::vector<int32_t> pf(std::max<size_t>(1, (size_t)nf * K), kTopoFixedRoot);
+  for (int f = 0; f < nf; ++f)
+    for (int k = 0; k < e->lg_h_np[f]; ++k) pf[(size_t)f * K + k] = parent_family[(size_t)f * K + k];
+  if (level_fam.empty()) level_fam.push_back(0);
+  DevBuf<int32_t> d_pf, d_lf;   // into locals: the engine takes them once both copies have been made
+  int rc;
+  if ((rc = upload(e, d_pf, pf))) return rc;
+  if ((rc = upload(e, d_lf, level_fam))) return rc;
+  e->d_lg_pf = std::move(d_pf);
+  e->d_lg_level_fam = std::move(d_lf);
+  e->lg_h_level_off = std::move(level_off);
+  e->lg_topo_improper = improper;
+  e->lg_topo = true;
+  return PGBP_OK;
+}
+
+// the range and, where the table says observed, the values: pgbp_lg_setup's checks of its data for sites [site_begin, site_end)
+static int lg_check_data(pgbp_engine* e, const char* fn, int32_t site_begin, int32_t site_end, const double* data, bool values) {
+  if (!e->lg_ready) return e->fail(PGBP_ERR_STATE, std::string(fn) + ": no family table (call pgbp_lg_setup first)");
+  if (site_begin < 0 || site_end < site_begin || site_end > e->plan.n_sites)
+    return e->fail(PGBP_ERR_INVALID, std::string(fn) + ": site range [" + std::to_string(site_begin) + ", " + std::to_string(site_end) +
+                                         ") outside the engine's " + std::to_string(e->plan.n_sites) + " sites");
+  const size_t per = (size_t)e->lg.n_rows * e->lg.p, ns = (size_t)(site_end - site_begin);
+  if (ns * per > 0 && !data) return e->fail(PGBP_ERR_INVALID, std::string(fn) + ": no data buffer");
+  if (!values) return PGBP_OK;
+  const int pp = e->lg.p;
+  const unsigned long long full = pp >= 64 ? ~0ull : ((1ull << pp) - 1ull);
+  if (e->lg_h_cmask.empty()) {
+    for (size_t i = 0; i < ns * per; ++i)
+      if (!std::isfinite(data[i]))
+        return e->fail(PGBP_ERR_INVALID, std::string(fn) + ": a tip value is missing or not finite (the table has no child_mask: the data are complete)");
+    return PGBP_OK;
+  }
+  for (int f = 0; f < e->lg_nf; ++f) {
+    if (!e->lg_h_tip[f]) continue;
+    const unsigned long long O = e->lg_h_cmask[f] & full;
+    for (size_t s = 0; s < ns; ++s)
+      for (int t = 0; t < pp; ++t)
+        if (((O >> t) & 1ull) && !std::isfinite(data[(s * e->lg.n_rows + e->lg_h_row[f]) * pp + t]))
+          return e->fail(PGBP_ERR_INVALID, std::string(fn) + ": family " + std::to_string(f) + ": a tip value is missing or not finite "
+                                               "where child_mask says observed (the missing-data pattern is the set-up's)");
+  }
+  return PGBP_OK;
+}
+
+int pgbp_lg_set_data(pgbp_engine* e, int32_t site_begin, int32_t site_end, const double* data) {
+  DeviceScope device_scope(e);
+  if (!e) return PGBP_ERR_INVALID;
+  const int rc = lg_check_data(e, "pgbp_lg_set_data", site_begin, site_end, data, true);
+  if (rc) return rc;
+  const size_t per = (size_t)e->lg.n_rows * e->lg.p, n = (size_t)(site_end - site_begin) * per;
+  if (n == 0) return PGBP_OK;
+  double* dst = e->lg_bufs.data.get() + (size_t)site_begin * per;
+  std::vector<double> clean;   // as the set-up: masked-out entries may be NaN on the host, they never reach arithmetic
+  if (!e->lg_h_cmask.empty()) {
+    clean.assign(data, data + n);
+    for (double& x : clean) if (!std::isfinite(x)) x = 0.0;
+    data = clean.data();
+  }
+  hipError_t herr = hipMemcpyAsync(dst, data, n * sizeof(double), hipMemcpyHostToDevice, e->st);
+  if (herr == hipSuccess && e->lg_bufs.data_sm)   // the [row][site] copy of a univariate batch, whole
+    launch_transpose_words_f64(e->lg_bufs.data.get(), e->lg_bufs.data_sm.get(), e->lg.n_rows, e->plan.n_sites, 1, e->st);
+  const hipError_t serr = hipStreamSynchronize(e->st);  // the host buffers may go away
+  if (herr == hipSuccess) herr = serr;
+  if (herr != hipSuccess) return e->fail(PGBP_ERR_HIP, std::string("pgbp_lg_set_data (upload): ") + hipGetErrorString(herr));
+  return PGBP_OK;
+}
+
+int pgbp_lg_get_data(pgbp_engine* e, int32_t site_begin, int32_t site_end, double* data) {
+  DeviceScope device_scope(e);
+  if (!e) return PGBP_ERR_INVALID;
+  const int rc = lg_check_data(e, "pgbp_lg_get_data", site_begin, site_end, data, false);
+  if (rc) return rc;
+  const size_t per = (size_t)e->lg.n_rows * e->lg.p, n = (size_t)(site_end - site_begin) * per;
+  if (n == 0) return PGBP_OK;
+  HIPCHK(e, hipMemcpyAsync(data, e->lg_bufs.data.get() + (size_t)site_begin * per, n * sizeof(double), hipMemcpyDeviceToHost, e->st));
+  HIPCHK(e, hipStreamSynchronize(e->st));
+  return PGBP_OK;
 }
 
 int pgbp_enqueue_loglik_lg(pgbp_engine* e, int32_t reps, const pgbp_opts* opts) {
@@ -2408,4 +2518,10 @@ bool engine_lg_params(const pgbp_engine* e, LgParams* out) {
 }
 LgShifts engine_lg_shifts(const pgbp_engine* e) { return e->lg_ready ? e->lgs : LgShifts{}; }
 LgNoise engine_lg_noise(const pgbp_engine* e) { return e->lg_ready ? e->lgn : LgNoise{}; }
+LgSimView engine_lg_sim(pgbp_engine* e) {
+  DeviceScope device_scope(e);
+  const bool ok = e->lg_ready && e->lg_topo;
+  return LgSimView{ok ? 1 : 0, e->lg_topo_improper, e->d_lg_pf.get(), e->d_lg_level_fam.get(), &e->lg_h_level_off, e->lg_nf,
+                   e->lg_bufs.data.get(), e->lg_bufs.data_sm.get()};
+}
 }  // namespace pgbp

@@ -331,6 +331,20 @@ bool engine_lg_params(const pgbp_engine* e, LgParams* out);
 LgShifts engine_lg_shifts(const pgbp_engine* e);
 // the tip noise of pgbp_lg_set_tip_noise (device pointers); slot == null: none set
 LgNoise engine_lg_noise(const pgbp_engine* e);
+// What pgbp_simulate.hip needs beyond the view: the node topology of pgbp_lg_set_topology (ready == 0: none) -- parents by
+// family on the device, the families grouped by level (level_off on the host: it outlives the call with the engine) -- and the
+// tip data as the one writer besides the set-up sees them (data_sm: null unless LgStatic::data_sm is kept).  Makes the
+// engine's device current.
+struct LgSimView {
+  int ready;
+  int32_t improper;                        // first topology entry f * K + k that is an improper root, -1: none
+  const int32_t* parent_family;            // device [n_families * K]
+  const int32_t* level_fam;                // device [n_families]
+  const std::vector<int32_t>* level_off;   // host [n_levels + 1]
+  int32_t n_families;
+  double *data, *data_sm;
+};
+LgSimView engine_lg_sim(pgbp_engine* e);
 // Which cluster each family of pgbp_lg_setup's table sits in: the table's CSR (LgStatic::cl_off, cl_fam) back from the device, a
 // word per family, inverted to fcl[f] (one entry per family).  max_m (may be null): the largest dimension among the clusters
 // that hold a family, 0 without families.  check_dims: a family in a cluster of more than kLdsMaxDim variables fails the call,

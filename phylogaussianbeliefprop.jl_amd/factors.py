@@ -20,10 +20,14 @@ def lg_families(beliefs, node2cluster, node2family, node2fixed, parent_edges, da
     scope masks (bit t = trait t): `child_mask` = an internal child's traits in scope / a tip's observed traits,
     `parent_mask` = each parent's traits in scope (src/beliefs.jl:551-559); the factor keeps the child_mask components of
     its residual, which is what absorbleaf! (src/beliefupdates.jl:266-274) and the partial-scope marginalisation of
-    assignfactors! (src/beliefs.jl:829-857) leave for the reference's models."""
+    assignfactors! (src/beliefs.jl:829-857) leave for the reference's models.
+
+    `parent_family` ([n_families * max_parents], what pgbp_lg_set_topology takes): the family whose child is each parent,
+    -1 for the fixed root, -2 for a root that is neither fixed nor given a proper prior (nothing can be simulated then)."""
     K = max([1] + [len(nf) - 1 for nf in node2family])
     out = {k: [] for k in ("cluster", "n_parents", "child_pos", "data_row")}
     ppos, length, gamma, color = [], [], [], []
+    pfam, family_of = [], {}
     pos_cache = {}
 
     if p > 64:
@@ -64,6 +68,8 @@ def lg_families(beliefs, node2cluster, node2family, node2fixed, parent_edges, da
                 continue
             out["cluster"].append(ci); out["n_parents"].append(0); out["child_pos"].append(pos[nf[0]][0])
             out["data_row"].append(-1)
+            family_of[nf[0]] = len(out["cluster"]) - 1
+            pfam += [-1] * K
             ppos += [-1] * K; length += [1.0] * K; gamma += [1.0] * K
             color += [int(root_prior_color)] + [0] * (K - 1)
             cmask.append(pos[nf[0]][1]); pmask += [full] * K
@@ -74,16 +80,21 @@ def lg_families(beliefs, node2cluster, node2family, node2fixed, parent_edges, da
         out["child_pos"].append(-1 if fixed_child else pos[nf[0]][0])
         out["data_row"].append(int(data_row[ni]) if fixed_child else -1)
         cmask.append(observed(int(data_row[ni])) if fixed_child else pos[nf[0]][1])
+        family_of[nf[0]] = len(out["cluster"]) - 1
         row_p, row_l, row_g, row_c, row_m = [-1] * K, [1.0] * K, [1.0] * K, [0] * K, [full] * K
+        row_f = [-1] * K
         for k, (pl, (t, gam, col)) in enumerate(zip(nf[1:], parent_edges[ni])):
+            # (a parent without a family is the root: fixed, or without a proper prior)
+            row_f[k] = family_of.get(pl, -1 if node2fixed[pl - 1] else -2)
             row_p[k] = -1 if node2fixed[pl - 1] else pos[pl][0]
             row_m[k] = full if node2fixed[pl - 1] else pos[pl][1]
             row_l[k], row_g[k], row_c[k] = float(t), float(gam), int(col)
-        ppos += row_p; length += row_l; gamma += row_g; color += row_c; pmask += row_m
+        ppos += row_p; length += row_l; gamma += row_g; color += row_c; pmask += row_m; pfam += row_f
     masks = {}
     if partial[0]:
         masks = dict(child_mask=np.array(cmask, np.uint64), parent_mask=np.array(pmask, np.uint64))
     return dict(**masks, p=int(p), max_parents=K, n_rates=int(n_rates), cluster=np.array(out["cluster"], np.int32),
                 n_parents=np.array(out["n_parents"], np.int32), child_pos=np.array(out["child_pos"], np.int32),
                 data_row=np.array(out["data_row"], np.int32), parent_pos=np.array(ppos, np.int32),
-                length=np.array(length, np.float64), gamma=np.array(gamma, np.float64), color=np.array(color, np.int32))
+                length=np.array(length, np.float64), gamma=np.array(gamma, np.float64), color=np.array(color, np.int32),
+                parent_family=np.array(pfam, np.int32))

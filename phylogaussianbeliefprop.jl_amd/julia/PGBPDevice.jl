@@ -459,6 +459,80 @@ function sample_posterior!(o::DeviceClusterGraphBelief, ndraws::Integer = 1;
     return x[1:sample_size(o), :]
 end
 
+# ---- the model run forwards (pgbp_lg_set_topology, pgbp_lg_set_data / pgbp_lg_get_data, pgbp_lg_simulate).  Like the rest
+# of this file these wrappers are NOT exercised in the build container (no Julia there); tests/test_gpu_simulate.py drives the
+# same five C functions through the ctypes mirror.
+
+"""
+    lg_set_topology!(obj, parent_family)
+
+Node topology of the family table (pgbp_lg_set_topology): `parent_family` is `max_parents x n_families`, entry `(k, f)` the
+0-based family whose child is parent `k` of family `f`; -1: the fixed root; -2: a root without a proper prior (`lg_simulate`
+is then refused).  Parents come before their children.  An invalid entry is an error that names it, and nothing changes.
+"""
+function lg_set_topology!(o::DeviceClusterGraphBelief, parent_family::AbstractArray{<:Integer})
+    pf = Array{Int32}(parent_family)
+    check(o.handle, @ccall LIB.pgbp_lg_set_topology(o.handle::Ptr{Cvoid}, pf::Ptr{Int32})::Cint)
+    return nothing
+end
+
+"""
+    lg_set_data!(obj, data; sites = nothing)
+
+Replace the tip data given to pgbp_lg_setup without a new set-up (pgbp_lg_set_data): `data` is `p x n_rows x length(sites)`,
+`sites` a 1-based unit range (default: as many sites as `data` has, from the first).  The missing-data pattern stays the
+set-up's.  The next pgbp_lg_assignfactors or pgbp_enqueue_loglik_lg uses the new data; nothing is refilled by this call.
+"""
+function lg_set_data!(o::DeviceClusterGraphBelief, data::AbstractArray{Float64}; sites::Union{Nothing,UnitRange{Int}} = nothing)
+    d = Array{Float64}(data)
+    r = sites === nothing ? (1:size(d, 3)) : sites
+    check(o.handle, @ccall LIB.pgbp_lg_set_data(o.handle::Ptr{Cvoid}, Int32(first(r) - 1)::Int32, Int32(last(r))::Int32,
+                                                d::Ptr{Float64})::Cint)
+    return nothing
+end
+
+"""
+    lg_get_data(obj, p, nrows, sites) -> data
+
+The tip data the device holds for the 1-based unit range `sites` (pgbp_lg_get_data): `p x nrows x length(sites)`.
+"""
+function lg_get_data(o::DeviceClusterGraphBelief, p::Integer, nrows::Integer, sites::UnitRange{Int})
+    d = zeros(p, nrows, Base.length(sites))
+    check(o.handle, @ccall LIB.pgbp_lg_get_data(o.handle::Ptr{Cvoid}, Int32(first(sites) - 1)::Int32, Int32(last(sites))::Int32,
+                                                d::Ptr{Float64})::Cint)
+    return d
+end
+
+"""
+    lg_simulate(obj, p, nfamilies, sites; z = nothing, seed = 0, write_data = false) -> (x, info)
+
+Every node of the network drawn from the current model (pgbp_lg_simulate) for the 1-based unit range `sites` (replicates):
+`x` is `p x nfamilies x length(sites)`, family order; `info[s]` is 0, or the 1-based family whose conditional variance is not
+positive definite (that site's `x` is NaN).  `z` (same shape as `x`) are the caller's standard normals -- `z = 0` gives the
+prior means --; with `z = nothing` the device draws them from `seed` (Philox4x32-10 and Box-Muller: include/pgbp.h has the
+recipe).  `write_data = true` puts the tips' observed traits into the engine's data, as `lg_set_data!` would.
+"""
+function lg_simulate(o::DeviceClusterGraphBelief, p::Integer, nfamilies::Integer, sites::UnitRange{Int};
+                     z::Union{Nothing,AbstractArray{Float64}} = nothing, seed::Integer = 0, write_data::Bool = false)
+    n = Base.length(sites)
+    x = zeros(p, nfamilies, n); info = zeros(Int32, n)
+    zz = z === nothing ? Ptr{Float64}(C_NULL) : Array{Float64}(z)
+    z === nothing || size(zz) == size(x) || error("z must be p x nfamilies x length(sites)")
+    check(o.handle, @ccall LIB.pgbp_lg_simulate(o.handle::Ptr{Cvoid}, Int32(first(sites) - 1)::Int32, Int32(last(sites))::Int32,
+                                                zz::Ptr{Float64}, UInt64(seed)::UInt64, x::Ptr{Float64},
+                                                Ptr{Float64}(C_NULL)::Ptr{Float64}, Int32(write_data)::Int32,
+                                                info::Ptr{Int32})::Cint)
+    return x, info
+end
+
+"""
+    simulate_scratch_limits(factor_doubles, state_doubles)
+
+Process-wide bounds of the scratch of `lg_simulate` in doubles (pgbp_simulate_scratch_limits); a value <= 0 restores the default.
+"""
+simulate_scratch_limits(factor_doubles::Integer, state_doubles::Integer) =
+    @ccall LIB.pgbp_simulate_scratch_limits(Int64(factor_doubles)::Int64, Int64(state_doubles)::Int64)::Cvoid
+
 "the reference's error line for a failed message (src/beliefupdates.jl:69-76): belief metadata + integrated indices"
 function report_failure(o::DeviceClusterGraphBelief, spt, res::Result, verbose::Bool)
     i = res.fail_edge + 1

@@ -411,3 +411,42 @@ def select_shifts_lg(beliefs, schedule_tree, max_shifts, min_lr=0.0, candidates=
         if not entered:
             break
     return dict(path=path, edges=list(chosen), fit=fit, loglik0=ll0)
+
+
+def bootstrap_shift_scan_lg(beliefs, schedule_tree, seed=None, z=None, min_info=1e-8):
+    """Parametric bootstrap of the shift scan on a clique tree: the null distribution of the LARGEST lr over all edges, which
+    has no closed form.  On an engine with B sites -- B replicates of one network, built with n_sites = B and the fitted null
+    model assigned (assignfactors_lg_, with the shifts and the tip noise that belong to the null in force) -- it
+      1. reads the data in force (get_data_lg), so that the caller can put them back;
+      2. simulates B data sets under the current model straight into the engine's data (simulate_lg(write_data=True,
+         all_sites=True), with the device's generator from `seed` or from the caller's normals z [B, n_families, p]);
+      3. fills, calibrates and scans every replicate at once (loglik_and_shift_scan_lg(all_sites=True, min_info=min_info));
+      4. takes per replicate the largest lr over the families select_shifts_lg would consider (dof > 0, lr finite; ties to
+         the lowest family) and the edge it would enter there (the parent edge with the largest gamma, ties to the lowest k).
+    Returns a dict: max_lr [B] (-inf for a replicate without any identified family, NaN for one whose info is not 0),
+    family [B] and edge [B, 2] = (family, k) of that maximum (-1 where there is none), loglik [B], info [B] (the simulation's,
+    else the calibration's), x [B, n_families, p] (the simulated states), data [B, n_rows, p] (the simulated tip data, as the
+    engine now holds them) and data_before (what it held: set_data_lg(out["data_before"]) restores it; nothing is refilled
+    until the next assignfactors_lg_ / loglik_lg).
+    THRESHOLD: a quantile of max_lr calibrates select_shifts_lg -- min_lr = np.quantile(max_lr, 0.95) lets a first shift
+    enter a data set WITHOUT any jump with probability about 5 % (Monte Carlo error of the quantile: about
+    sqrt(0.05 * 0.95 / B) / density; B of a few hundred).  It is the threshold of the FIRST step; later steps scan under the
+    chosen shifts, for which the same call, with those shifts in force, gives the matching null.  Exact on a clique tree
+    only, like the scan."""
+    before = beliefs.get_data_lg()
+    x, sim_info = beliefs.simulate_lg(z=z, seed=seed, write_data=True, all_sites=True)
+    ll, scan = beliefs.loglik_and_shift_scan_lg(schedule_tree, all_sites=True, min_info=min_info)
+    nf = len(beliefs._lg["cluster"])
+    K = beliefs._lg["length"].size // nf
+    gam = np.asarray(beliefs._lg["gamma"], np.float64).reshape(nf, K)
+    npar = np.asarray(beliefs._lg["n_parents"]).reshape(nf)
+    best_k = np.array([int(np.argmax(gam[f, :npar[f]])) if npar[f] > 0 else -1 for f in range(nf)])
+    info = np.where(sim_info != 0, sim_info, scan["info"])
+    lr = np.where((best_k >= 0)[None, :] & (scan["dof"] > 0) & np.isfinite(scan["lr"]), scan["lr"], -np.inf)
+    fam = np.argmax(lr, axis=1)                        # (argmax: first of ties)
+    top = lr[np.arange(lr.shape[0]), fam]
+    none = ~np.isfinite(top)
+    fam = np.where(none, -1, fam)
+    edge = np.stack([fam, np.where(none, -1, best_k[fam])], axis=1)
+    top = np.where(info != 0, np.nan, top)
+    return dict(max_lr=top, family=fam, edge=edge, loglik=ll, info=info, x=x, data=beliefs.get_data_lg(), data_before=before)

@@ -322,7 +322,8 @@ def lg_tree_table(tree: Tree, prob: Problem, p: int, colors=None):
                 cluster=(c - 1).astype(np.int32), n_parents=np.ones(N - 1, np.int32),
                 child_pos=np.where(leaf, -1, 0).astype(np.int32), data_row=np.where(leaf, c, -1).astype(np.int32),
                 parent_pos=np.where(pa_root, -1, np.where(leaf, 0, p)).astype(np.int32),
-                length=tree.length[c].astype(np.float64), gamma=np.ones(N - 1), color=col)
+                length=tree.length[c].astype(np.float64), gamma=np.ones(N - 1), color=col,
+                parent_family=np.where(pa_root, -1, tree.parent[c] - 1).astype(np.int32))   # (pgbp_lg_set_topology)
 
 def bm_loglik_pruning(tree: Tree, R: np.ndarray, mu: np.ndarray, Y: np.ndarray) -> float:
     """Independent O(n p^3) check: Felsenstein-style pruning for BM with a fixed root
