@@ -154,6 +154,26 @@ def main():
         q95 = float(np.quantile(null["max_lr"], 0.95))
         print(f"largest lr of the scan: observed {float(np.nanmax(scan['lr'])):.2f} (jump planted), bootstrap 95 % quantile "
               f"without a jump {q95:.2f} ({B} replicates) -> min_lr of select_shifts_lg")
+    # a batch of univariate problems fitted side by side: 32 OU sites on one 60-tip tree, each with its own stationary
+    # variance, alpha, theta and mu; every evaluation is one device pass for all sites (fit_sites_lg)
+    from pgbp_amd import synth as S
+    rng = np.random.default_rng(3)
+    tr = S.random_tree(60, rng)
+    ns = 32
+    depth = np.zeros(tr.nnodes)
+    for i in range(1, tr.nnodes):
+        depth[i] = depth[tr.parent[i]] + tr.length[i]
+    H = float(depth[tr.is_leaf].mean())           # (alpha H of 1 .. 3: the root value is still identified at the tips)
+    al, g2, th = rng.uniform(1, 3, ns) / H, rng.uniform(0.5, 2, ns), rng.normal(0, 2, ns)
+    X = S.simulate_ou_uni_sites(tr, 2 * al * g2, al, th, th + rng.normal(size=ns), rng)
+    prob = S.cliquetree_of_tree(tr, 1)
+    batch = P.ClusterGraphBelief.from_arrays(prob.dims, prob.sepset_clusters, prob.scope_off, prob.scope_idx, None, n_sites=ns)
+    batch.lg_setup(S.lg_tree_table(tr, prob, 1), np.ascontiguousarray(X[:, :, None]))
+    tipmean = X[:, tr.is_leaf].mean(axis=1)
+    fit = P.fit_sites_lg(batch, prob.schedule[0], "ou", np.ones(ns), tipmean, alpha0=np.full(ns, 1.0 / H), theta0=tipmean)
+    print(f"OU batch: {int(fit['converged'].sum())} of {ns} sites converged in {fit['n_device_evals']} device passes; site 0: "
+          f"alpha {fit['alpha'][0]:.3f} (simulated {al[0]:.3f}), theta {fit['theta'][0]:.3f} ({th[0]:.3f}), "
+          f"stationary variance {fit['R'][0]:.3f} ({g2[0]:.3f}), log-likelihood {fit['loglik'][0]:.4f}")
 
 
 if __name__ == "__main__":

@@ -450,6 +450,21 @@ int32_t pgbp_lg_tip_noise_count(pgbp_engine* e);
  * as dR: no atomics, two calls return the same bytes. */
 int pgbp_lg_gradient_noise(pgbp_engine* e, int32_t site_begin, int32_t site_end, double* dR, double* dmu, double* dalpha,
                            double* dtheta, double* dsigma_e, int32_t* info);
+/* pgbp_lg_gradient_noise for the sites of a UNIVARIATE BATCH, lanes = sites (csrc/pgbp_grad_uni.hip): the same quantities as
+ * documented for pgbp_lg_gradient, in the layout of pgbp_lg_gradient_noise at p = 1 -- dR [sites][n_rates], then one double per
+ * site in dmu, dalpha, dtheta and dsigma_e (NULL allowed).  Accepted only on a thread-per-site engine: p = 1, every belief of
+ * at most 2 variables, at least 8 sites; anything else is PGBP_ERR_INVALID before any launch, the reason named.  The state
+ * errors and range checks are those of pgbp_lg_gradient.
+ * A thread walks a block of 64 consecutive families for its one site and solves each family's cluster (0, 1 or 2 variables)
+ * in closed form; the blocks' partial sums are added in index order by a second kernel.  No atomics and every sum in a fixed
+ * order: two calls return the same bytes, and a site's bytes do not depend on the site range it is asked in.  The call reads
+ * the beliefs in the layout they are in (site-minor from 64 sites on) and converts nothing: pgbp_layout is the same before and
+ * after.  Shared and per-site parameters, the shifts and the tip noise in force are read as pgbp_lg_gradient reads them.
+ *   info[site]: 0, or the 1-based index of a cluster that is not positive definite (or whose family has a variance that is
+ *   not positive) at that site: the site's outputs are then NaN, every other site is unaffected.
+ * Values agree with pgbp_lg_gradient to rounding (the closed forms add in another order), not to the byte. */
+int pgbp_lg_gradient_sites(pgbp_engine* e, int32_t site_begin, int32_t site_end, double* dR, double* dmu, double* dalpha,
+                           double* dtheta, double* dsigma_e, int32_t* info);
 /* SCAN OF EVERY EDGE FOR A MEAN SHIFT from the CURRENT beliefs, for sites [site_begin, site_end): per family the maximum-
  * likelihood displacement of the child's conditional mean, its observed information and the likelihood-ratio statistic, under
  * the parameters the engine kept from the last pgbp_lg_assignfactors and the shifts in force.  EXACT ONLY WHEN THE BELIEFS ARE

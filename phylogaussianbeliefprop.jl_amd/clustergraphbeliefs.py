@@ -692,6 +692,46 @@ class ClusterGraphBelief:
             return norm, grad
         return float(norm[self.site]), self._gradient_of_site(grad, self.site)
 
+    def gradient_sites_lg(self):
+        """pgbp_lg_gradient_sites on the current beliefs: gradient_lg(all_sites=True) for a univariate batch on the
+        thread-per-site kernels (p = 1, every belief of at most 2 variables, at least 8 sites; anything else raises
+        PGBP_ERR_INVALID), lanes = sites.  The beliefs are read in the layout they are in: nothing is converted, the next
+        calibrate_ finds the site-minor layout it left.  Same keys and shapes as gradient_lg(all_sites=True) (dsigma_e when
+        tip noise is set); the values agree with it to rounding, and two calls return the same bytes."""
+        nr, n = self._lg_nrates, self.n_sites
+        dR = np.zeros((n, nr, 1, 1))
+        dmu = np.zeros((n, 1))
+        dalpha = np.zeros(n)
+        dtheta = np.zeros((n, 1))
+        info = np.zeros(n, dtype=np.int32)
+        noisy = self.tip_noise_count_lg() > 0
+        dsig = np.zeros((n, 1, 1)) if noisy else None
+        _check(self._lib.pgbp_lg_gradient_sites(self._eng, 0, n, L.f64p(dR), L.f64p(dmu), L.f64p(dalpha), L.f64p(dtheta),
+                                                L.f64p(dsig) if noisy else None, L.i32p(info)), self._eng)
+        d = dict(dR=dR, dmu=dmu, dalpha=dalpha, dtheta=dtheta, info=info)
+        if noisy:
+            d["dsigma_e"] = dsig
+        return d
+
+    def loglik_and_gradient_sites_lg(self, schedule_tree):
+        """loglik_and_gradient_lg(schedule_tree, all_sites=True) with the thread-per-site sweep (gradient_sites_lg): beliefs
+        reset from the factors -> one calibrate -> integratebelief! at the root cluster -> the sweep, all of it on the
+        thread-per-site kernels and in their layout.  Returns (loglik [n_sites], gradient dict); a failed site has info != 0
+        and NaN values."""
+        self._ensure_schedule([schedule_tree])
+        o = self._opts()
+        pa = np.asarray(schedule_tree[-2]).reshape(-1)
+        root = int(pa[0]) if pa.size else 0
+        _check(self._lib.pgbp_enqueue_calibrate(self._eng, 1, 1, C.byref(o)), self._eng)
+        _check(self._lib.pgbp_enqueue_integrate(self._eng, root), self._eng)
+        grad = self.gradient_sites_lg()
+        norm = np.zeros(self.n_sites)
+        info = np.zeros(self.n_sites, dtype=np.int32)
+        _check(self._lib.pgbp_fetch_loglik(self._eng, L.f64p(norm), L.i32p(info)), self._eng)
+        grad["info"] = np.where(grad["info"] != 0, grad["info"], info)
+        norm = np.where(grad["info"] != 0, np.nan, norm)
+        return norm, grad
+
     def edge_gradient_lg(self, all_sites=False):
         """pgbp_lg_edge_gradient on the current beliefs: the derivative of the log-likelihood in every edge length, in every
         inheritance and in a shift of the mean on every edge, under the parameters of the last assignfactors_lg_ -- one sweep

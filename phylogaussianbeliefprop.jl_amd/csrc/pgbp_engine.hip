@@ -2510,6 +2510,18 @@ EngineView engine_peek(pgbp_engine* e) {
   v.lg_ready = e->lg_ready ? 1 : 0;
   return v;
 }
+UniView engine_uni_view(pgbp_engine* e) {
+  UniView u;
+  u.tps = uni_engine(e) ? 1 : 0;
+  u.sm = e->layout_sm ? 1 : 0;
+  u.bs16 = e->layout_bs16 ? 1 : 0;
+  u.pool = e->layout_sm ? e->sm.pool.get() : e->d_pool.get();
+  u.stride = e->layout_sm ? sm_row(e->plan.n_sites) : e->plan.pool_stride();
+  u.off = e->layout_sm ? e->d_packed_off.get() : e->d_boff.get();
+  u.bdim = e->d_bdim.get();
+  u.fam_cluster = &e->lg_h_cluster;
+  return u;
+}
 const Plan* engine_plan(const pgbp_engine* e) { return &e->plan; }
 bool engine_lg_params(const pgbp_engine* e, LgParams* out) {
   if (!e->lg_ready || !e->lg_have_params) return false;

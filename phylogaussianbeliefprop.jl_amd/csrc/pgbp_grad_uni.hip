@@ -1,0 +1,292 @@
+// The gradient sweep of pgbp_grad.hip for univariate batches on a thread-per-site engine (pgbp_lg_gradient_sites of
+// include/pgbp.h): p = 1, every belief of at most 2 variables, at least 8 sites.  Lanes are sites: a workgroup is 256
+// consecutive sites, grid.y a block of kGradUniFamBlock consecutive families, a thread walks its block's families in index
+// order for its one site.  The family table is uniform across a wavefront (scalar loads); the belief entries and the tip data
+// are read as whole lines in the layout the pool is in (site-minor from 64 sites on, plain below: grad_uni_family<SM>), so the
+// call converts nothing and leaves the layout as it found it.
+//
+// Per (family, site) everything is closed form.  Notation of pgbp_grad.hip: r = sum_a c_a x_a - w with c_0 = 1 (child),
+// c_k = -qc_k.  The blocks in scope are variables of a cluster of at most 2, so r = u_0 x_0 + u_1 x_1 + const - w with u_v the
+// sum of the c_a that sit at variable v, and with Sigma = J^-1, m = Sigma h of the cluster:
+//   e = u'm + const - w,  Cov(r) = u' Sigma u,  M = Cov(r) + e^2,  V = sum_k vc_k R[colour_k] (+ E_f),  j = 1 / V,
+//   G_V = (j M j - j) / 2,  g_w = j e,  g_qk = j (e x_k + (Sigma u)[v_k])   (x_k: the parent's mean, or mu of the fixed root).
+// The alpha term sum_k (dvc_k R_k G_V + dwc_k theta g_w + dqc_k g_qk) is linear in per-parent sums, so one pass over the
+// parents is enough.  Coefficients, shift and noise from lg_coefs<false>, lg_coefs_dalpha, lg_shift_d and lg_noise_E.
+//
+// Reduction: each thread writes its block's partial sums to partial[family block][entry][site]; grad_uni_reduce adds the
+// blocks in index order.  No atomics, contraction off, every sum in a fixed order: the bytes of a site depend neither on the
+// call nor on the site range it came in.  A launch carries kGradUniRates rates in registers; a model with more rates is swept
+// once per group of rates (the scalar entries with the first).  The partials of a chunk of sites at a time (256 MB at most).
+// A lane whose cluster or variance is not positive definite records the 1-based cluster index and adds nothing; there is no
+// barrier in either kernel, and no lane's store depends on another lane.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cmath>
+#include <string>
+#include <vector>
+
+#include "pgbp_devmem.hpp"
+#include "pgbp_fam_dev.hpp"
+#include "pgbp_kernels.hpp"
+
+namespace pgbp {
+
+constexpr int kGradUniFamBlock = 64;   // families per thread (grid.y = blocks of them)
+constexpr int kGradUniRates = 4;       // rates a launch accumulates in registers
+constexpr int kGradUniNoInfo = 0x7fffffff;
+
+// entries of a site's gradient: [dR (n_rates) | dsigma_e | dmu | dtheta | dalpha]
+__host__ __device__ inline int grad_uni_entries(int nr) { return nr + 4; }
+
+template <bool SM>
+__device__ __forceinline__ double grad_uni_ld(const double* __restrict__ pool, int64_t stride, int64_t off, int t, int64_t as) {
+  return SM ? pool[(off + t) * stride + as] : pool[as * stride + off + t];
+}
+
+template <bool SM>
+__global__ __launch_bounds__(256) void grad_uni_family(const double* __restrict__ pool, int64_t stride,
+                                                       const int64_t* __restrict__ off, const int32_t* __restrict__ bdim,
+                                                       LgStatic F, LgParams M, LgShifts Sh, LgNoise Nz,
+                                                       const int32_t* __restrict__ fam_cluster, int n_fam, int64_t data_row_len,
+                                                       int site0, int n_sites, int r0, int64_t part_row,
+                                                       double* __restrict__ partial, int32_t* __restrict__ pinfo) {
+#pragma clang fp contract(off)
+  const int s = blockIdx.x * 256 + threadIdx.x, fb = blockIdx.y;
+  if (s >= n_sites) return;   // (a lane past the range: no barrier follows, and no other lane's store is its to make)
+  const int64_t as = (int64_t)site0 + s;
+  const int K = F.K, nr = F.n_rates;
+  const bool ou = M.model == PGBP_LG_OU;
+  const LgSite S = lg_site(M, nr, 1, as);
+  const double mu = S.mu[0], theta = S.theta ? S.theta[0] : 0.0;
+  double accR[kGradUniRates];
+#pragma unroll
+  for (int i = 0; i < kGradUniRates; ++i) accR[i] = 0.0;
+  double dsig = 0.0, dmu = 0.0, dth = 0.0, da = 0.0;
+  int bad = kGradUniNoInfo;
+  const int f0 = fb * kGradUniFamBlock, f1 = min(f0 + kGradUniFamBlock, n_fam);
+  for (int f = f0; f < f1; ++f) {
+    const int np = F.n_parents[f], cpos = F.child_pos[f];
+    // families the factor fill skips contribute nothing (and a root-prior family of a fixed root, which has no factor)
+    if (F.child_mask && !(F.child_mask[f] & 1ull)) continue;
+    if (np == 0 && cpos < 0) continue;
+    const int c = fam_cluster[f], m = bdim[c];
+    bool any_scope = cpos >= 0;
+    for (int k = 0; k < np; ++k) any_scope |= F.parent_pos[(size_t)f * K + k] >= 0;
+    // moments of the cluster: Sigma = J^-1 (PDMat(Symmetric(J)): the upper triangle), mean = Sigma h
+    double S00 = 0.0, S01 = 0.0, S11 = 0.0, m0 = 0.0, m1 = 0.0;
+    bool ok = true;
+    if (any_scope) {
+      const int64_t o = off[c];
+      if (m == 1) {
+        const double J = grad_uni_ld<SM>(pool, stride, o, 0, as), h = grad_uni_ld<SM>(pool, stride, o, 1, as);
+        ok = J > 0.0;
+        S00 = 1.0 / J;
+        m0 = h / J;
+      } else if (m == 2) {
+        const double a = grad_uni_ld<SM>(pool, stride, o, 0, as), b = grad_uni_ld<SM>(pool, stride, o, 2, as);
+        const double d = grad_uni_ld<SM>(pool, stride, o, 3, as);
+        const double h0 = grad_uni_ld<SM>(pool, stride, o, 4, as), h1 = grad_uni_ld<SM>(pool, stride, o, 5, as);
+        const double ba = b / a, sc = d - ba * b;   // the Schur complement of the first pivot
+        ok = a > 0.0 && sc > 0.0;
+        S11 = 1.0 / sc;
+        S01 = -(ba * S11);
+        S00 = 1.0 / a + ba * ba * S11;
+        m1 = (h1 - ba * h0) / sc;
+        m0 = (h0 - b * m1) / a;
+      } else {
+        ok = false;   // (a variable in scope of a cluster without variables: no moments)
+      }
+    }
+    // one pass over the blocks: u, the constant part, V, w, the chain-rule coefficients and the sums of the alpha term
+    double u0 = 0.0, u1 = 0.0, cst = 0.0;
+    if (cpos == 0) u0 = 1.0;
+    else if (cpos == 1) u1 = 1.0;
+    else if (F.data_row[f] >= 0)   // a tip: its data row, [row][site] where the engine keeps that copy
+      cst = F.data_sm ? F.data_sm[(int64_t)F.data_row[f] * data_row_len + as] : F.data[as * F.n_rows + F.data_row[f]];
+    double V = 0.0, w = 0.0, cmu = 0.0, cth = 0.0;
+    double A1 = 0.0, A2 = 0.0, A3 = 0.0, D0 = 0.0, D1 = 0.0;   // sum dvc R_k, sum dwc, sum dqc x_k, sum dqc at variable 0 / 1
+    double cr[kGradUniRates];
+#pragma unroll
+    for (int i = 0; i < kGradUniRates; ++i) cr[i] = 0.0;
+    if (np == 0) {
+      const int col = F.color[(size_t)f * K];
+      V = S.R[col];
+      w = mu;
+      cmu = 1.0;
+#pragma unroll
+      for (int i = 0; i < kGradUniRates; ++i)
+        if (col == r0 + i) cr[i] = 1.0;
+    } else {
+      for (int k = 0; k < np; ++k) {
+        const double len = F.length[(size_t)f * K + k], gam = F.gamma[(size_t)f * K + k];
+        const int col = F.color[(size_t)f * K + k], pk = F.parent_pos[(size_t)f * K + k];
+        double qc, vc, wc, dqc, dvc, dwc;
+        lg_coefs<false>(M.model, S.alpha, len, gam, qc, vc, wc);
+        lg_coefs_dalpha(M.model, S.alpha, len, gam, dqc, dvc, dwc);
+        const double Rk = S.R[col];
+        V = V + vc * Rk;
+        cth = cth + wc;
+        if (S.theta) w = w + wc * theta;
+        A1 = A1 + dvc * Rk;
+        A2 = A2 + dwc;
+        if (pk == 0) {
+          u0 = u0 - qc;
+          D0 = D0 + dqc;
+          A3 = A3 + dqc * m0;
+        } else if (pk == 1) {
+          u1 = u1 - qc;
+          D1 = D1 + dqc;
+          A3 = A3 + dqc * m1;
+        } else {   // the fixed root
+          cst = cst - qc * mu;
+          cmu = cmu + qc;
+          A3 = A3 + dqc * mu;
+        }
+#pragma unroll
+        for (int i = 0; i < kGradUniRates; ++i)
+          if (col == r0 + i) cr[i] = cr[i] + vc;
+      }
+      if (Sh.slot) w = w + lg_shift_d(Sh, F.gamma, f, K, np, 0, 1, as);   // a shift of the mean on a parent edge
+    }
+    const int sn = lg_noise_slot(Nz, f);
+    if (sn >= 0) V = V + lg_noise_E(Nz, sn, 0, 0, 1, as);   // a noisy tip: V + E
+    ok = ok && V > 0.0;
+    const double e = (u0 * m0 + u1 * m1 + cst) - w;
+    const double su0 = S00 * u0 + S01 * u1, su1 = S01 * u0 + S11 * u1;   // Sigma u
+    const double Mx = (u0 * su0 + u1 * su1) + e * e;
+    const double j = 1.0 / V;
+    const double ge = j * e;
+    const double G = 0.5 * ((j * Mx) * j - j);
+    if (ok) {
+#pragma unroll
+      for (int i = 0; i < kGradUniRates; ++i) accR[i] = accR[i] + G * cr[i];
+      if (sn >= 0) dsig = dsig + G * Nz.scale[sn];
+      dmu = dmu + ge * cmu;
+      dth = dth + ge * cth;
+      if (ou) da = da + ((A1 * G + A2 * (theta * ge)) + j * (e * A3 + (D0 * su0 + D1 * su1)));
+    } else {
+      bad = min(bad, c + 1);
+    }
+  }
+  const int n_ent = grad_uni_entries(nr);
+  double* __restrict__ o = partial + (int64_t)fb * n_ent * part_row + s;
+#pragma unroll
+  for (int i = 0; i < kGradUniRates; ++i)
+    if (r0 + i < nr) o[(int64_t)(r0 + i) * part_row] = accR[i];
+  if (r0 == 0) {
+    o[(int64_t)nr * part_row] = dsig;
+    o[(int64_t)(nr + 1) * part_row] = dmu;
+    o[(int64_t)(nr + 2) * part_row] = dth;
+    o[(int64_t)(nr + 3) * part_row] = da;
+    pinfo[(int64_t)fb * part_row + s] = bad;
+  }
+}
+
+// out[entry][out0 + site] = the blocks' partials added in index order; info[out0 + site] = the smallest mark of a block, 0: none
+__global__ __launch_bounds__(256) void grad_uni_reduce(const double* __restrict__ partial, const int32_t* __restrict__ pinfo,
+                                                       int nfb, int n_ent, int n_sites, int64_t part_row,
+                                                       double* __restrict__ out, int32_t* __restrict__ info, int out0,
+                                                       int64_t out_row) {
+#pragma clang fp contract(off)
+  const int s = blockIdx.x * 256 + threadIdx.x, en = blockIdx.y;
+  if (s >= n_sites) return;
+  if (en < n_ent) {
+    double acc = 0.0;
+    for (int b = 0; b < nfb; ++b) acc = acc + partial[((int64_t)b * n_ent + en) * part_row + s];
+    out[(int64_t)en * out_row + out0 + s] = acc;
+  } else {
+    int bad = kGradUniNoInfo;
+    for (int b = 0; b < nfb; ++b) bad = min(bad, pinfo[(int64_t)b * part_row + s]);
+    info[out0 + s] = bad == kGradUniNoInfo ? 0 : bad;
+  }
+}
+
+}  // namespace pgbp
+
+using namespace pgbp;
+
+extern "C" int pgbp_lg_gradient_sites(pgbp_engine* e, int32_t site_begin, int32_t site_end, double* dR, double* dmu,
+                                      double* dalpha, double* dtheta, double* dsigma_e, int32_t* info) {
+  if (!e) return PGBP_ERR_INVALID;
+  const char* fn = "pgbp_lg_gradient_sites";
+  const EngineView v = engine_peek(e);   // (the layout is not touched)
+  LgParams M{};
+  if (!v.lg_ready) return engine_fail(e, PGBP_ERR_STATE, std::string(fn) + ": no family table (call pgbp_lg_setup first)");
+  if (!engine_lg_params(e, &M))
+    return engine_fail(e, PGBP_ERR_STATE, std::string(fn) + ": no parameters yet (call pgbp_lg_assignfactors first)");
+  const Plan& pl = *v.plan;
+  if (site_begin < 0 || site_end < site_begin || site_end > pl.n_sites)
+    return engine_fail(e, PGBP_ERR_INVALID, std::string(fn) + ": site range outside the engine's sites");
+  if (!dR || !dmu) return engine_fail(e, PGBP_ERR_INVALID, std::string(fn) + ": no output buffer");
+  const bool ou = M.model == PGBP_LG_OU;
+  if (ou && (!dalpha || !dtheta)) return engine_fail(e, PGBP_ERR_INVALID, std::string(fn) + ": the OU model needs dalpha and dtheta");
+  const LgStatic& F = *v.lg;
+  const UniView U = engine_uni_view(e);
+  // a thread-per-site engine, as the plan defines it
+  if (F.p != 1)
+    return engine_fail(e, PGBP_ERR_INVALID, std::string(fn) + ": " + std::to_string(F.p) + " traits; the thread-per-site sweep is univariate (use pgbp_lg_gradient)");
+  if (pl.max_dim > 2)
+    return engine_fail(e, PGBP_ERR_INVALID, std::string(fn) + ": a belief of " + std::to_string(pl.max_dim) +
+                                                " variables; the thread-per-site sweep needs every belief at 2 variables or fewer (use pgbp_lg_gradient)");
+  if (pl.n_sites < 8)
+    return engine_fail(e, PGBP_ERR_INVALID, std::string(fn) + ": " + std::to_string(pl.n_sites) +
+                                                " sites; the thread-per-site kernels run from 8 sites on (use pgbp_lg_gradient)");
+  if (!U.tps || U.bs16) return engine_fail(e, PGBP_ERR_INVALID, std::string(fn) + ": the engine is not on the thread-per-site kernels");
+  const int ns = site_end - site_begin;
+  if (ns == 0) return PGBP_OK;
+  const int nr = F.n_rates, nf = (int)U.fam_cluster->size();
+  const int n_ent = grad_uni_entries(nr);
+  const int nfb = std::max(1, (nf + kGradUniFamBlock - 1) / kGradUniFamBlock);
+  // the partials of a chunk of sites at a time: 256 MB at most (whole workgroups of sites; one workgroup's sites at least)
+  const int64_t fit = (((int64_t)32 << 20) / ((int64_t)nfb * n_ent)) / 256 * 256;
+  const int chunk = (int)std::min<int64_t>(ns, std::max<int64_t>(256, fit));
+  std::vector<double> out((size_t)n_ent * ns);
+  std::vector<int32_t> inf(ns, 0);
+  DevBuf<int32_t> d_fcl, d_pinfo, d_info;
+  DevBuf<double> d_part, d_out;
+  hipError_t herr = (hipError_t)d_fcl.alloc(std::max(1, nf));
+  if (herr == hipSuccess) herr = (hipError_t)d_part.alloc((size_t)nfb * n_ent * chunk);
+  if (herr == hipSuccess) herr = (hipError_t)d_pinfo.alloc((size_t)nfb * chunk);
+  if (herr == hipSuccess) herr = (hipError_t)d_out.alloc((size_t)n_ent * ns);
+  if (herr == hipSuccess) herr = (hipError_t)d_info.alloc((size_t)ns);
+  if (herr == hipSuccess && nf > 0)
+    herr = hipMemcpyAsync(d_fcl.get(), U.fam_cluster->data(), sizeof(int32_t) * nf, hipMemcpyHostToDevice, v.st);
+  if (herr != hipSuccess) return engine_fail(e, PGBP_ERR_HIP, std::string(fn) + " (scratch): " + hipGetErrorString(herr));
+  (void)hipGetLastError();   // (an error an earlier asynchronous call left behind is that call's to report)
+  const LgShifts Sh = engine_lg_shifts(e);
+  const LgNoise Nz = engine_lg_noise(e);
+  const int64_t data_row_len = sm_row(pl.n_sites);
+  for (int s0 = 0; s0 < ns; s0 += chunk) {
+    const int n = std::min(chunk, ns - s0);
+    const dim3 grid((n + 255) / 256, nfb);
+    for (int r0 = 0; r0 == 0 || r0 < nr; r0 += kGradUniRates) {
+      if (U.sm)
+        hipLaunchKernelGGL(grad_uni_family<true>, grid, dim3(256), 0, v.st, U.pool, U.stride, U.off, U.bdim, F, M, Sh, Nz,
+                           d_fcl.get(), nf, data_row_len, site_begin + s0, n, r0, (int64_t)chunk, d_part.get(), d_pinfo.get());
+      else
+        hipLaunchKernelGGL(grad_uni_family<false>, grid, dim3(256), 0, v.st, U.pool, U.stride, U.off, U.bdim, F, M, Sh, Nz,
+                           d_fcl.get(), nf, data_row_len, site_begin + s0, n, r0, (int64_t)chunk, d_part.get(), d_pinfo.get());
+    }
+    hipLaunchKernelGGL(grad_uni_reduce, dim3((n + 255) / 256, n_ent + 1), dim3(256), 0, v.st, d_part.get(), d_pinfo.get(), nfb,
+                       n_ent, n, (int64_t)chunk, d_out.get(), d_info.get(), s0, (int64_t)ns);
+  }
+  herr = hipGetLastError();
+  if (herr == hipSuccess) herr = hipMemcpyAsync(out.data(), d_out.get(), sizeof(double) * out.size(), hipMemcpyDeviceToHost, v.st);
+  if (herr == hipSuccess) herr = hipMemcpyAsync(inf.data(), d_info.get(), sizeof(int32_t) * (size_t)ns, hipMemcpyDeviceToHost, v.st);
+  const hipError_t serr = hipStreamSynchronize(v.st);
+  if (herr == hipSuccess) herr = serr;
+  if (herr != hipSuccess) return engine_fail(e, PGBP_ERR_HIP, std::string(fn) + ": " + hipGetErrorString(herr));
+  // [entry][site] to the caller's arrays (the layout of pgbp_lg_gradient_noise at p = 1); a failed site holds NaN
+  for (int s = 0; s < ns; ++s) {
+    const bool bad = inf[s] != 0;
+    auto ent = [&](int en) { return bad ? (double)NAN : out[(size_t)en * ns + s]; };
+    for (int r = 0; r < nr; ++r) dR[(size_t)s * nr + r] = ent(r);
+    if (dsigma_e) dsigma_e[s] = ent(nr);
+    dmu[s] = ent(nr + 1);
+    if (dtheta) dtheta[s] = bad ? (double)NAN : (ou ? out[(size_t)(nr + 2) * ns + s] : 0.0);
+    if (dalpha) dalpha[s] = bad ? (double)NAN : (ou ? out[(size_t)(nr + 3) * ns + s] : 0.0);
+    if (info) info[s] = inf[s];
+  }
+  return PGBP_OK;
+}

@@ -324,6 +324,19 @@ struct EngineView {
 };
 int engine_view(pgbp_engine* e, EngineView* v);
 EngineView engine_peek(pgbp_engine* e);          // the same words without touching the layout, the device or the last error
+// What pgbp_grad_uni.hip reads of a thread-per-site engine: the belief pool in the layout it is in (never converted).
+// sm != 0: element t of belief b of site s at pool[(off[b] + t) * stride + s] (off: the packed offsets, stride: sm_row(n_sites));
+// else at pool[s * stride + off[b] + t] (off: Plan::boff, stride: the pool's doubles per site).  tps: the engine runs the
+// thread-per-site kernels (every belief <= 2 variables, at least 8 sites); fam_cluster: family -> cluster of pgbp_lg_setup.
+struct UniView {
+  int tps, sm, bs16;
+  const double* pool;
+  int64_t stride;
+  const int64_t* off;
+  const int32_t* bdim;
+  const std::vector<int32_t>* fam_cluster;
+};
+UniView engine_uni_view(pgbp_engine* e);
 const Plan* engine_plan(const pgbp_engine* e);
 // the parameters the engine kept from the last pgbp_lg_assignfactors (device pointers); false: none yet
 bool engine_lg_params(const pgbp_engine* e, LgParams* out);

@@ -259,6 +259,22 @@ function lg_gradient(o::DeviceClusterGraphBelief, p::Integer, nrates::Integer; o
 end
 
 """
+    lg_gradient_sites(obj, nsites, nrates; noise = false) -> (dR, dmu, dalpha, dtheta, dsigma_e, info)
+
+`lg_gradient` for every site of a univariate batch on the thread-per-site kernels (pgbp_lg_gradient_sites: p = 1, every belief
+of at most 2 variables, at least 8 sites), lanes = sites; the beliefs are read in the layout they are in.  `dR[c, s]` is rate c
+of site s, the others one number per site (`dsigma_e` is `nothing` unless `noise`).  `info[s] != 0` marks a site whose cluster
+`info[s]` is not positive definite: its outputs are NaN, no exception is thrown.
+"""
+function lg_gradient_sites(o::DeviceClusterGraphBelief, nsites::Integer, nrates::Integer; noise::Bool = false)
+    dR = zeros(nrates, nsites); dmu = zeros(nsites); dalpha = zeros(nsites); dtheta = zeros(nsites)
+    dsig = noise ? zeros(nsites) : nothing
+    info = zeros(Int32, nsites)
+    check(o.handle, @ccall LIB.pgbp_lg_gradient_sites(o.handle::Ptr{Cvoid}, Int32(0)::Int32, Int32(nsites)::Int32, dR::Ptr{Float64}, dmu::Ptr{Float64}, dalpha::Ptr{Float64}, dtheta::Ptr{Float64}, (noise ? pointer(dsig) : Ptr{Float64}(C_NULL))::Ptr{Float64}, info::Ptr{Int32})::Cint)
+    return (dR, dmu, dalpha, dtheta, dsig, info)
+end
+
+"""
     lg_loo_families(obj) -> Vector{Int}
 
 The tip families of the table given to pgbp_lg_setup (1-based indices into it), in the order of `lg_loo`'s outputs

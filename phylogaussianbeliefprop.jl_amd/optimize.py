@@ -450,3 +450,171 @@ def bootstrap_shift_scan_lg(beliefs, schedule_tree, seed=None, z=None, min_info=
     edge = np.stack([fam, np.where(none, -1, best_k[fam])], axis=1)
     top = np.where(info != 0, np.nan, top)
     return dict(max_lr=top, family=fam, edge=edge, loglik=ll, info=info, x=x, data=beliefs.get_data_lg(), data_before=before)
+
+
+def lbfgs_sites(value_and_grad, x0, maxiter=200, gtol=1e-8, memory=8, c1=1e-4):
+    """Batched L-BFGS: minimises n independent functions of d variables side by side, one callback per step for all of them.
+    value_and_grad(X [n, d]) -> (f [n], g [n, d]) evaluates every site at its row of X; a site whose value or gradient is
+    not finite there has FAILED at that point (NaN is how the caller reports info != 0).  A pure function of the callback.
+    Each site has its own history (`memory` pairs), direction and step.  Armijo backtracking: a site whose trial point
+    fails f(x + t d) <= f(x) + c1 t g'd, or fails outright, halves its step; the others keep their accepted point (a site
+    that is not moving is evaluated at its accepted point again and the result dropped: its x, f, g keep their bytes).  A
+    pair (s, y) enters the history only when s'y > 1e-10 |s| |y|; a direction that is not a descent direction, or a step
+    below 1e-12 of its first trial, drops the history and restarts from steepest descent; a steepest-descent step that small
+    stops the site unconverged.  A site stops when max|g| <= gtol max(1, |f|), or after `maxiter` accepted steps.
+    Returns a dict: x [n, d], f [n], g [n, d], converged [n], n_iter [n] (accepted steps), n_evals (callbacks)."""
+    x = np.array(x0, np.float64, copy=True)
+    n, d = x.shape
+    m = int(memory)
+
+    def evaluate(X):
+        f, g = value_and_grad(X)
+        f = np.array(f, np.float64, copy=True).reshape(n)
+        g = np.array(g, np.float64, copy=True).reshape(n, d)
+        ok = np.isfinite(f) & np.all(np.isfinite(g), axis=1)
+        return f, g, ok
+
+    f, g, ok = evaluate(x)
+    n_evals = 1
+    S, Y = np.zeros((m, n, d)), np.zeros((m, n, d))
+    rho = np.zeros((m, n))
+    n_hist = np.zeros(n, np.int64)
+    n_iter = np.zeros(n, np.int64)
+
+    def is_converged(f, g):
+        return np.max(np.abs(g), axis=1, initial=0.0) <= gtol * np.maximum(1.0, np.abs(f))
+    converged = ok & is_converged(np.where(ok, f, 0.0), np.where(ok[:, None], g, np.inf))
+    stopped = converged | ~ok                     # (a start that fails cannot move: stopped, not converged)
+    steepest = np.zeros(n, bool)
+
+    def direction(sel):
+        """-H g of the sites sel by the two-loop recursion over their own histories (slot m - 1 is the newest)"""
+        q = g[sel].copy()
+        nh = n_hist[sel]
+        al = np.zeros((m, q.shape[0]))
+        for j in range(m - 1, -1, -1):
+            valid = j >= m - nh
+            al[j] = np.where(valid, rho[j, sel] * np.sum(S[j, sel] * q, axis=1), 0.0)
+            q -= al[j][:, None] * Y[j, sel]
+        sy = np.sum(S[m - 1, sel] * Y[m - 1, sel], axis=1)
+        yy = np.sum(Y[m - 1, sel] * Y[m - 1, sel], axis=1)
+        gnorm = np.sqrt(np.sum(g[sel] * g[sel], axis=1))
+        h0 = np.where(nh > 0, sy / np.where(yy > 0, yy, 1.0), 1.0 / np.maximum(1.0, gnorm))
+        r = h0[:, None] * q
+        for j in range(m):
+            valid = j >= m - nh
+            be = np.where(valid, rho[j, sel] * np.sum(Y[j, sel] * r, axis=1), 0.0)
+            r += np.where(valid, al[j] - be, 0.0)[:, None] * S[j, sel]
+        return -r
+
+    dirn = np.zeros((n, d))
+    slope = np.zeros(n)
+    step = np.ones(n)
+
+    def new_direction(sel):
+        """direction, slope and first step of the sites sel (a boolean mask); steepest descent where L-BFGS gives no descent"""
+        if not sel.any():
+            return
+        idx = np.nonzero(sel)[0]
+        dd = direction(idx)
+        sl = np.sum(dd * g[idx], axis=1)
+        bad = ~(sl < 0.0) | ~np.all(np.isfinite(dd), axis=1)
+        if bad.any():
+            b = idx[bad]
+            n_hist[b] = 0
+            gn = np.sqrt(np.sum(g[b] * g[b], axis=1))
+            dd[bad] = -g[b] / np.maximum(1.0, gn)[:, None]
+            sl[bad] = np.sum(dd[bad] * g[b], axis=1)
+        steepest[idx] = bad
+        dirn[idx], slope[idx], step[idx] = dd, sl, 1.0
+
+    new_direction(~stopped)
+    while not stopped.all():
+        active = ~stopped
+        trial = np.where(active[:, None], x + step[:, None] * dirn, x)
+        ft, gt, okt = evaluate(trial)
+        n_evals += 1
+        with np.errstate(invalid="ignore"):
+            accept = active & okt & (ft <= f + c1 * step * slope)
+        reject = active & ~accept
+        if accept.any():
+            a = np.nonzero(accept)[0]
+            s = trial[a] - x[a]
+            y = gt[a] - g[a]
+            sy = np.sum(s * y, axis=1)
+            keep = sy > 1e-10 * np.sqrt(np.sum(s * s, axis=1) * np.sum(y * y, axis=1))
+            k = a[keep]
+            if k.size:
+                S[:-1, k], Y[:-1, k], rho[:-1, k] = S[1:, k], Y[1:, k], rho[1:, k]
+                S[-1, k], Y[-1, k], rho[-1, k] = s[keep], y[keep], 1.0 / sy[keep]
+                n_hist[k] = np.minimum(m, n_hist[k] + 1)
+            x[a], f[a], g[a] = trial[a], ft[a], gt[a]
+            n_iter[a] += 1
+            conv = np.zeros(n, bool)
+            conv[a] = is_converged(f[a], g[a])
+            converged |= conv
+            stopped |= conv | (accept & (n_iter >= maxiter))
+            new_direction(accept & ~stopped)
+        if reject.any():
+            step[reject] *= 0.5
+            tiny = reject & (step < 1e-12)
+            give_up = tiny & steepest
+            stopped |= give_up
+            restart = tiny & ~steepest
+            if restart.any():
+                n_hist[restart] = 0
+                new_direction(restart)      # (no history: steepest descent, from step 1)
+                steepest[restart] = True
+    return dict(x=x, f=f, g=g, converged=converged, n_iter=n_iter, n_evals=n_evals)
+
+
+def fit_sites_lg(beliefs, schedule_tree, model, R0, mu0, alpha0=None, theta0=None, extra_rates=(), fit_mu=True, maxiter=200,
+                 gtol=1e-8, memory=8):
+    """Maximum-likelihood fit of EVERY SITE of a univariate batch at once, on a clique tree, on the thread-per-site kernels
+    (p = 1, every belief of at most 2 variables, at least 8 sites).  model: "bm" or "ou".  Each site has its own free
+    parameters: log R[0] (the BM rate; under OU the stationary variance), mu when fit_mu, and under OU log alpha and theta.
+    R0, mu0, alpha0, theta0: scalars or [n_sites] start values; extra_rates: the rates that follow R[0] in the rate table of
+    lg_setup (scalars or [n_sites], e.g. a random root's prior variance), held at these values.
+    Every evaluation is ONE device pass for all sites -- assignfactors_lg_ with per-site parameters, then
+    loglik_and_gradient_sites_lg (reset, calibrate, root integrate, the lanes-are-sites sweep) -- driven by lbfgs_sites.
+    A site stops when max|g| <= gtol max(1, |loglik|) in the transformed parameters, or after maxiter steps.
+    Returns a dict of per-site arrays R, mu, alpha, theta (alpha, theta: NaN under BM), loglik, converged, n_iter, and
+    n_device_evals; the engine is left filled and calibrated at the estimates."""
+    if model not in ("bm", "ou"):
+        raise ValueError(f"fit_sites_lg: model must be 'bm' or 'ou', not {model!r}")
+    ou = model == "ou"
+    if ou and (alpha0 is None or theta0 is None):
+        raise ValueError("fit_sites_lg: the OU model needs alpha0 and theta0")
+    n = beliefs.n_sites
+    site = lambda v: np.broadcast_to(np.asarray(v, np.float64).reshape(-1), (n,)).copy()
+    extra = [site(r) for r in extra_rates]
+    mu_fixed = site(mu0)
+    cols = [np.log(site(R0))] + ([mu_fixed.copy()] if fit_mu else []) + ([np.log(site(alpha0)), site(theta0)] if ou else [])
+    i_mu = 1 if fit_mu else None
+    i_al = (2 if fit_mu else 1) if ou else None
+    count = [0]
+
+    def unpack(X):
+        with np.errstate(over="ignore"):
+            R = np.exp(X[:, 0])
+            alpha = np.exp(X[:, i_al]) if ou else None
+        return R, (X[:, i_mu] if fit_mu else mu_fixed), alpha, (X[:, i_al + 1] if ou else None)
+
+    def value_and_grad(X):
+        R, mu, alpha, theta = unpack(X)
+        rates = np.stack([R] + extra, axis=1)[:, :, None, None]
+        kw = dict(model="ou", alpha=alpha, theta=theta[:, None]) if ou else {}
+        beliefs.assignfactors_lg_(rates, mu[:, None], **kw)
+        count[0] += 1
+        ll, d = beliefs.loglik_and_gradient_sites_lg(schedule_tree)
+        g = [d["dR"][:, 0, 0, 0] * R] + ([d["dmu"][:, 0]] if fit_mu else []) + ([d["dalpha"] * alpha, d["dtheta"][:, 0]] if ou else [])
+        f = np.where(d["info"] != 0, np.nan, -ll)
+        return f, -np.stack(g, axis=1)
+
+    beliefs._ensure_schedule([schedule_tree])
+    opt = lbfgs_sites(value_and_grad, np.stack(cols, axis=1), maxiter=maxiter, gtol=gtol, memory=memory)
+    f_end, _ = value_and_grad(opt["x"])   # the engine filled and calibrated at the estimates (the last trial points are not)
+    R, mu, alpha, theta = unpack(opt["x"])
+    nan = np.full(n, np.nan)
+    return dict(R=R, mu=np.array(mu, copy=True), alpha=alpha if ou else nan, theta=np.array(theta, copy=True) if ou else nan.copy(),
+                loglik=-opt["f"], converged=opt["converged"], n_iter=opt["n_iter"], n_device_evals=count[0])
