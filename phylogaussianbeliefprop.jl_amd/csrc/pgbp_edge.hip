@@ -29,6 +29,7 @@
 #include "pgbp_devmem.hpp"
 #include "pgbp_fam_dev.hpp"
 #include "pgbp_kernels.hpp"
+#include "pgbp_lgmodel.hpp"
 
 namespace pgbp {
 
@@ -175,31 +176,24 @@ using namespace pgbp;
 extern "C" int pgbp_lg_edge_gradient(pgbp_engine* e, int32_t site_begin, int32_t site_end, double* dlength, double* dgamma,
                                      double* dshift, int32_t* info) {
   if (!e) return PGBP_ERR_INVALID;
-  LgParams M{};
-  {
-    const EngineView v0 = engine_peek(e);
-    if (!v0.lg_ready)
-      return engine_fail(e, PGBP_ERR_STATE, "pgbp_lg_edge_gradient: no family table (call pgbp_lg_setup first)");
-    if (!engine_lg_params(e, &M))
-      return engine_fail(e, PGBP_ERR_STATE, "pgbp_lg_edge_gradient: no parameters yet (call pgbp_lg_assignfactors first)");
-    if (site_begin < 0 || site_end < site_begin || site_end > v0.plan->n_sites)
-      return engine_fail(e, PGBP_ERR_INVALID, "pgbp_lg_edge_gradient: site range outside the engine's sites");
-    if (!dlength && !dgamma && !dshift) return engine_fail(e, PGBP_ERR_INVALID, "pgbp_lg_edge_gradient: no output buffer");
-  }
-  EngineView v;
-  int rc = engine_view(e, &v);
+  const LgModel* L = nullptr;
+  int rc = lg_sweep_state(e, "pgbp_lg_edge_gradient", site_begin, site_end, &L);
   if (rc) return rc;
+  const LgStatic& F = L->F;
+  const LgParams& M = L->M;
+  const LgShifts& Sh = L->Sh;
+  const LgNoise& Nz = L->Nz;
+  if (!dlength && !dgamma && !dshift) return engine_fail(e, PGBP_ERR_INVALID, "pgbp_lg_edge_gradient: no output buffer");
+  EngineView v;
+  if ((rc = engine_view(e, &v))) return rc;
   // (as in pgbp_lg_gradient, what follows runs on the caller's current device)
   const Plan& pl = *v.plan;
-  const LgStatic& F = *v.lg;
-  const LgShifts Sh = engine_lg_shifts(e);
-  const LgNoise Nz = engine_lg_noise(e);
   const int p = F.p, K = F.K;
-  std::vector<int32_t> fcl;   // which cluster each family sits in
+  const std::vector<int32_t>& fcl = L->T.cluster;   // which cluster each family sits in
   int max_m = 0;
-  rc = lg_family_clusters(e, "pgbp_lg_edge_gradient", v, true, &fcl, &max_m);
-  if (rc) return rc;
-  const int nf = (int)fcl.size();
+  std::string why;
+  if (!L->T.cluster_dims("pgbp_lg_edge_gradient", kLdsMaxDim, &max_m, why)) return engine_fail(e, PGBP_ERR_INVALID, why);
+  const int nf = L->T.n_families;
   const size_t lds_bytes = fam_score_lds_bytes(max_m, p, K, kEdgeRows, edge_extra_doubles(p));
   if (lds_bytes > 160 * 1024)
     return engine_fail(e, PGBP_ERR_INVALID, "pgbp_lg_edge_gradient: a cluster of " + std::to_string(max_m) + " variables with " +

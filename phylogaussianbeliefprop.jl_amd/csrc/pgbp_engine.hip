@@ -16,6 +16,7 @@
 #include "pgbp_devmem.hpp"
 #include "pgbp_internal.hpp"
 #include "pgbp_kernels.hpp"
+#include "pgbp_lgmodel.hpp"
 #include "pgbp_topology.hpp"
 
 using namespace pgbp;
@@ -77,24 +78,6 @@ struct OsBufs {
   DevBuf<int32_t> a_cl, ed_off, ed_msg, task_off;
   DevBuf<GRec> grecs;
   DevBuf<Entry> entries;
-};
-// what LgStatic points at: the family table of pgbp_lg_setup and the parameter slots pgbp_lg_assignfactors fills
-struct LgBufs {
-  DevBuf<int32_t> off, fam, np, cp, row, pp, col;
-  DevBuf<double> len, gam, data, data_sm;
-  DevBuf<unsigned long long> cm, pm;
-  DevBuf<LgSimpleFam> simple;
-  DevBuf<double> R, alpha, theta, mu;
-};
-// what LgShifts points at (pgbp_lg_set_shifts), and the clusters the correction kernel visits
-struct LgShiftBufs {
-  DevBuf<int32_t> slot, cl;
-  DevBuf<double> value, value_sm;
-};
-// what LgNoise points at (pgbp_lg_set_tip_noise), and the clusters the correction kernel visits
-struct LgNoiseBufs {
-  DevBuf<int32_t> slot, cl;
-  DevBuf<double> scale, sigma_e, se2, se2_sm;
 };
 
 hipEvent_t hip_event(void* ev) { return static_cast<hipEvent_t>(ev); }
@@ -185,36 +168,8 @@ struct pgbp_engine {
   bool bm_ready = false;
   int32_t bm_p = 0, bm_rows = 0, bm_per_site = 0;
   BmBufs bm;
-  // pgbp_lg_families: static description + last parameters of the general linear-Gaussian factor fill
-  LgStatic lg{};                  // device pointers (owned: lg_bufs)
-  LgParams lgp{};
-  LgBufs lg_bufs;
-  bool lg_ready = false, lg_have_params = false, lg_uni_ok = false;
-  // host side of the table for pgbp_lg_set_edges: families, parents of each, and -- where LgStatic::simple exists -- its
-  // records with the family each was made from
-  int32_t lg_nf = 0;
-  std::vector<int32_t> lg_h_np, lg_h_simple_fam;
-  std::vector<LgSimpleFam> lg_h_simple;
-  // pgbp_lg_set_shifts: mean shifts on edges (device pointers owned by lg_shift_bufs; slot == null: none), the number of
-  // clusters that hold a shifted family, and the cluster of every family (host side, for that list)
-  LgShifts lgs{};
-  LgShiftBufs lg_shift_bufs;
-  int32_t lg_n_shift_cl = 0;
-  std::vector<int32_t> lg_h_cluster;
-  // pgbp_lg_set_tip_noise: measurement error at the tips (device pointers owned by lg_noise_bufs; slot == null: none), the
-  // clusters that hold a noisy tip family and the largest of them, and which families are tip families (host side)
-  LgNoise lgn{};
-  LgNoiseBufs lg_noise_bufs;
-  int32_t lg_n_noise_cl = 0, lg_noise_max_dim = 0;
-  std::vector<char> lg_h_tip;
-  // pgbp_lg_set_data: what its checks read of the table (host side): data row and child_mask (empty: none) of every family
-  std::vector<int32_t> lg_h_row;
-  std::vector<unsigned long long> lg_h_cmask;
-  // pgbp_lg_set_topology: parents by family and the families grouped by level (pgbp_topology.hpp)
-  bool lg_topo = false;
-  int32_t lg_topo_improper = -1;
-  std::vector<int32_t> lg_h_level_off;
-  DevBuf<int32_t> d_lg_pf, d_lg_level_fam;
+  // pgbp_lg_setup: the linear-Gaussian model (table, device buffers, parameters, shifts, tip noise, topology); null: no table
+  std::unique_ptr<LgModel> lg;
   std::string err;
   // a step of an asynchronous enqueue that could not be issued (a workspace that could not be allocated: ensure_ws has
   // set `err`): the launches that needed it were skipped; every entry point that enqueued, and the next pgbp_sync /
@@ -1660,101 +1615,33 @@ int pgbp_enqueue_loglik_bm(pgbp_engine* e, int32_t reps, const pgbp_opts* opts) 
 
 int pgbp_lg_setup(pgbp_engine* e, const pgbp_lg_families* f) {
   DeviceScope device_scope(e);
-  if (!e || !f || f->p <= 0 || f->p > PGBP_MAX_DIM || f->n_families < 0 || f->max_parents < 1 || f->n_rates < 1 ||
-      f->n_rows < 0)
-    return PGBP_ERR_INVALID;
-  if (f->n_families > 0 && (!f->cluster || !f->n_parents || !f->child_pos || !f->data_row || !f->parent_pos || !f->length ||
-                            !f->gamma || !f->color))
-    return PGBP_ERR_INVALID;
-  if (f->n_rows > 0 && !f->data) return e->fail(PGBP_ERR_INVALID, "pgbp_lg_setup: data missing");
+  if (!e) return PGBP_ERR_INVALID;
   const Plan& p = e->plan;
-  const int nc = p.n_clusters, K = f->max_parents, pp = f->p;
-  if ((f->child_mask || f->parent_mask) && pp > 64) return e->fail(PGBP_ERR_INVALID, "pgbp_lg_setup: scope masks need p <= 64");
-  const unsigned long long full = pp >= 64 ? ~0ull : ((1ull << pp) - 1ull);
-  auto cmask = [&](int i) { return f->child_mask ? (unsigned long long)f->child_mask[i] & full : full; };
-  auto pmask = [&](int i, int k) { return f->parent_mask ? (unsigned long long)f->parent_mask[(size_t)i * f->max_parents + k] & full : full; };
-  // every family fits its cluster; the blocks of one family do not overlap
-  std::vector<int32_t> count(nc + 1, 0);
-  bool uni_ok = p.max_dim <= 2 && pp == 1;
-  if (f->n_rows > 0 && !f->child_mask)
-    for (size_t i = 0, n = (size_t)p.n_sites * f->n_rows * pp; i < n; ++i)
-      if (!std::isfinite(f->data[i]))
-        return e->fail(PGBP_ERR_INVALID, "pgbp_lg_setup: a tip value is missing or not finite (missing values need child_mask / parent_mask)");
-  for (int i = 0; i < f->n_families; ++i) {
-    const std::string where = "pgbp_lg_setup: family " + std::to_string(i) + ": ";
-    const int c = f->cluster[i], np = f->n_parents[i];
-    if (c < 0 || c >= nc) return e->fail(PGBP_ERR_INVALID, where + "cluster out of range");
-    if (np < 0 || np > K) return e->fail(PGBP_ERR_INVALID, where + "number of parents out of range");
-    const int m = p.dims[c];
-    std::vector<std::pair<int, int>> pos;  // (first variable, number of variables) of every in-scope block
-    const int cp = f->child_pos[i];
-    const unsigned long long O = cmask(i);
-    if (cp < 0 && O == 0 && f->child_mask) {
-      // a node with nothing in scope (no data below it) or a tip with every trait missing: the factor integrates to 1
-    } else if (cp < 0) {
-      if (np == 0) return e->fail(PGBP_ERR_INVALID, where + "a root prior needs the root in scope");
-      if (f->data_row[i] < 0 || f->data_row[i] >= f->n_rows) return e->fail(PGBP_ERR_INVALID, where + "data row out of range");
-      for (int s2 = 0; s2 < p.n_sites; ++s2)
-        for (int t = 0; t < pp; ++t)
-          if (((O >> t) & 1ull) && !std::isfinite(f->data[((size_t)s2 * f->n_rows + f->data_row[i]) * pp + t]))
-            return e->fail(PGBP_ERR_INVALID, where + "a tip value is missing or not finite where child_mask says observed "
-                                                     "(missing values: clear the trait's bit in child_mask; one pattern for all sites)");
-    } else {
-      pos.push_back({cp, __builtin_popcountll(O)});
-    }
-    if (np == 0 && (f->color[(size_t)i * K] < 0 || f->color[(size_t)i * K] >= f->n_rates))
-      return e->fail(PGBP_ERR_INVALID, where + "rate index out of range");
-    for (int k = 0; k < np; ++k) {
-      const size_t o = (size_t)i * K + k;
-      if (!(f->length[o] > 0.0) || !std::isfinite(f->length[o]))
-        return e->fail(PGBP_ERR_INVALID, where + "parent edge length must be positive (degenerate families are out of scope)");
-      if (!std::isfinite(f->gamma[o])) return e->fail(PGBP_ERR_INVALID, where + "inheritance not finite");
-      if (f->color[o] < 0 || f->color[o] >= f->n_rates) return e->fail(PGBP_ERR_INVALID, where + "rate index out of range");
-      if (f->parent_pos[o] >= 0) {
-        if ((O & ~pmask(i, k)) != 0)
-          return e->fail(PGBP_ERR_INVALID, where + "a trait kept by the child is out of the parent's scope");
-        pos.push_back({f->parent_pos[o], __builtin_popcountll(pmask(i, k))});
-      }
-    }
-    std::sort(pos.begin(), pos.end());
-    for (size_t a = 0; a < pos.size(); ++a)
-      if (pos[a].first + pos[a].second > m || (a > 0 && pos[a].first < pos[a - 1].first + pos[a - 1].second))
-        return e->fail(PGBP_ERR_INVALID, where + "variable blocks overlap or leave the cluster (dimension " + std::to_string(m) + ")");
-    ++count[c + 1];
-  }
-  for (int c = 0; c < nc; ++c) count[c + 1] += count[c];
-  std::vector<int32_t> fam(std::max(1, f->n_families));
-  {
-    std::vector<int32_t> at(count.begin(), count.end() - 1);
-    for (int i = 0; i < f->n_families; ++i) fam[at[f->cluster[i]]++] = i;  // stable: the reference's loop order
-  }
-  const size_t nf = (size_t)f->n_families, nfk = nf * K;
+  // a whole model into a local: the engine takes it once the last buffer exists, and until then keeps the one it had.  A new
+  // table so carries no parameters, shifts, tip noise or topology
+  auto L = std::make_unique<LgModel>();
+  std::string why;
+  if (!lg_table_build(f, p.dims.data(), p.n_clusters, p.n_sites, p.max_dim, L->T, why))
+    return why.empty() ? PGBP_ERR_INVALID : e->fail(PGBP_ERR_INVALID, why);
+  const LgTable& T = L->T;
+  const int pp = T.p;
   int rc;
-  LgBufs B;   // the whole table into a local: the engine takes it once the last buffer exists
-  if ((rc = upload(e, B.off, count))) return rc;
-  if ((rc = upload(e, B.fam, fam))) return rc;
-  if ((rc = upload(e, B.np, std::vector<int32_t>(f->n_parents, f->n_parents + nf)))) return rc;
-  if ((rc = upload(e, B.cp, std::vector<int32_t>(f->child_pos, f->child_pos + nf)))) return rc;
-  if ((rc = upload(e, B.row, std::vector<int32_t>(f->data_row, f->data_row + nf)))) return rc;
-  if ((rc = upload(e, B.pp, std::vector<int32_t>(f->parent_pos, f->parent_pos + nfk)))) return rc;
-  if ((rc = upload(e, B.col, std::vector<int32_t>(f->color, f->color + nfk)))) return rc;
-  if ((rc = upload(e, B.len, std::vector<double>(f->length, f->length + nfk)))) return rc;
-  if ((rc = upload(e, B.gam, std::vector<double>(f->gamma, f->gamma + nfk)))) return rc;
-  const size_t nd = (size_t)p.n_sites * f->n_rows * pp;
+  LgBufs& B = L->bufs;
+  if ((rc = upload(e, B.off, T.cl_off))) return rc;
+  if ((rc = upload(e, B.fam, T.cl_fam))) return rc;
+  if ((rc = upload(e, B.np, T.n_parents))) return rc;
+  if ((rc = upload(e, B.cp, T.child_pos))) return rc;
+  if ((rc = upload(e, B.row, T.data_row))) return rc;
+  if ((rc = upload(e, B.pp, T.parent_pos))) return rc;
+  if ((rc = upload(e, B.col, T.color))) return rc;
+  if ((rc = upload(e, B.len, T.length))) return rc;
+  if ((rc = upload(e, B.gam, T.gamma))) return rc;
+  const size_t nd = (size_t)p.n_sites * T.n_rows * pp;
   if ((rc = dev_alloc(e, B.data, nd))) return rc;
-  if (f->child_mask) {
-    std::vector<unsigned long long> v(nf);
-    for (size_t i = 0; i < nf; ++i) v[i] = cmask((int)i);
-    if ((rc = upload(e, B.cm, v))) return rc;
-  }
-  if (f->parent_mask) {
-    std::vector<unsigned long long> v(nfk);
-    for (size_t i = 0; i < nf; ++i)
-      for (int k = 0; k < K; ++k) v[i * K + k] = pmask((int)i, k);
-    if ((rc = upload(e, B.pm, v))) return rc;
-  }
+  if (f->child_mask && (rc = upload(e, B.cm, T.child_mask))) return rc;
+  if (f->parent_mask && (rc = upload(e, B.pm, T.parent_mask))) return rc;
   if (nd) {
-    if (!f->child_mask) {  // complete data: checked finite above
+    if (!f->child_mask) {  // complete data: checked finite
       HIPCHK(e, hipMemcpy(B.data.get(), f->data, nd * sizeof(double), hipMemcpyHostToDevice));
     } else {               // masked-out entries may be NaN on the host: never let them reach arithmetic
       std::vector<double> clean(f->data, f->data + nd);
@@ -1763,72 +1650,19 @@ int pgbp_lg_setup(pgbp_engine* e, const pgbp_lg_families* f) {
     }
   }
   const size_t ns = (size_t)p.n_sites;
-  if ((rc = dev_alloc(e, B.R, ns * f->n_rates * pp * pp))) return rc;
+  if ((rc = dev_alloc(e, B.R, ns * T.n_rates * pp * pp))) return rc;
   if ((rc = dev_alloc(e, B.alpha, ns))) return rc;
   if ((rc = dev_alloc(e, B.theta, ns * pp))) return rc;
   if ((rc = dev_alloc(e, B.mu, ns * pp))) return rc;
-  if (uni_ok && f->n_rows > 0) {   // the thread-per-site fill reads the tip data with lanes = sites: keep a [row][site] copy
-    if ((rc = dev_alloc(e, B.data_sm, (size_t)f->n_rows * (size_t)sm_row(p.n_sites)))) return rc;
-    launch_transpose_words_f64(B.data.get(), B.data_sm.get(), f->n_rows, p.n_sites, 1, e->st);
+  if (T.uni_ok && T.n_rows > 0) {   // the thread-per-site fill reads the tip data with lanes = sites: keep a [row][site] copy
+    if ((rc = dev_alloc(e, B.data_sm, (size_t)T.n_rows * (size_t)sm_row(p.n_sites)))) return rc;
+    launch_transpose_words_f64(B.data.get(), B.data_sm.get(), T.n_rows, p.n_sites, 1, e->st);
     HIPCHK(e, hipStreamSynchronize(e->st));
   }
-  // one record per cluster where every cluster holds exactly one family with at most one parent and there are no scope masks
-  std::vector<LgSimpleFam> h_simple;
-  std::vector<int32_t> h_simple_fam;
-  if (uni_ok && !f->child_mask && !f->parent_mask && f->n_families == nc) {
-    std::vector<LgSimpleFam> sf(nc);
-    std::vector<int32_t> sfam(nc);
-    bool simple = true;
-    for (int c = 0; c < nc && simple; ++c) {
-      if (count[c + 1] - count[c] != 1) { simple = false; break; }
-      const int i = fam[count[c]];
-      const int np = f->n_parents[i];
-      if (np > 1) { simple = false; break; }
-      LgSimpleFam r{};
-      r.np = np; r.cpos = f->child_pos[i]; r.row = f->data_row[i];
-      r.ppos = np > 0 ? f->parent_pos[(size_t)i * K] : -1;
-      r.color = f->color[(size_t)i * K];
-      r.length = np > 0 ? f->length[(size_t)i * K] : 0.0;
-      r.gamma = np > 0 ? f->gamma[(size_t)i * K] : 0.0;
-      if (r.cpos > 1 || r.ppos > 1) { simple = false; break; }
-      sf[c] = r;
-      sfam[c] = i;
-    }
-    if (simple && (rc = upload(e, B.simple, sf))) return rc;
-    if (simple) {
-      h_simple = std::move(sf);
-      h_simple_fam = std::move(sfam);
-    }
-  }
-  e->lg_bufs = std::move(B);
-  e->lg_nf = f->n_families;
-  e->lg_h_np.assign(f->n_parents, f->n_parents + nf);
-  e->lg_h_simple = std::move(h_simple);
-  e->lg_h_simple_fam = std::move(h_simple_fam);
-  e->lg_h_cluster.assign(f->cluster, f->cluster + nf);
-  e->lg_shift_bufs = LgShiftBufs{};   // a new table: no shifts
-  e->lgs = LgShifts{};
-  e->lg_n_shift_cl = 0;
-  e->lg_noise_bufs = LgNoiseBufs{};   // ... and no tip noise
-  e->lgn = LgNoise{};
-  e->lg_n_noise_cl = e->lg_noise_max_dim = 0;
-  e->lg_h_tip.assign(nf, 0);
-  for (size_t i = 0; i < nf; ++i) e->lg_h_tip[i] = f->child_pos[i] < 0 && f->data_row[i] >= 0 && f->n_parents[i] >= 1;
-  e->lg_h_row.assign(f->data_row, f->data_row + nf);
-  e->lg_h_cmask.clear();
-  if (f->child_mask)
-    for (size_t i = 0; i < nf; ++i) e->lg_h_cmask.push_back(cmask((int)i));
-  e->lg_topo = false;                 // ... and no topology
-  e->lg_topo_improper = -1;
-  e->lg_h_level_off.clear();
-  e->d_lg_pf.reset();
-  e->d_lg_level_fam.reset();
-  const LgBufs& L = e->lg_bufs;
-  e->lg = LgStatic{pp, K, f->n_rates, f->n_rows, L.off.get(), L.fam.get(), L.np.get(), L.cp.get(), L.row.get(), L.pp.get(), L.len.get(),
-                   L.gam.get(), L.col.get(), L.data.get(), L.cm.get(), L.pm.get(), L.data_sm.get(), L.simple.get()};
-  e->lg_ready = true;
-  e->lg_have_params = false;
-  e->lg_uni_ok = uni_ok;
+  if (!T.simple.empty() && (rc = upload(e, B.simple, T.simple))) return rc;
+  L->F = LgStatic{pp, T.K, T.n_rates, T.n_rows, B.off.get(), B.fam.get(), B.np.get(), B.cp.get(), B.row.get(), B.pp.get(), B.len.get(),
+                  B.gam.get(), B.col.get(), B.data.get(), B.cm.get(), B.pm.get(), B.data_sm.get(), B.simple.get()};
+  e->lg = std::move(L);
   return PGBP_OK;
 }
 
@@ -1836,12 +1670,13 @@ int pgbp_lg_setup(pgbp_engine* e, const pgbp_lg_families* f) {
 // the body of score() (src/calibration.jl:205-209)
 static int lg_fill_async(pgbp_engine* e, bool also_factors, bool skip_sepsets = false) {
   const Plan& p = e->plan;
-  if (e->layout_sm && e->lg_uni_ok) {
-    launch_lg_fill_uni_sm(e->lg, e->lgp, e->sm.pool.get(), also_factors ? e->sm.fpool.get() : nullptr, e->d_packed_off.get(), e->d_bdim.get(),
+  const LgModel& L = *e->lg;
+  if (e->layout_sm && L.T.uni_ok) {
+    launch_lg_fill_uni_sm(L.F, L.M, e->sm.pool.get(), also_factors ? e->sm.fpool.get() : nullptr, e->d_packed_off.get(), e->d_bdim.get(),
                           p.n_clusters, p.n_sites, e->st);
-    launch_lg_shift_uni_sm(e->lg, e->lgp, e->lgs, e->lg_shift_bufs.cl.get(), e->lg_n_shift_cl, e->sm.pool.get(),
+    launch_lg_shift_uni_sm(L.F, L.M, L.Sh, L.shift_bufs.cl.get(), L.n_shift_cl, e->sm.pool.get(),
                            also_factors ? e->sm.fpool.get() : nullptr, e->d_packed_off.get(), e->d_bdim.get(), p.n_sites, e->st);
-    launch_lg_noise_uni_sm(e->lg, e->lgp, e->lgs, e->lgn, e->lg_noise_bufs.cl.get(), e->lg_n_noise_cl, e->sm.pool.get(),
+    launch_lg_noise_uni_sm(L.F, L.M, L.Sh, L.Nz, L.noise_bufs.cl.get(), L.n_noise_cl, e->sm.pool.get(),
                            also_factors ? e->sm.fpool.get() : nullptr, e->d_packed_off.get(), e->d_bdim.get(), p.n_sites, e->st);
     const int64_t nc = p.packed_off[p.n_clusters] * sm_row(p.n_sites), nall = p.packed_off.back() * sm_row(p.n_sites);
     if (!skip_sepsets) HIPCHK(e, hipMemsetAsync(e->sm.pool.get() + nc, 0, sizeof(double) * (size_t)(nall - nc), e->st));  // sepsets = 1
@@ -1850,14 +1685,14 @@ static int lg_fill_async(pgbp_engine* e, bool also_factors, bool skip_sepsets = 
       const int rc0 = ensure_site_minor(e, false);
       if (rc0) return rc0;
     }
-    launch_lg_fill(e->lg, e->lgp, e->d_pool.get(), p.pool_stride(), also_factors ? e->d_fpool.get() : nullptr, p.cluster_stride(),
+    launch_lg_fill(L.F, L.M, e->d_pool.get(), p.pool_stride(), also_factors ? e->d_fpool.get() : nullptr, p.cluster_stride(),
                    e->d_boff.get(), e->d_bdim.get(), e->layout_bs16 ? 1 : 0, p.fast_p, p.max_dim, p.n_clusters, p.n_sites, e->st);
-    launch_lg_shift(e->lg, e->lgp, e->lgs, e->lg_shift_bufs.cl.get(), e->lg_n_shift_cl, e->d_pool.get(), p.pool_stride(),
+    launch_lg_shift(L.F, L.M, L.Sh, L.shift_bufs.cl.get(), L.n_shift_cl, e->d_pool.get(), p.pool_stride(),
                     also_factors ? e->d_fpool.get() : nullptr, p.cluster_stride(), e->d_boff.get(), e->d_bdim.get(),
                     e->layout_bs16 ? 1 : 0, p.fast_p, p.max_dim, p.n_sites, e->st);
-    launch_lg_noise(e->lg, e->lgp, e->lgs, e->lgn, e->lg_noise_bufs.cl.get(), e->lg_n_noise_cl, e->d_pool.get(), p.pool_stride(),
+    launch_lg_noise(L.F, L.M, L.Sh, L.Nz, L.noise_bufs.cl.get(), L.n_noise_cl, e->d_pool.get(), p.pool_stride(),
                     also_factors ? e->d_fpool.get() : nullptr, p.cluster_stride(), e->d_boff.get(), e->d_bdim.get(),
-                    e->layout_bs16 ? 1 : 0, p.fast_p, e->lg_noise_max_dim, p.n_sites, e->st);
+                    e->layout_bs16 ? 1 : 0, p.fast_p, L.noise_max_dim, p.n_sites, e->st);
     if (!skip_sepsets)
       launch_zero_strided(e->d_pool.get() + p.cluster_stride(), p.pool_stride(), p.pool_stride() - p.cluster_stride(),
                           p.n_sites, e->st);  // sepsets = 1 (init_beliefs_reset!)
@@ -1870,59 +1705,49 @@ static int lg_fill_async(pgbp_engine* e, bool also_factors, bool skip_sepsets = 
 int pgbp_lg_assignfactors(pgbp_engine* e, const pgbp_lg_params* m) {
   DeviceScope device_scope(e);
   if (!e || !m || !m->R || !m->mu) return PGBP_ERR_INVALID;
-  if (!e->lg_ready) return e->fail(PGBP_ERR_STATE, "pgbp_lg_assignfactors: call pgbp_lg_setup first");
+  if (!e->lg) return e->fail(PGBP_ERR_STATE, "pgbp_lg_assignfactors: call pgbp_lg_setup first");
   if (m->model != PGBP_LG_BM && m->model != PGBP_LG_OU) return e->fail(PGBP_ERR_INVALID, "pgbp_lg_assignfactors: unknown model");
   if (m->model == PGBP_LG_OU && (!m->alpha || !m->theta))
     return e->fail(PGBP_ERR_INVALID, "pgbp_lg_assignfactors: the OU model needs alpha and theta");
-  const size_t n = m->per_site ? (size_t)e->plan.n_sites : 1, pp = (size_t)e->lg.p;
-  HIPCHK(e, hipMemcpyAsync(e->lg_bufs.R.get(), m->R, n * e->lg.n_rates * pp * pp * sizeof(double), hipMemcpyHostToDevice, e->st));
-  HIPCHK(e, hipMemcpyAsync(e->lg_bufs.mu.get(), m->mu, n * pp * sizeof(double), hipMemcpyHostToDevice, e->st));
-  if (m->alpha) HIPCHK(e, hipMemcpyAsync(e->lg_bufs.alpha.get(), m->alpha, n * sizeof(double), hipMemcpyHostToDevice, e->st));
-  if (m->theta) HIPCHK(e, hipMemcpyAsync(e->lg_bufs.theta.get(), m->theta, n * pp * sizeof(double), hipMemcpyHostToDevice, e->st));
+  LgModel& L = *e->lg;
+  const LgBufs& B = L.bufs;
+  const size_t n = m->per_site ? (size_t)e->plan.n_sites : 1, pp = (size_t)L.T.p;
+  HIPCHK(e, hipMemcpyAsync(B.R.get(), m->R, n * L.T.n_rates * pp * pp * sizeof(double), hipMemcpyHostToDevice, e->st));
+  HIPCHK(e, hipMemcpyAsync(B.mu.get(), m->mu, n * pp * sizeof(double), hipMemcpyHostToDevice, e->st));
+  if (m->alpha) HIPCHK(e, hipMemcpyAsync(B.alpha.get(), m->alpha, n * sizeof(double), hipMemcpyHostToDevice, e->st));
+  if (m->theta) HIPCHK(e, hipMemcpyAsync(B.theta.get(), m->theta, n * pp * sizeof(double), hipMemcpyHostToDevice, e->st));
   HIPCHK(e, hipStreamSynchronize(e->st));  // the host buffers may go away
-  e->lgp = LgParams{m->model, m->per_site ? 1 : 0, e->lg_bufs.R.get(), e->lg_bufs.alpha.get(), m->theta ? e->lg_bufs.theta.get() : nullptr, e->lg_bufs.mu.get()};
-  e->lg_have_params = true;
+  L.M = LgParams{m->model, m->per_site ? 1 : 0, B.R.get(), B.alpha.get(), m->theta ? B.theta.get() : nullptr, B.mu.get()};
+  L.have_params = true;
   // the fill writes exactly symmetric blocks: the layout the traversals want can be kept
   e->sym_known = true;
   e->sym_ok = true;
   // a univariate batch is filled straight in the site-minor layout its traversals use (the wavefront-per-cluster
   // kernel would spend one workgroup per (cluster, site))
-  if (want_site_minor(e) && e->lg_uni_ok && !e->layout_sm) {
+  if (want_site_minor(e) && L.T.uni_ok && !e->layout_sm) {
     const int rc = ensure_layout(e, false, true);
     if (rc) return rc;
   }
   return lg_fill_async(e, true);
 }
 
+// The setters: every check (the table's: pgbp_lgtable.hpp) before anything changes; new buffers into a local group that
+// the model takes once every copy has been made.
+
 int pgbp_lg_set_edges(pgbp_engine* e, const double* length, const double* gamma) {
   DeviceScope device_scope(e);
   if (!e) return PGBP_ERR_INVALID;
-  if (!e->lg_ready) return e->fail(PGBP_ERR_STATE, "pgbp_lg_set_edges: no family table (call pgbp_lg_setup first)");
-  const int K = e->lg.K, nf = e->lg_nf;
-  // the checks of pgbp_lg_setup, all of them before anything changes
-  for (int i = 0; i < nf; ++i)
-    for (int k = 0; k < e->lg_h_np[i]; ++k) {
-      const size_t o = (size_t)i * K + k;
-      const bool bad_length = length && (!(length[o] > 0.0) || !std::isfinite(length[o]));
-      if (bad_length || (gamma && !std::isfinite(gamma[o])))
-        return e->fail(PGBP_ERR_INVALID, "pgbp_lg_set_edges: family " + std::to_string(i) + ": " +
-                                             (bad_length ? "parent edge length must be positive (degenerate families are out of scope)"
-                                                         : "inheritance not finite"));
-    }
-  const size_t bytes = (size_t)nf * K * sizeof(double);
-  if (length && bytes) HIPCHK(e, hipMemcpyAsync(e->lg_bufs.len.get(), length, bytes, hipMemcpyHostToDevice, e->st));
-  if (gamma && bytes) HIPCHK(e, hipMemcpyAsync(e->lg_bufs.gam.get(), gamma, bytes, hipMemcpyHostToDevice, e->st));
-  if (!e->lg_h_simple.empty()) {   // the per-cluster records of the thread-per-site fill carry their own copies
-    for (size_t c = 0; c < e->lg_h_simple.size(); ++c) {
-      LgSimpleFam& r = e->lg_h_simple[c];
-      if (r.np == 0) continue;
-      const size_t o = (size_t)e->lg_h_simple_fam[c] * K;
-      if (length) r.length = length[o];
-      if (gamma) r.gamma = gamma[o];
-    }
-    HIPCHK(e, hipMemcpyAsync(e->lg_bufs.simple.get(), e->lg_h_simple.data(), e->lg_h_simple.size() * sizeof(LgSimpleFam),
+  if (!e->lg) return e->fail(PGBP_ERR_STATE, "pgbp_lg_set_edges: no family table (call pgbp_lg_setup first)");
+  LgModel& L = *e->lg;
+  std::string why;
+  if (!L.T.check_edges(length, gamma, why)) return e->fail(PGBP_ERR_INVALID, why);
+  const size_t bytes = (size_t)L.T.n_families * L.T.K * sizeof(double);
+  if (length && bytes) HIPCHK(e, hipMemcpyAsync(L.bufs.len.get(), length, bytes, hipMemcpyHostToDevice, e->st));
+  if (gamma && bytes) HIPCHK(e, hipMemcpyAsync(L.bufs.gam.get(), gamma, bytes, hipMemcpyHostToDevice, e->st));
+  L.T.set_edges(length, gamma);
+  if (!L.T.simple.empty())   // the per-cluster records of the thread-per-site fill carry their own copies
+    HIPCHK(e, hipMemcpyAsync(L.bufs.simple.get(), L.T.simple.data(), L.T.simple.size() * sizeof(LgSimpleFam),
                              hipMemcpyHostToDevice, e->st));
-  }
   HIPCHK(e, hipStreamSynchronize(e->st));  // the host buffers may go away
   return PGBP_OK;
 }
@@ -1930,51 +1755,29 @@ int pgbp_lg_set_edges(pgbp_engine* e, const double* length, const double* gamma)
 int pgbp_lg_set_shifts(pgbp_engine* e, int32_t n_shifts, const int32_t* edge, const double* value, int32_t per_site) {
   DeviceScope device_scope(e);
   if (!e) return PGBP_ERR_INVALID;
-  if (!e->lg_ready) return e->fail(PGBP_ERR_STATE, "pgbp_lg_set_shifts: no family table (call pgbp_lg_setup first)");
-  if (n_shifts < 0 || (n_shifts > 0 && (!edge || !value)))
-    return e->fail(PGBP_ERR_INVALID, "pgbp_lg_set_shifts: a negative count or a missing array");
-  const int K = e->lg.K, nf = e->lg_nf, pp = e->lg.p;
+  if (!e->lg) return e->fail(PGBP_ERR_STATE, "pgbp_lg_set_shifts: no family table (call pgbp_lg_setup first)");
+  LgModel& L = *e->lg;
+  std::vector<int32_t> slot, cl;   // the slot table, and the clusters that hold a shifted family, in index order
+  std::string why;
+  if (!L.T.shift_list(n_shifts, edge, value, per_site, slot, cl, why)) return e->fail(PGBP_ERR_INVALID, why);
+  const int pp = L.T.p;
   const size_t ns = per_site ? (size_t)e->plan.n_sites : 1, n = (size_t)n_shifts;
-  // every check before anything changes
-  std::vector<int32_t> slot(std::max<size_t>(1, (size_t)nf * K), -1);
-  for (int i = 0; i < n_shifts; ++i) {
-    const std::string where = "pgbp_lg_set_shifts: entry " + std::to_string(i) + " (edge " + std::to_string(edge[i]) + "): ";
-    if (edge[i] < 0 || (int64_t)edge[i] >= (int64_t)nf * K) return e->fail(PGBP_ERR_INVALID, where + "edge index out of range");
-    const int fam = edge[i] / K, k = edge[i] - fam * K;
-    if (e->lg_h_np[fam] == 0)
-      return e->fail(PGBP_ERR_INVALID, where + "family " + std::to_string(fam) + " is a root prior, it has no edge");
-    if (k >= e->lg_h_np[fam])
-      return e->fail(PGBP_ERR_INVALID, where + "family " + std::to_string(fam) + " has " + std::to_string(e->lg_h_np[fam]) +
-                                           " parent edges, no edge " + std::to_string(k));
-    if (slot[edge[i]] >= 0)
-      return e->fail(PGBP_ERR_INVALID, where + "the edge is listed twice (entry " + std::to_string(slot[edge[i]]) + " has it too)");
-    slot[edge[i]] = i;
-    for (size_t s = 0; s < ns; ++s)
-      for (int t = 0; t < pp; ++t)
-        if (!std::isfinite(value[(s * n + i) * pp + t]))
-          return e->fail(PGBP_ERR_INVALID, where + "the value of trait " + std::to_string(t) + " is not finite");
-  }
   if (n_shifts == 0) {   // clear (kernels already enqueued may still read the old shifts)
     HIPCHK(e, hipStreamSynchronize(e->st));
-    e->lg_shift_bufs = LgShiftBufs{};
-    e->lgs = LgShifts{};
-    e->lg_n_shift_cl = 0;
+    L.shift_bufs = LgShiftBufs{};
+    L.Sh = LgShifts{};
+    L.n_shift_cl = 0;
     return PGBP_OK;
   }
-  // the clusters that hold a shifted family, in index order
-  std::vector<int32_t> cl;
-  for (int i = 0; i < n_shifts; ++i) cl.push_back(e->lg_h_cluster[edge[i] / K]);
-  std::sort(cl.begin(), cl.end());
-  cl.erase(std::unique(cl.begin(), cl.end()), cl.end());
   // univariate per-site batches: the values once more as [shift][site], what the thread-per-site correction reads
   std::vector<double> vsm;
-  if (per_site && e->lg_uni_ok) {
+  if (per_site && L.T.uni_ok) {
     const size_t row = (size_t)sm_row(e->plan.n_sites);
     vsm.assign(n * row, 0.0);
     for (size_t s = 0; s < ns; ++s)
       for (size_t i = 0; i < n; ++i) vsm[i * row + s] = value[s * n + i];
   }
-  LgShiftBufs B;   // into a local: the engine takes it once every copy has been made
+  LgShiftBufs B;
   int rc;
   if ((rc = dev_alloc(e, B.slot, slot.size()))) return rc;
   if ((rc = dev_alloc(e, B.cl, cl.size()))) return rc;
@@ -1989,77 +1792,33 @@ int pgbp_lg_set_shifts(pgbp_engine* e, int32_t n_shifts, const int32_t* edge, co
   const hipError_t serr = hipStreamSynchronize(e->st);  // the host buffers may go away; kernels that read the old shifts have finished
   if (herr == hipSuccess) herr = serr;
   if (herr != hipSuccess) return e->fail(PGBP_ERR_HIP, std::string("pgbp_lg_set_shifts (upload): ") + hipGetErrorString(herr));
-  e->lg_shift_bufs = std::move(B);
-  const LgShiftBufs& S = e->lg_shift_bufs;
-  e->lgs = LgShifts{S.slot.get(), S.value.get(), per_site ? 1 : 0, n_shifts, S.value_sm.get()};
-  e->lg_n_shift_cl = (int32_t)cl.size();
+  L.shift_bufs = std::move(B);
+  const LgShiftBufs& S = L.shift_bufs;
+  L.Sh = LgShifts{S.slot.get(), S.value.get(), per_site ? 1 : 0, n_shifts, S.value_sm.get()};
+  L.n_shift_cl = (int32_t)cl.size();
   return PGBP_OK;
 }
 
 int32_t pgbp_lg_shift_count(pgbp_engine* e) {
-  if (!e || !e->lg_ready) return -1;
-  return e->lgs.slot ? e->lgs.n : 0;
+  if (!e || !e->lg) return -1;
+  return e->lg->Sh.slot ? e->lg->Sh.n : 0;
 }
 
 int pgbp_lg_set_tip_noise(pgbp_engine* e, int32_t n, const int32_t* family, const double* scale, const double* sigma_e,
                           const double* se2, int32_t per_site) {
   DeviceScope device_scope(e);
   if (!e) return PGBP_ERR_INVALID;
-  if (!e->lg_ready) return e->fail(PGBP_ERR_STATE, "pgbp_lg_set_tip_noise: no family table (call pgbp_lg_setup first)");
-  if (n < 0 || (n > 0 && (!family || !scale || !sigma_e)))
-    return e->fail(PGBP_ERR_INVALID, "pgbp_lg_set_tip_noise: a negative count or a missing array");
-  const int nf = e->lg_nf, pp = e->lg.p, K = e->lg.K;
+  if (!e->lg) return e->fail(PGBP_ERR_STATE, "pgbp_lg_set_tip_noise: no family table (call pgbp_lg_setup first)");
+  LgModel& L = *e->lg;
+  // the slot table, sigma_e exactly symmetric, the clusters that hold a noisy tip family, in index order, and what the
+  // correction kernel needs for the largest of them
+  std::vector<int32_t> slot, cl;
+  std::vector<double> sig;
+  int32_t max_dim = 0;
+  std::string why;
+  if (!L.T.noise_list(n, family, scale, sigma_e, se2, per_site, slot, sig, cl, &max_dim, why)) return e->fail(PGBP_ERR_INVALID, why);
+  const int pp = L.T.p, K = L.T.K;
   const size_t ns = per_site ? (size_t)e->plan.n_sites : 1, nn = (size_t)n;
-  // every check before anything changes
-  std::vector<int32_t> slot(std::max<size_t>(1, (size_t)nf), -1);
-  std::vector<double> sig;   // sigma_e with the two triangles averaged: exactly symmetric on the device
-  if (n > 0) {
-    sig.assign(sigma_e, sigma_e + ns * pp * pp);
-    for (size_t s = 0; s < ns; ++s) {
-      const double* A = sigma_e + s * pp * pp;
-      const std::string where = "pgbp_lg_set_tip_noise: sigma_e" + (per_site ? " of site " + std::to_string(s) : std::string()) + ": ";
-      double big = 0.0;
-      for (int a = 0; a < pp * pp; ++a) {
-        if (!std::isfinite(A[a]))
-          return e->fail(PGBP_ERR_INVALID, where + "entry (" + std::to_string(a / pp) + ", " + std::to_string(a % pp) + ") is not finite");
-        big = std::max(big, std::fabs(A[a]));
-      }
-      for (int i = 0; i < pp; ++i) {
-        if (A[i * pp + i] < 0.0)
-          return e->fail(PGBP_ERR_INVALID, where + "diagonal entry " + std::to_string(i) + " is negative");
-        for (int j = 0; j < i; ++j) {
-          if (std::fabs(A[i * pp + j] - A[j * pp + i]) > 1e-12 * big)
-            return e->fail(PGBP_ERR_INVALID, where + "entries (" + std::to_string(i) + ", " + std::to_string(j) + ") and (" +
-                                                 std::to_string(j) + ", " + std::to_string(i) + ") differ: the matrix is not symmetric");
-          sig[s * pp * pp + i * pp + j] = sig[s * pp * pp + j * pp + i] = 0.5 * (A[i * pp + j] + A[j * pp + i]);
-        }
-      }
-    }
-  }
-  for (int i = 0; i < n; ++i) {
-    const std::string where = "pgbp_lg_set_tip_noise: entry " + std::to_string(i) + " (family " + std::to_string(family[i]) + "): ";
-    if (family[i] < 0 || family[i] >= nf) return e->fail(PGBP_ERR_INVALID, where + "family index out of range");
-    if (!e->lg_h_tip[family[i]])
-      return e->fail(PGBP_ERR_INVALID, where + "not a tip family (child_pos < 0, a data row and a parent edge)");
-    if (slot[family[i]] >= 0)
-      return e->fail(PGBP_ERR_INVALID, where + "the family is listed twice (entry " + std::to_string(slot[family[i]]) + " has it too)");
-    slot[family[i]] = i;
-    if (!std::isfinite(scale[i])) return e->fail(PGBP_ERR_INVALID, where + "the scale is not finite");
-    if (scale[i] < 0.0) return e->fail(PGBP_ERR_INVALID, where + "the scale is negative");
-    for (size_t s = 0; se2 && s < ns; ++s)
-      for (int t = 0; t < pp; ++t) {
-        const double v = se2[(s * nn + i) * pp + t];
-        if (!std::isfinite(v)) return e->fail(PGBP_ERR_INVALID, where + "se2 of trait " + std::to_string(t) + " is not finite");
-        if (v < 0.0) return e->fail(PGBP_ERR_INVALID, where + "se2 of trait " + std::to_string(t) + " is negative");
-      }
-  }
-  // the clusters that hold a noisy tip family, in index order, and what the correction kernel needs for the largest of them
-  std::vector<int32_t> cl;
-  for (int i = 0; i < n; ++i) cl.push_back(e->lg_h_cluster[family[i]]);
-  std::sort(cl.begin(), cl.end());
-  cl.erase(std::unique(cl.begin(), cl.end()), cl.end());
-  int max_dim = 0;
-  for (int32_t c : cl) max_dim = std::max(max_dim, (int)e->plan.dims[c]);
   if (n > 0) {
     const size_t bytes = lg_noise_lds_bytes(pp, K, max_dim);
     if (bytes > 160 * 1024)
@@ -2069,20 +1828,20 @@ int pgbp_lg_set_tip_noise(pgbp_engine* e, int32_t n, const int32_t* family, cons
   }
   if (n == 0) {   // clear (kernels already enqueued may still read the old noise)
     HIPCHK(e, hipStreamSynchronize(e->st));
-    e->lg_noise_bufs = LgNoiseBufs{};
-    e->lgn = LgNoise{};
-    e->lg_n_noise_cl = e->lg_noise_max_dim = 0;
+    L.noise_bufs = LgNoiseBufs{};
+    L.Nz = LgNoise{};
+    L.n_noise_cl = L.noise_max_dim = 0;
     return PGBP_OK;
   }
   // univariate per-site batches: se2 once more as [slot][site], what the thread-per-site correction reads
   std::vector<double> ssm;
-  if (per_site && se2 && e->lg_uni_ok) {
+  if (per_site && se2 && L.T.uni_ok) {
     const size_t row = (size_t)sm_row(e->plan.n_sites);
     ssm.assign(nn * row, 0.0);
     for (size_t s = 0; s < ns; ++s)
       for (size_t i = 0; i < nn; ++i) ssm[i * row + s] = se2[s * nn + i];
   }
-  LgNoiseBufs B;   // into a local: the engine takes it once every copy has been made
+  LgNoiseBufs B;
   int rc;
   if ((rc = dev_alloc(e, B.slot, slot.size()))) return rc;
   if ((rc = dev_alloc(e, B.cl, cl.size()))) return rc;
@@ -2102,73 +1861,51 @@ int pgbp_lg_set_tip_noise(pgbp_engine* e, int32_t n, const int32_t* family, cons
   const hipError_t serr = hipStreamSynchronize(e->st);  // the host buffers may go away; kernels that read the old noise have finished
   if (herr == hipSuccess) herr = serr;
   if (herr != hipSuccess) return e->fail(PGBP_ERR_HIP, std::string("pgbp_lg_set_tip_noise (upload): ") + hipGetErrorString(herr));
-  e->lg_noise_bufs = std::move(B);
-  const LgNoiseBufs& S = e->lg_noise_bufs;
-  e->lgn = LgNoise{S.slot.get(), S.scale.get(), S.sigma_e.get(), se2 ? S.se2.get() : nullptr, per_site ? 1 : 0, n, S.se2_sm.get()};
-  e->lg_n_noise_cl = (int32_t)cl.size();
-  e->lg_noise_max_dim = max_dim;
+  L.noise_bufs = std::move(B);
+  const LgNoiseBufs& S = L.noise_bufs;
+  L.Nz = LgNoise{S.slot.get(), S.scale.get(), S.sigma_e.get(), se2 ? S.se2.get() : nullptr, per_site ? 1 : 0, n, S.se2_sm.get()};
+  L.n_noise_cl = (int32_t)cl.size();
+  L.noise_max_dim = max_dim;
   return PGBP_OK;
 }
 
 int32_t pgbp_lg_tip_noise_count(pgbp_engine* e) {
-  if (!e || !e->lg_ready) return -1;
-  return e->lgn.slot ? e->lgn.n : 0;
+  if (!e || !e->lg) return -1;
+  return e->lg->Nz.slot ? e->lg->Nz.n : 0;
 }
 
 int pgbp_lg_set_topology(pgbp_engine* e, const int32_t* parent_family) {
   DeviceScope device_scope(e);
   if (!e) return PGBP_ERR_INVALID;
-  if (!e->lg_ready) return e->fail(PGBP_ERR_STATE, "pgbp_lg_set_topology: no family table (call pgbp_lg_setup first)");
-  const int K = e->lg.K, nf = e->lg_nf;
+  if (!e->lg) return e->fail(PGBP_ERR_STATE, "pgbp_lg_set_topology: no family table (call pgbp_lg_setup first)");
+  LgModel& L = *e->lg;
+  const int K = L.T.K, nf = L.T.n_families;
   if (nf > 0 && !parent_family) return e->fail(PGBP_ERR_INVALID, "pgbp_lg_set_topology: no table");
-  // every check before anything changes
   std::vector<int32_t> level_off, level_fam;
   int32_t improper = -1;
   std::string why;
-  if (!lg_topology_levels(nf, K, e->lg_h_np.data(), parent_family, level_off, level_fam, &improper, why))
+  if (!lg_topology_levels(nf, K, L.T.n_parents.data(), parent_family, level_off, level_fam, &improper, why))
     return e->fail(PGBP_ERR_INVALID, "pgbp_lg_set_topology: " + why);
   std::vector<int32_t> pf(std::max<size_t>(1, (size_t)nf * K), kTopoFixedRoot);
   for (int f = 0; f < nf; ++f)
-    for (int k = 0; k < e->lg_h_np[f]; ++k) pf[(size_t)f * K + k] = parent_family[(size_t)f * K + k];
+    for (int k = 0; k < L.T.n_parents[f]; ++k) pf[(size_t)f * K + k] = parent_family[(size_t)f * K + k];
   if (level_fam.empty()) level_fam.push_back(0);
-  DevBuf<int32_t> d_pf, d_lf;   // into locals: the engine takes them once both copies have been made
+  DevBuf<int32_t> d_pf, d_lf;
   int rc;
   if ((rc = upload(e, d_pf, pf))) return rc;
   if ((rc = upload(e, d_lf, level_fam))) return rc;
-  e->d_lg_pf = std::move(d_pf);
-  e->d_lg_level_fam = std::move(d_lf);
-  e->lg_h_level_off = std::move(level_off);
-  e->lg_topo_improper = improper;
-  e->lg_topo = true;
+  L.d_pf = std::move(d_pf);
+  L.d_level_fam = std::move(d_lf);
+  L.level_off = std::move(level_off);
+  L.improper = improper;
   return PGBP_OK;
 }
 
-// the range and, where the table says observed, the values: pgbp_lg_setup's checks of its data for sites [site_begin, site_end)
+// the table, then its checks of the range and, where it says observed, of the values of sites [site_begin, site_end)
 static int lg_check_data(pgbp_engine* e, const char* fn, int32_t site_begin, int32_t site_end, const double* data, bool values) {
-  if (!e->lg_ready) return e->fail(PGBP_ERR_STATE, std::string(fn) + ": no family table (call pgbp_lg_setup first)");
-  if (site_begin < 0 || site_end < site_begin || site_end > e->plan.n_sites)
-    return e->fail(PGBP_ERR_INVALID, std::string(fn) + ": site range [" + std::to_string(site_begin) + ", " + std::to_string(site_end) +
-                                         ") outside the engine's " + std::to_string(e->plan.n_sites) + " sites");
-  const size_t per = (size_t)e->lg.n_rows * e->lg.p, ns = (size_t)(site_end - site_begin);
-  if (ns * per > 0 && !data) return e->fail(PGBP_ERR_INVALID, std::string(fn) + ": no data buffer");
-  if (!values) return PGBP_OK;
-  const int pp = e->lg.p;
-  const unsigned long long full = pp >= 64 ? ~0ull : ((1ull << pp) - 1ull);
-  if (e->lg_h_cmask.empty()) {
-    for (size_t i = 0; i < ns * per; ++i)
-      if (!std::isfinite(data[i]))
-        return e->fail(PGBP_ERR_INVALID, std::string(fn) + ": a tip value is missing or not finite (the table has no child_mask: the data are complete)");
-    return PGBP_OK;
-  }
-  for (int f = 0; f < e->lg_nf; ++f) {
-    if (!e->lg_h_tip[f]) continue;
-    const unsigned long long O = e->lg_h_cmask[f] & full;
-    for (size_t s = 0; s < ns; ++s)
-      for (int t = 0; t < pp; ++t)
-        if (((O >> t) & 1ull) && !std::isfinite(data[(s * e->lg.n_rows + e->lg_h_row[f]) * pp + t]))
-          return e->fail(PGBP_ERR_INVALID, std::string(fn) + ": family " + std::to_string(f) + ": a tip value is missing or not finite "
-                                               "where child_mask says observed (the missing-data pattern is the set-up's)");
-  }
+  if (!e->lg) return e->fail(PGBP_ERR_STATE, std::string(fn) + ": no family table (call pgbp_lg_setup first)");
+  std::string why;
+  if (!e->lg->T.check_data(fn, site_begin, site_end, data, values, why)) return e->fail(PGBP_ERR_INVALID, why);
   return PGBP_OK;
 }
 
@@ -2177,18 +1914,19 @@ int pgbp_lg_set_data(pgbp_engine* e, int32_t site_begin, int32_t site_end, const
   if (!e) return PGBP_ERR_INVALID;
   const int rc = lg_check_data(e, "pgbp_lg_set_data", site_begin, site_end, data, true);
   if (rc) return rc;
-  const size_t per = (size_t)e->lg.n_rows * e->lg.p, n = (size_t)(site_end - site_begin) * per;
+  const LgModel& L = *e->lg;
+  const size_t per = (size_t)L.T.n_rows * L.T.p, n = (size_t)(site_end - site_begin) * per;
   if (n == 0) return PGBP_OK;
-  double* dst = e->lg_bufs.data.get() + (size_t)site_begin * per;
+  double* dst = L.bufs.data.get() + (size_t)site_begin * per;
   std::vector<double> clean;   // as the set-up: masked-out entries may be NaN on the host, they never reach arithmetic
-  if (!e->lg_h_cmask.empty()) {
+  if (!L.T.child_mask.empty()) {
     clean.assign(data, data + n);
     for (double& x : clean) if (!std::isfinite(x)) x = 0.0;
     data = clean.data();
   }
   hipError_t herr = hipMemcpyAsync(dst, data, n * sizeof(double), hipMemcpyHostToDevice, e->st);
-  if (herr == hipSuccess && e->lg_bufs.data_sm)   // the [row][site] copy of a univariate batch, whole
-    launch_transpose_words_f64(e->lg_bufs.data.get(), e->lg_bufs.data_sm.get(), e->lg.n_rows, e->plan.n_sites, 1, e->st);
+  if (herr == hipSuccess && L.bufs.data_sm)   // the [row][site] copy of a univariate batch, whole
+    launch_transpose_words_f64(L.bufs.data.get(), L.bufs.data_sm.get(), L.T.n_rows, e->plan.n_sites, 1, e->st);
   const hipError_t serr = hipStreamSynchronize(e->st);  // the host buffers may go away
   if (herr == hipSuccess) herr = serr;
   if (herr != hipSuccess) return e->fail(PGBP_ERR_HIP, std::string("pgbp_lg_set_data (upload): ") + hipGetErrorString(herr));
@@ -2200,9 +1938,10 @@ int pgbp_lg_get_data(pgbp_engine* e, int32_t site_begin, int32_t site_end, doubl
   if (!e) return PGBP_ERR_INVALID;
   const int rc = lg_check_data(e, "pgbp_lg_get_data", site_begin, site_end, data, false);
   if (rc) return rc;
-  const size_t per = (size_t)e->lg.n_rows * e->lg.p, n = (size_t)(site_end - site_begin) * per;
+  const LgModel& L = *e->lg;
+  const size_t per = (size_t)L.T.n_rows * L.T.p, n = (size_t)(site_end - site_begin) * per;
   if (n == 0) return PGBP_OK;
-  HIPCHK(e, hipMemcpyAsync(data, e->lg_bufs.data.get() + (size_t)site_begin * per, n * sizeof(double), hipMemcpyDeviceToHost, e->st));
+  HIPCHK(e, hipMemcpyAsync(data, L.bufs.data.get() + (size_t)site_begin * per, n * sizeof(double), hipMemcpyDeviceToHost, e->st));
   HIPCHK(e, hipStreamSynchronize(e->st));
   return PGBP_OK;
 }
@@ -2213,7 +1952,7 @@ int pgbp_enqueue_loglik_lg(pgbp_engine* e, int32_t reps, const pgbp_opts* opts) 
   int rc = check_opts(e, opts);
   if (rc) return rc;
   if ((rc = need_schedule(e, 0))) return rc;
-  if (!e->lg_ready || !e->lg_have_params)
+  if (!e->lg || !e->lg->have_params)
     return e->fail(PGBP_ERR_STATE, "pgbp_enqueue_loglik_lg: call pgbp_lg_setup / pgbp_lg_assignfactors first");
   if ((rc = reset_fail(e))) return rc;
   if ((rc = ensure_layout(e, want_bs16(e), want_site_minor(e)))) return rc;
@@ -2506,8 +2245,6 @@ EngineView engine_peek(pgbp_engine* e) {
   v.boff = e->d_boff.get();
   v.bdim = e->d_bdim.get();
   v.bs16 = e->layout_bs16 ? 1 : 0;
-  v.lg = &e->lg;
-  v.lg_ready = e->lg_ready ? 1 : 0;
   return v;
 }
 UniView engine_uni_view(pgbp_engine* e) {
@@ -2519,21 +2256,8 @@ UniView engine_uni_view(pgbp_engine* e) {
   u.stride = e->layout_sm ? sm_row(e->plan.n_sites) : e->plan.pool_stride();
   u.off = e->layout_sm ? e->d_packed_off.get() : e->d_boff.get();
   u.bdim = e->d_bdim.get();
-  u.fam_cluster = &e->lg_h_cluster;
   return u;
 }
 const Plan* engine_plan(const pgbp_engine* e) { return &e->plan; }
-bool engine_lg_params(const pgbp_engine* e, LgParams* out) {
-  if (!e->lg_ready || !e->lg_have_params) return false;
-  *out = e->lgp;
-  return true;
-}
-LgShifts engine_lg_shifts(const pgbp_engine* e) { return e->lg_ready ? e->lgs : LgShifts{}; }
-LgNoise engine_lg_noise(const pgbp_engine* e) { return e->lg_ready ? e->lgn : LgNoise{}; }
-LgSimView engine_lg_sim(pgbp_engine* e) {
-  DeviceScope device_scope(e);
-  const bool ok = e->lg_ready && e->lg_topo;
-  return LgSimView{ok ? 1 : 0, e->lg_topo_improper, e->d_lg_pf.get(), e->d_lg_level_fam.get(), &e->lg_h_level_off, e->lg_nf,
-                   e->lg_bufs.data.get(), e->lg_bufs.data_sm.get()};
-}
+const LgModel* engine_lg(const pgbp_engine* e) { return e->lg.get(); }
 }  // namespace pgbp

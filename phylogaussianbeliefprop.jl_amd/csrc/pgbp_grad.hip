@@ -32,6 +32,7 @@
 #include "pgbp_devmem.hpp"
 #include "pgbp_fam_dev.hpp"
 #include "pgbp_kernels.hpp"
+#include "pgbp_lgmodel.hpp"
 
 namespace pgbp {
 
@@ -224,35 +225,28 @@ using namespace pgbp;
 static int lg_gradient(pgbp_engine* e, int32_t site_begin, int32_t site_end, double* dR, double* dmu, double* dalpha,
                        double* dtheta, double* dsigma_e, int32_t* info) {
   if (!e) return PGBP_ERR_INVALID;
-  LgParams M{};
-  {
-    const EngineView v0 = engine_peek(e);
-    if (!v0.lg_ready)
-      return engine_fail(e, PGBP_ERR_STATE, "pgbp_lg_gradient: no family table (call pgbp_lg_setup first)");
-    if (!engine_lg_params(e, &M))
-      return engine_fail(e, PGBP_ERR_STATE, "pgbp_lg_gradient: no parameters yet (call pgbp_lg_assignfactors first)");
-    if (site_begin < 0 || site_end < site_begin || site_end > v0.plan->n_sites)
-      return engine_fail(e, PGBP_ERR_INVALID, "pgbp_lg_gradient: site range outside the engine's sites");
-    if (!dR || !dmu) return engine_fail(e, PGBP_ERR_INVALID, "pgbp_lg_gradient: no output buffer");
-    if (M.model == PGBP_LG_OU && (!dalpha || !dtheta))
-      return engine_fail(e, PGBP_ERR_INVALID, "pgbp_lg_gradient: the OU model needs dalpha and dtheta");
-  }
-  EngineView v;
-  int rc = engine_view(e, &v);
+  const LgModel* L = nullptr;
+  int rc = lg_sweep_state(e, "pgbp_lg_gradient", site_begin, site_end, &L);
   if (rc) return rc;
+  const LgStatic& F = L->F;
+  const LgParams& M = L->M;
+  const LgShifts& Sh = L->Sh;
+  const LgNoise& Nz = L->Nz;
+  if (!dR || !dmu) return engine_fail(e, PGBP_ERR_INVALID, "pgbp_lg_gradient: no output buffer");
+  if (M.model == PGBP_LG_OU && (!dalpha || !dtheta))
+    return engine_fail(e, PGBP_ERR_INVALID, "pgbp_lg_gradient: the OU model needs dalpha and dtheta");
+  EngineView v;
+  if ((rc = engine_view(e, &v))) return rc;
   // (as in pgbp_bm_exact_stats, what follows runs on the caller's current device: an engine of a multi-device group is
   // swept from the thread that has its device current)
   const Plan& pl = *v.plan;
-  const LgStatic& F = *v.lg;
-  const LgShifts Sh = engine_lg_shifts(e);
-  const LgNoise Nz = engine_lg_noise(e);
   const int p = F.p, K = F.K, nr0 = F.n_rates;
   const int nr = nr0 + (Nz.slot ? 1 : 0);   // the slots and the reduction carry Sigma_e as one more rate (grad_family)
-  std::vector<int32_t> fcl;   // which cluster each family sits in
+  const std::vector<int32_t>& fcl = L->T.cluster;   // which cluster each family sits in
   int max_m = 0;
-  rc = lg_family_clusters(e, "pgbp_lg_gradient", v, true, &fcl, &max_m);
-  if (rc) return rc;
-  const int nf = (int)fcl.size();
+  std::string why;
+  if (!L->T.cluster_dims("pgbp_lg_gradient", kLdsMaxDim, &max_m, why)) return engine_fail(e, PGBP_ERR_INVALID, why);
+  const int nf = L->T.n_families;
   const size_t lds_bytes = fam_score_lds_bytes(max_m, p, K, kGradRows, 0);
   if (lds_bytes > 160 * 1024)
     return engine_fail(e, PGBP_ERR_INVALID, "pgbp_lg_gradient: a cluster of " + std::to_string(max_m) + " variables with " +

@@ -29,6 +29,7 @@
 #include "pgbp_devmem.hpp"
 #include "pgbp_fam_dev.hpp"
 #include "pgbp_kernels.hpp"
+#include "pgbp_lgmodel.hpp"
 
 namespace pgbp {
 
@@ -210,18 +211,18 @@ extern "C" int pgbp_lg_gradient_sites(pgbp_engine* e, int32_t site_begin, int32_
                                       double* dalpha, double* dtheta, double* dsigma_e, int32_t* info) {
   if (!e) return PGBP_ERR_INVALID;
   const char* fn = "pgbp_lg_gradient_sites";
+  const LgModel* L = nullptr;
+  const int rc = lg_sweep_state(e, fn, site_begin, site_end, &L);
+  if (rc) return rc;
+  const LgStatic& F = L->F;
+  const LgParams& M = L->M;
+  const LgShifts& Sh = L->Sh;
+  const LgNoise& Nz = L->Nz;
   const EngineView v = engine_peek(e);   // (the layout is not touched)
-  LgParams M{};
-  if (!v.lg_ready) return engine_fail(e, PGBP_ERR_STATE, std::string(fn) + ": no family table (call pgbp_lg_setup first)");
-  if (!engine_lg_params(e, &M))
-    return engine_fail(e, PGBP_ERR_STATE, std::string(fn) + ": no parameters yet (call pgbp_lg_assignfactors first)");
   const Plan& pl = *v.plan;
-  if (site_begin < 0 || site_end < site_begin || site_end > pl.n_sites)
-    return engine_fail(e, PGBP_ERR_INVALID, std::string(fn) + ": site range outside the engine's sites");
   if (!dR || !dmu) return engine_fail(e, PGBP_ERR_INVALID, std::string(fn) + ": no output buffer");
   const bool ou = M.model == PGBP_LG_OU;
   if (ou && (!dalpha || !dtheta)) return engine_fail(e, PGBP_ERR_INVALID, std::string(fn) + ": the OU model needs dalpha and dtheta");
-  const LgStatic& F = *v.lg;
   const UniView U = engine_uni_view(e);
   // a thread-per-site engine, as the plan defines it
   if (F.p != 1)
@@ -235,7 +236,7 @@ extern "C" int pgbp_lg_gradient_sites(pgbp_engine* e, int32_t site_begin, int32_
   if (!U.tps || U.bs16) return engine_fail(e, PGBP_ERR_INVALID, std::string(fn) + ": the engine is not on the thread-per-site kernels");
   const int ns = site_end - site_begin;
   if (ns == 0) return PGBP_OK;
-  const int nr = F.n_rates, nf = (int)U.fam_cluster->size();
+  const int nr = F.n_rates, nf = L->T.n_families;
   const int n_ent = grad_uni_entries(nr);
   const int nfb = std::max(1, (nf + kGradUniFamBlock - 1) / kGradUniFamBlock);
   // the partials of a chunk of sites at a time: 256 MB at most (whole workgroups of sites; one workgroup's sites at least)
@@ -251,11 +252,9 @@ extern "C" int pgbp_lg_gradient_sites(pgbp_engine* e, int32_t site_begin, int32_
   if (herr == hipSuccess) herr = (hipError_t)d_out.alloc((size_t)n_ent * ns);
   if (herr == hipSuccess) herr = (hipError_t)d_info.alloc((size_t)ns);
   if (herr == hipSuccess && nf > 0)
-    herr = hipMemcpyAsync(d_fcl.get(), U.fam_cluster->data(), sizeof(int32_t) * nf, hipMemcpyHostToDevice, v.st);
+    herr = hipMemcpyAsync(d_fcl.get(), L->T.cluster.data(), sizeof(int32_t) * nf, hipMemcpyHostToDevice, v.st);
   if (herr != hipSuccess) return engine_fail(e, PGBP_ERR_HIP, std::string(fn) + " (scratch): " + hipGetErrorString(herr));
   (void)hipGetLastError();   // (an error an earlier asynchronous call left behind is that call's to report)
-  const LgShifts Sh = engine_lg_shifts(e);
-  const LgNoise Nz = engine_lg_noise(e);
   const int64_t data_row_len = sm_row(pl.n_sites);
   for (int s0 = 0; s0 < ns; s0 += chunk) {
     const int n = std::min(chunk, ns - s0);

@@ -35,6 +35,7 @@
 #include "pgbp_devmem.hpp"
 #include "pgbp_fam_dev.hpp"
 #include "pgbp_kernels.hpp"
+#include "pgbp_lgmodel.hpp"
 
 namespace pgbp {
 
@@ -253,83 +254,28 @@ __global__ __launch_bounds__(NT) void impute_family(const double* __restrict__ p
 // bound of the call's device outputs, in doubles: those of a chunk of sites (pgbp_impute_scratch_limit)
 static std::atomic<int64_t> g_impute_limit{(int64_t)32 << 20};
 
-// the listed families of the table given to pgbp_lg_setup (tip families with a missing trait), in table order, the cluster of
-// each and its mask P
-// (fcl, check_dims, max_m: lg_family_clusters -- the count and the list are served whatever the clusters' sizes, the sweep is not)
-static int impute_list(pgbp_engine* e, const EngineView& v, const char* fn, bool check_dims, std::vector<int32_t>& fams,
-                       std::vector<int32_t>& cls, std::vector<unsigned long long>& pred, std::vector<int32_t>& fcl, int* max_m) {
-  const LgStatic& F = *v.lg;
-  const int K = F.K;
-  const int rc = lg_family_clusters(e, fn, v, check_dims, &fcl, max_m);
-  if (rc) return rc;
-  const int nf = (int)fcl.size();
-  const size_t n1 = (size_t)std::max(nf, 1);
-  std::vector<int32_t> cpos(n1), drow(n1), npar(n1), ppos(n1 * K);
-  std::vector<unsigned long long> cmask, pmask;
-  hipError_t herr = hipSuccess;
-  const bool masks = F.child_mask && F.parent_mask;   // complete data: nothing is listed
-  if (nf > 0 && masks) {
-    cmask.resize(nf);
-    pmask.resize((size_t)nf * K);
-    herr = hipMemcpy(cpos.data(), F.child_pos, sizeof(int32_t) * nf, hipMemcpyDeviceToHost);
-    if (herr == hipSuccess) herr = hipMemcpy(drow.data(), F.data_row, sizeof(int32_t) * nf, hipMemcpyDeviceToHost);
-    if (herr == hipSuccess) herr = hipMemcpy(npar.data(), F.n_parents, sizeof(int32_t) * nf, hipMemcpyDeviceToHost);
-    if (herr == hipSuccess) herr = hipMemcpy(ppos.data(), F.parent_pos, sizeof(int32_t) * nf * K, hipMemcpyDeviceToHost);
-    if (herr == hipSuccess) herr = hipMemcpy(cmask.data(), F.child_mask, sizeof(unsigned long long) * nf, hipMemcpyDeviceToHost);
-    if (herr == hipSuccess)
-      herr = hipMemcpy(pmask.data(), F.parent_mask, sizeof(unsigned long long) * nf * K, hipMemcpyDeviceToHost);
-  }
-  if (herr != hipSuccess) return engine_fail(e, PGBP_ERR_HIP, std::string(fn) + " (family table): " + hipGetErrorString(herr));
-  const unsigned long long full = F.p >= 64 ? ~0ull : ((1ull << F.p) - 1ull);
-  fams.clear();
-  cls.clear();
-  pred.clear();
-  for (int f = 0; masks && f < nf; ++f) {
-    if (!(cpos[f] < 0 && drow[f] >= 0 && npar[f] >= 1)) continue;
-    const unsigned long long miss = full & ~cmask[f];
-    if (!miss) continue;
-    unsigned long long P = miss;
-    for (int k = 0; k < npar[f] && k < K; ++k) {
-      const unsigned long long mk = pmask[(size_t)f * K + k] & full;
-      if (!(ppos[(size_t)f * K + k] < 0 && mk == full)) P &= mk;   // a cluster parent (not the fixed root)
-    }
-    fams.push_back(f);
-    cls.push_back(fcl[f]);
-    pred.push_back(P);
-  }
-  return PGBP_OK;
-}
-
-static int impute_table(pgbp_engine* e, const char* fn, EngineView* v, std::vector<int32_t>& fams, std::vector<int32_t>& cls,
-                        std::vector<unsigned long long>& pred, std::vector<int32_t>& fcl, bool check_dims = false,
-                        int* max_m = nullptr) {
-  if (!engine_peek(e).lg_ready)
-    return engine_fail(e, PGBP_ERR_STATE, std::string(fn) + ": no family table (call pgbp_lg_setup first)");
-  const int rc = engine_view(e, v);
-  if (rc) return rc;
-  return impute_list(e, *v, fn, check_dims, fams, cls, pred, fcl, max_m);
-}
-
 }  // namespace pgbp
 
 using namespace pgbp;
 
+// the count and the list are the host table's, whatever the clusters' sizes (the sweep is not served above 128 variables)
 extern "C" int32_t pgbp_lg_impute_count(pgbp_engine* e) {
   if (!e) return -1;
-  EngineView v;
-  std::vector<int32_t> fams, cls, fcl;
+  const LgModel* L = engine_lg(e);
+  if (!L) return engine_fail(e, PGBP_ERR_STATE, "pgbp_lg_impute_count: no family table (call pgbp_lg_setup first)"), -1;
+  std::vector<int32_t> fams;
   std::vector<unsigned long long> pred;
-  if (impute_table(e, "pgbp_lg_impute_count", &v, fams, cls, pred, fcl)) return -1;
+  L->T.impute_list(fams, pred);
   return (int32_t)fams.size();
 }
 
 extern "C" int pgbp_lg_impute_families(pgbp_engine* e, int32_t* fam, uint64_t* predicted) {
   if (!e) return PGBP_ERR_INVALID;
-  EngineView v;
-  std::vector<int32_t> fams, cls, fcl;
+  const LgModel* L = engine_lg(e);
+  if (!L) return engine_fail(e, PGBP_ERR_STATE, "pgbp_lg_impute_families: no family table (call pgbp_lg_setup first)");
+  std::vector<int32_t> fams;
   std::vector<unsigned long long> pred;
-  const int rc = impute_table(e, "pgbp_lg_impute_families", &v, fams, cls, pred, fcl);
-  if (rc) return rc;
+  L->T.impute_list(fams, pred);
   if (fam) std::copy(fams.begin(), fams.end(), fam);
   if (predicted)
     for (size_t i = 0; i < pred.size(); ++i) predicted[i] = (uint64_t)pred[i];
@@ -340,28 +286,27 @@ extern "C" void pgbp_impute_scratch_limit(int64_t doubles) { g_impute_limit.stor
 
 extern "C" int pgbp_lg_impute(pgbp_engine* e, int32_t site_begin, int32_t site_end, double* mean, double* cov, int32_t* info) {
   if (!e) return PGBP_ERR_INVALID;
-  LgParams M{};
-  {
-    const EngineView v0 = engine_peek(e);
-    if (!v0.lg_ready) return engine_fail(e, PGBP_ERR_STATE, "pgbp_lg_impute: no family table (call pgbp_lg_setup first)");
-    if (!engine_lg_params(e, &M))
-      return engine_fail(e, PGBP_ERR_STATE, "pgbp_lg_impute: no parameters yet (call pgbp_lg_assignfactors first)");
-    if (site_begin < 0 || site_end < site_begin || site_end > v0.plan->n_sites)
-      return engine_fail(e, PGBP_ERR_INVALID, "pgbp_lg_impute: site range outside the engine's sites");
-    if (!mean && !cov) return engine_fail(e, PGBP_ERR_INVALID, "pgbp_lg_impute: no output buffer (mean and cov are both NULL)");
-  }
+  const LgModel* L = nullptr;
+  int rc = lg_sweep_state(e, "pgbp_lg_impute", site_begin, site_end, &L);
+  if (rc) return rc;
+  const LgStatic& F = L->F;
+  const LgParams& M = L->M;
+  const LgShifts& Sh = L->Sh;
+  const LgNoise& Nz = L->Nz;
+  if (!mean && !cov) return engine_fail(e, PGBP_ERR_INVALID, "pgbp_lg_impute: no output buffer (mean and cov are both NULL)");
   EngineView v;
-  std::vector<int32_t> fams, cls, fcl;
-  std::vector<unsigned long long> pred;
+  if ((rc = engine_view(e, &v))) return rc;
   // the limits are pgbp_lg_loo's, over the clusters of ALL families of the table: an engine serves every sweep or none
   int max_m = 0;
-  int rc = impute_table(e, "pgbp_lg_impute", &v, fams, cls, pred, fcl, true, &max_m);
-  if (rc) return rc;
+  std::string why;
+  if (!L->T.cluster_dims("pgbp_lg_impute", kLdsMaxDim, &max_m, why)) return engine_fail(e, PGBP_ERR_INVALID, why);
+  // the listed families (tip families with a missing trait), in table order, the cluster of each and its mask P
+  std::vector<int32_t> fams, cls;
+  std::vector<unsigned long long> pred;
+  L->T.impute_list(fams, pred);
+  for (int32_t f : fams) cls.push_back(L->T.cluster[f]);
   // (as in pgbp_lg_loo, what follows runs on the caller's current device)
   const Plan& pl = *v.plan;
-  const LgStatic& F = *v.lg;
-  const LgShifts Sh = engine_lg_shifts(e);
-  const LgNoise Nz = engine_lg_noise(e);
   const int p = F.p, K = F.K, n = (int)fams.size();
   size_t stage = 0;   // a packed record's plain copy
   for (int i = 0; i < n && v.bs16; ++i) {

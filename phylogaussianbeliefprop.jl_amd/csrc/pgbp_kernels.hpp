@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 
 #include "pgbp_internal.hpp"
+#include "pgbp_lgtable.hpp"
 
 namespace pgbp {
 
@@ -196,12 +197,6 @@ struct LgStatic {
   // a tree: cfg4): that family per cluster as one 48-byte record, or null (lg_fill_uni_sm_kernel then walks the general tables)
   const struct LgSimpleFam* simple;
 };
-struct LgSimpleFam {
-  int32_t np, cpos, ppos, row, color, pad;   // parents (0: a root prior), positions of child / parent in the cluster (-1: fixed), data row, rate
-  double length, gamma;
-  double pad2[2];
-};
-static_assert(sizeof(LgSimpleFam) == 56 || sizeof(LgSimpleFam) == 64, "LgSimpleFam");
 struct LgParams {
   int32_t model, per_site;
   const double *R, *alpha, *theta, *mu;  // device pointers
@@ -319,50 +314,21 @@ struct EngineView {
   const int64_t* boff;    // device copies of Plan::boff / Plan::dims
   const int32_t* bdim;
   int bs16;               // beliefs of dimension P / 2P are in the packed layout (pgbp_bs16.hpp)
-  const LgStatic* lg;     // the family table of pgbp_lg_setup (device pointers); lg_ready == 0: none
-  int lg_ready;
 };
 int engine_view(pgbp_engine* e, EngineView* v);
 EngineView engine_peek(pgbp_engine* e);          // the same words without touching the layout, the device or the last error
 // What pgbp_grad_uni.hip reads of a thread-per-site engine: the belief pool in the layout it is in (never converted).
 // sm != 0: element t of belief b of site s at pool[(off[b] + t) * stride + s] (off: the packed offsets, stride: sm_row(n_sites));
 // else at pool[s * stride + off[b] + t] (off: Plan::boff, stride: the pool's doubles per site).  tps: the engine runs the
-// thread-per-site kernels (every belief <= 2 variables, at least 8 sites); fam_cluster: family -> cluster of pgbp_lg_setup.
+// thread-per-site kernels (every belief <= 2 variables, at least 8 sites).
 struct UniView {
   int tps, sm, bs16;
   const double* pool;
   int64_t stride;
   const int64_t* off;
   const int32_t* bdim;
-  const std::vector<int32_t>* fam_cluster;
 };
 UniView engine_uni_view(pgbp_engine* e);
 const Plan* engine_plan(const pgbp_engine* e);
-// the parameters the engine kept from the last pgbp_lg_assignfactors (device pointers); false: none yet
-bool engine_lg_params(const pgbp_engine* e, LgParams* out);
-// the shifts of pgbp_lg_set_shifts (device pointers); slot == null: none set
-LgShifts engine_lg_shifts(const pgbp_engine* e);
-// the tip noise of pgbp_lg_set_tip_noise (device pointers); slot == null: none set
-LgNoise engine_lg_noise(const pgbp_engine* e);
-// What pgbp_simulate.hip needs beyond the view: the node topology of pgbp_lg_set_topology (ready == 0: none) -- parents by
-// family on the device, the families grouped by level (level_off on the host: it outlives the call with the engine) -- and the
-// tip data as the one writer besides the set-up sees them (data_sm: null unless LgStatic::data_sm is kept).  Makes the
-// engine's device current.
-struct LgSimView {
-  int ready;
-  int32_t improper;                        // first topology entry f * K + k that is an improper root, -1: none
-  const int32_t* parent_family;            // device [n_families * K]
-  const int32_t* level_fam;                // device [n_families]
-  const std::vector<int32_t>* level_off;   // host [n_levels + 1]
-  int32_t n_families;
-  double *data, *data_sm;
-};
-LgSimView engine_lg_sim(pgbp_engine* e);
-// Which cluster each family of pgbp_lg_setup's table sits in: the table's CSR (LgStatic::cl_off, cl_fam) back from the device, a
-// word per family, inverted to fcl[f] (one entry per family).  max_m (may be null): the largest dimension among the clusters
-// that hold a family, 0 without families.  check_dims: a family in a cluster of more than kLdsMaxDim variables fails the call,
-// "<fn>: family F (cluster C): the cluster has more than 128 variables".  Returns PGBP_OK or engine_fail's code.
-int lg_family_clusters(pgbp_engine* e, const char* fn, const EngineView& v, bool check_dims, std::vector<int32_t>* fcl,
-                       int* max_m);
 
 }  // namespace pgbp

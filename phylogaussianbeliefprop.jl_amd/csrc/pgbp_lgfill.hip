@@ -413,30 +413,4 @@ void launch_lg_fill_uni_sm(const LgStatic& F, const LgParams& M, double* pool_sm
                      d_poff, d_dim, n_clusters, n_sites);
 }
 
-int lg_family_clusters(pgbp_engine* e, const char* fn, const EngineView& v, bool check_dims, std::vector<int32_t>* fcl,
-                       int* max_m) {
-  const Plan& pl = *v.plan;
-  const LgStatic& F = *v.lg;
-  const int nc = pl.n_clusters;
-  std::vector<int32_t> off(nc + 1);
-  hipError_t herr = hipMemcpy(off.data(), F.cl_off, sizeof(int32_t) * (nc + 1), hipMemcpyDeviceToHost);
-  const int nf = herr == hipSuccess ? off[nc] : 0;
-  std::vector<int32_t> cfam(nf);
-  if (herr == hipSuccess && nf > 0) herr = hipMemcpy(cfam.data(), F.cl_fam, sizeof(int32_t) * nf, hipMemcpyDeviceToHost);
-  if (herr != hipSuccess) return engine_fail(e, PGBP_ERR_HIP, std::string(fn) + " (family table): " + hipGetErrorString(herr));
-  fcl->assign(nf, 0);
-  int mm = 0;
-  for (int c = 0; c < nc; ++c)
-    for (int q = off[c]; q < off[c + 1]; ++q) {
-      (*fcl)[cfam[q]] = c;
-      if (check_dims && pl.dims[c] > kLdsMaxDim)
-        return engine_fail(e, PGBP_ERR_INVALID, std::string(fn) + ": family " + std::to_string(cfam[q]) + " (cluster " +
-                                                    std::to_string(c) + "): the cluster has more than " +
-                                                    std::to_string(kLdsMaxDim) + " variables");
-      mm = std::max(mm, (int)pl.dims[c]);
-    }
-  if (max_m) *max_m = mm;
-  return PGBP_OK;
-}
-
 }  // namespace pgbp

@@ -1,0 +1,70 @@
+// The one owner of everything behind a family table: the table on the host, the device buffers, the
+// kernel-argument structs that borrow from them, and what the setters added.  pgbp_lg_setup builds a whole one and the
+// engine takes it; an engine without a table holds none.
+#pragma once
+#include <memory>
+#include <vector>
+
+#include "pgbp_devmem.hpp"
+#include "pgbp_kernels.hpp"
+#include "pgbp_lgtable.hpp"
+
+namespace pgbp {
+
+// what LgStatic points at: the family table of pgbp_lg_setup and the parameter slots pgbp_lg_assignfactors fills
+struct LgBufs {
+  DevBuf<int32_t> off, fam, np, cp, row, pp, col;
+  DevBuf<double> len, gam, data, data_sm;
+  DevBuf<unsigned long long> cm, pm;
+  DevBuf<LgSimpleFam> simple;
+  DevBuf<double> R, alpha, theta, mu;
+};
+// what LgShifts points at (pgbp_lg_set_shifts), and the clusters the correction kernel visits
+struct LgShiftBufs {
+  DevBuf<int32_t> slot, cl;
+  DevBuf<double> value, value_sm;
+};
+// what LgNoise points at (pgbp_lg_set_tip_noise), and the clusters the correction kernel visits
+struct LgNoiseBufs {
+  DevBuf<int32_t> slot, cl;
+  DevBuf<double> scale, sigma_e, se2, se2_sm;
+};
+
+struct LgModel {
+  LgTable T;
+  LgBufs bufs;
+  LgStatic F{};             // device pointers into bufs
+  LgParams M{};             // the last pgbp_lg_assignfactors (have_params), into bufs
+  bool have_params = false;
+  // pgbp_lg_set_shifts: Sh.slot == null: none; the number of clusters that hold a shifted family (shift_bufs.cl)
+  LgShiftBufs shift_bufs;
+  LgShifts Sh{};
+  int32_t n_shift_cl = 0;
+  // pgbp_lg_set_tip_noise: Nz.slot == null: none; the clusters that hold a noisy tip family and the largest of them
+  LgNoiseBufs noise_bufs;
+  LgNoise Nz{};
+  int32_t n_noise_cl = 0, noise_max_dim = 0;
+  // pgbp_lg_set_topology (d_pf null: none): parents by family [n_families * K] and the families grouped by level
+  // (pgbp_topology.hpp); improper: the first entry f * K + k that is an improper root, -1: none
+  DevBuf<int32_t> d_pf, d_level_fam;
+  std::vector<int32_t> level_off;
+  int32_t improper = -1;
+};
+
+// the model of the engine's family table, null when there is none (defined in pgbp_engine.hip)
+const LgModel* engine_lg(const pgbp_engine* e);
+
+// What a sweep `fn` checks of the engine's state before anything else, in this order: a table, parameters, the site range.
+// PGBP_OK with *out, or engine_fail's code.
+inline int lg_sweep_state(pgbp_engine* e, const char* fn, int32_t site_begin, int32_t site_end, const LgModel** out) {
+  const LgModel* L = engine_lg(e);
+  if (!L) return engine_fail(e, PGBP_ERR_STATE, std::string(fn) + ": no family table (call pgbp_lg_setup first)");
+  if (!L->have_params)
+    return engine_fail(e, PGBP_ERR_STATE, std::string(fn) + ": no parameters yet (call pgbp_lg_assignfactors first)");
+  if (site_begin < 0 || site_end < site_begin || site_end > engine_n_sites(e))
+    return engine_fail(e, PGBP_ERR_INVALID, std::string(fn) + ": site range outside the engine's sites");
+  *out = L;
+  return PGBP_OK;
+}
+
+}  // namespace pgbp

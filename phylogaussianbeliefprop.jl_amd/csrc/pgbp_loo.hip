@@ -31,6 +31,7 @@
 #include "pgbp_devmem.hpp"
 #include "pgbp_fam_dev.hpp"
 #include "pgbp_kernels.hpp"
+#include "pgbp_lgmodel.hpp"
 
 namespace pgbp {
 
@@ -232,62 +233,23 @@ __global__ __launch_bounds__(256) void loo_reduce(const double* __restrict__ lpd
 // bound of the call's device outputs, in doubles: those of a chunk of sites (pgbp_loo_scratch_limit)
 static std::atomic<int64_t> g_loo_limit{(int64_t)32 << 20};
 
-// the tip families of the table given to pgbp_lg_setup, in order, and the cluster of each
-// (fcl, check_dims, max_m: lg_family_clusters -- the count and the list are served whatever the clusters' sizes, the sweep is not)
-static int loo_tips(pgbp_engine* e, const EngineView& v, const char* fn, bool check_dims, std::vector<int32_t>& tips,
-                    std::vector<int32_t>& tcl, std::vector<int32_t>& fcl, int* max_m) {
-  const LgStatic& F = *v.lg;
-  const int rc = lg_family_clusters(e, fn, v, check_dims, &fcl, max_m);
-  if (rc) return rc;
-  const int nf = (int)fcl.size();
-  std::vector<int32_t> cpos(std::max(nf, 1)), drow(std::max(nf, 1));
-  std::vector<unsigned long long> cmask;
-  hipError_t herr = hipSuccess;
-  if (nf > 0) herr = hipMemcpy(cpos.data(), F.child_pos, sizeof(int32_t) * nf, hipMemcpyDeviceToHost);
-  if (herr == hipSuccess && nf > 0) herr = hipMemcpy(drow.data(), F.data_row, sizeof(int32_t) * nf, hipMemcpyDeviceToHost);
-  if (herr == hipSuccess && nf > 0 && F.child_mask) {
-    cmask.resize(nf);
-    herr = hipMemcpy(cmask.data(), F.child_mask, sizeof(unsigned long long) * nf, hipMemcpyDeviceToHost);
-  }
-  if (herr != hipSuccess) return engine_fail(e, PGBP_ERR_HIP, std::string(fn) + " (family table): " + hipGetErrorString(herr));
-  const unsigned long long full = F.p >= 64 ? ~0ull : ((1ull << F.p) - 1ull);
-  tips.clear();
-  tcl.clear();
-  for (int f = 0; f < nf; ++f)
-    if (cpos[f] < 0 && drow[f] >= 0 && (cmask.empty() || (cmask[f] & full) != 0)) {
-      tips.push_back(f);
-      tcl.push_back(fcl[f]);
-    }
-  return PGBP_OK;
-}
-
-static int loo_table(pgbp_engine* e, const char* fn, EngineView* v, std::vector<int32_t>& tips, std::vector<int32_t>& tcl,
-                     std::vector<int32_t>& fcl, bool check_dims = false, int* max_m = nullptr) {
-  if (!engine_peek(e).lg_ready)
-    return engine_fail(e, PGBP_ERR_STATE, std::string(fn) + ": no family table (call pgbp_lg_setup first)");
-  const int rc = engine_view(e, v);
-  if (rc) return rc;
-  return loo_tips(e, *v, fn, check_dims, tips, tcl, fcl, max_m);
-}
-
 }  // namespace pgbp
 
 using namespace pgbp;
 
+// the count and the list are the host table's, whatever the clusters' sizes (the sweep is not served above 128 variables)
 extern "C" int32_t pgbp_lg_loo_count(pgbp_engine* e) {
   if (!e) return -1;
-  EngineView v;
-  std::vector<int32_t> tips, tcl, fcl;
-  if (loo_table(e, "pgbp_lg_loo_count", &v, tips, tcl, fcl)) return -1;
-  return (int32_t)tips.size();
+  const LgModel* L = engine_lg(e);
+  if (!L) return engine_fail(e, PGBP_ERR_STATE, "pgbp_lg_loo_count: no family table (call pgbp_lg_setup first)"), -1;
+  return (int32_t)L->T.loo_tips().size();
 }
 
 extern "C" int pgbp_lg_loo_families(pgbp_engine* e, int32_t* fam) {
   if (!e) return PGBP_ERR_INVALID;
-  EngineView v;
-  std::vector<int32_t> tips, tcl, fcl;
-  const int rc = loo_table(e, "pgbp_lg_loo_families", &v, tips, tcl, fcl);
-  if (rc) return rc;
+  const LgModel* L = engine_lg(e);
+  if (!L) return engine_fail(e, PGBP_ERR_STATE, "pgbp_lg_loo_families: no family table (call pgbp_lg_setup first)");
+  const std::vector<int32_t> tips = L->T.loo_tips();
   if (!fam && !tips.empty()) return engine_fail(e, PGBP_ERR_INVALID, "pgbp_lg_loo_families: no output buffer");
   std::copy(tips.begin(), tips.end(), fam);
   return PGBP_OK;
@@ -298,28 +260,26 @@ extern "C" void pgbp_loo_scratch_limit(int64_t doubles) { g_loo_limit.store(doub
 extern "C" int pgbp_lg_loo(pgbp_engine* e, int32_t site_begin, int32_t site_end, double* mean, double* cov, double* lpd,
                            double* total, int32_t* info) {
   if (!e) return PGBP_ERR_INVALID;
-  LgParams M{};
-  {
-    const EngineView v0 = engine_peek(e);
-    if (!v0.lg_ready) return engine_fail(e, PGBP_ERR_STATE, "pgbp_lg_loo: no family table (call pgbp_lg_setup first)");
-    if (!engine_lg_params(e, &M))
-      return engine_fail(e, PGBP_ERR_STATE, "pgbp_lg_loo: no parameters yet (call pgbp_lg_assignfactors first)");
-    if (site_begin < 0 || site_end < site_begin || site_end > v0.plan->n_sites)
-      return engine_fail(e, PGBP_ERR_INVALID, "pgbp_lg_loo: site range outside the engine's sites");
-    if (!lpd) return engine_fail(e, PGBP_ERR_INVALID, "pgbp_lg_loo: no output buffer (lpd)");
-  }
+  const LgModel* L = nullptr;
+  int rc = lg_sweep_state(e, "pgbp_lg_loo", site_begin, site_end, &L);
+  if (rc) return rc;
+  const LgStatic& F = L->F;
+  const LgParams& M = L->M;
+  const LgShifts& Sh = L->Sh;
+  const LgNoise& Nz = L->Nz;
+  if (!lpd) return engine_fail(e, PGBP_ERR_INVALID, "pgbp_lg_loo: no output buffer (lpd)");
   EngineView v;
-  std::vector<int32_t> tips, tcl, fcl;
+  if ((rc = engine_view(e, &v))) return rc;
   // the limits are pgbp_lg_gradient's, over the clusters of ALL families of the table: an engine either serves both sweeps
   // or neither, and the dimension class of the launch is the gradient's
   int max_m = 0;
-  int rc = loo_table(e, "pgbp_lg_loo", &v, tips, tcl, fcl, true, &max_m);
-  if (rc) return rc;
+  std::string why;
+  if (!L->T.cluster_dims("pgbp_lg_loo", kLdsMaxDim, &max_m, why)) return engine_fail(e, PGBP_ERR_INVALID, why);
+  const std::vector<int32_t> tips = L->T.loo_tips();   // the tip families, in table order, and the cluster of each
+  std::vector<int32_t> tcl;
+  for (int32_t f : tips) tcl.push_back(L->T.cluster[f]);
   // (as in pgbp_lg_gradient, what follows runs on the caller's current device)
   const Plan& pl = *v.plan;
-  const LgStatic& F = *v.lg;
-  const LgShifts Sh = engine_lg_shifts(e);
-  const LgNoise Nz = engine_lg_noise(e);
   const int p = F.p, K = F.K, nt = (int)tips.size();
   size_t stage = 0;   // a packed record's plain copy
   for (int i = 0; i < nt && v.bs16; ++i) {

@@ -27,6 +27,7 @@
 #include "pgbp_bs16.hpp"
 #include "pgbp_devmem.hpp"
 #include "pgbp_kernels.hpp"
+#include "pgbp_lgmodel.hpp"
 #include "pgbp_mom_dev.hpp"
 
 namespace pgbp {
@@ -477,43 +478,24 @@ extern "C" int pgbp_moments(pgbp_engine* e, int32_t n, const int32_t* beliefs, i
 
 extern "C" int pgbp_bm_exact_stats(pgbp_engine* e, int32_t site_begin, int32_t site_end, double* num, double* den, int32_t* info) {
   if (!e) return PGBP_ERR_INVALID;
-  {
-    const EngineView v0 = engine_peek(e);
-    if (!v0.lg_ready)
-      return engine_fail(e, PGBP_ERR_STATE, "pgbp_bm_exact_stats: no family table (call pgbp_lg_setup first)");
-    if (site_begin < 0 || site_end < site_begin || site_end > v0.plan->n_sites)
-      return engine_fail(e, PGBP_ERR_INVALID, "pgbp_bm_exact_stats: site range outside the engine's sites");
-    if (!num || !den) return engine_fail(e, PGBP_ERR_INVALID, "pgbp_bm_exact_stats: no output buffer");
-  }
+  const LgModel* L = engine_lg(e);
+  if (!L) return engine_fail(e, PGBP_ERR_STATE, "pgbp_bm_exact_stats: no family table (call pgbp_lg_setup first)");
+  if (site_begin < 0 || site_end < site_begin || site_end > engine_n_sites(e))
+    return engine_fail(e, PGBP_ERR_INVALID, "pgbp_bm_exact_stats: site range outside the engine's sites");
+  if (!num || !den) return engine_fail(e, PGBP_ERR_INVALID, "pgbp_bm_exact_stats: no output buffer");
   EngineView v;
   int rc = engine_view(e, &v);
   if (rc) return rc;
   const Plan& pl = *v.plan;
-  const LgStatic& F = *v.lg;
+  const LgStatic& F = L->F;
   const int p = F.p, K = F.K;
-  // the family table back from the device (a few words per family) for the checks of src/calibration.jl:416-421 and of this
-  // sweep; the size of a family's cluster is checked below, family by family, behind the reference's own checks
-  std::vector<int32_t> fcl;
-  rc = lg_family_clusters(e, "pgbp_bm_exact_stats", v, false, &fcl, nullptr);
-  if (rc) return rc;
-  const int nf = (int)fcl.size();
-  std::vector<int32_t> npar(std::max(nf, 1)), cpos(std::max(nf, 1)), ppos((size_t)std::max(nf, 1) * K);
-  std::vector<unsigned long long> cmask, pmask;
+  // the host table for the checks of src/calibration.jl:416-421 and of this sweep; the size of a family's cluster is checked
+  // below, family by family, behind the reference's own checks
+  const LgTable& T = L->T;
+  const std::vector<int32_t> &fcl = T.cluster, &npar = T.n_parents, &cpos = T.child_pos, &ppos = T.parent_pos;
+  const std::vector<unsigned long long> &cmask = T.child_mask, &pmask = T.parent_mask;
+  const int nf = T.n_families;
   hipError_t herr = hipSuccess;
-  if (nf > 0) {
-    herr = hipMemcpy(npar.data(), F.n_parents, sizeof(int32_t) * nf, hipMemcpyDeviceToHost);
-    if (herr == hipSuccess) herr = hipMemcpy(cpos.data(), F.child_pos, sizeof(int32_t) * nf, hipMemcpyDeviceToHost);
-    if (herr == hipSuccess) herr = hipMemcpy(ppos.data(), F.parent_pos, sizeof(int32_t) * (size_t)nf * K, hipMemcpyDeviceToHost);
-    if (herr == hipSuccess && F.child_mask) {
-      cmask.resize(nf);
-      herr = hipMemcpy(cmask.data(), F.child_mask, sizeof(unsigned long long) * nf, hipMemcpyDeviceToHost);
-    }
-    if (herr == hipSuccess && F.parent_mask) {
-      pmask.resize((size_t)nf * K);
-      herr = hipMemcpy(pmask.data(), F.parent_mask, sizeof(unsigned long long) * (size_t)nf * K, hipMemcpyDeviceToHost);
-    }
-  }
-  if (herr != hipSuccess) return engine_fail(e, PGBP_ERR_HIP, std::string("pgbp_bm_exact_stats: ") + hipGetErrorString(herr));
   const unsigned long long full = p >= 64 ? ~0ull : ((1ull << p) - 1ull);
   int max_m = 1;
   for (int f = 0; f < nf; ++f) {

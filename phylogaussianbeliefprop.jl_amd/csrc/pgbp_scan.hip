@@ -32,6 +32,7 @@
 #include "pgbp_devmem.hpp"
 #include "pgbp_fam_dev.hpp"
 #include "pgbp_kernels.hpp"
+#include "pgbp_lgmodel.hpp"
 
 namespace pgbp {
 
@@ -210,36 +211,31 @@ using namespace pgbp;
 extern "C" int pgbp_lg_shift_scan(pgbp_engine* e, int32_t site_begin, int32_t site_end, double min_info, double* jump, double* lr,
                                   uint64_t* identified, double* information, int32_t* info) {
   if (!e) return PGBP_ERR_INVALID;
-  LgParams M{};
-  {
-    const EngineView v0 = engine_peek(e);
-    if (!v0.lg_ready) return engine_fail(e, PGBP_ERR_STATE, "pgbp_lg_shift_scan: no family table (call pgbp_lg_setup first)");
-    if (v0.lg->p > 64)   // (a table the scan cannot serve, whatever its parameters)
-      return engine_fail(e, PGBP_ERR_INVALID,
-                         "pgbp_lg_shift_scan: p = " + std::to_string(v0.lg->p) + " traits, more than the 64 of a trait mask");
-    if (!engine_lg_params(e, &M))
-      return engine_fail(e, PGBP_ERR_STATE, "pgbp_lg_shift_scan: no parameters yet (call pgbp_lg_assignfactors first)");
-    if (site_begin < 0 || site_end < site_begin || site_end > v0.plan->n_sites)
-      return engine_fail(e, PGBP_ERR_INVALID, "pgbp_lg_shift_scan: site range outside the engine's sites");
-    if (!jump && !lr && !identified && !information)
-      return engine_fail(e, PGBP_ERR_INVALID, "pgbp_lg_shift_scan: no output buffer");
-    if (!(min_info >= 0.0 && min_info < 1.0))
-      return engine_fail(e, PGBP_ERR_INVALID, "pgbp_lg_shift_scan: min_info = " + std::to_string(min_info) + " is not in [0, 1)");
-  }
-  EngineView v;
-  int rc = engine_view(e, &v);
+  const LgModel* L = engine_lg(e);
+  if (!L) return engine_fail(e, PGBP_ERR_STATE, "pgbp_lg_shift_scan: no family table (call pgbp_lg_setup first)");
+  if (L->T.p > 64)   // (a table the scan cannot serve, whatever its parameters)
+    return engine_fail(e, PGBP_ERR_INVALID,
+                       "pgbp_lg_shift_scan: p = " + std::to_string(L->T.p) + " traits, more than the 64 of a trait mask");
+  int rc = lg_sweep_state(e, "pgbp_lg_shift_scan", site_begin, site_end, &L);
   if (rc) return rc;
+  const LgStatic& F = L->F;
+  const LgParams& M = L->M;
+  const LgShifts& Sh = L->Sh;
+  const LgNoise& Nz = L->Nz;
+  if (!jump && !lr && !identified && !information)
+    return engine_fail(e, PGBP_ERR_INVALID, "pgbp_lg_shift_scan: no output buffer");
+  if (!(min_info >= 0.0 && min_info < 1.0))
+    return engine_fail(e, PGBP_ERR_INVALID, "pgbp_lg_shift_scan: min_info = " + std::to_string(min_info) + " is not in [0, 1)");
+  EngineView v;
+  if ((rc = engine_view(e, &v))) return rc;
   // (as in pgbp_lg_edge_gradient, what follows runs on the caller's current device)
   const Plan& pl = *v.plan;
-  const LgStatic& F = *v.lg;
-  const LgShifts Sh = engine_lg_shifts(e);
-  const LgNoise Nz = engine_lg_noise(e);
   const int p = F.p, K = F.K;
-  std::vector<int32_t> fcl;   // which cluster each family sits in
+  const std::vector<int32_t>& fcl = L->T.cluster;   // which cluster each family sits in
   int max_m = 0;
-  rc = lg_family_clusters(e, "pgbp_lg_shift_scan", v, true, &fcl, &max_m);
-  if (rc) return rc;
-  const int nf = (int)fcl.size();
+  std::string why;
+  if (!L->T.cluster_dims("pgbp_lg_shift_scan", kLdsMaxDim, &max_m, why)) return engine_fail(e, PGBP_ERR_INVALID, why);
+  const int nf = L->T.n_families;
   size_t stage = 0;   // a packed record's plain copy
   for (int f = 0; f < nf && v.bs16; ++f) {
     const size_t m = (size_t)pl.dims[fcl[f]];

@@ -31,6 +31,7 @@
 #include "pgbp_devmem.hpp"
 #include "pgbp_fam_dev.hpp"
 #include "pgbp_kernels.hpp"
+#include "pgbp_lgmodel.hpp"
 #include "pgbp_topology.hpp"
 
 namespace pgbp {
@@ -299,15 +300,22 @@ static int lg_simulate(pgbp_engine* e, int32_t site_begin, int32_t site_end, con
   if (!e) return PGBP_ERR_INVALID;
   const std::string fn = "pgbp_lg_simulate: ";
   const EngineView v = engine_peek(e);
-  const LgSimView T = engine_lg_sim(e);
-  LgParams M{};
-  if (!v.lg_ready) return engine_fail(e, PGBP_ERR_STATE, fn + "no family table (call pgbp_lg_setup first)");
-  if (!T.ready) return engine_fail(e, PGBP_ERR_STATE, fn + "no topology (call pgbp_lg_set_topology first)");
-  if (!engine_lg_params(e, &M)) return engine_fail(e, PGBP_ERR_STATE, fn + "no parameters yet (call pgbp_lg_assignfactors first)");
-  const LgStatic& F = *v.lg;
-  const int p = F.p, K = F.K, nf = T.n_families;
-  if (T.improper >= 0)
-    return engine_fail(e, PGBP_ERR_INVALID, fn + "family " + std::to_string(T.improper / K) + ", parent " + std::to_string(T.improper % K) +
+  (void)hipSetDevice(engine_device(e));
+  const LgModel* L = engine_lg(e);
+  if (!L) return engine_fail(e, PGBP_ERR_STATE, fn + "no family table (call pgbp_lg_setup first)");
+  if (!L->d_pf) return engine_fail(e, PGBP_ERR_STATE, fn + "no topology (call pgbp_lg_set_topology first)");
+  if (!L->have_params) return engine_fail(e, PGBP_ERR_STATE, fn + "no parameters yet (call pgbp_lg_assignfactors first)");
+  const LgStatic& F = L->F;
+  const LgParams& M = L->M;
+  const LgShifts& Sh = L->Sh;
+  const LgNoise& Nz = L->Nz;
+  // the node topology (parents by family on the device, the families grouped by level) and the tip data as the one writer
+  // besides the set-up sees them (data_sm: null unless the table keeps the [row][site] copy)
+  const int32_t *parent_family = L->d_pf.get(), *level_fam = L->d_level_fam.get();
+  double *data = L->bufs.data.get(), *data_sm = L->bufs.data_sm.get();
+  const int p = F.p, K = F.K, nf = L->T.n_families;
+  if (L->improper >= 0)
+    return engine_fail(e, PGBP_ERR_INVALID, fn + "family " + std::to_string(L->improper / K) + ", parent " + std::to_string(L->improper % K) +
                                                 " is a root without a proper prior: the model has no joint distribution to draw from");
   if (site_begin < 0 || site_end < site_begin || site_end > v.plan->n_sites)
     return engine_fail(e, PGBP_ERR_INVALID, fn + "site range [" + std::to_string(site_begin) + ", " + std::to_string(site_end) +
@@ -320,10 +328,8 @@ static int lg_simulate(pgbp_engine* e, int32_t site_begin, int32_t site_end, con
     if (info) std::fill(info, info + ns, 0);
     return PGBP_OK;
   }
-  const LgShifts Sh = engine_lg_shifts(e);
-  const LgNoise Nz = engine_lg_noise(e);
   const int per_set = (M.per_site || (Sh.slot && Sh.per_site) || (Nz.slot && Nz.per_site)) ? 1 : 0;
-  const bool sm = p == 1 && T.data_sm != nullptr;
+  const bool sm = p == 1 && data_sm != nullptr;
   const int64_t rec = sim_rec(p, K), f_stride = (int64_t)nf * rec, size = (int64_t)nf * p;
   int64_t chunk = std::max<int64_t>(1, std::min<int64_t>(ns, g_sim_state_limit.load() / size));
   if (per_set) chunk = std::max<int64_t>(1, std::min<int64_t>(chunk, g_sim_factor_limit.load() / f_stride));
@@ -353,7 +359,7 @@ static int lg_simulate(pgbp_engine* e, int32_t site_begin, int32_t site_end, con
   if (ms) ms[0] = ms[1] = ms[2] = ms[3] = 0.0;
   (void)hipGetLastError();   // (an error an earlier asynchronous call left behind is that call's to report)
   phase(-1);
-  const std::vector<int32_t>& lo = *T.level_off;
+  const std::vector<int32_t>& lo = L->level_off;
   const size_t lds = sizeof(double) * (size_t)sim_region(p, K) * (p <= 16 ? 4 : 1);   // (p = 1: sim_factor_uni uses none)
   const uint32_t k0 = (uint32_t)(seed & 0xffffffffu), k1 = (uint32_t)(seed >> 32);
   for (int64_t s0 = 0; herr == hipSuccess && s0 < ns; s0 += chunk) {
@@ -367,15 +373,15 @@ static int lg_simulate(pgbp_engine* e, int32_t site_begin, int32_t site_end, con
         herr = hipMemsetAsync(d_stat.get(), 0, sizeof(int32_t) * (size_t)n_sets * nf, v.st);
         if (pool_sm)
           hipLaunchKernelGGL(sim_factor_uni<true>, dim3((n_sets + 255) / 256, std::min(nf, 65535)), dim3(256), 0, v.st, F, M, Sh, Nz,
-                             T.parent_family, nf, site0, n_sets, per_set, d_f.get(), pss, pfs, d_stat.get());
+                             parent_family, nf, site0, n_sets, per_set, d_f.get(), pss, pfs, d_stat.get());
         else
-          hipLaunchKernelGGL(sim_factor_uni<false>, dim3((nf + 255) / 256, gy), dim3(256), 0, v.st, F, M, Sh, Nz, T.parent_family, nf,
+          hipLaunchKernelGGL(sim_factor_uni<false>, dim3((nf + 255) / 256, gy), dim3(256), 0, v.st, F, M, Sh, Nz, parent_family, nf,
                              site0, n_sets, per_set, d_f.get(), pss, pfs, d_stat.get());
       } else if (p <= 16)
-        hipLaunchKernelGGL(sim_factor<16>, dim3((nf + 3) / 4, gy), dim3(kWave), lds, v.st, F, M, Sh, Nz, T.parent_family, nf, site0,
+        hipLaunchKernelGGL(sim_factor<16>, dim3((nf + 3) / 4, gy), dim3(kWave), lds, v.st, F, M, Sh, Nz, parent_family, nf, site0,
                            n_sets, per_set, d_f.get(), f_stride, d_stat.get());
       else
-        hipLaunchKernelGGL(sim_factor<64>, dim3(nf, gy), dim3(kWave), lds, v.st, F, M, Sh, Nz, T.parent_family, nf, site0, n_sets,
+        hipLaunchKernelGGL(sim_factor<64>, dim3(nf, gy), dim3(kWave), lds, v.st, F, M, Sh, Nz, parent_family, nf, site0, n_sets,
                            per_set, d_f.get(), f_stride, d_stat.get());
       hipLaunchKernelGGL(sim_info, dim3(gy), dim3(256), 0, v.st, d_stat.get(), nf, n_sets, d_info.get());
       if (herr == hipSuccess) herr = hipGetLastError();
@@ -397,13 +403,13 @@ static int lg_simulate(pgbp_engine* e, int32_t site_begin, int32_t site_end, con
       const int n_lf = lo[l + 1] - lo[l];
       if (n_lf == 0) continue;
       if (sm)
-        hipLaunchKernelGGL(sim_apply<true>, dim3((n + 255) / 256, std::min(n_lf, 65535)), dim3(256), 0, v.st, F, T.parent_family,
-                           T.level_fam + lo[l], n_lf, site0, n, per_set, d_f.get(), pss, pfs, d_info.get(), d_z.get(), d_x.get(), ss,
-                           fs, write_data, T.data, T.data_sm, sm_row(v.plan->n_sites));
+        hipLaunchKernelGGL(sim_apply<true>, dim3((n + 255) / 256, std::min(n_lf, 65535)), dim3(256), 0, v.st, F, parent_family,
+                           level_fam + lo[l], n_lf, site0, n, per_set, d_f.get(), pss, pfs, d_info.get(), d_z.get(), d_x.get(), ss,
+                           fs, write_data, data, data_sm, sm_row(v.plan->n_sites));
       else
         hipLaunchKernelGGL(sim_apply<false>, dim3((unsigned)(((int64_t)n_lf * p + 255) / 256), std::min(n, 65535)), dim3(256), 0, v.st,
-                           F, T.parent_family, T.level_fam + lo[l], n_lf, site0, n, per_set, d_f.get(), pss, pfs, d_info.get(),
-                           d_z.get(), d_x.get(), ss, fs, write_data, T.data, T.data_sm, sm_row(v.plan->n_sites));
+                           F, parent_family, level_fam + lo[l], n_lf, site0, n, per_set, d_f.get(), pss, pfs, d_info.get(),
+                           d_z.get(), d_x.get(), ss, fs, write_data, data, data_sm, sm_row(v.plan->n_sites));
     }
     if (herr == hipSuccess) herr = hipGetLastError();
     phase(2);

@@ -489,3 +489,112 @@ def test_a_patterns_handle_takes_the_calls(P):
     e = float(np.max(np.abs(ll2 - ll) / np.maximum(1.0, np.abs(ll))))
     print(f"patterns handle: simulated data, loglik of the handle against the engine's {e:.2e}")
     assert not info2.any() and e <= TOL
+
+
+# ----------------------------------------------------------------------------- 9: a set-up replaces the whole model, or nothing
+
+def _six_tips(P, p, n_sites, other=False, topology=True):
+    """loo_ref.batch_case on 6 tips under a fixed root, the second tip's last trait missing at every site (the table carries
+    masks); other: another table on the same graph (other edge lengths and data).  (family table, data, assignfactors_lg_
+    arguments, schedule tree, a constructor of engines on the graph).  One site: the plain layout; 9 univariate sites: the
+    site-minor one, with a ragged row."""
+    nwk, taxa, data, Rs, mus = LR.batch_case(p, n_sites=n_sites, ntips=6)
+    data = data.copy()
+    if other:
+        data = 1.5 * data[::-1] + 0.25
+    data[:, 1, p - 1] = np.nan
+    net, names = P.read_newick(nwk)
+    row = {t: r for r, t in enumerate(taxa)}
+    cn, ed, sn = P.cliquetree(net.node2family)
+    st = P.allocate_scopes(cn, ed, sn, net, p, fixedroot=True)
+    fam = P.lg_families(st.clusters, st.node2cluster, net.node2family, st.node2fixed,
+                        [list(zip(net.length[i], net.gamma[i], net.color[i])) for i in range(net.nnodes)],
+                        [row.get(names[i], -1) for i in range(net.nnodes)], p, data=data[0])
+    assert fam.get("child_mask") is not None and fam.get("parent_family") is not None
+    if other:
+        fam = dict(fam, length=np.asarray(fam["length"]) * 1.75)
+    if not topology:
+        fam = {k: v for k, v in fam.items() if k != "parent_family"}
+    spt = P.spanningtree_clusterlist(len(cn), ed, P.default_rootcluster(cn, net.is_leaf))
+    new = lambda: P.ClusterGraphBelief.from_arrays(st.dims, st.sepset_clusters, st.scope_off, st.scope_idx, None, n_sites=n_sites)
+    kw = dict(R=Rs[:, None], mu=mus) if n_sites > 1 else dict(R=Rs[0][None], mu=mus[0])
+    return fam, data, kw, spt, new
+
+
+def _dressed(P, p, n_sites):
+    """An engine with parameters, two shifts, noise on two tips and a topology."""
+    fam, data, kw, spt, new = _six_tips(P, p, n_sites)
+    cgb = new()
+    cgb.lg_setup(fam, data)
+    cgb.assignfactors_lg_(**kw)
+    real = [f for f in range(len(fam["cluster"])) if fam["n_parents"][f] == 1]
+    cgb.set_shifts_lg([(real[0], 0), (real[-1], 0)], np.array([[0.5] * p, [-0.25] * p]))
+    tips = [f for f in LR.tip_families(fam)]
+    cgb.set_tip_noise_lg(tips[:2], 0.1 * np.eye(p), se2=np.full((2, p), 0.05))
+    cgb.assignfactors_lg_(**kw)
+    assert cgb.shift_count_lg() == 2 and cgb.tip_noise_count_lg() == 2
+    return cgb, spt, kw
+
+
+def _sweep_bytes(cgb, spt):
+    """The bytes of the log-likelihood and of every sweep on a calibration under the engine's current model."""
+    cgb._ensure_schedule([spt])
+    d = dict(loglik=cgb.loglik_lg()[0])
+    if cgb.n_sites >= 8:      # (first: it reads the beliefs in the layout the calibration leaves)
+        ll, g = cgb.loglik_and_gradient_sites_lg(spt)
+        d.update(ll_sites=np.asarray(ll), **{"s_" + k: np.asarray(v) for k, v in g.items()})
+    ll, g = cgb.loglik_and_gradient_lg(spt, all_sites=True)
+    d.update(ll=np.asarray(ll), **{"g_" + k: np.asarray(v) for k, v in g.items()})
+    for tag, out in (("e_", cgb.edge_gradient_lg(all_sites=True)), ("c_", cgb.shift_scan_lg(all_sites=True, information=True)),
+                     ("l_", cgb.loo_lg(all_sites=True)), ("i_", cgb.impute_lg(all_sites=True))):
+        d.update({tag + k: np.asarray(v) for k, v in out.items()})
+    # (the second tip misses its last trait: at p = 1 it has no observed trait left and is no leave-one-out target)
+    assert len(d["l_families"]) == (6 if cgb._lg_p > 1 else 5) and len(d["i_families"]) == 1 and not d["g_info"].any()
+    return {k: v.tobytes() for k, v in d.items()}
+
+
+@pytest.mark.parametrize("p,n_sites", [(2, 1), (1, 9)])
+def test_a_second_setup_is_a_clean_slate(P, p, n_sites):
+    """lg_setup with another table on an engine that has parameters, shifts, tip noise and a topology: none of them is left,
+    and after assignfactors_lg_ the log-likelihood and every sweep return the bytes of a fresh engine set up the same way."""
+    cgb, spt, kw = _dressed(P, p, n_sites)
+    _sweep_bytes(cgb, spt)
+    fam2, data2, kw2, _, new = _six_tips(P, p, n_sites, other=True, topology=False)
+    cgb.lg_setup(fam2, data2)
+    assert cgb.shift_count_lg() == 0 and cgb.tip_noise_count_lg() == 0
+    with pytest.raises(P.PgbpError, match="no topology"):
+        cgb.simulate_lg(seed=1, all_sites=True)
+    for sweep in (cgb.gradient_lg, cgb.edge_gradient_lg, cgb.shift_scan_lg, cgb.loo_lg, cgb.impute_lg):
+        with pytest.raises(P.PgbpError, match="no parameters yet"):
+            sweep(all_sites=True)
+    cgb.assignfactors_lg_(**kw2)
+    got = _sweep_bytes(cgb, spt)
+    fresh = new()
+    fresh.lg_setup(fam2, data2)
+    fresh.assignfactors_lg_(**kw2)
+    want = _sweep_bytes(fresh, spt)
+    assert got.keys() == want.keys()
+    for k in want:
+        assert got[k] == want[k], k
+
+
+@pytest.mark.parametrize("p,n_sites", [(2, 1), (1, 9)])
+def test_a_refused_setup_leaves_the_old_model_whole(P, p, n_sites):
+    """lg_setup with a table whose last family has a non-positive edge length is refused: the counts, a seeded simulation (the
+    topology) and every sweep are what they were before the call."""
+    cgb, spt, kw = _dressed(P, p, n_sites)
+    before = _sweep_bytes(cgb, spt)
+    x0, _ = cgb.simulate_lg(seed=SR.SEED, all_sites=True)
+    fam2, data2, _, _, _ = _six_tips(P, p, n_sites, other=True)
+    bad = np.array(fam2["length"], np.float64)
+    bad[-1] = 0.0
+    mirror = cgb._lg      # (the wrapper's own copy of the table: it is replaced before the engine is asked)
+    with pytest.raises(P.PgbpError, match="parent edge length must be positive"):
+        cgb.lg_setup(dict(fam2, length=bad), data2)
+    cgb._lg = mirror
+    assert cgb.shift_count_lg() == 2 and cgb.tip_noise_count_lg() == 2
+    x1, info = cgb.simulate_lg(seed=SR.SEED, all_sites=True)
+    assert not info.any() and x1.tobytes() == x0.tobytes()
+    after = _sweep_bytes(cgb, spt)
+    for k in before:
+        assert after[k] == before[k], k
