@@ -47,6 +47,20 @@ def main():
           + ("" if exact else "  (loopy graph: approximations)"))
     if exact:
         assert abs(norm - g["ll"]) <= 1e-9 * abs(g["ll"])
+        # an out-of-clique query from the same calibration: the difference between two internal nodes that may share no
+        # cluster, with its standard error (posterior_cov_: w = A'c for the contrast c, Var(c'x | data) = |w|^2)
+        off = np.concatenate([[0], np.cumsum(st.dims[: len(cn)])])
+        where = {}                                               # internal node -> (its first cluster, position there)
+        for ci, sc in enumerate(st.clusters):
+            for pos, v in enumerate(np.array(sc.nodelabel)[sc.inscope[0]]):
+                where.setdefault(int(v), (ci, pos))
+        (ca, pa), (cb, pb) = where[min(where)], where[max(where)]
+        contrast = np.zeros(int(off[-1]))
+        contrast[off[ca] + pa], contrast[off[cb] + pb] = 1.0, -1.0
+        w, _, _ = cgb.posterior_cov_(contrast, want_k=False)
+        mom = cgb.moments_([ca, cb], cov=False)
+        print(f"ancestral states: {names[min(where) - 1]} - {names[max(where) - 1]} = {mom[0][0][pa] - mom[1][0][pb]:.4f} "
+              f"+- {np.linalg.norm(w):.4f} (clusters {ca} and {cb})")
         # leave-one-out cross-validation from the same calibration: how well do the other tips predict each tip?
         loo = cgb.loo_lg()
         z = P.loo_zscores(loo)[:, 0]

@@ -633,6 +633,37 @@ void    pgbp_sample_scratch_limits(int64_t factor_doubles, int64_t draw_doubles)
  * milliseconds of {factor phase, copy of z to the device, apply phase, copy of x to the host}, summed over the chunks. */
 int     pgbp_sample_posterior_timed(pgbp_engine* e, int32_t tree, int32_t site_begin, int32_t site_end, int32_t n_draws,
                                     const double* z, double* x, int32_t* info, double* ms4);
+/* EXACT posterior covariance between any two entries of the sampler's layout, in the same tree: the adjoint of the sweep above.
+ * At one site pgbp_sample_posterior is a linear map x = m + A z, so Cov(x) = A A' and, for a functional c (a weight per entry of
+ * the layout), Cov(x, c'x) = A (A'c) and Var(c'x) = |A'c|^2.  `tree`, the site range, size = pgbp_sample_size, the layout of an
+ * entry and a cluster's split into S and R are the sampler's.
+ *   c [n_cols][size]: the functionals, shared by all sites; a column may put weight on any copy of a variable several clusters hold.
+ *   w [n_cols][sites][size] (may be NULL): w = A'c at that site.  Entries at S positions of non-root clusters are +0.0 (the sampler
+ *     ignores z there); w_a . w_b = Cov(c_a'x, c_b'x | data).
+ *   k [n_cols][sites][size] (may be NULL, not both): k = A w = Cov(x, c'x | data), the covariance of every entry with the functional;
+ *     a variable held by several clusters has the same bits in every copy.
+ * With T = L^-T (upper triangular) and G = J_RR^-1 J_RS of a cluster, PS the positions of S in the parent:
+ *   adjoint, from the deepest level to the root, xbar = c at the start: once all children of C are done
+ *     w_C[R_l] = sum_{i <= l} T_il xbar_C[R_i],     xbar_P[PS_j] += xbar_C[S_j] - sum_i G_ij xbar_C[R_i];
+ *   forward, from the root: k_C[S_j] = k_P[PS_j],   k_C[R_i] = -sum_j G_ij k_C[S_j] + sum_{l >= i} T_il w_C[R_l].
+ * Device (csrc/pgbp_sample.hip): the sampler's FACTOR phase and scratch pool as they are; an ADJOINT phase, one launch per level
+ * from the deepest, in gather form -- a thread owns (cluster of the level, column, variable) and adds the terms of the children
+ * whose sepsets map to its variable, children in index order, then their S positions in order, from a list the host builds once
+ * per call -- and one flat launch for w; a FORWARD phase, one launch per preorder level, the sampler's apply without its offset
+ * and with w for z.  No atomics, every sum in a fixed index order: two calls return the same bytes, and the bytes of a (column,
+ * site) do not depend on the other columns or sites of the call, nor on the chunks (sites by the factor limit, columns by the
+ * draw limit of pgbp_sample_scratch_limits).  Read-only on the beliefs; every layout, as the sampler.  EXACT ONLY FOR BELIEFS
+ * CALIBRATED ON A CLIQUE TREE; the call does not verify that.
+ * info[site - site_begin] (may be NULL): the sampler's value; w and k of a site whose info is not 0 are NaN, other sites are
+ * unaffected.  Fails before any launch as the sampler does, with this function's name in the text: PGBP_ERR_STATE without a
+ * schedule; PGBP_ERR_INVALID for `tree` out of range, a tree that does not span or a graph with a cycle, a cluster of more than 128
+ * variables, n_cols < 1, a bad site range, c NULL, w and k both NULL. */
+int     pgbp_posterior_cov(pgbp_engine* e, int32_t tree, int32_t site_begin, int32_t site_end, int32_t n_cols,
+                           const double* c, double* w, double* k, int32_t* info);
+/* The same call with the stream drained after each phase (measurement only: tools/time_posterior_cov.py): ms5[0 .. 4] = wall
+ * milliseconds of {factor phase, copy of c, adjoint phase with w, forward phase, copies of w and k}, summed over the chunks. */
+int     pgbp_posterior_cov_timed(pgbp_engine* e, int32_t tree, int32_t site_begin, int32_t site_end, int32_t n_cols,
+                                 const double* c, double* w, double* k, int32_t* info, double* ms5);
 
 /* ---- the model run forwards: simulated traits, and tip data without a new set-up ------------------ */
 /* NODE TOPOLOGY of the family table.  pgbp_lg_families names a family's parents by their position in a cluster, which is not

@@ -143,6 +143,8 @@ SYMBOLS = {
     "pgbp_sample_size": (C.c_int64, [_P]),
     "pgbp_sample_scratch_limits": (None, [C.c_int64, C.c_int64]),
     "pgbp_sample_posterior_timed": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _F64P, _F64P, _I32P, _F64P]),
+    "pgbp_posterior_cov": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _F64P, _F64P, _F64P, _I32P]),
+    "pgbp_posterior_cov_timed": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _F64P, _F64P, _F64P, _I32P, _F64P]),
     "pgbp_lg_set_topology": (C.c_int, [_P, _I32P]),
     "pgbp_lg_set_data": (C.c_int, [_P, C.c_int32, C.c_int32, _F64P]),
     "pgbp_lg_get_data": (C.c_int, [_P, C.c_int32, C.c_int32, _F64P]),

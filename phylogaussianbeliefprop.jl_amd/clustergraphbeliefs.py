@@ -504,6 +504,128 @@ class ClusterGraphBelief:
                 at += n
         return out
 
+    def posterior_cov_(self, c, schedule_tree=0, all_sites=False, want_w=True, want_k=True):
+        """Exact posterior covariances of linear functionals of the cluster variables in ONE device call
+        (pgbp_posterior_cov): the adjoint of sample_posterior_'s sweep, x = m + A z at one site.
+        c: [n_cols, size] (or [size]), a weight per entry of sample_posterior_'s layout, shared by the sites.
+        Returns (w, k, info): w [n_cols, n_sites or 1, size] = A'c, so that w_a . w_b = Cov(c_a'x, c_b'x | data), +0.0 at the
+        entries the sampler conditions on; k [n_cols, n_sites or 1, size] = A w = Cov(x, c'x | data), the covariance of every
+        entry with the functional; info as sample_posterior_'s (a site whose info is not 0 is NaN).  want_w / want_k false:
+        that array is None (without k no forward pass is run).  Exact only if the beliefs are calibrated on a clique tree;
+        the call does not verify that."""
+        size = int(self._lib.pgbp_sample_size(self._eng))
+        s0, s1 = (0, self.n_sites) if all_sites else (self.site, self.site + 1)
+        c = np.ascontiguousarray(np.atleast_2d(np.asarray(c, dtype=np.float64)))
+        if c.ndim != 2 or c.shape[1] != size:
+            raise ValueError(f"c has shape {c.shape}, expected (n_cols, {size})")
+        shape = (c.shape[0], s1 - s0, size)
+        w = np.zeros(shape) if want_w else None
+        k = np.zeros(shape) if want_k else None
+        info = np.zeros(s1 - s0, dtype=np.int32)
+        ptr = lambda a: None if a is None else L.f64p(a if a.size else np.zeros(1))
+        _check(self._lib.pgbp_posterior_cov(self._eng, int(schedule_tree), s0, s1, int(c.shape[0]),
+                                            L.f64p(c if c.size else np.zeros(1)), ptr(w), ptr(k), L.i32p(info)), self._eng)
+        return w, k, info
+
+    def _node_entries(self, who):
+        """{node label: (cluster, positions in the cluster [p], entries of sample_posterior_'s layout [p])} from the first
+        cluster that holds the node (node_samples' rule); -1 where the trait is out of scope."""
+        if self._objs is None:
+            raise ValueError(f"{who} needs labelled beliefs (an object built from CanonicalBelief objects)")
+        out, at = {}, 0
+        for ci, b in enumerate(self._objs[: self.nclusters]):
+            insc = np.asarray(b.inscope, dtype=bool)
+            inside = 0
+            for k, lab in enumerate(b.nodelabel):
+                n = int(insc[:, k].sum())
+                if lab not in out:
+                    pos = np.full(insc.shape[0], -1, dtype=np.int64)
+                    pos[insc[:, k]] = inside + np.arange(n)
+                    out[lab] = (ci, pos, np.where(pos >= 0, at - inside + pos, -1))
+                at += n
+                inside += n
+        return out
+
+    def sample_index(self, node, trait):
+        """The entry of sample_posterior_'s layout (a column of x, an index into a row of c) of trait `trait` of the node
+        labelled `node`, in the first cluster that holds the node; -1 when that trait is out of scope there."""
+        ent = self._node_entries("sample_index")
+        if node not in ent:
+            raise ValueError(f"no cluster holds node {node!r}")
+        return int(ent[node][2][int(trait)])
+
+    def _node_means(self, ent, nodes):
+        """posterior means [len(nodes), p] from moments_ (NaN out of scope)"""
+        clusters = sorted({ent[v][0] for v in nodes})
+        mom = dict(zip(clusters, self.moments_(clusters, cov=False)))
+        out = np.full((len(nodes), len(ent[nodes[0]][1]) if nodes else 0), np.nan)
+        for i, v in enumerate(nodes):
+            ci, pos, _ = ent[v]
+            out[i, pos >= 0] = mom[ci][0][pos[pos >= 0]]
+        return out
+
+    def node_cov(self, nodes_a, nodes_b=None, schedule_tree=0):
+        """Posterior covariance blocks between nodes that need not share a cluster: [len(a), len(b), p, p], entry
+        [i, j, s, t] = Cov(trait s of a_i, trait t of b_j | data) at the current site; nodes_b=None: nodes_a among
+        themselves.  One column of posterior_cov_ per in-scope (node of b, trait); traits out of scope are NaN."""
+        ent = self._node_entries("node_cov")
+        nodes_a = list(nodes_a)
+        nodes_b = nodes_a if nodes_b is None else list(nodes_b)
+        for v in nodes_a + nodes_b:
+            if v not in ent:
+                raise ValueError(f"no cluster holds node {v!r}")
+        size = int(self._lib.pgbp_sample_size(self._eng))
+        cols = [(j, t, int(e)) for j, v in enumerate(nodes_b) for t, e in enumerate(ent[v][2]) if e >= 0]
+        p = len(next(iter(ent.values()))[1]) if ent else 0
+        out = np.full((len(nodes_a), len(nodes_b), p, p), np.nan)
+        if not cols or not nodes_a:
+            return out
+        c = np.zeros((len(cols), size))
+        c[np.arange(len(cols)), [e for _, _, e in cols]] = 1.0
+        _, k, info = self.posterior_cov_(c, schedule_tree, want_w=False)
+        if info[0] != 0:
+            raise np.linalg.LinAlgError(f"PosDefException: the conditional precision of cluster {info[0]} is not positive definite.")
+        for i, v in enumerate(nodes_a):
+            ea = ent[v][2]
+            for q, (j, t, _) in enumerate(cols):
+                out[i, j, ea >= 0, t] = k[q, 0, ea[ea >= 0]]
+        return out
+
+    def nodes_joint_posterior(self, nodes, schedule_tree=0):
+        """The joint posterior of several nodes, wherever they sit in the clique tree (an out-of-clique query):
+        (mean [n, p], cov [n p, n p]), node-major; the mean from moments_, the covariance from node_cov."""
+        nodes = list(nodes)
+        cov = self.node_cov(nodes, None, schedule_tree)
+        n, p = cov.shape[0], cov.shape[2]
+        return self._node_means(self._node_entries("nodes_joint_posterior"), nodes), cov.transpose(0, 2, 1, 3).reshape(n * p, n * p)
+
+    def functional_moments(self, weights, schedule_tree=0):
+        """Posterior mean [q] and covariance [q, q] of the q linear functionals sum_v W_v x_v; weights: {node label: W_v [q, p]}.
+        The covariance is w w' of posterior_cov_ (no forward pass).  A non-zero weight on a trait out of scope is refused."""
+        ent = self._node_entries("functional_moments")
+        nodes = list(weights)
+        size = int(self._lib.pgbp_sample_size(self._eng))
+        W = [np.atleast_2d(np.asarray(weights[v], dtype=np.float64)) for v in nodes]
+        q = W[0].shape[0] if W else 0
+        c = np.zeros((q, size))
+        for v, Wv in zip(nodes, W):
+            if v not in ent:
+                raise ValueError(f"no cluster holds node {v!r}")
+            e = ent[v][2]
+            if Wv.shape != (q, len(e)):
+                raise ValueError(f"the weights of node {v!r} have shape {Wv.shape}, expected {(q, len(e))}")
+            if np.any(Wv[:, e < 0] != 0.0):
+                raise ValueError(f"node {v!r}: weight on a trait that is out of scope")
+            c[:, e[e >= 0]] += Wv[:, e >= 0]
+        if q == 0:
+            return np.zeros(0), np.zeros((0, 0))
+        w, _, info = self.posterior_cov_(c, schedule_tree, want_k=False)
+        if info[0] != 0:
+            raise np.linalg.LinAlgError(f"PosDefException: the conditional precision of cluster {info[0]} is not positive definite.")
+        mu = np.nan_to_num(self._node_means(ent, nodes))
+        mean = sum((Wv @ m for Wv, m in zip(W, mu)), np.zeros(q))
+        return mean, w[:, 0] @ w[:, 0].T
+
     def default_sepset1(self):
         """default_sepset1 (src/clustergraphbeliefs.jl:197-202)."""
         for j in range(self.nclusters, self.nbeliefs):

@@ -14,6 +14,10 @@
 //          x_R[i] = a_i - sum_j G_ij x_S[j] + sum_{l >= i} T_il z_R[l], every sum in index order by one thread (no atomics),
 //          and the copy of x_S.  The factor is computed once however many draws are asked for.
 // The factors of a chunk of sites at a time (256 MB at most), z up and x down as one (strided) copy each per chunk.
+//
+// The same factors give the exact posterior covariance of any two entries (pgbp_posterior_cov): at one site the sweep is linear,
+// x = m + A z, and the adjoint sweep w = A'c runs the levels from the deepest to the root (cov_adjoint, cov_w), k = A w the apply
+// without its offset (cov_forward).  Both entry points share the host-side plan (sample_plan) and the factor phase (SampDev).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -156,6 +160,121 @@ __global__ __launch_bounds__(256) void sample_apply(const SampItem* __restrict__
   }
 }
 
+// ---- pgbp_posterior_cov: the adjoint of the sweep above.  At one site the sampler is x = m + A z; for a functional c the call
+// returns w = A'c (cov_adjoint level by level from the deepest, then cov_w) and k = A w (cov_forward, sample_apply without the
+// offset).  c: [n_cols][size], shared by the sites; xb, w: [n_cols][n_sites][size] of this chunk, k is written over xb.
+
+// one level of the adjoint, in gather form: thread = (cluster P of the level, column, variable v < mpad) forms
+//   xbar_P[v] = c_P[v] + sum over P's children in index order, then over their S positions j that map to v, of
+//               (xbar_C[S_j] - sum_i G_ij xbar_C[R_i]),
+// every child's xbar being final (the level below ran before).  start[e] .. start[e + 1]: the (child among `items`, j) pairs of
+// entry e of the layout in `pairs`.  `items`: all of them by level, P = first + ...
+__global__ __launch_bounds__(256) void cov_adjoint(const SampItem* __restrict__ items, int first, int n_items, int mpad, int n_cols,
+                                                   int n_sites, const int32_t* __restrict__ idx, const int32_t* __restrict__ start,
+                                                   const int32_t* __restrict__ pairs, const double* __restrict__ fpool, int64_t f_stride,
+                                                   const int32_t* __restrict__ info, const double* __restrict__ c,
+                                                   double* __restrict__ xb, int64_t size) {
+#pragma clang fp contract(off)
+  const int64_t gid = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (gid >= (int64_t)n_items * n_cols * mpad) return;
+  const int vv = (int)(gid % mpad);
+  const int64_t q = gid / mpad;
+  const int col = (int)(q % n_cols);
+  const int P = first + (int)(q / n_cols);
+  const SampItem item = items[P];
+  if (vv >= item.m) return;
+  const int e0 = start[item.x_off + vv], e1 = start[item.x_off + vv + 1];
+  const double cv = c[(int64_t)col * size + item.x_off + vv];
+  for (int site = blockIdx.y; site < n_sites; site += gridDim.y) {
+    if (info[site] != 0) continue;   // (cov_w and cov_forward write the NaN; no factor of the site is read)
+    const int64_t base = ((int64_t)col * n_sites + site) * size;
+    double acc = cv;
+    for (int e = e0; e < e1; ++e) {
+      const SampItem ch = items[pairs[2 * e]];
+      const int j = pairs[2 * e + 1], r = ch.r;
+      const int32_t* __restrict__ cperm = idx + ch.perm;
+      const double* __restrict__ xc = xb + base + ch.x_off;
+      const double* __restrict__ Gj = fpool + (int64_t)site * f_stride + ch.f_off + (int64_t)r * r + (int64_t)j * r;
+      double t = xc[cperm[r + j]];
+      for (int i = 0; i < r; ++i) t = fma(-Gj[i], xc[cperm[i]], t);
+      acc += t;
+    }
+    xb[base + item.x_off + vv] = acc;
+  }
+}
+
+// w_C[R_l] = sum_{i <= l} T_il xbar_C[R_i], +0.0 at the S positions: one flat launch over (cluster, column, variable l < mpad)
+__global__ __launch_bounds__(256) void cov_w(const SampItem* __restrict__ items, int n_items, int mpad, int n_cols, int n_sites,
+                                             const int32_t* __restrict__ idx, const double* __restrict__ fpool, int64_t f_stride,
+                                             const int32_t* __restrict__ info, const double* __restrict__ xb,
+                                             double* __restrict__ w, int64_t size) {
+#pragma clang fp contract(off)
+  const int64_t gid = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (gid >= (int64_t)n_items * n_cols * mpad) return;
+  const int l = (int)(gid % mpad);
+  const int64_t q = gid / mpad;
+  const int col = (int)(q % n_cols);
+  const SampItem item = items[q / n_cols];
+  const int m = item.m, r = item.r;
+  if (l >= m) return;
+  const int32_t* __restrict__ perm = idx + item.perm;
+  const int pos = perm[l];
+  for (int site = blockIdx.y; site < n_sites; site += gridDim.y) {
+    const int64_t base = ((int64_t)col * n_sites + site) * size + item.x_off;
+    if (info[site] != 0) {
+      w[base + pos] = NAN;
+      continue;
+    }
+    double acc = 0.0;
+    if (l < r) {
+      const double* __restrict__ Tl = fpool + (int64_t)site * f_stride + item.f_off + (int64_t)l * r;
+      for (int i = 0; i <= l; ++i) acc = fma(Tl[i], xb[base + perm[i]], acc);
+    }
+    w[base + pos] = acc;
+  }
+}
+
+// one preorder level of k = A w: sample_apply with w for z and without the offset a
+__global__ __launch_bounds__(256) void cov_forward(const SampItem* __restrict__ items, int n_items, int mpad, int n_cols,
+                                                   int n_sites, const int32_t* __restrict__ idx,
+                                                   const double* __restrict__ fpool, int64_t f_stride,
+                                                   const int32_t* __restrict__ info, const double* __restrict__ w,
+                                                   double* __restrict__ k, int64_t size) {
+#pragma clang fp contract(off)
+  const int64_t gid = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (gid >= (int64_t)n_items * n_cols * mpad) return;
+  const int i = (int)(gid % mpad);
+  const int64_t q = gid / mpad;
+  const int col = (int)(q % n_cols);
+  const SampItem item = items[q / n_cols];
+  const int m = item.m, r = item.r, s = m - r;
+  if (i >= m) return;
+  const int32_t* __restrict__ perm = idx + item.perm;
+  const int32_t* __restrict__ ppos = perm + m;
+  const int pos = perm[i];
+  for (int site = blockIdx.y; site < n_sites; site += gridDim.y) {
+    const int64_t base = ((int64_t)col * n_sites + site) * size;
+    double* __restrict__ ko = k + base + item.x_off;
+    if (info[site] != 0) {
+      ko[pos] = NAN;
+      continue;
+    }
+    const double* __restrict__ kp = k + base + item.px_off;
+    if (i >= r) {
+      ko[pos] = kp[ppos[i - r]];
+      continue;
+    }
+    const double* __restrict__ F = fpool + (int64_t)site * f_stride + item.f_off;
+    const double* __restrict__ Gt = F + r * r;
+    double acc = 0.0;
+    for (int j = 0; j < s; ++j) acc = fma(-Gt[j * r + i], kp[ppos[j]], acc);
+    const double* __restrict__ wi = w + base + item.x_off;
+    double nz = 0.0;
+    for (int l = i; l < r; ++l) nz = fma(F[l * r + i], wi[perm[l]], nz);
+    ko[pos] = acc + nz;
+  }
+}
+
 // bounds of the call's scratch, in doubles: the factors of a chunk of sites, z (and x) of a chunk of draws (pgbp_sample_scratch_limits)
 static std::atomic<int64_t> g_factor_limit{(int64_t)32 << 20}, g_draw_limit{(int64_t)128 << 20};
 
@@ -173,17 +292,26 @@ extern "C" int64_t pgbp_sample_size(pgbp_engine* e) {
   return n;
 }
 
-// ms (pgbp_sample_posterior_timed): the stream is drained after every phase and the wall time of the phase is added to
-// ms[0 .. 3] = {factor, copy of z, apply, copy of x}
-static int sample_posterior(pgbp_engine* e, int32_t tree, int32_t site_begin, int32_t site_end, int32_t n_draws,
-                            const double* z, double* x, int32_t* info, double* ms) {
-  if (!e) return PGBP_ERR_INVALID;
-  const std::string fn = "pgbp_sample_posterior: ";
+// The host-side plan of a sweep over schedule tree `tree`, shared by pgbp_sample_posterior and pgbp_posterior_cov: the refusals
+// (in the order of the header; `count` is n_draws or n_cols, `buffers` returns the text of a refusal of the call's own pointers
+// or an empty string), every cluster's item, the items by dimension class (the factor phase) and by preorder level (the sweeps).
+struct SampPlan {
   std::vector<SampItem> by_class, by_level;
   std::vector<int32_t> idx, order, level_off, level_mpad;
   int n_class[3] = {0, 0, 0}, max_m[3] = {0, 0, 0};
   int64_t size = 0, f_stride = 0;
   int nc = 0;
+};
+
+template <class Buffers>
+static int sample_plan(pgbp_engine* e, const std::string& fn, int32_t tree, int32_t site_begin, int32_t site_end, int32_t count,
+                       const char* count_name, const char* count_unit, Buffers buffers, SampPlan& sp) {
+  std::vector<SampItem>&by_class = sp.by_class, &by_level = sp.by_level;
+  std::vector<int32_t>&idx = sp.idx, &order = sp.order, &level_off = sp.level_off, &level_mpad = sp.level_mpad;
+  int* n_class = sp.n_class;
+  int* max_m = sp.max_m;
+  int64_t &size = sp.size, &f_stride = sp.f_stride;
+  int& nc = sp.nc;
   {
     const Plan& p = *engine_peek(e).plan;
     nc = p.n_clusters;
@@ -217,12 +345,13 @@ static int sample_posterior(pgbp_engine* e, int32_t tree, int32_t site_begin, in
         return engine_fail(e, PGBP_ERR_INVALID, fn + "belief " + std::to_string(c) + " has " + std::to_string(p.dims[c]) +
                                                     " variables, more than the " + std::to_string(kLdsMaxDim) +
                                                     " the moments kernels take");
-    if (n_draws < 1) return engine_fail(e, PGBP_ERR_INVALID, fn + "n_draws = " + std::to_string(n_draws) + ", at least one draw is needed");
+    if (count < 1)
+      return engine_fail(e, PGBP_ERR_INVALID, fn + count_name + " = " + std::to_string(count) + ", at least one " + count_unit + " is needed");
     if (site_begin < 0 || site_end < site_begin || site_end > p.n_sites)
       return engine_fail(e, PGBP_ERR_INVALID, fn + "site range [" + std::to_string(site_begin) + ", " + std::to_string(site_end) +
                                                   ") outside the engine's " + std::to_string(p.n_sites) + " sites");
-    if (!z) return engine_fail(e, PGBP_ERR_INVALID, fn + "no input buffer z");
-    if (!x) return engine_fail(e, PGBP_ERR_INVALID, fn + "no output buffer x");
+    const std::string refused = buffers();
+    if (!refused.empty()) return engine_fail(e, PGBP_ERR_INVALID, fn + refused);
     // items: where every cluster's variables sit in x, its split into R and S, its factor
     std::vector<int64_t> x_off(nc + 1, 0);
     for (int c = 0; c < nc; ++c) x_off[c + 1] = x_off[c] + p.dims[c];
@@ -277,6 +406,84 @@ static int sample_posterior(pgbp_engine* e, int32_t tree, int32_t site_begin, in
       level_mpad.push_back(mp);
     }
   }
+  return PGBP_OK;
+}
+
+// the sites whose factors are held at a time
+static int sample_site_chunk(const SampPlan& sp, int ns) {
+  return (int)std::max<int64_t>(1, std::min<int64_t>(ns, g_factor_limit.load() / std::max<int64_t>(1, sp.f_stride)));
+}
+
+// What both sweeps keep on the device, and the factor phase of a chunk of sites.
+struct SampDev {
+  DevBuf<SampItem> items;   // by class, then by level
+  DevBuf<int32_t> idx, order, stat, info;
+  DevBuf<double> f;
+  size_t n_items = 0, b1 = 0, b2 = 0;
+
+  const SampItem* by_level() const { return items.get() + n_items; }
+
+  hipError_t upload(const EngineView& v, SampPlan& sp, int chunk, int ns) {
+    n_items = sp.by_class.size();
+    const int nc = sp.nc;
+    if (sp.idx.empty()) sp.idx.push_back(0);
+    hipError_t herr = (hipError_t)items.alloc(2 * n_items);
+    if (herr == hipSuccess) herr = (hipError_t)idx.alloc(sp.idx.size());
+    if (herr == hipSuccess) herr = (hipError_t)order.alloc(nc);
+    if (herr == hipSuccess) herr = (hipError_t)stat.alloc((size_t)chunk * nc);
+    if (herr == hipSuccess) herr = (hipError_t)info.alloc((size_t)ns);
+    if (herr == hipSuccess) herr = (hipError_t)f.alloc((size_t)std::max<int64_t>(1, sp.f_stride) * chunk);
+    if (herr == hipSuccess) herr = hipMemcpyAsync(items.get(), sp.by_class.data(), sizeof(SampItem) * n_items, hipMemcpyHostToDevice, v.st);
+    if (herr == hipSuccess) herr = hipMemcpyAsync(items.get() + n_items, sp.by_level.data(), sizeof(SampItem) * n_items, hipMemcpyHostToDevice, v.st);
+    if (herr == hipSuccess) herr = hipMemcpyAsync(idx.get(), sp.idx.data(), sizeof(int32_t) * sp.idx.size(), hipMemcpyHostToDevice, v.st);
+    if (herr == hipSuccess) herr = hipMemcpyAsync(order.get(), sp.order.data(), sizeof(int32_t) * nc, hipMemcpyHostToDevice, v.st);
+    if (herr == hipSuccess) herr = hipMemsetAsync(stat.get(), 0, sizeof(int32_t) * (size_t)chunk * nc, v.st);   // (clusters without variables)
+    return herr;
+  }
+
+  hipError_t prepare(const SampPlan& sp) {
+    b1 = sample_lds_bytes(sp.max_m[1]);
+    b2 = sample_lds_bytes(sp.max_m[2]);
+    if (b2 > 64 * 1024)
+      return hipFuncSetAttribute(reinterpret_cast<const void*>(sample_factor<256, 256>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)b2);
+    return hipSuccess;
+  }
+
+  // the factors and info of the n sites from site_begin + s0 (info at s0 of the call's)
+  void factor(const EngineView& v, const SampPlan& sp, int site_begin, int s0, int n) {
+    const Plan& p = *v.plan;
+    const int gy = std::min(n, 65535), nc = sp.nc;
+    const int* n_class = sp.n_class;
+    const int64_t f_stride = sp.f_stride;
+    const SampItem* it = items.get();
+    if (n_class[0] > 0)
+      hipLaunchKernelGGL((sample_factor<64, 16>), dim3((n_class[0] + 3) / 4, gy), dim3(64), sizeof(double) * 4 * kSampSmallRegion,
+                         v.st, v.pool, p.pool_stride(), v.bs16, p.fast_p, it, n_class[0], idx.get(), kSampSmallRegion,
+                         site_begin + s0, n, f.get(), f_stride, stat.get(), nc);
+    it += n_class[0];
+    if (n_class[1] > 0)
+      hipLaunchKernelGGL((sample_factor<64, 64>), dim3(n_class[1], gy), dim3(64), b1, v.st, v.pool, p.pool_stride(), v.bs16,
+                         p.fast_p, it, n_class[1], idx.get(), 0, site_begin + s0, n, f.get(), f_stride, stat.get(), nc);
+    it += n_class[1];
+    if (n_class[2] > 0)
+      hipLaunchKernelGGL((sample_factor<256, 256>), dim3(n_class[2], gy), dim3(256), b2, v.st, v.pool, p.pool_stride(), v.bs16,
+                         p.fast_p, it, n_class[2], idx.get(), 0, site_begin + s0, n, f.get(), f_stride, stat.get(), nc);
+    hipLaunchKernelGGL(sample_info, dim3(gy), dim3(256), 0, v.st, stat.get(), order.get(), nc, n, info.get() + s0);
+  }
+};
+
+// ms (pgbp_sample_posterior_timed): the stream is drained after every phase and the wall time of the phase is added to
+// ms[0 .. 3] = {factor, copy of z, apply, copy of x}
+static int sample_posterior(pgbp_engine* e, int32_t tree, int32_t site_begin, int32_t site_end, int32_t n_draws,
+                            const double* z, double* x, int32_t* info, double* ms) {
+  if (!e) return PGBP_ERR_INVALID;
+  const std::string fn = "pgbp_sample_posterior: ";
+  SampPlan sp;
+  const int prc = sample_plan(e, fn, tree, site_begin, site_end, n_draws, "n_draws", "draw",
+                              [&]() { return std::string(!z ? "no input buffer z" : (!x ? "no output buffer x" : "")); }, sp);
+  if (prc) return prc;
+  const std::vector<int32_t>&level_off = sp.level_off, &level_mpad = sp.level_mpad;
+  const int64_t size = sp.size, f_stride = sp.f_stride;
   const int ns = site_end - site_begin;
   if (ns == 0) return PGBP_OK;
   if (size == 0) {
@@ -286,28 +493,14 @@ static int sample_posterior(pgbp_engine* e, int32_t tree, int32_t site_begin, in
   EngineView v;
   int rc = engine_view(e, &v);
   if (rc) return rc;
-  const Plan& p = *v.plan;
   // the factors of a chunk of sites at a time (256 MB at most); z and x of a chunk of draws (1 GB each at most)
-  const int chunk = (int)std::max<int64_t>(1, std::min<int64_t>(ns, g_factor_limit.load() / std::max<int64_t>(1, f_stride)));
+  const int chunk = sample_site_chunk(sp, ns);
   const int dchunk = (int)std::max<int64_t>(1, std::min<int64_t>(n_draws, g_draw_limit.load() / ((int64_t)chunk * size)));
-  const size_t n_items = by_class.size();
-  DevBuf<SampItem> d_items;   // by class, then by level
-  DevBuf<int32_t> d_idx, d_order, d_stat, d_info;
-  DevBuf<double> d_f, d_z, d_x;
-  if (idx.empty()) idx.push_back(0);
-  hipError_t herr = (hipError_t)d_items.alloc(2 * n_items);
-  if (herr == hipSuccess) herr = (hipError_t)d_idx.alloc(idx.size());
-  if (herr == hipSuccess) herr = (hipError_t)d_order.alloc(nc);
-  if (herr == hipSuccess) herr = (hipError_t)d_stat.alloc((size_t)chunk * nc);
-  if (herr == hipSuccess) herr = (hipError_t)d_info.alloc((size_t)ns);
-  if (herr == hipSuccess) herr = (hipError_t)d_f.alloc((size_t)std::max<int64_t>(1, f_stride) * chunk);
+  SampDev d;
+  DevBuf<double> d_z, d_x;
+  hipError_t herr = d.upload(v, sp, chunk, ns);
   if (herr == hipSuccess) herr = (hipError_t)d_z.alloc((size_t)dchunk * chunk * size);
   if (herr == hipSuccess) herr = (hipError_t)d_x.alloc((size_t)dchunk * chunk * size);
-  if (herr == hipSuccess) herr = hipMemcpyAsync(d_items.get(), by_class.data(), sizeof(SampItem) * n_items, hipMemcpyHostToDevice, v.st);
-  if (herr == hipSuccess) herr = hipMemcpyAsync(d_items.get() + n_items, by_level.data(), sizeof(SampItem) * n_items, hipMemcpyHostToDevice, v.st);
-  if (herr == hipSuccess) herr = hipMemcpyAsync(d_idx.get(), idx.data(), sizeof(int32_t) * idx.size(), hipMemcpyHostToDevice, v.st);
-  if (herr == hipSuccess) herr = hipMemcpyAsync(d_order.get(), order.data(), sizeof(int32_t) * nc, hipMemcpyHostToDevice, v.st);
-  if (herr == hipSuccess) herr = hipMemsetAsync(d_stat.get(), 0, sizeof(int32_t) * (size_t)chunk * nc, v.st);   // (clusters without variables)
   auto t_last = std::chrono::steady_clock::now();
   auto phase = [&](int k) {   // timed variant only
     if (!ms) return;
@@ -321,26 +514,11 @@ static int sample_posterior(pgbp_engine* e, int32_t tree, int32_t site_begin, in
   if (herr == hipSuccess) {
     (void)hipGetLastError();   // (an error an earlier asynchronous call left behind is that call's to report)
     phase(-1);
-    const size_t b1 = sample_lds_bytes(max_m[1]), b2 = sample_lds_bytes(max_m[2]);
-    if (b2 > 64 * 1024)
-      herr = hipFuncSetAttribute(reinterpret_cast<const void*>(sample_factor<256, 256>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)b2);
+    herr = d.prepare(sp);
     const size_t row = sizeof(double) * size;
     for (int s0 = 0; herr == hipSuccess && s0 < ns; s0 += chunk) {
       const int n = std::min(chunk, ns - s0), gy = std::min(n, 65535);
-      const SampItem* it = d_items.get();
-      if (n_class[0] > 0)
-        hipLaunchKernelGGL((sample_factor<64, 16>), dim3((n_class[0] + 3) / 4, gy), dim3(64), sizeof(double) * 4 * kSampSmallRegion,
-                           v.st, v.pool, p.pool_stride(), v.bs16, p.fast_p, it, n_class[0], d_idx.get(), kSampSmallRegion,
-                           site_begin + s0, n, d_f.get(), f_stride, d_stat.get(), nc);
-      it += n_class[0];
-      if (n_class[1] > 0)
-        hipLaunchKernelGGL((sample_factor<64, 64>), dim3(n_class[1], gy), dim3(64), b1, v.st, v.pool, p.pool_stride(), v.bs16,
-                           p.fast_p, it, n_class[1], d_idx.get(), 0, site_begin + s0, n, d_f.get(), f_stride, d_stat.get(), nc);
-      it += n_class[1];
-      if (n_class[2] > 0)
-        hipLaunchKernelGGL((sample_factor<256, 256>), dim3(n_class[2], gy), dim3(256), b2, v.st, v.pool, p.pool_stride(), v.bs16,
-                           p.fast_p, it, n_class[2], d_idx.get(), 0, site_begin + s0, n, d_f.get(), f_stride, d_stat.get(), nc);
-      hipLaunchKernelGGL(sample_info, dim3(gy), dim3(256), 0, v.st, d_stat.get(), d_order.get(), nc, n, d_info.get() + s0);
+      d.factor(v, sp, site_begin, s0, n);
       phase(0);
       for (int d0 = 0; herr == hipSuccess && d0 < n_draws; d0 += dchunk) {
         const int nd = std::min(dchunk, n_draws - d0);
@@ -354,7 +532,7 @@ static int sample_posterior(pgbp_engine* e, int32_t tree, int32_t site_begin, in
           const int ni = level_off[l + 1] - level_off[l], mp = level_mpad[l];
           const int64_t threads = (int64_t)ni * nd * mp;
           hipLaunchKernelGGL(sample_apply, dim3((unsigned)((threads + 255) / 256), gy), dim3(256), 0, v.st,
-                             d_items.get() + n_items + level_off[l], ni, mp, nd, n, d_idx.get(), d_f.get(), f_stride, d_info.get() + s0, d_z.get(), d_x.get(), size);
+                             d.by_level() + level_off[l], ni, mp, nd, n, d.idx.get(), d.f.get(), f_stride, d.info.get() + s0, d_z.get(), d_x.get(), size);
         }
         if (herr == hipSuccess) herr = hipGetLastError();
         phase(2);
@@ -366,7 +544,7 @@ static int sample_posterior(pgbp_engine* e, int32_t tree, int32_t site_begin, in
       }
     }
   }
-  if (herr == hipSuccess && info) herr = hipMemcpyAsync(info, d_info.get(), sizeof(int32_t) * (size_t)ns, hipMemcpyDeviceToHost, v.st);
+  if (herr == hipSuccess && info) herr = hipMemcpyAsync(info, d.info.get(), sizeof(int32_t) * (size_t)ns, hipMemcpyDeviceToHost, v.st);
   const hipError_t serr = hipStreamSynchronize(v.st);   // (also when something failed: the uploads read this call's locals)
   if (herr == hipSuccess) herr = serr;
   if (herr != hipSuccess) return engine_fail(e, PGBP_ERR_HIP, fn + hipGetErrorString(herr));
@@ -382,6 +560,145 @@ extern "C" int pgbp_sample_posterior_timed(pgbp_engine* e, int32_t tree, int32_t
                                            const double* z, double* x, int32_t* info, double* ms4) {
   if (e && !ms4) return engine_fail(e, PGBP_ERR_INVALID, "pgbp_sample_posterior_timed: no buffer for the phase times");
   return sample_posterior(e, tree, site_begin, site_end, n_draws, z, x, info, ms4);
+}
+
+// ms (pgbp_posterior_cov_timed): as sample_posterior's, ms[0 .. 4] = {factor, copy of c, adjoint (with w), forward, copies of w and k}
+static int posterior_cov(pgbp_engine* e, int32_t tree, int32_t site_begin, int32_t site_end, int32_t n_cols, const double* c,
+                         double* w, double* k, int32_t* info, double* ms) {
+  if (!e) return PGBP_ERR_INVALID;
+  const std::string fn = "pgbp_posterior_cov: ";
+  SampPlan sp;
+  const int prc = sample_plan(e, fn, tree, site_begin, site_end, n_cols, "n_cols", "column",
+                              [&]() { return std::string(!c ? "no input buffer c" : (!w && !k ? "no output buffer: w and k are both NULL" : "")); }, sp);
+  if (prc) return prc;
+  const std::vector<int32_t>&level_off = sp.level_off, &level_mpad = sp.level_mpad;
+  const int64_t size = sp.size, f_stride = sp.f_stride;
+  const int ns = site_end - site_begin;
+  if (ns == 0) return PGBP_OK;
+  if (size == 0) {
+    if (info) std::fill(info, info + ns, 0);
+    return PGBP_OK;
+  }
+  // the gather lists of the adjoint, behind the index pool: one offset per entry of the layout (and the end), then the
+  // (child among the items by level, j) pairs, sorted by the parent's entry -- a counting sort, so the pairs of one entry keep
+  // the order they are met in: the children in index order, a child's S positions in order
+  const int n_items = (int)sp.by_level.size();
+  const size_t start0 = sp.idx.size();
+  int mpad_all = 0;
+  {
+    std::vector<int32_t> at(sp.nc, -1);
+    size_t n_pairs = 0;
+    for (int q = 0; q < n_items; ++q) {
+      const SampItem& it = sp.by_level[q];
+      at[it.cluster] = q;
+      mpad_all = std::max(mpad_all, (int)it.m);
+      n_pairs += (size_t)(it.m - it.r);
+    }
+    sp.idx.resize(start0 + (size_t)size + 1 + 2 * n_pairs, 0);
+    int32_t* start = sp.idx.data() + start0;
+    int32_t* pairs = start + size + 1;
+    auto each_pair = [&](auto&& f) {
+      for (int ch = 0; ch < sp.nc; ++ch) {
+        if (at[ch] < 0) continue;
+        const SampItem& it = sp.by_level[at[ch]];   // (the root has no S)
+        for (int j = 0; j < it.m - it.r; ++j) f(it.px_off + sp.idx[it.perm + it.m + j], at[ch], j);
+      }
+    };
+    each_pair([&](int64_t entry, int, int) { ++start[entry + 1]; });
+    for (int64_t q = 0; q < size; ++q) start[q + 1] += start[q];
+    each_pair([&](int64_t entry, int child, int j) {   // (start[entry] walks to the end of its list ...)
+      const size_t o = 2 * (size_t)start[entry]++;
+      pairs[o] = child;
+      pairs[o + 1] = j;
+    });
+    for (int64_t q = size; q > 0; --q) start[q] = start[q - 1];   // (... which is where the next one begins)
+    start[0] = 0;
+  }
+  EngineView v;
+  int rc = engine_view(e, &v);
+  if (rc) return rc;
+  // the factors of a chunk of sites at a time; xbar (then k) and w of a chunk of columns, by the sampler's draw limit
+  const int chunk = sample_site_chunk(sp, ns);
+  const int cchunk = (int)std::max<int64_t>(1, std::min<int64_t>(n_cols, g_draw_limit.load() / ((int64_t)chunk * size)));
+  SampDev d;
+  DevBuf<double> d_c, d_w, d_k;
+  hipError_t herr = d.upload(v, sp, chunk, ns);
+  if (herr == hipSuccess) herr = (hipError_t)d_c.alloc((size_t)cchunk * size);
+  if (herr == hipSuccess) herr = (hipError_t)d_w.alloc((size_t)cchunk * chunk * size);
+  if (herr == hipSuccess) herr = (hipError_t)d_k.alloc((size_t)cchunk * chunk * size);
+  auto t_last = std::chrono::steady_clock::now();
+  auto phase = [&](int q) {   // timed variant only
+    if (!ms) return;
+    const hipError_t perr = hipStreamSynchronize(v.st);
+    if (herr == hipSuccess) herr = perr;
+    const auto now = std::chrono::steady_clock::now();
+    if (q >= 0) ms[q] += std::chrono::duration<double, std::milli>(now - t_last).count();
+    t_last = now;
+  };
+  if (ms) std::fill(ms, ms + 5, 0.0);
+  if (herr == hipSuccess) {
+    (void)hipGetLastError();   // (an error an earlier asynchronous call left behind is that call's to report)
+    phase(-1);
+    herr = d.prepare(sp);
+    const size_t row = sizeof(double) * size;
+    const int32_t* start = d.idx.get() + start0;
+    const int32_t* pairs = start + size + 1;
+    const int n_levels = (int)level_off.size() - 1;
+    auto down = [&](double* host, const double* dev, int s0, int n, int c0, int ncol) {   // [ncol][n][size] -> [n_cols][ns][size]
+      if (n == ns) return hipMemcpyAsync(host + (size_t)c0 * ns * size, dev, row * n * ncol, hipMemcpyDeviceToHost, v.st);
+      return hipMemcpy2DAsync(host + ((size_t)c0 * ns + s0) * size, row * ns, dev, row * n, row * n, ncol, hipMemcpyDeviceToHost, v.st);
+    };
+    for (int s0 = 0; herr == hipSuccess && s0 < ns; s0 += chunk) {
+      const int n = std::min(chunk, ns - s0), gy = std::min(n, 65535);
+      d.factor(v, sp, site_begin, s0, n);
+      phase(0);
+      for (int c0 = 0; herr == hipSuccess && c0 < n_cols; c0 += cchunk) {
+        const int ncol = std::min(cchunk, n_cols - c0);
+        herr = hipMemcpyAsync(d_c.get(), c + (size_t)c0 * size, row * ncol, hipMemcpyHostToDevice, v.st);
+        phase(1);
+        for (int l = n_levels - 1; herr == hipSuccess && l >= 0; --l) {
+          const int ni = level_off[l + 1] - level_off[l], mp = level_mpad[l];
+          const int64_t threads = (int64_t)ni * ncol * mp;
+          hipLaunchKernelGGL(cov_adjoint, dim3((unsigned)((threads + 255) / 256), gy), dim3(256), 0, v.st, d.by_level(), level_off[l],
+                             ni, mp, ncol, n, d.idx.get(), start, pairs, d.f.get(), f_stride, d.info.get() + s0, d_c.get(), d_k.get(), size);
+        }
+        if (herr == hipSuccess) {
+          const int64_t threads = (int64_t)n_items * ncol * mpad_all;
+          hipLaunchKernelGGL(cov_w, dim3((unsigned)((threads + 255) / 256), gy), dim3(256), 0, v.st, d.by_level(), n_items, mpad_all,
+                             ncol, n, d.idx.get(), d.f.get(), f_stride, d.info.get() + s0, d_k.get(), d_w.get(), size);
+          herr = hipGetLastError();
+        }
+        phase(2);
+        for (int l = 0; k && herr == hipSuccess && l < n_levels; ++l) {
+          const int ni = level_off[l + 1] - level_off[l], mp = level_mpad[l];
+          const int64_t threads = (int64_t)ni * ncol * mp;
+          hipLaunchKernelGGL(cov_forward, dim3((unsigned)((threads + 255) / 256), gy), dim3(256), 0, v.st, d.by_level() + level_off[l],
+                             ni, mp, ncol, n, d.idx.get(), d.f.get(), f_stride, d.info.get() + s0, d_w.get(), d_k.get(), size);
+        }
+        if (herr == hipSuccess) herr = hipGetLastError();
+        phase(3);
+        if (herr == hipSuccess && w) herr = down(w, d_w.get(), s0, n, c0, ncol);
+        if (herr == hipSuccess && k) herr = down(k, d_k.get(), s0, n, c0, ncol);
+        phase(4);
+      }
+    }
+  }
+  if (herr == hipSuccess && info) herr = hipMemcpyAsync(info, d.info.get(), sizeof(int32_t) * (size_t)ns, hipMemcpyDeviceToHost, v.st);
+  const hipError_t serr = hipStreamSynchronize(v.st);   // (also when something failed: the uploads read this call's locals)
+  if (herr == hipSuccess) herr = serr;
+  if (herr != hipSuccess) return engine_fail(e, PGBP_ERR_HIP, fn + hipGetErrorString(herr));
+  return PGBP_OK;
+}
+
+extern "C" int pgbp_posterior_cov(pgbp_engine* e, int32_t tree, int32_t site_begin, int32_t site_end, int32_t n_cols,
+                                  const double* c, double* w, double* k, int32_t* info) {
+  return posterior_cov(e, tree, site_begin, site_end, n_cols, c, w, k, info, nullptr);
+}
+
+extern "C" int pgbp_posterior_cov_timed(pgbp_engine* e, int32_t tree, int32_t site_begin, int32_t site_end, int32_t n_cols,
+                                        const double* c, double* w, double* k, int32_t* info, double* ms5) {
+  if (e && !ms5) return engine_fail(e, PGBP_ERR_INVALID, "pgbp_posterior_cov_timed: no buffer for the phase times");
+  return posterior_cov(e, tree, site_begin, site_end, n_cols, c, w, k, info, ms5);
 }
 
 extern "C" void pgbp_sample_scratch_limits(int64_t factor_doubles, int64_t draw_doubles) {

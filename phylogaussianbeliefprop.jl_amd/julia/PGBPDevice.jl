@@ -475,6 +475,24 @@ function sample_posterior!(o::DeviceClusterGraphBelief, ndraws::Integer = 1;
     return x[1:sample_size(o), :]
 end
 
+"""
+    posterior_cov(obj, c; tree = 1) -> (w, k)
+
+Exact posterior covariances of linear functionals of the cluster variables (pgbp_posterior_cov): the adjoint of
+`sample_posterior!`'s sweep `x = m + A z`.  `c` is `sample_size(obj) x ncols`, a weight per entry of a draw; column `a` of `w` is
+`A'c_a` (`w[:, a]' * w[:, b]` is the posterior covariance of the functionals `a` and `b`), column `a` of `k` is `A w_a`, the
+covariance of every entry with functional `a`.  Exact only when the beliefs are calibrated on a clique tree; the call does not
+verify that.  A cluster whose conditional precision is not positive definite throws its PosDefException.
+"""
+function posterior_cov(o::DeviceClusterGraphBelief, c::AbstractVecOrMat{Float64}; tree::Integer = 1)
+    cc = Matrix{Float64}(reshape(c, size(c, 1), :)); ncols = size(cc, 2)
+    size(cc, 1) == sample_size(o) || error("c must be sample_size(obj) x ncols")
+    w = zeros(max(sample_size(o), 1), ncols); k = zeros(max(sample_size(o), 1), ncols); info = Ref(Int32(0))
+    check(o.handle, @ccall LIB.pgbp_posterior_cov(o.handle::Ptr{Cvoid}, (tree-1)::Int32, Int32(0)::Int32, Int32(1)::Int32, ncols::Int32, cc::Ptr{Float64}, w::Ptr{Float64}, k::Ptr{Float64}, info::Ref{Int32})::Cint)
+    info[] == 0 || throw(PGBP.LA.PosDefException(info[]))
+    return (w[1:sample_size(o), :], k[1:sample_size(o), :])
+end
+
 # ---- the model run forwards (pgbp_lg_set_topology, pgbp_lg_set_data / pgbp_lg_get_data, pgbp_lg_simulate).  Like the rest
 # of this file these wrappers are NOT exercised in the build container (no Julia there); tests/test_gpu_simulate.py drives the
 # same five C functions through the ctypes mirror.
