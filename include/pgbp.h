@@ -545,6 +545,49 @@ int     pgbp_lg_loo_families(pgbp_engine* e, int32_t* fam);
 int     pgbp_lg_loo(pgbp_engine* e, int32_t site_begin, int32_t site_end, double* mean, double* cov, double* lpd,
                     double* total, int32_t* info);
 void    pgbp_loo_scratch_limit(int64_t doubles);
+/* pgbp_lg_shift_scan, pgbp_lg_edge_gradient and pgbp_lg_loo for the sites of a UNIVARIATE BATCH, lanes = sites
+ * (csrc/pgbp_fam_uni.hip; the shared closed forms in csrc/pgbp_fam_uni_dev.hpp): each is the p = 1 case of the statement
+ * documented for the general call, with its conventions for root-prior families, skipped families (child_mask == 0), entries
+ * k >= n_parents and failed sites.  Accepted only on a thread-per-site engine, as pgbp_lg_gradient_sites: p = 1, every belief
+ * of at most 2 variables, at least 8 sites; anything else is PGBP_ERR_INVALID before any launch, the outputs untouched, the
+ * reason naming the general call to use instead.  The state errors and range checks are those of pgbp_lg_gradient_sites.
+ * A workgroup is 256 consecutive sites; a thread walks a block of 64 consecutive families (tip families for the leave-one-out
+ * sweep) for its one site and solves each family's cluster (0, 1 or 2 variables) in closed form.  The calls read the beliefs
+ * in the layout they are in (site-minor from 64 sites on) and convert nothing: pgbp_layout is the same before and after, and
+ * the next calibration finds the layout it left.  Shared and per-site parameters, the shifts and the tip noise in force are
+ * read as the general calls read them.  No atomics, every sum in a fixed order: two calls return the same bytes, and a site's
+ * bytes depend neither on the site range nor on the chunks it came in.  Values agree with the general calls to rounding (the
+ * closed forms add in another order), not to the byte.
+ * OUTPUTS ARE SITE-MINOR: one row of (site_end - site_begin) values per (family[, entry]) -- the transpose of the general
+ * calls' tables.  The rows of a chunk of sites at a time go through device scratch (256 MB at most, whole workgroups of 256
+ * sites; pgbp_sites_sweep_scratch_limit: that bound in doubles, process-wide, <= 0 restores the default -- the results do not
+ * depend on the chunks) and are copied into the caller's rows by strided copies; one stream synchronisation per call.
+ * pgbp_lg_shift_scan_sites: with j = 1 / V, C = u' Sigma u, g_w = j e and H = j - j C j (formed from C), a family is
+ *   identified iff H > min_info * j; then jump = g_w / H, lr = g_w^2 / H.
+ *   jump, lr, information [n_families][sites] (each may be NULL): jump and information NaN where the family is not identified,
+ *       is skipped or is a root-prior family; lr 0 where it is not identified or skipped, NaN for a root-prior family.
+ *   top_lr, top_family [sites] (may be NULL; not all five NULL): the largest lr of the site over the families that have at
+ *       least one parent, are identified and whose lr is finite, and the family that has it -- ties go to the lowest family
+ *       (a thread keeps its block's best with a strict >, a second kernel folds the blocks in index order with a strict >).
+ *       A site with nothing identified: -inf and -1.  With only these two asked for no table is allocated or copied.
+ *   info [sites] (may be NULL): as pgbp_lg_shift_scan's; that site's tables and top_lr are NaN, its top_family -1.
+ *   min_info outside [0, 1) is PGBP_ERR_INVALID.
+ * pgbp_lg_edge_gradient_sites: dlength, dgamma [n_families][K][sites], dshift [n_families][sites] (any may be NULL, not all
+ *   three), info [sites] (may be NULL): the quantities of pgbp_lg_edge_gradient; dgamma carries the s_k g_w term of a shift.
+ * pgbp_lg_loo_sites: for the tip families of pgbp_lg_loo_families, in that order: with S = Var(u) over the cluster parents
+ *   and D = V - S, the prediction is determined iff D > 2^-40 V and V > 0; var = V^2 / D, mean = y - V r / D,
+ *   lpd = -(log 2pi + 2 log V - log D + r^2 / D) / 2.
+ *   mean, var [n_tip][sites] (may be NULL), lpd [n_tip][sites] (required), info [n_tip][sites] (may be NULL; the codes of
+ *   pgbp_lg_loo), total [sites] (may be NULL): the per-block partial sums of lpd (blocks of 64 tips, added in tip order) added
+ *   in block order by a second kernel -- another order than pgbp_lg_loo's, so the two totals agree to rounding.  NaN where
+ *   a tip of the site is not determined. */
+int  pgbp_lg_shift_scan_sites(pgbp_engine* e, int32_t site_begin, int32_t site_end, double min_info, double* jump, double* lr,
+                              double* information, double* top_lr, int32_t* top_family, int32_t* info);
+int  pgbp_lg_edge_gradient_sites(pgbp_engine* e, int32_t site_begin, int32_t site_end, double* dlength, double* dgamma,
+                                 double* dshift, int32_t* info);
+int  pgbp_lg_loo_sites(pgbp_engine* e, int32_t site_begin, int32_t site_end, double* mean, double* var, double* lpd,
+                       double* total, int32_t* info);
+void pgbp_sites_sweep_scratch_limit(int64_t doubles);
 /* IMPUTATION of the missing tip values from CALIBRATED beliefs, for sites [site_begin, site_end): the posterior mean and
  * covariance of the traits a tip does not observe, given ALL the data (the tip's own observed traits included) -- the
  * leave-NOTHING-out complement of pgbp_lg_loo, with the parameters the engine kept from the last pgbp_lg_assignfactors (shared

@@ -135,6 +135,10 @@ SYMBOLS = {
     "pgbp_lg_loo_families": (C.c_int, [_P, _I32P]),
     "pgbp_lg_loo": (C.c_int, [_P, C.c_int32, C.c_int32, _F64P, _F64P, _F64P, _F64P, _I32P]),
     "pgbp_loo_scratch_limit": (None, [C.c_int64]),
+    "pgbp_lg_shift_scan_sites": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_double, _F64P, _F64P, _F64P, _F64P, _I32P, _I32P]),
+    "pgbp_lg_edge_gradient_sites": (C.c_int, [_P, C.c_int32, C.c_int32, _F64P, _F64P, _F64P, _I32P]),
+    "pgbp_lg_loo_sites": (C.c_int, [_P, C.c_int32, C.c_int32, _F64P, _F64P, _F64P, _F64P, _I32P]),
+    "pgbp_sites_sweep_scratch_limit": (None, [C.c_int64]),
     "pgbp_lg_impute_count": (C.c_int32, [_P]),
     "pgbp_lg_impute_families": (C.c_int, [_P, _I32P, C.POINTER(C.c_uint64)]),
     "pgbp_lg_impute": (C.c_int, [_P, C.c_int32, C.c_int32, _F64P, _F64P, _I32P]),

@@ -854,6 +854,136 @@ class ClusterGraphBelief:
         norm = np.where(grad["info"] != 0, np.nan, norm)
         return norm, grad
 
+    def _loglik_and_sites(self, schedule_tree, sweep, refill=False):
+        """the steps of loglik_and_gradient_sites_lg around one of the thread-per-site sweeps (`sweep`: its dict); refill:
+        the factors are filled again first, as loglik_and_shift_scan_lg does.  (loglik [n_sites], the sweep's dict, the
+        calibration's info [n_sites])"""
+        if refill:
+            if getattr(self, "_lg_last", None) is None:
+                raise L.PgbpError(L.ERR_STATE, "no parameters yet (call assignfactors_lg_ first)")
+            m, _keep = self._lg_last
+            _check(self._lib.pgbp_lg_assignfactors(self._eng, C.byref(m)), self._eng)
+        self._ensure_schedule([schedule_tree])
+        o = self._opts()
+        pa = np.asarray(schedule_tree[-2]).reshape(-1)
+        root = int(pa[0]) if pa.size else 0
+        _check(self._lib.pgbp_enqueue_calibrate(self._eng, 1, 1, C.byref(o)), self._eng)
+        _check(self._lib.pgbp_enqueue_integrate(self._eng, root), self._eng)
+        d = sweep()
+        norm = np.zeros(self.n_sites)
+        info = np.zeros(self.n_sites, dtype=np.int32)
+        _check(self._lib.pgbp_fetch_loglik(self._eng, L.f64p(norm), L.i32p(info)), self._eng)
+        return norm, d, info
+
+    def shift_scan_sites_lg(self, min_info=1e-8, information=False, tables=True):
+        """pgbp_lg_shift_scan_sites on the current beliefs: shift_scan_lg(all_sites=True) for a univariate batch on the
+        thread-per-site kernels (p = 1, every belief of at most 2 variables, at least 8 sites; anything else raises
+        PGBP_ERR_INVALID), lanes = sites.  The beliefs are read in the layout they are in: nothing is converted.
+        Same keys and [site, family, ...] indexing as shift_scan_lg(all_sites=True) -- jump, lr, dof, identified, edge_jump,
+        info, and with information=True H and se = H^-1/2 -- as transposed VIEWS of the call's site-minor rows, not copies;
+        the values agree with shift_scan_lg to rounding, and two calls return the same bytes.  Also top_lr [n_sites] and
+        top_family [n_sites], formed on the device: the largest lr of each site over the families with an edge that are
+        identified and whose lr is finite, and that family (ties to the lowest; -inf and -1 for a site with nothing
+        identified; NaN and -1 for a failed site).  tables=False returns only top_lr, top_family and info: no table is
+        allocated or fetched."""
+        n = self.n_sites
+        nf = len(self._lg["cluster"])
+        K = self._lg["length"].size // nf if nf else 1
+        jump = np.zeros((nf, n)) if tables else None
+        lr = np.zeros((nf, n)) if tables else None
+        H = np.zeros((nf, n)) if tables and information else None
+        top_lr = np.zeros(n)
+        top_family = np.zeros(n, dtype=np.int32)
+        info = np.zeros(n, dtype=np.int32)
+        _check(self._lib.pgbp_lg_shift_scan_sites(self._eng, 0, n, float(min_info), L.f64p(jump) if tables else None,
+                                                  L.f64p(lr) if tables else None, L.f64p(H) if H is not None else None,
+                                                  L.f64p(top_lr), L.i32p(top_family), L.i32p(info)), self._eng)
+        d = dict(top_lr=top_lr, top_family=top_family, info=info)
+        if not tables:
+            return d
+        jump = jump.T[:, :, None]
+        bits = ~np.isnan(jump)
+        gam = np.asarray(self._lg["gamma"], np.float64).reshape(nf, K)
+        real = np.arange(K)[None, :] < np.asarray(self._lg["n_parents"]).reshape(nf, 1)
+        inv = np.full((nf, K), np.nan)
+        ok = real & (gam != 0.0)
+        inv[ok] = 1.0 / gam[ok]
+        d.update(jump=jump, lr=lr.T, dof=bits.sum(axis=2).astype(np.int32), identified=bits,
+                 edge_jump=jump[:, :, None, :] * inv[None, :, :, None])
+        if information:
+            d["H"] = H.T[:, :, None, None]
+            d["se"] = 1.0 / np.sqrt(H.T[:, :, None])
+        return d
+
+    def loglik_and_shift_scan_sites_lg(self, schedule_tree, min_info=1e-8, information=False, tables=True):
+        """loglik_and_shift_scan_lg(schedule_tree, all_sites=True) with the thread-per-site scan (shift_scan_sites_lg): the
+        factors filled again (so that shifts set since the last assignfactors_lg_ are in) -> one calibrate -> integratebelief!
+        at the root cluster -> the scan, all of it on the thread-per-site kernels and in their layout.  Returns
+        (loglik [n_sites], scan dict); a failed site has info != 0 and NaN values (top_family -1)."""
+        norm, scan, info = self._loglik_and_sites(
+            schedule_tree, lambda: self.shift_scan_sites_lg(min_info=min_info, information=information, tables=tables), refill=True)
+        scan["info"] = np.where(scan["info"] != 0, scan["info"], info)
+        return np.where(scan["info"] != 0, np.nan, norm), scan
+
+    def edge_gradient_sites_lg(self):
+        """pgbp_lg_edge_gradient_sites on the current beliefs: edge_gradient_lg(all_sites=True) for a univariate batch on the
+        thread-per-site kernels (the conditions of gradient_sites_lg), lanes = sites, nothing converted.  Same keys and
+        [site, family, ...] indexing -- dlength, dgamma [n_sites, n_families, K], dshift [n_sites, n_families, 1], info -- as
+        transposed views of the call's site-minor rows; the values agree with edge_gradient_lg to rounding, and two calls
+        return the same bytes."""
+        n = self.n_sites
+        nf = len(self._lg["cluster"])
+        K = self._lg["length"].size // nf if nf else 1
+        dlength = np.zeros((nf, K, n))
+        dgamma = np.zeros((nf, K, n))
+        dshift = np.zeros((nf, n))
+        info = np.zeros(n, dtype=np.int32)
+        _check(self._lib.pgbp_lg_edge_gradient_sites(self._eng, 0, n, L.f64p(dlength), L.f64p(dgamma), L.f64p(dshift),
+                                                     L.i32p(info)), self._eng)
+        return dict(dlength=dlength.transpose(2, 0, 1), dgamma=dgamma.transpose(2, 0, 1), dshift=dshift.T[:, :, None], info=info)
+
+    def loglik_and_edge_gradient_sites_lg(self, schedule_tree):
+        """loglik_and_edge_gradient_lg(schedule_tree, all_sites=True) with the thread-per-site sweep (edge_gradient_sites_lg),
+        built as loglik_and_gradient_sites_lg is.  Returns (loglik [n_sites], edge-gradient dict); a failed site has
+        info != 0 and NaN values."""
+        norm, grad, info = self._loglik_and_sites(schedule_tree, self.edge_gradient_sites_lg)
+        grad["info"] = np.where(grad["info"] != 0, grad["info"], info)
+        return np.where(grad["info"] != 0, np.nan, norm), grad
+
+    def loo_sites_lg(self):
+        """pgbp_lg_loo_sites on the current beliefs: loo_lg(all_sites=True) for a univariate batch on the thread-per-site
+        kernels (the conditions of gradient_sites_lg), lanes = sites, nothing converted.  Same keys and [site, tip, ...]
+        indexing -- families, mean [n_sites, n_tip, 1], cov [n_sites, n_tip, 1, 1], lpd, total, info [n_sites, n_tip], y -- as
+        transposed views of the call's site-minor rows.  total adds the tips in another order than loo_lg: the two agree to
+        rounding, as every other value; two calls return the same bytes."""
+        nt = int(self._lib.pgbp_lg_loo_count(self._eng))
+        if nt < 0:
+            _check(self._lib.pgbp_lg_loo_sites(self._eng, 0, 0, None, None, None, None, None), self._eng)
+            raise L.PgbpError(L.ERR_STATE, "pgbp_lg_loo_count failed")
+        fam = np.zeros(max(nt, 1), dtype=np.int32)
+        _check(self._lib.pgbp_lg_loo_families(self._eng, L.i32p(fam)), self._eng)
+        fam = fam[:nt]
+        n = self.n_sites
+        mean = np.zeros((max(nt, 1), n))
+        var = np.zeros((max(nt, 1), n))
+        lpd = np.zeros((max(nt, 1), n))
+        total = np.zeros(n)
+        info = np.zeros((max(nt, 1), n), dtype=np.int32)
+        _check(self._lib.pgbp_lg_loo_sites(self._eng, 0, n, L.f64p(mean), L.f64p(var), L.f64p(lpd), L.f64p(total), L.i32p(info)),
+               self._eng)
+        y = self._lg["data"][:, self._lg["data_row"][fam]]
+        return dict(families=fam, mean=mean[:nt].T[:, :, None], cov=var[:nt].T[:, :, None, None], lpd=lpd[:nt].T, total=total,
+                    info=info[:nt].T, y=y)
+
+    def loo_and_loglik_sites_lg(self, schedule_tree):
+        """loo_and_loglik_lg(schedule_tree, all_sites=True) with the thread-per-site sweep (loo_sites_lg), built as
+        loglik_and_gradient_sites_lg is.  Returns (loglik [n_sites], loo dict); loglik of a site whose calibration failed is
+        NaN."""
+        norm, loo, info = self._loglik_and_sites(schedule_tree, self.loo_sites_lg)
+        return np.where(info != 0, np.nan, norm), loo
+
+    loglik_and_loo_sites_lg = loo_and_loglik_sites_lg
+
     def edge_gradient_lg(self, all_sites=False):
         """pgbp_lg_edge_gradient on the current beliefs: the derivative of the log-likelihood in every edge length, in every
         inheritance and in a shift of the mean on every edge, under the parameters of the last assignfactors_lg_ -- one sweep

@@ -275,6 +275,54 @@ function lg_gradient_sites(o::DeviceClusterGraphBelief, nsites::Integer, nrates:
 end
 
 """
+    lg_shift_scan_sites(obj, nsites, nfamilies; min_info = 1e-8, information = false, tables = true)
+        -> (jump, lr, H, top_lr, top_family, info)
+
+The scan of every edge for a mean shift for every site of a univariate batch on the thread-per-site kernels
+(pgbp_lg_shift_scan_sites; the conditions of `lg_gradient_sites`), lanes = sites, nothing converted.  `jump[s, f]`, `lr[s, f]` and
+`H[s, f]` (with `information`) are the call's site-minor rows; `top_lr[s]` and `top_family[s]` (1-based, 0: nothing identified
+or a failed site) the largest lr of a site and its family, formed on the device.  `tables = false` fetches no table (`nothing`).
+"""
+function lg_shift_scan_sites(o::DeviceClusterGraphBelief, nsites::Integer, nfamilies::Integer; min_info::Real = 1e-8,
+                             information::Bool = false, tables::Bool = true)
+    jump = tables ? zeros(nsites, nfamilies) : nothing
+    lr = tables ? zeros(nsites, nfamilies) : nothing
+    H = (tables && information) ? zeros(nsites, nfamilies) : nothing
+    top = zeros(nsites); topf = zeros(Int32, nsites); info = zeros(Int32, nsites)
+    ptr(x) = x === nothing ? Ptr{Float64}(C_NULL) : pointer(x)
+    GC.@preserve jump lr H check(o.handle, @ccall LIB.pgbp_lg_shift_scan_sites(o.handle::Ptr{Cvoid}, Int32(0)::Int32, Int32(nsites)::Int32, Float64(min_info)::Float64, ptr(jump)::Ptr{Float64}, ptr(lr)::Ptr{Float64}, ptr(H)::Ptr{Float64}, top::Ptr{Float64}, topf::Ptr{Int32}, info::Ptr{Int32})::Cint)
+    return (jump, lr, H, top, Int.(topf) .+ 1, info)
+end
+
+"""
+    lg_edge_gradient_sites(obj, nsites, nfamilies, K) -> (dlength, dgamma, dshift, info)
+
+`lg_edge_gradient` for every site of a univariate batch on the thread-per-site kernels (pgbp_lg_edge_gradient_sites), lanes =
+sites: `dlength[s, k, f]`, `dgamma[s, k, f]`, `dshift[s, f]`; a failed site (`info[s] != 0`) holds NaN.
+"""
+function lg_edge_gradient_sites(o::DeviceClusterGraphBelief, nsites::Integer, nfamilies::Integer, K::Integer)
+    dlength = zeros(nsites, K, nfamilies); dgamma = zeros(nsites, K, nfamilies); dshift = zeros(nsites, nfamilies)
+    info = zeros(Int32, nsites)
+    check(o.handle, @ccall LIB.pgbp_lg_edge_gradient_sites(o.handle::Ptr{Cvoid}, Int32(0)::Int32, Int32(nsites)::Int32, dlength::Ptr{Float64}, dgamma::Ptr{Float64}, dshift::Ptr{Float64}, info::Ptr{Int32})::Cint)
+    return (dlength, dgamma, dshift, info)
+end
+
+"""
+    lg_loo_sites(obj, nsites) -> (mean, var, lpd, total, info)
+
+`lg_loo` for every site of a univariate batch on the thread-per-site kernels (pgbp_lg_loo_sites), lanes = sites, for the tip
+families of `lg_loo_families` in that order: `mean[s, t]`, `var[s, t]`, `lpd[s, t]`, `info[s, t]` and `total[s]` (NaN where a
+tip of the site is not determined).
+"""
+function lg_loo_sites(o::DeviceClusterGraphBelief, nsites::Integer)
+    nt = max(length(lg_loo_families(o)), 1)
+    mean = zeros(nsites, nt); var = zeros(nsites, nt); lpd = zeros(nsites, nt); total = zeros(nsites)
+    info = zeros(Int32, nsites, nt)
+    check(o.handle, @ccall LIB.pgbp_lg_loo_sites(o.handle::Ptr{Cvoid}, Int32(0)::Int32, Int32(nsites)::Int32, mean::Ptr{Float64}, var::Ptr{Float64}, lpd::Ptr{Float64}, total::Ptr{Float64}, info::Ptr{Int32})::Cint)
+    return (mean, var, lpd, total, info)
+end
+
+"""
     lg_loo_families(obj) -> Vector{Int}
 
 The tip families of the table given to pgbp_lg_setup (1-based indices into it), in the order of `lg_loo`'s outputs

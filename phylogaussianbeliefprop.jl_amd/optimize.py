@@ -413,7 +413,7 @@ def select_shifts_lg(beliefs, schedule_tree, max_shifts, min_lr=0.0, candidates=
     return dict(path=path, edges=list(chosen), fit=fit, loglik0=ll0)
 
 
-def bootstrap_shift_scan_lg(beliefs, schedule_tree, seed=None, z=None, min_info=1e-8):
+def bootstrap_shift_scan_lg(beliefs, schedule_tree, seed=None, z=None, min_info=1e-8, sites=False):
     """Parametric bootstrap of the shift scan on a clique tree: the null distribution of the LARGEST lr over all edges, which
     has no closed form.  On an engine with B sites -- B replicates of one network, built with n_sites = B and the fitted null
     model assigned (assignfactors_lg_, with the shifts and the tip noise that belong to the null in force) -- it
@@ -428,6 +428,10 @@ def bootstrap_shift_scan_lg(beliefs, schedule_tree, seed=None, z=None, min_info=
     else the calibration's), x [B, n_families, p] (the simulated states), data [B, n_rows, p] (the simulated tip data, as the
     engine now holds them) and data_before (what it held: set_data_lg(out["data_before"]) restores it; nothing is refilled
     until the next assignfactors_lg_ / loglik_lg).
+    sites=True (a thread-per-site engine: one trait, every belief of at most 2 variables, B >= 8): step 3 is
+    loglik_and_shift_scan_sites_lg(tables=False), lanes = replicates -- the scan converts no layout and steps 3 and 4 fetch
+    no table: the maximum and its family are taken on the device, the edge from that family.  The same keys; max_lr agrees
+    with the default path to rounding.
     THRESHOLD: a quantile of max_lr calibrates select_shifts_lg -- min_lr = np.quantile(max_lr, 0.95) lets a first shift
     enter a data set WITHOUT any jump with probability about 5 % (Monte Carlo error of the quantile: about
     sqrt(0.05 * 0.95 / B) / density; B of a few hundred).  It is the threshold of the FIRST step; later steps scan under the
@@ -435,12 +439,20 @@ def bootstrap_shift_scan_lg(beliefs, schedule_tree, seed=None, z=None, min_info=
     only, like the scan."""
     before = beliefs.get_data_lg()
     x, sim_info = beliefs.simulate_lg(z=z, seed=seed, write_data=True, all_sites=True)
-    ll, scan = beliefs.loglik_and_shift_scan_lg(schedule_tree, all_sites=True, min_info=min_info)
     nf = len(beliefs._lg["cluster"])
     K = beliefs._lg["length"].size // nf
     gam = np.asarray(beliefs._lg["gamma"], np.float64).reshape(nf, K)
     npar = np.asarray(beliefs._lg["n_parents"]).reshape(nf)
     best_k = np.array([int(np.argmax(gam[f, :npar[f]])) if npar[f] > 0 else -1 for f in range(nf)])
+    if sites:
+        ll, scan = beliefs.loglik_and_shift_scan_sites_lg(schedule_tree, min_info=min_info, tables=False)
+        info = np.where(sim_info != 0, sim_info, scan["info"])
+        fam = scan["top_family"].astype(np.int64)
+        none = fam < 0
+        edge = np.stack([fam, np.where(none, -1, best_k[fam])], axis=1)
+        top = np.where(info != 0, np.nan, np.where(none, -np.inf, scan["top_lr"]))
+        return dict(max_lr=top, family=fam, edge=edge, loglik=ll, info=info, x=x, data=beliefs.get_data_lg(), data_before=before)
+    ll, scan = beliefs.loglik_and_shift_scan_lg(schedule_tree, all_sites=True, min_info=min_info)
     info = np.where(sim_info != 0, sim_info, scan["info"])
     lr = np.where((best_k >= 0)[None, :] & (scan["dof"] > 0) & np.isfinite(scan["lr"]), scan["lr"], -np.inf)
     fam = np.argmax(lr, axis=1)                        # (argmax: first of ties)
