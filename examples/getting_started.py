@@ -188,6 +188,15 @@ def main():
     print(f"OU batch: {int(fit['converged'].sum())} of {ns} sites converged in {fit['n_device_evals']} device passes; site 0: "
           f"alpha {fit['alpha'][0]:.3f} (simulated {al[0]:.3f}), theta {fit['theta'][0]:.3f} ({th[0]:.3f}), "
           f"stationary variance {fit['R'][0]:.3f} ({g2[0]:.3f}), log-likelihood {fit['loglik'][0]:.4f}")
+    # the engine is left calibrated at the estimates: ancestral states of every site, lanes = sites (moments_sites_; the root is
+    # fixed at mu, so the deepest ancestor with a posterior is the first internal node below it: variable 0 of its cluster)
+    c = int(np.flatnonzero(prob.meta["child_dim"] > 0)[0])
+    m, S, _, info = batch.moments_sites_([c])[0]
+    print(f"ancestral state of node {c + 1} (below the root), posterior mean +- sd at the first four sites: " +
+          ", ".join(f"{m[s, 0]:.3f} +- {np.sqrt(S[s, 0, 0]):.3f}" for s in range(4)) + f"; {int((info != 0).sum())} sites failed")
+    x, _, _ = batch.sample_posterior_sites_(n_draws=200, seed=11)
+    print(f"  and from 200 joint draws of all ancestral states (device generator): {x[:, 0, :].mean(axis=0)[int(prob.dims[:c].sum())]:.3f} "
+          f"+- {x[:, 0, :].std(axis=0)[int(prob.dims[:c].sum())]:.3f} at site 0")
 
 
 if __name__ == "__main__":

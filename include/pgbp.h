@@ -588,6 +588,60 @@ int  pgbp_lg_edge_gradient_sites(pgbp_engine* e, int32_t site_begin, int32_t sit
 int  pgbp_lg_loo_sites(pgbp_engine* e, int32_t site_begin, int32_t site_end, double* mean, double* var, double* lpd,
                        double* total, int32_t* info);
 void pgbp_sites_sweep_scratch_limit(int64_t doubles);
+/* pgbp_moments, pgbp_sample_posterior and pgbp_lg_impute for the sites of a UNIVARIATE BATCH, lanes = sites
+ * (csrc/pgbp_post_uni.hip): what is asked of a fitted batch -- the posterior moments of every belief, joint draws of all
+ * ancestral states, the predictions of the tips without data -- in the frame of the three calls above.  Accepted and refused
+ * as pgbp_lg_gradient_sites: a family table and parameters (PGBP_ERR_STATE otherwise), a site range inside the engine's, p = 1,
+ * every belief of at most 2 variables, at least 8 sites; anything else is PGBP_ERR_INVALID before any launch, the outputs
+ * untouched, the reason naming the general call to use instead.  A workgroup is 256 consecutive sites; a thread walks a block of
+ * 64 table entries for its one site, everything in closed form.  The beliefs are read in the layout they are in and nothing is
+ * converted: pgbp_layout is the same before and after and the pool keeps its bytes.  No atomics, every sum in a fixed order:
+ * two calls return the same bytes, and a site's bytes depend neither on the site range nor on the chunks.  Values agree with
+ * the general calls to rounding, not to the byte.  ALL OUTPUTS ARE SITE-MINOR ROWS of (site_end - site_begin) values; a chunk
+ * of sites at a time goes through device scratch bounded by pgbp_sites_sweep_scratch_limit (whole workgroups of 256 sites, one
+ * at least; the draws of pgbp_sample_posterior_sites are cut first); one stream synchronisation per call.
+ * pgbp_moments_sites: the semantics of pgbp_moments for the n listed beliefs (beliefs == NULL: every cluster; sepset beliefs
+ *   are allowed; an index out of range is PGBP_ERR_INVALID).
+ *   mean [sum of dims][sites]            the variables of the listed beliefs, belief after belief;
+ *   cov  [sum of m (m + 1) / 2][sites]   the upper triangle of Sigma = J^-1 in column order: S00, S01, S11; may be NULL;
+ *   norm [n][sites]                      g + ((m log 2pi - log det J) + h'mu) / 2, log det J = log a (+ log of the Schur
+ *                                        complement) -- the terms in this order;
+ *   info [n][sites]                      may be NULL: 0, or PosDefException.info (that entry's mean, cov and norm are NaN).
+ *   The all-zero belief (J = 0, h = 0) has mean Inf, norm g, cov NaN, info 0; a belief without variables has only norm = g.
+ *   mean and norm NULL is PGBP_ERR_INVALID.
+ * pgbp_sample_posterior_sites: the semantics documented for pgbp_sample_posterior -- S and R of a child cluster of schedule
+ *   tree `tree`, x_R = J_RR^-1 (h_R - J_RS x_S) + L^-T z_R with L lower triangular in the child's variable order, z at S
+ *   positions ignored, a 0-variable sepset an independent draw, a shared variable the same bits in every cluster that holds it,
+ *   z = 0 the joint mean -- and its refusals, after those above: no schedule (PGBP_ERR_STATE), `tree` out of range, not a
+ *   spanning clique tree, n_draws < 1, x NULL.  The same z gives pgbp_sample_posterior's draw to rounding.
+ *   z, x [n_draws][pgbp_sample_size][sites]: the entry layout of pgbp_sample_posterior, transposed.
+ *   z == NULL: the device generates the normals itself from `seed`:
+ *     (r0, r1, r2, r3) = Philox4x32-10(counter = (entry, draw, absolute site, 1), key = (seed & 0xffffffff, seed >> 32)), the
+ *     constants and the two 53-bit uniforms u1 (r0, r1), u2 (r2, r3) as documented for pgbp_lg_simulate;
+ *     z = sqrt(-2 log u1) cos(2 pi u2), 2 pi = 6.283185307179586 (one normal per counter; the sine is dropped).
+ *   The last counter word 1 keeps the stream disjoint from pgbp_lg_simulate's under the same seed.  The generator is
+ *   stateless: the value of an (entry, draw, site) depends neither on the site range nor on the chunks.  With z != NULL the
+ *   seed is not read.
+ *   info [sites] (may be NULL): 0, or the 1-based index of the first cluster in preorder whose J_RR is not positive definite
+ *   (pivot by pivot, in the order of R); all draws of that site are NaN, other sites keep their bytes.
+ *   Device: a validity pass (a thread walks blocks of 64 clusters in preorder rank, the blocks folded in order), then one
+ *   launch per preorder level, thread = site, the clusters of the level along grid.y, the draws in a loop; the at most five
+ *   coefficients of a cluster's conditional are formed in registers by the launch that uses them -- no factor pool.
+ * pgbp_lg_impute_sites: the p = 1 case of pgbp_lg_impute for the families of pgbp_lg_impute_families, in that order.  A listed
+ *   tip observes nothing at p = 1: mean = E[u] + w, var = u' Sigma u + V over the cluster parents, with the shifts and the tip
+ *   noise in force (a noisy tip predicts the observation).
+ *   mean, var [n_listed][sites] (either may be NULL, not both), info [n_listed][sites] (may be NULL): the codes of
+ *   pgbp_lg_impute -- 0; -1 where the static mask `predicted` is empty (a cluster parent lacks the trait: NaN); 1 when V is not
+ *   positive or the cluster's belief is the constant 1; 1 + PosDefException.info of the cluster. */
+int  pgbp_moments_sites(pgbp_engine* e, int32_t n, const int32_t* beliefs, int32_t site_begin, int32_t site_end, double* mean,
+                        double* cov, double* norm, int32_t* info);
+int  pgbp_sample_posterior_sites(pgbp_engine* e, int32_t tree, int32_t site_begin, int32_t site_end, int32_t n_draws,
+                                 const double* z, uint64_t seed, double* x, int32_t* info);
+int  pgbp_lg_impute_sites(pgbp_engine* e, int32_t site_begin, int32_t site_end, double* mean, double* var, int32_t* info);
+/* pgbp_sample_posterior_sites with the stream drained after each phase (measurement only: tools/time_post_uni.py):
+ * ms4[0 .. 3] = wall milliseconds of {validity pass, copy of z, level launches, copy of x}, summed over the chunks. */
+int  pgbp_sample_posterior_sites_timed(pgbp_engine* e, int32_t tree, int32_t site_begin, int32_t site_end, int32_t n_draws,
+                                       const double* z, uint64_t seed, double* x, int32_t* info, double* ms4);
 /* IMPUTATION of the missing tip values from CALIBRATED beliefs, for sites [site_begin, site_end): the posterior mean and
  * covariance of the traits a tip does not observe, given ALL the data (the tip's own observed traits included) -- the
  * leave-NOTHING-out complement of pgbp_lg_loo, with the parameters the engine kept from the last pgbp_lg_assignfactors (shared

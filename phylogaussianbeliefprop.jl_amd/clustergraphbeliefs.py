@@ -443,7 +443,8 @@ class ClusterGraphBelief:
             m = int(self._dims[b])
             Sig = None
             if cov:
-                Sig = out[:, at: at + m * m].reshape(-1, m, m).transpose(0, 2, 1)   # (column-major records)
+                # (column-major records; the site count spelled out: -1 cannot be inferred for a belief without variables)
+                Sig = out[:, at: at + m * m].reshape(out.shape[0], m, m).transpose(0, 2, 1)
                 at += m * m
             mu = out[:, at: at + m]
             norm = out[:, at + m]
@@ -983,6 +984,119 @@ class ClusterGraphBelief:
         return np.where(info != 0, np.nan, norm), loo
 
     loglik_and_loo_sites_lg = loo_and_loglik_sites_lg
+
+    def moments_sites_(self, beliefs=None, cov=True):
+        """pgbp_moments_sites on the current beliefs: moments_(beliefs, cov, all_sites=True) for a univariate batch on the
+        thread-per-site kernels (the conditions of gradient_sites_lg; anything else raises PGBP_ERR_INVALID), lanes = sites,
+        nothing converted.  The same list of (mu [n_sites, m], Sigma [n_sites, m, m] or None, norm [n_sites], info [n_sites]):
+        mu, norm and info as transposed views of the call's site-minor rows, Sigma expanded from the packed upper triangle.
+        The values agree with moments_ to rounding; two calls return the same bytes."""
+        if beliefs is None:
+            lst = np.arange(self.nclusters, dtype=np.int32)
+            ptr, n = None, 0
+        else:
+            lst = np.ascontiguousarray(beliefs, dtype=np.int32).reshape(-1)
+            ptr, n = L.i32p(lst if lst.size else np.zeros(1, dtype=np.int32)), int(lst.size)
+        ok = (lst >= 0) & (lst < len(self._dims))
+        dims = np.where(ok, self._dims[np.where(ok, lst, 0)], 0).astype(np.int64)   # (the call reports a bad index)
+        ns = self.n_sites
+        nm, nt, nl = int(dims.sum()), int((dims * (dims + 1) // 2).sum()), int(lst.size)
+        mean = np.zeros((max(nm, 1), ns))
+        tri = np.zeros((max(nt, 1), ns)) if cov else None
+        norm = np.zeros((max(nl, 1), ns))
+        info = np.zeros((max(nl, 1), ns), dtype=np.int32)
+        _check(self._lib.pgbp_moments_sites(self._eng, n, ptr, 0, ns, L.f64p(mean), L.f64p(tri) if cov else None, L.f64p(norm),
+                                            L.i32p(info)), self._eng)
+        res, am, at = [], 0, 0
+        for i, m in enumerate(int(d) for d in dims):
+            Sig = None
+            if cov:
+                Sig = np.empty((ns, m, m))
+                for b in range(m):
+                    for a in range(b + 1):
+                        Sig[:, a, b] = Sig[:, b, a] = tri[at + b * (b + 1) // 2 + a]
+                at += m * (m + 1) // 2
+            res.append((mean[am: am + m].T, Sig, norm[i], info[i]))
+            am += m
+        return res
+
+    def node_moments_sites(self, nodes=None):
+        """Posterior mean and variance of the nodes of a univariate batch, lanes = sites: {node label: (mean [n_sites],
+        var [n_sites])} from one moments_sites_ call over the first cluster that holds each node (node_samples' rule); NaN for
+        a node whose trait is out of scope there and where the cluster's info is not 0.  nodes=None: every labelled node."""
+        ent = self._node_entries("node_moments_sites")
+        nodes = list(ent) if nodes is None else list(nodes)
+        for v in nodes:
+            if v not in ent:
+                raise ValueError(f"no cluster holds node {v!r}")
+        clusters = sorted({ent[v][0] for v in nodes})
+        mom = dict(zip(clusters, self.moments_sites_(clusters, cov=True)))
+        out = {}
+        for v in nodes:
+            ci, pos, _ = ent[v]
+            if pos[0] < 0:
+                out[v] = (np.full(self.n_sites, np.nan), np.full(self.n_sites, np.nan))
+            else:
+                out[v] = (mom[ci][0][:, pos[0]], mom[ci][1][:, pos[0], pos[0]])
+        return out
+
+    def sample_posterior_sites_(self, n_draws=1, z=None, seed=None, schedule_tree=0):
+        """pgbp_sample_posterior_sites: sample_posterior_(all_sites=True) for a univariate batch on the thread-per-site kernels
+        (the conditions of gradient_sites_lg), lanes = sites, nothing converted.  z: standard normals [n_draws, n_sites, size]
+        as sample_posterior_ takes them (copied once into the call's site-minor order), or None: the DEVICE generates them
+        from `seed` (Philox4x32-10, the convention of include/pgbp.h; None: a seed drawn from numpy) and nothing is copied up.
+        Returns (x, info, views) indexed as sample_posterior_(all_sites=True) -- x [n_draws, n_sites, size], info [n_sites],
+        views[i] = x[:, :, cluster i's variables] -- as views of the call's site-minor array [n_draws, size, n_sites], so
+        node_samples works unchanged.  The same z gives sample_posterior_'s draws to rounding."""
+        size = int(self._lib.pgbp_sample_size(self._eng))
+        ns, n_draws = self.n_sites, int(n_draws)
+        shape = (max(n_draws, 0), ns, size)
+        zp = None
+        if z is not None:
+            z = np.asarray(z, dtype=np.float64)
+            if z.shape != shape:
+                raise ValueError(f"z has shape {z.shape}, expected {shape}")
+            zs = np.ascontiguousarray(z.transpose(0, 2, 1))
+            zp = L.f64p(zs if zs.size else np.zeros(1))
+        elif seed is None:
+            seed = int(np.random.default_rng().integers(0, 2 ** 63))
+        xs = np.zeros((shape[0], size, ns))
+        info = np.zeros(ns, dtype=np.int32)
+        _check(self._lib.pgbp_sample_posterior_sites(self._eng, int(schedule_tree), 0, ns, n_draws, zp,
+                                                     int(seed or 0) & 0xFFFFFFFFFFFFFFFF, L.f64p(xs if xs.size else np.zeros(1)),
+                                                     L.i32p(info)), self._eng)
+        x = xs.transpose(0, 2, 1)
+        off = np.concatenate([[0], np.cumsum(self._dims[: self.nclusters].astype(np.int64))])
+        return x, info, [x[:, :, off[i]: off[i + 1]] for i in range(self.nclusters)]
+
+    def impute_sites_lg(self):
+        """pgbp_lg_impute_sites on the current beliefs: impute_lg(all_sites=True) for a univariate batch on the thread-per-site
+        kernels (the conditions of gradient_sites_lg), lanes = sites, nothing converted.  Same keys and [site, tip, ...]
+        indexing -- families, rows, predicted [n, 1], mean [n_sites, n, 1], cov [n_sites, n, 1, 1], info [n_sites, n] -- as
+        transposed views of the call's site-minor rows, so imputed_data takes a site of it; the values agree with impute_lg
+        to rounding, and two calls return the same bytes."""
+        n = int(self._lib.pgbp_lg_impute_count(self._eng))
+        if n < 0:
+            _check(self._lib.pgbp_lg_impute_sites(self._eng, 0, 0, None, None, None), self._eng)
+            raise L.PgbpError(L.ERR_STATE, "pgbp_lg_impute_count failed")
+        fam = np.zeros(max(n, 1), dtype=np.int32)
+        pred = np.zeros(max(n, 1), dtype=np.uint64)
+        _check(self._lib.pgbp_lg_impute_families(self._eng, L.i32p(fam), pred.ctypes.data_as(C.POINTER(C.c_uint64))), self._eng)
+        fam, pred = fam[:n], pred[:n]
+        ns = self.n_sites
+        mean = np.full((max(n, 1), ns), np.nan)
+        var = np.full((max(n, 1), ns), np.nan)
+        info = np.zeros((max(n, 1), ns), dtype=np.int32)
+        _check(self._lib.pgbp_lg_impute_sites(self._eng, 0, ns, L.f64p(mean), L.f64p(var), L.i32p(info)), self._eng)
+        return dict(families=fam, rows=self._lg["data_row"][fam], predicted=(pred & np.uint64(1)).astype(bool).reshape(n, 1),
+                    mean=mean[:n].T[:, :, None], cov=var[:n].T[:, :, None, None], info=info[:n].T)
+
+    def impute_and_loglik_sites_lg(self, schedule_tree):
+        """impute_and_loglik_lg(schedule_tree, all_sites=True) with the thread-per-site sweep (impute_sites_lg), built as
+        loglik_and_gradient_sites_lg is.  Returns (loglik [n_sites], impute dict); loglik of a site whose calibration failed
+        is NaN."""
+        norm, imp, info = self._loglik_and_sites(schedule_tree, self.impute_sites_lg)
+        return np.where(info != 0, np.nan, norm), imp
 
     def edge_gradient_lg(self, all_sites=False):
         """pgbp_lg_edge_gradient on the current beliefs: the derivative of the log-likelihood in every edge length, in every

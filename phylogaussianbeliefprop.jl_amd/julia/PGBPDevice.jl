@@ -323,6 +323,58 @@ function lg_loo_sites(o::DeviceClusterGraphBelief, nsites::Integer)
 end
 
 """
+    moments_sites(obj, nsites, dims; cov = true) -> (mean, tri, norm, info)
+
+`moments!` of EVERY CLUSTER for every site of a univariate batch on the thread-per-site kernels (pgbp_moments_sites; the
+conditions of `lg_gradient_sites`), lanes = sites, nothing converted.  `dims`: the clusters' dimensions (0, 1 or 2).  The
+call's site-minor rows: `mean[s, i]` over the clusters' variables, cluster after cluster; `tri[s, i]` the packed upper triangle
+of Sigma = J^-1 per cluster (S00, S01, S11; `nothing` without `cov`); `norm[s, c]`, `info[s, c]` (0, or PosDefException.info:
+that cluster's entries are NaN).  Untested: there is no Julia on the test machines.
+"""
+function moments_sites(o::DeviceClusterGraphBelief, nsites::Integer, dims::AbstractVector{<:Integer}; cov::Bool = true)
+    nc = length(dims)
+    mean = zeros(nsites, max(sum(dims), 1))
+    tri = cov ? zeros(nsites, max(sum(m * (m + 1) ÷ 2 for m in dims), 1)) : nothing
+    norm = zeros(nsites, max(nc, 1)); info = zeros(Int32, nsites, max(nc, 1))
+    GC.@preserve tri check(o.handle, @ccall LIB.pgbp_moments_sites(o.handle::Ptr{Cvoid}, Int32(0)::Int32, Ptr{Int32}(C_NULL)::Ptr{Int32}, Int32(0)::Int32, Int32(nsites)::Int32, mean::Ptr{Float64}, (cov ? pointer(tri) : Ptr{Float64}(C_NULL))::Ptr{Float64}, norm::Ptr{Float64}, info::Ptr{Int32})::Cint)
+    return (mean, tri, norm, info)
+end
+
+"""
+    sample_posterior_sites(obj, nsites, ndraws = 1; z = nothing, seed = 0, tree = 1) -> (x, info)
+
+`sample_posterior!` for every site of a univariate batch on the thread-per-site kernels (pgbp_sample_posterior_sites), lanes =
+sites: `x[s, i, d]` = entry `i` of draw `d` at site `s` (the entry layout of `sample_posterior!`, transposed); `z` the same
+shape, or `nothing`: the device generates the normals from `seed` (Philox4x32-10, the convention of include/pgbp.h).
+`info[s]`: 0, or the 1-based index of the first cluster in preorder whose conditional precision is not positive definite
+(that site's draws are NaN).  `tree`: 1-based index into the schedule that was set.  Untested: no Julia on the test machines.
+"""
+function sample_posterior_sites(o::DeviceClusterGraphBelief, nsites::Integer, ndraws::Integer = 1;
+                                z::Union{Nothing,Array{Float64,3}} = nothing, seed::Integer = 0, tree::Integer = 1)
+    size = sample_size(o)
+    z === nothing || Base.size(z) == (nsites, size, ndraws) || error("z has size $(Base.size(z)), expected $((nsites, size, ndraws))")
+    x = zeros(nsites, max(size, 1), max(ndraws, 1)); info = zeros(Int32, nsites)
+    GC.@preserve z check(o.handle, @ccall LIB.pgbp_sample_posterior_sites(o.handle::Ptr{Cvoid}, Int32(tree - 1)::Int32, Int32(0)::Int32, Int32(nsites)::Int32, Int32(ndraws)::Int32, (z === nothing ? Ptr{Float64}(C_NULL) : pointer(z))::Ptr{Float64}, UInt64(seed)::UInt64, x::Ptr{Float64}, info::Ptr{Int32})::Cint)
+    return (x, info)
+end
+
+"""
+    lg_impute_sites(obj, nsites) -> (mean, var, info)
+
+`lg_impute` for every site of a univariate batch on the thread-per-site kernels (pgbp_lg_impute_sites), lanes = sites, for the
+families of `lg_impute_families` in that order: `mean[s, t]`, `var[s, t]` (NaN where nothing is predicted) and `info[s, t]`
+(the codes of `lg_impute`).  Untested: no Julia on the test machines.
+"""
+function lg_impute_sites(o::DeviceClusterGraphBelief, nsites::Integer)
+    n = @ccall LIB.pgbp_lg_impute_count(o.handle::Ptr{Cvoid})::Int32
+    n >= 0 || error("pgbp_lg_impute_count: no family table (call pgbp_lg_setup first)")
+    nt = max(Int(n), 1)
+    mean = fill(NaN, nsites, nt); var = fill(NaN, nsites, nt); info = zeros(Int32, nsites, nt)
+    check(o.handle, @ccall LIB.pgbp_lg_impute_sites(o.handle::Ptr{Cvoid}, Int32(0)::Int32, Int32(nsites)::Int32, mean::Ptr{Float64}, var::Ptr{Float64}, info::Ptr{Int32})::Cint)
+    return (mean[:, 1:n], var[:, 1:n], info[:, 1:n])
+end
+
+"""
     lg_loo_families(obj) -> Vector{Int}
 
 The tip families of the table given to pgbp_lg_setup (1-based indices into it), in the order of `lg_loo`'s outputs
