@@ -197,6 +197,17 @@ def main():
     x, _, _ = batch.sample_posterior_sites_(n_draws=200, seed=11)
     print(f"  and from 200 joint draws of all ancestral states (device generator): {x[:, 0, :].mean(axis=0)[int(prob.dims[:c].sum())]:.3f} "
           f"+- {x[:, 0, :].std(axis=0)[int(prob.dims[:c].sum())]:.3f} at site 0")
+    # the difference of two ancestors that share no cluster, with its standard error, for every site at once: the contrast as
+    # one column of posterior_cov_sites_, its variance folded on the device (gram) -- no table leaves it
+    c2 = int(np.flatnonzero(prob.meta["child_dim"] > 0)[-1])
+    e1, e2 = int(prob.dims[:c].sum()), int(prob.dims[:c2].sum())
+    contrast = np.zeros((1, int(prob.dims[: batch.nclusters].sum())))
+    contrast[0, e1], contrast[0, e2] = 1.0, -1.0
+    _, _, gram, cinfo = batch.posterior_cov_sites_(contrast, want_w=False, want_k=False)
+    m2 = batch.moments_sites_([c2], cov=False)[0][0]
+    print(f"  node {c + 1} minus node {c2 + 1}, posterior mean +- se at the first four sites: " +
+          ", ".join(f"{m[s, 0] - m2[s, 0]:.3f} +- {np.sqrt(gram[s, 0, 0]):.3f}" for s in range(4)) +
+          f"; {int((cinfo != 0).sum())} sites failed")
 
 
 if __name__ == "__main__":

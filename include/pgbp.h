@@ -642,6 +642,45 @@ int  pgbp_lg_impute_sites(pgbp_engine* e, int32_t site_begin, int32_t site_end, 
  * ms4[0 .. 3] = wall milliseconds of {validity pass, copy of z, level launches, copy of x}, summed over the chunks. */
 int  pgbp_sample_posterior_sites_timed(pgbp_engine* e, int32_t tree, int32_t site_begin, int32_t site_end, int32_t n_draws,
                                        const double* z, uint64_t seed, double* x, int32_t* info, double* ms4);
+/* POSTERIOR COVARIANCE OF A UNIVARIATE BATCH WITH LANES = SITES (csrc/pgbp_cov_uni.hip): pgbp_posterior_cov (below) in the
+ * frame of the three calls above, for the out-of-clique queries of a fitted batch -- the covariance of two ancestors that share
+ * no cluster, the variance of a clade mean or of a contrast -- at every site at once.  The semantics are pgbp_posterior_cov's:
+ * the same `tree`, size = pgbp_sample_size, entry layout and split of a cluster into S and R; with x = m + A z at one site
+ *   c    [n_cols][size]                       the functionals, shared by the sites (wave-uniform on the device: scalar loads);
+ *   w    [n_cols][size][sites] (may be NULL)  w = A'c; +0.0 at the S positions of non-root clusters;
+ *   k    [n_cols][size][sites] (may be NULL)  k = A w = Cov(x, c'x | data); a variable held by several clusters has the same bits
+ *                                             in every copy;
+ *   gram [n_cols (n_cols + 1) / 2][sites] (may be NULL)  the upper triangle in column order (G00, G01, G11, ...: the packing of
+ *                                             pgbp_moments_sites' cov) of G_ab = w_a . w_b = Cov(c_a'x, c_b'x | data), folded on
+ *                                             the device: the sum over the entries is taken per block of 64 entries in index
+ *                                             order (from 0.0), and the blocks are added in block order (from 0.0), as
+ *                                             pgbp_lg_gradient_sites adds its partial sums;
+ *   info [sites] (may be NULL)                the value of pgbp_sample_posterior_sites; w, k and gram of a site whose info is not
+ *                                             0 are NaN, its neighbours keep their bytes.
+ * w, k and gram may not all be NULL.  With only gram asked, no table of size x sites is allocated on the host or copied to it.
+ * Accepted and refused as pgbp_sample_posterior_sites, in its order (the reason names pgbp_posterior_cov as the call to use
+ * instead where one applies), then: n_cols < 1, c NULL, all three outputs NULL; every refusal before any launch, the outputs,
+ * pgbp_layout and the pool untouched.  Scratch is bounded by pgbp_sites_sweep_scratch_limit: chunks are whole workgroups of 256
+ * sites (one at least); without gram the columns are cut as the draws of pgbp_sample_posterior_sites are; with gram all n_cols
+ * columns of a chunk are resident together, and when the columns of one workgroup of sites -- n_cols size doubles each for w (twice
+ * that with k), (blocks + 1) n_cols (n_cols + 1) / 2 for gram and its partial sums, one mark per 64 clusters -- exceed the limit
+ * the call is PGBP_ERR_INVALID and the text says how many columns fit.
+ * Device: the sampler's validity pass; an ADJOINT phase, one launch per level from the deepest, thread = site, the clusters of the
+ * level along grid.y, the columns in a loop, in gather form and in place: a cluster adds to c the terms its children left at
+ * their S entries (children in index order, then their S positions in order: pgbp_posterior_cov's list, built once per call;
+ * what is taken is left +0.0), forms its at most four coefficients once in registers, and writes w at its R entries and
+ * t_C[S_j] = xbar_C[S_j] - sum_i G_ij xbar_C[R_i] at its S entries for its parent -- no factor pool; GRAM, a thread per site and
+ * block of 64 entries over all pairs of columns, then the fold; a FORWARD phase, one launch per preorder level, the sampler's
+ * apply without its offset and with w for z.  Read-only on the pool, nothing converted.  Two calls return the same bytes, and
+ * the bytes of a (column, site) depend neither on the site range nor on the chunks or the other columns.  Values agree with
+ * pgbp_posterior_cov to rounding, not to the byte.  EXACT ONLY FOR BELIEFS CALIBRATED ON A CLIQUE TREE; not verified. */
+int  pgbp_posterior_cov_sites(pgbp_engine* e, int32_t tree, int32_t site_begin, int32_t site_end, int32_t n_cols,
+                              const double* c, double* w, double* k, double* gram, int32_t* info);
+/* The same call with the stream drained after each phase (measurement only: tools/time_cov_uni.py): ms5[0 .. 4] = wall
+ * milliseconds of {validity pass, adjoint phase, gram and its fold, forward phase, copies of w, k and gram}, summed over the
+ * chunks. */
+int  pgbp_posterior_cov_sites_timed(pgbp_engine* e, int32_t tree, int32_t site_begin, int32_t site_end, int32_t n_cols,
+                                    const double* c, double* w, double* k, double* gram, int32_t* info, double* ms5);
 /* IMPUTATION of the missing tip values from CALIBRATED beliefs, for sites [site_begin, site_end): the posterior mean and
  * covariance of the traits a tip does not observe, given ALL the data (the tip's own observed traits included) -- the
  * leave-NOTHING-out complement of pgbp_lg_loo, with the parameters the engine kept from the last pgbp_lg_assignfactors (shared

@@ -142,6 +142,8 @@ SYMBOLS = {
     "pgbp_moments_sites": (C.c_int, [_P, C.c_int32, _I32P, C.c_int32, C.c_int32, _F64P, _F64P, _F64P, _I32P]),
     "pgbp_sample_posterior_sites": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _F64P, C.c_uint64, _F64P, _I32P]),
     "pgbp_sample_posterior_sites_timed": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _F64P, C.c_uint64, _F64P, _I32P, _F64P]),
+    "pgbp_posterior_cov_sites": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _F64P, _F64P, _F64P, _F64P, _I32P]),
+    "pgbp_posterior_cov_sites_timed": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _F64P, _F64P, _F64P, _F64P, _I32P, _F64P]),
     "pgbp_lg_impute_sites": (C.c_int, [_P, C.c_int32, C.c_int32, _F64P, _F64P, _I32P]),
     "pgbp_lg_impute_count": (C.c_int32, [_P]),
     "pgbp_lg_impute_families": (C.c_int, [_P, _I32P, C.POINTER(C.c_uint64)]),

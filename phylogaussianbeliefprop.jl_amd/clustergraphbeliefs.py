@@ -1069,6 +1069,100 @@ class ClusterGraphBelief:
         off = np.concatenate([[0], np.cumsum(self._dims[: self.nclusters].astype(np.int64))])
         return x, info, [x[:, :, off[i]: off[i + 1]] for i in range(self.nclusters)]
 
+    def posterior_cov_sites_(self, c, schedule_tree=0, want_w=True, want_k=True, want_gram=True):
+        """pgbp_posterior_cov_sites: posterior_cov_(all_sites=True) for a univariate batch on the thread-per-site kernels (the
+        conditions of gradient_sites_lg), lanes = sites, nothing converted, plus the Gram matrix of the columns folded on the
+        device.  c: [n_cols, size] (or [size]), shared by the sites.
+        Returns (w, k, gram, info): w and k indexed as posterior_cov_(all_sites=True) -- [n_cols, n_sites, size] -- as
+        transposed views of the call's site-minor rows; gram [n_sites, n_cols, n_cols], gram[s, a, b] = w_a . w_b =
+        Cov(c_a'x, c_b'x | data) at site s, expanded from the packed upper triangle; info [n_sites] as sample_posterior_sites_'
+        (a site whose info is not 0 is NaN in all three).  want_* false: that array is None and is neither computed beyond
+        what the others need nor moved -- with only gram no table of size x sites exists on the host.  The values agree with
+        posterior_cov_ to rounding; two calls return the same bytes."""
+        size = int(self._lib.pgbp_sample_size(self._eng))
+        ns = self.n_sites
+        c = np.ascontiguousarray(np.atleast_2d(np.asarray(c, dtype=np.float64)))
+        if c.ndim != 2 or c.shape[1] != size:
+            raise ValueError(f"c has shape {c.shape}, expected (n_cols, {size})")
+        nc = int(c.shape[0])
+        ws = np.zeros((nc, size, ns)) if want_w else None
+        ks = np.zeros((nc, size, ns)) if want_k else None
+        tri = np.zeros((max(nc * (nc + 1) // 2, 1), ns)) if want_gram else None
+        info = np.zeros(ns, dtype=np.int32)
+        ptr = lambda a: None if a is None else L.f64p(a if a.size else np.zeros(1))
+        _check(self._lib.pgbp_posterior_cov_sites(self._eng, int(schedule_tree), 0, ns, nc, L.f64p(c if c.size else np.zeros(1)),
+                                                  ptr(ws), ptr(ks), ptr(tri), L.i32p(info)), self._eng)
+        gram = None
+        if want_gram:
+            gram = np.empty((ns, nc, nc))
+            for b in range(nc):
+                for a in range(b + 1):
+                    gram[:, a, b] = gram[:, b, a] = tri[b * (b + 1) // 2 + a]
+        tr = lambda a: None if a is None else a.transpose(0, 2, 1)
+        return tr(ws), tr(ks), gram, info
+
+    def node_cov_sites(self, nodes_a, nodes_b=None, schedule_tree=0):
+        """Posterior covariance between nodes that need not share a cluster, at every site of a univariate batch:
+        [n_sites, len(a), len(b)], entry [s, i, j] = Cov(a_i, b_j | data) at site s; nodes_b=None: nodes_a among themselves.
+        One column of posterior_cov_sites_ per in-scope node of b, node_cov's rule for the cluster that holds a node.  NaN for
+        a node whose trait is out of scope and at a site whose info is not 0 -- it does not raise: one bad site must not hide
+        the others."""
+        ent = self._node_entries("node_cov_sites")
+        nodes_a = list(nodes_a)
+        nodes_b = nodes_a if nodes_b is None else list(nodes_b)
+        for v in nodes_a + nodes_b:
+            if v not in ent:
+                raise ValueError(f"no cluster holds node {v!r}")
+        size = int(self._lib.pgbp_sample_size(self._eng))
+        cols = [(j, int(ent[v][2][0])) for j, v in enumerate(nodes_b) if ent[v][2][0] >= 0]
+        out = np.full((self.n_sites, len(nodes_a), len(nodes_b)), np.nan)
+        if not cols or not nodes_a:
+            return out
+        c = np.zeros((len(cols), size))
+        c[np.arange(len(cols)), [e for _, e in cols]] = 1.0
+        _, k, _, _ = self.posterior_cov_sites_(c, schedule_tree, want_w=False, want_gram=False)
+        for i, v in enumerate(nodes_a):
+            ea = int(ent[v][2][0])
+            if ea >= 0:
+                for q, (j, _) in enumerate(cols):
+                    out[:, i, j] = k[q, :, ea]
+        return out
+
+    def functional_moments_sites(self, weights, schedule_tree=0):
+        """Posterior mean [n_sites, q] and covariance [n_sites, q, q] of the q linear functionals sum_v W_v x_v at every site
+        of a univariate batch; weights: {node label: W_v [q] or [q, 1]}.  The covariance is the device's gram of
+        posterior_cov_sites_ alone (no table is fetched), the mean comes from moments_sites_ without the covariance.  A
+        non-zero weight on a trait out of scope is refused, as functional_moments does; a site whose info is not 0 is NaN."""
+        ent = self._node_entries("functional_moments_sites")
+        nodes = list(weights)
+        size = int(self._lib.pgbp_sample_size(self._eng))
+        W = [np.asarray(weights[v], dtype=np.float64).reshape(-1, 1) for v in nodes]
+        q = W[0].shape[0] if W else 0
+        c = np.zeros((q, size))
+        for v, Wv in zip(nodes, W):
+            if v not in ent:
+                raise ValueError(f"no cluster holds node {v!r}")
+            e = ent[v][2]
+            if Wv.shape != (q, len(e)):
+                raise ValueError(f"the weights of node {v!r} have shape {Wv.shape}, expected {(q, len(e))}")
+            if np.any(Wv[:, e < 0] != 0.0):
+                raise ValueError(f"node {v!r}: weight on a trait that is out of scope")
+            c[:, e[e >= 0]] += Wv[:, e >= 0]
+        ns = self.n_sites
+        if q == 0:
+            return np.zeros((ns, 0)), np.zeros((ns, 0, 0))
+        _, _, gram, _ = self.posterior_cov_sites_(c, schedule_tree, want_w=False, want_k=False)
+        held = [v for v in nodes if ent[v][1][0] >= 0]
+        clusters = sorted({ent[v][0] for v in held})
+        mom = dict(zip(clusters, self.moments_sites_(clusters, cov=False))) if clusters else {}
+        mean = np.zeros((ns, q))
+        for v, Wv in zip(nodes, W):
+            ci, pos, _ = ent[v]
+            if pos[0] >= 0:
+                with np.errstate(invalid="ignore"):   # (a failed site: Inf or NaN times a zero weight; NaN below)
+                    mean = mean + mom[ci][0][:, pos[0]][:, None] * Wv[:, 0][None, :]
+        return np.where(np.isnan(gram[:, np.arange(q), np.arange(q)]), np.nan, mean), gram
+
     def impute_sites_lg(self):
         """pgbp_lg_impute_sites on the current beliefs: impute_lg(all_sites=True) for a univariate batch on the thread-per-site
         kernels (the conditions of gradient_sites_lg), lanes = sites, nothing converted.  Same keys and [site, tip, ...]

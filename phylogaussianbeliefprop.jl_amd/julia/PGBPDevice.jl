@@ -359,6 +359,31 @@ function sample_posterior_sites(o::DeviceClusterGraphBelief, nsites::Integer, nd
 end
 
 """
+    posterior_cov_sites(obj, nsites, c; tree = 1, want_w = true, want_k = true, want_gram = true) -> (w, k, gram, info)
+
+`posterior_cov` for every site of a univariate batch on the thread-per-site kernels (pgbp_posterior_cov_sites), lanes = sites.
+`c[i, a]`: the weight of column `a` on entry `i` of `sample_posterior!`'s layout, shared by the sites.  `w[s, i, a]` = A'c and
+`k[s, i, a]` = Cov(x_i, c_a'x | data) at site `s`; `gram[s, q]`, `q` over the upper triangle in column order (G00, G01, G11,
+...), = Cov(c_a'x, c_b'x | data), folded on the device -- with `gram` alone no table of size x sites is moved.  An output that
+is not wanted is `nothing`.  `info[s]`: 0, or the 1-based index of the first cluster in preorder whose conditional precision is
+not positive definite (that site is NaN).  `tree`: 1-based index into the schedule that was set.  Untested: no Julia on the test
+machines.
+"""
+function posterior_cov_sites(o::DeviceClusterGraphBelief, nsites::Integer, c::Matrix{Float64}; tree::Integer = 1,
+                             want_w::Bool = true, want_k::Bool = true, want_gram::Bool = true)
+    size = sample_size(o)
+    Base.size(c, 1) == size || error("c has $(Base.size(c, 1)) rows, expected $size")
+    ncols = Base.size(c, 2)
+    w = want_w ? zeros(nsites, max(size, 1), max(ncols, 1)) : nothing
+    k = want_k ? zeros(nsites, max(size, 1), max(ncols, 1)) : nothing
+    gram = want_gram ? zeros(nsites, max(ncols * (ncols + 1) ÷ 2, 1)) : nothing
+    info = zeros(Int32, nsites)
+    ptr(a) = a === nothing ? Ptr{Float64}(C_NULL) : pointer(a)
+    GC.@preserve w k gram check(o.handle, @ccall LIB.pgbp_posterior_cov_sites(o.handle::Ptr{Cvoid}, Int32(tree - 1)::Int32, Int32(0)::Int32, Int32(nsites)::Int32, Int32(ncols)::Int32, c::Ptr{Float64}, ptr(w)::Ptr{Float64}, ptr(k)::Ptr{Float64}, ptr(gram)::Ptr{Float64}, info::Ptr{Int32})::Cint)
+    return (w, k, gram, info)
+end
+
+"""
     lg_impute_sites(obj, nsites) -> (mean, var, info)
 
 `lg_impute` for every site of a univariate batch on the thread-per-site kernels (pgbp_lg_impute_sites), lanes = sites, for the
