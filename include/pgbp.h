@@ -460,6 +460,8 @@ int pgbp_lg_gradient_noise(pgbp_engine* e, int32_t site_begin, int32_t site_end,
  * order: two calls return the same bytes, and a site's bytes do not depend on the site range it is asked in.  The call reads
  * the beliefs in the layout they are in (site-minor from 64 sites on) and converts nothing: pgbp_layout is the same before and
  * after.  Shared and per-site parameters, the shifts and the tip noise in force are read as pgbp_lg_gradient reads them.
+ * The partial sums of a chunk of sites at a time (whole workgroups of 256 sites) are bounded by
+ * pgbp_sites_sweep_scratch_limit, 256 MB unless it is set; the bytes do not depend on the chunks.
  *   info[site]: 0, or the 1-based index of a cluster that is not positive definite (or whose family has a variance that is
  *   not positive) at that site: the site's outputs are then NaN, every other site is unaffected.
  * Values agree with pgbp_lg_gradient to rounding (the closed forms add in another order), not to the byte. */

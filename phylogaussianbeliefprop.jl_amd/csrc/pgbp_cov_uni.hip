@@ -22,14 +22,13 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <chrono>
 #include <cmath>
 #include <string>
 #include <vector>
 
 #include "pgbp_devmem.hpp"
 #include "pgbp_fam_uni_dev.hpp"
-#include "pgbp_fam_uni_host.hpp"
+#include "pgbp_sites_host.hpp"
 #include "pgbp_kernels.hpp"
 #include "pgbp_post_uni_dev.hpp"
 #include "pgbp_sample_plan.hpp"
@@ -54,7 +53,7 @@ __device__ __forceinline__ double cov_uni_gather(const double* __restrict__ c, c
 // c: [nc][size]; x: [nc][size][row] of this chunk; start[e] .. start[e + 1]: the entries in `src` whose t entry e gathers;
 // bad[site]: not 0 where the site is NaN
 template <bool SM>
-__global__ __launch_bounds__(256) void cov_uni_adjoint(PostUniArgs A, const SampItem* __restrict__ items, int n_items,
+__global__ __launch_bounds__(256) void cov_uni_adjoint(SitesArgs A, const SampItem* __restrict__ items, int n_items,
                                                        const int32_t* __restrict__ idx, const int32_t* __restrict__ start,
                                                        const int32_t* __restrict__ src, const int32_t* __restrict__ bad, int nc,
                                                        int64_t size, const double* __restrict__ c, double* __restrict__ x) {
@@ -96,7 +95,7 @@ __global__ __launch_bounds__(256) void cov_uni_adjoint(PostUniArgs A, const Samp
 
 // One preorder level of k = A w: post_uni_apply without its offset and with w for z.  w, k: [nc][size][row] of this chunk
 template <bool SM>
-__global__ __launch_bounds__(256) void cov_uni_forward(PostUniArgs A, const SampItem* __restrict__ items, int n_items,
+__global__ __launch_bounds__(256) void cov_uni_forward(SitesArgs A, const SampItem* __restrict__ items, int n_items,
                                                        const int32_t* __restrict__ idx, const int32_t* __restrict__ bad, int nc,
                                                        int64_t size, const double* __restrict__ w, double* __restrict__ k) {
 #pragma clang fp contract(off)
@@ -194,8 +193,8 @@ static int posterior_cov_sites(pgbp_engine* e, int32_t tree, int32_t site_begin,
                                double* w, double* k, double* gram, int32_t* info, double* ms) {
   if (!e) return PGBP_ERR_INVALID;
   const char* fn = "pgbp_posterior_cov_sites";
-  FamUniCall fc{};
-  int rc = fam_uni_accept(e, fn, "pgbp_posterior_cov", site_begin, site_end, nullptr, &fc);
+  SitesCall fc{};
+  int rc = sites_accept(e, fn, "pgbp_posterior_cov", site_begin, site_end, nullptr, &fc);
   if (rc) return rc;
   SampPlan sp;
   rc = sample_plan(e, std::string(fn) + ": ", tree, site_begin, site_end, n_cols, "n_cols", "column",
@@ -204,18 +203,8 @@ static int posterior_cov_sites(pgbp_engine* e, int32_t tree, int32_t site_begin,
   if (rc) return rc;
   const int ns = fc.ns;
   const int64_t size = sp.size;
-  // the clusters with variables by preorder rank (the validity pass), behind the items by level
-  std::vector<int32_t> at(sp.nc, -1);
-  for (size_t q = 0; q < sp.by_level.size(); ++q) at[sp.by_level[q].cluster] = (int32_t)q;
-  std::vector<SampItem> tab = sp.by_level;
-  std::vector<int32_t> pre_cluster;
-  for (int32_t cl : sp.order)
-    if (at[cl] >= 0) {
-      tab.push_back(sp.by_level[at[cl]]);
-      pre_cluster.push_back(cl);
-    }
-  const int n_items = (int)sp.by_level.size(), n_pre = (int)pre_cluster.size();
-  const int nvb = (n_pre + kFamUniBlock - 1) / kFamUniBlock;
+  const PostUniPre pre = post_uni_pre(sp);
+  const int nvb = pre.nvb;
   const int ngb = (int)((size + kFamUniBlock - 1) / kFamUniBlock);
   const int np = n_cols * (n_cols + 1) / 2;
   // the columns of a chunk: with gram all of them are resident together (refused when one workgroup's sites do not fit); without,
@@ -254,8 +243,8 @@ static int posterior_cov_sites(pgbp_engine* e, int32_t tree, int32_t site_begin,
     int32_t* src = start + size + 1;
     auto each = [&](auto&& f) {
       for (int ch = 0; ch < sp.nc; ++ch) {
-        if (at[ch] < 0) continue;
-        const SampItem& it = sp.by_level[at[ch]];   // (the root has no S)
+        if (pre.at[ch] < 0) continue;
+        const SampItem& it = sp.by_level[pre.at[ch]];   // (the root has no S)
         for (int j = 0; j < it.m - it.r; ++j)
           f(it.px_off + sp.idx[it.perm + it.m + j], it.x_off + sp.idx[it.perm + it.r + j]);
       }
@@ -266,101 +255,68 @@ static int posterior_cov_sites(pgbp_engine* e, int32_t tree, int32_t site_begin,
     for (int64_t q = size; q > 0; --q) start[q] = start[q - 1];                         // (... which is where the next one begins)
     start[0] = 0;
   }
-  const hipStream_t st = fc.v.st;
   std::vector<int32_t> rank(ns, 0);
   DevBuf<SampItem> d_tab;
   DevBuf<int32_t> d_idx, d_pfirst, d_rank;
   DevBuf<double> d_c, d_x, d_k, d_part, d_gram;
   const size_t table = (size_t)cchunk * size * chunk;
-  hipError_t herr = (hipError_t)d_tab.alloc(tab.size());
-  if (herr == hipSuccess) herr = (hipError_t)d_idx.alloc(sp.idx.size());
-  if (herr == hipSuccess) herr = (hipError_t)d_pfirst.alloc((size_t)nvb * chunk);
-  if (herr == hipSuccess) herr = (hipError_t)d_rank.alloc((size_t)ns);
-  if (herr == hipSuccess) herr = (hipError_t)d_c.alloc((size_t)n_cols * size);
-  if (herr == hipSuccess) herr = (hipError_t)d_x.alloc(table);
-  if (herr == hipSuccess && k) herr = (hipError_t)d_k.alloc(table);
-  if (herr == hipSuccess && gram) herr = (hipError_t)d_part.alloc((size_t)ngb * np * chunk);
-  if (herr == hipSuccess && gram) herr = (hipError_t)d_gram.alloc((size_t)np * chunk);
-  if (herr == hipSuccess) herr = hipMemcpyAsync(d_tab.get(), tab.data(), sizeof(SampItem) * tab.size(), hipMemcpyHostToDevice, st);
-  if (herr == hipSuccess) herr = hipMemcpyAsync(d_idx.get(), sp.idx.data(), sizeof(int32_t) * sp.idx.size(), hipMemcpyHostToDevice, st);
-  if (herr == hipSuccess) herr = hipMemcpyAsync(d_c.get(), c, sizeof(double) * (size_t)n_cols * size, hipMemcpyHostToDevice, st);
-  if (herr != hipSuccess) {
-    (void)hipStreamSynchronize(st);   // (the uploads read this call's locals)
-    return engine_fail(e, PGBP_ERR_HIP, std::string(fn) + " (scratch): " + hipGetErrorString(herr));
-  }
-  (void)hipGetLastError();   // (an error an earlier asynchronous call left behind is that call's to report)
-  auto t_last = std::chrono::steady_clock::now();
-  auto phase = [&](int q) {   // timed variant only
-    if (!ms) return;
-    const hipError_t perr = hipStreamSynchronize(st);
-    if (herr == hipSuccess) herr = perr;
-    const auto now = std::chrono::steady_clock::now();
-    if (q >= 0) ms[q] += std::chrono::duration<double, std::milli>(now - t_last).count();
-    t_last = now;
-  };
-  if (ms) std::fill(ms, ms + 5, 0.0);
-  phase(-1);
+  SitesScratch S(e, fn, fc.v.st);
+  S.alloc(d_tab, pre.tab.size());
+  S.alloc(d_idx, sp.idx.size());
+  S.alloc(d_pfirst, (size_t)nvb * chunk);
+  S.alloc(d_rank, ns);
+  S.alloc(d_c, (size_t)n_cols * size);
+  S.alloc(d_x, table);
+  S.alloc(d_k, table, k != nullptr);
+  S.alloc(d_part, (size_t)ngb * np * chunk, gram != nullptr);
+  S.alloc(d_gram, (size_t)np * chunk, gram != nullptr);
+  S.upload(d_tab, pre.tab.data(), pre.tab.size());
+  S.upload(d_idx, sp.idx.data(), sp.idx.size());
+  S.upload(d_c, c, (size_t)n_cols * size);
+  if ((rc = S.ready())) return rc;
+  SitesClock phase(S, ms, 5);
   const int32_t* d_start = d_idx.get() + start0;
   const int32_t* d_src = d_start + size + 1;
   const int n_levels = (int)sp.level_off.size() - 1;
-  for (int s0 = 0; herr == hipSuccess && s0 < ns; s0 += chunk) {
+  for (int s0 = 0; S.ok() && s0 < ns; s0 += chunk) {
     const int nn = std::min(chunk, ns - s0);
-    const PostUniArgs A{fc.U.pool, fc.U.stride, fc.U.off, fc.U.bdim, site_begin + s0, nn, (int64_t)chunk};
+    const SitesArgs A = sites_args(fc, site_begin + s0, nn, chunk);
     const dim3 gs((nn + 255) / 256);
-    if (fc.U.sm)
-      hipLaunchKernelGGL(post_uni_valid<true>, dim3(gs.x, nvb), dim3(256), 0, st, A, d_tab.get() + n_items, n_pre, d_idx.get(), d_pfirst.get());
-    else
-      hipLaunchKernelGGL(post_uni_valid<false>, dim3(gs.x, nvb), dim3(256), 0, st, A, d_tab.get() + n_items, n_pre, d_idx.get(), d_pfirst.get());
-    hipLaunchKernelGGL(post_uni_first, gs, dim3(256), 0, st, d_pfirst.get(), nvb, nn, (int64_t)chunk, d_rank.get(), s0);
-    herr = hipGetLastError();
+    post_uni_validity(S, fc.U.sm, A, pre, d_tab.get(), d_idx.get(), d_pfirst.get(), d_rank.get(), s0);
     phase(0);
-    for (int c0 = 0; herr == hipSuccess && c0 < n_cols; c0 += cchunk) {
+    for (int c0 = 0; S.ok() && c0 < n_cols; c0 += cchunk) {
       const int ncol = std::min(cchunk, n_cols - c0);
       const int64_t rows = (int64_t)ncol * size;
       const double* cc = d_c.get() + (size_t)c0 * size;
       for (int l = n_levels - 1; l >= 0; --l) {
         const int ni = sp.level_off[l + 1] - sp.level_off[l];
-        const dim3 grid(gs.x, std::min(ni, 65535));
-        if (fc.U.sm)
-          hipLaunchKernelGGL(cov_uni_adjoint<true>, grid, dim3(256), 0, st, A, d_tab.get() + sp.level_off[l], ni, d_idx.get(), d_start,
-                             d_src, d_rank.get() + s0, ncol, size, cc, d_x.get());
-        else
-          hipLaunchKernelGGL(cov_uni_adjoint<false>, grid, dim3(256), 0, st, A, d_tab.get() + sp.level_off[l], ni, d_idx.get(), d_start,
-                             d_src, d_rank.get() + s0, ncol, size, cc, d_x.get());
+        PGBP_SITES_LAUNCH(S, fc.U.sm, cov_uni_adjoint, dim3(gs.x, std::min(ni, 65535)), A, d_tab.get() + sp.level_off[l], ni,
+                          d_idx.get(), d_start, d_src, d_rank.get() + s0, ncol, size, cc, d_x.get());
       }
-      herr = hipGetLastError();
+      S.check();
       phase(1);
-      if (herr == hipSuccess && gram) {
-        hipLaunchKernelGGL(cov_uni_gram, dim3(gs.x, ngb), dim3(256), 0, st, d_x.get(), ncol, size, nn, (int64_t)chunk, d_part.get());
-        hipLaunchKernelGGL(cov_uni_fold, dim3(gs.x, std::min(np, 65535)), dim3(256), 0, st, d_part.get(), ngb, np, nn, (int64_t)chunk,
-                           d_gram.get());
-        herr = hipGetLastError();
+      if (gram) {
+        S.launch(cov_uni_gram, dim3(gs.x, ngb), d_x.get(), ncol, size, nn, (int64_t)chunk, d_part.get());
+        S.launch(cov_uni_fold, dim3(gs.x, std::min(np, 65535)), d_part.get(), ngb, np, nn, (int64_t)chunk, d_gram.get());
+        S.check();
       }
       phase(2);
-      for (int l = 0; k && herr == hipSuccess && l < n_levels; ++l) {
+      for (int l = 0; k && l < n_levels; ++l) {
         const int ni = sp.level_off[l + 1] - sp.level_off[l];
-        const dim3 grid(gs.x, std::min(ni, 65535));
-        if (fc.U.sm)
-          hipLaunchKernelGGL(cov_uni_forward<true>, grid, dim3(256), 0, st, A, d_tab.get() + sp.level_off[l], ni, d_idx.get(),
-                             d_rank.get() + s0, ncol, size, d_x.get(), d_k.get());
-        else
-          hipLaunchKernelGGL(cov_uni_forward<false>, grid, dim3(256), 0, st, A, d_tab.get() + sp.level_off[l], ni, d_idx.get(),
-                             d_rank.get() + s0, ncol, size, d_x.get(), d_k.get());
+        PGBP_SITES_LAUNCH(S, fc.U.sm, cov_uni_forward, dim3(gs.x, std::min(ni, 65535)), A, d_tab.get() + sp.level_off[l], ni,
+                          d_idx.get(), d_rank.get() + s0, ncol, size, d_x.get(), d_k.get());
       }
-      if (herr == hipSuccess) herr = hipGetLastError();
+      S.check();
       phase(3);
-      if (herr == hipSuccess && w) herr = fam_uni_copy(w + (size_t)c0 * size * ns, ns, s0, d_x.get(), chunk, nn, rows, st);
-      if (herr == hipSuccess && k) herr = fam_uni_copy(k + (size_t)c0 * size * ns, ns, s0, d_k.get(), chunk, nn, rows, st);
-      if (herr == hipSuccess && gram) herr = fam_uni_copy(gram, ns, s0, d_gram.get(), chunk, nn, np, st);
+      S.rows(w ? w + (size_t)c0 * size * ns : nullptr, ns, s0, d_x.get(), chunk, nn, rows);
+      S.rows(k ? k + (size_t)c0 * size * ns : nullptr, ns, s0, d_k.get(), chunk, nn, rows);
+      S.rows(gram, ns, s0, d_gram.get(), chunk, nn, np);
       phase(4);
     }
   }
-  if (herr == hipSuccess) herr = hipMemcpyAsync(rank.data(), d_rank.get(), sizeof(int32_t) * (size_t)ns, hipMemcpyDeviceToHost, st);
-  const hipError_t serr = hipStreamSynchronize(st);   // (also when something failed: the uploads read this call's locals)
-  if (herr == hipSuccess) herr = serr;
-  if (herr != hipSuccess) return engine_fail(e, PGBP_ERR_HIP, std::string(fn) + ": " + hipGetErrorString(herr));
-  if (info)
-    for (int s = 0; s < ns; ++s) info[s] = rank[s] ? pre_cluster[rank[s] - 1] + 1 : 0;
+  S.download(rank.data(), d_rank.get(), ns);
+  if ((rc = S.finish())) return rc;
+  post_uni_info(pre, rank, info);
   return PGBP_OK;
 }
 

@@ -28,7 +28,7 @@
 
 #include "pgbp_devmem.hpp"
 #include "pgbp_fam_uni_dev.hpp"
-#include "pgbp_fam_uni_host.hpp"
+#include "pgbp_sites_host.hpp"
 #include "pgbp_kernels.hpp"
 #include "pgbp_lgmodel.hpp"
 
@@ -36,22 +36,10 @@ namespace pgbp {
 
 #define PGBP_FAM_UNI_LOG2PI 1.8378770664093454835606594728112
 
-// what every kernel below takes of the engine and of the call
-struct FamUniArgs {
-  const double* pool;
-  int64_t stride;
-  const int64_t* off;
-  const int32_t* bdim;
-  const int32_t* fam_cluster;
-  int64_t data_row_len;
-  int site0, n_sites;
-  int64_t row;   // the row length of the scratch (the chunk)
-};
-
 // jump, lr, hinf: [n_fam][row] (any may be null); pbest / pfam: [blocks][row], the largest lr of the block's families that
 // have an edge, are identified and whose lr is finite, and the first family that has it (-inf, -1: none); pinfo: [blocks][row]
 template <bool SM>
-__global__ __launch_bounds__(256) void fam_uni_scan(FamUniArgs A, LgStatic F, LgParams M, LgShifts Sh, LgNoise Nz, int n_fam,
+__global__ __launch_bounds__(256) void fam_uni_scan(SitesArgs A, LgStatic F, LgParams M, LgShifts Sh, LgNoise Nz, int n_fam,
                                                     double min_info, double* __restrict__ jump, double* __restrict__ lr,
                                                     double* __restrict__ hinf, double* __restrict__ pbest,
                                                     int32_t* __restrict__ pfam, int32_t* __restrict__ pinfo) {
@@ -101,7 +89,7 @@ __global__ __launch_bounds__(256) void fam_uni_scan(FamUniArgs A, LgStatic F, Lg
 
 // dlen, dgam: [n_fam][K][row], dshift: [n_fam][row] (any may be null); pinfo: [blocks][row]
 template <bool SM>
-__global__ __launch_bounds__(256) void fam_uni_edge(FamUniArgs A, LgStatic F, LgParams M, LgShifts Sh, LgNoise Nz, int n_fam,
+__global__ __launch_bounds__(256) void fam_uni_edge(SitesArgs A, LgStatic F, LgParams M, LgShifts Sh, LgNoise Nz, int n_fam,
                                                     double* __restrict__ dlen, double* __restrict__ dgam,
                                                     double* __restrict__ dshift, int32_t* __restrict__ pinfo) {
 #pragma clang fp contract(off)
@@ -149,7 +137,7 @@ __global__ __launch_bounds__(256) void fam_uni_edge(FamUniArgs A, LgStatic F, Lg
 // tip_fam[ti]: the family of tip ti.  mean, var (either may be null), lpd: [n_tip][row]; info: [n_tip][row] (may be null);
 // psum: [blocks][row], the block's lpd added in tip order
 template <bool SM>
-__global__ __launch_bounds__(256) void fam_uni_loo(FamUniArgs A, LgStatic F, LgParams M, LgShifts Sh, LgNoise Nz,
+__global__ __launch_bounds__(256) void fam_uni_loo(SitesArgs A, LgStatic F, LgParams M, LgShifts Sh, LgNoise Nz,
                                                    const int32_t* __restrict__ tip_fam, int n_tip, double* __restrict__ mean,
                                                    double* __restrict__ var, double* __restrict__ lpd,
                                                    int32_t* __restrict__ info, double* __restrict__ psum) {
@@ -223,14 +211,10 @@ __global__ __launch_bounds__(256) void fam_uni_fold(const int32_t* __restrict__ 
   }
 }
 
-// (pgbp_fam_uni_host.hpp: the acceptance checks, the chunks and the copies, shared with pgbp_post_uni.hip)
+// (pgbp_sites_host.hpp: the host frame of every lanes-are-sites call)
 std::atomic<int64_t> g_fam_uni_limit{(int64_t)32 << 20};
 
 namespace {
-
-FamUniArgs fam_uni_args(const FamUniCall& c, const int32_t* d_fcl, int site0, int n, int chunk) {
-  return FamUniArgs{c.U.pool, c.U.stride, c.U.off, c.U.bdim, d_fcl, sm_row(c.v.plan->n_sites), site0, n, (int64_t)chunk};
-}
 
 // every row of a failed site: NaN
 void fam_uni_nan(double* out, int64_t rows, int ns, int s) {
@@ -250,16 +234,15 @@ extern "C" int pgbp_lg_shift_scan_sites(pgbp_engine* e, int32_t site_begin, int3
                                         double* lr, double* information, double* top_lr, int32_t* top_family, int32_t* info) {
   if (!e) return PGBP_ERR_INVALID;
   const char* fn = "pgbp_lg_shift_scan_sites";
-  FamUniCall c{};
+  SitesCall c{};
   const bool none = !jump && !lr && !information && !top_lr && !top_family;
-  int rc = fam_uni_accept(e, fn, "pgbp_lg_shift_scan", site_begin, site_end, none ? "no output buffer" : nullptr, &c);
+  int rc = sites_accept(e, fn, "pgbp_lg_shift_scan", site_begin, site_end, none ? "no output buffer" : nullptr, &c);
   if (rc) return rc;
   if (!(min_info >= 0.0 && min_info < 1.0))
     return engine_fail(e, PGBP_ERR_INVALID, std::string(fn) + ": min_info = " + std::to_string(min_info) + " is not in [0, 1)");
   const LgModel* L = c.L;
   const int ns = c.ns, nf = L->T.n_families;
   if (ns == 0) return PGBP_OK;
-  const hipStream_t st = c.v.st;
   const int nfb = std::max(1, (nf + kFamUniBlock - 1) / kFamUniBlock);
   const bool top = top_lr || top_family;
   const int n_tab = (jump ? 1 : 0) + (lr ? 1 : 0) + (information ? 1 : 0);
@@ -268,44 +251,36 @@ extern "C" int pgbp_lg_shift_scan_sites(pgbp_engine* e, int32_t site_begin, int3
   DevBuf<int32_t> d_fcl, d_pinfo, d_pfam, d_info, d_topf;
   DevBuf<double> d_jump, d_lr, d_hinf, d_pbest, d_top;
   const size_t tab = (size_t)nf * chunk, blk = (size_t)nfb * chunk;
-  hipError_t herr = (hipError_t)d_fcl.alloc(std::max(1, nf));
-  if (herr == hipSuccess && jump) herr = (hipError_t)d_jump.alloc(tab);
-  if (herr == hipSuccess && lr) herr = (hipError_t)d_lr.alloc(tab);
-  if (herr == hipSuccess && information) herr = (hipError_t)d_hinf.alloc(tab);
-  if (herr == hipSuccess) herr = (hipError_t)d_pinfo.alloc(blk);
-  if (herr == hipSuccess && top) herr = (hipError_t)d_pbest.alloc(blk);
-  if (herr == hipSuccess && top) herr = (hipError_t)d_pfam.alloc(blk);
-  if (herr == hipSuccess) herr = (hipError_t)d_info.alloc((size_t)ns);
-  if (herr == hipSuccess && top) herr = (hipError_t)d_top.alloc((size_t)ns);
-  if (herr == hipSuccess && top) herr = (hipError_t)d_topf.alloc((size_t)ns);
-  if (herr == hipSuccess && nf > 0)
-    herr = hipMemcpyAsync(d_fcl.get(), L->T.cluster.data(), sizeof(int32_t) * nf, hipMemcpyHostToDevice, st);
-  if (herr != hipSuccess) return engine_fail(e, PGBP_ERR_HIP, std::string(fn) + " (scratch): " + hipGetErrorString(herr));
-  (void)hipGetLastError();   // (an error an earlier asynchronous call left behind is that call's to report)
-  for (int s0 = 0; herr == hipSuccess && s0 < ns; s0 += chunk) {
+  SitesScratch S(e, fn, c.v.st);
+  S.alloc(d_fcl, std::max(1, nf));
+  S.alloc(d_jump, tab, jump != nullptr);
+  S.alloc(d_lr, tab, lr != nullptr);
+  S.alloc(d_hinf, tab, information != nullptr);
+  S.alloc(d_pinfo, blk);
+  S.alloc(d_pbest, blk, top);
+  S.alloc(d_pfam, blk, top);
+  S.alloc(d_info, ns);
+  S.alloc(d_top, ns, top);
+  S.alloc(d_topf, ns, top);
+  S.upload(d_fcl, L->T.cluster.data(), nf);
+  if ((rc = S.ready())) return rc;
+  for (int s0 = 0; S.ok() && s0 < ns; s0 += chunk) {
     const int n = std::min(chunk, ns - s0);
-    const FamUniArgs A = fam_uni_args(c, d_fcl.get(), site_begin + s0, n, chunk);
+    const SitesArgs A = sites_args(c, site_begin + s0, n, chunk, d_fcl.get());
     const dim3 grid((n + 255) / 256, nfb);
-    if (c.U.sm)
-      hipLaunchKernelGGL(fam_uni_scan<true>, grid, dim3(256), 0, st, A, L->F, L->M, L->Sh, L->Nz, nf, min_info, d_jump.get(),
-                         d_lr.get(), d_hinf.get(), d_pbest.get(), d_pfam.get(), d_pinfo.get());
-    else
-      hipLaunchKernelGGL(fam_uni_scan<false>, grid, dim3(256), 0, st, A, L->F, L->M, L->Sh, L->Nz, nf, min_info, d_jump.get(),
-                         d_lr.get(), d_hinf.get(), d_pbest.get(), d_pfam.get(), d_pinfo.get());
-    hipLaunchKernelGGL(fam_uni_fold, dim3((n + 255) / 256), dim3(256), 0, st, d_pinfo.get(), d_pbest.get(), d_pfam.get(),
-                       (const double*)nullptr, nfb, n, (int64_t)chunk, d_info.get(), d_top.get(), d_topf.get(), (double*)nullptr, s0);
-    herr = hipGetLastError();
-    if (herr == hipSuccess) herr = fam_uni_copy(jump, ns, s0, d_jump.get(), chunk, n, nf, st);
-    if (herr == hipSuccess) herr = fam_uni_copy(lr, ns, s0, d_lr.get(), chunk, n, nf, st);
-    if (herr == hipSuccess) herr = fam_uni_copy(information, ns, s0, d_hinf.get(), chunk, n, nf, st);
+    PGBP_SITES_LAUNCH(S, c.U.sm, fam_uni_scan, grid, A, L->F, L->M, L->Sh, L->Nz, nf, min_info, d_jump.get(), d_lr.get(),
+                      d_hinf.get(), d_pbest.get(), d_pfam.get(), d_pinfo.get());
+    S.launch(fam_uni_fold, dim3(grid.x), d_pinfo.get(), d_pbest.get(), d_pfam.get(), nullptr, nfb, n, (int64_t)chunk, d_info.get(),
+             d_top.get(), d_topf.get(), nullptr, s0);
+    S.check();
+    S.rows(jump, ns, s0, d_jump.get(), chunk, n, nf);
+    S.rows(lr, ns, s0, d_lr.get(), chunk, n, nf);
+    S.rows(information, ns, s0, d_hinf.get(), chunk, n, nf);
   }
-  if (herr == hipSuccess) herr = hipMemcpyAsync(inf.data(), d_info.get(), sizeof(int32_t) * (size_t)ns, hipMemcpyDeviceToHost, st);
-  if (herr == hipSuccess && top_lr) herr = hipMemcpyAsync(top_lr, d_top.get(), sizeof(double) * (size_t)ns, hipMemcpyDeviceToHost, st);
-  if (herr == hipSuccess && top_family)
-    herr = hipMemcpyAsync(top_family, d_topf.get(), sizeof(int32_t) * (size_t)ns, hipMemcpyDeviceToHost, st);
-  const hipError_t serr = hipStreamSynchronize(st);
-  if (herr == hipSuccess) herr = serr;
-  if (herr != hipSuccess) return engine_fail(e, PGBP_ERR_HIP, std::string(fn) + ": " + hipGetErrorString(herr));
+  S.download(inf.data(), d_info.get(), ns);
+  S.download(top_lr, d_top.get(), ns);
+  S.download(top_family, d_topf.get(), ns);
+  if ((rc = S.finish())) return rc;
   for (int s = 0; s < ns; ++s) {
     if (info) info[s] = inf[s];
     if (!inf[s]) continue;   // a site with a cluster that is not positive definite: NaN throughout
@@ -320,51 +295,42 @@ extern "C" int pgbp_lg_edge_gradient_sites(pgbp_engine* e, int32_t site_begin, i
                                            double* dshift, int32_t* info) {
   if (!e) return PGBP_ERR_INVALID;
   const char* fn = "pgbp_lg_edge_gradient_sites";
-  FamUniCall c{};
+  SitesCall c{};
   const bool none = !dlength && !dgamma && !dshift;
-  int rc = fam_uni_accept(e, fn, "pgbp_lg_edge_gradient", site_begin, site_end, none ? "no output buffer" : nullptr, &c);
+  int rc = sites_accept(e, fn, "pgbp_lg_edge_gradient", site_begin, site_end, none ? "no output buffer" : nullptr, &c);
   if (rc) return rc;
   const LgModel* L = c.L;
   const int ns = c.ns, nf = L->T.n_families, K = L->F.K;
   if (ns == 0) return PGBP_OK;
-  const hipStream_t st = c.v.st;
   const int nfb = std::max(1, (nf + kFamUniBlock - 1) / kFamUniBlock);
   const int chunk = fam_uni_chunk(ns, (int64_t)nf * ((dlength ? K : 0) + (dgamma ? K : 0) + (dshift ? 1 : 0)) + nfb);
   std::vector<int32_t> inf(ns, 0);
   DevBuf<int32_t> d_fcl, d_pinfo, d_info;
   DevBuf<double> d_len, d_gam, d_shift;
-  hipError_t herr = (hipError_t)d_fcl.alloc(std::max(1, nf));
-  if (herr == hipSuccess && dlength) herr = (hipError_t)d_len.alloc((size_t)nf * K * chunk);
-  if (herr == hipSuccess && dgamma) herr = (hipError_t)d_gam.alloc((size_t)nf * K * chunk);
-  if (herr == hipSuccess && dshift) herr = (hipError_t)d_shift.alloc((size_t)nf * chunk);
-  if (herr == hipSuccess) herr = (hipError_t)d_pinfo.alloc((size_t)nfb * chunk);
-  if (herr == hipSuccess) herr = (hipError_t)d_info.alloc((size_t)ns);
-  if (herr == hipSuccess && nf > 0)
-    herr = hipMemcpyAsync(d_fcl.get(), L->T.cluster.data(), sizeof(int32_t) * nf, hipMemcpyHostToDevice, st);
-  if (herr != hipSuccess) return engine_fail(e, PGBP_ERR_HIP, std::string(fn) + " (scratch): " + hipGetErrorString(herr));
-  (void)hipGetLastError();   // (an error an earlier asynchronous call left behind is that call's to report)
-  for (int s0 = 0; herr == hipSuccess && s0 < ns; s0 += chunk) {
+  SitesScratch S(e, fn, c.v.st);
+  S.alloc(d_fcl, std::max(1, nf));
+  S.alloc(d_len, (size_t)nf * K * chunk, dlength != nullptr);
+  S.alloc(d_gam, (size_t)nf * K * chunk, dgamma != nullptr);
+  S.alloc(d_shift, (size_t)nf * chunk, dshift != nullptr);
+  S.alloc(d_pinfo, (size_t)nfb * chunk);
+  S.alloc(d_info, ns);
+  S.upload(d_fcl, L->T.cluster.data(), nf);
+  if ((rc = S.ready())) return rc;
+  for (int s0 = 0; S.ok() && s0 < ns; s0 += chunk) {
     const int n = std::min(chunk, ns - s0);
-    const FamUniArgs A = fam_uni_args(c, d_fcl.get(), site_begin + s0, n, chunk);
+    const SitesArgs A = sites_args(c, site_begin + s0, n, chunk, d_fcl.get());
     const dim3 grid((n + 255) / 256, nfb);
-    if (c.U.sm)
-      hipLaunchKernelGGL(fam_uni_edge<true>, grid, dim3(256), 0, st, A, L->F, L->M, L->Sh, L->Nz, nf, d_len.get(), d_gam.get(),
-                         d_shift.get(), d_pinfo.get());
-    else
-      hipLaunchKernelGGL(fam_uni_edge<false>, grid, dim3(256), 0, st, A, L->F, L->M, L->Sh, L->Nz, nf, d_len.get(), d_gam.get(),
-                         d_shift.get(), d_pinfo.get());
-    hipLaunchKernelGGL(fam_uni_fold, dim3((n + 255) / 256), dim3(256), 0, st, d_pinfo.get(), (const double*)nullptr,
-                       (const int32_t*)nullptr, (const double*)nullptr, nfb, n, (int64_t)chunk, d_info.get(), (double*)nullptr,
-                       (int32_t*)nullptr, (double*)nullptr, s0);
-    herr = hipGetLastError();
-    if (herr == hipSuccess) herr = fam_uni_copy(dlength, ns, s0, d_len.get(), chunk, n, (int64_t)nf * K, st);
-    if (herr == hipSuccess) herr = fam_uni_copy(dgamma, ns, s0, d_gam.get(), chunk, n, (int64_t)nf * K, st);
-    if (herr == hipSuccess) herr = fam_uni_copy(dshift, ns, s0, d_shift.get(), chunk, n, nf, st);
+    PGBP_SITES_LAUNCH(S, c.U.sm, fam_uni_edge, grid, A, L->F, L->M, L->Sh, L->Nz, nf, d_len.get(), d_gam.get(), d_shift.get(),
+                      d_pinfo.get());
+    S.launch(fam_uni_fold, dim3(grid.x), d_pinfo.get(), nullptr, nullptr, nullptr, nfb, n, (int64_t)chunk, d_info.get(), nullptr,
+             nullptr, nullptr, s0);
+    S.check();
+    S.rows(dlength, ns, s0, d_len.get(), chunk, n, (int64_t)nf * K);
+    S.rows(dgamma, ns, s0, d_gam.get(), chunk, n, (int64_t)nf * K);
+    S.rows(dshift, ns, s0, d_shift.get(), chunk, n, nf);
   }
-  if (herr == hipSuccess) herr = hipMemcpyAsync(inf.data(), d_info.get(), sizeof(int32_t) * (size_t)ns, hipMemcpyDeviceToHost, st);
-  const hipError_t serr = hipStreamSynchronize(st);
-  if (herr == hipSuccess) herr = serr;
-  if (herr != hipSuccess) return engine_fail(e, PGBP_ERR_HIP, std::string(fn) + ": " + hipGetErrorString(herr));
+  S.download(inf.data(), d_info.get(), ns);
+  if ((rc = S.finish())) return rc;
   for (int s = 0; s < ns; ++s) {
     if (info) info[s] = inf[s];
     if (!inf[s]) continue;   // a site with a cluster that is not positive definite: every entry NaN
@@ -379,8 +345,8 @@ extern "C" int pgbp_lg_loo_sites(pgbp_engine* e, int32_t site_begin, int32_t sit
                                  double* total, int32_t* info) {
   if (!e) return PGBP_ERR_INVALID;
   const char* fn = "pgbp_lg_loo_sites";
-  FamUniCall c{};
-  int rc = fam_uni_accept(e, fn, "pgbp_lg_loo", site_begin, site_end, lpd ? nullptr : "no output buffer (lpd)", &c);
+  SitesCall c{};
+  int rc = sites_accept(e, fn, "pgbp_lg_loo", site_begin, site_end, lpd ? nullptr : "no output buffer (lpd)", &c);
   if (rc) return rc;
   const LgModel* L = c.L;
   const std::vector<int32_t> tips = L->T.loo_tips();   // the tip families, in table order
@@ -390,46 +356,37 @@ extern "C" int pgbp_lg_loo_sites(pgbp_engine* e, int32_t site_begin, int32_t sit
     if (total) std::fill(total, total + ns, 0.0);
     return PGBP_OK;
   }
-  const hipStream_t st = c.v.st;
   const int ntb = (nt + kFamUniBlock - 1) / kFamUniBlock;
   const int chunk = fam_uni_chunk(ns, (int64_t)nt * (1 + (mean ? 1 : 0) + (var ? 1 : 0) + (info ? 1 : 0)) + ntb);
   DevBuf<int32_t> d_fcl, d_tips, d_info;
   DevBuf<double> d_mean, d_var, d_lpd, d_psum, d_total;
   const size_t tab = (size_t)nt * chunk;
-  hipError_t herr = (hipError_t)d_fcl.alloc(std::max(1, nf));
-  if (herr == hipSuccess) herr = (hipError_t)d_tips.alloc(nt);
-  if (herr == hipSuccess && mean) herr = (hipError_t)d_mean.alloc(tab);
-  if (herr == hipSuccess && var) herr = (hipError_t)d_var.alloc(tab);
-  if (herr == hipSuccess) herr = (hipError_t)d_lpd.alloc(tab);
-  if (herr == hipSuccess && info) herr = (hipError_t)d_info.alloc(tab);
-  if (herr == hipSuccess) herr = (hipError_t)d_psum.alloc((size_t)ntb * chunk);
-  if (herr == hipSuccess) herr = (hipError_t)d_total.alloc((size_t)ns);
-  if (herr == hipSuccess) herr = hipMemcpyAsync(d_fcl.get(), L->T.cluster.data(), sizeof(int32_t) * nf, hipMemcpyHostToDevice, st);
-  if (herr == hipSuccess) herr = hipMemcpyAsync(d_tips.get(), tips.data(), sizeof(int32_t) * nt, hipMemcpyHostToDevice, st);
-  if (herr != hipSuccess) return engine_fail(e, PGBP_ERR_HIP, std::string(fn) + " (scratch): " + hipGetErrorString(herr));
-  (void)hipGetLastError();   // (an error an earlier asynchronous call left behind is that call's to report)
-  for (int s0 = 0; herr == hipSuccess && s0 < ns; s0 += chunk) {
+  SitesScratch S(e, fn, c.v.st);
+  S.alloc(d_fcl, std::max(1, nf));
+  S.alloc(d_tips, nt);
+  S.alloc(d_mean, tab, mean != nullptr);
+  S.alloc(d_var, tab, var != nullptr);
+  S.alloc(d_lpd, tab);
+  S.alloc(d_info, tab, info != nullptr);
+  S.alloc(d_psum, (size_t)ntb * chunk);
+  S.alloc(d_total, ns);
+  S.upload(d_fcl, L->T.cluster.data(), nf);
+  S.upload(d_tips, tips.data(), nt);
+  if ((rc = S.ready())) return rc;
+  for (int s0 = 0; S.ok() && s0 < ns; s0 += chunk) {
     const int n = std::min(chunk, ns - s0);
-    const FamUniArgs A = fam_uni_args(c, d_fcl.get(), site_begin + s0, n, chunk);
+    const SitesArgs A = sites_args(c, site_begin + s0, n, chunk, d_fcl.get());
     const dim3 grid((n + 255) / 256, ntb);
-    if (c.U.sm)
-      hipLaunchKernelGGL(fam_uni_loo<true>, grid, dim3(256), 0, st, A, L->F, L->M, L->Sh, L->Nz, d_tips.get(), nt, d_mean.get(),
-                         d_var.get(), d_lpd.get(), d_info.get(), d_psum.get());
-    else
-      hipLaunchKernelGGL(fam_uni_loo<false>, grid, dim3(256), 0, st, A, L->F, L->M, L->Sh, L->Nz, d_tips.get(), nt, d_mean.get(),
-                         d_var.get(), d_lpd.get(), d_info.get(), d_psum.get());
-    hipLaunchKernelGGL(fam_uni_fold, dim3((n + 255) / 256), dim3(256), 0, st, (const int32_t*)nullptr, (const double*)nullptr,
-                       (const int32_t*)nullptr, d_psum.get(), ntb, n, (int64_t)chunk, (int32_t*)nullptr, (double*)nullptr,
-                       (int32_t*)nullptr, d_total.get(), s0);
-    herr = hipGetLastError();
-    if (herr == hipSuccess) herr = fam_uni_copy(mean, ns, s0, d_mean.get(), chunk, n, nt, st);
-    if (herr == hipSuccess) herr = fam_uni_copy(var, ns, s0, d_var.get(), chunk, n, nt, st);
-    if (herr == hipSuccess) herr = fam_uni_copy(lpd, ns, s0, d_lpd.get(), chunk, n, nt, st);
-    if (herr == hipSuccess) herr = fam_uni_copy(info, ns, s0, d_info.get(), chunk, n, nt, st);
+    PGBP_SITES_LAUNCH(S, c.U.sm, fam_uni_loo, grid, A, L->F, L->M, L->Sh, L->Nz, d_tips.get(), nt, d_mean.get(), d_var.get(),
+                      d_lpd.get(), d_info.get(), d_psum.get());
+    S.launch(fam_uni_fold, dim3(grid.x), nullptr, nullptr, nullptr, d_psum.get(), ntb, n, (int64_t)chunk, nullptr, nullptr, nullptr,
+             d_total.get(), s0);
+    S.check();
+    S.rows(mean, ns, s0, d_mean.get(), chunk, n, nt);
+    S.rows(var, ns, s0, d_var.get(), chunk, n, nt);
+    S.rows(lpd, ns, s0, d_lpd.get(), chunk, n, nt);
+    S.rows(info, ns, s0, d_info.get(), chunk, n, nt);
   }
-  if (herr == hipSuccess && total) herr = hipMemcpyAsync(total, d_total.get(), sizeof(double) * (size_t)ns, hipMemcpyDeviceToHost, st);
-  const hipError_t serr = hipStreamSynchronize(st);
-  if (herr == hipSuccess) herr = serr;
-  if (herr != hipSuccess) return engine_fail(e, PGBP_ERR_HIP, std::string(fn) + ": " + hipGetErrorString(herr));
-  return PGBP_OK;
+  S.download(total, d_total.get(), ns);
+  return S.finish();
 }

@@ -6,8 +6,9 @@
 //     r = u_0 x_0 + u_1 x_1 + const - w with u_v the sum of the c_a that sit at variable v -- which gives u, the constant, V
 //     (with the tip noise E_f) and w (with the shifts), and per parent the coefficients and the parent's mean;
 //   * what all three sweeps form from them: e = E[r], Sigma u, C = u' Sigma u, j = 1 / V, g_w = j e.
-// Notation and frame of pgbp_grad_uni.hip (which keeps its own copy of the first two).  Arithmetic contract of
-// pgbp_fam_dev.hpp: every sum in a fixed index order, contraction off.
+// Notation and frame of pgbp_grad_uni.hip, which takes the moments from here and keeps its own pass over the parents: it adds
+// the alpha-derivative sums in the same loop, and a second pass would evaluate lg_coefs twice per edge.  Arithmetic contract
+// of pgbp_fam_dev.hpp: every sum in a fixed index order, contraction off.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -18,6 +19,19 @@ namespace pgbp {
 
 constexpr int kFamUniBlock = 64;   // families per thread (grid.y = blocks of them)
 constexpr int kFamUniNoInfo = 0x7fffffff;
+
+// what every lanes-are-sites kernel takes of the engine and of the call (sites_args of pgbp_sites_host.hpp fills it;
+// grad_uni_family takes its members as a flat list)
+struct SitesArgs {
+  const double* pool;
+  int64_t stride;
+  const int64_t* off;
+  const int32_t* bdim;
+  int site0, n_sites;
+  int64_t row;                  // the row length of the scratch (the chunk)
+  const int32_t* fam_cluster;   // the family sweeps only: the cluster of a family, and the row length of the site-minor data
+  int64_t data_row_len;
+};
 
 // element t of the belief at offset `off` for site `as`, in the layout the pool is in (UniView of pgbp_kernels.hpp)
 template <bool SM>

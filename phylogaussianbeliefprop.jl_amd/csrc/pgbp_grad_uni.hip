@@ -1,6 +1,6 @@
 // The gradient sweep of pgbp_grad.hip for univariate batches on a thread-per-site engine (pgbp_lg_gradient_sites of
 // include/pgbp.h): p = 1, every belief of at most 2 variables, at least 8 sites.  Lanes are sites: a workgroup is 256
-// consecutive sites, grid.y a block of kGradUniFamBlock consecutive families, a thread walks its block's families in index
+// consecutive sites, grid.y a block of kFamUniBlock consecutive families, a thread walks its block's families in index
 // order for its one site.  The family table is uniform across a wavefront (scalar loads); the belief entries and the tip data
 // are read as whole lines in the layout the pool is in (site-minor from 64 sites on, plain below: grad_uni_family<SM>), so the
 // call converts nothing and leaves the layout as it found it.
@@ -16,7 +16,8 @@
 // Reduction: each thread writes its block's partial sums to partial[family block][entry][site]; grad_uni_reduce adds the
 // blocks in index order.  No atomics, contraction off, every sum in a fixed order: the bytes of a site depend neither on the
 // call nor on the site range it came in.  A launch carries kGradUniRates rates in registers; a model with more rates is swept
-// once per group of rates (the scalar entries with the first).  The partials of a chunk of sites at a time (256 MB at most).
+// once per group of rates (the scalar entries with the first).  The partials of a chunk of sites at a time (256 MB at most,
+// whole workgroups: pgbp_sites_sweep_scratch_limit).  Host frame of pgbp_sites_host.hpp, moments of pgbp_fam_uni_dev.hpp.
 // A lane whose cluster or variance is not positive definite records the 1-based cluster index and adds nothing; there is no
 // barrier in either kernel, and no lane's store depends on another lane.
 #include <hip/hip_runtime.h>
@@ -27,24 +28,20 @@
 #include <vector>
 
 #include "pgbp_devmem.hpp"
-#include "pgbp_fam_dev.hpp"
+#include "pgbp_fam_uni_dev.hpp"
 #include "pgbp_kernels.hpp"
 #include "pgbp_lgmodel.hpp"
+#include "pgbp_sites_host.hpp"
 
 namespace pgbp {
 
-constexpr int kGradUniFamBlock = 64;   // families per thread (grid.y = blocks of them)
-constexpr int kGradUniRates = 4;       // rates a launch accumulates in registers
-constexpr int kGradUniNoInfo = 0x7fffffff;
+constexpr int kGradUniRates = 4;   // rates a launch accumulates in registers
 
 // entries of a site's gradient: [dR (n_rates) | dsigma_e | dmu | dtheta | dalpha]
 __host__ __device__ inline int grad_uni_entries(int nr) { return nr + 4; }
 
-template <bool SM>
-__device__ __forceinline__ double grad_uni_ld(const double* __restrict__ pool, int64_t stride, int64_t off, int t, int64_t as) {
-  return SM ? pool[(off + t) * stride + as] : pool[as * stride + off + t];
-}
-
+// partial: [blocks][entries][part_row], pinfo: [blocks][part_row] (written by the launch of the first rates, r0 == 0).  The
+// members of SitesArgs as a flat list: with the struct the kernel keeps its 129 VGPRs but spills 24 more SGPRs into them.
 template <bool SM>
 __global__ __launch_bounds__(256) void grad_uni_family(const double* __restrict__ pool, int64_t stride,
                                                        const int64_t* __restrict__ off, const int32_t* __restrict__ bdim,
@@ -64,41 +61,21 @@ __global__ __launch_bounds__(256) void grad_uni_family(const double* __restrict_
 #pragma unroll
   for (int i = 0; i < kGradUniRates; ++i) accR[i] = 0.0;
   double dsig = 0.0, dmu = 0.0, dth = 0.0, da = 0.0;
-  int bad = kGradUniNoInfo;
-  const int f0 = fb * kGradUniFamBlock, f1 = min(f0 + kGradUniFamBlock, n_fam);
+  int bad = kFamUniNoInfo;
+  const int f0 = fb * kFamUniBlock, f1 = min(f0 + kFamUniBlock, n_fam);
   for (int f = f0; f < f1; ++f) {
     const int np = F.n_parents[f], cpos = F.child_pos[f];
     // families the factor fill skips contribute nothing (and a root-prior family of a fixed root, which has no factor)
     if (F.child_mask && !(F.child_mask[f] & 1ull)) continue;
     if (np == 0 && cpos < 0) continue;
-    const int c = fam_cluster[f], m = bdim[c];
+    const int c = fam_cluster[f];
     bool any_scope = cpos >= 0;
     for (int k = 0; k < np; ++k) any_scope |= F.parent_pos[(size_t)f * K + k] >= 0;
-    // moments of the cluster: Sigma = J^-1 (PDMat(Symmetric(J)): the upper triangle), mean = Sigma h
-    double S00 = 0.0, S01 = 0.0, S11 = 0.0, m0 = 0.0, m1 = 0.0;
-    bool ok = true;
-    if (any_scope) {
-      const int64_t o = off[c];
-      if (m == 1) {
-        const double J = grad_uni_ld<SM>(pool, stride, o, 0, as), h = grad_uni_ld<SM>(pool, stride, o, 1, as);
-        ok = J > 0.0;
-        S00 = 1.0 / J;
-        m0 = h / J;
-      } else if (m == 2) {
-        const double a = grad_uni_ld<SM>(pool, stride, o, 0, as), b = grad_uni_ld<SM>(pool, stride, o, 2, as);
-        const double d = grad_uni_ld<SM>(pool, stride, o, 3, as);
-        const double h0 = grad_uni_ld<SM>(pool, stride, o, 4, as), h1 = grad_uni_ld<SM>(pool, stride, o, 5, as);
-        const double ba = b / a, sc = d - ba * b;   // the Schur complement of the first pivot
-        ok = a > 0.0 && sc > 0.0;
-        S11 = 1.0 / sc;
-        S01 = -(ba * S11);
-        S00 = 1.0 / a + ba * ba * S11;
-        m1 = (h1 - ba * h0) / sc;
-        m0 = (h0 - b * m1) / a;
-      } else {
-        ok = false;   // (a variable in scope of a cluster without variables: no moments)
-      }
-    }
+    // moments of the cluster (no variable in scope: none are needed)
+    FamUniMom q{0.0, 0.0, 0.0, 0.0, 0.0, 0, true};
+    if (any_scope) q = fam_uni_moments<SM>(pool, stride, off[c], bdim[c], as);
+    const double S00 = q.S00, S01 = q.S01, S11 = q.S11, m0 = q.m0, m1 = q.m1;
+    bool ok = q.ok;
     // one pass over the blocks: u, the constant part, V, w, the chain-rule coefficients and the sums of the alpha term
     double u0 = 0.0, u1 = 0.0, cst = 0.0;
     if (cpos == 0) u0 = 1.0;
@@ -197,9 +174,9 @@ __global__ __launch_bounds__(256) void grad_uni_reduce(const double* __restrict_
     for (int b = 0; b < nfb; ++b) acc = acc + partial[((int64_t)b * n_ent + en) * part_row + s];
     out[(int64_t)en * out_row + out0 + s] = acc;
   } else {
-    int bad = kGradUniNoInfo;
+    int bad = kFamUniNoInfo;
     for (int b = 0; b < nfb; ++b) bad = min(bad, pinfo[(int64_t)b * part_row + s]);
-    info[out0 + s] = bad == kGradUniNoInfo ? 0 : bad;
+    info[out0 + s] = bad == kFamUniNoInfo ? 0 : bad;
   }
 }
 
@@ -211,71 +188,46 @@ extern "C" int pgbp_lg_gradient_sites(pgbp_engine* e, int32_t site_begin, int32_
                                       double* dalpha, double* dtheta, double* dsigma_e, int32_t* info) {
   if (!e) return PGBP_ERR_INVALID;
   const char* fn = "pgbp_lg_gradient_sites";
-  const LgModel* L = nullptr;
-  const int rc = lg_sweep_state(e, fn, site_begin, site_end, &L);
+  SitesCall c{};
+  int rc = sites_accept_state(e, fn, site_begin, site_end, &c);
   if (rc) return rc;
-  const LgStatic& F = L->F;
-  const LgParams& M = L->M;
-  const LgShifts& Sh = L->Sh;
-  const LgNoise& Nz = L->Nz;
-  const EngineView v = engine_peek(e);   // (the layout is not touched)
-  const Plan& pl = *v.plan;
+  const LgModel* L = c.L;
   if (!dR || !dmu) return engine_fail(e, PGBP_ERR_INVALID, std::string(fn) + ": no output buffer");
-  const bool ou = M.model == PGBP_LG_OU;
+  const bool ou = L->M.model == PGBP_LG_OU;
   if (ou && (!dalpha || !dtheta)) return engine_fail(e, PGBP_ERR_INVALID, std::string(fn) + ": the OU model needs dalpha and dtheta");
-  const UniView U = engine_uni_view(e);
-  // a thread-per-site engine, as the plan defines it
-  if (F.p != 1)
-    return engine_fail(e, PGBP_ERR_INVALID, std::string(fn) + ": " + std::to_string(F.p) + " traits; the thread-per-site sweep is univariate (use pgbp_lg_gradient)");
-  if (pl.max_dim > 2)
-    return engine_fail(e, PGBP_ERR_INVALID, std::string(fn) + ": a belief of " + std::to_string(pl.max_dim) +
-                                                " variables; the thread-per-site sweep needs every belief at 2 variables or fewer (use pgbp_lg_gradient)");
-  if (pl.n_sites < 8)
-    return engine_fail(e, PGBP_ERR_INVALID, std::string(fn) + ": " + std::to_string(pl.n_sites) +
-                                                " sites; the thread-per-site kernels run from 8 sites on (use pgbp_lg_gradient)");
-  if (!U.tps || U.bs16) return engine_fail(e, PGBP_ERR_INVALID, std::string(fn) + ": the engine is not on the thread-per-site kernels");
-  const int ns = site_end - site_begin;
+  if ((rc = sites_accept_engine(e, fn, "pgbp_lg_gradient", c))) return rc;
+  const int ns = c.ns;
   if (ns == 0) return PGBP_OK;
-  const int nr = F.n_rates, nf = L->T.n_families;
+  const int nr = L->F.n_rates, nf = L->T.n_families;
   const int n_ent = grad_uni_entries(nr);
-  const int nfb = std::max(1, (nf + kGradUniFamBlock - 1) / kGradUniFamBlock);
-  // the partials of a chunk of sites at a time: 256 MB at most (whole workgroups of sites; one workgroup's sites at least)
-  const int64_t fit = (((int64_t)32 << 20) / ((int64_t)nfb * n_ent)) / 256 * 256;
-  const int chunk = (int)std::min<int64_t>(ns, std::max<int64_t>(256, fit));
+  const int nfb = std::max(1, (nf + kFamUniBlock - 1) / kFamUniBlock);
+  const int chunk = fam_uni_chunk(ns, (int64_t)nfb * n_ent);   // the partials of a chunk of sites at a time
   std::vector<double> out((size_t)n_ent * ns);
   std::vector<int32_t> inf(ns, 0);
   DevBuf<int32_t> d_fcl, d_pinfo, d_info;
   DevBuf<double> d_part, d_out;
-  hipError_t herr = (hipError_t)d_fcl.alloc(std::max(1, nf));
-  if (herr == hipSuccess) herr = (hipError_t)d_part.alloc((size_t)nfb * n_ent * chunk);
-  if (herr == hipSuccess) herr = (hipError_t)d_pinfo.alloc((size_t)nfb * chunk);
-  if (herr == hipSuccess) herr = (hipError_t)d_out.alloc((size_t)n_ent * ns);
-  if (herr == hipSuccess) herr = (hipError_t)d_info.alloc((size_t)ns);
-  if (herr == hipSuccess && nf > 0)
-    herr = hipMemcpyAsync(d_fcl.get(), L->T.cluster.data(), sizeof(int32_t) * nf, hipMemcpyHostToDevice, v.st);
-  if (herr != hipSuccess) return engine_fail(e, PGBP_ERR_HIP, std::string(fn) + " (scratch): " + hipGetErrorString(herr));
-  (void)hipGetLastError();   // (an error an earlier asynchronous call left behind is that call's to report)
-  const int64_t data_row_len = sm_row(pl.n_sites);
-  for (int s0 = 0; s0 < ns; s0 += chunk) {
+  SitesScratch S(e, fn, c.v.st);
+  S.alloc(d_fcl, std::max(1, nf));
+  S.alloc(d_part, (size_t)nfb * n_ent * chunk);
+  S.alloc(d_pinfo, (size_t)nfb * chunk);
+  S.alloc(d_out, (size_t)n_ent * ns);
+  S.alloc(d_info, ns);
+  S.upload(d_fcl, L->T.cluster.data(), nf);
+  if ((rc = S.ready())) return rc;
+  for (int s0 = 0; S.ok() && s0 < ns; s0 += chunk) {
     const int n = std::min(chunk, ns - s0);
+    const SitesArgs A = sites_args(c, site_begin + s0, n, chunk, d_fcl.get());
     const dim3 grid((n + 255) / 256, nfb);
-    for (int r0 = 0; r0 == 0 || r0 < nr; r0 += kGradUniRates) {
-      if (U.sm)
-        hipLaunchKernelGGL(grad_uni_family<true>, grid, dim3(256), 0, v.st, U.pool, U.stride, U.off, U.bdim, F, M, Sh, Nz,
-                           d_fcl.get(), nf, data_row_len, site_begin + s0, n, r0, (int64_t)chunk, d_part.get(), d_pinfo.get());
-      else
-        hipLaunchKernelGGL(grad_uni_family<false>, grid, dim3(256), 0, v.st, U.pool, U.stride, U.off, U.bdim, F, M, Sh, Nz,
-                           d_fcl.get(), nf, data_row_len, site_begin + s0, n, r0, (int64_t)chunk, d_part.get(), d_pinfo.get());
-    }
-    hipLaunchKernelGGL(grad_uni_reduce, dim3((n + 255) / 256, n_ent + 1), dim3(256), 0, v.st, d_part.get(), d_pinfo.get(), nfb,
-                       n_ent, n, (int64_t)chunk, d_out.get(), d_info.get(), s0, (int64_t)ns);
+    for (int r0 = 0; r0 == 0 || r0 < nr; r0 += kGradUniRates)
+      PGBP_SITES_LAUNCH(S, c.U.sm, grad_uni_family, grid, A.pool, A.stride, A.off, A.bdim, L->F, L->M, L->Sh, L->Nz, A.fam_cluster, nf,
+                        A.data_row_len, A.site0, A.n_sites, r0, A.row, d_part.get(), d_pinfo.get());
+    S.launch(grad_uni_reduce, dim3(grid.x, n_ent + 1), d_part.get(), d_pinfo.get(), nfb, n_ent, n, (int64_t)chunk, d_out.get(),
+             d_info.get(), s0, (int64_t)ns);
+    S.check();
   }
-  herr = hipGetLastError();
-  if (herr == hipSuccess) herr = hipMemcpyAsync(out.data(), d_out.get(), sizeof(double) * out.size(), hipMemcpyDeviceToHost, v.st);
-  if (herr == hipSuccess) herr = hipMemcpyAsync(inf.data(), d_info.get(), sizeof(int32_t) * (size_t)ns, hipMemcpyDeviceToHost, v.st);
-  const hipError_t serr = hipStreamSynchronize(v.st);
-  if (herr == hipSuccess) herr = serr;
-  if (herr != hipSuccess) return engine_fail(e, PGBP_ERR_HIP, std::string(fn) + ": " + hipGetErrorString(herr));
+  S.download(out.data(), d_out.get(), out.size());
+  S.download(inf.data(), d_info.get(), ns);
+  if ((rc = S.finish())) return rc;
   // [entry][site] to the caller's arrays (the layout of pgbp_lg_gradient_noise at p = 1); a failed site holds NaN
   for (int s = 0; s < ns; ++s) {
     const bool bad = inf[s] != 0;

@@ -22,14 +22,13 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <chrono>
 #include <cmath>
 #include <string>
 #include <vector>
 
 #include "pgbp_devmem.hpp"
 #include "pgbp_fam_uni_dev.hpp"
-#include "pgbp_fam_uni_host.hpp"
+#include "pgbp_sites_host.hpp"
 #include "pgbp_kernels.hpp"
 #include "pgbp_lgmodel.hpp"
 #include "pgbp_philox_dev.hpp"
@@ -49,7 +48,7 @@ struct PostMomItem {
 
 // mean: [sum of dims][row], cov: [sum of m (m + 1) / 2][row] (may be null), norm: [n][row], info: [n][row] (may be null)
 template <bool SM>
-__global__ __launch_bounds__(256) void post_uni_moments(PostUniArgs A, const PostMomItem* __restrict__ items, int n_items,
+__global__ __launch_bounds__(256) void post_uni_moments(SitesArgs A, const PostMomItem* __restrict__ items, int n_items,
                                                         double* __restrict__ mean, double* __restrict__ cov,
                                                         double* __restrict__ norm, int32_t* __restrict__ info) {
 #pragma clang fp contract(off)
@@ -99,7 +98,7 @@ __global__ __launch_bounds__(256) void post_uni_moments(PostUniArgs A, const Pos
 
 // fam[ti]: the listed family ti, pred[ti]: its mask of predicted traits; mean, var (either may be null), info: [n_list][row]
 template <bool SM>
-__global__ __launch_bounds__(256) void post_uni_impute(PostUniArgs A, LgStatic F, LgParams M, LgShifts Sh, LgNoise Nz,
+__global__ __launch_bounds__(256) void post_uni_impute(SitesArgs A, LgStatic F, LgParams M, LgShifts Sh, LgNoise Nz,
                                                        const int32_t* __restrict__ fam, const int32_t* __restrict__ fcl,
                                                        const unsigned long long* __restrict__ pred, int n_list,
                                                        double* __restrict__ mean, double* __restrict__ var,
@@ -171,7 +170,7 @@ __device__ __forceinline__ double post_normal(uint32_t entry, uint32_t draw, uin
 // One preorder level: thread = site, the items of the level along grid.y, the nd draws of the launch in a loop.  z (null: the
 // generator, draws d0 .. d0 + nd) and x: [nd][size][row] of this chunk; bad[site]: not 0 where the site's draws are NaN
 template <bool SM>
-__global__ __launch_bounds__(256) void post_uni_apply(PostUniArgs A, const SampItem* __restrict__ items, int n_items,
+__global__ __launch_bounds__(256) void post_uni_apply(SitesArgs A, const SampItem* __restrict__ items, int n_items,
                                                       const int32_t* __restrict__ idx, const int32_t* __restrict__ bad, int d0,
                                                       int nd, int64_t size, const double* __restrict__ z, uint32_t k0, uint32_t k1,
                                                       double* __restrict__ x) {
@@ -219,14 +218,6 @@ __global__ __launch_bounds__(256) void post_uni_apply(PostUniArgs A, const SampI
   }
 }
 
-namespace {
-
-PostUniArgs post_uni_args(const FamUniCall& c, int site0, int n, int chunk) {
-  return PostUniArgs{c.U.pool, c.U.stride, c.U.off, c.U.bdim, site0, n, (int64_t)chunk};
-}
-
-}  // namespace
-
 }  // namespace pgbp
 
 using namespace pgbp;
@@ -235,8 +226,8 @@ extern "C" int pgbp_moments_sites(pgbp_engine* e, int32_t n, const int32_t* beli
                                   double* mean, double* cov, double* norm, int32_t* info) {
   if (!e) return PGBP_ERR_INVALID;
   const char* fn = "pgbp_moments_sites";
-  FamUniCall c{};
-  int rc = fam_uni_accept(e, fn, "pgbp_moments", site_begin, site_end, (!mean || !norm) ? "no output buffer (mean, norm)" : nullptr, &c);
+  SitesCall c{};
+  int rc = sites_accept(e, fn, "pgbp_moments", site_begin, site_end, (!mean || !norm) ? "no output buffer (mean, norm)" : nullptr, &c);
   if (rc) return rc;
   const Plan& pl = *c.v.plan;
   if (beliefs && n < 0) return engine_fail(e, PGBP_ERR_INVALID, std::string(fn) + ": negative number of beliefs");
@@ -255,51 +246,39 @@ extern "C" int pgbp_moments_sites(pgbp_engine* e, int32_t n, const int32_t* beli
   }
   const int ns = c.ns;
   if (ns == 0 || nl == 0) return PGBP_OK;
-  const hipStream_t st = c.v.st;
   const int nb = (nl + kFamUniBlock - 1) / kFamUniBlock;
   const int chunk = fam_uni_chunk(ns, (int64_t)nm + (cov ? nt : 0) + nl + (info ? nl : 0));
   DevBuf<PostMomItem> d_items;
   DevBuf<double> d_mean, d_cov, d_norm;
   DevBuf<int32_t> d_info;
-  hipError_t herr = (hipError_t)d_items.alloc(nl);
-  if (herr == hipSuccess) herr = (hipError_t)d_mean.alloc((size_t)std::max(1, nm) * chunk);
-  if (herr == hipSuccess && cov) herr = (hipError_t)d_cov.alloc((size_t)std::max(1, nt) * chunk);
-  if (herr == hipSuccess) herr = (hipError_t)d_norm.alloc((size_t)nl * chunk);
-  if (herr == hipSuccess && info) herr = (hipError_t)d_info.alloc((size_t)nl * chunk);
-  if (herr == hipSuccess) herr = hipMemcpyAsync(d_items.get(), items.data(), sizeof(PostMomItem) * nl, hipMemcpyHostToDevice, st);
-  if (herr != hipSuccess) {
-    (void)hipStreamSynchronize(st);   // (the upload reads this call's locals)
-    return engine_fail(e, PGBP_ERR_HIP, std::string(fn) + " (scratch): " + hipGetErrorString(herr));
-  }
-  (void)hipGetLastError();   // (an error an earlier asynchronous call left behind is that call's to report)
-  for (int s0 = 0; herr == hipSuccess && s0 < ns; s0 += chunk) {
+  SitesScratch S(e, fn, c.v.st);
+  S.alloc(d_items, nl);
+  S.alloc(d_mean, (size_t)std::max(1, nm) * chunk);
+  S.alloc(d_cov, (size_t)std::max(1, nt) * chunk, cov != nullptr);
+  S.alloc(d_norm, (size_t)nl * chunk);
+  S.alloc(d_info, (size_t)nl * chunk, info != nullptr);
+  S.upload(d_items, items.data(), nl);
+  if ((rc = S.ready())) return rc;
+  for (int s0 = 0; S.ok() && s0 < ns; s0 += chunk) {
     const int nn = std::min(chunk, ns - s0);
-    const PostUniArgs A = post_uni_args(c, site_begin + s0, nn, chunk);
+    const SitesArgs A = sites_args(c, site_begin + s0, nn, chunk);
     const dim3 grid((nn + 255) / 256, nb);
-    if (c.U.sm)
-      hipLaunchKernelGGL(post_uni_moments<true>, grid, dim3(256), 0, st, A, d_items.get(), nl, d_mean.get(), d_cov.get(),
-                         d_norm.get(), d_info.get());
-    else
-      hipLaunchKernelGGL(post_uni_moments<false>, grid, dim3(256), 0, st, A, d_items.get(), nl, d_mean.get(), d_cov.get(),
-                         d_norm.get(), d_info.get());
-    herr = hipGetLastError();
-    if (herr == hipSuccess) herr = fam_uni_copy(mean, ns, s0, d_mean.get(), chunk, nn, nm, st);
-    if (herr == hipSuccess) herr = fam_uni_copy(cov, ns, s0, d_cov.get(), chunk, nn, nt, st);
-    if (herr == hipSuccess) herr = fam_uni_copy(norm, ns, s0, d_norm.get(), chunk, nn, nl, st);
-    if (herr == hipSuccess) herr = fam_uni_copy(info, ns, s0, d_info.get(), chunk, nn, nl, st);
+    PGBP_SITES_LAUNCH(S, c.U.sm, post_uni_moments, grid, A, d_items.get(), nl, d_mean.get(), d_cov.get(), d_norm.get(), d_info.get());
+    S.check();
+    S.rows(mean, ns, s0, d_mean.get(), chunk, nn, nm);
+    S.rows(cov, ns, s0, d_cov.get(), chunk, nn, nt);
+    S.rows(norm, ns, s0, d_norm.get(), chunk, nn, nl);
+    S.rows(info, ns, s0, d_info.get(), chunk, nn, nl);
   }
-  const hipError_t serr = hipStreamSynchronize(st);
-  if (herr == hipSuccess) herr = serr;
-  if (herr != hipSuccess) return engine_fail(e, PGBP_ERR_HIP, std::string(fn) + ": " + hipGetErrorString(herr));
-  return PGBP_OK;
+  return S.finish();
 }
 
 extern "C" int pgbp_lg_impute_sites(pgbp_engine* e, int32_t site_begin, int32_t site_end, double* mean, double* var,
                                     int32_t* info) {
   if (!e) return PGBP_ERR_INVALID;
   const char* fn = "pgbp_lg_impute_sites";
-  FamUniCall c{};
-  int rc = fam_uni_accept(e, fn, "pgbp_lg_impute", site_begin, site_end,
+  SitesCall c{};
+  int rc = sites_accept(e, fn, "pgbp_lg_impute", site_begin, site_end,
                           (!mean && !var) ? "no output buffer (mean and var are both NULL)" : nullptr, &c);
   if (rc) return rc;
   const LgModel* L = c.L;
@@ -309,46 +288,35 @@ extern "C" int pgbp_lg_impute_sites(pgbp_engine* e, int32_t site_begin, int32_t 
   for (int32_t f : fams) cls.push_back(L->T.cluster[f]);
   const int ns = c.ns, nl = (int)fams.size();
   if (ns == 0 || nl == 0) return PGBP_OK;
-  const hipStream_t st = c.v.st;
   const int nb = (nl + kFamUniBlock - 1) / kFamUniBlock;
   const int chunk = fam_uni_chunk(ns, (int64_t)nl * ((mean ? 1 : 0) + (var ? 1 : 0) + (info ? 1 : 0)));
   DevBuf<int32_t> d_fams, d_cls, d_info;
   DevBuf<unsigned long long> d_pred;
   DevBuf<double> d_mean, d_var;
   const size_t tab = (size_t)nl * chunk;
-  hipError_t herr = (hipError_t)d_fams.alloc(nl);
-  if (herr == hipSuccess) herr = (hipError_t)d_cls.alloc(nl);
-  if (herr == hipSuccess) herr = (hipError_t)d_pred.alloc(nl);
-  if (herr == hipSuccess && mean) herr = (hipError_t)d_mean.alloc(tab);
-  if (herr == hipSuccess && var) herr = (hipError_t)d_var.alloc(tab);
-  if (herr == hipSuccess && info) herr = (hipError_t)d_info.alloc(tab);
-  if (herr == hipSuccess) herr = hipMemcpyAsync(d_fams.get(), fams.data(), sizeof(int32_t) * nl, hipMemcpyHostToDevice, st);
-  if (herr == hipSuccess) herr = hipMemcpyAsync(d_cls.get(), cls.data(), sizeof(int32_t) * nl, hipMemcpyHostToDevice, st);
-  if (herr == hipSuccess) herr = hipMemcpyAsync(d_pred.get(), pred.data(), sizeof(unsigned long long) * nl, hipMemcpyHostToDevice, st);
-  if (herr != hipSuccess) {
-    (void)hipStreamSynchronize(st);
-    return engine_fail(e, PGBP_ERR_HIP, std::string(fn) + " (scratch): " + hipGetErrorString(herr));
-  }
-  (void)hipGetLastError();
-  for (int s0 = 0; herr == hipSuccess && s0 < ns; s0 += chunk) {
+  SitesScratch S(e, fn, c.v.st);
+  S.alloc(d_fams, nl);
+  S.alloc(d_cls, nl);
+  S.alloc(d_pred, nl);
+  S.alloc(d_mean, tab, mean != nullptr);
+  S.alloc(d_var, tab, var != nullptr);
+  S.alloc(d_info, tab, info != nullptr);
+  S.upload(d_fams, fams.data(), nl);
+  S.upload(d_cls, cls.data(), nl);
+  S.upload(d_pred, pred.data(), nl);
+  if ((rc = S.ready())) return rc;
+  for (int s0 = 0; S.ok() && s0 < ns; s0 += chunk) {
     const int nn = std::min(chunk, ns - s0);
-    const PostUniArgs A = post_uni_args(c, site_begin + s0, nn, chunk);
+    const SitesArgs A = sites_args(c, site_begin + s0, nn, chunk);
     const dim3 grid((nn + 255) / 256, nb);
-    if (c.U.sm)
-      hipLaunchKernelGGL(post_uni_impute<true>, grid, dim3(256), 0, st, A, L->F, L->M, L->Sh, L->Nz, d_fams.get(), d_cls.get(),
-                         d_pred.get(), nl, d_mean.get(), d_var.get(), d_info.get());
-    else
-      hipLaunchKernelGGL(post_uni_impute<false>, grid, dim3(256), 0, st, A, L->F, L->M, L->Sh, L->Nz, d_fams.get(), d_cls.get(),
-                         d_pred.get(), nl, d_mean.get(), d_var.get(), d_info.get());
-    herr = hipGetLastError();
-    if (herr == hipSuccess) herr = fam_uni_copy(mean, ns, s0, d_mean.get(), chunk, nn, nl, st);
-    if (herr == hipSuccess) herr = fam_uni_copy(var, ns, s0, d_var.get(), chunk, nn, nl, st);
-    if (herr == hipSuccess) herr = fam_uni_copy(info, ns, s0, d_info.get(), chunk, nn, nl, st);
+    PGBP_SITES_LAUNCH(S, c.U.sm, post_uni_impute, grid, A, L->F, L->M, L->Sh, L->Nz, d_fams.get(), d_cls.get(), d_pred.get(), nl,
+                      d_mean.get(), d_var.get(), d_info.get());
+    S.check();
+    S.rows(mean, ns, s0, d_mean.get(), chunk, nn, nl);
+    S.rows(var, ns, s0, d_var.get(), chunk, nn, nl);
+    S.rows(info, ns, s0, d_info.get(), chunk, nn, nl);
   }
-  const hipError_t serr = hipStreamSynchronize(st);
-  if (herr == hipSuccess) herr = serr;
-  if (herr != hipSuccess) return engine_fail(e, PGBP_ERR_HIP, std::string(fn) + ": " + hipGetErrorString(herr));
-  return PGBP_OK;
+  return S.finish();
 }
 
 // ms (pgbp_sample_posterior_sites_timed): the stream is drained after every phase and the wall time of the phase is added to
@@ -357,8 +325,8 @@ static int sample_posterior_sites(pgbp_engine* e, int32_t tree, int32_t site_beg
                                   const double* z, uint64_t seed, double* x, int32_t* info, double* ms) {
   if (!e) return PGBP_ERR_INVALID;
   const char* fn = "pgbp_sample_posterior_sites";
-  FamUniCall c{};
-  int rc = fam_uni_accept(e, fn, "pgbp_sample_posterior", site_begin, site_end, nullptr, &c);
+  SitesCall c{};
+  int rc = sites_accept(e, fn, "pgbp_sample_posterior", site_begin, site_end, nullptr, &c);
   if (rc) return rc;
   SampPlan sp;
   rc = sample_plan(e, std::string(fn) + ": ", tree, site_begin, site_end, n_draws, "n_draws", "draw",
@@ -371,92 +339,54 @@ static int sample_posterior_sites(pgbp_engine* e, int32_t tree, int32_t site_beg
     if (info) std::fill(info, info + ns, 0);
     return PGBP_OK;
   }
-  // the clusters with variables by preorder rank (the validity pass), behind the items by level
-  std::vector<int32_t> at(sp.nc, -1);
-  for (size_t q = 0; q < sp.by_level.size(); ++q) at[sp.by_level[q].cluster] = (int32_t)q;
-  std::vector<SampItem> tab = sp.by_level;
-  std::vector<int32_t> pre_cluster;
-  for (int32_t cl : sp.order)
-    if (at[cl] >= 0) {
-      tab.push_back(sp.by_level[at[cl]]);
-      pre_cluster.push_back(cl);
-    }
-  const int n_items = (int)sp.by_level.size(), n_pre = (int)pre_cluster.size();
-  const int nvb = (n_pre + kFamUniBlock - 1) / kFamUniBlock;
+  const PostUniPre pre = post_uni_pre(sp);
   // z (when given) and x of a chunk of draws and a chunk of sites: one workgroup's sites at least, so the draws are cut first
-  const hipStream_t st = c.v.st;
   const int64_t per_draw = size * (z ? 2 : 1);
   const int dchunk = (int)std::min<int64_t>(n_draws, std::max<int64_t>(1, g_fam_uni_limit.load() / (256 * per_draw)));
-  const int chunk = fam_uni_chunk(ns, per_draw * dchunk + nvb);
+  const int chunk = fam_uni_chunk(ns, per_draw * dchunk + pre.nvb);
   std::vector<int32_t> rank(ns, 0);
   DevBuf<SampItem> d_tab;
   DevBuf<int32_t> d_idx, d_pfirst, d_rank;
   DevBuf<double> d_z, d_x;
-  hipError_t herr = (hipError_t)d_tab.alloc(tab.size());
-  if (herr == hipSuccess) herr = (hipError_t)d_idx.alloc(sp.idx.size());
-  if (herr == hipSuccess) herr = (hipError_t)d_pfirst.alloc((size_t)nvb * chunk);
-  if (herr == hipSuccess) herr = (hipError_t)d_rank.alloc((size_t)ns);
-  if (herr == hipSuccess && z) herr = (hipError_t)d_z.alloc((size_t)dchunk * size * chunk);
-  if (herr == hipSuccess) herr = (hipError_t)d_x.alloc((size_t)dchunk * size * chunk);
-  if (herr == hipSuccess) herr = hipMemcpyAsync(d_tab.get(), tab.data(), sizeof(SampItem) * tab.size(), hipMemcpyHostToDevice, st);
-  if (herr == hipSuccess) herr = hipMemcpyAsync(d_idx.get(), sp.idx.data(), sizeof(int32_t) * sp.idx.size(), hipMemcpyHostToDevice, st);
-  if (herr != hipSuccess) {
-    (void)hipStreamSynchronize(st);
-    return engine_fail(e, PGBP_ERR_HIP, std::string(fn) + " (scratch): " + hipGetErrorString(herr));
-  }
-  (void)hipGetLastError();
-  auto t_last = std::chrono::steady_clock::now();
-  auto phase = [&](int k) {   // timed variant only
-    if (!ms) return;
-    const hipError_t perr = hipStreamSynchronize(st);
-    if (herr == hipSuccess) herr = perr;
-    const auto now = std::chrono::steady_clock::now();
-    if (k >= 0) ms[k] += std::chrono::duration<double, std::milli>(now - t_last).count();
-    t_last = now;
-  };
-  if (ms) ms[0] = ms[1] = ms[2] = ms[3] = 0.0;
-  phase(-1);
+  SitesScratch S(e, fn, c.v.st);
+  S.alloc(d_tab, pre.tab.size());
+  S.alloc(d_idx, sp.idx.size());
+  S.alloc(d_pfirst, (size_t)pre.nvb * chunk);
+  S.alloc(d_rank, ns);
+  S.alloc(d_z, (size_t)dchunk * size * chunk, z != nullptr);
+  S.alloc(d_x, (size_t)dchunk * size * chunk);
+  S.upload(d_tab, pre.tab.data(), pre.tab.size());
+  S.upload(d_idx, sp.idx.data(), sp.idx.size());
+  if ((rc = S.ready())) return rc;
+  SitesClock phase(S, ms, 4);
   const uint32_t k0 = (uint32_t)(seed & 0xffffffffull), k1 = (uint32_t)(seed >> 32);
-  for (int s0 = 0; herr == hipSuccess && s0 < ns; s0 += chunk) {
+  for (int s0 = 0; S.ok() && s0 < ns; s0 += chunk) {
     const int nn = std::min(chunk, ns - s0);
-    const PostUniArgs A = post_uni_args(c, site_begin + s0, nn, chunk);
-    const dim3 gs((nn + 255) / 256);
-    if (c.U.sm)
-      hipLaunchKernelGGL(post_uni_valid<true>, dim3(gs.x, nvb), dim3(256), 0, st, A, d_tab.get() + n_items, n_pre, d_idx.get(), d_pfirst.get());
-    else
-      hipLaunchKernelGGL(post_uni_valid<false>, dim3(gs.x, nvb), dim3(256), 0, st, A, d_tab.get() + n_items, n_pre, d_idx.get(), d_pfirst.get());
-    hipLaunchKernelGGL(post_uni_first, gs, dim3(256), 0, st, d_pfirst.get(), nvb, nn, (int64_t)chunk, d_rank.get(), s0);
-    herr = hipGetLastError();
+    const SitesArgs A = sites_args(c, site_begin + s0, nn, chunk);
+    post_uni_validity(S, c.U.sm, A, pre, d_tab.get(), d_idx.get(), d_pfirst.get(), d_rank.get(), s0);
     phase(0);
-    for (int d0 = 0; herr == hipSuccess && d0 < n_draws; d0 += dchunk) {
+    for (int d0 = 0; S.ok() && d0 < n_draws; d0 += dchunk) {
       const int nd = std::min(dchunk, n_draws - d0);
       const int64_t rows = (int64_t)nd * size;
       if (z)   // rows of the caller's [n_draws][size][ns] into the chunk's [nd][size][chunk]
-        herr = hipMemcpy2DAsync(d_z.get(), sizeof(double) * (size_t)chunk, z + (size_t)d0 * size * ns + s0, sizeof(double) * (size_t)ns,
-                                sizeof(double) * (size_t)nn, (size_t)rows, hipMemcpyHostToDevice, st);
+        S.err = hipMemcpy2DAsync(d_z.get(), sizeof(double) * (size_t)chunk, z + (size_t)d0 * size * ns + s0, sizeof(double) * (size_t)ns,
+                                 sizeof(double) * (size_t)nn, (size_t)rows, hipMemcpyHostToDevice, S.st);
       phase(1);
-      for (size_t l = 0; herr == hipSuccess && l + 1 < sp.level_off.size(); ++l) {
+      for (size_t l = 0; l + 1 < sp.level_off.size(); ++l) {
         const int ni = sp.level_off[l + 1] - sp.level_off[l];
-        const dim3 grid(gs.x, std::min(ni, 65535));
-        if (c.U.sm)
-          hipLaunchKernelGGL(post_uni_apply<true>, grid, dim3(256), 0, st, A, d_tab.get() + sp.level_off[l], ni, d_idx.get(),
-                             d_rank.get() + s0, d0, nd, size, d_z.get(), k0, k1, d_x.get());
-        else
-          hipLaunchKernelGGL(post_uni_apply<false>, grid, dim3(256), 0, st, A, d_tab.get() + sp.level_off[l], ni, d_idx.get(),
-                             d_rank.get() + s0, d0, nd, size, d_z.get(), k0, k1, d_x.get());
+        const dim3 grid((nn + 255) / 256, std::min(ni, 65535));
+        PGBP_SITES_LAUNCH(S, c.U.sm, post_uni_apply, grid, A, d_tab.get() + sp.level_off[l], ni, d_idx.get(), d_rank.get() + s0, d0,
+                          nd, size, d_z.get(), k0, k1, d_x.get());
       }
-      if (herr == hipSuccess) herr = hipGetLastError();
+      S.check();
       phase(2);
-      if (herr == hipSuccess) herr = fam_uni_copy(x + (size_t)d0 * size * ns, ns, s0, d_x.get(), chunk, nn, rows, st);
+      S.rows(x + (size_t)d0 * size * ns, ns, s0, d_x.get(), chunk, nn, rows);
       phase(3);
     }
   }
-  if (herr == hipSuccess) herr = hipMemcpyAsync(rank.data(), d_rank.get(), sizeof(int32_t) * (size_t)ns, hipMemcpyDeviceToHost, st);
-  const hipError_t serr = hipStreamSynchronize(st);   // (also when something failed: the uploads read this call's locals)
-  if (herr == hipSuccess) herr = serr;
-  if (herr != hipSuccess) return engine_fail(e, PGBP_ERR_HIP, std::string(fn) + ": " + hipGetErrorString(herr));
-  if (info)
-    for (int s = 0; s < ns; ++s) info[s] = rank[s] ? pre_cluster[rank[s] - 1] + 1 : 0;
+  S.download(rank.data(), d_rank.get(), ns);
+  if ((rc = S.finish())) return rc;
+  post_uni_info(pre, rank, info);
   return PGBP_OK;
 }
 

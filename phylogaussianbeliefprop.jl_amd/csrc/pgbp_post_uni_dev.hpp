@@ -1,24 +1,18 @@
 // Device pieces shared by the lanes-are-sites sweeps over a schedule tree of a univariate batch (pgbp_post_uni.hip: the joint
-// draws; pgbp_cov_uni.hip: the posterior covariance): what every kernel takes of the engine and of the call, the closed-form
-// conditional of a cluster's R given its S at a site, and the validity pass -- which site has a conditional J_RR that is not
-// positive definite, and which cluster in preorder is the first.  Frame and arithmetic contract of pgbp_fam_uni_dev.hpp.
+// draws; pgbp_cov_uni.hip: the posterior covariance): the closed-form conditional of a cluster's R given its S at a site, and
+// the validity pass -- which site has a conditional J_RR that is not positive definite, and which cluster in preorder is the
+// first -- with its host side: its table, its two launches, and the info it gives.  Frame and arithmetic contract of
+// pgbp_fam_uni_dev.hpp.
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <vector>
+
 #include "pgbp_fam_uni_dev.hpp"
 #include "pgbp_sample_plan.hpp"
+#include "pgbp_sites_host.hpp"
 
 namespace pgbp {
-
-// what every kernel takes of the engine and of the call
-struct PostUniArgs {
-  const double* pool;
-  int64_t stride;
-  const int64_t* off;
-  const int32_t* bdim;
-  int site0, n_sites;
-  int64_t row;   // the row length of the scratch (the chunk)
-};
 
 // The conditional of a cluster's R given its S at a site: x_R = a - G x_S + T z_R (at most five numbers; r = 1: a0, G, T00;
 // r = 2: a0, a1, T00, T01, T11).  ok: J_RR is positive definite, pivot by pivot as mom_cond_factor tests it.
@@ -58,7 +52,7 @@ __device__ __forceinline__ PostUniCond post_uni_cond(const double* __restrict__ 
 // pre[k]: the item of the cluster of preorder rank k (clusters with variables only).  pfirst: [blocks][row], the smallest rank of
 // the block whose J_RR is not positive definite, kFamUniNoInfo: none
 template <bool SM>
-__global__ __launch_bounds__(256) void post_uni_valid(PostUniArgs A, const SampItem* __restrict__ pre, int n_pre,
+__global__ __launch_bounds__(256) void post_uni_valid(SitesArgs A, const SampItem* __restrict__ pre, int n_pre,
                                                       const int32_t* __restrict__ idx, int32_t* __restrict__ pfirst) {
   const int s = blockIdx.x * 256 + threadIdx.x;
   if (s >= A.n_sites) return;
@@ -86,6 +80,42 @@ static __global__ __launch_bounds__(256) void post_uni_first(const int32_t* __re
     if (first == kFamUniNoInfo) first = v;
   }
   rank[out0 + s] = first == kFamUniNoInfo ? 0 : first + 1;
+}
+
+// The table of a sweep: the items by level, and behind them the items of the clusters with variables by preorder rank (the
+// validity pass).  at[c]: the item of cluster c among those by level, -1: no variables.
+struct PostUniPre {
+  std::vector<SampItem> tab;
+  std::vector<int32_t> at, pre_cluster;
+  int n_items, n_pre, nvb;   // items by level, by preorder rank, and the blocks of the latter
+};
+
+inline PostUniPre post_uni_pre(const SampPlan& sp) {
+  PostUniPre pre{sp.by_level, std::vector<int32_t>(sp.nc, -1), {}, (int)sp.by_level.size(), 0, 0};
+  for (size_t q = 0; q < sp.by_level.size(); ++q) pre.at[sp.by_level[q].cluster] = (int32_t)q;
+  for (int32_t cl : sp.order)
+    if (pre.at[cl] >= 0) {
+      pre.tab.push_back(sp.by_level[pre.at[cl]]);
+      pre.pre_cluster.push_back(cl);
+    }
+  pre.n_pre = (int)pre.pre_cluster.size();
+  pre.nvb = (pre.n_pre + kFamUniBlock - 1) / kFamUniBlock;
+  return pre;
+}
+
+// the pass over the chunk of A: d_rank[s0 + site] for its sites (d_pfirst: [nvb][row] of scratch)
+static inline void post_uni_validity(SitesScratch& S, int sm, const SitesArgs& A, const PostUniPre& pre, const SampItem* d_tab,
+                                     const int32_t* d_idx, int32_t* d_pfirst, int32_t* d_rank, int s0) {
+  const dim3 gs((A.n_sites + 255) / 256);
+  PGBP_SITES_LAUNCH(S, sm, post_uni_valid, dim3(gs.x, pre.nvb), A, d_tab + pre.n_items, pre.n_pre, d_idx, d_pfirst);
+  S.launch(post_uni_first, gs, d_pfirst, pre.nvb, A.n_sites, A.row, d_rank, s0);
+  S.check();
+}
+
+// info[s]: the 1-based index of the first cluster in preorder whose J_RR is not positive definite at site s, 0: none
+inline void post_uni_info(const PostUniPre& pre, const std::vector<int32_t>& rank, int32_t* info) {
+  if (!info) return;
+  for (size_t s = 0; s < rank.size(); ++s) info[s] = rank[s] ? pre.pre_cluster[rank[s] - 1] + 1 : 0;
 }
 
 }  // namespace pgbp

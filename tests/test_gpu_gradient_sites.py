@@ -291,9 +291,9 @@ def test_family_block_boundaries(P, n_fam, n_rates):
 
 # ----------------------------------------------------------------------------- 7: determinism, read-only
 
-def _raw(cgb, a, b):
+def _raw(cgb, a, b, n_rates=1):
     n = b - a
-    out = [np.zeros((n, 1)), np.zeros(n), np.zeros(n), np.zeros(n), np.zeros(n)]
+    out = [np.zeros((n, n_rates)), np.zeros(n), np.zeros(n), np.zeros(n), np.zeros(n)]
     info = np.ones(n, np.int32)
     from pgbp_amd import _lib as L
     rc = cgb._lib.pgbp_lg_gradient_sites(cgb._eng, a, b, *[L.f64p(x) for x in out], L.i32p(info))
@@ -339,6 +339,43 @@ def test_determinism_and_read_only(P):
     assert _layout(cgb) == 2
     cgb.pull()
     assert np.array_equal(after, cgb._packed_raw)
+
+
+def test_chunks_of_the_scratch_limit(P):
+    """600 sites of an OU model with 6 rates (two rate groups of the kernel) on a tree of 66 families (two family blocks): the
+    call at the default scratch limit and the call at pgbp_sites_sweep_scratch_limit(1) -- one workgroup's sites per chunk,
+    256 + 256 + 88 -- return the same bytes in every output, info included; and the call on [256, 600) returns rows 256.. of
+    the full call."""
+    from pgbp_amd import synth
+    rng = np.random.default_rng(36)
+    ns, n_rates = 600, 6
+    tree = synth.random_tree(34, rng)
+    assert tree.nnodes - 1 == 66
+    colors = rng.integers(n_rates, size=tree.nnodes)
+    colors[1:n_rates + 1] = np.arange(n_rates)   # (every rate is used)
+    alpha, theta, mu = rng.uniform(0.3, 1.5, ns), rng.normal(size=ns), rng.normal(size=ns)
+    gam2 = rng.uniform(0.5, 2.0, size=(ns, n_rates))
+    X = synth.simulate_ou_uni_sites(tree, 2 * alpha * gam2[:, 0], alpha, theta, mu, rng)
+    cgb, spt, fam = _synth_engine(P, tree, X, colors=colors)
+    assert fam["n_rates"] == n_rates and len(fam["cluster"]) >= 65
+    cgb.assignfactors_lg_(gam2[:, :, None, None], mu[:, None], model="ou", alpha=alpha, theta=theta[:, None])
+    ll, got = cgb.loglik_and_gradient_sites_lg(spt)
+    assert _layout(cgb) == 2 and not got["info"].any()
+    full, finfo = _raw(cgb, 0, ns, n_rates)
+    assert np.array_equal(full[0].reshape(-1), got["dR"].reshape(-1)) and all(np.all(np.isfinite(x)) for x in full)
+    assert np.all(full[0] != 0) and np.all(full[2] != 0) and np.all(full[3] != 0)   # (every rate, dalpha and dtheta are live)
+    cgb._lib.pgbp_sites_sweep_scratch_limit(1)
+    try:
+        cut, cinfo = _raw(cgb, 0, ns, n_rates)
+        hi, hinfo = _raw(cgb, 256, ns, n_rates)
+    finally:
+        cgb._lib.pgbp_sites_sweep_scratch_limit(0)
+    for f, c, h in zip(full + [finfo], cut + [cinfo], hi + [hinfo]):
+        assert f.tobytes() == c.tobytes() and f[256:].tobytes() == h.tobytes()
+    whole, winfo = _raw(cgb, 256, ns, n_rates)   # (the slice at the default limit as well)
+    for h, w in zip(hi + [hinfo], whole + [winfo]):
+        assert h.tobytes() == w.tobytes()
+    assert _layout(cgb) == 2
 
 
 # ----------------------------------------------------------------------------- 8: one bad lane
