@@ -208,6 +208,30 @@ def main():
     print(f"  node {c + 1} minus node {c2 + 1}, posterior mean +- se at the first four sites: " +
           ", ".join(f"{m[s, 0] - m2[s, 0]:.3f} +- {np.sqrt(gram[s, 0, 0]):.3f}" for s in range(4)) +
           f"; {int((cinfo != 0).sum())} sites failed")
+    # real batches have gaps, another set of unmeasured species at almost every site: a table with NaN at its gaps goes to
+    # lg_setup with finite placeholders (split_missing_data) and its gaps to set_site_missing_lg; every site is then fitted to
+    # its own observed tips and its gaps are imputed, all sites in one call each (lanes = sites)
+    table = X.copy()
+    leaves = np.flatnonzero(tr.is_leaf)
+    gaps = np.zeros(table.shape, bool)
+    gaps[:, leaves] = rng.random((ns, len(leaves))) < 0.2
+    table[gaps] = np.nan
+    clean, mask = P.split_missing_data(table)
+    gappy = P.ClusterGraphBelief.from_arrays(prob.dims, prob.sepset_clusters, prob.scope_off, prob.scope_idx, None, n_sites=ns)
+    from pgbp_amd import synth   # (S is the covariance of the moments above by now)
+    gappy.lg_setup(synth.lg_tree_table(tr, prob, 1), clean)
+    gappy.set_site_missing_lg(mask)
+    obsmean = np.nanmean(table[:, leaves], axis=1)
+    fit2 = P.fit_sites_lg(gappy, prob.schedule[0], "ou", np.ones(ns), obsmean, alpha0=np.full(ns, 1.0 / H), theta0=obsmean)
+    imp = gappy.impute_sites_lg()
+    site0 = {k: (v[0] if k in ("mean", "cov", "info") else v) for k, v in imp.items()}
+    filled = P.imputed_data(site0, table[0][:, None])
+    row = int(np.flatnonzero(gaps[0])[0])
+    k = int(np.flatnonzero(imp["rows"] == row)[0])
+    print(f"the same batch with 20 % of the tip values missing ({int(mask.sum())} gaps): {int(fit2['converged'].sum())} of {ns} sites "
+          f"converged in {fit2['n_device_evals']} device passes; site 0: alpha {fit2['alpha'][0]:.3f} ({fit['alpha'][0]:.3f} from the "
+          f"complete data); its first gap (row {row}) imputed as {filled[row, 0]:.3f} +- {np.sqrt(imp['cov'][0, k, 0, 0]):.3f}, "
+          f"the value held back was {X[0, row]:.3f}")
 
 
 if __name__ == "__main__":

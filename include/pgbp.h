@@ -443,6 +443,63 @@ int32_t pgbp_lg_shift_count(pgbp_engine* e);
 int pgbp_lg_set_tip_noise(pgbp_engine* e, int32_t n, const int32_t* family, const double* scale, const double* sigma_e,
                           const double* se2, int32_t per_site);
 int32_t pgbp_lg_tip_noise_count(pgbp_engine* e);
+/* PER-SITE MISSING TIPS of a UNIVARIATE BATCH.  child_mask of pgbp_lg_families is one missingness pattern for all sites of the
+ * engine; a real batch (thousands of characters on one tree) lacks another set of species at almost every site.  At p = 1 a
+ * tip that is not observed is exactly a family the fill skips -- its factor is 1 -- with no change of scopes or of the cluster
+ * graph, so the pattern may depend on the site:
+ *   missing [n_sites][n_rows], nonzero = the tip with that data row is NOT observed at that site; NULL clears the mask (so does
+ *           a mask without a nonzero entry).  The call REPLACES the previous mask.
+ * ACCEPTED ONLY ON A THREAD-PER-SITE ENGINE, as pgbp_lg_gradient_sites: p = 1, every belief of at most 2 variables, at least 8
+ * sites; anything else is PGBP_ERR_INVALID before anything changes, and the text points to pgbp_patterns (one engine per
+ * pattern), which stays the route at p > 1.  Clearing (NULL) is accepted on every engine with a family table, whatever its
+ * shape: there is nothing to clear there and the call returns PGBP_OK.  PGBP_ERR_STATE without a family table.
+ * Takes effect as pgbp_lg_set_shifts does: at the next pgbp_lg_assignfactors or pgbp_enqueue_loglik_lg; beliefs and factors
+ * are not refilled by this call.  The mask survives pgbp_lg_set_edges, pgbp_lg_set_shifts, pgbp_lg_set_tip_noise and
+ * pgbp_lg_set_data; a new pgbp_lg_setup clears it.  An engine borrowed from a pgbp_group or pgbp_patterns takes the call like
+ * any other; there is no group-level call.
+ * REFUSED with PGBP_ERR_INVALID and NOTHING changed (the previous mask stays in force; the text names the site and the row):
+ * a nonzero entry at a row that belongs to no tip family (child_pos < 0, a data row, a parent edge); a nonzero entry at a row
+ * whose tip the set-up's child_mask already skips at every site (the text names the family; harmless, but most likely not
+ * what was meant); a site left with no observed tip (where tip families share a data row a masked row hides every one of them:
+ * observed tips are counted in families).
+ * DATA: the value at a masked entry is never used.  The setter stores 0.0 there in the engine's copies of the data
+ * (pgbp_lg_get_data returns it), and while a mask is in force pgbp_lg_set_data accepts any value, finite or not, at a masked
+ * entry and stores 0.0.  An entry that a later mask no longer covers keeps that 0.0 until new data are given.
+ * pgbp_lg_simulate is left alone: with write_data it writes every statically observed row; a value written under the mask is
+ * ignored like any other.
+ * DEVICE: the mask is kept as bit-packed words uint64 [n_rows][W], W = ceil(n_sites / 64), bit (s & 63) of word s >> 6 = site
+ * s: a wavefront of 64 consecutive sites reads at most two words of a row.  Every fill, after its shift and noise
+ * corrections, is followed by csrc/pgbp_sitemiss.hip: lanes = sites, 256 sites per workgroup, one row of workgroups per
+ * cluster that holds a tip family masked at some site (a sparse list the setter builds).  A thread whose site masks no family
+ * of its cluster stores nothing -- that record keeps the fill's bytes --; one whose site does RECOMPUTES the cluster's record
+ * (J, h, g, with the shifts and the tip noise in force) from the family table without the masked families and writes it to
+ * beliefs and, where the fill does, factors.  Recomputed, never subtracted: a cluster whose only family is the masked tip
+ * holds exactly +0.0 in every entry, nothing depends on the stored placeholder, and no cancellation error remains.  One writer
+ * per record, no atomics: the same bytes on every call.  Nothing is launched when no mask is set, and every call then returns
+ * the bytes it returned before this call existed.
+ * THE SWEEPS.  The lanes-are-sites calls read the CURRENT mask as they read the shifts and the noise:
+ *   pgbp_lg_gradient_sites, pgbp_lg_shift_scan_sites, pgbp_lg_edge_gradient_sites: a masked (family, site) is a skipped family
+ *     with that call's convention for one (it adds nothing; jump / information NaN, lr 0; derivatives and dshift 0);
+ *   pgbp_lg_loo_sites: a masked (tip, site) has mean, var and lpd NaN and info PGBP_INFO_NOT_OBSERVED, and adds nothing to
+ *     total (unlike a tip that is not determined, which makes total NaN);
+ *   pgbp_lg_impute_count / _families / _sites: the list is the statically missing tips plus every tip masked at some site, in
+ *     family order (predicted mask 1).  At a site where such a tip is observed mean and var are NaN and info is
+ *     PGBP_INFO_NOT_OBSERVED (there is nothing to impute); at a masked site the prediction is the existing
+ *     closed form from the cluster's belief, which then does not contain the tip.
+ *   pgbp_moments_sites, pgbp_sample_posterior_sites and pgbp_posterior_cov_sites read beliefs only and need no change.
+ * Where every tip below an internal node is masked at a site, scopes do not shrink as they would in the reference: the cluster
+ * {node, parent} then sends the message q^2 j - (q j)^2 / j, zero up to an ulp and possibly slightly negative.  It is added to
+ * a positive precision and is harmless; the scan reports the edge above such a clade as not identified at that site
+ * (H = j - j C j is 0 to rounding).
+ * THE GENERAL SWEEPS cannot honour the mask and would be silently wrong: while one is in force pgbp_lg_gradient(_noise),
+ * pgbp_lg_edge_gradient, pgbp_lg_shift_scan, pgbp_lg_loo, pgbp_lg_impute and pgbp_bm_exact_stats return PGBP_ERR_INVALID
+ * before anything else happens (layout, pool and outputs untouched), the text naming the _sites call to use.
+ * pgbp_lg_get_site_missing: the mask in force as bytes [n_sites][n_rows] (0 / 1), zeros when none.
+ * pgbp_lg_site_missing_count: the number of masked (row, site) pairs (0: no mask; -1: no family table). */
+#define PGBP_INFO_NOT_OBSERVED (-2)
+int pgbp_lg_set_site_missing(pgbp_engine* e, const uint8_t* missing);
+int pgbp_lg_get_site_missing(pgbp_engine* e, uint8_t* missing);
+int32_t pgbp_lg_site_missing_count(pgbp_engine* e);
 /* pgbp_lg_gradient with one more output (NULL allowed: then exactly pgbp_lg_gradient):
  *   dsigma_e [sites][p*p] column-major, symmetric: sum over the noisy tip families of scale_f G_V(f), G_V formed with
  *            j = (V_OO + E_OO)^-1, so that d loglik = tr(dsigma_e dSigma_e); zeros when no noise is set.

@@ -716,6 +716,8 @@ class ClusterGraphBelief:
         self._lg_shift_edges = np.zeros(0, np.int32)   # a new table clears the shifts (pgbp_lg_setup)
         self._lg_noise = None                          # ... and the tip noise
         self._lg_last = None                           # ... and has no parameters yet
+        self._lg_data_nan = np.isnan(data[:, :, 0]) if int(fam["p"]) == 1 else None   # (set_site_missing_lg("nan"); no mask yet)
+        self._lg_site_mask = None                      # ... and no per-site mask
 
     def assignfactors_lg_(self, R, mu, model="bm", alpha=None, theta=None, sync=False):
         """assignfactors!(beliefs, model, ...) (src/beliefs.jl:786-861) on the device for a Brownian motion
@@ -956,7 +958,8 @@ class ClusterGraphBelief:
         kernels (the conditions of gradient_sites_lg), lanes = sites, nothing converted.  Same keys and [site, tip, ...]
         indexing -- families, mean [n_sites, n_tip, 1], cov [n_sites, n_tip, 1, 1], lpd, total, info [n_sites, n_tip], y -- as
         transposed views of the call's site-minor rows.  total adds the tips in another order than loo_lg: the two agree to
-        rounding, as every other value; two calls return the same bytes."""
+        rounding, as every other value; two calls return the same bytes.  A (tip, site) that a per-site mask hides
+        (set_site_missing_lg) has NaN values and info -2 (PGBP_INFO_NOT_OBSERVED), and adds nothing to total."""
         nt = int(self._lib.pgbp_lg_loo_count(self._eng))
         if nt < 0:
             _check(self._lib.pgbp_lg_loo_sites(self._eng, 0, 0, None, None, None, None, None), self._eng)
@@ -1168,7 +1171,9 @@ class ClusterGraphBelief:
         kernels (the conditions of gradient_sites_lg), lanes = sites, nothing converted.  Same keys and [site, tip, ...]
         indexing -- families, rows, predicted [n, 1], mean [n_sites, n, 1], cov [n_sites, n, 1, 1], info [n_sites, n] -- as
         transposed views of the call's site-minor rows, so imputed_data takes a site of it; the values agree with impute_lg
-        to rounding, and two calls return the same bytes."""
+        to rounding, and two calls return the same bytes.  With a per-site mask in force (set_site_missing_lg) the list also
+        holds every tip masked at some site: predicted where it is masked, NaN with info -2 (PGBP_INFO_NOT_OBSERVED) where it
+        is observed."""
         n = int(self._lib.pgbp_lg_impute_count(self._eng))
         if n < 0:
             _check(self._lib.pgbp_lg_impute_sites(self._eng, 0, 0, None, None, None), self._eng)
@@ -1337,16 +1342,80 @@ class ClusterGraphBelief:
         """pgbp_lg_tip_noise_count: the number of noisy tips in force (0: none)."""
         return int(self._lib.pgbp_lg_tip_noise_count(self._eng))
 
+    def set_site_missing_lg(self, mask, data=None):
+        """pgbp_lg_set_site_missing: per-site missing tips of a univariate batch.  mask: bool [n_sites, n_rows], True = the
+        tip with that data row is NOT observed at that site; None clears the mask; "nan": the mask is taken from the NaNs
+        of `data` when given, else of the data last given to lg_setup / set_data_lg.  data (optional, [n_sites, n_rows] or
+        [n_sites, n_rows, 1]): installed by set_data_lg once the mask is in force, so a table with NaNs at its gaps goes in
+        with one call (split_missing_data gives the finite table lg_setup wants first).  Accepted only on a thread-per-site
+        engine (p = 1, every belief of at most 2 variables, at least 8 sites; pgbp_patterns otherwise).  The call REPLACES
+        the previous mask; the next assignfactors_lg_ or loglik_lg uses it, beliefs and factors are not refilled by this
+        call.  The lanes-are-sites sweeps (gradient_sites_lg, shift_scan_sites_lg, edge_gradient_sites_lg, loo_sites_lg,
+        impute_sites_lg) read it; the general sweeps raise while it is in force.  A row without a tip, a tip the set-up's
+        child_mask already skips, or a site left with nothing observed raises and leaves the previous mask in force.
+        UNCOVERED ENTRIES: the device keeps 0.0 at every entry a mask has covered (the value there is never used).  A new
+        mask -- or None -- that no longer covers such an entry would make that 0.0 an observed value and the likelihood
+        silently wrong, so this wrapper raises ValueError, with nothing changed, unless `data` comes with the call (the C
+        call itself leaves this to its caller; include/pgbp.h).
+        mask="nan" without `data` reads the NaNs of what lg_setup or set_data_lg were last given: lg_setup takes no NaN
+        without a child_mask, so after a complete-data set-up that pattern is empty until set_data_lg has been given NaNs
+        under a mask -- pass the table as `data` instead."""
+        rows = int(self._lg["data"].shape[1])
+        if isinstance(mask, str) and mask == "nan" and data is None and self._lg_data_nan is None:
+            raise ValueError("set_site_missing_lg: mask='nan' but no data have been given")
+        old = getattr(self, "_lg_site_mask", None)
+        if old is not None and data is None:
+            if mask is None:
+                new = np.zeros_like(old)
+            elif isinstance(mask, str):
+                new = self._lg_data_nan if mask == "nan" else None
+            else:
+                new = np.asarray(mask).reshape(self.n_sites, rows) != 0
+            if new is not None and (old & ~new).any():
+                s_, r_ = np.argwhere(old & ~new)[0]
+                raise ValueError(f"set_site_missing_lg: {int((old & ~new).sum())} entries the mask in force covers (the first: site "
+                                 f"{int(s_)}, row {int(r_)}) would be uncovered and hold the 0.0 stored there; give `data` with the call")
+        if mask is None:
+            _check(self._lib.pgbp_lg_set_site_missing(self._eng, None), self._eng)
+            self._lg_site_mask = None
+        else:
+            if isinstance(mask, str):
+                if mask != "nan":
+                    raise ValueError("set_site_missing_lg: mask is a bool array, None or 'nan'")
+                src = self._lg_data_nan if data is None else np.isnan(np.asarray(data, np.float64).reshape(self.n_sites, rows))
+                if src is None:
+                    raise ValueError("set_site_missing_lg: mask='nan' but no data have been given")
+                mask = src
+            m = np.ascontiguousarray(np.asarray(mask).reshape(self.n_sites, rows) != 0, np.uint8)
+            _check(self._lib.pgbp_lg_set_site_missing(self._eng, m.ctypes.data_as(C.POINTER(C.c_uint8))), self._eng)
+            self._lg_site_mask = m.astype(bool) if m.any() else None
+        if data is not None:
+            self.set_data_lg(np.asarray(data, np.float64).reshape(self.n_sites, rows, 1))
+
+    def site_missing_lg(self):
+        """pgbp_lg_get_site_missing: the mask in force, bool [n_sites, n_rows]; all False when none is set."""
+        rows = int(self._lg["data"].shape[1])
+        m = np.zeros((self.n_sites, max(rows, 1)), np.uint8)
+        _check(self._lib.pgbp_lg_get_site_missing(self._eng, m.ctypes.data_as(C.POINTER(C.c_uint8))), self._eng)
+        return m.reshape(-1)[: self.n_sites * rows].reshape(self.n_sites, rows).astype(bool)
+
+    def site_missing_count_lg(self):
+        """pgbp_lg_site_missing_count: the number of masked (row, site) pairs (0: no mask)."""
+        return int(self._lib.pgbp_lg_site_missing_count(self._eng))
+
     def set_data_lg(self, data, all_sites=True):
         """pgbp_lg_set_data: replace the tip data given to lg_setup -- [n_sites, n_rows, p] (or [n_rows, p] on a one-site
         object; all_sites=False: [n_rows, p] or [1, n_rows, p] for the current site) -- without a new set-up.  The
         missing-data pattern stays the set-up's: an entry outside a tip's mask is ignored (NaN allowed), one inside it that is
         not finite raises and leaves the data as they were.  The next assignfactors_lg_ or loglik_lg uses the new data;
-        beliefs and factors are not refilled by this call."""
+        beliefs and factors are not refilled by this call.  With a per-site mask in force (set_site_missing_lg) an entry
+        it masks may hold anything, NaN included; the device stores 0 there."""
         s0, s1 = (0, self.n_sites) if all_sites else (self.site, self.site + 1)
         rows = int(self._lg["data"].shape[1])
         d = np.ascontiguousarray(np.asarray(data, np.float64).reshape(s1 - s0, rows, self._lg_p))
         _check(self._lib.pgbp_lg_set_data(self._eng, s0, s1, L.f64p(d if d.size else np.zeros(1))), self._eng)
+        if self._lg_p == 1 and self._lg_data_nan is not None:   # (what set_site_missing_lg("nan") reads)
+            self._lg_data_nan[s0:s1] = np.isnan(d[:, :, 0])
 
     def get_data_lg(self):
         """pgbp_lg_get_data: the tip data the device holds, [n_sites, n_rows, p] (what lg_setup, set_data_lg or
@@ -1651,13 +1720,29 @@ def loo_zscores(d):
 def imputed_data(d, data):
     """A copy of the data table [n_rows, p] (NaN where missing) with the entries the dict impute_lg returns predicts filled
     by their posterior mean (d["mean"] [n, p]: one site); every other missing entry stays NaN, and so does a tip whose info
-    is not 0.  On the host."""
+    is not 0 -- but for info -2 (PGBP_INFO_NOT_OBSERVED: a tip of impute_sites_lg that is observed at this site under a
+    per-site mask), whose entry of `data` is kept.  On the host."""
     out = np.array(data, dtype=np.float64, copy=True)
     mean, pred = np.asarray(d["mean"]), np.asarray(d["predicted"], bool)
     assert out.ndim == 2 and mean.ndim == 2, "one site: data [n_rows, p], d['mean'] [n, p]"
+    info = np.asarray(d["info"]) if d.get("info") is not None else None
     for i, r in enumerate(np.asarray(d["rows"])):
+        if info is not None and info.ndim == 1 and int(info[i]) == -2:
+            continue   # (PGBP_INFO_NOT_OBSERVED: a tip observed at this site under a per-site mask, nothing to fill)
         out[int(r), pred[i]] = mean[i, pred[i]]
     return out
+
+
+def split_missing_data(table, fill=0.0):
+    """A univariate data table with NaN at its gaps, [n_sites, n_rows] (or [n_sites, n_rows, 1]), as (clean, mask): clean
+    [n_sites, n_rows, 1] with `fill` at the gaps -- what lg_setup takes, which refuses values that are not finite -- and
+    mask bool [n_sites, n_rows], True at the gaps -- what set_site_missing_lg takes.  The value at a gap is never used."""
+    t = np.asarray(table, np.float64)
+    if t.ndim == 3:
+        assert t.shape[2] == 1, "per-site masks are univariate"
+        t = t[:, :, 0]
+    mask = np.isnan(t)
+    return np.where(mask, float(fill), t)[:, :, None], mask
 
 
 class _ResidualDict:

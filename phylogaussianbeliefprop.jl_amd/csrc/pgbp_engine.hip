@@ -17,6 +17,7 @@
 #include "pgbp_internal.hpp"
 #include "pgbp_kernels.hpp"
 #include "pgbp_lgmodel.hpp"
+#include "pgbp_sites_host.hpp"
 #include "pgbp_topology.hpp"
 
 using namespace pgbp;
@@ -1678,6 +1679,9 @@ static int lg_fill_async(pgbp_engine* e, bool also_factors, bool skip_sepsets = 
                            also_factors ? e->sm.fpool.get() : nullptr, e->d_packed_off.get(), e->d_bdim.get(), p.n_sites, e->st);
     launch_lg_noise_uni_sm(L.F, L.M, L.Sh, L.Nz, L.noise_bufs.cl.get(), L.n_noise_cl, e->sm.pool.get(),
                            also_factors ? e->sm.fpool.get() : nullptr, e->d_packed_off.get(), e->d_bdim.get(), p.n_sites, e->st);
+    launch_lg_sitemiss(L.F, L.M, L.Sh, L.Nz, L.Ms, L.miss_bufs.cl.get(), (int)L.miss.cl.size(), 1, e->sm.pool.get(), sm_row(p.n_sites),
+                       also_factors ? e->sm.fpool.get() : nullptr, sm_row(p.n_sites), e->d_packed_off.get(), e->d_bdim.get(), p.n_sites,
+                       e->st);
     const int64_t nc = p.packed_off[p.n_clusters] * sm_row(p.n_sites), nall = p.packed_off.back() * sm_row(p.n_sites);
     if (!skip_sepsets) HIPCHK(e, hipMemsetAsync(e->sm.pool.get() + nc, 0, sizeof(double) * (size_t)(nall - nc), e->st));  // sepsets = 1
   } else {
@@ -1693,6 +1697,11 @@ static int lg_fill_async(pgbp_engine* e, bool also_factors, bool skip_sepsets = 
     launch_lg_noise(L.F, L.M, L.Sh, L.Nz, L.noise_bufs.cl.get(), L.n_noise_cl, e->d_pool.get(), p.pool_stride(),
                     also_factors ? e->d_fpool.get() : nullptr, p.cluster_stride(), e->d_boff.get(), e->d_bdim.get(),
                     e->layout_bs16 ? 1 : 0, p.fast_p, L.noise_max_dim, p.n_sites, e->st);
+    if (L.Ms.words && e->layout_bs16)   // (a thread-per-site engine is never in the packed layout)
+      return e->fail(PGBP_ERR_STATE, "a per-site mask of missing tips is in force but the engine is in the packed layout");
+    launch_lg_sitemiss(L.F, L.M, L.Sh, L.Nz, L.Ms, L.miss_bufs.cl.get(), (int)L.miss.cl.size(), 0, e->d_pool.get(), p.pool_stride(),
+                       also_factors ? e->d_fpool.get() : nullptr, p.cluster_stride(), e->d_boff.get(), e->d_bdim.get(), p.n_sites,
+                       e->st);
     if (!skip_sepsets)
       launch_zero_strided(e->d_pool.get() + p.cluster_stride(), p.pool_stride(), p.pool_stride() - p.cluster_stride(),
                           p.n_sites, e->st);  // sepsets = 1 (init_beliefs_reset!)
@@ -1874,6 +1883,63 @@ int32_t pgbp_lg_tip_noise_count(pgbp_engine* e) {
   return e->lg->Nz.slot ? e->lg->Nz.n : 0;
 }
 
+int pgbp_lg_set_site_missing(pgbp_engine* e, const uint8_t* missing) {
+  DeviceScope device_scope(e);
+  if (!e) return PGBP_ERR_INVALID;
+  const char* fn = "pgbp_lg_set_site_missing";
+  if (!e->lg) return e->fail(PGBP_ERR_STATE, std::string(fn) + ": no family table (call pgbp_lg_setup first)");
+  LgModel& L = *e->lg;
+  if (!missing) {   // clear, on any engine with a table (kernels already enqueued may still read the old mask)
+    HIPCHK(e, hipStreamSynchronize(e->st));
+    L.miss_bufs = LgSiteMissBufs{};
+    L.Ms = LgSiteMiss{};
+    L.miss = SiteMissPack{};
+    return PGBP_OK;
+  }
+  // a thread-per-site engine, as the lanes-are-sites sweeps define it (pgbp_sites_host.hpp)
+  const SitesCall c{&L, engine_peek(e), engine_uni_view(e), 0};
+  int rc = sites_accept_engine(e, fn, "pgbp_patterns: one engine per missingness pattern", c);
+  if (rc) return rc;
+  const LgTable& T = L.T;
+  const SiteMissTable tab{e->plan.n_sites, T.n_rows, T.n_families, T.cluster.data(), T.data_row.data(), T.tip.data(),
+                          T.child_mask.empty() ? nullptr : T.child_mask.data()};
+  SiteMissPack P;
+  std::string why;
+  if (!site_missing_pack(tab, missing, P, why)) return e->fail(PGBP_ERR_INVALID, why);
+  if (P.count == 0) return pgbp_lg_set_site_missing(e, nullptr);   // nothing is masked: no mask, nothing is launched
+  LgSiteMissBufs B;
+  if ((rc = dev_alloc(e, B.words, P.words.size()))) return rc;
+  if ((rc = dev_alloc(e, B.cl, P.cl.size()))) return rc;
+  // every buffer exists: the copies, the 0.0 at the masked entries of both copies of the data, then ONE synchronisation
+  hipError_t herr = hipMemcpyAsync(B.words.get(), P.words.data(), P.words.size() * sizeof(unsigned long long), hipMemcpyHostToDevice, e->st);
+  if (herr == hipSuccess) herr = hipMemcpyAsync(B.cl.get(), P.cl.data(), P.cl.size() * sizeof(int32_t), hipMemcpyHostToDevice, e->st);
+  const LgSiteMiss Ms{B.words.get(), P.W};
+  if (herr == hipSuccess) {
+    launch_lg_sitemiss_zero(Ms, L.bufs.data.get(), L.bufs.data_sm.get(), T.n_rows, e->plan.n_sites, e->st);
+    herr = hipGetLastError();
+  }
+  const hipError_t serr = hipStreamSynchronize(e->st);  // the host buffers may go away; kernels that read the old mask have finished
+  if (herr == hipSuccess) herr = serr;
+  if (herr != hipSuccess) return e->fail(PGBP_ERR_HIP, std::string(fn) + " (upload): " + hipGetErrorString(herr));
+  L.miss_bufs = std::move(B);
+  L.Ms = Ms;
+  L.miss = std::move(P);
+  return PGBP_OK;
+}
+
+int pgbp_lg_get_site_missing(pgbp_engine* e, uint8_t* missing) {
+  if (!e) return PGBP_ERR_INVALID;
+  if (!e->lg) return e->fail(PGBP_ERR_STATE, "pgbp_lg_get_site_missing: no family table (call pgbp_lg_setup first)");
+  if (!missing) return e->fail(PGBP_ERR_INVALID, "pgbp_lg_get_site_missing: no buffer");
+  site_missing_unpack(e->lg->miss, e->plan.n_sites, e->lg->T.n_rows, missing);
+  return PGBP_OK;
+}
+
+int32_t pgbp_lg_site_missing_count(pgbp_engine* e) {
+  if (!e || !e->lg) return -1;
+  return e->lg->Ms.words ? (int32_t)std::min<int64_t>(e->lg->miss.count, INT32_MAX) : 0;
+}
+
 int pgbp_lg_set_topology(pgbp_engine* e, const int32_t* parent_family) {
   DeviceScope device_scope(e);
   if (!e) return PGBP_ERR_INVALID;
@@ -1905,7 +1971,8 @@ int pgbp_lg_set_topology(pgbp_engine* e, const int32_t* parent_family) {
 static int lg_check_data(pgbp_engine* e, const char* fn, int32_t site_begin, int32_t site_end, const double* data, bool values) {
   if (!e->lg) return e->fail(PGBP_ERR_STATE, std::string(fn) + ": no family table (call pgbp_lg_setup first)");
   std::string why;
-  if (!e->lg->T.check_data(fn, site_begin, site_end, data, values, why)) return e->fail(PGBP_ERR_INVALID, why);
+  if (!e->lg->T.check_data(fn, site_begin, site_end, data, values, why, e->lg->Ms.words ? &e->lg->miss : nullptr))
+    return e->fail(PGBP_ERR_INVALID, why);
   return PGBP_OK;
 }
 
@@ -1919,9 +1986,13 @@ int pgbp_lg_set_data(pgbp_engine* e, int32_t site_begin, int32_t site_end, const
   if (n == 0) return PGBP_OK;
   double* dst = L.bufs.data.get() + (size_t)site_begin * per;
   std::vector<double> clean;   // as the set-up: masked-out entries may be NaN on the host, they never reach arithmetic
-  if (!L.T.child_mask.empty()) {
+  if (!L.T.child_mask.empty() || L.Ms.words) {
     clean.assign(data, data + n);
     for (double& x : clean) if (!std::isfinite(x)) x = 0.0;
+    if (L.Ms.words)   // a per-site mask in force: 0.0 at its entries, whatever was given
+      for (int32_t s = site_begin; s < site_end; ++s)
+        for (int32_t r = 0; r < L.T.n_rows; ++r)
+          if (site_missing_test(L.miss, r, s)) clean[(size_t)(s - site_begin) * per + r] = 0.0;
     data = clean.data();
   }
   hipError_t herr = hipMemcpyAsync(dst, data, n * sizeof(double), hipMemcpyHostToDevice, e->st);

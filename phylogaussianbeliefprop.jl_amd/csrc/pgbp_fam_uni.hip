@@ -39,8 +39,8 @@ namespace pgbp {
 // jump, lr, hinf: [n_fam][row] (any may be null); pbest / pfam: [blocks][row], the largest lr of the block's families that
 // have an edge, are identified and whose lr is finite, and the first family that has it (-inf, -1: none); pinfo: [blocks][row]
 template <bool SM>
-__global__ __launch_bounds__(256) void fam_uni_scan(SitesArgs A, LgStatic F, LgParams M, LgShifts Sh, LgNoise Nz, int n_fam,
-                                                    double min_info, double* __restrict__ jump, double* __restrict__ lr,
+__global__ __launch_bounds__(256) void fam_uni_scan(SitesArgs A, LgStatic F, LgParams M, LgShifts Sh, LgNoise Nz, LgSiteMiss Ms,
+                                                    int n_fam, double min_info, double* __restrict__ jump, double* __restrict__ lr,
                                                     double* __restrict__ hinf, double* __restrict__ pbest,
                                                     int32_t* __restrict__ pfam, int32_t* __restrict__ pinfo) {
 #pragma clang fp contract(off)
@@ -52,7 +52,7 @@ __global__ __launch_bounds__(256) void fam_uni_scan(SitesArgs A, LgStatic F, LgP
   int bf = -1, bad = kFamUniNoInfo;
   const int f0 = fb * kFamUniBlock, f1 = min(f0 + kFamUniBlock, n_fam);
   for (int f = f0; f < f1; ++f) {
-    const FamUni X = fam_uni_family<SM>(A.pool, A.stride, A.off, A.bdim, F, M, Sh, Nz, S, A.fam_cluster, f, A.data_row_len, as);
+    const FamUni X = fam_uni_family<SM>(A.pool, A.stride, A.off, A.bdim, F, M, Sh, Nz, Ms, S, A.fam_cluster, f, A.data_row_len, as);
     double jv = NAN, lv = NAN, hv = NAN;
     if (X.skip) {
       lv = X.np == 0 ? (double)NAN : 0.0;
@@ -89,7 +89,7 @@ __global__ __launch_bounds__(256) void fam_uni_scan(SitesArgs A, LgStatic F, LgP
 
 // dlen, dgam: [n_fam][K][row], dshift: [n_fam][row] (any may be null); pinfo: [blocks][row]
 template <bool SM>
-__global__ __launch_bounds__(256) void fam_uni_edge(SitesArgs A, LgStatic F, LgParams M, LgShifts Sh, LgNoise Nz, int n_fam,
+__global__ __launch_bounds__(256) void fam_uni_edge(SitesArgs A, LgStatic F, LgParams M, LgShifts Sh, LgNoise Nz, LgSiteMiss Ms, int n_fam,
                                                     double* __restrict__ dlen, double* __restrict__ dgam,
                                                     double* __restrict__ dshift, int32_t* __restrict__ pinfo) {
 #pragma clang fp contract(off)
@@ -102,7 +102,7 @@ __global__ __launch_bounds__(256) void fam_uni_edge(SitesArgs A, LgStatic F, LgP
   int bad = kFamUniNoInfo;
   const int f0 = fb * kFamUniBlock, f1 = min(f0 + kFamUniBlock, n_fam);
   for (int f = f0; f < f1; ++f) {
-    const FamUni X = fam_uni_family<SM>(A.pool, A.stride, A.off, A.bdim, F, M, Sh, Nz, S, A.fam_cluster, f, A.data_row_len, as);
+    const FamUni X = fam_uni_family<SM>(A.pool, A.stride, A.off, A.bdim, F, M, Sh, Nz, Ms, S, A.fam_cluster, f, A.data_row_len, as);
     const int np = X.np;
     const bool fail = !X.skip && !(X.q.ok && X.V > 0.0);
     if (fail) bad = min(bad, X.c + 1);
@@ -137,7 +137,7 @@ __global__ __launch_bounds__(256) void fam_uni_edge(SitesArgs A, LgStatic F, LgP
 // tip_fam[ti]: the family of tip ti.  mean, var (either may be null), lpd: [n_tip][row]; info: [n_tip][row] (may be null);
 // psum: [blocks][row], the block's lpd added in tip order
 template <bool SM>
-__global__ __launch_bounds__(256) void fam_uni_loo(SitesArgs A, LgStatic F, LgParams M, LgShifts Sh, LgNoise Nz,
+__global__ __launch_bounds__(256) void fam_uni_loo(SitesArgs A, LgStatic F, LgParams M, LgShifts Sh, LgNoise Nz, LgSiteMiss Ms,
                                                    const int32_t* __restrict__ tip_fam, int n_tip, double* __restrict__ mean,
                                                    double* __restrict__ var, double* __restrict__ lpd,
                                                    int32_t* __restrict__ info, double* __restrict__ psum) {
@@ -150,10 +150,12 @@ __global__ __launch_bounds__(256) void fam_uni_loo(SitesArgs A, LgStatic F, LgPa
   const int t0 = tb * kFamUniBlock, t1 = min(t0 + kFamUniBlock, n_tip);
   for (int ti = t0; ti < t1; ++ti) {
     const int f = tip_fam[ti];
-    const FamUni X = fam_uni_family<SM>(A.pool, A.stride, A.off, A.bdim, F, M, Sh, Nz, S, A.fam_cluster, f, A.data_row_len, as);
+    const FamUni X = fam_uni_family<SM>(A.pool, A.stride, A.off, A.bdim, F, M, Sh, Nz, Ms, S, A.fam_cluster, f, A.data_row_len, as);
     double mv = NAN, vv = NAN, lv = NAN;
     int st = 1;
-    if (!X.skip && X.q.st != 0) {
+    if (X.masked) {
+      st = PGBP_INFO_NOT_OBSERVED;   // not observed at this site: nothing to leave out, nothing for the total
+    } else if (!X.skip && X.q.st != 0) {
       st = X.q.st > 0 ? 1 + X.q.st : 1;   // the cluster is not positive definite; the constant belief: u is undetermined
     } else if (!X.skip) {
       const double D = X.V - X.C;   // S = Var(u) = u' Sigma u over the cluster parents
@@ -169,7 +171,7 @@ __global__ __launch_bounds__(256) void fam_uni_loo(SitesArgs A, LgStatic F, LgPa
     if (var) var[o] = vv;
     lpd[o] = lv;
     if (info) info[o] = st;
-    acc = acc + lv;
+    if (!X.masked) acc = acc + lv;
   }
   psum[(int64_t)tb * A.row + s] = acc;
 }
@@ -268,7 +270,7 @@ extern "C" int pgbp_lg_shift_scan_sites(pgbp_engine* e, int32_t site_begin, int3
     const int n = std::min(chunk, ns - s0);
     const SitesArgs A = sites_args(c, site_begin + s0, n, chunk, d_fcl.get());
     const dim3 grid((n + 255) / 256, nfb);
-    PGBP_SITES_LAUNCH(S, c.U.sm, fam_uni_scan, grid, A, L->F, L->M, L->Sh, L->Nz, nf, min_info, d_jump.get(), d_lr.get(),
+    PGBP_SITES_LAUNCH(S, c.U.sm, fam_uni_scan, grid, A, L->F, L->M, L->Sh, L->Nz, L->Ms, nf, min_info, d_jump.get(), d_lr.get(),
                       d_hinf.get(), d_pbest.get(), d_pfam.get(), d_pinfo.get());
     S.launch(fam_uni_fold, dim3(grid.x), d_pinfo.get(), d_pbest.get(), d_pfam.get(), nullptr, nfb, n, (int64_t)chunk, d_info.get(),
              d_top.get(), d_topf.get(), nullptr, s0);
@@ -320,7 +322,7 @@ extern "C" int pgbp_lg_edge_gradient_sites(pgbp_engine* e, int32_t site_begin, i
     const int n = std::min(chunk, ns - s0);
     const SitesArgs A = sites_args(c, site_begin + s0, n, chunk, d_fcl.get());
     const dim3 grid((n + 255) / 256, nfb);
-    PGBP_SITES_LAUNCH(S, c.U.sm, fam_uni_edge, grid, A, L->F, L->M, L->Sh, L->Nz, nf, d_len.get(), d_gam.get(), d_shift.get(),
+    PGBP_SITES_LAUNCH(S, c.U.sm, fam_uni_edge, grid, A, L->F, L->M, L->Sh, L->Nz, L->Ms, nf, d_len.get(), d_gam.get(), d_shift.get(),
                       d_pinfo.get());
     S.launch(fam_uni_fold, dim3(grid.x), d_pinfo.get(), nullptr, nullptr, nullptr, nfb, n, (int64_t)chunk, d_info.get(), nullptr,
              nullptr, nullptr, s0);
@@ -377,7 +379,7 @@ extern "C" int pgbp_lg_loo_sites(pgbp_engine* e, int32_t site_begin, int32_t sit
     const int n = std::min(chunk, ns - s0);
     const SitesArgs A = sites_args(c, site_begin + s0, n, chunk, d_fcl.get());
     const dim3 grid((n + 255) / 256, ntb);
-    PGBP_SITES_LAUNCH(S, c.U.sm, fam_uni_loo, grid, A, L->F, L->M, L->Sh, L->Nz, d_tips.get(), nt, d_mean.get(), d_var.get(),
+    PGBP_SITES_LAUNCH(S, c.U.sm, fam_uni_loo, grid, A, L->F, L->M, L->Sh, L->Nz, L->Ms, d_tips.get(), nt, d_mean.get(), d_var.get(),
                       d_lpd.get(), d_info.get(), d_psum.get());
     S.launch(fam_uni_fold, dim3(grid.x), nullptr, nullptr, nullptr, d_psum.get(), ntb, n, (int64_t)chunk, nullptr, nullptr, nullptr,
              d_total.get(), s0);

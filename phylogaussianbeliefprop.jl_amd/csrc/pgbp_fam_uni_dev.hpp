@@ -14,6 +14,7 @@
 
 #include "pgbp_fam_dev.hpp"
 #include "pgbp_kernels.hpp"
+#include "pgbp_sitemiss_dev.hpp"
 
 namespace pgbp {
 
@@ -93,11 +94,12 @@ __device__ __forceinline__ FamUniParent fam_uni_parent(const LgStatic& F, const 
   return P;
 }
 
-// A family at a site.  skip: the factor fill skips it (child_mask == 0), or it is the root-prior family of a fixed root, which
-// has no factor -- nothing else is set then.  y: the tip's data value (0 when the child is not a tip with data).
+// A family at a site.  skip: the factor fill skips it (child_mask == 0, or a tip the per-site mask says is not observed at this
+// site: masked), or it is the root-prior family of a fixed root, which has no factor -- nothing else is set then.  y: the tip's
+// data value (0 when the child is not a tip with data).
 struct FamUni {
   int np, cpos, c, sn;
-  bool skip;
+  bool skip, masked;
   FamUniMom q;
   double u0, u1, cst, V, w, y;
   // what the sweeps form from them
@@ -107,7 +109,7 @@ struct FamUni {
 template <bool SM>
 __device__ __forceinline__ FamUni fam_uni_family(const double* __restrict__ pool, int64_t stride, const int64_t* __restrict__ off,
                                                  const int32_t* __restrict__ bdim, const LgStatic& F, const LgParams& M,
-                                                 const LgShifts& Sh, const LgNoise& Nz, const LgSite& S,
+                                                 const LgShifts& Sh, const LgNoise& Nz, const LgSiteMiss& Ms, const LgSite& S,
                                                  const int32_t* __restrict__ fam_cluster, int f, int64_t data_row_len, int64_t as) {
 #pragma clang fp contract(off)
   FamUni A;
@@ -117,7 +119,8 @@ __device__ __forceinline__ FamUni fam_uni_family(const double* __restrict__ pool
   A.cpos = cpos;
   A.c = fam_cluster[f];
   A.sn = -1;
-  A.skip = (F.child_mask && !(F.child_mask[f] & 1ull)) || (np == 0 && cpos < 0);
+  A.masked = lg_site_masked_family(Ms, F, f, as);
+  A.skip = (F.child_mask && !(F.child_mask[f] & 1ull)) || (np == 0 && cpos < 0) || A.masked;
   A.q = FamUniMom{0.0, 0.0, 0.0, 0.0, 0.0, 0, true};
   A.u0 = A.u1 = A.cst = A.V = A.w = A.y = 0.0;
   A.e = A.su0 = A.su1 = A.C = A.j = A.gw = 0.0;

@@ -226,7 +226,7 @@ static int lg_gradient(pgbp_engine* e, int32_t site_begin, int32_t site_end, dou
                        double* dtheta, double* dsigma_e, int32_t* info) {
   if (!e) return PGBP_ERR_INVALID;
   const LgModel* L = nullptr;
-  int rc = lg_sweep_state(e, "pgbp_lg_gradient", site_begin, site_end, &L);
+  int rc = lg_sweep_state(e, "pgbp_lg_gradient", site_begin, site_end, &L, "pgbp_lg_gradient_sites");
   if (rc) return rc;
   const LgStatic& F = L->F;
   const LgParams& M = L->M;

@@ -45,7 +45,7 @@ __host__ __device__ inline int grad_uni_entries(int nr) { return nr + 4; }
 template <bool SM>
 __global__ __launch_bounds__(256) void grad_uni_family(const double* __restrict__ pool, int64_t stride,
                                                        const int64_t* __restrict__ off, const int32_t* __restrict__ bdim,
-                                                       LgStatic F, LgParams M, LgShifts Sh, LgNoise Nz,
+                                                       LgStatic F, LgParams M, LgShifts Sh, LgNoise Nz, LgSiteMiss Ms,
                                                        const int32_t* __restrict__ fam_cluster, int n_fam, int64_t data_row_len,
                                                        int site0, int n_sites, int r0, int64_t part_row,
                                                        double* __restrict__ partial, int32_t* __restrict__ pinfo) {
@@ -68,6 +68,15 @@ __global__ __launch_bounds__(256) void grad_uni_family(const double* __restrict_
     // families the factor fill skips contribute nothing (and a root-prior family of a fixed root, which has no factor)
     if (F.child_mask && !(F.child_mask[f] & 1ull)) continue;
     if (np == 0 && cpos < 0) continue;
+    // u and the constant part of the child; a tip the per-site mask says is not observed at this site is skipped as above
+    double u0 = 0.0, u1 = 0.0, cst = 0.0;
+    if (cpos == 0) u0 = 1.0;
+    else if (cpos == 1) u1 = 1.0;
+    else if (F.data_row[f] >= 0) {   // a tip: its data row, [row][site] where the engine keeps that copy
+      const int row = F.data_row[f];
+      if (np > 0 && lg_site_masked(Ms, row, as)) continue;
+      cst = F.data_sm ? F.data_sm[(int64_t)row * data_row_len + as] : F.data[as * F.n_rows + row];
+    }
     const int c = fam_cluster[f];
     bool any_scope = cpos >= 0;
     for (int k = 0; k < np; ++k) any_scope |= F.parent_pos[(size_t)f * K + k] >= 0;
@@ -76,12 +85,8 @@ __global__ __launch_bounds__(256) void grad_uni_family(const double* __restrict_
     if (any_scope) q = fam_uni_moments<SM>(pool, stride, off[c], bdim[c], as);
     const double S00 = q.S00, S01 = q.S01, S11 = q.S11, m0 = q.m0, m1 = q.m1;
     bool ok = q.ok;
-    // one pass over the blocks: u, the constant part, V, w, the chain-rule coefficients and the sums of the alpha term
-    double u0 = 0.0, u1 = 0.0, cst = 0.0;
-    if (cpos == 0) u0 = 1.0;
-    else if (cpos == 1) u1 = 1.0;
-    else if (F.data_row[f] >= 0)   // a tip: its data row, [row][site] where the engine keeps that copy
-      cst = F.data_sm ? F.data_sm[(int64_t)F.data_row[f] * data_row_len + as] : F.data[as * F.n_rows + F.data_row[f]];
+    // one pass over the blocks: V, w, the rest of u and of the constant part, the chain-rule coefficients and the sums of
+    // the alpha term
     double V = 0.0, w = 0.0, cmu = 0.0, cth = 0.0;
     double A1 = 0.0, A2 = 0.0, A3 = 0.0, D0 = 0.0, D1 = 0.0;   // sum dvc R_k, sum dwc, sum dqc x_k, sum dqc at variable 0 / 1
     double cr[kGradUniRates];
@@ -219,7 +224,7 @@ extern "C" int pgbp_lg_gradient_sites(pgbp_engine* e, int32_t site_begin, int32_
     const SitesArgs A = sites_args(c, site_begin + s0, n, chunk, d_fcl.get());
     const dim3 grid((n + 255) / 256, nfb);
     for (int r0 = 0; r0 == 0 || r0 < nr; r0 += kGradUniRates)
-      PGBP_SITES_LAUNCH(S, c.U.sm, grad_uni_family, grid, A.pool, A.stride, A.off, A.bdim, L->F, L->M, L->Sh, L->Nz, A.fam_cluster, nf,
+      PGBP_SITES_LAUNCH(S, c.U.sm, grad_uni_family, grid, A.pool, A.stride, A.off, A.bdim, L->F, L->M, L->Sh, L->Nz, L->Ms, A.fam_cluster, nf,
                         A.data_row_len, A.site0, A.n_sites, r0, A.row, d_part.get(), d_pinfo.get());
     S.launch(grad_uni_reduce, dim3(grid.x, n_ent + 1), d_part.get(), d_pinfo.get(), nfb, n_ent, n, (int64_t)chunk, d_out.get(),
              d_info.get(), s0, (int64_t)ns);

@@ -265,7 +265,7 @@ extern "C" int32_t pgbp_lg_impute_count(pgbp_engine* e) {
   if (!L) return engine_fail(e, PGBP_ERR_STATE, "pgbp_lg_impute_count: no family table (call pgbp_lg_setup first)"), -1;
   std::vector<int32_t> fams;
   std::vector<unsigned long long> pred;
-  L->T.impute_list(fams, pred);
+  lg_impute_list(*L, fams, pred);   // (with the tips a per-site mask hides at some site: pgbp_lg_impute_sites)
   return (int32_t)fams.size();
 }
 
@@ -275,7 +275,7 @@ extern "C" int pgbp_lg_impute_families(pgbp_engine* e, int32_t* fam, uint64_t* p
   if (!L) return engine_fail(e, PGBP_ERR_STATE, "pgbp_lg_impute_families: no family table (call pgbp_lg_setup first)");
   std::vector<int32_t> fams;
   std::vector<unsigned long long> pred;
-  L->T.impute_list(fams, pred);
+  lg_impute_list(*L, fams, pred);
   if (fam) std::copy(fams.begin(), fams.end(), fam);
   if (predicted)
     for (size_t i = 0; i < pred.size(); ++i) predicted[i] = (uint64_t)pred[i];
@@ -287,7 +287,7 @@ extern "C" void pgbp_impute_scratch_limit(int64_t doubles) { g_impute_limit.stor
 extern "C" int pgbp_lg_impute(pgbp_engine* e, int32_t site_begin, int32_t site_end, double* mean, double* cov, int32_t* info) {
   if (!e) return PGBP_ERR_INVALID;
   const LgModel* L = nullptr;
-  int rc = lg_sweep_state(e, "pgbp_lg_impute", site_begin, site_end, &L);
+  int rc = lg_sweep_state(e, "pgbp_lg_impute", site_begin, site_end, &L, "pgbp_lg_impute_sites");
   if (rc) return rc;
   const LgStatic& F = L->F;
   const LgParams& M = L->M;

@@ -237,6 +237,22 @@ void launch_lg_noise(const LgStatic& F, const LgParams& M, const LgShifts& S, co
 void launch_lg_noise_uni_sm(const LgStatic& F, const LgParams& M, const LgShifts& S, const LgNoise& Nz, const int32_t* d_ncl,
                             int n_ncl, double* pool_sm, double* fpool_sm, const int64_t* d_poff, const int32_t* d_dim,
                             int n_sites, hipStream_t st);
+// Per-site missing tips of a univariate batch (pgbp_lg_set_site_missing): bit (s & 63) of word [row][s >> 6] set = the tip with
+// that data row is not observed at site s.  A struct of its own, as LgShifts and LgNoise are.  words == null: no mask is set.
+struct LgSiteMiss {
+  const unsigned long long* words;   // [n_rows][W]
+  int32_t W;                         // ceil(n_sites / 64)
+};
+// the correction of a fill for the mask (pgbp_sitemiss.hip), launched after the fill and its shift and noise corrections:
+// lanes = sites, one row of workgroups per cluster of d_mcl (the clusters that hold a tip family masked at some site); a thread
+// whose site masks a family of the cluster rewrites the cluster's record in pool and, when not null, fpool, without the masked
+// families; every other thread stores nothing.  sm != 0: the site-minor layout (off: packed offsets, stride / fstride: the row
+// length), else the plain one (off: Plan::boff, stride / fstride: doubles per site of pool / fpool)
+void launch_lg_sitemiss(const LgStatic& F, const LgParams& M, const LgShifts& S, const LgNoise& Nz, const LgSiteMiss& Ms,
+                        const int32_t* d_mcl, int n_mcl, int sm, double* pool, int64_t stride, double* fpool, int64_t fstride,
+                        const int64_t* d_off, const int32_t* d_dim, int n_sites, hipStream_t st);
+// the setter's own step: 0.0 into data [site][row] and data_sm [row][site] at every masked entry
+void launch_lg_sitemiss_zero(const LgSiteMiss& Ms, double* data, double* data_sm, int n_rows, int n_sites, hipStream_t st);
 // one workgroup per (cluster, site); pool / fpool in the current layout (fpool may be null: beliefs only)
 void launch_lg_fill(const LgStatic& F, const LgParams& M, double* pool, int64_t pool_stride, double* fpool,
                     int64_t fpool_stride, const int64_t* d_boff, const int32_t* d_dim, int bs16, int fast_p, int max_dim,

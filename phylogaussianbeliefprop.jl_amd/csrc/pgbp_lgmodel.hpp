@@ -8,6 +8,7 @@
 #include "pgbp_devmem.hpp"
 #include "pgbp_kernels.hpp"
 #include "pgbp_lgtable.hpp"
+#include "pgbp_sitemiss_host.hpp"
 
 namespace pgbp {
 
@@ -30,6 +31,12 @@ struct LgNoiseBufs {
   DevBuf<double> scale, sigma_e, se2, se2_sm;
 };
 
+// what LgSiteMiss points at (pgbp_lg_set_site_missing), and the clusters the correction kernel visits
+struct LgSiteMissBufs {
+  DevBuf<unsigned long long> words;
+  DevBuf<int32_t> cl;
+};
+
 struct LgModel {
   LgTable T;
   LgBufs bufs;
@@ -44,6 +51,10 @@ struct LgModel {
   LgNoiseBufs noise_bufs;
   LgNoise Nz{};
   int32_t n_noise_cl = 0, noise_max_dim = 0;
+  // pgbp_lg_set_site_missing: Ms.words == null: none; the mask on the host (words, the masked tip families, their clusters)
+  LgSiteMissBufs miss_bufs;
+  LgSiteMiss Ms{};
+  SiteMissPack miss;
   // pgbp_lg_set_topology (d_pf null: none): parents by family [n_families * K] and the families grouped by level
   // (pgbp_topology.hpp); improper: the first entry f * K + k that is an improper root, -1: none
   DevBuf<int32_t> d_pf, d_level_fam;
@@ -55,16 +66,44 @@ struct LgModel {
 const LgModel* engine_lg(const pgbp_engine* e);
 
 // What a sweep `fn` checks of the engine's state before anything else, in this order: a table, parameters, the site range.
-// PGBP_OK with *out, or engine_fail's code.
-inline int lg_sweep_state(pgbp_engine* e, const char* fn, int32_t site_begin, int32_t site_end, const LgModel** out) {
+// PGBP_OK with *out, or engine_fail's code.  sites_call: for a general sweep, whose kernels cannot honour a per-site mask, the
+// lanes-are-sites call to use while one is in force (pgbp_lg_set_site_missing); null: the call reads the mask itself.
+inline int lg_sweep_state(pgbp_engine* e, const char* fn, int32_t site_begin, int32_t site_end, const LgModel** out,
+                          const char* sites_call = nullptr) {
   const LgModel* L = engine_lg(e);
   if (!L) return engine_fail(e, PGBP_ERR_STATE, std::string(fn) + ": no family table (call pgbp_lg_setup first)");
+  if (sites_call && L->Ms.words)
+    return engine_fail(e, PGBP_ERR_INVALID, std::string(fn) + ": a per-site mask of missing tips is in force (pgbp_lg_set_site_missing), "
+                                                "which this sweep cannot honour (use " + sites_call + ")");
   if (!L->have_params)
     return engine_fail(e, PGBP_ERR_STATE, std::string(fn) + ": no parameters yet (call pgbp_lg_assignfactors first)");
   if (site_begin < 0 || site_end < site_begin || site_end > engine_n_sites(e))
     return engine_fail(e, PGBP_ERR_INVALID, std::string(fn) + ": site range outside the engine's sites");
   *out = L;
   return PGBP_OK;
+}
+
+// The families pgbp_lg_impute_count / _families / _sites list: the statically missing tips of the table (impute_list) and, with
+// a per-site mask in force, every tip masked at some site, merged in family order.  dyn[i] != 0: family i of the list is
+// observed wherever the mask does not say otherwise (its predicted mask is then 1: p = 1, every parent in scope).
+inline void lg_impute_list(const LgModel& L, std::vector<int32_t>& fams, std::vector<unsigned long long>& pred,
+                           std::vector<int32_t>* dyn = nullptr) {
+  std::vector<int32_t> f0;
+  std::vector<unsigned long long> p0;
+  L.T.impute_list(f0, p0);
+  fams.clear();
+  pred.clear();
+  if (dyn) dyn->clear();
+  const std::vector<int32_t>& f1 = L.Ms.words ? L.miss.fams : std::vector<int32_t>();
+  size_t a = 0, b = 0;
+  while (a < f0.size() || b < f1.size()) {
+    const bool take0 = b >= f1.size() || (a < f0.size() && f0[a] <= f1[b]);
+    if (take0 && b < f1.size() && f0[a] == f1[b]) ++b;   // (the setter refuses a statically missing tip: not reached)
+    fams.push_back(take0 ? f0[a] : f1[b]);
+    pred.push_back(take0 ? p0[a] : 1ull);
+    if (dyn) dyn->push_back(take0 ? 0 : 1);
+    if (take0) ++a; else ++b;
+  }
 }
 
 }  // namespace pgbp

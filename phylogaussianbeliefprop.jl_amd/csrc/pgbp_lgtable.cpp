@@ -153,13 +153,23 @@ void LgTable::set_edges(const double* new_length, const double* new_gamma) {
 }
 
 bool LgTable::check_data(const char* fn, int32_t site_begin, int32_t site_end, const double* data, bool values,
-                         std::string& why) const {
+                         std::string& why, const SiteMissPack* miss) const {
   if (site_begin < 0 || site_end < site_begin || site_end > n_sites)
     return refuse(why, std::string(fn) + ": site range [" + std::to_string(site_begin) + ", " + std::to_string(site_end) +
                            ") outside the engine's " + std::to_string(n_sites) + " sites");
   const size_t per = (size_t)n_rows * p, ns = (size_t)(site_end - site_begin);
   if (ns * per > 0 && !data) return refuse(why, std::string(fn) + ": no data buffer");
   if (!values) return true;
+  if (miss && !miss->words.empty()) {   // (p = 1: the mask is accepted on univariate tables only)
+    for (int f = 0; f < n_families; ++f) {
+      if (!tip[f] || (!child_mask.empty() && !(child_mask[f] & 1ull))) continue;
+      for (size_t s = 0; s < ns; ++s)
+        if (!site_missing_test(*miss, data_row[f], site_begin + (int32_t)s) && !std::isfinite(data[(s * n_rows + data_row[f]) * p]))
+          return refuse(why, std::string(fn) + ": family " + std::to_string(f) + ", site " + std::to_string(site_begin + (int32_t)s) +
+                        ": a tip value is missing or not finite where neither child_mask nor the per-site mask says so");
+    }
+    return true;
+  }
   if (child_mask.empty()) {
     for (size_t i = 0; i < ns * per; ++i)
       if (!std::isfinite(data[i]))

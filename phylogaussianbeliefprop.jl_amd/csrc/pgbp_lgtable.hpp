@@ -7,6 +7,7 @@
 #include <vector>
 
 #include "../../include/pgbp.h"
+#include "pgbp_sitemiss_host.hpp"
 
 namespace pgbp {
 
@@ -43,7 +44,9 @@ struct LgTable {
   // ... and, after the check: the table's copies and those of the simple records
   void set_edges(const double* new_length, const double* new_gamma);
   // pgbp_lg_set_data / pgbp_lg_get_data (`fn`): the site range, the buffer and -- values -- finite where the table says observed
-  bool check_data(const char* fn, int32_t site_begin, int32_t site_end, const double* data, bool values, std::string& why) const;
+  // (miss: the per-site mask in force, null: none -- an entry it masks is not observed and may hold anything)
+  bool check_data(const char* fn, int32_t site_begin, int32_t site_end, const double* data, bool values, std::string& why,
+                  const SiteMissPack* miss = nullptr) const;
   // pgbp_lg_set_shifts: slot [max(1, n_families * K)] = index into the list of the shift on that edge, -1: none; cl = the
   // clusters that hold a shifted family, sorted, each once
   bool shift_list(int32_t n_shifts, const int32_t* edge, const double* value, int32_t per_site, std::vector<int32_t>& slot,

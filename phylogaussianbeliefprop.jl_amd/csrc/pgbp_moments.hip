@@ -483,6 +483,9 @@ extern "C" int pgbp_bm_exact_stats(pgbp_engine* e, int32_t site_begin, int32_t s
   if (site_begin < 0 || site_end < site_begin || site_end > engine_n_sites(e))
     return engine_fail(e, PGBP_ERR_INVALID, "pgbp_bm_exact_stats: site range outside the engine's sites");
   if (!num || !den) return engine_fail(e, PGBP_ERR_INVALID, "pgbp_bm_exact_stats: no output buffer");
+  if (L->Ms.words)
+    return engine_fail(e, PGBP_ERR_INVALID, "pgbp_bm_exact_stats: a per-site mask of missing tips is in force (pgbp_lg_set_site_missing), "
+                                            "which this sweep cannot honour (use pgbp_lg_gradient_sites: fit_sites_lg)");
   EngineView v;
   int rc = engine_view(e, &v);
   if (rc) return rc;

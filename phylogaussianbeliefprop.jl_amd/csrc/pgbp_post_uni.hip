@@ -96,11 +96,13 @@ __global__ __launch_bounds__(256) void post_uni_moments(SitesArgs A, const PostM
 
 // ---- imputation
 
-// fam[ti]: the listed family ti, pred[ti]: its mask of predicted traits; mean, var (either may be null), info: [n_list][row]
+// fam[ti]: the listed family ti, pred[ti]: its mask of predicted traits, dyn[ti] != 0: listed because the per-site mask hides it
+// at some site, and observed (nothing to predict) at every other; mean, var (either may be null), info: [n_list][row]
 template <bool SM>
-__global__ __launch_bounds__(256) void post_uni_impute(SitesArgs A, LgStatic F, LgParams M, LgShifts Sh, LgNoise Nz,
+__global__ __launch_bounds__(256) void post_uni_impute(SitesArgs A, LgStatic F, LgParams M, LgShifts Sh, LgNoise Nz, LgSiteMiss Ms,
                                                        const int32_t* __restrict__ fam, const int32_t* __restrict__ fcl,
-                                                       const unsigned long long* __restrict__ pred, int n_list,
+                                                       const unsigned long long* __restrict__ pred,
+                                                       const int32_t* __restrict__ dyn, int n_list,
                                                        double* __restrict__ mean, double* __restrict__ var,
                                                        int32_t* __restrict__ info) {
 #pragma clang fp contract(off)
@@ -115,7 +117,9 @@ __global__ __launch_bounds__(256) void post_uni_impute(SitesArgs A, LgStatic F, 
     const int f = fam[ti];
     double mv = NAN, vv = NAN;
     int st = -1;   // nothing of this tip is predicted: a cluster parent lacks the trait
-    if (pred[ti] & 1ull) {
+    if (dyn[ti] && !lg_site_masked_family(Ms, F, f, as)) {
+      st = PGBP_INFO_NOT_OBSERVED;   // observed at this site: nothing to impute
+    } else if (pred[ti] & 1ull) {
       const int np = F.n_parents[f], c = fcl[ti];
       bool any_scope = false;
       for (int k = 0; k < np; ++k) any_scope |= F.parent_pos[(size_t)f * K + k] >= 0;
@@ -282,15 +286,15 @@ extern "C" int pgbp_lg_impute_sites(pgbp_engine* e, int32_t site_begin, int32_t 
                           (!mean && !var) ? "no output buffer (mean and var are both NULL)" : nullptr, &c);
   if (rc) return rc;
   const LgModel* L = c.L;
-  std::vector<int32_t> fams, cls;
+  std::vector<int32_t> fams, cls, dyn;
   std::vector<unsigned long long> pred;
-  L->T.impute_list(fams, pred);
+  lg_impute_list(*L, fams, pred, &dyn);   // (with the tips the per-site mask hides at some site)
   for (int32_t f : fams) cls.push_back(L->T.cluster[f]);
   const int ns = c.ns, nl = (int)fams.size();
   if (ns == 0 || nl == 0) return PGBP_OK;
   const int nb = (nl + kFamUniBlock - 1) / kFamUniBlock;
   const int chunk = fam_uni_chunk(ns, (int64_t)nl * ((mean ? 1 : 0) + (var ? 1 : 0) + (info ? 1 : 0)));
-  DevBuf<int32_t> d_fams, d_cls, d_info;
+  DevBuf<int32_t> d_fams, d_cls, d_dyn, d_info;
   DevBuf<unsigned long long> d_pred;
   DevBuf<double> d_mean, d_var;
   const size_t tab = (size_t)nl * chunk;
@@ -298,18 +302,20 @@ extern "C" int pgbp_lg_impute_sites(pgbp_engine* e, int32_t site_begin, int32_t 
   S.alloc(d_fams, nl);
   S.alloc(d_cls, nl);
   S.alloc(d_pred, nl);
+  S.alloc(d_dyn, nl);
   S.alloc(d_mean, tab, mean != nullptr);
   S.alloc(d_var, tab, var != nullptr);
   S.alloc(d_info, tab, info != nullptr);
   S.upload(d_fams, fams.data(), nl);
   S.upload(d_cls, cls.data(), nl);
   S.upload(d_pred, pred.data(), nl);
+  S.upload(d_dyn, dyn.data(), nl);
   if ((rc = S.ready())) return rc;
   for (int s0 = 0; S.ok() && s0 < ns; s0 += chunk) {
     const int nn = std::min(chunk, ns - s0);
     const SitesArgs A = sites_args(c, site_begin + s0, nn, chunk);
     const dim3 grid((nn + 255) / 256, nb);
-    PGBP_SITES_LAUNCH(S, c.U.sm, post_uni_impute, grid, A, L->F, L->M, L->Sh, L->Nz, d_fams.get(), d_cls.get(), d_pred.get(), nl,
+    PGBP_SITES_LAUNCH(S, c.U.sm, post_uni_impute, grid, A, L->F, L->M, L->Sh, L->Nz, L->Ms, d_fams.get(), d_cls.get(), d_pred.get(), d_dyn.get(), nl,
                       d_mean.get(), d_var.get(), d_info.get());
     S.check();
     S.rows(mean, ns, s0, d_mean.get(), chunk, nn, nl);

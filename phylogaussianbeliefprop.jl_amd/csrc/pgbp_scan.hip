@@ -216,7 +216,7 @@ extern "C" int pgbp_lg_shift_scan(pgbp_engine* e, int32_t site_begin, int32_t si
   if (L->T.p > 64)   // (a table the scan cannot serve, whatever its parameters)
     return engine_fail(e, PGBP_ERR_INVALID,
                        "pgbp_lg_shift_scan: p = " + std::to_string(L->T.p) + " traits, more than the 64 of a trait mask");
-  int rc = lg_sweep_state(e, "pgbp_lg_shift_scan", site_begin, site_end, &L);
+  int rc = lg_sweep_state(e, "pgbp_lg_shift_scan", site_begin, site_end, &L, "pgbp_lg_shift_scan_sites");
   if (rc) return rc;
   const LgStatic& F = L->F;
   const LgParams& M = L->M;

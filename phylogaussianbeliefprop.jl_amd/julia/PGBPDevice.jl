@@ -554,6 +554,39 @@ Number of noisy tips in force (pgbp_lg_tip_noise_count): 0 when none is set, -1 
 lg_tip_noise_count(o::DeviceClusterGraphBelief) = Int(@ccall LIB.pgbp_lg_tip_noise_count(o.handle::Ptr{Cvoid})::Int32)
 
 """
+    lg_set_site_missing!(obj, missing)
+
+Per-site missing tips of a univariate batch (pgbp_lg_set_site_missing): `missing` is an `n_rows x n_sites` array of Bool (or
+any integer type), `true` where the tip with that data row is NOT observed at that site; `nothing` clears the mask.  Accepted
+only on a thread-per-site engine (p = 1, every belief of at most 2 variables, at least 8 sites).  The call replaces the previous
+mask; the next pgbp_lg_assignfactors or pgbp_enqueue_loglik_lg uses it, and the lanes-are-sites sweeps read it.  A row without
+a tip, a tip the set-up's child_mask already skips, or a site left with nothing observed is an error and nothing changes.
+"""
+function lg_set_site_missing!(o::DeviceClusterGraphBelief, missing::Union{Nothing,AbstractMatrix})
+    m = missing === nothing ? Ptr{UInt8}(C_NULL) : Matrix{UInt8}(missing .!= 0)
+    check(o.handle, @ccall LIB.pgbp_lg_set_site_missing(o.handle::Ptr{Cvoid}, m::Ptr{UInt8})::Cint)
+    return nothing
+end
+
+"""
+    lg_site_missing(obj, n_rows, n_sites) -> Matrix{Bool}
+
+The mask in force (pgbp_lg_get_site_missing), `n_rows x n_sites`; all `false` when none is set.
+"""
+function lg_site_missing(o::DeviceClusterGraphBelief, n_rows::Integer, n_sites::Integer)
+    m = zeros(UInt8, max(n_rows, 1), max(n_sites, 1))
+    check(o.handle, @ccall LIB.pgbp_lg_get_site_missing(o.handle::Ptr{Cvoid}, m::Ptr{UInt8})::Cint)
+    return reshape(m[1:n_rows * n_sites], n_rows, n_sites) .!= 0
+end
+
+"""
+    lg_site_missing_count(obj) -> Int
+
+Number of masked (row, site) pairs in force (pgbp_lg_site_missing_count): 0 when no mask is set, -1 without a family table.
+"""
+lg_site_missing_count(o::DeviceClusterGraphBelief) = Int(@ccall LIB.pgbp_lg_site_missing_count(o.handle::Ptr{Cvoid})::Int32)
+
+"""
     lg_shift_scan(obj, p, nfamilies; min_info = 1e-8) -> (jump, lr, identified, information)
 
 Every edge scanned for a mean shift from the current beliefs (pgbp_lg_shift_scan: one sweep over the node families).  Per

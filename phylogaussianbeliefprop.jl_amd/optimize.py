@@ -591,7 +591,10 @@ def fit_sites_lg(beliefs, schedule_tree, model, R0, mu0, alpha0=None, theta0=Non
     loglik_and_gradient_sites_lg (reset, calibrate, root integrate, the lanes-are-sites sweep) -- driven by lbfgs_sites.
     A site stops when max|g| <= gtol max(1, |loglik|) in the transformed parameters, or after maxiter steps.
     Returns a dict of per-site arrays R, mu, alpha, theta (alpha, theta: NaN under BM), loglik, converged, n_iter, and
-    n_device_evals; the engine is left filled and calibrated at the estimates."""
+    n_device_evals; the engine is left filled and calibrated at the estimates.
+    A per-site mask of missing tips (set_site_missing_lg) needs no change here: every evaluation refills the factors, whose
+    correction skips the masked tips of each site, and the gradient sweep reads the same mask -- each site is fitted to its
+    own observed tips (tests/test_gpu_site_missing.py: against the closed-form GLS optimum of every site)."""
     if model not in ("bm", "ou"):
         raise ValueError(f"fit_sites_lg: model must be 'bm' or 'ou', not {model!r}")
     ou = model == "ou"
