@@ -701,6 +701,38 @@ int  pgbp_lg_impute_sites(pgbp_engine* e, int32_t site_begin, int32_t site_end, 
  * ms4[0 .. 3] = wall milliseconds of {validity pass, copy of z, level launches, copy of x}, summed over the chunks. */
 int  pgbp_sample_posterior_sites_timed(pgbp_engine* e, int32_t tree, int32_t site_begin, int32_t site_end, int32_t n_draws,
                                        const double* z, uint64_t seed, double* x, int32_t* info, double* ms4);
+/* CLOSED-FORM BM FIT OF EVERY SITE OF A UNIVARIATE BATCH, LANES = SITES (csrc/pgbp_exact_uni.hip): the family sweep of
+ * pgbp_bm_exact_stats (src/calibration.jl:440-499) in the frame of the calls above, with the per-site mask of missing tips
+ * (pgbp_lg_set_site_missing), the shifts in force and the root's posterior mean in the same call.  THE CALLER GUARANTEES, as
+ * for pgbp_bm_exact_stats, THAT THE BELIEFS WERE CALIBRATED ON A CLIQUE TREE UNDER A BROWNIAN MOTION WITH R = 1 AND AN IMPROPER
+ * ROOT; the call does not verify it.
+ * Per (family f, site) that is not skipped: t_f = sum_k gamma_k^2 length_k (:459); r = x_child - sum_k gamma_k x_k - d_f, with
+ * x_child the tip's data value when the child is a tip and d_f the displacement of the shifts on the family's parent edges;
+ * e = E[r | data] and C = Var(r | data) from the calibrated belief of the family's cluster (0, 1 or 2 variables, closed form);
+ * the family adds e^2 / t_f to num and 1 - C / t_f to den.  Skipped, as the reference and pgbp_bm_exact_stats skip them: a
+ * root-prior family, t_f == 0, child_mask == 0, a tip whose parent holds nothing in scope, a cluster without variables; and a
+ * tip the per-site mask says is not observed at this site.  The scopes are those of the complete data: an internal family whose
+ * whole clade is masked at a site stays in the sweep and adds e = 0, C = t_f, that is 0 to both sums.  den is then the number
+ * of tips the site observes less one, to rounding, and num / den the REML estimate of the rate on those tips.
+ *   num, den [sites]   required;
+ *   mu  [sites]        may be NULL: the posterior mean of variable root_pos of belief root_belief -- mu_hat of :435-437;
+ *   info [sites]       may be NULL: 0, or the 1-based index of the lowest cluster the site needed (root_belief with mu) that is
+ *                      not positive definite; that site's num, den and mu are NaN, its neighbours keep their bytes.  A needed
+ *                      cluster whose belief is the constant 1 gives NaN with info 0, as in pgbp_bm_exact_stats.
+ * Device: a workgroup is 256 consecutive sites, grid.y a block of 64 consecutive families; a thread walks its block in index
+ * order for its one site and writes its two sums, each started from 0.0, to partial[block][2][site]; a second kernel adds the
+ * blocks in block order (and forms mu).  No atomics, no LDS, no barrier, contraction off: two calls return the same bytes, and a
+ * site's bytes depend neither on the site range nor on the chunks (pgbp_sites_sweep_scratch_limit).  The pool is read in the
+ * layout it is in: pgbp_layout and the pool's bytes are the same before and after.  One stream synchronisation per call.
+ * Refused before any launch -- outputs, layout and pool untouched --: as pgbp_lg_gradient_sites, in its order (no table, no
+ * parameters: PGBP_ERR_STATE; the site range; num or den NULL; more than one trait, a belief above 2 variables, fewer than 8
+ * sites, an engine off the thread-per-site kernels: the text names pgbp_bm_exact_stats), then with PGBP_ERR_INVALID when the
+ * last pgbp_lg_assignfactors was an Ornstein-Uhlenbeck fill; when tip noise is in force (the variance is then not proportional
+ * to the rate: fit_sites_lg); for a family whose parent is the fixed root (the wording of pgbp_bm_exact_stats); for a tip family
+ * with more than one parent (the reference raises there: a hybrid tip); and for mu != NULL with root_belief or root_pos out of
+ * range. */
+int  pgbp_bm_exact_stats_sites(pgbp_engine* e, int32_t site_begin, int32_t site_end, int32_t root_belief, int32_t root_pos,
+                               double* num, double* den, double* mu, int32_t* info);
 /* POSTERIOR COVARIANCE OF A UNIVARIATE BATCH WITH LANES = SITES (csrc/pgbp_cov_uni.hip): pgbp_posterior_cov (below) in the
  * frame of the three calls above, for the out-of-clique queries of a fitted batch -- the covariance of two ancestors that share
  * no cluster, the variance of a clade mean or of a contrast -- at every site at once.  The semantics are pgbp_posterior_cov's:

@@ -1,5 +1,5 @@
 // Host side of the lanes-are-sites calls of a univariate batch (pgbp_grad_uni.hip, pgbp_fam_uni.hip, pgbp_post_uni.hip,
-// pgbp_cov_uni.hip), written once: what a call checks before it is accepted, the chunk of sites whose rows fit the scratch, the
+// pgbp_cov_uni.hip, pgbp_exact_uni.hip), written once: what a call checks before it is accepted, the chunk of sites whose rows fit the scratch, the
 // kernel arguments of a chunk, the scratch of a call with its one sticky error, the launch of a kernel in the layout the pool is
 // in, and the clock of the timed variants.  Plain helpers: every entry point still reads top to bottom in its own file --
 // accept, sizes, scratch, the chunk loop with its launches, copies, finish.

@@ -24,6 +24,58 @@ def bm_exact_stats(beliefs, all_sites=False):
     return num[0], float(den[0])
 
 
+def bm_exact_stats_sites(beliefs, root=None):
+    """pgbp_bm_exact_stats_sites on the current beliefs: the sweep of bm_exact_stats(all_sites=True) for a univariate batch on
+    the thread-per-site kernels (p = 1, every belief of at most 2 variables, at least 8 sites; anything else raises
+    PGBP_ERR_INVALID), lanes = sites, with the per-site mask of set_site_missing_lg and the shifts in force.  The beliefs are
+    read in the layout they are in: nothing is converted.  root = (belief index, position of the root variable in it), or None.
+    Returns (num [n_sites], den [n_sites], mu [n_sites] or None, info [n_sites]): den is the number of tips a site observes
+    less one, to rounding; a site whose info is not 0 holds NaN."""
+    n = beliefs.n_sites
+    num, den = np.zeros(n), np.zeros(n)
+    mu = np.zeros(n) if root is not None else None
+    info = np.zeros(n, dtype=np.int32)
+    rb, rp = (int(root[0]), int(root[1])) if root is not None else (0, 0)
+    _check(beliefs._lib.pgbp_bm_exact_stats_sites(beliefs._eng, 0, n, rb, rp, L.f64p(num), L.f64p(den),
+                                                  L.f64p(mu) if root is not None else None, L.i32p(info)), beliefs._eng)
+    return num, den, mu, info
+
+
+def calibrate_exact_sites_(beliefs, schedule_tree, root, beliefs_fixedroot=None):
+    """calibrate_exact_cliquetree_ for every site of a univariate batch at once, on the thread-per-site kernels and in their
+    layout: the closed-form REML fit of a Brownian motion at each site, from one calibration and one sweep -- no optimiser, no
+    start values, no tolerance.  It works with a per-site mask of missing tips in force (set_site_missing_lg, on both engines)
+    and with shifts set.
+
+    beliefs: the engine of the batch on the clique tree, built with fixedroot=False and ONE rate, family table set up.
+    root = (cluster index, position of the root variable in it).  Steps: factors of R = 1, mu = 0 -> one calibration (calibrate_'s
+    postorder and preorder of `schedule_tree`, enqueued as loglik_and_gradient_sites_lg enqueues them) -> the sweep (bm_exact_stats_sites) -> R_hat = num / den, NaN where den < 0.5: den is the number of observed tips less one to
+    rounding, and 0.5 separates a site that observes one tip from a site that observes two.  With beliefs_fixedroot (the engine
+    of the same batch built with fixedroot=True) the returned model is scored there: a per-site fill at (R_hat, mu_hat) and
+    loglik_lg.  Returns dict(R, mu, loglik, den [n_sites] float, info [n_sites] int32); a site whose info is not 0 (the sweep's
+    code, or -1 where the calibration itself failed at that site) is NaN in R, mu and loglik and does not raise; loglik is NaN
+    without beliefs_fixedroot and where R is."""
+    n = beliefs.n_sites
+    beliefs.assignfactors_lg_(np.ones((1, 1, 1)), np.zeros(1))
+    # reset from the factors, one calibration and the root integration enqueued without host synchronisation, as
+    # loglik_and_gradient_sites_lg does; the sweep's fetch is the one wait, the pool stays in the site-minor layout and, like
+    # loglik_lg, the host mirrors of the beliefs are not refreshed (beliefs.pull() does that)
+    _, (num, den, mu, info), cal = beliefs._loglik_and_sites(schedule_tree, lambda: bm_exact_stats_sites(beliefs, root))
+    info = np.where((cal != 0) & (info == 0), -1, info).astype(np.int32)   # (a message of that site was not positive definite)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        R = np.where((den >= 0.5) & (info == 0), num / den, np.nan)
+    mu = np.where(info == 0, mu, np.nan)
+    ll = np.full(n, np.nan)
+    if beliefs_fixedroot is not None:
+        fx = beliefs_fixedroot
+        fx._ensure_schedule([schedule_tree])
+        ok = np.isfinite(R) & (R > 0) & np.isfinite(mu)
+        fx.assignfactors_lg_(np.where(ok, R, 1.0).reshape(n, 1, 1, 1), np.where(ok, mu, 0.0).reshape(n, 1))
+        norm, linfo = fx.loglik_lg()
+        ll = np.where(ok & (linfo == 0), norm, np.nan)
+    return dict(R=R, mu=mu, loglik=ll, den=den, info=info)
+
+
 def calibrate_exact_cliquetree_(beliefs, schedule_tree, root, beliefs_fixedroot=None, all_sites=False):
     """calibrate_exact_cliquetree!(beliefs, spt, prenodes, tbl, taxa, evomodelfun) (src/calibration.jl:404-517) for a
     (univariate or full) Brownian motion.

@@ -323,6 +323,21 @@ function lg_loo_sites(o::DeviceClusterGraphBelief, nsites::Integer)
 end
 
 """
+    bm_exact_stats_sites(obj, nsites, rootcluster, rootpos) -> (num, den, mu, info)
+
+The family sweep of `calibrate_exact_cliquetree!` for every site of a univariate batch on the thread-per-site kernels
+(pgbp_bm_exact_stats_sites), lanes = sites, with the per-site mask of missing tips and the shifts in force: `num[s]`, `den[s]`
+(the number of tips site `s` observes less one, to rounding; `num ./ den` is the REML rate) and `mu[s]`, the posterior mean of
+variable `rootpos` of cluster `rootcluster` (both 1-based).  The beliefs must be calibrated under a BM with R = 1 and an improper
+root.  A failed site (`info[s] != 0`) holds NaN.  Untested: there is no Julia on the test machines.
+"""
+function bm_exact_stats_sites(o::DeviceClusterGraphBelief, nsites::Integer, rootcluster::Integer, rootpos::Integer)
+    num = zeros(nsites); den = zeros(nsites); mu = zeros(nsites); info = zeros(Int32, nsites)
+    check(o.handle, @ccall LIB.pgbp_bm_exact_stats_sites(o.handle::Ptr{Cvoid}, Int32(0)::Int32, Int32(nsites)::Int32, Int32(rootcluster - 1)::Int32, Int32(rootpos - 1)::Int32, num::Ptr{Float64}, den::Ptr{Float64}, mu::Ptr{Float64}, info::Ptr{Int32})::Cint)
+    return (num, den, mu, info)
+end
+
+"""
     moments_sites(obj, nsites, dims; cov = true) -> (mean, tri, norm, info)
 
 `moments!` of EVERY CLUSTER for every site of a univariate batch on the thread-per-site kernels (pgbp_moments_sites; the
