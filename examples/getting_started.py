@@ -208,6 +208,39 @@ def main():
     print(f"  node {c + 1} minus node {c2 + 1}, posterior mean +- se at the first four sites: " +
           ", ".join(f"{m[s, 0] - m2[s, 0]:.3f} +- {np.sqrt(gram[s, 0, 0]):.3f}" for s in range(4)) +
           f"; {int((cinfo != 0).sum())} sites failed")
+    # Hansen's model: two clades in selective regimes of their own.  The optimum is painted on the edges (set_optima_lg, as
+    # `color` paints rates): regime 1 and 2 on every edge of two clades, theta on the rest; each site fits its own theta_1 and
+    # theta_2 beside alpha, theta and the stationary variance, with the derivative doptima of the lanes-are-sites sweep
+    from pgbp_amd import synth   # (S is the covariance of the moments above by now)
+    kids = [np.flatnonzero(tr.parent == i) for i in range(tr.nnodes)]
+    def clade(i):
+        out = [i]
+        for c_ in kids[i]:
+            out += clade(int(c_))
+        return out
+    size = {i: int(tr.is_leaf[clade(i)].sum()) for i in range(1, tr.nnodes)}
+    k1 = min(size, key=lambda i: (abs(size[i] - 12), i))
+    k2 = min((i for i in size if i not in clade(k1) and k1 not in clade(i)), key=lambda i: (abs(size[i] - 12), i))
+    node_regime = np.zeros(tr.nnodes, np.int32)
+    node_regime[clade(k1)], node_regime[clade(k2)] = 1, 2
+    opt = th[:, None] + np.array([2.5, -2.5])               # the two clades' optima, per site
+    rng_p = np.random.default_rng(5)                          # (a generator of its own: the draws below stay as they were)
+    Xp = np.empty_like(X)
+    Xp[:, 0] = X[:, 0]
+    for i in range(1, tr.nnodes):
+        a_ = np.exp(-al * tr.length[i])
+        target = th if node_regime[i] == 0 else opt[:, node_regime[i] - 1]
+        Xp[:, i] = a_ * Xp[:, tr.parent[i]] + (1 - a_) * target + np.sqrt(g2 * (1 - a_ * a_)) * rng_p.normal(size=ns)
+    batch.lg_setup(synth.lg_tree_table(tr, prob, 1), np.ascontiguousarray(Xp[:, :, None]))
+    batch.set_optima_lg(node_regime[1:, None], np.zeros((2, 1)))   # (family f of the table is node f + 1)
+    tipmean_p = Xp[:, tr.is_leaf].mean(axis=1)
+    fitp = P.fit_sites_lg(batch, prob.schedule[0], "ou", np.ones(ns), Xp[:, 0], alpha0=np.full(ns, 1.0 / H), theta0=tipmean_p,
+                          fit_mu=False, optima0=np.stack([tipmean_p, tipmean_p], axis=1))
+    print(f"painted optima: clades of {size[k1]} and {size[k2]} tips, {int(fitp['converged'].sum())} of {ns} sites converged in "
+          f"{fitp['n_device_evals']} device passes; theta_1 - theta, theta_2 - theta at the first four sites (simulated +2.5, "
+          f"-2.5): " + ", ".join(f"{fitp['optima'][s, 0] - fitp['theta'][s]:+.2f} {fitp['optima'][s, 1] - fitp['theta'][s]:+.2f}"
+                                 for s in range(4)))
+    batch.lg_setup(synth.lg_tree_table(tr, prob, 1), np.ascontiguousarray(X[:, :, None]))   # (the unpainted batch again)
     # real batches have gaps, another set of unmeasured species at almost every site: a table with NaN at its gaps goes to
     # lg_setup with finite placeholders (split_missing_data) and its gaps to set_site_missing_lg; every site is then fitted to
     # its own observed tips and its gaps are imputed, all sites in one call each (lanes = sites)
@@ -218,7 +251,6 @@ def main():
     table[gaps] = np.nan
     clean, mask = P.split_missing_data(table)
     gappy = P.ClusterGraphBelief.from_arrays(prob.dims, prob.sepset_clusters, prob.scope_off, prob.scope_idx, None, n_sites=ns)
-    from pgbp_amd import synth   # (S is the covariance of the moments above by now)
     gappy.lg_setup(synth.lg_tree_table(tr, prob, 1), clean)
     gappy.set_site_missing_lg(mask)
     obsmean = np.nanmean(table[:, leaves], axis=1)

@@ -412,6 +412,58 @@ int pgbp_lg_set_edges(pgbp_engine* e, const double* length, const double* gamma)
  * pgbp_lg_shift_count: the number of shifts in force (0: none; -1: no family table). */
 int pgbp_lg_set_shifts(pgbp_engine* e, int32_t n_shifts, const int32_t* edge, const double* value, int32_t per_site);
 int32_t pgbp_lg_shift_count(pgbp_engine* e);
+/* PAINTED OPTIMA under PGBP_LG_OU (Hansen's model): theta painted on the edges as `color` paints the rates.  In the notation of
+ * pgbp_lg_params the offset of family f is w = sum_k wc_k theta_{r(f,k)} instead of sum_k wc_k theta: w gains
+ * d_opt = sum_k wc_k (theta_{r(f,k)} - theta) on the kept traits O = child_mask[f].  Variances, J, qc and vc are untouched.
+ *   regime [n_families * max_parents] int32, indexed f * max_parents + k as length and gamma: 0 = the edge keeps theta of
+ *          pgbp_lg_params, r in 1 .. n_regimes = its optimum is value[r - 1]; entries of a root-prior family and of
+ *          k >= n_parents[f] are ignored;
+ *   value  [n_regimes][p], or with per_site != 0 [n_sites][n_regimes][p] (allowed whether the parameters are shared or per site);
+ *   n_regimes = 0 clears (regime and value may be NULL).  The call REPLACES the previous setting.
+ * Takes effect as pgbp_lg_set_shifts does, at the next fill: the fill kernels keep their code and the optimum enters as a
+ * displacement through the correction that follows every fill (csrc/pgbp_shift.hip: delta = the shifts' d + d_opt, the clusters
+ * visited are those of either list); the tip-noise and the per-site-mask corrections form the same offset.  Under PGBP_LG_BM
+ * wc = 0: the optima have no effect, nothing is launched for them and every byte is that of an engine without optima.
+ * ACCURACY: "fill with theta, then add wc (theta_r - theta)" leaves an error of about 2^-52 |wc| (|theta| + |theta_r|) in w where
+ * a direct fill would leave 2^-52 |wc theta_r|: nothing is lost while theta is of the size of the optima.
+ * The optima survive pgbp_lg_set_edges, pgbp_lg_set_shifts, pgbp_lg_set_tip_noise and pgbp_lg_set_site_missing; a new
+ * pgbp_lg_setup clears them.  An engine borrowed from a pgbp_group or pgbp_patterns takes the call like any other.
+ * THE SWEEPS while optima are in force under PGBP_LG_OU: pgbp_moments, pgbp_sample_posterior, pgbp_posterior_cov and their
+ * _sites twins read beliefs only and are unaffected.  pgbp_lg_gradient_optima and pgbp_lg_gradient_sites_optima (below) honour
+ * them and return the derivative in every optimum.  pgbp_lg_gradient(_noise) and pgbp_lg_gradient_sites cannot return it -- and
+ * their dtheta and dalpha would read as the unpainted model's --, and pgbp_lg_edge_gradient, pgbp_lg_shift_scan, pgbp_lg_loo,
+ * pgbp_lg_impute, their _sites twins and pgbp_lg_simulate form w themselves and do not know the optima yet: each of these
+ * REFUSES before any launch (PGBP_ERR_INVALID, naming the optima) with its outputs, the layout, the pool and the setting
+ * untouched; none returns the unpainted answer.  Under PGBP_LG_BM they all run as without optima.
+ * PGBP_ERR_STATE without a family table.  PGBP_ERR_INVALID with NOTHING changed (the previous optima stay in force) and a text
+ * that names the entry for: a regime outside 0 .. n_regimes on a real edge, a value that is not finite.  Up to four copies (the
+ * regime map, the cluster list, the values and, for a univariate per-site batch, their [regime][site] copy) and one stream
+ * synchronisation.
+ * pgbp_lg_optima_count: the number of regimes in force (0: none; -1: no family table). */
+int pgbp_lg_set_optima(pgbp_engine* e, int32_t n_regimes, const int32_t* regime, const double* value, int32_t per_site);
+int32_t pgbp_lg_optima_count(pgbp_engine* e);
+/* The values of the setting in force alone -- what a fit moves at every step: `value` in the shape the setter was given
+ * ([n_regimes][p], or [n_sites][n_regimes][p] when it was set per site) goes into the buffers the device already holds; the
+ * regime map, the cluster list and the allocations stay (one or two copies, no allocation).  Takes effect at the next fill.
+ * PGBP_ERR_STATE without a family table or without optima; PGBP_ERR_INVALID, with nothing changed, for a value that is not
+ * finite. */
+int pgbp_lg_update_optima(pgbp_engine* e, const double* value);
+/* pgbp_lg_gradient_noise with one more output, doptima [sites][n_regimes][p] (n_regimes of pgbp_lg_optima_count; NULL only when
+ * no optima are set; dsigma_e may be NULL).  With optima in force under PGBP_LG_OU:
+ *   doptima[r] = sum over the edges (f, k) of regime r of wc_k g_w(f)   (a regime no edge carries: 0),
+ *   dtheta     = the same sum over the edges of regime 0 only,
+ *   dalpha     uses theta_{r(f,k)} in its dwc_k theta g_w term,
+ * and dR, dmu, dsigma_e see the optima through e = E[r] only.  doptima is one more block of the family slot, added by the same
+ * fixed tree as dR: two calls return the same bytes.  Without optima, and under PGBP_LG_BM, every other output holds the bytes
+ * of pgbp_lg_gradient_noise and doptima holds zeros.
+ * pgbp_lg_gradient_sites_optima: the same for pgbp_lg_gradient_sites (a univariate batch on the thread-per-site kernels),
+ * doptima [sites][n_regimes].  The regime of an edge is uniform across a wavefront; a launch carries four regimes in registers
+ * beside its four rates, more are swept in groups.  A site's bytes depend neither on the call nor on the site range or the
+ * chunking.  The instance that runs without optima is the kernel of pgbp_lg_gradient_sites, unchanged. */
+int pgbp_lg_gradient_optima(pgbp_engine* e, int32_t site_begin, int32_t site_end, double* dR, double* dmu, double* dalpha,
+                            double* dtheta, double* dsigma_e, double* doptima, int32_t* info);
+int pgbp_lg_gradient_sites_optima(pgbp_engine* e, int32_t site_begin, int32_t site_end, double* dR, double* dmu, double* dalpha,
+                                  double* dtheta, double* dsigma_e, double* doptima, int32_t* info);
 /* MEASUREMENT ERROR AT THE TIPS: species means with known standard errors, or means of n_f individuals with a within-species
  * covariance.  A tip family f (child_pos < 0, a data row, at least one parent edge) that is listed gets the conditional variance
  *     V_f = sum_k vc_k R[colour_k] + E_f,      E_f = scale_f * Sigma_e + diag(se2_f):

@@ -127,12 +127,17 @@ SYMBOLS = {
     "pgbp_lg_set_edges": (C.c_int, [_P, _F64P, _F64P]),
     "pgbp_lg_set_shifts": (C.c_int, [_P, C.c_int32, _I32P, _F64P, C.c_int32]),
     "pgbp_lg_shift_count": (C.c_int32, [_P]),
+    "pgbp_lg_set_optima": (C.c_int, [_P, C.c_int32, _I32P, _F64P, C.c_int32]),
+    "pgbp_lg_optima_count": (C.c_int32, [_P]),
+    "pgbp_lg_update_optima": (C.c_int, [_P, _F64P]),
     "pgbp_lg_set_tip_noise": (C.c_int, [_P, C.c_int32, _I32P, _F64P, _F64P, _F64P, C.c_int32]),
     "pgbp_lg_tip_noise_count": (C.c_int32, [_P]),
     "pgbp_lg_set_site_missing": (C.c_int, [_P, C.POINTER(C.c_uint8)]),
     "pgbp_lg_get_site_missing": (C.c_int, [_P, C.POINTER(C.c_uint8)]),
     "pgbp_lg_site_missing_count": (C.c_int32, [_P]),
     "pgbp_lg_gradient_noise": (C.c_int, [_P, C.c_int32, C.c_int32, _F64P, _F64P, _F64P, _F64P, _F64P, _I32P]),
+    "pgbp_lg_gradient_optima": (C.c_int, [_P, C.c_int32, C.c_int32, _F64P, _F64P, _F64P, _F64P, _F64P, _F64P, _I32P]),
+    "pgbp_lg_gradient_sites_optima": (C.c_int, [_P, C.c_int32, C.c_int32, _F64P, _F64P, _F64P, _F64P, _F64P, _F64P, _I32P]),
     "pgbp_lg_gradient_sites": (C.c_int, [_P, C.c_int32, C.c_int32, _F64P, _F64P, _F64P, _F64P, _F64P, _I32P]),
     "pgbp_lg_shift_scan": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_double, _F64P, _F64P, C.POINTER(C.c_uint64), _F64P, _I32P]),
     "pgbp_lg_loo_count": (C.c_int32, [_P]),

@@ -715,6 +715,7 @@ class ClusterGraphBelief:
             _check(self._lib.pgbp_lg_set_topology(self._eng, L.i32p(k["parent_family"])), self._eng)
         self._lg_shift_edges = np.zeros(0, np.int32)   # a new table clears the shifts (pgbp_lg_setup)
         self._lg_noise = None                          # ... and the tip noise
+        self._lg_optima = None                         # ... and the painted optima
         self._lg_last = None                           # ... and has no parameters yet
         self._lg_data_nan = np.isnan(data[:, :, 0]) if int(fam["p"]) == 1 else None   # (set_site_missing_lg("nan"); no mask yet)
         self._lg_site_mask = None                      # ... and no per-site mask
@@ -760,7 +761,9 @@ class ClusterGraphBelief:
         dtheta [p] (zero for a Brownian motion), info; with a leading site axis when all_sites.  A site whose info is
         not 0 (1-based index of a cluster that is not positive definite) holds NaN; for the current site that raises.
         With tip noise set (set_tip_noise_lg) the dict also holds dsigma_e [p, p] (symmetric; d loglik = tr(dsigma_e
-        dSigma_e)): pgbp_lg_gradient_noise."""
+        dSigma_e)): pgbp_lg_gradient_noise.  With painted optima set (set_optima_lg) it also holds doptima [n_regimes, p],
+        the derivative in each regime's optimum (0 for a regime no edge carries); dtheta is then the derivative in theta of
+        the unpainted edges alone: pgbp_lg_gradient_optima."""
         p, nr = self._lg_p, self._lg_nrates
         s0, s1 = (0, self.n_sites) if all_sites else (self.site, self.site + 1)
         n = s1 - s0
@@ -770,7 +773,14 @@ class ClusterGraphBelief:
         dtheta = np.zeros((n, p))
         info = np.zeros(n, dtype=np.int32)
         noisy = self.tip_noise_count_lg() > 0
-        if noisy:
+        nopt = self.optima_count_lg()
+        if nopt > 0:   # painted optima: dtheta covers the unpainted edges, doptima [n_regimes, p] the painted ones
+            dsig = np.zeros((n, p, p)) if noisy else None
+            dopt = np.zeros((n, nopt, p))
+            _check(self._lib.pgbp_lg_gradient_optima(self._eng, s0, s1, L.f64p(dR), L.f64p(dmu), L.f64p(dalpha),
+                                                     L.f64p(dtheta), L.f64p(dsig) if noisy else None, L.f64p(dopt),
+                                                     L.i32p(info)), self._eng)
+        elif noisy:
             dsig = np.zeros((n, p, p))
             _check(self._lib.pgbp_lg_gradient_noise(self._eng, s0, s1, L.f64p(dR), L.f64p(dmu), L.f64p(dalpha),
                                                     L.f64p(dtheta), L.f64p(dsig), L.i32p(info)), self._eng)
@@ -781,6 +791,8 @@ class ClusterGraphBelief:
         d = dict(dR=dR, dmu=dmu, dalpha=dalpha, dtheta=dtheta, info=info)
         if noisy:
             d["dsigma_e"] = dsig.transpose(0, 2, 1)
+        if nopt > 0:
+            d["doptima"] = dopt
         return d if all_sites else self._gradient_of_site(d, 0)
 
     @staticmethod
@@ -791,6 +803,8 @@ class ClusterGraphBelief:
                    info=0)
         if "dsigma_e" in d:
             out["dsigma_e"] = d["dsigma_e"][s].copy()
+        if "doptima" in d:
+            out["doptima"] = d["doptima"][s].copy()
         return out
 
     def loglik_and_gradient_lg(self, schedule_tree, all_sites=False):
@@ -822,7 +836,8 @@ class ClusterGraphBelief:
         thread-per-site kernels (p = 1, every belief of at most 2 variables, at least 8 sites; anything else raises
         PGBP_ERR_INVALID), lanes = sites.  The beliefs are read in the layout they are in: nothing is converted, the next
         calibrate_ finds the site-minor layout it left.  Same keys and shapes as gradient_lg(all_sites=True) (dsigma_e when
-        tip noise is set); the values agree with it to rounding, and two calls return the same bytes."""
+        tip noise is set, doptima [n_sites, n_regimes, 1] when painted optima are set); the values agree with it to rounding,
+        and two calls return the same bytes."""
         nr, n = self._lg_nrates, self.n_sites
         dR = np.zeros((n, nr, 1, 1))
         dmu = np.zeros((n, 1))
@@ -831,11 +846,20 @@ class ClusterGraphBelief:
         info = np.zeros(n, dtype=np.int32)
         noisy = self.tip_noise_count_lg() > 0
         dsig = np.zeros((n, 1, 1)) if noisy else None
-        _check(self._lib.pgbp_lg_gradient_sites(self._eng, 0, n, L.f64p(dR), L.f64p(dmu), L.f64p(dalpha), L.f64p(dtheta),
-                                                L.f64p(dsig) if noisy else None, L.i32p(info)), self._eng)
+        nopt = self.optima_count_lg()
+        if nopt > 0:   # painted optima: pgbp_lg_gradient_sites_optima
+            dopt = np.zeros((n, nopt, 1))
+            _check(self._lib.pgbp_lg_gradient_sites_optima(self._eng, 0, n, L.f64p(dR), L.f64p(dmu), L.f64p(dalpha),
+                                                           L.f64p(dtheta), L.f64p(dsig) if noisy else None, L.f64p(dopt),
+                                                           L.i32p(info)), self._eng)
+        else:
+            _check(self._lib.pgbp_lg_gradient_sites(self._eng, 0, n, L.f64p(dR), L.f64p(dmu), L.f64p(dalpha), L.f64p(dtheta),
+                                                    L.f64p(dsig) if noisy else None, L.i32p(info)), self._eng)
         d = dict(dR=dR, dmu=dmu, dalpha=dalpha, dtheta=dtheta, info=info)
         if noisy:
             d["dsigma_e"] = dsig
+        if nopt > 0:
+            d["doptima"] = dopt
         return d
 
     def loglik_and_gradient_sites_lg(self, schedule_tree):
@@ -1301,6 +1325,66 @@ class ClusterGraphBelief:
     def shift_count_lg(self):
         """pgbp_lg_shift_count: the number of shifts in force (0: none)."""
         return int(self._lib.pgbp_lg_shift_count(self._eng))
+
+    def set_optima_lg(self, regime, values):
+        """pgbp_lg_set_optima: optima painted on the edges under OU (Hansen's model), as `color` paints the rates.  regime:
+        the dense int map [n_families, K] (or flat [n_families * K]; 0 = the edge keeps theta of assignfactors_lg_, r >= 1 =
+        its optimum is values[r - 1]; entries of a root-prior family and of k >= n_parents are ignored), or a dict
+        {edge: r} with edge a (family, k) pair or a flat index family * K + k (every other edge 0).  values: [n_regimes, p]
+        ([n_regimes] at p = 1), or [n_sites, n_regimes, p] for one set per site.  The offset of a family becomes
+        sum_k wc_k theta_{r(f,k)}; variances, J, qc and vc are untouched, and under BM (wc = 0) nothing changes.  The call
+        REPLACES the previous setting (no values clears it); the next assignfactors_lg_ or loglik_lg uses it, beliefs and
+        factors are not refilled by this call.  gradient_lg and gradient_sites_lg honour the optima and return doptima.  The
+        other sweeps that form the offsets themselves (edge_gradient_lg, shift_scan_lg, loo_lg, impute_lg, simulate_lg and
+        their _sites forms) raise under OU while optima are in force; moments, samples and posterior covariances read
+        beliefs only.  An invalid entry raises and leaves the previous optima in force."""
+        nf = len(self._lg["cluster"])
+        K = self._lg["length"].size // nf if nf else 1
+        p = self._lg_p
+        if isinstance(regime, dict):
+            m = np.zeros(max(1, nf * K), np.int32)
+            for edge, r in regime.items():
+                m[int(self._shift_edges([edge])[0])] = int(r)
+        else:
+            m = np.ascontiguousarray(np.asarray(regime, np.int64).reshape(-1), np.int32)
+            if m.size != nf * K:
+                raise ValueError(f"regime: {nf * K} entries (n_families * K) expected, got {m.size}")
+        v = np.asarray(values, np.float64)
+        per_site = v.ndim == 3
+        n = int(v.shape[1] if per_site else (v.shape[0] if v.ndim else 1)) if v.size else 0
+        if n == 0:
+            return self.clear_optima_lg()
+        v = np.ascontiguousarray(v.reshape((self.n_sites, n, p) if per_site else (n, p)))
+        _check(self._lib.pgbp_lg_set_optima(self._eng, n, L.i32p(m), L.f64p(v), int(per_site)), self._eng)
+        self._lg_optima = dict(regime=m.reshape(nf, K).copy(), values=v.copy(), per_site=bool(per_site))
+
+    def update_optima_lg(self, values):
+        """pgbp_lg_update_optima: new values for the optima in force, in the shape set_optima_lg was given; the regime map
+        and the device buffers stay (what fit_sites_lg does at every step).  Takes effect at the next fill; a value that is
+        not finite raises and leaves the previous values in force."""
+        o = getattr(self, "_lg_optima", None)
+        if o is None:
+            raise L.PgbpError(L.ERR_STATE, "no optima are set (call set_optima_lg first)")
+        v = np.ascontiguousarray(np.asarray(values, np.float64).reshape(o["values"].shape))
+        _check(self._lib.pgbp_lg_update_optima(self._eng, L.f64p(v)), self._eng)
+        o["values"] = v.copy()
+
+    def clear_optima_lg(self):
+        """Remove the painted optima (pgbp_lg_set_optima with no regime)."""
+        _check(self._lib.pgbp_lg_set_optima(self._eng, 0, None, None, 0), self._eng)
+        self._lg_optima = None
+
+    def optima_lg(self):
+        """The painted optima in force: None, or a dict with regime [n_families, K], values [n_regimes, p] (or
+        [n_sites, n_regimes, p]) and per_site -- copies of what set_optima_lg was given."""
+        o = getattr(self, "_lg_optima", None)
+        if o is None or self.optima_count_lg() == 0:
+            return None
+        return dict(regime=o["regime"].copy(), values=o["values"].copy(), per_site=o["per_site"])
+
+    def optima_count_lg(self):
+        """pgbp_lg_optima_count: the number of regimes in force (0: none)."""
+        return int(self._lib.pgbp_lg_optima_count(self._eng))
 
     def set_tip_noise_lg(self, families, sigma_e, scale=None, se2=None):
         """pgbp_lg_set_tip_noise: measurement error at the tips.  The conditional variance of every listed tip family f

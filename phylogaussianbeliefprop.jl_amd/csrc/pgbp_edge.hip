@@ -179,6 +179,7 @@ extern "C" int pgbp_lg_edge_gradient(pgbp_engine* e, int32_t site_begin, int32_t
   const LgModel* L = nullptr;
   int rc = lg_sweep_state(e, "pgbp_lg_edge_gradient", site_begin, site_end, &L, "pgbp_lg_edge_gradient_sites");
   if (rc) return rc;
+  if ((rc = lg_refuse_optima(e, "pgbp_lg_edge_gradient", L))) return rc;
   const LgStatic& F = L->F;
   const LgParams& M = L->M;
   const LgShifts& Sh = L->Sh;

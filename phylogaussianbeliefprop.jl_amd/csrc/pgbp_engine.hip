@@ -9,6 +9,7 @@
 #include <cstdlib>
 #include <cstdio>
 #include <cstring>
+#include <iterator>
 #include <memory>
 #include <string>
 #include <vector>
@@ -1672,14 +1673,18 @@ int pgbp_lg_setup(pgbp_engine* e, const pgbp_lg_families* f) {
 static int lg_fill_async(pgbp_engine* e, bool also_factors, bool skip_sepsets = false) {
   const Plan& p = e->plan;
   const LgModel& L = *e->lg;
+  // the displacement correction: the shifted clusters, or with painted optima in force their union with the painted ones
+  const LgOptima Op = L.optima_in_force();
+  const int32_t* dcl = Op.regime ? L.disp_cl.get() : L.shift_bufs.cl.get();
+  const int32_t n_dcl = Op.regime ? L.n_disp_cl : L.n_shift_cl;
   if (e->layout_sm && L.T.uni_ok) {
     launch_lg_fill_uni_sm(L.F, L.M, e->sm.pool.get(), also_factors ? e->sm.fpool.get() : nullptr, e->d_packed_off.get(), e->d_bdim.get(),
                           p.n_clusters, p.n_sites, e->st);
-    launch_lg_shift_uni_sm(L.F, L.M, L.Sh, L.shift_bufs.cl.get(), L.n_shift_cl, e->sm.pool.get(),
+    launch_lg_shift_uni_sm(L.F, L.M, L.Sh, Op, dcl, n_dcl, e->sm.pool.get(),
                            also_factors ? e->sm.fpool.get() : nullptr, e->d_packed_off.get(), e->d_bdim.get(), p.n_sites, e->st);
-    launch_lg_noise_uni_sm(L.F, L.M, L.Sh, L.Nz, L.noise_bufs.cl.get(), L.n_noise_cl, e->sm.pool.get(),
+    launch_lg_noise_uni_sm(L.F, L.M, L.Sh, Op, L.Nz, L.noise_bufs.cl.get(), L.n_noise_cl, e->sm.pool.get(),
                            also_factors ? e->sm.fpool.get() : nullptr, e->d_packed_off.get(), e->d_bdim.get(), p.n_sites, e->st);
-    launch_lg_sitemiss(L.F, L.M, L.Sh, L.Nz, L.Ms, L.miss_bufs.cl.get(), (int)L.miss.cl.size(), 1, e->sm.pool.get(), sm_row(p.n_sites),
+    launch_lg_sitemiss(L.F, L.M, L.Sh, Op, L.Nz, L.Ms, L.miss_bufs.cl.get(), (int)L.miss.cl.size(), 1, e->sm.pool.get(), sm_row(p.n_sites),
                        also_factors ? e->sm.fpool.get() : nullptr, sm_row(p.n_sites), e->d_packed_off.get(), e->d_bdim.get(), p.n_sites,
                        e->st);
     const int64_t nc = p.packed_off[p.n_clusters] * sm_row(p.n_sites), nall = p.packed_off.back() * sm_row(p.n_sites);
@@ -1691,15 +1696,15 @@ static int lg_fill_async(pgbp_engine* e, bool also_factors, bool skip_sepsets = 
     }
     launch_lg_fill(L.F, L.M, e->d_pool.get(), p.pool_stride(), also_factors ? e->d_fpool.get() : nullptr, p.cluster_stride(),
                    e->d_boff.get(), e->d_bdim.get(), e->layout_bs16 ? 1 : 0, p.fast_p, p.max_dim, p.n_clusters, p.n_sites, e->st);
-    launch_lg_shift(L.F, L.M, L.Sh, L.shift_bufs.cl.get(), L.n_shift_cl, e->d_pool.get(), p.pool_stride(),
+    launch_lg_shift(L.F, L.M, L.Sh, Op, dcl, n_dcl, e->d_pool.get(), p.pool_stride(),
                     also_factors ? e->d_fpool.get() : nullptr, p.cluster_stride(), e->d_boff.get(), e->d_bdim.get(),
                     e->layout_bs16 ? 1 : 0, p.fast_p, p.max_dim, p.n_sites, e->st);
-    launch_lg_noise(L.F, L.M, L.Sh, L.Nz, L.noise_bufs.cl.get(), L.n_noise_cl, e->d_pool.get(), p.pool_stride(),
+    launch_lg_noise(L.F, L.M, L.Sh, Op, L.Nz, L.noise_bufs.cl.get(), L.n_noise_cl, e->d_pool.get(), p.pool_stride(),
                     also_factors ? e->d_fpool.get() : nullptr, p.cluster_stride(), e->d_boff.get(), e->d_bdim.get(),
                     e->layout_bs16 ? 1 : 0, p.fast_p, L.noise_max_dim, p.n_sites, e->st);
     if (L.Ms.words && e->layout_bs16)   // (a thread-per-site engine is never in the packed layout)
       return e->fail(PGBP_ERR_STATE, "a per-site mask of missing tips is in force but the engine is in the packed layout");
-    launch_lg_sitemiss(L.F, L.M, L.Sh, L.Nz, L.Ms, L.miss_bufs.cl.get(), (int)L.miss.cl.size(), 0, e->d_pool.get(), p.pool_stride(),
+    launch_lg_sitemiss(L.F, L.M, L.Sh, Op, L.Nz, L.Ms, L.miss_bufs.cl.get(), (int)L.miss.cl.size(), 0, e->d_pool.get(), p.pool_stride(),
                        also_factors ? e->d_fpool.get() : nullptr, p.cluster_stride(), e->d_boff.get(), e->d_bdim.get(), p.n_sites,
                        e->st);
     if (!skip_sepsets)
@@ -1743,6 +1748,17 @@ int pgbp_lg_assignfactors(pgbp_engine* e, const pgbp_lg_params* m) {
 // The setters: every check (the table's: pgbp_lgtable.hpp) before anything changes; new buffers into a local group that
 // the model takes once every copy has been made.
 
+// the sorted union of two sorted cluster lists on the device (one word at least), uploaded synchronously: what the displacement
+// correction visits when shifts and painted optima are both in force
+static int lg_union_clusters(pgbp_engine* e, const std::vector<int32_t>& a, const std::vector<int32_t>& b, DevBuf<int32_t>& out,
+                             int32_t* n = nullptr) {
+  std::vector<int32_t> u;
+  std::set_union(a.begin(), a.end(), b.begin(), b.end(), std::back_inserter(u));
+  if (n) *n = (int32_t)u.size();
+  if (u.empty()) u.push_back(0);
+  return upload(e, out, u);
+}
+
 int pgbp_lg_set_edges(pgbp_engine* e, const double* length, const double* gamma) {
   DeviceScope device_scope(e);
   if (!e) return PGBP_ERR_INVALID;
@@ -1771,11 +1787,16 @@ int pgbp_lg_set_shifts(pgbp_engine* e, int32_t n_shifts, const int32_t* edge, co
   if (!L.T.shift_list(n_shifts, edge, value, per_site, slot, cl, why)) return e->fail(PGBP_ERR_INVALID, why);
   const int pp = L.T.p;
   const size_t ns = per_site ? (size_t)e->plan.n_sites : 1, n = (size_t)n_shifts;
+  DevBuf<int32_t> ucl;   // with painted optima in force: the clusters of either list, for the displacement correction
+  int rc0;
   if (n_shifts == 0) {   // clear (kernels already enqueued may still read the old shifts)
     HIPCHK(e, hipStreamSynchronize(e->st));
+    if (L.Op.regime && (rc0 = lg_union_clusters(e, {}, L.opt_cl, ucl))) return rc0;
     L.shift_bufs = LgShiftBufs{};
     L.Sh = LgShifts{};
     L.n_shift_cl = 0;
+    L.shift_cl.clear();
+    if (L.Op.regime) { L.n_disp_cl = (int32_t)L.opt_cl.size(); L.disp_cl = std::move(ucl); }
     return PGBP_OK;
   }
   // univariate per-site batches: the values once more as [shift][site], what the thread-per-site correction reads
@@ -1792,6 +1813,8 @@ int pgbp_lg_set_shifts(pgbp_engine* e, int32_t n_shifts, const int32_t* edge, co
   if ((rc = dev_alloc(e, B.cl, cl.size()))) return rc;
   if ((rc = dev_alloc(e, B.value, ns * n * pp))) return rc;
   if (!vsm.empty() && (rc = dev_alloc(e, B.value_sm, vsm.size()))) return rc;
+  int32_t n_ucl = 0;
+  if (L.Op.regime && (rc = lg_union_clusters(e, cl, L.opt_cl, ucl, &n_ucl))) return rc;
   // every buffer exists: the copies, then ONE synchronisation whatever they returned (none may outlive the host vectors)
   hipError_t herr = hipMemcpyAsync(B.slot.get(), slot.data(), slot.size() * sizeof(int32_t), hipMemcpyHostToDevice, e->st);
   if (herr == hipSuccess) herr = hipMemcpyAsync(B.cl.get(), cl.data(), cl.size() * sizeof(int32_t), hipMemcpyHostToDevice, e->st);
@@ -1805,12 +1828,103 @@ int pgbp_lg_set_shifts(pgbp_engine* e, int32_t n_shifts, const int32_t* edge, co
   const LgShiftBufs& S = L.shift_bufs;
   L.Sh = LgShifts{S.slot.get(), S.value.get(), per_site ? 1 : 0, n_shifts, S.value_sm.get()};
   L.n_shift_cl = (int32_t)cl.size();
+  L.shift_cl = std::move(cl);
+  if (L.Op.regime) { L.n_disp_cl = n_ucl; L.disp_cl = std::move(ucl); }
   return PGBP_OK;
 }
 
 int32_t pgbp_lg_shift_count(pgbp_engine* e) {
   if (!e || !e->lg) return -1;
   return e->lg->Sh.slot ? e->lg->Sh.n : 0;
+}
+
+int pgbp_lg_set_optima(pgbp_engine* e, int32_t n_regimes, const int32_t* regime, const double* value, int32_t per_site) {
+  DeviceScope device_scope(e);
+  if (!e) return PGBP_ERR_INVALID;
+  if (!e->lg) return e->fail(PGBP_ERR_STATE, "pgbp_lg_set_optima: no family table (call pgbp_lg_setup first)");
+  LgModel& L = *e->lg;
+  std::vector<int32_t> map, cl;   // the regime of every edge, and the clusters that hold a painted family, in index order
+  std::string why;
+  if (!L.T.optima_list(n_regimes, regime, value, per_site, map, cl, why)) return e->fail(PGBP_ERR_INVALID, why);
+  if (n_regimes == 0) {   // clear (kernels already enqueued may still read the old optima)
+    HIPCHK(e, hipStreamSynchronize(e->st));
+    L.opt_bufs = LgOptimaBufs{};
+    L.Op = LgOptima{};
+    L.opt_cl.clear();
+    L.disp_cl = DevBuf<int32_t>{};
+    L.n_disp_cl = 0;
+    return PGBP_OK;
+  }
+  const int pp = L.T.p;
+  const size_t ns = per_site ? (size_t)e->plan.n_sites : 1, n = (size_t)n_regimes;
+  // univariate per-site batches: the values once more as [regime][site], whole lines for lanes = sites
+  std::vector<double> vsm;
+  if (per_site && L.T.uni_ok) {
+    const size_t row = (size_t)sm_row(e->plan.n_sites);
+    vsm.assign(n * row, 0.0);
+    for (size_t s = 0; s < ns; ++s)
+      for (size_t i = 0; i < n; ++i) vsm[i * row + s] = value[s * n + i];
+  }
+  LgOptimaBufs B;
+  DevBuf<int32_t> ucl;
+  int32_t n_ucl = 0;
+  int rc;
+  if ((rc = dev_alloc(e, B.regime, map.size()))) return rc;
+  if ((rc = dev_alloc(e, B.value, ns * n * pp))) return rc;
+  if (!vsm.empty() && (rc = dev_alloc(e, B.value_sm, vsm.size()))) return rc;
+  if ((rc = lg_union_clusters(e, L.shift_cl, cl, ucl, &n_ucl))) return rc;
+  // every buffer exists: the copies, then ONE synchronisation whatever they returned (none may outlive the host vectors)
+  hipError_t herr = hipMemcpyAsync(B.regime.get(), map.data(), map.size() * sizeof(int32_t), hipMemcpyHostToDevice, e->st);
+  if (herr == hipSuccess) herr = hipMemcpyAsync(B.value.get(), value, ns * n * pp * sizeof(double), hipMemcpyHostToDevice, e->st);
+  if (herr == hipSuccess && !vsm.empty())
+    herr = hipMemcpyAsync(B.value_sm.get(), vsm.data(), vsm.size() * sizeof(double), hipMemcpyHostToDevice, e->st);
+  const hipError_t serr = hipStreamSynchronize(e->st);  // the host buffers may go away; kernels that read the old optima have finished
+  if (herr == hipSuccess) herr = serr;
+  if (herr != hipSuccess) return e->fail(PGBP_ERR_HIP, std::string("pgbp_lg_set_optima (upload): ") + hipGetErrorString(herr));
+  L.opt_bufs = std::move(B);
+  const LgOptimaBufs& S = L.opt_bufs;
+  L.Op = LgOptima{S.regime.get(), S.value.get(), per_site ? 1 : 0, n_regimes, S.value_sm.get()};
+  L.opt_cl = std::move(cl);
+  L.disp_cl = std::move(ucl);
+  L.n_disp_cl = n_ucl;
+  return PGBP_OK;
+}
+
+// The values alone, into the buffers of the setting in force: what a fit moves at every step.  The regime map, the cluster
+// union and the buffers stay; every check before anything changes.
+int pgbp_lg_update_optima(pgbp_engine* e, const double* value) {
+  DeviceScope device_scope(e);
+  if (!e) return PGBP_ERR_INVALID;
+  if (!e->lg) return e->fail(PGBP_ERR_STATE, "pgbp_lg_update_optima: no family table (call pgbp_lg_setup first)");
+  LgModel& L = *e->lg;
+  if (!L.Op.regime) return e->fail(PGBP_ERR_STATE, "pgbp_lg_update_optima: no optima are set (call pgbp_lg_set_optima first)");
+  if (!value) return e->fail(PGBP_ERR_INVALID, "pgbp_lg_update_optima: no values");
+  const size_t ns = L.Op.per_site ? (size_t)e->plan.n_sites : 1, n = (size_t)L.Op.n, pp = (size_t)L.T.p;
+  for (size_t i = 0; i < ns * n * pp; ++i)
+    if (!std::isfinite(value[i]))
+      return e->fail(PGBP_ERR_INVALID, "pgbp_lg_update_optima: value of regime " + std::to_string((i / pp) % n + 1) +
+                                           (L.Op.per_site ? " at site " + std::to_string(i / (pp * n)) : std::string()) + ": trait " +
+                                           std::to_string(i % pp) + " is not finite");
+  std::vector<double> vsm;
+  if (L.Op.value_sm) {   // (a univariate per-site batch: the [regime][site] rows as well)
+    const size_t row = (size_t)sm_row(e->plan.n_sites);
+    vsm.assign(n * row, 0.0);
+    for (size_t s = 0; s < ns; ++s)
+      for (size_t i = 0; i < n; ++i) vsm[i * row + s] = value[s * n + i];
+  }
+  hipError_t herr = hipStreamSynchronize(e->st);   // kernels that read the old values have finished
+  if (herr == hipSuccess) herr = hipMemcpyAsync(L.opt_bufs.value.get(), value, ns * n * pp * sizeof(double), hipMemcpyHostToDevice, e->st);
+  if (herr == hipSuccess && !vsm.empty())
+    herr = hipMemcpyAsync(L.opt_bufs.value_sm.get(), vsm.data(), vsm.size() * sizeof(double), hipMemcpyHostToDevice, e->st);
+  const hipError_t serr = hipStreamSynchronize(e->st);   // the host buffers may go away
+  if (herr == hipSuccess) herr = serr;
+  if (herr != hipSuccess) return e->fail(PGBP_ERR_HIP, std::string("pgbp_lg_update_optima (upload): ") + hipGetErrorString(herr));
+  return PGBP_OK;
+}
+
+int32_t pgbp_lg_optima_count(pgbp_engine* e) {
+  if (!e || !e->lg) return -1;
+  return e->lg->Op.regime ? e->lg->Op.n : 0;
 }
 
 int pgbp_lg_set_tip_noise(pgbp_engine* e, int32_t n, const int32_t* family, const double* scale, const double* sigma_e,

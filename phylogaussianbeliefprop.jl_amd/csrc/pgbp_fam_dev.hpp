@@ -286,11 +286,12 @@ __device__ __forceinline__ double fam_j(const double* __restrict__ A, int ldv, i
 // From the moments of the family's cluster (mom_solve has run, or nothing is in scope and a barrier stands behind the previous
 // site's reads) to T = j M: fills cf rows 0 .. 2, ipos, oidx, vi, xm, ev = e, Mx = M, the right half of A = j, Tx = j M,
 // ge = g_w.  A noisy tip family (Nz: pgbp_lg_set_tip_noise) has V_OO + E_OO in place of V_OO, and so j = (V_OO + E_OO)^-1
-// in everything formed from it.  false when that variance is not positive definite.  No barrier stands behind the writes of Tx and ge:
+// in everything formed from it.  Op: painted optima (pgbp_lg_set_optima; regime null: none), whose d_opt w gains.
+// false when that variance is not positive definite.  No barrier stands behind the writes of Tx and ge:
 // fam_score_gv begins with it.
-template <int NT>
-__device__ __forceinline__ bool fam_score_T(const FamLds& L, const LgStatic& F, const LgParams& M, const LgShifts& Sh,
-                                            const LgNoise& Nz, const LgSite& S, int f, int m, unsigned long long O, int64_t as, int t) {
+template <int NT, bool OPT>
+__device__ __forceinline__ bool fam_score_T_opt(const FamLds& L, const LgStatic& F, const LgParams& M, const LgShifts& Sh,
+                                                const LgOptima& Op, const LgNoise& Nz, const LgSite& S, int f, int m, unsigned long long O, int64_t as, int t) {
 #pragma clang fp contract(off)
   const int p = F.p, K = F.K, np = F.n_parents[f], nn = np + 1, mo = __popcll(O);
   const int ld = (m + 1) | 1, ldv = fam_ldv(p);
@@ -341,6 +342,9 @@ __device__ __forceinline__ bool fam_score_T(const FamLds& L, const LgStatic& F, 
       for (int k = 0; k < np; ++k) w = w + cf[2 * K + k] * S.theta[tr];
     }
     if (Sh.slot) w = w + lg_shift_d(Sh, F.gamma, f, K, np, tr, p, as);   // a shift of the mean on a parent edge
+    if constexpr (OPT) {   // painted optima
+      if (Op.regime) w = w + lg_optima_d(Op, S.theta, S.alpha, F.length, F.gamma, f, K, np, tr, p, as, 0);
+    }
     L.ev[i] = e - w;
   }
   __syncthreads();
@@ -363,6 +367,13 @@ __device__ __forceinline__ bool fam_score_T(const FamLds& L, const LgStatic& F, 
     L.ge[i] = s;
   }
   return true;
+}
+
+// the body without painted optima (pgbp_edge.hip, pgbp_scan.hip: they refuse while optima are in force)
+template <int NT>
+__device__ __forceinline__ bool fam_score_T(const FamLds& L, const LgStatic& F, const LgParams& M, const LgShifts& Sh,
+                                            const LgNoise& Nz, const LgSite& S, int f, int m, unsigned long long O, int64_t as, int t) {
+  return fam_score_T_opt<NT, false>(L, F, M, Sh, LgOptima{}, Nz, S, f, m, O, as, t);
 }
 
 // G_V = (j M j - j) / 2 (upper triangle computed, mirrored) over M in Mx, which T = j M has consumed; o: null, or the p x p

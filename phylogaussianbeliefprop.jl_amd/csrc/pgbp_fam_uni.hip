@@ -240,6 +240,7 @@ extern "C" int pgbp_lg_shift_scan_sites(pgbp_engine* e, int32_t site_begin, int3
   const bool none = !jump && !lr && !information && !top_lr && !top_family;
   int rc = sites_accept(e, fn, "pgbp_lg_shift_scan", site_begin, site_end, none ? "no output buffer" : nullptr, &c);
   if (rc) return rc;
+  if ((rc = lg_refuse_optima(e, fn, c.L))) return rc;
   if (!(min_info >= 0.0 && min_info < 1.0))
     return engine_fail(e, PGBP_ERR_INVALID, std::string(fn) + ": min_info = " + std::to_string(min_info) + " is not in [0, 1)");
   const LgModel* L = c.L;
@@ -301,6 +302,7 @@ extern "C" int pgbp_lg_edge_gradient_sites(pgbp_engine* e, int32_t site_begin, i
   const bool none = !dlength && !dgamma && !dshift;
   int rc = sites_accept(e, fn, "pgbp_lg_edge_gradient", site_begin, site_end, none ? "no output buffer" : nullptr, &c);
   if (rc) return rc;
+  if ((rc = lg_refuse_optima(e, fn, c.L))) return rc;
   const LgModel* L = c.L;
   const int ns = c.ns, nf = L->T.n_families, K = L->F.K;
   if (ns == 0) return PGBP_OK;
@@ -350,6 +352,7 @@ extern "C" int pgbp_lg_loo_sites(pgbp_engine* e, int32_t site_begin, int32_t sit
   SitesCall c{};
   int rc = sites_accept(e, fn, "pgbp_lg_loo", site_begin, site_end, lpd ? nullptr : "no output buffer (lpd)", &c);
   if (rc) return rc;
+  if ((rc = lg_refuse_optima(e, fn, c.L))) return rc;
   const LgModel* L = c.L;
   const std::vector<int32_t> tips = L->T.loo_tips();   // the tip families, in table order
   const int ns = c.ns, nf = L->T.n_families, nt = (int)tips.size();

@@ -17,6 +17,10 @@
 // and the scalar chain-rule coefficients beside them, so that the slot does not grow with the number of rates.  With tip noise
 // set (pgbp_lg_set_tip_noise) the slot carries one more coefficient behind c_R: scale_f of a noisy tip family (else 0), and the
 // reduction one more p x p block, dsigma_e = sum_f scale_f G_V(f) (pgbp_lg_gradient_noise): Sigma_e is reduced as one more rate.
+// With painted optima in force under OU (pgbp_lg_set_optima) w is sum_k wc_k theta_{r(f,k)} (fam_score_T), the dalpha term of
+// edge k uses theta_{r(f,k)}, c_theta sums wc_k over the unpainted edges only, and the slot carries one coefficient per regime
+// behind the others: doptima[r] = sum_f (sum over the edges of regime r of wc_k) g_w(f), one more block of the reduction
+// (pgbp_lg_gradient_optima).
 // Stage 2 (grad_reduce_blocks, grad_reduce_final): the slots are added in a FIXED order -- 256 consecutive families per
 // workgroup, four lanes of 64 families each in family order, the four lanes added in lane order, then the block partials by a
 // fixed tree -- no floating-point atomics: two calls return the same bytes.  The slots of a chunk of sites at a time
@@ -46,7 +50,7 @@ constexpr int kGradRows = 6;
 template <int NT>
 __global__ __launch_bounds__(NT) void grad_family(const double* __restrict__ pool, int64_t pool_stride,
                                                   const int64_t* __restrict__ boff, const int32_t* __restrict__ bdim, int bs,
-                                                  int fp, LgStatic F, LgParams M, LgShifts Sh, LgNoise Nz,
+                                                  int fp, LgStatic F, LgParams M, LgShifts Sh, LgOptima Op, LgNoise Nz,
                                                   const int32_t* __restrict__ fam_cluster,
                                                   int n_fam, int site0, int n_sites, double* __restrict__ slots,
                                                   int32_t* __restrict__ info, int info0) {
@@ -61,7 +65,10 @@ __global__ __launch_bounds__(NT) void grad_family(const double* __restrict__ poo
   // with tip noise set the slot carries one more coefficient behind those of the rates: scale_f of a noisy tip family (else
   // 0), the weight of G_V in dsigma_e -- Sigma_e is reduced as one more rate
   const int nrs = nr + (Nz.slot ? 1 : 0);
-  const int sl = p * p + p + 3 + nrs;
+  // with painted optima in force (pgbp_lg_set_optima) one more coefficient per regime behind those: the sum of wc_k over the
+  // family's edges of that regime, the weight of g_w in doptima[regime]
+  const int nopt = Op.regime ? Op.n : 0;
+  const int sl = p * p + p + 3 + nrs + nopt;
   const int DA = p * p + p, CMU = DA + 1, CTH = DA + 2, CR = DA + 3;
   const FamLds L = fam_carve(grad_lds, m, p, K, kGradRows, 0);
   const int ldv = fam_ldv(p);
@@ -95,7 +102,7 @@ __global__ __launch_bounds__(NT) void grad_family(const double* __restrict__ poo
       for (int k = t; k < np; k += NT)
         lg_coefs_dalpha(M.model, S.alpha, F.length[(size_t)f * K + k], F.gamma[(size_t)f * K + k], cf[3 * K + k], cf[4 * K + k],
                         cf[5 * K + k]);
-      if (!fam_score_T<NT>(L, F, M, Sh, Nz, S, f, m, O, as, t)) st = 1;
+      if (!fam_score_T_opt<NT, true>(L, F, M, Sh, Op, Nz, S, f, m, O, as, t)) st = 1;
     }
     if (st != 0) {
       for (int a = t; a < sl; a += NT) o[a] = NAN;
@@ -114,11 +121,14 @@ __global__ __launch_bounds__(NT) void grad_family(const double* __restrict__ poo
       } else {
         for (int k = 0; k < np; ++k) {
           if (L.ipos[k + 1] < 0) cmu = cmu - fam_c(cf, k + 1);   // qc_k: the parent is the fixed root
-          cth = cth + cf[2 * K + k];
+          if (!Op.regime || Op.regime[(size_t)f * K + k] <= 0) cth = cth + cf[2 * K + k];   // theta: the unpainted edges
         }
         if (ou) {
           for (int k = 0; k < np; ++k) {
             const double* __restrict__ Rk = S.R + (int64_t)F.color[(size_t)f * K + k] * p * p;
+            // the optimum of this edge: theta, or the value of its regime
+            const int rk = Op.regime ? Op.regime[(size_t)f * K + k] : 0;
+            const double* __restrict__ thk = rk > 0 ? Op.value + ((Op.per_site ? as * Op.n : 0) + (rk - 1)) * p : S.theta;
             double trGR = 0.0, thg = 0.0, gq = 0.0;
             for (int i = 0; i < mo; ++i) {
               for (int l = 0; l < mo; ++l) {
@@ -134,7 +144,7 @@ __global__ __launch_bounds__(NT) void grad_family(const double* __restrict__ poo
                 }
                 gq = gq + fam_j(L.A, ldv, mo, l, i) * ex;
               }
-              if (S.theta) thg = thg + S.theta[L.oidx[i]] * L.ge[i];
+              if (thk) thg = thg + thk[L.oidx[i]] * L.ge[i];
             }
             da = da + cf[4 * K + k] * trGR + cf[5 * K + k] * thg + cf[3 * K + k] * gq;
           }
@@ -157,10 +167,17 @@ __global__ __launch_bounds__(NT) void grad_family(const double* __restrict__ poo
       }
       o[CR + r] = cr;
     }
+    for (int r = t; r < nopt; r += NT) {
+      double co = 0.0;
+      for (int k = 0; k < np; ++k)
+        if (Op.regime[(size_t)f * K + k] == r + 1) co = co + cf[2 * K + k];
+      o[CR + nrs + r] = co;
+    }
   }
 }
 
-// entry en of a site's gradient [dR (n_rates * p*p) | dmu (p) | dtheta (p) | dalpha] as this family's slot gives it
+// entry en of a site's gradient [dR (n_rates * p*p) | dmu (p) | dtheta (p) | dalpha | doptima (n_regimes * p)] as this
+// family's slot gives it
 __device__ __forceinline__ double grad_entry(const double* __restrict__ o, int en, int p, int nr) {
 #pragma clang fp contract(off)
   const int pp = p * p, DA = pp + p;
@@ -172,18 +189,21 @@ __device__ __forceinline__ double grad_entry(const double* __restrict__ o, int e
   if (en < p) return o[pp + en] * o[DA + 1];
   en -= p;
   if (en < p) return o[pp + en] * o[DA + 2];
-  return o[DA];
+  if (en == p) return o[DA];
+  en -= p + 1;   // doptima[r][trait] = g_w[trait] * (the slot's coefficient of regime r)
+  const int r = en / p;
+  return o[pp + en - r * p] * o[DA + 3 + nr + r];
 }
 
 // partial[site][block][entry]: kGradFamBlock consecutive families, lane q = t / 64 adds its 64 families in family order,
 // the four lanes are added in lane order
-__global__ __launch_bounds__(256) void grad_reduce_blocks(const double* __restrict__ slots, int n_fam, int p, int nr,
+__global__ __launch_bounds__(256) void grad_reduce_blocks(const double* __restrict__ slots, int n_fam, int p, int nr, int nopt,
                                                           int n_ent, int n_sites, double* __restrict__ partial) {
 #pragma clang fp contract(off)
   __shared__ double part[256];
   const int t = threadIdx.x, el = t & 63, q = t >> 6;
   const int en = blockIdx.x * 64 + el, fb = blockIdx.y, nfb = gridDim.y;
-  const int sl = p * p + p + 3 + nr;
+  const int sl = p * p + p + 3 + nr + nopt;
   for (int site = blockIdx.z; site < n_sites; site += gridDim.z) {
     double acc = 0.0;
     if (en < n_ent) {
@@ -223,7 +243,7 @@ __global__ __launch_bounds__(256) void grad_reduce_final(const double* __restric
 using namespace pgbp;
 
 static int lg_gradient(pgbp_engine* e, int32_t site_begin, int32_t site_end, double* dR, double* dmu, double* dalpha,
-                       double* dtheta, double* dsigma_e, int32_t* info) {
+                       double* dtheta, double* dsigma_e, double* doptima, int32_t* info) {
   if (!e) return PGBP_ERR_INVALID;
   const LgModel* L = nullptr;
   int rc = lg_sweep_state(e, "pgbp_lg_gradient", site_begin, site_end, &L, "pgbp_lg_gradient_sites");
@@ -232,6 +252,13 @@ static int lg_gradient(pgbp_engine* e, int32_t site_begin, int32_t site_end, dou
   const LgParams& M = L->M;
   const LgShifts& Sh = L->Sh;
   const LgNoise& Nz = L->Nz;
+  LgOptima Op = L->optima_in_force();
+  Op.value_sm = nullptr;   // (the [regime][site] rows are for lanes = sites)
+  const int nopt = Op.regime ? Op.n : 0, nopt_out = L->Op.regime ? L->Op.n : 0;
+  // painted optima change dtheta and dalpha: a caller that cannot take doptima would read them as the unpainted model's
+  if (nopt > 0 && !doptima)
+    return engine_fail(e, PGBP_ERR_INVALID, "pgbp_lg_gradient: painted optima are in force (pgbp_lg_set_optima): use "
+                                            "pgbp_lg_gradient_optima, which returns doptima");
   if (!dR || !dmu) return engine_fail(e, PGBP_ERR_INVALID, "pgbp_lg_gradient: no output buffer");
   if (M.model == PGBP_LG_OU && (!dalpha || !dtheta))
     return engine_fail(e, PGBP_ERR_INVALID, "pgbp_lg_gradient: the OU model needs dalpha and dtheta");
@@ -255,7 +282,7 @@ static int lg_gradient(pgbp_engine* e, int32_t site_begin, int32_t site_end, dou
   const int ns = site_end - site_begin;
   if (ns == 0) return PGBP_OK;
   const bool ou = M.model == PGBP_LG_OU;
-  const int pp = p * p, n_ent = nr * pp + 2 * p + 1;
+  const int pp = p * p, n_ent = nr * pp + 2 * p + 1 + nopt * p;
   auto scatter = [&](const double* src, const int32_t* inf) {   // a site's [dR | dmu | dtheta | dalpha] to the caller's arrays
     for (int s = 0; s < ns; ++s) {
       const bool bad = inf && inf[s] != 0;
@@ -267,6 +294,9 @@ static int lg_gradient(pgbp_engine* e, int32_t site_begin, int32_t site_end, dou
       if (dtheta)
         for (int a = 0; a < p; ++a) dtheta[(size_t)s * p + a] = bad ? NAN : ((g && ou) ? g[nr * pp + p + a] : 0.0);
       if (dalpha) dalpha[s] = bad ? NAN : ((g && ou) ? g[nr * pp + 2 * p] : 0.0);
+      if (doptima)   // (set under BM: the optima have no effect, their derivative is 0)
+        for (int a = 0; a < nopt_out * p; ++a)
+          doptima[(size_t)s * nopt_out * p + a] = bad ? NAN : ((g && nopt > 0) ? g[nr * pp + 2 * p + 1 + a] : 0.0);
       if (info) info[s] = inf ? inf[s] : 0;
     }
   };
@@ -274,7 +304,7 @@ static int lg_gradient(pgbp_engine* e, int32_t site_begin, int32_t site_end, dou
     scatter(nullptr, nullptr);
     return PGBP_OK;
   }
-  const int sl = pp + p + 3 + nr;
+  const int sl = pp + p + 3 + nr + nopt;
   const int64_t per_site = (int64_t)nf * sl;
   const int chunk = (int)std::max<int64_t>(1, std::min<int64_t>(ns, ((int64_t)32 << 20) / per_site));
   const int nfb = (nf + kGradFamBlock - 1) / kGradFamBlock;
@@ -298,11 +328,11 @@ static int lg_gradient(pgbp_engine* e, int32_t site_begin, int32_t site_end, dou
       const int n = std::min(chunk, ns - s0), gy = std::min(n, 65535);
       if (max_m <= 64)
         hipLaunchKernelGGL(grad_family<64>, dim3(nf, gy), dim3(64), lds_bytes, v.st, v.pool, pl.pool_stride(), v.boff, v.bdim,
-                           v.bs16, pl.fast_p, F, M, Sh, Nz, d_fcl.get(), nf, site_begin + s0, n, d_slots.get(), d_info.get(), s0);
+                           v.bs16, pl.fast_p, F, M, Sh, Op, Nz, d_fcl.get(), nf, site_begin + s0, n, d_slots.get(), d_info.get(), s0);
       else
         hipLaunchKernelGGL(grad_family<256>, dim3(nf, gy), dim3(256), lds_bytes, v.st, v.pool, pl.pool_stride(), v.boff, v.bdim,
-                           v.bs16, pl.fast_p, F, M, Sh, Nz, d_fcl.get(), nf, site_begin + s0, n, d_slots.get(), d_info.get(), s0);
-      hipLaunchKernelGGL(grad_reduce_blocks, dim3((n_ent + 63) / 64, nfb, gy), dim3(256), 0, v.st, d_slots.get(), nf, p, nr, n_ent, n,
+                           v.bs16, pl.fast_p, F, M, Sh, Op, Nz, d_fcl.get(), nf, site_begin + s0, n, d_slots.get(), d_info.get(), s0);
+      hipLaunchKernelGGL(grad_reduce_blocks, dim3((n_ent + 63) / 64, nfb, gy), dim3(256), 0, v.st, d_slots.get(), nf, p, nr, nopt, n_ent, n,
                          d_part.get());
       hipLaunchKernelGGL(grad_reduce_final, dim3(n_ent, gy), dim3(256), 0, v.st, d_part.get(), nfb, n_ent, n, d_out.get(), s0);
     }
@@ -320,10 +350,17 @@ static int lg_gradient(pgbp_engine* e, int32_t site_begin, int32_t site_end, dou
 
 extern "C" int pgbp_lg_gradient(pgbp_engine* e, int32_t site_begin, int32_t site_end, double* dR, double* dmu, double* dalpha,
                                 double* dtheta, int32_t* info) {
-  return lg_gradient(e, site_begin, site_end, dR, dmu, dalpha, dtheta, nullptr, info);
+  return lg_gradient(e, site_begin, site_end, dR, dmu, dalpha, dtheta, nullptr, nullptr, info);
 }
 
 extern "C" int pgbp_lg_gradient_noise(pgbp_engine* e, int32_t site_begin, int32_t site_end, double* dR, double* dmu,
                                       double* dalpha, double* dtheta, double* dsigma_e, int32_t* info) {
-  return lg_gradient(e, site_begin, site_end, dR, dmu, dalpha, dtheta, dsigma_e, info);
+  return lg_gradient(e, site_begin, site_end, dR, dmu, dalpha, dtheta, dsigma_e, nullptr, info);
+}
+
+extern "C" int pgbp_lg_gradient_optima(pgbp_engine* e, int32_t site_begin, int32_t site_end, double* dR, double* dmu,
+                                       double* dalpha, double* dtheta, double* dsigma_e, double* doptima, int32_t* info) {
+  if (e && !doptima && pgbp_lg_optima_count(e) > 0)
+    return engine_fail(e, PGBP_ERR_INVALID, "pgbp_lg_gradient_optima: no output buffer (doptima)");
+  return lg_gradient(e, site_begin, site_end, dR, dmu, dalpha, dtheta, dsigma_e, doptima, info);
 }

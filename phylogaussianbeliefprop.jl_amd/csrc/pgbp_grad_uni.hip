@@ -35,20 +35,29 @@
 
 namespace pgbp {
 
-constexpr int kGradUniRates = 4;   // rates a launch accumulates in registers
+constexpr int kGradUniRates = 4;    // rates a launch accumulates in registers
+constexpr int kGradUniOptima = 4;   // regimes a launch of the painted instance accumulates in registers
 
-// entries of a site's gradient: [dR (n_rates) | dsigma_e | dmu | dtheta | dalpha]
-__host__ __device__ inline int grad_uni_entries(int nr) { return nr + 4; }
+// entries of a site's gradient: [dR (n_rates) | dsigma_e | dmu | dtheta | dalpha | doptima (n_regimes)]
+__host__ __device__ inline int grad_uni_entries(int nr, int nopt = 0) { return nr + 4 + nopt; }
 
 // partial: [blocks][entries][part_row], pinfo: [blocks][part_row] (written by the launch of the first rates, r0 == 0).  The
 // members of SitesArgs as a flat list: with the struct the kernel keeps its 129 VGPRs but spills 24 more SGPRs into them.
-template <bool SM>
-__global__ __launch_bounds__(256) void grad_uni_family(const double* __restrict__ pool, int64_t stride,
-                                                       const int64_t* __restrict__ off, const int32_t* __restrict__ bdim,
-                                                       LgStatic F, LgParams M, LgShifts Sh, LgNoise Nz, LgSiteMiss Ms,
-                                                       const int32_t* __restrict__ fam_cluster, int n_fam, int64_t data_row_len,
-                                                       int site0, int n_sites, int r0, int64_t part_row,
-                                                       double* __restrict__ partial, int32_t* __restrict__ pinfo) {
+//
+// OPT: the instance for painted optima under OU (pgbp_lg_set_optima; pgbp_lg_gradient_sites_optima).  The regime of an edge is
+// uniform across the wavefront (scalar loads); its optimum theta_r is a whole line of the [regime][site] rows, or one scalar
+// when the values are shared.  w = sum_k wc_k theta_{r(f,k)}, the dwc term of dalpha uses theta_{r(f,k)}, dtheta sums wc_k
+// over the unpainted edges, and doptima[r] = sum over the edges of regime r of wc_k g_w: kGradUniOptima regimes from g0 on in
+// registers per launch, entries [nr + 4 + r] of the partial sums.  The instance without optima is the kernel as it was: every
+// painted statement is under `if constexpr (OPT)`.
+template <bool SM, bool OPT>
+__device__ __forceinline__ void grad_uni_family_body(const double* __restrict__ pool, int64_t stride,
+                                                     const int64_t* __restrict__ off, const int32_t* __restrict__ bdim,
+                                                     const LgStatic& F, const LgParams& M, const LgShifts& Sh, const LgNoise& Nz,
+                                                     const LgSiteMiss& Ms, const LgOptima& Op,
+                                                     const int32_t* __restrict__ fam_cluster, int n_fam, int64_t data_row_len,
+                                                     int site0, int n_sites, int r0, int g0, int64_t part_row,
+                                                     double* __restrict__ partial, int32_t* __restrict__ pinfo) {
 #pragma clang fp contract(off)
   const int s = blockIdx.x * 256 + threadIdx.x, fb = blockIdx.y;
   if (s >= n_sites) return;   // (a lane past the range: no barrier follows, and no other lane's store is its to make)
@@ -61,6 +70,10 @@ __global__ __launch_bounds__(256) void grad_uni_family(const double* __restrict_
 #pragma unroll
   for (int i = 0; i < kGradUniRates; ++i) accR[i] = 0.0;
   double dsig = 0.0, dmu = 0.0, dth = 0.0, da = 0.0;
+  double accO[OPT ? kGradUniOptima : 1];
+#pragma unroll
+  for (int i = 0; i < (OPT ? kGradUniOptima : 1); ++i) accO[i] = 0.0;
+  const int nopt = OPT ? Op.n : 0;
   int bad = kFamUniNoInfo;
   const int f0 = fb * kFamUniBlock, f1 = min(f0 + kFamUniBlock, n_fam);
   for (int f = f0; f < f1; ++f) {
@@ -92,6 +105,9 @@ __global__ __launch_bounds__(256) void grad_uni_family(const double* __restrict_
     double cr[kGradUniRates];
 #pragma unroll
     for (int i = 0; i < kGradUniRates; ++i) cr[i] = 0.0;
+    double co[OPT ? kGradUniOptima : 1];   // sum of wc_k over the edges of regime g0 + 1 + i
+#pragma unroll
+    for (int i = 0; i < (OPT ? kGradUniOptima : 1); ++i) co[i] = 0.0;
     if (np == 0) {
       const int col = F.color[(size_t)f * K];
       V = S.R[col];
@@ -109,10 +125,22 @@ __global__ __launch_bounds__(256) void grad_uni_family(const double* __restrict_
         lg_coefs_dalpha(M.model, S.alpha, len, gam, dqc, dvc, dwc);
         const double Rk = S.R[col];
         V = V + vc * Rk;
-        cth = cth + wc;
-        if (S.theta) w = w + wc * theta;
         A1 = A1 + dvc * Rk;
-        A2 = A2 + dwc;
+        if constexpr (OPT) {
+          const int rk = Op.regime[(size_t)f * K + k];   // (uniform across the wavefront)
+          double thk = theta;
+          if (rk > 0) thk = Op.value_sm ? Op.value_sm[(int64_t)(rk - 1) * data_row_len + as] : Op.value[rk - 1];
+          else cth = cth + wc;
+          w = w + wc * thk;
+          A2 = A2 + dwc * thk;   // (the optimum inside the sum: it differs by edge)
+#pragma unroll
+          for (int i = 0; i < kGradUniOptima; ++i)
+            if (rk == g0 + 1 + i) co[i] = co[i] + wc;
+        } else {
+          cth = cth + wc;
+          if (S.theta) w = w + wc * theta;
+          A2 = A2 + dwc;
+        }
         if (pk == 0) {
           u0 = u0 - qc;
           D0 = D0 + dqc;
@@ -147,12 +175,18 @@ __global__ __launch_bounds__(256) void grad_uni_family(const double* __restrict_
       if (sn >= 0) dsig = dsig + G * Nz.scale[sn];
       dmu = dmu + ge * cmu;
       dth = dth + ge * cth;
-      if (ou) da = da + ((A1 * G + A2 * (theta * ge)) + j * (e * A3 + (D0 * su0 + D1 * su1)));
+      if constexpr (OPT) {
+#pragma unroll
+        for (int i = 0; i < kGradUniOptima; ++i) accO[i] = accO[i] + ge * co[i];
+        da = da + ((A1 * G + A2 * ge) + j * (e * A3 + (D0 * su0 + D1 * su1)));
+      } else {
+        if (ou) da = da + ((A1 * G + A2 * (theta * ge)) + j * (e * A3 + (D0 * su0 + D1 * su1)));
+      }
     } else {
       bad = min(bad, c + 1);
     }
   }
-  const int n_ent = grad_uni_entries(nr);
+  const int n_ent = grad_uni_entries(nr, nopt);
   double* __restrict__ o = partial + (int64_t)fb * n_ent * part_row + s;
 #pragma unroll
   for (int i = 0; i < kGradUniRates; ++i)
@@ -164,6 +198,35 @@ __global__ __launch_bounds__(256) void grad_uni_family(const double* __restrict_
     o[(int64_t)(nr + 3) * part_row] = da;
     pinfo[(int64_t)fb * part_row + s] = bad;
   }
+  if constexpr (OPT) {
+#pragma unroll
+    for (int i = 0; i < kGradUniOptima; ++i)
+      if (g0 + i < nopt) o[(int64_t)(nr + 4 + g0 + i) * part_row] = accO[i];
+  }
+}
+
+template <bool SM>
+__global__ __launch_bounds__(256) void grad_uni_family(const double* __restrict__ pool, int64_t stride,
+                                                       const int64_t* __restrict__ off, const int32_t* __restrict__ bdim,
+                                                       LgStatic F, LgParams M, LgShifts Sh, LgNoise Nz, LgSiteMiss Ms,
+                                                       const int32_t* __restrict__ fam_cluster, int n_fam, int64_t data_row_len,
+                                                       int site0, int n_sites, int r0, int64_t part_row,
+                                                       double* __restrict__ partial, int32_t* __restrict__ pinfo) {
+  grad_uni_family_body<SM, false>(pool, stride, off, bdim, F, M, Sh, Nz, Ms, LgOptima{}, fam_cluster, n_fam, data_row_len, site0,
+                                  n_sites, r0, 0, part_row, partial, pinfo);
+}
+
+// the painted instance: launch l carries the rates from l * kGradUniRates and the regimes from l * kGradUniOptima on
+template <bool SM>
+__global__ __launch_bounds__(256) void grad_uni_family_optima(const double* __restrict__ pool, int64_t stride,
+                                                              const int64_t* __restrict__ off, const int32_t* __restrict__ bdim,
+                                                              LgStatic F, LgParams M, LgShifts Sh, LgNoise Nz, LgSiteMiss Ms,
+                                                              LgOptima Op, const int32_t* __restrict__ fam_cluster, int n_fam,
+                                                              int64_t data_row_len, int site0, int n_sites, int r0, int g0,
+                                                              int64_t part_row, double* __restrict__ partial,
+                                                              int32_t* __restrict__ pinfo) {
+  grad_uni_family_body<SM, true>(pool, stride, off, bdim, F, M, Sh, Nz, Ms, Op, fam_cluster, n_fam, data_row_len, site0, n_sites, r0,
+                                 g0, part_row, partial, pinfo);
 }
 
 // out[entry][out0 + site] = the blocks' partials added in index order; info[out0 + site] = the smallest mark of a block, 0: none
@@ -189,14 +252,20 @@ __global__ __launch_bounds__(256) void grad_uni_reduce(const double* __restrict_
 
 using namespace pgbp;
 
-extern "C" int pgbp_lg_gradient_sites(pgbp_engine* e, int32_t site_begin, int32_t site_end, double* dR, double* dmu,
-                                      double* dalpha, double* dtheta, double* dsigma_e, int32_t* info) {
+static int lg_gradient_sites(pgbp_engine* e, const char* fn, int32_t site_begin, int32_t site_end, double* dR, double* dmu,
+                             double* dalpha, double* dtheta, double* dsigma_e, double* doptima, bool takes_optima, int32_t* info) {
   if (!e) return PGBP_ERR_INVALID;
-  const char* fn = "pgbp_lg_gradient_sites";
   SitesCall c{};
   int rc = sites_accept_state(e, fn, site_begin, site_end, &c);
   if (rc) return rc;
   const LgModel* L = c.L;
+  const LgOptima Op = L->optima_in_force();
+  const int nopt = Op.regime ? Op.n : 0, nopt_out = L->Op.regime ? L->Op.n : 0;
+  // painted optima change dtheta and dalpha: a caller that cannot take doptima would read them as the unpainted model's
+  if (nopt > 0 && !takes_optima)
+    return engine_fail(e, PGBP_ERR_INVALID, std::string(fn) + ": painted optima are in force (pgbp_lg_set_optima): use "
+                                                "pgbp_lg_gradient_sites_optima, which returns doptima");
+  if (nopt_out > 0 && takes_optima && !doptima) return engine_fail(e, PGBP_ERR_INVALID, std::string(fn) + ": no output buffer (doptima)");
   if (!dR || !dmu) return engine_fail(e, PGBP_ERR_INVALID, std::string(fn) + ": no output buffer");
   const bool ou = L->M.model == PGBP_LG_OU;
   if (ou && (!dalpha || !dtheta)) return engine_fail(e, PGBP_ERR_INVALID, std::string(fn) + ": the OU model needs dalpha and dtheta");
@@ -204,7 +273,7 @@ extern "C" int pgbp_lg_gradient_sites(pgbp_engine* e, int32_t site_begin, int32_
   const int ns = c.ns;
   if (ns == 0) return PGBP_OK;
   const int nr = L->F.n_rates, nf = L->T.n_families;
-  const int n_ent = grad_uni_entries(nr);
+  const int n_ent = grad_uni_entries(nr, nopt);
   const int nfb = std::max(1, (nf + kFamUniBlock - 1) / kFamUniBlock);
   const int chunk = fam_uni_chunk(ns, (int64_t)nfb * n_ent);   // the partials of a chunk of sites at a time
   std::vector<double> out((size_t)n_ent * ns);
@@ -223,9 +292,15 @@ extern "C" int pgbp_lg_gradient_sites(pgbp_engine* e, int32_t site_begin, int32_
     const int n = std::min(chunk, ns - s0);
     const SitesArgs A = sites_args(c, site_begin + s0, n, chunk, d_fcl.get());
     const dim3 grid((n + 255) / 256, nfb);
-    for (int r0 = 0; r0 == 0 || r0 < nr; r0 += kGradUniRates)
-      PGBP_SITES_LAUNCH(S, c.U.sm, grad_uni_family, grid, A.pool, A.stride, A.off, A.bdim, L->F, L->M, L->Sh, L->Nz, L->Ms, A.fam_cluster, nf,
-                        A.data_row_len, A.site0, A.n_sites, r0, A.row, d_part.get(), d_pinfo.get());
+    if (nopt == 0) {
+      for (int r0 = 0; r0 == 0 || r0 < nr; r0 += kGradUniRates)
+        PGBP_SITES_LAUNCH(S, c.U.sm, grad_uni_family, grid, A.pool, A.stride, A.off, A.bdim, L->F, L->M, L->Sh, L->Nz, L->Ms, A.fam_cluster, nf,
+                          A.data_row_len, A.site0, A.n_sites, r0, A.row, d_part.get(), d_pinfo.get());
+    } else {   // the painted instance: rates and regimes in groups, side by side
+      for (int r0 = 0, g0 = 0; r0 == 0 || r0 < nr || g0 < nopt; r0 += kGradUniRates, g0 += kGradUniOptima)
+        PGBP_SITES_LAUNCH(S, c.U.sm, grad_uni_family_optima, grid, A.pool, A.stride, A.off, A.bdim, L->F, L->M, L->Sh, L->Nz, L->Ms, Op,
+                          A.fam_cluster, nf, A.data_row_len, A.site0, A.n_sites, r0, g0, A.row, d_part.get(), d_pinfo.get());
+    }
     S.launch(grad_uni_reduce, dim3(grid.x, n_ent + 1), d_part.get(), d_pinfo.get(), nfb, n_ent, n, (int64_t)chunk, d_out.get(),
              d_info.get(), s0, (int64_t)ns);
     S.check();
@@ -242,7 +317,21 @@ extern "C" int pgbp_lg_gradient_sites(pgbp_engine* e, int32_t site_begin, int32_
     dmu[s] = ent(nr + 1);
     if (dtheta) dtheta[s] = bad ? (double)NAN : (ou ? out[(size_t)(nr + 2) * ns + s] : 0.0);
     if (dalpha) dalpha[s] = bad ? (double)NAN : (ou ? out[(size_t)(nr + 3) * ns + s] : 0.0);
+    if (doptima)   // (set under BM: the optima have no effect, their derivative is 0)
+      for (int r = 0; r < nopt_out; ++r)
+        doptima[(size_t)s * nopt_out + r] = bad ? (double)NAN : (nopt > 0 ? out[(size_t)(nr + 4 + r) * ns + s] : 0.0);
     if (info) info[s] = inf[s];
   }
   return PGBP_OK;
+}
+
+extern "C" int pgbp_lg_gradient_sites(pgbp_engine* e, int32_t site_begin, int32_t site_end, double* dR, double* dmu,
+                                      double* dalpha, double* dtheta, double* dsigma_e, int32_t* info) {
+  return lg_gradient_sites(e, "pgbp_lg_gradient_sites", site_begin, site_end, dR, dmu, dalpha, dtheta, dsigma_e, nullptr, false, info);
+}
+
+extern "C" int pgbp_lg_gradient_sites_optima(pgbp_engine* e, int32_t site_begin, int32_t site_end, double* dR, double* dmu,
+                                             double* dalpha, double* dtheta, double* dsigma_e, double* doptima, int32_t* info) {
+  return lg_gradient_sites(e, "pgbp_lg_gradient_sites_optima", site_begin, site_end, dR, dmu, dalpha, dtheta, dsigma_e, doptima, true,
+                           info);
 }

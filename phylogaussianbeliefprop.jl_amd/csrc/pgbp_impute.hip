@@ -289,6 +289,7 @@ extern "C" int pgbp_lg_impute(pgbp_engine* e, int32_t site_begin, int32_t site_e
   const LgModel* L = nullptr;
   int rc = lg_sweep_state(e, "pgbp_lg_impute", site_begin, site_end, &L, "pgbp_lg_impute_sites");
   if (rc) return rc;
+  if ((rc = lg_refuse_optima(e, "pgbp_lg_impute", L))) return rc;
   const LgStatic& F = L->F;
   const LgParams& M = L->M;
   const LgShifts& Sh = L->Sh;

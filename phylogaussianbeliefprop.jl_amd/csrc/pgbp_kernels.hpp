@@ -209,12 +209,22 @@ struct LgShifts {
   int32_t per_site, n;
   const double* value_sm;  // univariate per-site batches: the values once more as [n][site] (rows padded: sm_row), else null
 };
-// the correction of a fill for the shifts (pgbp_shift.hip), launched right after it: one workgroup per (cluster of d_shcl, site)
-// adds Delta h and Delta g to the records in pool and, when not null, fpool (current layout)
-void launch_lg_shift(const LgStatic& F, const LgParams& M, const LgShifts& S, const int32_t* d_shcl, int n_shcl, double* pool,
+// Painted optima under OU (pgbp_lg_set_optima): the optimum of parent edge k of family f is value[regime - 1] where
+// regime[f * K + k] > 0, theta of LgParams where it is 0.  A struct of its own, as LgShifts is.  regime == null: none in force
+// (none set, or the model is BM, under which the optima have no effect).
+struct LgOptima {
+  const int32_t* regime;   // [n_families * K]
+  const double* value;     // [n][p], per_site: [n_sites][n][p]
+  int32_t per_site, n;
+  const double* value_sm;  // univariate per-site batches: the values once more as [n][site] (rows padded: sm_row), else null
+};
+// the correction of a fill for the displacements -- shifts and painted optima (pgbp_shift.hip) --, launched right after it: one
+// workgroup per (cluster of d_shcl, site) adds Delta h and Delta g to the records in pool and, when not null, fpool (current
+// layout).  d_shcl: the clusters that hold a shifted or a painted family
+void launch_lg_shift(const LgStatic& F, const LgParams& M, const LgShifts& S, const LgOptima& Op, const int32_t* d_shcl, int n_shcl, double* pool,
                      int64_t pool_stride, double* fpool, int64_t fpool_stride, const int64_t* d_boff, const int32_t* d_dim,
                      int bs16, int fast_p, int max_dim, int n_sites, hipStream_t st);
-void launch_lg_shift_uni_sm(const LgStatic& F, const LgParams& M, const LgShifts& S, const int32_t* d_shcl, int n_shcl,
+void launch_lg_shift_uni_sm(const LgStatic& F, const LgParams& M, const LgShifts& S, const LgOptima& Op, const int32_t* d_shcl, int n_shcl,
                             double* pool_sm, double* fpool_sm, const int64_t* d_poff, const int32_t* d_dim, int n_sites,
                             hipStream_t st);
 // Measurement error at the tips (pgbp_lg_set_tip_noise): the variance of a noisy tip family gains
@@ -231,11 +241,12 @@ struct LgNoise {
 // per (cluster of d_ncl, site) adds Delta J, Delta h and Delta g to the records in pool and, when not null, fpool (current
 // layout).  max_dim_ncl: the largest dimension among the clusters of d_ncl (lg_noise_lds_bytes: what the kernel needs for it)
 size_t lg_noise_lds_bytes(int p, int K, int max_dim_ncl);
-void launch_lg_noise(const LgStatic& F, const LgParams& M, const LgShifts& S, const LgNoise& Nz, const int32_t* d_ncl, int n_ncl,
+void launch_lg_noise(const LgStatic& F, const LgParams& M, const LgShifts& S, const LgOptima& Op, const LgNoise& Nz,
+                     const int32_t* d_ncl, int n_ncl,
                      double* pool, int64_t pool_stride, double* fpool, int64_t fpool_stride, const int64_t* d_boff,
                      const int32_t* d_dim, int bs16, int fast_p, int max_dim_ncl, int n_sites, hipStream_t st);
-void launch_lg_noise_uni_sm(const LgStatic& F, const LgParams& M, const LgShifts& S, const LgNoise& Nz, const int32_t* d_ncl,
-                            int n_ncl, double* pool_sm, double* fpool_sm, const int64_t* d_poff, const int32_t* d_dim,
+void launch_lg_noise_uni_sm(const LgStatic& F, const LgParams& M, const LgShifts& S, const LgOptima& Op, const LgNoise& Nz,
+                            const int32_t* d_ncl, int n_ncl, double* pool_sm, double* fpool_sm, const int64_t* d_poff, const int32_t* d_dim,
                             int n_sites, hipStream_t st);
 // Per-site missing tips of a univariate batch (pgbp_lg_set_site_missing): bit (s & 63) of word [row][s >> 6] set = the tip with
 // that data row is not observed at site s.  A struct of its own, as LgShifts and LgNoise are.  words == null: no mask is set.
@@ -248,7 +259,8 @@ struct LgSiteMiss {
 // whose site masks a family of the cluster rewrites the cluster's record in pool and, when not null, fpool, without the masked
 // families; every other thread stores nothing.  sm != 0: the site-minor layout (off: packed offsets, stride / fstride: the row
 // length), else the plain one (off: Plan::boff, stride / fstride: doubles per site of pool / fpool)
-void launch_lg_sitemiss(const LgStatic& F, const LgParams& M, const LgShifts& S, const LgNoise& Nz, const LgSiteMiss& Ms,
+void launch_lg_sitemiss(const LgStatic& F, const LgParams& M, const LgShifts& S, const LgOptima& Op, const LgNoise& Nz,
+                        const LgSiteMiss& Ms,
                         const int32_t* d_mcl, int n_mcl, int sm, double* pool, int64_t stride, double* fpool, int64_t fstride,
                         const int64_t* d_off, const int32_t* d_dim, int n_sites, hipStream_t st);
 // the setter's own step: 0.0 into data [site][row] and data_sm [row][site] at every masked entry

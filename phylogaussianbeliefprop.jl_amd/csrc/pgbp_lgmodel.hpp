@@ -25,6 +25,11 @@ struct LgShiftBufs {
   DevBuf<int32_t> slot, cl;
   DevBuf<double> value, value_sm;
 };
+// what LgOptima points at (pgbp_lg_set_optima)
+struct LgOptimaBufs {
+  DevBuf<int32_t> regime;
+  DevBuf<double> value, value_sm;
+};
 // what LgNoise points at (pgbp_lg_set_tip_noise), and the clusters the correction kernel visits
 struct LgNoiseBufs {
   DevBuf<int32_t> slot, cl;
@@ -47,6 +52,15 @@ struct LgModel {
   LgShiftBufs shift_bufs;
   LgShifts Sh{};
   int32_t n_shift_cl = 0;
+  // pgbp_lg_set_optima: Op.regime == null: none.  The clusters that hold a shifted (shift_cl) and a painted (opt_cl) family on
+  // the host, and their union on the device (disp_cl, n_disp_cl): what the displacement correction visits while optima are set
+  LgOptimaBufs opt_bufs;
+  LgOptima Op{};
+  std::vector<int32_t> shift_cl, opt_cl;
+  DevBuf<int32_t> disp_cl;
+  int32_t n_disp_cl = 0;
+  // the optima as the kernels take them: none under BM, where wc = 0 and they have no effect
+  LgOptima optima_in_force() const { return (Op.regime && M.model == PGBP_LG_OU) ? Op : LgOptima{}; }
   // pgbp_lg_set_tip_noise: Nz.slot == null: none; the clusters that hold a noisy tip family and the largest of them
   LgNoiseBufs noise_bufs;
   LgNoise Nz{};
@@ -81,6 +95,14 @@ inline int lg_sweep_state(pgbp_engine* e, const char* fn, int32_t site_begin, in
     return engine_fail(e, PGBP_ERR_INVALID, std::string(fn) + ": site range outside the engine's sites");
   *out = L;
   return PGBP_OK;
+}
+
+// A sweep `fn` that forms the families' offsets itself and does not know painted optima (pgbp_lg_set_optima): refused while
+// they are in force under OU, before any launch; PGBP_OK otherwise (under BM the optima have no effect).
+inline int lg_refuse_optima(pgbp_engine* e, const char* fn, const LgModel* L) {
+  if (!L || !L->optima_in_force().regime) return PGBP_OK;
+  return engine_fail(e, PGBP_ERR_INVALID, std::string(fn) + ": painted optima are in force (pgbp_lg_set_optima: " + std::to_string(L->Op.n) +
+                                              " regimes), which this sweep does not honour yet; it would return the unpainted answer");
 }
 
 // The families pgbp_lg_impute_count / _families / _sites list: the statically missing tips of the table (impute_list) and, with

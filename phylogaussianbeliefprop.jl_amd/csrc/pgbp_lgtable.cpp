@@ -224,6 +224,37 @@ bool LgTable::shift_list(int32_t n_shifts, const int32_t* edge, const double* va
   return true;
 }
 
+bool LgTable::optima_list(int32_t n_regimes, const int32_t* regime, const double* value, int32_t per_site, std::vector<int32_t>& map,
+                          std::vector<int32_t>& cl, std::string& why) const {
+  if (n_regimes < 0 || (n_regimes > 0 && (!regime || !value))) return refuse(why, "pgbp_lg_set_optima: a negative count or a missing array");
+  const int nf = n_families;
+  const size_t ns = per_site ? (size_t)n_sites : 1, n = (size_t)n_regimes;
+  std::vector<int32_t> mp(std::max<size_t>(1, (size_t)nf * K), 0), c;
+  for (int f = 0; f < nf && n_regimes > 0; ++f) {
+    bool painted = false;
+    for (int k = 0; k < n_parents[f]; ++k) {
+      const int32_t r = regime[(size_t)f * K + k];
+      if (r < 0 || r > n_regimes)
+        return refuse(why, "pgbp_lg_set_optima: entry " + std::to_string((size_t)f * K + k) + " (family " + std::to_string(f) + ", edge " +
+                               std::to_string(k) + "): regime " + std::to_string(r) + " is not in 0 .. " + std::to_string(n_regimes));
+      mp[(size_t)f * K + k] = r;
+      painted |= r > 0;
+    }
+    if (painted) c.push_back(cluster[f]);
+  }
+  for (size_t s = 0; s < ns; ++s)
+    for (size_t r = 0; r < n; ++r)
+      for (int t = 0; t < p; ++t)
+        if (!std::isfinite(value[(s * n + r) * p + t]))
+          return refuse(why, "pgbp_lg_set_optima: value of regime " + std::to_string(r + 1) + (per_site ? " at site " + std::to_string(s) : std::string()) +
+                                 ": trait " + std::to_string(t) + " is not finite");
+  std::sort(c.begin(), c.end());
+  c.erase(std::unique(c.begin(), c.end()), c.end());
+  map = std::move(mp);
+  cl = std::move(c);
+  return true;
+}
+
 bool LgTable::noise_list(int32_t n, const int32_t* family, const double* scale, const double* sigma_e, const double* se2,
                          int32_t per_site, std::vector<int32_t>& slot, std::vector<double>& sig, std::vector<int32_t>& cl,
                          int32_t* max_dim, std::string& why) const {

@@ -51,6 +51,10 @@ struct LgTable {
   // clusters that hold a shifted family, sorted, each once
   bool shift_list(int32_t n_shifts, const int32_t* edge, const double* value, int32_t per_site, std::vector<int32_t>& slot,
                   std::vector<int32_t>& cl, std::string& why) const;
+  // pgbp_lg_set_optima: map [max(1, n_families * K)] = the regime of that edge, 0 where the edge keeps theta and at every entry
+  // the call ignores (root priors, k >= n_parents[f]); cl = the clusters that hold a family with a painted edge, sorted, each once
+  bool optima_list(int32_t n_regimes, const int32_t* regime, const double* value, int32_t per_site, std::vector<int32_t>& map,
+                   std::vector<int32_t>& cl, std::string& why) const;
   // pgbp_lg_set_tip_noise, host part: slot [max(1, n_families)]; sig = sigma_e with the two triangles averaged; cl = the clusters
   // that hold a noisy tip family, sorted, each once, and the largest dimension among them
   bool noise_list(int32_t n, const int32_t* family, const double* scale, const double* sigma_e, const double* se2,

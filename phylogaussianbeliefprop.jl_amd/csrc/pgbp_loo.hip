@@ -263,6 +263,7 @@ extern "C" int pgbp_lg_loo(pgbp_engine* e, int32_t site_begin, int32_t site_end,
   const LgModel* L = nullptr;
   int rc = lg_sweep_state(e, "pgbp_lg_loo", site_begin, site_end, &L, "pgbp_lg_loo_sites");
   if (rc) return rc;
+  if ((rc = lg_refuse_optima(e, "pgbp_lg_loo", L))) return rc;
   const LgStatic& F = L->F;
   const LgParams& M = L->M;
   const LgShifts& Sh = L->Sh;

@@ -69,7 +69,8 @@ inline size_t noise_lds_doubles(int p, int K, int max_dim) {
 size_t lg_noise_lds_bytes(int p, int K, int max_dim_ncl) { return sizeof(double) * noise_lds_doubles(p, K, max_dim_ncl); }
 
 // plain and BS16 packed records.  ncl: the clusters that hold a noisy tip family; acc_cap: doubles kept for the accumulator
-__global__ __launch_bounds__(64) void noise_kernel(LgStatic F, LgParams M, LgShifts S, LgNoise Nz, const int32_t* __restrict__ ncl,
+__global__ __launch_bounds__(64) void noise_kernel(LgStatic F, LgParams M, LgShifts S, LgOptima Op, LgNoise Nz,
+                                                   const int32_t* __restrict__ ncl,
                                                    double* __restrict__ pool, int64_t pool_stride, double* __restrict__ fpool,
                                                    int64_t fpool_stride, const int64_t* __restrict__ boff,
                                                    const int32_t* __restrict__ dim, int bs, int fp, int acc_cap) {
@@ -145,7 +146,7 @@ __global__ __launch_bounds__(64) void noise_kernel(LgStatic F, LgParams M, LgShi
         if (F.parent_pos[(int64_t)f * K + k] < 0) z += qc * mu[t];
       }
       z -= F.data[((int64_t)site * F.n_rows + F.data_row[f]) * p + t];
-      z += lg_shift_d(S, F.gamma, f, K, np, t, p, site);
+      z += lg_disp_d(S, Op, theta, alpha, F.length, F.gamma, f, K, np, t, p, site, 0);
       W1[i * ld + 2 * mo] = z;
       W2[i * ld + 2 * mo] = z;
     }
@@ -225,7 +226,7 @@ __global__ __launch_bounds__(64) void noise_kernel(LgStatic F, LgParams M, LgShi
 
 // The same for univariate batches in the site-minor layout (every belief dimension <= 2): thread = site, one row of
 // workgroups per noisy cluster, closed-form scalars; per-site se2 comes from the [slot][site] copy, a line per wavefront.
-__global__ __launch_bounds__(256) void noise_uni_sm_kernel(LgStatic F, LgParams M, LgShifts S, LgNoise Nz,
+__global__ __launch_bounds__(256) void noise_uni_sm_kernel(LgStatic F, LgParams M, LgShifts S, LgOptima Op, LgNoise Nz,
                                                            const int32_t* __restrict__ ncl, double* __restrict__ pool,
                                                            double* __restrict__ fpool, const int64_t* __restrict__ poff,
                                                            const int32_t* __restrict__ dim, int n_sites) {
@@ -259,6 +260,7 @@ __global__ __launch_bounds__(256) void noise_uni_sm_kernel(LgStatic F, LgParams 
         if (s >= 0) z += F.gamma[(int64_t)f * K + k] * (S.per_site ? S.value_sm[(int64_t)s * ns + site] : S.value[s]);
       }
     }
+    if (Op.regime) z += lg_optima_d(Op, &theta, alpha, F.length, F.gamma, f, K, np, 0, 1, site, ns);
     z -= F.data_sm[(int64_t)F.data_row[f] * ns + site];
     double E = Nz.scale[sn] * sig;
     if (Nz.se2) E += Nz.per_site ? Nz.se2_sm[(int64_t)sn * ns + site] : Nz.se2[sn];
@@ -300,26 +302,29 @@ __global__ __launch_bounds__(256) void noise_uni_sm_kernel(LgStatic F, LgParams 
   }
 }
 
-void launch_lg_noise(const LgStatic& F, const LgParams& M, const LgShifts& S, const LgNoise& Nz, const int32_t* d_ncl, int n_ncl,
+void launch_lg_noise(const LgStatic& F, const LgParams& M, const LgShifts& S, const LgOptima& Op, const LgNoise& Nz,
+                     const int32_t* d_ncl, int n_ncl,
                      double* pool, int64_t pool_stride, double* fpool, int64_t fpool_stride, const int64_t* d_boff,
                      const int32_t* d_dim, int bs16, int fast_p, int max_dim_ncl, int n_sites, hipStream_t st) {
   if (n_ncl <= 0 || !Nz.slot) return;
+  LgOptima O = Op;
+  O.value_sm = nullptr;   // (the [regime][site] rows are for lanes = sites)
   const int acc_cap = (int)noise_acc_cap(max_dim_ncl);
   const size_t bytes = lg_noise_lds_bytes(F.p, F.K, max_dim_ncl);   // (the engine has checked it against the compute unit's LDS)
   if (bytes > 64 * 1024) {
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(noise_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
     (void)hipGetLastError();
   }
-  hipLaunchKernelGGL(noise_kernel, dim3(n_ncl, n_sites), dim3(kWave), bytes, st, F, M, S, Nz, d_ncl, pool, pool_stride, fpool,
+  hipLaunchKernelGGL(noise_kernel, dim3(n_ncl, n_sites), dim3(kWave), bytes, st, F, M, S, O, Nz, d_ncl, pool, pool_stride, fpool,
                      fpool_stride, d_boff, d_dim, bs16, fast_p, acc_cap);
 }
 
-void launch_lg_noise_uni_sm(const LgStatic& F, const LgParams& M, const LgShifts& S, const LgNoise& Nz, const int32_t* d_ncl,
-                            int n_ncl, double* pool_sm, double* fpool_sm, const int64_t* d_poff, const int32_t* d_dim,
+void launch_lg_noise_uni_sm(const LgStatic& F, const LgParams& M, const LgShifts& S, const LgOptima& Op, const LgNoise& Nz,
+                            const int32_t* d_ncl, int n_ncl, double* pool_sm, double* fpool_sm, const int64_t* d_poff, const int32_t* d_dim,
                             int n_sites, hipStream_t st) {
   if (n_ncl <= 0 || !Nz.slot) return;
   const int bs = n_sites >= 256 ? 256 : 64;
-  hipLaunchKernelGGL(noise_uni_sm_kernel, dim3(n_ncl, (n_sites + bs - 1) / bs), dim3(bs), 0, st, F, M, S, Nz, d_ncl, pool_sm,
+  hipLaunchKernelGGL(noise_uni_sm_kernel, dim3(n_ncl, (n_sites + bs - 1) / bs), dim3(bs), 0, st, F, M, S, Op, Nz, d_ncl, pool_sm,
                      fpool_sm, d_poff, d_dim, n_sites);
 }
 

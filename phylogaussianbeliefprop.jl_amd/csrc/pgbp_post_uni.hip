@@ -285,6 +285,7 @@ extern "C" int pgbp_lg_impute_sites(pgbp_engine* e, int32_t site_begin, int32_t 
   int rc = sites_accept(e, fn, "pgbp_lg_impute", site_begin, site_end,
                           (!mean && !var) ? "no output buffer (mean and var are both NULL)" : nullptr, &c);
   if (rc) return rc;
+  if ((rc = lg_refuse_optima(e, fn, c.L))) return rc;
   const LgModel* L = c.L;
   std::vector<int32_t> fams, cls, dyn;
   std::vector<unsigned long long> pred;

@@ -218,6 +218,7 @@ extern "C" int pgbp_lg_shift_scan(pgbp_engine* e, int32_t site_begin, int32_t si
                        "pgbp_lg_shift_scan: p = " + std::to_string(L->T.p) + " traits, more than the 64 of a trait mask");
   int rc = lg_sweep_state(e, "pgbp_lg_shift_scan", site_begin, site_end, &L, "pgbp_lg_shift_scan_sites");
   if (rc) return rc;
+  if ((rc = lg_refuse_optima(e, "pgbp_lg_shift_scan", L))) return rc;
   const LgStatic& F = L->F;
   const LgParams& M = L->M;
   const LgShifts& Sh = L->Sh;

@@ -13,6 +13,9 @@
 // cluster's families in table order, eliminates [V_OO | z | delta] in LDS, accumulates Delta h and Delta g of the cluster in
 // LDS in family order and adds them to the record once: one writer per record, no atomics, every sum in a fixed order --
 // the same bytes on every call.  Nothing is launched when no shift is set; the cost is that of the shifted clusters.
+//
+// Painted optima under OU (pgbp_lg_set_optima) enter here too: an edge of regime r displaces w by wc_k (theta_r - theta), so
+// delta = (shifts' d + d_opt)_O (lg_disp_d of pgbp_shift_dev.hpp) and the clusters visited are those of either list.
 #include <hip/hip_runtime.h>
 
 #include "pgbp_bs16.hpp"
@@ -53,7 +56,10 @@ inline size_t shift_lds_doubles(int p, int K, int max_dim) {
 }
 
 // plain and BS16 packed records.  shcl: the clusters that hold a shifted family; acc_cap: doubles kept for the accumulator
-__global__ __launch_bounds__(64) void shift_kernel(LgStatic F, LgParams M, LgShifts S, const int32_t* __restrict__ shcl,
+// OPT: the instance that also reads painted optima; without it the kernel is the shifts' own, as it was
+template <bool OPT>
+__global__ __launch_bounds__(64) void shift_kernel(LgStatic F, LgParams M, LgShifts S, LgOptima Op,
+                                                   const int32_t* __restrict__ shcl,
                                                    double* __restrict__ pool, int64_t pool_stride, double* __restrict__ fpool,
                                                    int64_t fpool_stride, const int64_t* __restrict__ boff,
                                                    const int32_t* __restrict__ dim, int bs, int fp, int acc_cap) {
@@ -79,7 +85,7 @@ __global__ __launch_bounds__(64) void shift_kernel(LgStatic F, LgParams M, LgShi
   for (int fi = F.cl_off[c]; fi < F.cl_off[c + 1]; ++fi) {
     const int f = F.cl_fam[fi];
     const int np = F.n_parents[f];
-    if (!lg_shift_any(S, f, K, np)) continue;   // (the same in every lane)
+    if (!lg_shift_any(S, f, K, np) && !(OPT && lg_optima_any(Op, f, K, np))) continue;   // (the same in every lane)
     const int cpos = F.child_pos[f];
     const unsigned long long O = F.child_mask ? (F.child_mask[f] & full) : full;
     const int mo = __popcll(O);
@@ -124,7 +130,8 @@ __global__ __launch_bounds__(64) void shift_kernel(LgStatic F, LgParams M, LgShi
       }
       if (cpos < 0) z -= F.data[((int64_t)site * F.n_rows + F.data_row[f]) * p + t];
       W[i * ld + mo] = z;
-      W[i * ld + mo + 1] = lg_shift_d(S, F.gamma, f, K, np, t, p, site);
+      W[i * ld + mo + 1] = OPT ? lg_disp_d(S, Op, theta, alpha, F.length, F.gamma, f, K, np, t, p, site, 0)
+                               : lg_shift_d(S, F.gamma, f, K, np, t, p, site);
     }
     __syncthreads();
     const double di = (lane < mo) ? W[lane * ld + mo + 1] : 0.0;   // (mo <= 64: one lane per kept trait)
@@ -162,8 +169,9 @@ __global__ __launch_bounds__(64) void shift_kernel(LgStatic F, LgParams M, LgShi
 
 // The same for univariate batches in the site-minor layout (every belief dimension <= 2): thread = site, one row of
 // workgroups per shifted cluster; the per-site values come from the [slot][site] copy, a line per wavefront.
-__global__ __launch_bounds__(256) void shift_uni_sm_kernel(LgStatic F, LgParams M, LgShifts S, const int32_t* __restrict__ shcl,
-                                                           double* __restrict__ pool, double* __restrict__ fpool,
+template <bool OPT>
+__global__ __launch_bounds__(256) void shift_uni_sm_kernel(LgStatic F, LgParams M, LgShifts S, LgOptima Op,
+                                                           const int32_t* __restrict__ shcl, double* __restrict__ pool, double* __restrict__ fpool,
                                                            const int64_t* __restrict__ poff, const int32_t* __restrict__ dim,
                                                            int n_sites) {
   const int site = blockIdx.y * blockDim.x + threadIdx.x;
@@ -180,7 +188,7 @@ __global__ __launch_bounds__(256) void shift_uni_sm_kernel(LgStatic F, LgParams 
   for (int fi = F.cl_off[c]; fi < F.cl_off[c + 1]; ++fi) {
     const int f = F.cl_fam[fi];
     const int np = F.n_parents[f], cpos = F.child_pos[f];
-    if (!lg_shift_any(S, f, K, np)) continue;
+    if (!lg_shift_any(S, f, K, np) && !(OPT && lg_optima_any(Op, f, K, np))) continue;
     if (F.child_mask && !(F.child_mask[f] & 1ull)) continue;
     double V = 0.0, z = 0.0, d = 0.0;
     for (int k = 0; k < np; ++k) {
@@ -189,9 +197,10 @@ __global__ __launch_bounds__(256) void shift_uni_sm_kernel(LgStatic F, LgParams 
       V += vc * R[F.color[(int64_t)f * K + k]];
       z += wc * theta;
       if (F.parent_pos[(int64_t)f * K + k] < 0) z += qc * mu;
-      const int s = S.slot[(int64_t)f * K + k];
+      const int s = (!OPT || S.slot) ? S.slot[(int64_t)f * K + k] : -1;
       if (s >= 0) d += F.gamma[(int64_t)f * K + k] * (S.per_site ? S.value_sm[(int64_t)s * ns + site] : S.value[s]);
     }
+    if (OPT && Op.regime) d += lg_optima_d(Op, &theta, alpha, F.length, F.gamma, f, K, np, 0, 1, site, ns);
     if (cpos < 0) z -= F.data_sm[(int64_t)F.data_row[f] * ns + site];
     const double j = 1.0 / V;
     dg += -(d * j * z + 0.5 * (d * j * d));
@@ -217,28 +226,40 @@ __global__ __launch_bounds__(256) void shift_uni_sm_kernel(LgStatic F, LgParams 
   }
 }
 
-void launch_lg_shift(const LgStatic& F, const LgParams& M, const LgShifts& S, const int32_t* d_shcl, int n_shcl, double* pool,
+void launch_lg_shift(const LgStatic& F, const LgParams& M, const LgShifts& S, const LgOptima& Op, const int32_t* d_shcl,
+                     int n_shcl, double* pool,
                      int64_t pool_stride, double* fpool, int64_t fpool_stride, const int64_t* d_boff, const int32_t* d_dim,
                      int bs16, int fast_p, int max_dim, int n_sites, hipStream_t st) {
-  if (n_shcl <= 0 || !S.slot) return;
+  if (n_shcl <= 0 || (!S.slot && !Op.regime)) return;
+  LgOptima O = Op;
+  O.value_sm = nullptr;   // (the [regime][site] rows are for lanes = sites)
   const int acc_cap = (max_dim + 1 + 1) & ~1;
   const size_t doubles = shift_lds_doubles(F.p, F.K, max_dim);
+  const void* kern = O.regime ? reinterpret_cast<const void*>(shift_kernel<true>) : reinterpret_cast<const void*>(shift_kernel<false>);
   if (doubles * sizeof(double) > 64 * 1024) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(shift_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                              (int)(doubles * sizeof(double)));
+    (void)hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(doubles * sizeof(double)));
     (void)hipGetLastError();
   }
-  hipLaunchKernelGGL(shift_kernel, dim3(n_shcl, n_sites), dim3(kWave), doubles * sizeof(double), st, F, M, S, d_shcl, pool,
-                     pool_stride, fpool, fpool_stride, d_boff, d_dim, bs16, fast_p, acc_cap);
+  if (O.regime)
+    hipLaunchKernelGGL(shift_kernel<true>, dim3(n_shcl, n_sites), dim3(kWave), doubles * sizeof(double), st, F, M, S, O, d_shcl, pool,
+                       pool_stride, fpool, fpool_stride, d_boff, d_dim, bs16, fast_p, acc_cap);
+  else
+    hipLaunchKernelGGL(shift_kernel<false>, dim3(n_shcl, n_sites), dim3(kWave), doubles * sizeof(double), st, F, M, S, O, d_shcl, pool,
+                       pool_stride, fpool, fpool_stride, d_boff, d_dim, bs16, fast_p, acc_cap);
 }
 
-void launch_lg_shift_uni_sm(const LgStatic& F, const LgParams& M, const LgShifts& S, const int32_t* d_shcl, int n_shcl,
+void launch_lg_shift_uni_sm(const LgStatic& F, const LgParams& M, const LgShifts& S, const LgOptima& Op, const int32_t* d_shcl,
+                            int n_shcl,
                             double* pool_sm, double* fpool_sm, const int64_t* d_poff, const int32_t* d_dim, int n_sites,
                             hipStream_t st) {
-  if (n_shcl <= 0 || !S.slot) return;
+  if (n_shcl <= 0 || (!S.slot && !Op.regime)) return;
   const int bs = n_sites >= 256 ? 256 : 64;
-  hipLaunchKernelGGL(shift_uni_sm_kernel, dim3(n_shcl, (n_sites + bs - 1) / bs), dim3(bs), 0, st, F, M, S, d_shcl, pool_sm,
-                     fpool_sm, d_poff, d_dim, n_sites);
+  if (Op.regime)
+    hipLaunchKernelGGL(shift_uni_sm_kernel<true>, dim3(n_shcl, (n_sites + bs - 1) / bs), dim3(bs), 0, st, F, M, S, Op, d_shcl, pool_sm,
+                       fpool_sm, d_poff, d_dim, n_sites);
+  else
+    hipLaunchKernelGGL(shift_uni_sm_kernel<false>, dim3(n_shcl, (n_sites + bs - 1) / bs), dim3(bs), 0, st, F, M, S, Op, d_shcl, pool_sm,
+                       fpool_sm, d_poff, d_dim, n_sites);
 }
 
 }  // namespace pgbp

@@ -282,6 +282,7 @@ static int lg_simulate(pgbp_engine* e, int32_t site_begin, int32_t site_end, con
   if (!L) return engine_fail(e, PGBP_ERR_STATE, fn + "no family table (call pgbp_lg_setup first)");
   if (!L->d_pf) return engine_fail(e, PGBP_ERR_STATE, fn + "no topology (call pgbp_lg_set_topology first)");
   if (!L->have_params) return engine_fail(e, PGBP_ERR_STATE, fn + "no parameters yet (call pgbp_lg_assignfactors first)");
+  if (const int orc = lg_refuse_optima(e, "pgbp_lg_simulate", L)) return orc;
   const LgStatic& F = L->F;
   const LgParams& M = L->M;
   const LgShifts& Sh = L->Sh;

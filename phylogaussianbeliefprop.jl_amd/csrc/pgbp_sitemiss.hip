@@ -27,7 +27,7 @@ namespace pgbp {
 #define PGBP_SITEMISS_LOG2PI 1.8378770664093454835606594728112
 
 template <bool SM>
-__global__ __launch_bounds__(256) void sitemiss_fill_kernel(LgStatic F, LgParams M, LgShifts Sh, LgNoise Nz, LgSiteMiss Ms,
+__global__ __launch_bounds__(256) void sitemiss_fill_kernel(LgStatic F, LgParams M, LgShifts Sh, LgOptima Op, LgNoise Nz, LgSiteMiss Ms,
                                                             const int32_t* __restrict__ mcl, double* __restrict__ pool,
                                                             int64_t stride, double* __restrict__ fpool, int64_t fstride,
                                                             const int64_t* __restrict__ off, const int32_t* __restrict__ dim,
@@ -63,7 +63,8 @@ __global__ __launch_bounds__(256) void sitemiss_fill_kernel(LgStatic F, LgParams
         z = z + wc * theta;
         if (F.parent_pos[(int64_t)f * K + k] < 0) z = z + qc * mu;   // the fixed root
       }
-      z = z + lg_shift_d(Sh, F.gamma, f, K, np, 0, 1, site);          // a shift of the mean on a parent edge
+      // a shift of the mean on a parent edge, a painted optimum
+      z = z + lg_disp_d(Sh, Op, &theta, S.alpha, F.length, F.gamma, f, K, np, 0, 1, site, drow);
       if (cpos < 0) z = z - F.data_sm[(int64_t)F.data_row[f] * drow + site];   // a tip: its value
       const int sn = lg_noise_slot(Nz, f);
       if (sn >= 0) V = V + lg_noise_E(Nz, sn, 0, 0, 1, site);        // a noisy tip: V + E
@@ -125,7 +126,8 @@ __global__ __launch_bounds__(256) void sitemiss_zero_kernel(LgSiteMiss Ms, doubl
   if (data_sm) data_sm[(int64_t)row * drow + site] = 0.0;
 }
 
-void launch_lg_sitemiss(const LgStatic& F, const LgParams& M, const LgShifts& S, const LgNoise& Nz, const LgSiteMiss& Ms,
+void launch_lg_sitemiss(const LgStatic& F, const LgParams& M, const LgShifts& S, const LgOptima& Op, const LgNoise& Nz,
+                        const LgSiteMiss& Ms,
                         const int32_t* d_mcl, int n_mcl, int sm, double* pool, int64_t stride, double* fpool, int64_t fstride,
                         const int64_t* d_off, const int32_t* d_dim, int n_sites, hipStream_t st) {
   if (n_mcl <= 0 || !Ms.words) return;
@@ -133,10 +135,10 @@ void launch_lg_sitemiss(const LgStatic& F, const LgParams& M, const LgShifts& S,
   for (int c0 = 0; c0 < n_mcl; c0 += 65535) {   // (grid.y is 16 bits wide)
     const dim3 grid(gx, n_mcl - c0 < 65535 ? n_mcl - c0 : 65535);
     if (sm)
-      hipLaunchKernelGGL(sitemiss_fill_kernel<true>, grid, dim3(256), 0, st, F, M, S, Nz, Ms, d_mcl + c0, pool, stride, fpool,
+      hipLaunchKernelGGL(sitemiss_fill_kernel<true>, grid, dim3(256), 0, st, F, M, S, Op, Nz, Ms, d_mcl + c0, pool, stride, fpool,
                          fstride, d_off, d_dim, n_sites);
     else
-      hipLaunchKernelGGL(sitemiss_fill_kernel<false>, grid, dim3(256), 0, st, F, M, S, Nz, Ms, d_mcl + c0, pool, stride, fpool,
+      hipLaunchKernelGGL(sitemiss_fill_kernel<false>, grid, dim3(256), 0, st, F, M, S, Op, Nz, Ms, d_mcl + c0, pool, stride, fpool,
                          fstride, d_off, d_dim, n_sites);
   }
 }

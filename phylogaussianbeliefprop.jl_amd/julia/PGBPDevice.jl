@@ -538,6 +538,75 @@ Number of mean shifts in force (pgbp_lg_shift_count): 0 when none is set, -1 wit
 lg_shift_count(o::DeviceClusterGraphBelief) = Int(@ccall LIB.pgbp_lg_shift_count(o.handle::Ptr{Cvoid})::Int32)
 
 """
+    lg_set_optima!(obj, regime, values)
+
+Painted optima under OU (pgbp_lg_set_optima): `regime` holds one integer per entry `f * K + k` of the family table given to
+pgbp_lg_setup (`K x n_families` as a matrix; 0: the edge keeps `theta`, `r >= 1`: its optimum is column `r` of `values`),
+`values` is `p x n_regimes`, or `p x n_regimes x n_sites` for one set per site.  The offset of a family becomes
+`sum_k wc_k theta_{r(f,k)}`; under BM nothing changes.  An empty `values` clears the optima; the call replaces the previous
+setting and takes effect at the next fill; an invalid entry is an error and nothing changes.  `lg_gradient_optima` and
+`lg_gradient_sites_optima` return the derivative in every optimum; the other sweeps that form the offsets refuse under OU while
+optima are in force.
+"""
+function lg_set_optima!(o::DeviceClusterGraphBelief, regime::AbstractArray{<:Integer}, values::AbstractArray{Float64})
+    reg = Vector{Int32}(vec(regime))
+    val = Array{Float64}(values)
+    per_site = ndims(val) == 3 ? Int32(1) : Int32(0)
+    n = isempty(val) ? Int32(0) : Int32(size(val, 2))
+    check(o.handle, @ccall LIB.pgbp_lg_set_optima(o.handle::Ptr{Cvoid}, n::Int32, reg::Ptr{Int32}, val::Ptr{Float64},
+                                                  per_site::Int32)::Cint)
+    return nothing
+end
+
+"""
+    lg_update_optima!(obj, values)
+
+New values for the optima in force (pgbp_lg_update_optima), in the shape `lg_set_optima!` was given; the regime map stays.
+"""
+function lg_update_optima!(o::DeviceClusterGraphBelief, values::AbstractArray{Float64})
+    val = Array{Float64}(values)
+    check(o.handle, @ccall LIB.pgbp_lg_update_optima(o.handle::Ptr{Cvoid}, val::Ptr{Float64})::Cint)
+    return nothing
+end
+
+"""
+    lg_optima_count(obj) -> Int
+
+Number of regimes in force (pgbp_lg_optima_count): 0 when none is set, -1 without a family table.
+"""
+lg_optima_count(o::DeviceClusterGraphBelief) = Int(@ccall LIB.pgbp_lg_optima_count(o.handle::Ptr{Cvoid})::Int32)
+
+"""
+    lg_gradient_optima(obj, p, nrates, nregimes; noise = false) -> (dR, dmu, dalpha, dtheta, dsigma_e, doptima)
+
+`lg_gradient` of the current site with painted optima in force (pgbp_lg_gradient_optima): `doptima` is `p x nregimes`, `dtheta`
+the derivative in the optimum of the unpainted edges, `dsigma_e` `nothing` unless `noise`.
+"""
+function lg_gradient_optima(o::DeviceClusterGraphBelief, p::Integer, nrates::Integer, nregimes::Integer; noise::Bool = false)
+    dR = zeros(p * p * nrates); dmu = zeros(p); dalpha = Ref(0.0); dtheta = zeros(p); info = Ref(Int32(0))
+    dsig = noise ? zeros(p, p) : nothing
+    dopt = zeros(p, nregimes)
+    GC.@preserve dsig check(o.handle, @ccall LIB.pgbp_lg_gradient_optima(o.handle::Ptr{Cvoid}, Int32(0)::Int32, Int32(1)::Int32, dR::Ptr{Float64}, dmu::Ptr{Float64}, dalpha::Ref{Float64}, dtheta::Ptr{Float64}, (noise ? pointer(dsig) : Ptr{Float64}(C_NULL))::Ptr{Float64}, dopt::Ptr{Float64}, info::Ref{Int32})::Cint)
+    info[] == 0 || throw(PGBP.LA.PosDefException(info[]))
+    return (reshape(dR, p, p, nrates), dmu, dalpha[], dtheta, dsig, dopt)
+end
+
+"""
+    lg_gradient_sites_optima(obj, nsites, nrates, nregimes; noise = false) -> (dR, dmu, dalpha, dtheta, dsigma_e, doptima, info)
+
+`lg_gradient_sites` with painted optima in force (pgbp_lg_gradient_sites_optima): `doptima[r, s]` is the derivative of site s in
+the optimum of regime r.
+"""
+function lg_gradient_sites_optima(o::DeviceClusterGraphBelief, nsites::Integer, nrates::Integer, nregimes::Integer; noise::Bool = false)
+    dR = zeros(nrates, nsites); dmu = zeros(nsites); dalpha = zeros(nsites); dtheta = zeros(nsites)
+    dsig = noise ? zeros(nsites) : nothing
+    dopt = zeros(nregimes, nsites)
+    info = zeros(Int32, nsites)
+    GC.@preserve dsig check(o.handle, @ccall LIB.pgbp_lg_gradient_sites_optima(o.handle::Ptr{Cvoid}, Int32(0)::Int32, Int32(nsites)::Int32, dR::Ptr{Float64}, dmu::Ptr{Float64}, dalpha::Ptr{Float64}, dtheta::Ptr{Float64}, (noise ? pointer(dsig) : Ptr{Float64}(C_NULL))::Ptr{Float64}, dopt::Ptr{Float64}, info::Ptr{Int32})::Cint)
+    return (dR, dmu, dalpha, dtheta, dsig, dopt, info)
+end
+
+"""
     lg_set_tip_noise!(obj, families, sigma_e; scale = ones(length(families)), se2 = nothing)
 
 Measurement error at the tips (pgbp_lg_set_tip_noise): the conditional variance of every listed tip family (0-based indices

@@ -581,7 +581,7 @@ def lbfgs_sites(value_and_grad, x0, maxiter=200, gtol=1e-8, memory=8, c1=1e-4):
 
 
 def fit_sites_lg(beliefs, schedule_tree, model, R0, mu0, alpha0=None, theta0=None, extra_rates=(), fit_mu=True, maxiter=200,
-                 gtol=1e-8, memory=8):
+                 gtol=1e-8, memory=8, optima0=None):
     """Maximum-likelihood fit of EVERY SITE of a univariate batch at once, on a clique tree, on the thread-per-site kernels
     (p = 1, every belief of at most 2 variables, at least 8 sites).  model: "bm" or "ou".  Each site has its own free
     parameters: log R[0] (the BM rate; under OU the stationary variance), mu when fit_mu, and under OU log alpha and theta.
@@ -594,19 +594,39 @@ def fit_sites_lg(beliefs, schedule_tree, model, R0, mu0, alpha0=None, theta0=Non
     n_device_evals; the engine is left filled and calibrated at the estimates.
     A per-site mask of missing tips (set_site_missing_lg) needs no change here: every evaluation refills the factors, whose
     correction skips the masked tips of each site, and the gradient sweep reads the same mask -- each site is fitted to its
-    own observed tips (tests/test_gpu_site_missing.py: against the closed-form GLS optimum of every site)."""
+    own observed tips (tests/test_gpu_site_missing.py: against the closed-form GLS optimum of every site).
+    optima0 ([n_regimes] or [n_sites, n_regimes]; OU only): painted optima (Hansen's model).  The regime map is the one in
+    force (set_optima_lg first; its values are replaced); each site then also fits its own theta_r, one more free parameter
+    per regime with the derivative doptima of the sweep, and the result gains optima [n_sites, n_regimes].  theta stays the
+    optimum of the unpainted edges.  Every evaluation uploads n_sites x n_regimes numbers (update_optima_lg).  With the default the function
+    is what it was."""
     if model not in ("bm", "ou"):
         raise ValueError(f"fit_sites_lg: model must be 'bm' or 'ou', not {model!r}")
     ou = model == "ou"
     if ou and (alpha0 is None or theta0 is None):
         raise ValueError("fit_sites_lg: the OU model needs alpha0 and theta0")
     n = beliefs.n_sites
+    painted = optima0 is not None
+    if painted:
+        if not ou:
+            raise ValueError("fit_sites_lg: optima0 needs the OU model (under BM the optima have no effect)")
+        cur = beliefs.optima_lg()
+        if cur is None:
+            raise ValueError("fit_sites_lg: optima0 given but no regimes are painted (call set_optima_lg first)")
+        regime, n_reg = cur["regime"], cur["values"].shape[-2]
+        o0 = np.asarray(optima0, np.float64)
+        if o0.shape not in ((n_reg,), (n, n_reg)):
+            raise ValueError(f"fit_sites_lg: optima0 must be [{n_reg}] or [{n}, {n_reg}], not {list(o0.shape)}")
+        o0 = np.broadcast_to(o0, (n, n_reg)).copy()
     site = lambda v: np.broadcast_to(np.asarray(v, np.float64).reshape(-1), (n,)).copy()
     extra = [site(r) for r in extra_rates]
     mu_fixed = site(mu0)
     cols = [np.log(site(R0))] + ([mu_fixed.copy()] if fit_mu else []) + ([np.log(site(alpha0)), site(theta0)] if ou else [])
     i_mu = 1 if fit_mu else None
     i_al = (2 if fit_mu else 1) if ou else None
+    if painted:
+        i_op = len(cols)
+        cols = cols + [o0[:, r] for r in range(n_reg)]
     count = [0]
 
     def unpack(X):
@@ -619,17 +639,26 @@ def fit_sites_lg(beliefs, schedule_tree, model, R0, mu0, alpha0=None, theta0=Non
         R, mu, alpha, theta = unpack(X)
         rates = np.stack([R] + extra, axis=1)[:, :, None, None]
         kw = dict(model="ou", alpha=alpha, theta=theta[:, None]) if ou else {}
+        if painted:
+            beliefs.update_optima_lg(X[:, i_op:])   # (the values alone: n_sites x n_regimes numbers)
         beliefs.assignfactors_lg_(rates, mu[:, None], **kw)
         count[0] += 1
         ll, d = beliefs.loglik_and_gradient_sites_lg(schedule_tree)
         g = [d["dR"][:, 0, 0, 0] * R] + ([d["dmu"][:, 0]] if fit_mu else []) + ([d["dalpha"] * alpha, d["dtheta"][:, 0]] if ou else [])
+        if painted:
+            g = g + [d["doptima"][:, r, 0] for r in range(n_reg)]
         f = np.where(d["info"] != 0, np.nan, -ll)
         return f, -np.stack(g, axis=1)
 
+    if painted:   # per-site values from here on; every evaluation then moves the values alone
+        beliefs.set_optima_lg(regime, o0[:, :, None])
     beliefs._ensure_schedule([schedule_tree])
     opt = lbfgs_sites(value_and_grad, np.stack(cols, axis=1), maxiter=maxiter, gtol=gtol, memory=memory)
     f_end, _ = value_and_grad(opt["x"])   # the engine filled and calibrated at the estimates (the last trial points are not)
     R, mu, alpha, theta = unpack(opt["x"])
     nan = np.full(n, np.nan)
-    return dict(R=R, mu=np.array(mu, copy=True), alpha=alpha if ou else nan, theta=np.array(theta, copy=True) if ou else nan.copy(),
-                loglik=-opt["f"], converged=opt["converged"], n_iter=opt["n_iter"], n_device_evals=count[0])
+    out = dict(R=R, mu=np.array(mu, copy=True), alpha=alpha if ou else nan, theta=np.array(theta, copy=True) if ou else nan.copy(),
+               loglik=-opt["f"], converged=opt["converged"], n_iter=opt["n_iter"], n_device_evals=count[0])
+    if painted:
+        out["optima"] = np.array(opt["x"][:, i_op:], copy=True)
+    return out
