@@ -286,6 +286,19 @@ def main():
     print(f"BM in closed form on the gappy batch: site 0 observes {int(round(reml['den'][0])) + 1} of {len(leaves)} tips: REML rate "
           f"{reml['R'][0]:.4f}, root mean {reml['mu'][0]:.4f}, log-likelihood {reml['loglik'][0]:.4f}; "
           f"{int((reml['info'] != 0).sum())} sites failed")
+    # how the sites evolve TOGETHER: the evolutionary rate matrix between them (evol.vcv), their evolutionary correlations and
+    # the phylogenetic principal components (phyl.pca), from one calibration of the univariate engine and one call that forms
+    # Y'PY on the matrix cores.  A cross-site estimate needs the same observed tips at every site: the complete table here.
+    sc = pair[0][0]
+    whole = P.ClusterGraphBelief.from_arrays(sc.dims, sc.sepset_clusters, sc.scope_off, sc.scope_idx, None, n_sites=ns)
+    whole.lg_setup(P.lg_families(sc.clusters, sc.node2cluster, net.node2family, sc.node2fixed, pe, data_row, 1),
+                   np.ascontiguousarray(X[:, leaves, None]))
+    root = (ci, int(sc.dims[ci]) - 1)
+    rate = P.calibrate_rate_matrix_sites_(whole, tree_sched, root)
+    pca = P.phylo_pca_sites(whole, tree_sched, root, mode="corr", n_components=2)
+    print(f"sites 0 and 1 of the complete batch: evolutionary covariance {rate['R'][0, 1]:.4f}, correlation {rate['corr'][0, 1]:.4f}; "
+          f"the first two phylogenetic PCs of the {ns} sites carry {pca['values'][0] / ns:.1%} and {pca['values'][1] / ns:.1%} of the "
+          f"standardised variance; tip 0 scores {pca['scores'][0, 0]:.3f}, {pca['scores'][0, 1]:.3f} on them")
 
 
 if __name__ == "__main__":

@@ -785,6 +785,36 @@ int  pgbp_sample_posterior_sites_timed(pgbp_engine* e, int32_t tree, int32_t sit
  * range. */
 int  pgbp_bm_exact_stats_sites(pgbp_engine* e, int32_t site_begin, int32_t site_end, int32_t root_belief, int32_t root_pos,
                                double* num, double* den, double* mu, int32_t* info);
+/* EVOLUTIONARY RATE MATRIX BETWEEN THE SITES OF A UNIVARIATE BATCH (csrc/pgbp_rate_uni.hip): the cross-site form of the call
+ * above -- evol.vcv / ratematrix, the evolutionary correlations, phyl.pca -- for the sites [row_begin, row_end) against the
+ * sites [col_begin, col_end) of a thread-per-site engine whose beliefs are CALIBRATED UNDER THE FACTORS OF R = 1, mu = 0 WITH AN
+ * IMPROPER ROOT.  With e_fs = E[r_f | data of site s] and t_f as above, and the same observed tips at every site,
+ *   gram[a][b] = (Y'PY)_ab = sum_f e_fa e_fb / t_f        (P: the projected precision of the tips)
+ * whose diagonal is num of the call above; R_hat_ab = gram[a][b] / sqrt(den_a den_b) (den_a = den_b = tips - 1).
+ *   gram [row_end - row_begin][col_end - col_begin]  required, row-major;
+ *   den, mu, info [rows] then [cols]                 each may be NULL; the values of pgbp_bm_exact_stats_sites (den to the byte).
+ * A site whose info is not 0 has NaN in its whole row or column of gram and in its den and mu; every other entry keeps its bytes.
+ * Device, per chunk of families: rate_uni_resid, the frame of the sweep above, stores U[family][site] = e / sqrt(t_f) (+0.0 for
+ * a skipped family and for the rows that pad the last family to a multiple of 4) and the block's den partial and mark, folded
+ * in block order across the chunks; rate_uni_syrk adds U'U to the device-resident gram block on the matrix cores
+ * (v_mfma_f64_16x16x4_f64): a workgroup of four wavefronts per 128 x 128 tile, accumulators in registers, the family axis walked
+ * in index order 4 families per step through LDS slabs of 16 families.  No atomics, no split over the family axis, contraction
+ * off: an entry sees the same sequence of steps whatever the ranges of the query, its tile and the chunks, so two calls, a query
+ * cut into blocks, and the transposed query return the same bytes, and gram of a square query is symmetric to the byte (its
+ * tiles wholly below the diagonal are copied from their mirror images, which have the bytes the update would have formed).
+ * Scratch: the U rows of a chunk -- whole blocks of 64 families (one at least) over all row and column sites -- are bounded by
+ * pgbp_sites_sweep_scratch_limit; the gram block, rows x cols doubles, is allocated outside that limit (PGBP_ERR_HIP with the
+ * call's name when it does not fit: tile a large matrix through the ranges).  The pool is read in the layout it is in.
+ * Refused before any launch -- outputs, layout and pool untouched --: as pgbp_bm_exact_stats_sites in its order (either range
+ * outside the sites; gram NULL; not a thread-per-site engine: the text names pgbp_bm_exact_stats), then a per-site mask in
+ * force (pgbp_lg_set_site_missing: a cross-site estimate needs the same observed tips at both sites; a shared child_mask is
+ * fine), an Ornstein-Uhlenbeck fill, tip noise, a fixed-root parent, a leaf with two parents, and with mu the root out of range.
+ * _timed: ms3 = {residual rows, rank-k update, copies} in milliseconds, the stream drained after every phase. */
+int  pgbp_bm_rate_matrix_sites(pgbp_engine* e, int32_t row_begin, int32_t row_end, int32_t col_begin, int32_t col_end,
+                               int32_t root_belief, int32_t root_pos, double* gram, double* den, double* mu, int32_t* info);
+int  pgbp_bm_rate_matrix_sites_timed(pgbp_engine* e, int32_t row_begin, int32_t row_end, int32_t col_begin, int32_t col_end,
+                                     int32_t root_belief, int32_t root_pos, double* gram, double* den, double* mu, int32_t* info,
+                                     double* ms3);
 /* POSTERIOR COVARIANCE OF A UNIVARIATE BATCH WITH LANES = SITES (csrc/pgbp_cov_uni.hip): pgbp_posterior_cov (below) in the
  * frame of the three calls above, for the out-of-clique queries of a fitted batch -- the covariance of two ancestors that share
  * no cluster, the variance of a clade mean or of a contrast -- at every site at once.  The semantics are pgbp_posterior_cov's:

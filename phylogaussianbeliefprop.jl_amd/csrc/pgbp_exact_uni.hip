@@ -116,36 +116,11 @@ extern "C" int pgbp_bm_exact_stats_sites(pgbp_engine* e, int32_t site_begin, int
   if (rc) return rc;
   const LgModel* L = c.L;
   const Plan& pl = *c.v.plan;
-  if (L->M.model == PGBP_LG_OU)
-    return engine_fail(e, PGBP_ERR_INVALID, std::string(fn) + ": the last pgbp_lg_assignfactors was an Ornstein-Uhlenbeck fill; the "
-                                                "closed form is that of a Brownian motion with R = 1 (use fit_sites_lg)");
-  if (L->Nz.slot)
-    return engine_fail(e, PGBP_ERR_INVALID, std::string(fn) + ": tip noise is in force (pgbp_lg_set_tip_noise): the variance is then "
-                                                "not proportional to the rate and the fit has no closed form (use fit_sites_lg)");
-  // the checks of the general call that can fail at p = 1 (src/calibration.jl:416-421 and the sweep's own)
+  // the model and the family table (shared with pgbp_bm_rate_matrix_sites), then the root
+  if ((rc = sites_bm_closed_form_checks(e, fn, L))) return rc;
+  if (mu && (rc = sites_root_check(e, fn, pl, root_belief, root_pos))) return rc;
   const LgTable& T = L->T;
-  const int nf = T.n_families, K = L->F.K;
-  for (int f = 0; f < nf; ++f) {
-    const std::string where = std::string(fn) + ": family " + std::to_string(f) + " (cluster " + std::to_string(T.cluster[f]) + "): ";
-    const unsigned long long cm = T.child_mask.empty() ? 1ull : T.child_mask[f];
-    bool pm0 = true;
-    for (int k = 0; k < T.n_parents[f]; ++k) {
-      const unsigned long long pm = T.parent_mask.empty() ? 1ull : T.parent_mask[(size_t)f * K + k];
-      if (k == 0) pm0 = pm != 0;
-      if (T.parent_pos[(size_t)f * K + k] < 0 && pm != 0)   // (-1 with an empty mask: a parent with nothing in scope)
-        return engine_fail(e, PGBP_ERR_INVALID, where + "its parent is the fixed root: the sweep is defined on the engine with "
-                                                        "an improper root prior (fixedroot = false)");
-    }
-    if (T.n_parents[f] > 1 && T.child_pos[f] < 0 && cm != 0 && pm0)
-      return engine_fail(e, PGBP_ERR_INVALID, where + "a leaf with more than one parent");
-  }
-  if (mu) {
-    if (root_belief < 0 || root_belief >= pl.n_beliefs())
-      return engine_fail(e, PGBP_ERR_INVALID, std::string(fn) + ": root belief " + std::to_string(root_belief) + " out of range");
-    if (root_pos < 0 || root_pos >= pl.dims[root_belief])
-      return engine_fail(e, PGBP_ERR_INVALID, std::string(fn) + ": root position " + std::to_string(root_pos) + " out of range: belief " +
-                                                  std::to_string(root_belief) + " has " + std::to_string(pl.dims[root_belief]) + " variables");
-  }
+  const int nf = T.n_families;
   const int ns = c.ns;
   if (ns == 0) return PGBP_OK;
   const int nfb = std::max(1, (nf + kFamUniBlock - 1) / kFamUniBlock);

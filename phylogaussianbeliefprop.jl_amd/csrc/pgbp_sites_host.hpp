@@ -66,6 +66,45 @@ inline int sites_accept(pgbp_engine* e, const char* fn, const char* general, int
   return sites_accept_engine(e, fn, general, *c);
 }
 
+// What the closed forms of a Brownian motion with R = 1 (pgbp_bm_exact_stats_sites, pgbp_bm_rate_matrix_sites) check of the
+// model and of the family table once the call is accepted: no Ornstein-Uhlenbeck fill, no tip noise, and the checks of the
+// general call that can fail at p = 1 (src/calibration.jl:416-421 and the sweep's own).  PGBP_OK, or engine_fail's code.
+inline int sites_bm_closed_form_checks(pgbp_engine* e, const char* fn, const LgModel* L) {
+  if (L->M.model == PGBP_LG_OU)
+    return engine_fail(e, PGBP_ERR_INVALID, std::string(fn) + ": the last pgbp_lg_assignfactors was an Ornstein-Uhlenbeck fill; the "
+                                                "closed form is that of a Brownian motion with R = 1 (use fit_sites_lg)");
+  if (L->Nz.slot)
+    return engine_fail(e, PGBP_ERR_INVALID, std::string(fn) + ": tip noise is in force (pgbp_lg_set_tip_noise): the variance is then "
+                                                "not proportional to the rate and the fit has no closed form (use fit_sites_lg)");
+  const LgTable& T = L->T;
+  const int nf = T.n_families, K = L->F.K;
+  for (int f = 0; f < nf; ++f) {
+    const std::string where = std::string(fn) + ": family " + std::to_string(f) + " (cluster " + std::to_string(T.cluster[f]) + "): ";
+    const unsigned long long cm = T.child_mask.empty() ? 1ull : T.child_mask[f];
+    bool pm0 = true;
+    for (int k = 0; k < T.n_parents[f]; ++k) {
+      const unsigned long long pm = T.parent_mask.empty() ? 1ull : T.parent_mask[(size_t)f * K + k];
+      if (k == 0) pm0 = pm != 0;
+      if (T.parent_pos[(size_t)f * K + k] < 0 && pm != 0)   // (-1 with an empty mask: a parent with nothing in scope)
+        return engine_fail(e, PGBP_ERR_INVALID, where + "its parent is the fixed root: the sweep is defined on the engine with "
+                                                        "an improper root prior (fixedroot = false)");
+    }
+    if (T.n_parents[f] > 1 && T.child_pos[f] < 0 && cm != 0 && pm0)
+      return engine_fail(e, PGBP_ERR_INVALID, where + "a leaf with more than one parent");
+  }
+  return PGBP_OK;
+}
+
+// the root (belief, position) a call forms mu from, when it is asked for
+inline int sites_root_check(pgbp_engine* e, const char* fn, const Plan& pl, int32_t root_belief, int32_t root_pos) {
+  if (root_belief < 0 || root_belief >= pl.n_beliefs())
+    return engine_fail(e, PGBP_ERR_INVALID, std::string(fn) + ": root belief " + std::to_string(root_belief) + " out of range");
+  if (root_pos < 0 || root_pos >= pl.dims[root_belief])
+    return engine_fail(e, PGBP_ERR_INVALID, std::string(fn) + ": root position " + std::to_string(root_pos) + " out of range: belief " +
+                                                std::to_string(root_belief) + " has " + std::to_string(pl.dims[root_belief]) + " variables");
+  return PGBP_OK;
+}
+
 // sites per chunk when a site takes per_site doubles of scratch: whole workgroups, one workgroup's sites at least
 inline int fam_uni_chunk(int ns, int64_t per_site) {
   const int64_t fit = (g_fam_uni_limit.load() / std::max<int64_t>(1, per_site)) / 256 * 256;

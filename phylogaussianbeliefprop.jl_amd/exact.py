@@ -76,6 +76,122 @@ def calibrate_exact_sites_(beliefs, schedule_tree, root, beliefs_fixedroot=None)
     return dict(R=R, mu=mu, loglik=ll, den=den, info=info)
 
 
+def _site_range(r, n):
+    """(begin, end) of a site range given as None (all), (begin, end), a range or a slice with step 1"""
+    if r is None:
+        return 0, n
+    if isinstance(r, slice):
+        a, b, st = r.indices(n)
+        if st != 1:
+            raise ValueError("a site range is contiguous")
+        return a, max(a, b)
+    if isinstance(r, range):
+        if r.step != 1:
+            raise ValueError("a site range is contiguous")
+        return r.start, max(r.start, r.stop)
+    a, b = r
+    return int(a), int(b)
+
+
+def bm_rate_matrix_sites(beliefs, rows=None, cols=None, root=None):
+    """pgbp_bm_rate_matrix_sites on the current beliefs (calibrated under R = 1, mu = 0, improper root): the cross-site form
+    of bm_exact_stats_sites for a univariate batch on the thread-per-site kernels.  rows, cols: contiguous site ranges
+    ((begin, end), a range, a slice; None: all sites) -- a matrix too large for one device block is tiled through them.
+    Returns (gram [rows, cols] = (Y'PY)_ab = sum_f e_fa e_fb / t_f on the matrix cores, den, mu or None, info), the last three
+    as pairs (of the row sites, of the column sites).  gram of a square query is symmetric to the byte, and a block of it has
+    the bytes of the same entries of the whole; a site whose info is not 0 is NaN in its row or column, its den and its mu.
+    Refused (PGBP_ERR_INVALID) with a per-site mask of missing tips in force, after an OU fill and with tip noise."""
+    n = beliefs.n_sites
+    r0, r1 = _site_range(rows, n)
+    c0, c1 = _site_range(cols, n)
+    nr, nc = max(0, r1 - r0), max(0, c1 - c0)
+    gram = np.zeros((nr, nc))
+    den = np.zeros(nr + nc)
+    mu = np.zeros(nr + nc) if root is not None else None
+    info = np.zeros(nr + nc, dtype=np.int32)
+    rb, rp = (int(root[0]), int(root[1])) if root is not None else (0, 0)
+    _check(beliefs._lib.pgbp_bm_rate_matrix_sites(beliefs._eng, r0, r1, c0, c1, rb, rp, L.f64p(gram), L.f64p(den),
+                                                  L.f64p(mu) if root is not None else None, L.i32p(info)), beliefs._eng)
+    split = lambda x: None if x is None else (x[:nr], x[nr:])
+    return gram, split(den), split(mu), split(info)
+
+
+def calibrate_rate_matrix_sites_(beliefs, schedule_tree, root, rows=None, cols=None):
+    """The evolutionary rate matrix between the sites of a univariate batch (evol.vcv / ratematrix): the REML estimate
+    R_hat = Y'PY / (n_tips - 1) under a multivariate Brownian motion whose traits are the sites, from one calibration of the
+    univariate engine and one call, on the thread-per-site kernels and in their layout.
+
+    beliefs: as for calibrate_exact_sites_ (fixedroot=False, ONE rate, family table set up); every site observes the same tips
+    (a shared child_mask is fine, a per-site mask is refused); shifts in force are honoured.  Steps: factors of R = 1, mu = 0 ->
+    one calibration enqueued without refreshing the host mirrors -> bm_rate_matrix_sites(rows, cols, root).  Returns
+    dict(R [rows, cols] = gram / sqrt(den_a den_b), corr = R_ab / sqrt(var_a var_b) (the evolutionary correlations), gram, and
+    the pairs (of the row sites, of the column sites) var (the sites' own rates R_aa), mu, den, info).  A site whose info is not
+    0 (the call's code, or -1 where the calibration failed at that site) is NaN in its row or column and in mu; R is NaN where
+    den < 0.5 (fewer than two observed tips)."""
+    n = beliefs.n_sites
+    r0, r1 = _site_range(rows, n)
+    c0, c1 = _site_range(cols, n)
+    beliefs.assignfactors_lg_(np.ones((1, 1, 1)), np.zeros(1))
+    _, (gram, den, mu, info), cal = beliefs._loglik_and_sites(
+        schedule_tree, lambda: bm_rate_matrix_sites(beliefs, (r0, r1), (c0, c1), root))
+    gram = gram.copy()
+    cals = (cal[r0:r1], cal[c0:c1])
+    info = tuple(np.where((c != 0) & (i == 0), -1, i).astype(np.int32) for c, i in zip(cals, info))
+    gram[info[0] != 0, :] = np.nan
+    gram[:, info[1] != 0] = np.nan
+    den = tuple(np.where((d >= 0.5) & (i == 0), d, np.nan) for d, i in zip(den, info))
+    mu = tuple(np.where(i == 0, m, np.nan) for m, i in zip(mu, info))
+    # the sites' own rates gram_aa / den_a: the diagonal of a square query, else num of the per-site call on the same beliefs
+    if (r0, r1) == (c0, c1):
+        num_r = num_c = np.diagonal(gram).copy()
+    else:
+        num = bm_exact_stats_sites(beliefs, None)[0]
+        num_r, num_c = num[r0:r1], num[c0:c1]
+    with np.errstate(divide="ignore", invalid="ignore"):
+        R = gram / np.sqrt(den[0][:, None] * den[1][None, :])
+        var = (num_r / den[0], num_c / den[1])
+        corr = R / np.sqrt(var[0][:, None] * var[1][None, :])
+    return dict(R=R, corr=corr, var=var, mu=mu, den=den, info=info, gram=gram)
+
+
+def _observed_tips(beliefs):
+    """the data rows of the tips the family table observes (child_mask bit 0, a tip with a data row and a parent)"""
+    k = beliefs._lg
+    cm = k.get("child_mask")
+    tip = (k["child_pos"] < 0) & (k["data_row"] >= 0) & (k["n_parents"] > 0)
+    if cm is not None:
+        tip &= (np.asarray(cm) & np.uint64(1)).astype(bool)
+    return np.asarray(k["data_row"])[tip]
+
+
+def phylo_pca_sites(beliefs, schedule_tree, root, mode="cov", n_components=None):
+    """Phylogenetic principal components of a univariate batch (phyl.pca), the sites as the traits: the eigendecomposition of
+    the evolutionary rate matrix (mode="cov") or of the evolutionary correlations (mode="corr") from
+    calibrate_rate_matrix_sites_ over all sites.
+
+    The rate matrix is formed on the device; the eigendecomposition is HOST work, numpy.linalg.eigh of the dense
+    [n_sites, n_sites] matrix: O(n_sites^3) flops and 8 n_sites^2 bytes, seconds up to a few thousand sites and the wrong tool
+    beyond some ten thousand (form R in blocks with calibrate_rate_matrix_sites_ and use an iterative solver there).
+    Returns dict(values [k] in decreasing order, loadings [n_sites, k] (unit columns, sign free), scores [n_observed_tips, k]
+    = (Y - 1 mu') V over the tips the table observes in data-row order (with mode="corr" the columns of Y - 1 mu' are divided
+    by the evolutionary standard deviations), rows: those data rows, mu, R: the matrix decomposed).  The data are those given
+    to lg_setup; displacements of shifts in force are not taken off the scores.  A site with info != 0 raises LinAlgError."""
+    if mode not in ("cov", "corr"):
+        raise ValueError("mode is 'cov' or 'corr'")
+    fit = calibrate_rate_matrix_sites_(beliefs, schedule_tree, root)
+    if fit["info"][0].any():
+        raise np.linalg.LinAlgError(f"phylo_pca_sites: site {int(np.flatnonzero(fit['info'][0])[0])} has no rate estimate")
+    A = fit["R"] if mode == "cov" else fit["corr"]
+    w, V = np.linalg.eigh(A)
+    order = np.argsort(w)[::-1][: (len(w) if n_components is None else int(n_components))]
+    w, V = w[order], V[:, order]
+    rows = _observed_tips(beliefs)
+    Y = np.asarray(beliefs._lg["data"])[:, rows, 0].T - fit["mu"][0][None, :]
+    if mode == "corr":
+        Y = Y / np.sqrt(fit["var"][0])[None, :]
+    return dict(values=w, loadings=V, scores=Y @ V, rows=rows, mu=fit["mu"][0], R=A)
+
+
 def calibrate_exact_cliquetree_(beliefs, schedule_tree, root, beliefs_fixedroot=None, all_sites=False):
     """calibrate_exact_cliquetree!(beliefs, spt, prenodes, tbl, taxa, evomodelfun) (src/calibration.jl:404-517) for a
     (univariate or full) Brownian motion.

@@ -338,6 +338,24 @@ function bm_exact_stats_sites(o::DeviceClusterGraphBelief, nsites::Integer, root
 end
 
 """
+    bm_rate_matrix_sites(obj, rows, cols, rootcluster, rootpos) -> (gram, den, mu, info)
+
+The evolutionary rate matrix between the sites of a univariate batch on the thread-per-site kernels
+(pgbp_bm_rate_matrix_sites): `gram[a, b] = (Y'PY)_ab` for the sites `rows` against the sites `cols` (1-based unit ranges),
+formed on the matrix cores; `den`, `mu`, `info`: the values of `bm_exact_stats_sites` for the row sites, then for the column
+sites.  `gram ./ sqrt.(den_rows * den_cols')` is the REML rate matrix.  The beliefs must be calibrated under a BM with R = 1
+and an improper root, and every site must observe the same tips (a per-site mask is refused).  A failed site holds NaN in its
+row or column.  Untested: there is no Julia on the test machines.
+"""
+function bm_rate_matrix_sites(o::DeviceClusterGraphBelief, rows::UnitRange{<:Integer}, cols::UnitRange{<:Integer}, rootcluster::Integer, rootpos::Integer)
+    nr = length(rows); nc = length(cols)
+    g = zeros(nc, nr)   # (the call writes row-major [rows][cols]: column-major [cols, rows])
+    den = zeros(nr + nc); mu = zeros(nr + nc); info = zeros(Int32, nr + nc)
+    check(o.handle, @ccall LIB.pgbp_bm_rate_matrix_sites(o.handle::Ptr{Cvoid}, Int32(first(rows) - 1)::Int32, Int32(last(rows))::Int32, Int32(first(cols) - 1)::Int32, Int32(last(cols))::Int32, Int32(rootcluster - 1)::Int32, Int32(rootpos - 1)::Int32, g::Ptr{Float64}, den::Ptr{Float64}, mu::Ptr{Float64}, info::Ptr{Int32})::Cint)
+    return (permutedims(g), den, mu, info)
+end
+
+"""
     moments_sites(obj, nsites, dims; cov = true) -> (mean, tri, norm, info)
 
 `moments!` of EVERY CLUSTER for every site of a univariate batch on the thread-per-site kernels (pgbp_moments_sites; the
