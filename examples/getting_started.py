@@ -299,6 +299,12 @@ def main():
     print(f"sites 0 and 1 of the complete batch: evolutionary covariance {rate['R'][0, 1]:.4f}, correlation {rate['corr'][0, 1]:.4f}; "
           f"the first two phylogenetic PCs of the {ns} sites carry {pca['values'][0] / ns:.1%} and {pca['values'][1] / ns:.1%} of the "
           f"standardised variance; tip 0 scores {pca['scores'][0, 0]:.3f}, {pca['scores'][0, 1]:.3f} on them")
+    # the same components WITHOUT the sites x sites matrix, for batches where it does not fit: subspace iteration on the
+    # operator v -> R v, one device pass over the residual rows per iteration (pgbp_bm_rate_apply_sites)
+    lead = P.phylo_pca_leading_sites(whole, tree_sched, root, 3, mode="corr")
+    print(f"the first three phylogenetic PCs by subspace iteration: {', '.join(f'{x:.1%}' for x in lead['explained'])} of the "
+          f"standardised variance after {lead['iterations']} iterations (converged: {lead['converged']}); the first two values "
+          f"differ from the dense route by {np.max(np.abs(lead['values'][:2] - pca['values'])) / pca['values'][0]:.1e}")
 
 
 if __name__ == "__main__":

@@ -815,6 +815,37 @@ int  pgbp_bm_rate_matrix_sites(pgbp_engine* e, int32_t row_begin, int32_t row_en
 int  pgbp_bm_rate_matrix_sites_timed(pgbp_engine* e, int32_t row_begin, int32_t row_end, int32_t col_begin, int32_t col_end,
                                      int32_t root_belief, int32_t root_pos, double* gram, double* den, double* mu, int32_t* info,
                                      double* ms3);
+/* THE RATE MATRIX OF A UNIVARIATE BATCH APPLIED TO A BLOCK OF VECTORS (csrc/pgbp_rate_apply_uni.hip): the operator of an
+ * iterative consumer -- the leading phylogenetic principal components, a solve, a trace estimate -- where sites x sites doubles
+ * are too many.  On the beliefs pgbp_bm_rate_matrix_sites expects (CALIBRATED UNDER R = 1, mu = 0 WITH AN IMPROPER ROOT), with
+ * U[f][s] = e_fs / sqrt(t_f) its residual rows over the sites [site_begin, site_end) and n = site_end - site_begin,
+ *   gv[j][a] = sum_f U[f][a] * (sum_b U[f][b] v[j][b])      = (gram of pgbp_bm_rate_matrix_sites(rows = cols = the range)) v_j
+ * without the gram block being formed; R_hat v = gv / den.
+ *   v    [n_vec][n]  required, vector-major (site-minor); 1 <= n_vec <= 64 (block a wider set over several calls);
+ *   gv   [n_vec][n]  required;
+ *   den, mu, info [n]   each may be NULL (mu NULL: the root is not read); the bytes pgbp_bm_rate_matrix_sites returns.
+ * A SITE WHOSE info IS NOT 0 has no residual column, and U v mixes all the sites of the range: the call still returns PGBP_OK,
+ * den and mu are NaN at that site only, and gv is NaN IN EVERY ENTRY (filled by the host after the last chunk) -- check info
+ * once before iterating.  A sub-range is another operator (a principal block of the matrix), not a part of the same result.
+ * Device, per chunk of whole 64-family blocks: rate_uni_resid / rate_uni_reduce of the rate matrix (one source, shared);
+ * rate_apply_uv: W[f][j] = sum_b U[f][b] v[j][b], the site axis in index order 4 sites per v_mfma_f64_16x16x4_f64, a wavefront
+ * per 16 families and all vectors; rate_apply_utw: Z[a][j] += sum_f U[f][a] W[f][j], the family axis in index order 4 families
+ * per MFMA on top of what the chunks before left (the rule of rate_uni_syrk), a wavefront per 16 sites and all vectors.  Vectors
+ * are padded to 16 with +0.0 vectors, sites to 16, the last family block with +0.0 rows.  One owner per tile, no split of a
+ * contracted axis, no atomics, contraction off: two calls, every chunking (pgbp_sites_sweep_scratch_limit bounds U, W, Z and the
+ * transposed v; a chunk is one block at least), the site-minor and the plain layout, and a vector sent alone or among 63 others
+ * give the same bytes.  The pool is read in the layout it is in.  One stream synchronisation per call.
+ * Refused before any launch -- outputs, layout and pool untouched --: as pgbp_bm_rate_matrix_sites in its order, with n_vec
+ * outside 1 .. 64 and v or gv NULL (PGBP_ERR_INVALID) after the site range.
+ * _timed: ms4 = {residual rows, U v, U' W, copies} in milliseconds, the stream drained after every phase. */
+int  pgbp_bm_rate_apply_sites(pgbp_engine* e, int32_t site_begin, int32_t site_end, int32_t n_vec,
+                              const double* v,      /* [n_vec][sites of the range], site-minor */
+                              int32_t root_belief, int32_t root_pos,
+                              double* gv,           /* [n_vec][sites of the range] */
+                              double* den, double* mu, int32_t* info);   /* [sites], each may be NULL (mu: see root) */
+int  pgbp_bm_rate_apply_sites_timed(pgbp_engine* e, int32_t site_begin, int32_t site_end, int32_t n_vec, const double* v,
+                                    int32_t root_belief, int32_t root_pos, double* gv, double* den, double* mu, int32_t* info,
+                                    double* ms4);
 /* POSTERIOR COVARIANCE OF A UNIVARIATE BATCH WITH LANES = SITES (csrc/pgbp_cov_uni.hip): pgbp_posterior_cov (below) in the
  * frame of the three calls above, for the out-of-clique queries of a fitted batch -- the covariance of two ancestors that share
  * no cluster, the variance of a clade mean or of a contrast -- at every site at once.  The semantics are pgbp_posterior_cov's:

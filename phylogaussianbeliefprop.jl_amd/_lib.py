@@ -124,6 +124,8 @@ SYMBOLS = {
     "pgbp_bm_exact_stats_sites": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _F64P, _F64P, _F64P, _I32P]),
     "pgbp_bm_rate_matrix_sites": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _F64P, _F64P, _F64P, _I32P]),
     "pgbp_bm_rate_matrix_sites_timed": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _F64P, _F64P, _F64P, _I32P, _F64P]),
+    "pgbp_bm_rate_apply_sites": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, _F64P, C.c_int32, C.c_int32, _F64P, _F64P, _F64P, _I32P]),
+    "pgbp_bm_rate_apply_sites_timed": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, _F64P, C.c_int32, C.c_int32, _F64P, _F64P, _F64P, _I32P, _F64P]),
     "pgbp_lg_gradient": (C.c_int, [_P, C.c_int32, C.c_int32, _F64P, _F64P, _F64P, _F64P, _I32P]),
     "pgbp_lg_edge_gradient": (C.c_int, [_P, C.c_int32, C.c_int32, _F64P, _F64P, _F64P, _I32P]),
     "pgbp_lg_set_edges": (C.c_int, [_P, _F64P, _F64P]),

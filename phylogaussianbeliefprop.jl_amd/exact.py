@@ -171,7 +171,7 @@ def phylo_pca_sites(beliefs, schedule_tree, root, mode="cov", n_components=None)
 
     The rate matrix is formed on the device; the eigendecomposition is HOST work, numpy.linalg.eigh of the dense
     [n_sites, n_sites] matrix: O(n_sites^3) flops and 8 n_sites^2 bytes, seconds up to a few thousand sites and the wrong tool
-    beyond some ten thousand (form R in blocks with calibrate_rate_matrix_sites_ and use an iterative solver there).
+    beyond some ten thousand (phylo_pca_leading_sites gives the leading components there, without forming R).
     Returns dict(values [k] in decreasing order, loadings [n_sites, k] (unit columns, sign free), scores [n_observed_tips, k]
     = (Y - 1 mu') V over the tips the table observes in data-row order (with mode="corr" the columns of Y - 1 mu' are divided
     by the evolutionary standard deviations), rows: those data rows, mu, R: the matrix decomposed).  The data are those given
@@ -190,6 +190,123 @@ def phylo_pca_sites(beliefs, schedule_tree, root, mode="cov", n_components=None)
     if mode == "corr":
         Y = Y / np.sqrt(fit["var"][0])[None, :]
     return dict(values=w, loadings=V, scores=Y @ V, rows=rows, mu=fit["mu"][0], R=A)
+
+
+RATE_APPLY_MAX_VECTORS = 64   # vectors per pgbp_bm_rate_apply_sites call
+
+
+def bm_rate_apply_sites(beliefs, V, sites=None, root=None):
+    """pgbp_bm_rate_apply_sites on the current beliefs (calibrated under R = 1, mu = 0, improper root): gram @ V with gram of
+    bm_rate_matrix_sites(rows = cols = sites), the matrix never formed -- two skinny products with the residual rows U on the
+    matrix cores, U recomputed per call.  V: [sites, k] or [sites]; sites: a contiguous range (None: all sites).  V travels
+    as its [k][sites] transpose, in calls of at most 64 vectors; a vector's result does not depend on the vectors it travels
+    with.  Returns (GV of V's shape, den, mu or None, info) over the sites of the range.  If any site has info != 0, GV is
+    NaN in every entry (a bad site has no column of U and U V mixes all sites): check info once.  Refusals as
+    bm_rate_matrix_sites."""
+    n = beliefs.n_sites
+    s0, s1 = _site_range(sites, n)
+    ns = max(0, s1 - s0)
+    V = np.asarray(V, dtype=float)
+    flat = V.ndim == 1
+    V2 = V.reshape(-1, 1) if flat else V
+    if V2.ndim != 2 or V2.shape[0] != ns:
+        raise ValueError(f"V has shape {V.shape}; the range holds {ns} sites")
+    k = V2.shape[1]
+    GV = np.zeros((k, ns))
+    den = np.zeros(ns)
+    mu = np.zeros(ns) if root is not None else None
+    info = np.zeros(ns, dtype=np.int32)
+    rb, rp = (int(root[0]), int(root[1])) if root is not None else (0, 0)
+    for j0 in range(0, max(k, 1), RATE_APPLY_MAX_VECTORS):
+        vt = np.ascontiguousarray(V2[:, j0: j0 + RATE_APPLY_MAX_VECTORS].T)
+        out = np.zeros_like(vt)
+        # (k = 0: the call itself refuses, as every other misuse)
+        _check(beliefs._lib.pgbp_bm_rate_apply_sites(beliefs._eng, s0, s1, vt.shape[0], L.f64p(vt), rb, rp, L.f64p(out), L.f64p(den),
+                                                     L.f64p(mu) if root is not None else None, L.i32p(info)), beliefs._eng)
+        GV[j0: j0 + vt.shape[0]] = out
+    GV = GV.T.copy()
+    return (GV[:, 0] if flat else GV), den, mu, info
+
+
+def leading_eigenpairs(apply, n, k, block=None, maxiter=200, rtol=1e-10, seed=0):
+    """The k largest eigenpairs of a symmetric positive semidefinite operator of order n given as apply(Q [n, b]) -> G Q: block
+    subspace iteration with Rayleigh-Ritz, a pure numpy function of its callback.
+
+    Q0 = qr(standard normals from default_rng(seed)) [n, block]; per iteration ONE apply: Z = apply(Q), T = Q'Z symmetrised,
+    eigh(T) -> Ritz pairs (theta_i, x_i = Q y_i) in decreasing order with residuals |Z y_i - theta_i x_i|_2; stop when the
+    first k residuals are at most rtol * theta_1, else Q = qr(Z).  The error of theta_i is then at most its residual and that
+    of x_i at most residual / gap (Davis-Kahan); the residuals shrink by about lambda_{block+1} / lambda_k per iteration, so
+    the default block = min(n, 16 ceil((k + 8) / 16)) carries at least 8 guard vectors and is a whole number of the device
+    call's tiles.  k and block are clamped to n (block to k from below).  Householder QR: a Z of rank below block gives an
+    orthonormal Q all the same, the Ritz values beyond the rank are rounding, and the iteration stops as usual.
+    Returns dict(values [k], vectors [n, k], residuals [k], iterations, converged); not converging within maxiter is reported,
+    not raised."""
+    n = int(n)
+    k = max(1, min(int(k), n))
+    b = 16 * -(-(k + 8) // 16) if block is None else int(block)
+    b = max(k, min(n, b))
+    Q = np.linalg.qr(np.random.default_rng(seed).standard_normal((n, b)))[0]
+    theta, X, res, it, done = np.zeros(b), Q, np.full(b, np.inf), 0, False
+    for it in range(1, int(maxiter) + 1):
+        Z = np.asarray(apply(Q), dtype=float)
+        T = Q.T @ Z
+        theta, Y = np.linalg.eigh(0.5 * (T + T.T))
+        order = np.argsort(theta)[::-1]
+        theta, Y = theta[order], Y[:, order]
+        X = Q @ Y
+        res = np.linalg.norm(Z @ Y - X * theta[None, :], axis=0)
+        if not np.all(np.isfinite(res)):
+            break
+        if np.all(res[:k] <= rtol * abs(theta[0])):
+            done = True
+            break
+        Q = np.linalg.qr(Z)[0]
+    return dict(values=theta[:k].copy(), vectors=X[:, :k].copy(), residuals=res[:k].copy(), iterations=it, converged=done)
+
+
+def phylo_pca_leading_sites(beliefs, schedule_tree, root, n_components, mode="cov", block=None, maxiter=200, rtol=1e-10, seed=0):
+    """The leading n_components phylogenetic principal components of a univariate batch (phyl.pca, the sites as the traits)
+    WITHOUT the [n_sites, n_sites] matrix: what phylo_pca_sites returns for its first components, for batches whose rate
+    matrix does not fit or whose full eigendecomposition nobody wants.
+
+    Steps: factors of R = 1, mu = 0 -> one calibration enqueued as calibrate_rate_matrix_sites_ does it (the host mirrors are
+    not refreshed) -> one bm_exact_stats_sites for num, den, mu, info (any info != 0, or a site without a finite estimate, raises LinAlgError naming the site) ->
+    leading_eigenpairs with apply(Q) = D (G (D Q)) / den, G by bm_rate_apply_sites (one device pass over the residual rows per
+    iteration), D = I (mode="cov") or diag(1 / sqrt(num_a / den)) (mode="corr": the evolutionary correlations); the scaling is
+    numpy on [n_sites, block].  den is one number: every site observes the same tips.
+    Returns the keys of phylo_pca_sites without R -- values, loadings, scores = (Y - 1 mu') V (columns divided by the
+    evolutionary standard deviations with mode="corr"), rows, mu -- and explained = values / trace (the trace from num / den;
+    n_sites with mode="corr"), residuals, iterations, converged (False: maxiter reached; not raised)."""
+    if mode not in ("cov", "corr"):
+        raise ValueError("mode is 'cov' or 'corr'")
+    n = beliefs.n_sites
+    beliefs.assignfactors_lg_(np.ones((1, 1, 1)), np.zeros(1))
+    _, (num, den, mu, info), cal = beliefs._loglik_and_sites(schedule_tree, lambda: bm_exact_stats_sites(beliefs, root))
+    info = np.where((cal != 0) & (info == 0), -1, info)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        var = num / den
+    # (a site can be NaN with info 0 -- a cluster whose belief is the constant 1 --; it has no residual column either)
+    none = (info != 0) | ~np.isfinite(var) | (den < 0.5)
+    if none.any():
+        raise np.linalg.LinAlgError(f"phylo_pca_leading_sites: site {int(np.flatnonzero(none)[0])} has no rate estimate")
+    d = np.ones(n) if mode == "cov" else 1.0 / np.sqrt(var)
+    den0 = float(den[0])   # (to rounding the same at every site: the observed tips less one)
+
+    def apply(Q):
+        GV, _, _, inf = bm_rate_apply_sites(beliefs, d[:, None] * Q)
+        if inf.any():
+            raise np.linalg.LinAlgError(f"phylo_pca_leading_sites: site {int(np.flatnonzero(inf)[0])} has no rate estimate")
+        return d[:, None] * GV / den0
+
+    eig = leading_eigenpairs(apply, n, n_components, block=block, maxiter=maxiter, rtol=rtol, seed=seed)
+    w, V = eig["values"], eig["vectors"]
+    rows = _observed_tips(beliefs)
+    Y = np.asarray(beliefs._lg["data"])[:, rows, 0].T - mu[None, :]
+    if mode == "corr":
+        Y = Y / np.sqrt(var)[None, :]
+    trace = float(np.sum(var)) if mode == "cov" else float(n)
+    return dict(values=w, loadings=V, scores=Y @ V, rows=rows, mu=mu, explained=w / trace, residuals=eig["residuals"],
+                iterations=eig["iterations"], converged=eig["converged"])
 
 
 def calibrate_exact_cliquetree_(beliefs, schedule_tree, root, beliefs_fixedroot=None, all_sites=False):

@@ -356,6 +356,30 @@ function bm_rate_matrix_sites(o::DeviceClusterGraphBelief, rows::UnitRange{<:Int
 end
 
 """
+    bm_rate_apply_sites(obj, V, sites, rootcluster, rootpos) -> (GV, den, mu, info)
+
+The rate matrix of `bm_rate_matrix_sites(obj, sites, sites, ...)` applied to the columns of `V` (`length(sites)` x k) without
+the matrix being formed (pgbp_bm_rate_apply_sites): `GV = gram * V`, two skinny products with the residual rows on the matrix
+cores, for iterative consumers (leading principal components, solves, trace estimates).  `V` travels in calls of at most 64
+columns; `den`, `mu`, `info`: as `bm_exact_stats_sites` over `sites` (a 1-based unit range).  If any site has `info != 0`, `GV`
+is NaN in every entry: check `info` once.  Untested: there is no Julia on the test machines.
+"""
+function bm_rate_apply_sites(o::DeviceClusterGraphBelief, V::AbstractMatrix{<:Real}, sites::UnitRange{<:Integer}, rootcluster::Integer, rootpos::Integer)
+    n = length(sites); k = size(V, 2)
+    size(V, 1) == n || throw(DimensionMismatch("V has $(size(V, 1)) rows; the range holds $n sites"))
+    GV = zeros(n, k)
+    den = zeros(n); mu = zeros(n); info = zeros(Int32, n)
+    for j0 in 1:64:max(k, 1)
+        j1 = min(k, j0 + 63)
+        v = Matrix{Float64}(V[:, j0:j1])   # (column-major [sites, vectors] is the call's [n_vec][sites], site-minor)
+        gv = zeros(n, j1 - j0 + 1)
+        check(o.handle, @ccall LIB.pgbp_bm_rate_apply_sites(o.handle::Ptr{Cvoid}, Int32(first(sites) - 1)::Int32, Int32(last(sites))::Int32, Int32(j1 - j0 + 1)::Int32, v::Ptr{Float64}, Int32(rootcluster - 1)::Int32, Int32(rootpos - 1)::Int32, gv::Ptr{Float64}, den::Ptr{Float64}, mu::Ptr{Float64}, info::Ptr{Int32})::Cint)
+        GV[:, j0:j1] = gv
+    end
+    return (GV, den, mu, info)
+end
+
+"""
     moments_sites(obj, nsites, dims; cov = true) -> (mean, tri, norm, info)
 
 `moments!` of EVERY CLUSTER for every site of a univariate batch on the thread-per-site kernels (pgbp_moments_sites; the
