@@ -240,6 +240,38 @@ def main():
           f"{fitp['n_device_evals']} device passes; theta_1 - theta, theta_2 - theta at the first four sites (simulated +2.5, "
           f"-2.5): " + ", ".join(f"{fitp['optima'][s, 0] - fitp['theta'][s]:+.2f} {fitp['optima'][s, 1] - fitp['theta'][s]:+.2f}"
                                  for s in range(4)))
+    # and when the regimes are NOT known: which clade is pulled to another optimum?  The plain OU model fitted to the same data,
+    # then one sweep that scans every edge for a shift of the optimum of its whole clade (optimum_scan_sites_lg: the exact ML
+    # increment and its likelihood ratio per edge and site, all edges from one calibration).  The clade that leads at most
+    # sites is painted (add_optimum_shift refines the regime map) at each site's own increment, and the next scan looks for
+    # the second one with the first in force.
+    batch.clear_optima_lg()
+    fit0 = P.fit_sites_lg(batch, prob.schedule[0], "ou", np.ones(ns), Xp[:, 0], alpha0=np.full(ns, 1.0 / H), theta0=tipmean_p,
+                          fit_mu=False)
+    ll0, sc = batch.loglik_and_optimum_scan_sites_lg(prob.schedule[0], information=True)
+    lead = int(np.bincount(sc["top_family"][sc["top_family"] >= 0]).argmax())
+    table = synth.lg_tree_table(tr, prob, 1)
+    reg1, origin = P.add_optimum_shift(np.zeros((tr.nnodes - 1, 1), np.int32), table["parent_family"], lead)
+    delta = np.nan_to_num(sc["delta"][:, lead])
+    batch.set_optima_lg(reg1, (fit0["theta"] + delta)[:, None, None])        # (origin == [0]: the new regime came from theta)
+    ll1, sc1 = batch.loglik_and_optimum_scan_sites_lg(prob.schedule[0])
+    nxt = int(np.bincount(sc1["top_family"][sc1["top_family"] >= 0]).argmax())
+    print(f"scan for a shifted optimum: the clade below node {lead + 1} ({size[lead + 1]} tips; the painted clades hang below nodes "
+          f"{k1} and {k2}) leads at {int((sc['top_family'] == lead).sum())} of {ns} sites; delta +- se at the first four sites: " +
+          ", ".join(f"{sc['delta'][s, lead]:+.2f} +- {sc['se'][s, lead]:.2f}" for s in range(4)) +
+          f"; painting it gains 2 x {float(ll1[0] - ll0[0]):.3f} = lr {sc['lr'][0, lead]:.3f} at site 0; the next scan leads with the "
+          f"clade below node {nxt + 1} ({size[nxt + 1]} tips)")
+    # how large is the largest lr over all edges when NO clade has shifted?  200 replicates of site 0 simulated under its plain
+    # OU fit and scanned at once (bootstrap_optimum_scan_lg, lanes = replicates)
+    B = 200
+    boot = P.ClusterGraphBelief.from_arrays(prob.dims, prob.sepset_clusters, prob.scope_off, prob.scope_idx, None, n_sites=B)
+    boot.lg_setup(table, np.repeat(Xp[:1, :, None], B, axis=0))
+    boot.assignfactors_lg_(np.array([[[fit0["R"][0]]]]), np.array([Xp[0, 0]]), model="ou", alpha=float(fit0["alpha"][0]),
+                           theta=np.array([fit0["theta"][0]]))
+    null = P.bootstrap_optimum_scan_lg(boot, prob.schedule[0], seed=7)
+    print(f"  largest lr over all edges at site 0: observed {sc['top_lr'][0]:.2f}, bootstrap 95 % quantile without a shift "
+          f"{float(np.quantile(null['max_lr'], 0.95)):.2f} ({B} replicates)")
+    batch.clear_optima_lg()
     batch.lg_setup(synth.lg_tree_table(tr, prob, 1), np.ascontiguousarray(X[:, :, None]))   # (the unpainted batch again)
     # real batches have gaps, another set of unmeasured species at almost every site: a table with NaN at its gaps goes to
     # lg_setup with finite placeholders (split_missing_data) and its gaps to set_site_missing_lg; every site is then fitted to

@@ -699,6 +699,45 @@ int  pgbp_lg_edge_gradient_sites(pgbp_engine* e, int32_t site_begin, int32_t sit
 int  pgbp_lg_loo_sites(pgbp_engine* e, int32_t site_begin, int32_t site_end, double* mean, double* var, double* lpd,
                        double* total, int32_t* info);
 void pgbp_sites_sweep_scratch_limit(int64_t doubles);
+/* pgbp_lg_optimum_scan_sites: every edge scanned for a SHIFT OF THE OPTIMUM OF ITS CLADE under PGBP_LG_OU, for the sites of a
+ * univariate batch on a tree, lanes = sites (csrc/pgbp_optscan_uni.hip; the plan in csrc/pgbp_optscan_host.cpp), in the frame
+ * of the three calls above.  For the edge above family v the question is an increment delta added to the optimum of EVERY edge
+ * of clade(v) -- that edge and all edges below it, whatever regimes they carry (the nested-shift parametrisation).  The
+ * log-likelihood is exactly quadratic in delta, so the calibrated beliefs -- at the parameters, shifts, tip noise, painted
+ * optima and per-site mask in force -- hold the exact ML increment and its likelihood ratio of every edge.  With j = 1 / V
+ * (tip noise included), kappa = wc j and e = E[r | data] of a family (the offset with the painted optima), and over the child
+ * families c of v that are not skipped at the site, in index order (B = S = G = K = 0 at a tip):
+ *     B_v = sum_c [(kappa_c + B_c) rho_c - kappa_c qc_c]        S_v = sum_c [S_c + (kappa_c + B_c)^2 tau_c]
+ *     G_v = sum_c [G_c + kappa_c e_c]                           K_v = sum_c [K_c + wc_c kappa_c]
+ *   rho_c = Cov(x_c, x_v) / Var(x_v), tau_c = Var(x_c) - Cov(x_c, x_v)^2 / Var(x_v) from the posterior of c's own cluster
+ *   (0 for a tip).  Then g_v = G_v + kappa_v e_v, Kt_v = K_v + wc_v kappa_v, a = kappa_v + B_v, b = -kappa_v qc_v,
+ *     Var_v = a^2 Var(x_v) + 2 a b Cov(x_v, x_u) + b^2 Var(x_u) + S_v   (a tip: b^2 Var(x_u); no x_u terms under the fixed root)
+ *   and H_v = Kt_v - Var_v.  Family v is identified iff H_v > min_info Kt_v; then delta = g_v / H_v, lr = g_v^2 / H_v,
+ *   information = H_v (se = 1 / sqrt(H_v)).  A family the fill skips at a site (child_mask == 0, a tip masked at that site)
+ *   contributes nothing and is no candidate there.
+ * One launch per height of the family tree, from the tips up (a tip has height 0, any other family 1 + the largest height of
+ * its child families); a thread owns one (family of that height, site) and gathers four numbers per child family.
+ *   delta, lr, information [n_families][sites] (each may be NULL): delta and information NaN where the family is not
+ *       identified or skipped, lr 0 there; all three NaN for a root-prior family.
+ *   top_lr, top_family [sites] (may be NULL; not all five NULL): the largest lr over the identified families that have a
+ *       parent, and the first family that has it; -inf and -1 when nothing is identified; NaN and -1 at a failed site.  With
+ *       only these two asked for no table is allocated on the host or copied.
+ *   info [sites] (may be NULL): the 1-based index of the first cluster in preorder of schedule tree 0 whose conditional
+ *       precision is not positive definite at that site (the validity pass of pgbp_sample_posterior_sites), 0: none; such a
+ *       site is NaN everywhere.
+ * Refused before any launch, outputs, layout, pool and settings untouched: what pgbp_lg_gradient_sites refuses; a
+ * Brownian-motion fill (wc = 0: use pgbp_lg_shift_scan_sites); no topology (PGBP_ERR_STATE: call pgbp_lg_set_topology); a
+ * family with two or more parents (named); min_info outside [0, 1); a scratch limit below what one workgroup of 256 sites
+ * takes -- 256 (n_families (4 + tables + 1 with top) + ...) doubles, the text names the number that suffices.  Painted optima
+ * are read, not refused; an improper root is accepted.  No atomics, contraction off, every sum in a fixed order: two calls,
+ * every split of the site range, every chunking and both layouts give the same bytes.
+ * _timed (measurement only): ms4 = {validity pass, height launches, top fold, copies} in milliseconds, the stream drained
+ * after every phase; launches (may be NULL): the number of height launches of the call. */
+int  pgbp_lg_optimum_scan_sites(pgbp_engine* e, int32_t site_begin, int32_t site_end, double min_info, double* delta, double* lr,
+                                double* information, double* top_lr, int32_t* top_family, int32_t* info);
+int  pgbp_lg_optimum_scan_sites_timed(pgbp_engine* e, int32_t site_begin, int32_t site_end, double min_info, double* delta,
+                                      double* lr, double* information, double* top_lr, int32_t* top_family, int32_t* info,
+                                      double* ms4, int32_t* launches);
 /* pgbp_moments, pgbp_sample_posterior and pgbp_lg_impute for the sites of a UNIVARIATE BATCH, lanes = sites
  * (csrc/pgbp_post_uni.hip): what is asked of a fitted batch -- the posterior moments of every belief, joint draws of all
  * ancestral states, the predictions of the tips without data -- in the frame of the three calls above.  Accepted and refused

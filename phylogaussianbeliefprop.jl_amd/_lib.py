@@ -149,6 +149,9 @@ SYMBOLS = {
     "pgbp_lg_loo": (C.c_int, [_P, C.c_int32, C.c_int32, _F64P, _F64P, _F64P, _F64P, _I32P]),
     "pgbp_loo_scratch_limit": (None, [C.c_int64]),
     "pgbp_lg_shift_scan_sites": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_double, _F64P, _F64P, _F64P, _F64P, _I32P, _I32P]),
+    "pgbp_lg_optimum_scan_sites": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_double, _F64P, _F64P, _F64P, _F64P, _I32P, _I32P]),
+    "pgbp_lg_optimum_scan_sites_timed": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_double, _F64P, _F64P, _F64P, _F64P, _I32P, _I32P,
+                                                   _F64P, _I32P]),
     "pgbp_lg_edge_gradient_sites": (C.c_int, [_P, C.c_int32, C.c_int32, _F64P, _F64P, _F64P, _I32P]),
     "pgbp_lg_loo_sites": (C.c_int, [_P, C.c_int32, C.c_int32, _F64P, _F64P, _F64P, _F64P, _I32P]),
     "pgbp_sites_sweep_scratch_limit": (None, [C.c_int64]),

@@ -952,6 +952,46 @@ class ClusterGraphBelief:
         scan["info"] = np.where(scan["info"] != 0, scan["info"], info)
         return np.where(scan["info"] != 0, np.nan, norm), scan
 
+    def optimum_scan_sites_lg(self, min_info=1e-8, information=False, tables=True):
+        """pgbp_lg_optimum_scan_sites on the current beliefs: every edge scanned for a shift of the optimum of its clade under
+        OU, for a univariate batch on a tree on the thread-per-site kernels (the conditions of gradient_sites_lg, a topology
+        set, every family with one parent), lanes = sites.  For the edge above family v the increment `delta` is added to the
+        optimum of every edge of clade(v), whatever regimes they carry; the painted optima in force are read, so after a
+        regime is painted the scan gives the NEXT increment.  Returns a dict: delta, lr [site, family] as transposed views of
+        the call's site-minor rows (delta NaN and lr 0 where the family is not identified or skipped; both NaN for a
+        root-prior family), with information=True also information (H) and se = H^-1/2; top_lr, top_family [n_sites] formed
+        on the device (the largest lr over the identified families that have a parent, ties to the lowest family; -inf and -1
+        where nothing is identified; NaN and -1 at a failed site) and info [n_sites].  tables=False returns only top_lr,
+        top_family and info: no table is allocated or fetched.  Two calls return the same bytes."""
+        n = self.n_sites
+        nf = len(self._lg["cluster"])
+        delta = np.zeros((nf, n)) if tables else None
+        lr = np.zeros((nf, n)) if tables else None
+        H = np.zeros((nf, n)) if tables and information else None
+        top_lr = np.zeros(n)
+        top_family = np.zeros(n, dtype=np.int32)
+        info = np.zeros(n, dtype=np.int32)
+        _check(self._lib.pgbp_lg_optimum_scan_sites(self._eng, 0, n, float(min_info), L.f64p(delta) if tables else None,
+                                                    L.f64p(lr) if tables else None, L.f64p(H) if H is not None else None,
+                                                    L.f64p(top_lr), L.i32p(top_family), L.i32p(info)), self._eng)
+        d = dict(top_lr=top_lr, top_family=top_family, info=info)
+        if not tables:
+            return d
+        d.update(delta=delta.T, lr=lr.T)
+        if information:
+            d["information"] = H.T
+            d["se"] = 1.0 / np.sqrt(H.T)
+        return d
+
+    def loglik_and_optimum_scan_sites_lg(self, schedule_tree, min_info=1e-8, information=False, tables=True):
+        """The factors filled again (so that optima, shifts and noise set since the last assignfactors_lg_ are in) -> one
+        calibrate -> integratebelief! at the root cluster, enqueued as loglik_and_gradient_sites_lg does -> the sweep of
+        optimum_scan_sites_lg.  Returns (loglik [n_sites], scan dict); a failed site has info != 0 and NaN values."""
+        norm, scan, info = self._loglik_and_sites(
+            schedule_tree, lambda: self.optimum_scan_sites_lg(min_info=min_info, information=information, tables=tables), refill=True)
+        scan["info"] = np.where(scan["info"] != 0, scan["info"], info)
+        return np.where(scan["info"] != 0, np.nan, norm), scan
+
     def edge_gradient_sites_lg(self):
         """pgbp_lg_edge_gradient_sites on the current beliefs: edge_gradient_lg(all_sites=True) for a univariate batch on the
         thread-per-site kernels (the conditions of gradient_sites_lg), lanes = sites, nothing converted.  Same keys and

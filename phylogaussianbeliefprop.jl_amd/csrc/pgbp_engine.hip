@@ -2070,10 +2070,24 @@ int pgbp_lg_set_topology(pgbp_engine* e, const int32_t* parent_family) {
   for (int f = 0; f < nf; ++f)
     for (int k = 0; k < L.T.n_parents[f]; ++k) pf[(size_t)f * K + k] = parent_family[(size_t)f * K + k];
   if (level_fam.empty()) level_fam.push_back(0);
-  DevBuf<int32_t> d_pf, d_lf;
+  // the plan of the optimum-shift scan: child lists, heights (a network is accepted here and refused by the scan)
+  OptScanPlan os;
+  if (!optscan_plan_build(nf, K, L.T.n_parents.data(), parent_family, os, why))
+    return e->fail(PGBP_ERR_INVALID, "pgbp_lg_set_topology: " + why);
+  std::vector<int32_t> os_cf = os.child_fam, os_hf = os.height_fam;
+  if (os_cf.empty()) os_cf.push_back(0);
+  if (os_hf.empty()) os_hf.push_back(0);
+  DevBuf<int32_t> d_pf, d_lf, d_co, d_cf, d_hf;
   int rc;
   if ((rc = upload(e, d_pf, pf))) return rc;
   if ((rc = upload(e, d_lf, level_fam))) return rc;
+  if ((rc = upload(e, d_co, os.child_off))) return rc;
+  if ((rc = upload(e, d_cf, os_cf))) return rc;
+  if ((rc = upload(e, d_hf, os_hf))) return rc;
+  L.optscan = std::move(os);
+  L.d_os_child_off = std::move(d_co);
+  L.d_os_child_fam = std::move(d_cf);
+  L.d_os_height_fam = std::move(d_hf);
   L.d_pf = std::move(d_pf);
   L.d_level_fam = std::move(d_lf);
   L.level_off = std::move(level_off);

@@ -8,6 +8,7 @@
 #include "pgbp_devmem.hpp"
 #include "pgbp_kernels.hpp"
 #include "pgbp_lgtable.hpp"
+#include "pgbp_optscan_host.hpp"
 #include "pgbp_sitemiss_host.hpp"
 
 namespace pgbp {
@@ -74,6 +75,10 @@ struct LgModel {
   DevBuf<int32_t> d_pf, d_level_fam;
   std::vector<int32_t> level_off;
   int32_t improper = -1;
+  // the plan of pgbp_lg_optimum_scan_sites, built with the topology (pgbp_optscan_host.hpp; built == false: no topology): the
+  // child lists and the families by height, on the host and on the device
+  OptScanPlan optscan;
+  DevBuf<int32_t> d_os_child_off, d_os_child_fam, d_os_height_fam;
 };
 
 // the model of the engine's family table, null when there is none (defined in pgbp_engine.hip)

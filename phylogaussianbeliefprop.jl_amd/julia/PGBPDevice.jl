@@ -295,6 +295,28 @@ function lg_shift_scan_sites(o::DeviceClusterGraphBelief, nsites::Integer, nfami
 end
 
 """
+    lg_optimum_scan_sites(obj, nsites, nfamilies; min_info = 1e-8, information = false, tables = true)
+        -> (delta, lr, H, top_lr, top_family, info)
+
+The scan of every edge for a shift of the optimum of its clade under OU, for every site of a univariate batch on a tree on the
+thread-per-site kernels (pgbp_lg_optimum_scan_sites; the conditions of `lg_gradient_sites`, a topology set, one parent per
+family), lanes = sites, nothing converted.  The painted optima in force are read: the scan gives the increment.  `delta[s, f]`,
+`lr[s, f]` and `H[s, f]` (with `information`; se = 1 / sqrt(H)) are the call's site-minor rows; `top_lr[s]` and `top_family[s]`
+(1-based, 0: nothing identified or a failed site) the largest lr of a site and its family, formed on the device.
+`tables = false` fetches no table (`nothing`).  Written, not yet run.
+"""
+function lg_optimum_scan_sites(o::DeviceClusterGraphBelief, nsites::Integer, nfamilies::Integer; min_info::Real = 1e-8,
+                               information::Bool = false, tables::Bool = true)
+    delta = tables ? zeros(nsites, nfamilies) : nothing
+    lr = tables ? zeros(nsites, nfamilies) : nothing
+    H = (tables && information) ? zeros(nsites, nfamilies) : nothing
+    top = zeros(nsites); topf = zeros(Int32, nsites); info = zeros(Int32, nsites)
+    ptr(x) = x === nothing ? Ptr{Float64}(C_NULL) : pointer(x)
+    GC.@preserve delta lr H check(o.handle, @ccall LIB.pgbp_lg_optimum_scan_sites(o.handle::Ptr{Cvoid}, Int32(0)::Int32, Int32(nsites)::Int32, Float64(min_info)::Float64, ptr(delta)::Ptr{Float64}, ptr(lr)::Ptr{Float64}, ptr(H)::Ptr{Float64}, top::Ptr{Float64}, topf::Ptr{Int32}, info::Ptr{Int32})::Cint)
+    return (delta, lr, H, top, Int.(topf) .+ 1, info)
+end
+
+"""
     lg_edge_gradient_sites(obj, nsites, nfamilies, K) -> (dlength, dgamma, dshift, info)
 
 `lg_edge_gradient` for every site of a univariate batch on the thread-per-site kernels (pgbp_lg_edge_gradient_sites), lanes =

@@ -464,6 +464,63 @@ def bootstrap_shift_scan_lg(beliefs, schedule_tree, seed=None, z=None, min_info=
     return dict(max_lr=top, family=fam, edge=edge, loglik=ll, info=info, x=x, data=beliefs.get_data_lg(), data_before=before)
 
 
+def add_optimum_shift(regime, parent_family, family):
+    """Refine a regime map by clade(family): the nested-shift parametrisation optimum_scan_sites_lg scans.  regime: the int
+    map [n_families, K] (or flat) of set_optima_lg on a TREE (one parent per family: K = 1, or only column 0 in use), 0 = the
+    edge keeps theta; parent_family [n_families * K]: what lg_families gives (the family of each parent, negative: a root);
+    family: the family above whose edge the optimum shifts.  Every regime that meets the clade -- the edge above `family` and
+    all edges below it -- is split: its edges inside the clade get a new regime, in the order the old regimes are first met
+    in family order.  Returns (new_regime, origin): new_regime shaped as `regime`; origin[r - 1] is the regime the new map's
+    regime r came from (0: theta; origin[r - 1] == r for the regimes the old map had).  A caller sets the values of a new
+    regime r to value[origin[r - 1]] + delta (value[0] = theta) and keeps the others.  Pure numpy."""
+    reg = np.array(regime, np.int32, copy=True)
+    shape = reg.shape
+    nf = shape[0] if reg.ndim >= 1 else 1    # (a flat map is that of a table with K = 1, as a tree's is)
+    K = max(1, reg.size // max(1, nf))
+    if np.asarray(parent_family).size != nf * K:
+        raise ValueError(f"add_optimum_shift: parent_family has {np.asarray(parent_family).size} entries, the map {nf * K}")
+    reg = reg.reshape(nf, K)
+    pf = np.asarray(parent_family, np.int64).reshape(nf, K)[:, 0]
+    family = int(family)
+    if not 0 <= family < nf:
+        raise ValueError(f"add_optimum_shift: family {family} out of range ({nf} families)")
+    inside = np.zeros(nf, bool)
+    inside[family] = True
+    for f in range(family + 1, nf):          # families are in preorder: a parent comes before its children
+        inside[f] = pf[f] >= 0 and inside[pf[f]]
+    n_old = int(reg.max()) if reg.size else 0
+    origin = list(range(1, n_old + 1))
+    new_of = {}
+    out = reg.copy()
+    for f in np.flatnonzero(inside):
+        r = int(reg[f, 0])
+        if r not in new_of:
+            origin.append(r)
+            new_of[r] = len(origin)
+        out[f, 0] = new_of[r]
+    return out.reshape(shape), np.array(origin, np.int32)
+
+
+def bootstrap_optimum_scan_lg(beliefs, schedule_tree, seed=None, z=None, min_info=1e-8):
+    """Parametric bootstrap of the optimum-shift scan on a clique tree: the null distribution of the LARGEST lr over all edges
+    of optimum_scan_sites_lg -- the twin of bootstrap_shift_scan_lg(sites=True).  On a thread-per-site engine with B sites (B
+    replicates of one tree, the fitted null model assigned) it reads the data in force, simulates B data sets under the
+    current model into the engine's data (simulate_lg(write_data=True, all_sites=True)), fills, calibrates and scans every
+    replicate at once (loglik_and_optimum_scan_sites_lg(tables=False): no table is fetched, the maximum and its family are
+    taken on the device).  Returns a dict: max_lr [B] (-inf for a replicate without any identified family, NaN where info is
+    not 0), family [B] (-1 where there is none), loglik [B], info [B], x, data and data_before as bootstrap_shift_scan_lg.
+    np.quantile(max_lr, 0.95) is the threshold at which a first clade's optimum shifts with probability about 5 % under the
+    null.  WITH PAINTED OPTIMA IN FORCE the call inherits simulate_lg's refusal (the simulation does not honour them yet), so
+    today it calibrates the FIRST shift only."""
+    before = beliefs.get_data_lg()
+    x, sim_info = beliefs.simulate_lg(z=z, seed=seed, write_data=True, all_sites=True)
+    ll, scan = beliefs.loglik_and_optimum_scan_sites_lg(schedule_tree, min_info=min_info, tables=False)
+    info = np.where(sim_info != 0, sim_info, scan["info"])
+    fam = scan["top_family"].astype(np.int64)
+    top = np.where(info != 0, np.nan, np.where(fam < 0, -np.inf, scan["top_lr"]))
+    return dict(max_lr=top, family=fam, loglik=ll, info=info, x=x, data=beliefs.get_data_lg(), data_before=before)
+
+
 def lbfgs_sites(value_and_grad, x0, maxiter=200, gtol=1e-8, memory=8, c1=1e-4):
     """Batched L-BFGS: minimises n independent functions of d variables side by side, one callback per step for all of them.
     value_and_grad(X [n, d]) -> (f [n], g [n, d]) evaluates every site at its row of X; a site whose value or gradient is
