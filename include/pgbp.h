@@ -146,6 +146,13 @@ int  pgbp_plan_chunks(const pgbp_plan* p, int32_t tree, int32_t dir, int32_t* n_
  * the entry in front of the record's own, in the same task. */
 int  pgbp_plan_prologues(const pgbp_plan* p, int32_t tree, int32_t dir, int32_t* level_pro, int32_t* tail_pro,
                          int32_t* chunk_pro);
+/* LEAF SEPSETS (any may be NULL): one word per record, order as for pgbp_plan_prologues: 1 where the record is a preorder
+ * message into a leaf L of the schedule tree whose postorder message on the same edge is L's whole belief (nothing
+ * integrated, sepset dimension = cluster dimension).  In a postorder + preorder pair the sepset then holds exactly what L
+ * holds, and the register-resident kernels take it from L's block instead of loading it (PGBP_TUNING leaf_sepset=0: they
+ * load it). */
+int  pgbp_plan_leaf_sepset(const pgbp_plan* p, int32_t tree, int32_t dir, int32_t* level_leaf, int32_t* tail_leaf,
+                           int32_t* chunk_leaf);
 /* CHAINS of the loop launches in the packed layout (csrc/pgbp_loop.hip), one word per record of the tail and of the chunks
  * (order as above; either may be NULL): kind | source record of the previous group << 8 | late << 16.  A workgroup loads
  * the operands of a group while the group before it still runs: kind 1 / 3 = the integrated block of the record's 2P-dim

@@ -281,6 +281,7 @@ DevState dev_state(pgbp_engine* e, const pgbp_opts* o) {
   S.packed_off = e->d_packed_off.get();
   S.rpacked_off = e->d_rpacked_off.get();
   S.sep_zero = 0;
+  S.leaf_sepset = 0;
   S.notcal = nullptr;
   if (e->layout_sm) {
     S.pool = e->sm.pool.get();
@@ -561,11 +562,16 @@ void enqueue_levels(pgbp_engine* e, const DevState& S, const Traversal& tr, cons
 // Once the postorder of a tree failed, its preorder does not run here.  (The reference still walks it, on beliefs the
 // sequential postorder left half-updated, may log a second failure, and returns (false, false): src/calibration.jl:80-82.
 // The first failure of the reference's order is what the engine reports; the state after a failure is unspecified.)
-void enqueue_tree(pgbp_engine* e, const DevState& S, int tree, int dirs, unsigned long long pair_index, bool kl = false,
+void enqueue_tree(pgbp_engine* e, const DevState& S_in, int tree, int dirs, unsigned long long pair_index, bool kl = false,
                   int* n_launches = nullptr) {
   const Tree& T = e->plan.trees[tree];
   const unsigned long long seq_base = pair_index * seq_stride(e);
   const unsigned long long stop_post = seq_base, stop_pre = seq_base + (unsigned long long)T.pa.size();
+  // LEAF SEPSETS (FEntry::pad[3]): only when this very call runs the postorder that fills them in front of the preorder that
+  // would read them, and every message of it runs on the register-resident kernels (they copy a leaf's belief into its
+  // sepset bit for bit; kl: residual_kldiv! reads the sepsets between the levels, on the generic path's terms)
+  DevState S = S_in;
+  S.leaf_sepset = (dirs == 3 && !kl && e->plan.tune.leaf_sepset && e->plan.all_fast && !uni_engine(e) && !e->layout_sm) ? 1 : 0;
   const int np = (dirs & 1) ? tail_levels(e, T.post, kl) : 0, nq = (dirs & 2) ? tail_levels(e, T.pre, kl) : 0;
   const int nlev_post = (int)T.post.level_off.size() - 1, nlev_pre = (int)T.pre.level_off.size() - 1;
   if (dirs & 1) enqueue_levels(e, S, T.post, e->dpost[tree], 0, nlev_post - np, seq_base, stop_post, kl, n_launches);
@@ -582,17 +588,32 @@ void enqueue_tree(pgbp_engine* e, const DevState& S, int tree, int dirs, unsigne
 // One iteration of calibrate! on one schedule tree (postorder + preorder) followed by iscalibrated_residnorm(beliefs) into
 // `d_out` [n_sites].  Thread-per-site engines whose tree holds every sepset: the message kernels mark the sites with a false
 // flag themselves (DevState::notcal) and the all-flags reduction is a kernel of n_sites threads instead of one over
-// n_sites x n_messages words.
+// n_sites x n_messages words.  Engines whose every message runs on the register-resident kernels (bp_fast16, bp_loop16) do
+// the same: one launch of n_sites workgroups in place of the fill of `d_out` and the reduction.
 void enqueue_pair_and_iscal(pgbp_engine* e, const DevState& S, int tree, unsigned long long pair, bool kl, int32_t* d_out,
                             int* n_launches = nullptr) {
   const Plan& p = e->plan;
   const bool fused = e->layout_sm && !kl && S.update_resnorm != 0 && (int)p.trees[tree].pa.size() == p.n_sepsets;
+  // (not for a tree with prologues: the loop kernel's prologue instance sets no marks, pgbp_loop.hip; nor on the lane grids
+  // whose instances set none: leaf_mark_grid)
+  const bool fused_fast = !fused && leaf_mark_grid(p.fast_p + (p.fast_p & 1)) && !e->layout_sm && !uni_engine(e) && p.all_fast && !kl && S.update_resnorm != 0 &&
+                          (int)p.trees[tree].pa.size() == p.n_sepsets && !p.trees[tree].post.has_pro && !p.trees[tree].pre.has_pro;
   if (fused) {
     (void)hipMemsetAsync(e->d_notcal.get(), 0, sizeof(int32_t) * (size_t)p.n_sites, e->st);
     DevState S1 = S;
     S1.notcal = e->d_notcal.get();
     enqueue_tree(e, S1, tree, 3, pair, kl, n_launches);
     launch_iscal_from_notcal(e->d_notcal.get(), d_out, p.n_sites, e->st);
+  } else if (fused_fast) {
+    // the register-resident kernels mark a false flag too.  A message that failed or did not run (behind a failure, at a
+    // site `auto` has halted) leaves its flag as it was, and that flag counts: such a site -- its fail word holds a key
+    // below the end of this pair -- gets the reduction over its flags inside the same launch.  That launch also clears the
+    // marks it has read: no fill in front of the traversals (d_notcal is clear from pgbp_create on).
+    DevState S1 = S;
+    S1.notcal = e->d_notcal.get();
+    enqueue_tree(e, S1, tree, 3, pair, kl, n_launches);
+    launch_iscal_from_notcal_or_flags(e->d_notcal.get(), e->d_flags.get(), p.n_msgs(), e->d_fail.get(), (pair + 1) * seq_stride(e), d_out,
+                                      p.n_sites, e->st);
   } else {
     enqueue_tree(e, S, tree, 3, pair, kl, n_launches);
     launch_reduce_flags(e->d_flags.get(), p.n_msgs(), p.n_sites, d_out, e->st, e->layout_sm ? 1 : 0);
@@ -744,6 +765,11 @@ int pgbp_create(const pgbp_desc* desc, pgbp_engine** out) {
   if ((rc = dev_alloc(e, e->d_poison, nsw * (size_t)p.n_clusters))) return bail(rc);
   if ((rc = dev_alloc(e, e->d_iscal, ns))) return bail(rc);
   if ((rc = dev_alloc(e, e->d_notcal, ns))) return bail(rc);
+  // (the marks of the register-resident kernels are cleared by the kernel that reads them: they start out clear.  On the
+  // engine's stream, like every later access.  They are clear between pairs because enqueue_pair_and_iscal has no way out
+  // between its traversals and the launch that reads and clears them: enqueue_tree returns nothing and records a failed
+  // workspace allocation in enqueue_rc only)
+  if (hipMemsetAsync(e->d_notcal.get(), 0, sizeof(int32_t) * ns, e->st) != hipSuccess) return bail(PGBP_ERR_HIP);
   if ((rc = upload(e, e->d_boff, p.boff))) return bail(rc);
   if ((rc = upload(e, e->d_packed_off, p.packed_off))) return bail(rc);
   if ((rc = upload(e, e->d_roff, p.roff))) return bail(rc);

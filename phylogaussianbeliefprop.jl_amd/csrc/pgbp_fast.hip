@@ -185,6 +185,9 @@ __global__ __launch_bounds__(MODE == kTail ? kTailWaves * 64 : kFastMaxWaves * 6
     const bool recv_blk = has_block || (accum && !(en.mode & kFNoBlock));
     const bool provider = en.src_wave == wave;      // computes the marginal itself
     const int first_wave = en.grp_base;             // first wave of this record's task
+    // LEAF SEPSET (FEntry::pad[3], DevState::leaf_sepset): the old sepset is, bit for bit, the receiver block loaded below
+    // (not in every instance: leaf_mark_grid, pgbp_internal.hpp)
+    const bool leafsep = leaf_mark_grid(P) && en.pad[3] != 0 && S.leaf_sepset != 0;
 
     double* __restrict__ sep = pool + en.sep_off;
     double* __restrict__ to = pool + en.to_off;
@@ -217,7 +220,7 @@ __global__ __launch_bounds__(MODE == kTail ? kTailWaves * 64 : kFastMaxWaves * 6
       // ---- every load of this message is issued before any arithmetic; the sender (the largest operand and
       // the one the elimination waits for) goes first, the sepset and the receiver block right behind it
       auto load_sep_to = [&]() {
-        if (!S.sep_zero) {
+        if (!S.sep_zero && !leafsep) {
           if (has_block) {
             sJ = load_blk<BS, ODD, kStream, PL>(sep, PR, a, b, up, kidx, PR);
             if (b == 0) sh = load_pair<ODD>(sep + sepH, a, PR);
@@ -379,7 +382,12 @@ __global__ __launch_bounds__(MODE == kTail ? kTailWaves * 64 : kFastMaxWaves * 6
               }
               if (S.update_resnorm) {   // iscalibrated_residnorm! (src/beliefs.jl:994-1003)
                 const bool all_ok2 = __all(maxh2 <= S.thr_h_p && maxJ2 <= S.thr_J_p);
-                if (lane == 0) S.flags[(int64_t)site * S.n_msgs + pr.msg] = all_ok2 ? 1 : 0;
+                if (lane == 0) {
+                  S.flags[(int64_t)site * S.n_msgs + pr.msg] = all_ok2 ? 1 : 0;
+                  if constexpr (leaf_mark_grid(P)) {
+                    if (!all_ok2 && S.notcal) S.notcal[site] = 1;
+                  }
+                }
               }
               // mult! (src/beliefupdates.jl:483-488): F's integrated block, in the registers of the elimination ...
               f.w[0][0] += d2.x; f.w[1][0] += d2.y; f.w[0][1] += d2.z; f.w[1][1] += d2.w;
@@ -468,6 +476,11 @@ __global__ __launch_bounds__(MODE == kTail ? kTailWaves * 64 : kFastMaxWaves * 6
     // ---- divide! (src/beliefupdates.jl:579-587): every wave for its own sepset
     Blk dJ{0, 0, 0, 0};
     double dh0 = 0.0, dh1 = 0.0, dg = 0.0;
+    if (leafsep) {   // (wave-uniform; such a record owns its receiver, a P-dim block at offset 0: the sepset's own layout)
+      sJ = tJ;
+      sh = make_double2(th[0], th[1]);
+      sg = tg;
+    }
     if (state == 1) {
       double maxJ = 0.0, maxh = 0.0;
       if (has_block) {
@@ -496,7 +509,12 @@ __global__ __launch_bounds__(MODE == kTail ? kTailWaves * 64 : kFastMaxWaves * 6
         // compares its own maximum": one ballot instead of two 6-step wave reductions on the critical path
         const bool lane_ok = maxh <= S.thr_h_p && maxJ <= S.thr_J_p;   // (DevState::thr: no division here)
         const bool all_ok = __all(lane_ok);
-        if (lane == 0) S.flags[(int64_t)site * S.n_msgs + en.msg] = (!has_block || all_ok) ? 1 : 0;
+        if (lane == 0) {
+          S.flags[(int64_t)site * S.n_msgs + en.msg] = (!has_block || all_ok) ? 1 : 0;
+          if constexpr (leaf_mark_grid(P)) {
+            if (has_block && !all_ok && S.notcal) S.notcal[site] = 1;   // (every writer writes the same value)
+          }
+        }
       }
     } else if (state >= 2 && lane == 0) {
       // not positive definite, or downstream of a failure: nothing of this message is applied

@@ -43,7 +43,9 @@ struct Entry {
   int32_t tflags; // fast kernels: bit 0 = load the receiver's block before this entry, bit 1 = store it after
   int32_t pro;    // 1: this entry is the PROLOGUE of the next one (a message X -> F that integrates nothing, sent by the
                   // wavefront that then sends F's own message: build_traversals, bp_fast16)
-  int32_t pad[2];
+  int32_t leafsep; // preorder: 1 = the receiver is a leaf of the schedule tree whose postorder message on this edge is its
+                  // whole belief (ni == 0, s == mf): the sepset then still holds what the leaf holds (FEntry::pad[3])
+  int32_t pad[1];
 };
 constexpr int kTLoad = 1, kTStore = 2;
 
@@ -107,6 +109,10 @@ struct FEntry {
   // sender (1: the integrated block of a 2P sender, 3: a P-dim sender's whole belief) or its prologue's X (2) received
   // in the previous pass of the walk is taken from the LDS chain slot of wave pad[1] instead of memory; pad[2] != 0: the
   // record's group is LATE (it reads from memory something else the previous pass wrote: full barrier, loads at its top)
+  // pad[3] (any launch; set by append_group): LEAF SEPSET -- a preorder record into a leaf L of the schedule tree whose
+  // postorder message on the same edge was L's whole belief: sepset == belief(L) bit for bit when the preorder of the same
+  // enqueue_tree call gets here, so the kernel takes the sepset from the receiver block it loads anyway
+  // (DevState::leaf_sepset; bp_fast16, bp_loop16)
   uint8_t pad[6];
 };
 static_assert(sizeof(FEntry) == 64, "FEntry must be one 64-byte record");
@@ -122,6 +128,13 @@ struct FPro {
 };
 static_assert(sizeof(FPro) == 32, "FPro is half a 64-byte line");
 constexpr int kFOwn = 1, kFAccum = 2;
+// Which instances of the register-resident kernels carry the LEAF SEPSET shortcut (pad[3] above) and the "not calibrated"
+// mark (DevState::notcal), by the lane grid P they are built for (an odd sepset dimension runs on the grid of the next even
+// one).  Both keep a kernel argument live across the body, and the instances left out pay for that in scratch memory:
+// bp_loop16<2, false> 0 -> 36 bytes per lane, the level instances bp_fast16<14, true, false, 0, true> 24 -> 28,
+// <10, true, false, 0, true> 20 -> 24 and <10, true, false, 0, false> 12 -> 16 (DESIGN.md section 4.1 has the whole table).
+// An instance without them loads the sepset and sets no mark; the engine keeps the flag reduction for it.
+constexpr bool leaf_mark_grid(int P) { return P != 2 && P != 10 && P != 14; }
 constexpr int kFPro = 8;           // the record has a PROLOGUE (FPro, same index in the parallel array): see bp_fast16
 constexpr int kFNoBlock = 4;       // accumulate task whose messages are all constants (dimension-0 sepsets): only the receiver's g
 constexpr int kFastMaxWaves = 4;   // messages per fast-class task at most = records per group of a level launch
@@ -166,6 +179,7 @@ struct Tuning {
   bool packed_layouts = true;  // plain_layout: keep the ABI's record layout on the device (no BS16, no site-minor)
   long long mixed_fast_min = -1;   // mixed_fast_min=n: a level with both task classes splits from n fast-class tasks on (-1: default)
   int small4_min = kSmall4MinTasksDefault;   // small4_min=n: four tasks per wavefront from n tasks on (-1: never)
+  bool leaf_sepset = true;     // leaf_sepset=0: a preorder message into a leaf of the schedule tree loads the old sepset like any other
   int chunk_bins = -1;         // chunk_bins=n: workgroups of a chunk launch at most (0: one per tree of its forest; -1: kChunkBins)
 };
 // parses PGBP_TUNING; false + message on an unknown token or a bad value

@@ -2770,6 +2770,30 @@ void launch_iscal_from_notcal(const int32_t* d_notcal, int32_t* d_iscal, int n_s
   hipLaunchKernelGGL(iscal_from_notcal_kernel, dim3((n_sites + 255) / 256), dim3(256), 0, st, d_notcal, d_iscal, n_sites);
 }
 
+// The register-resident kernels' marks (bp_fast16, bp_loop16): one workgroup per site.  Every message of the pair that RAN
+// rewrote its flag and marked a false one; a message that failed, or did not run (behind a failure of this or an earlier
+// pair, at a site that `auto` has halted), left its flag as it was -- and reduce_flags_kernel counts that flag.  Such a
+// site's fail word holds a key below `seq_end`, the first sequence number behind this pair: the workgroup then reduces
+// the site's flags itself, so iscal is in every case what the reduction gives.  The mark is cleared for the next pair.
+__global__ __launch_bounds__(256) void iscal_from_notcal_or_flags_kernel(int32_t* __restrict__ notcal, const int32_t* __restrict__ flags,
+                                                                         int n_msgs, const unsigned long long* __restrict__ fail,
+                                                                         unsigned long long seq_end, int32_t* __restrict__ iscal) {
+  const int site = blockIdx.x;
+  int bad = notcal[site] != 0;
+  if ((fail[site] >> kInfoBits) < seq_end)   // (uniform over the workgroup)
+    for (int d = threadIdx.x; d < n_msgs; d += blockDim.x) bad |= (flags[(int64_t)site * n_msgs + d] == 0);
+  bad = __syncthreads_or(bad);
+  if (threadIdx.x == 0) {
+    iscal[site] = bad ? 0 : 1;
+    notcal[site] = 0;
+  }
+}
+void launch_iscal_from_notcal_or_flags(int32_t* d_notcal, const int32_t* d_flags, int n_msgs, const unsigned long long* d_fail,
+                                       unsigned long long seq_end, int32_t* d_iscal, int n_sites, hipStream_t st) {
+  hipLaunchKernelGGL(iscal_from_notcal_or_flags_kernel, dim3(n_sites), dim3(256), 0, st, d_notcal, d_flags, n_msgs, d_fail, seq_end,
+                     d_iscal);
+}
+
 void launch_reduce_flags(const int32_t* flags, int n_msgs, int n_sites, int32_t* d_iscal, hipStream_t st, int sm) {
   (void)hipMemsetAsync(d_iscal, 0x01, sizeof(int32_t) * (size_t)n_sites, st);
   if (n_msgs <= 0) return;

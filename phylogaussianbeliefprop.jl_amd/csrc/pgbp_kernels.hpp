@@ -43,7 +43,7 @@ struct DevState {
   int32_t n_sites;
   const int64_t* packed_off;
   const int64_t* rpacked_off;
-  // thread-per-site kernels only, may be null: notcal[site] is set by a message whose residual-norm flag comes out false.  When
+  // thread-per-site kernels and the register-resident ones (bp_fast16, bp_loop16), may be null: notcal[site] is set by a message whose residual-norm flag comes out false.  When
   // a postorder + preorder pair over a spanning tree that holds EVERY sepset has run (each of the 2 n_sepsets flags rewritten
   // once), iscalibrated_residnorm(beliefs) (src/clustergraphbeliefs.jl:168-169) of a site is "no message set the mark": the
   // engine then skips the reduction over the flag array (80 M words per calibrate of a 1 000-site batch on a 20 000-tip tree)
@@ -51,6 +51,11 @@ struct DevState {
   // every sepset this launch touches is known to hold the constant 1 (J = h = g = 0: straight after a reset, in a
   // postorder that overwrites all of them): the register-resident kernel then does not read them
   int32_t sep_zero;
+  // this launch belongs to a postorder + preorder pair of ONE enqueue_tree call: a preorder record marked LEAF SEPSET
+  // (FEntry::pad[3]) finds in its sepset what the pair's postorder copied there from the receiving leaf, which nothing has
+  // touched since -- the register-resident kernels then take the sepset from the receiver block they load anyway.  0 in a
+  // preorder-only traversal and in pgbp_propagate, where the sepset may hold anything.
+  int32_t leaf_sepset;
 };
 
 size_t generic_lds_bytes(int max_mf);
@@ -321,6 +326,10 @@ void launch_regularize_onschedule(double* pool, int64_t pool_stride, const int32
 void launch_reduce_flags(const int32_t* flags, int n_msgs, int n_sites, int32_t* d_iscal, hipStream_t st, int sm = 0);
 // iscal[site] = notcal[site] == 0 (DevState::notcal)
 void launch_iscal_from_notcal(const int32_t* d_notcal, int32_t* d_iscal, int n_sites, hipStream_t st);
+// ... of the register-resident kernels: a site whose fail word holds a key below seq_end (a message of the pair failed or did
+// not run) gets the reduction over its flags instead; clears the marks
+void launch_iscal_from_notcal_or_flags(int32_t* d_notcal, const int32_t* d_flags, int n_msgs, const unsigned long long* d_fail,
+                                       unsigned long long seq_end, int32_t* d_iscal, int n_sites, hipStream_t st);
 // fail[site] = min(fail[site], key) where iscal[site] != 0 (key carries info = 0: a halt, not a failure)
 void launch_halt_if_calibrated(const int32_t* d_iscal, unsigned long long* d_fail, unsigned long long key, int n_sites,
                                hipStream_t st);

@@ -437,6 +437,12 @@ __global__ __launch_bounds__(kLoopWaves * 64) void bp_loop16(DevState S_arg, con
       const int64_t tH0 = (tpk ? (mt == P ? bs16::h1(P) : bs16::h2(P)) : (int64_t)mt * mt) + up0;
       const int64_t tG0 = tpk ? (mt == P ? bs16::g1(P) : bs16::g2(P)) : (int64_t)mt * mt + mt;
       const bool sepz = S.sep_zero != 0;
+      // LEAF SEPSET (FEntry::pad[3], DevState::leaf_sepset): the old sepset is, bit for bit, the receiver block loaded below.
+      // Not in the prologue instance, and no DevState::notcal marks there either (pgbp_engine.hip keeps the flag reduction
+      // for trees with prologues): it has no scalar register left -- with either, the compiler moves part of its spilled
+      // scalars on into scratch memory (bp_loop16<16, true>: 11 -> 17 spilled, 0 -> 36 bytes per lane).  The P = 2 instance
+      // is left out for the same reason (leaf_mark_grid, pgbp_internal.hpp).
+      const bool leafsep = !PRO && leaf_mark_grid(P) && en.pad[3] != 0 && S.leaf_sepset != 0;
       issue_next();
       const int f_ii = en.keep0 == 0 ? bs16::t11(P) : 0, f_hi = bs16::h2(P) + (en.keep0 == 0 ? P : 0);
       // ---- its loads, at the top of the pass: the sepset, the receiver block, the prologue's operands
@@ -448,7 +454,7 @@ __global__ __launch_bounds__(kLoopWaves * 64) void bp_loop16(DevState S_arg, con
       double p_xh0 = 0.0, p_xh1 = 0.0, p_dh0 = 0.0, p_dh1 = 0.0, p_xg = 0.0, p_h0 = 0.0, p_h1 = 0.0, p_g = 0.0;
       bool p_ok = false;
       if (live) {
-        if (!sepz) {
+        if (!sepz && !leafsep) {
           if (has_block) {
             sJ = load_blk<true, false, !PRO, PL>(sep, P, a, b, up, kidx);
             if (b == 0) sh = load_pair<false>(sep + bs16::h1(P), a, P);
@@ -513,6 +519,11 @@ __global__ __launch_bounds__(kLoopWaves * 64) void bp_loop16(DevState S_arg, con
       // everything this wavefront stored in the pass before is complete (the barrier below orders it before the early
       // loads of the providers), and so are its own loads of this pass
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      if (leafsep) {   // (never an accumulating record: nothing above has read sJ; it owns its receiver, a P-dim block)
+        sJ = tJ;
+        sh = make_double2(th0, th1);
+        sg = tg;
+      }
       PGBP_LT(4);
       lds_barrier();   // B1: the marginals are out
       PGBP_LT(5);
@@ -617,7 +628,9 @@ __global__ __launch_bounds__(kLoopWaves * 64) void bp_loop16(DevState S_arg, con
         }
         if (S.update_resnorm) {
           const bool all_ok2 = __all(maxh2 <= S.thr_h_p && maxJ2 <= S.thr_J_p);
-          if (lane == 0) S.flags[(int64_t)site * S.n_msgs + pr.msg] = all_ok2 ? 1 : 0;
+          if (lane == 0) {
+            S.flags[(int64_t)site * S.n_msgs + pr.msg] = all_ok2 ? 1 : 0;
+          }
         }
         store_blk<true, false, false, PL>(fw + f_ii, P, a, b, up, act, kidx, p_ii);
         if (act && b == 0) store_pair<false>(fw + f_hi, a, p_h0, p_h1, P);
@@ -641,7 +654,12 @@ __global__ __launch_bounds__(kLoopWaves * 64) void bp_loop16(DevState S_arg, con
           // iscalibrated_residnorm! (src/beliefs.jl:994-1003); an empty message is calibrated
           const bool lane_ok = maxh <= S.thr_h_p && maxJ <= S.thr_J_p;
           const bool all_ok = __all(lane_ok);
-          if (lane == 0) S.flags[(int64_t)site * S.n_msgs + en.msg] = (!has_block || all_ok) ? 1 : 0;
+          if (lane == 0) {
+            S.flags[(int64_t)site * S.n_msgs + en.msg] = (!has_block || all_ok) ? 1 : 0;
+            if constexpr (!PRO && leaf_mark_grid(P)) {
+              if (has_block && !all_ok && S.notcal) S.notcal[site] = 1;   // (every writer writes the same value)
+            }
+          }
         }
         if (own) {
           if (recv_blk) {

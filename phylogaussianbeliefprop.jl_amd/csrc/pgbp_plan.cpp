@@ -57,6 +57,7 @@ bool read_tuning(Tuning& t, std::string& err) {
     else if (key == "plain_layout") { ok = flag; t.packed_layouts = false; }
     else if (key == "pair") { ok = within(0, 1); t.pair2 = num != 0; }
     else if (key == "loop") { ok = within(0, 1); t.loop2 = num != 0; }
+    else if (key == "leaf_sepset") { ok = within(0, 1); t.leaf_sepset = num != 0; }
     else if (key == "mixed_fast_min") { ok = within(-1, LLONG_MAX); t.mixed_fast_min = num; }
     else if (key == "small4_min") { ok = within(-1, INT_MAX); t.small4_min = (int)num; }
     else if (key == "chunk_bins") { ok = within(0, INT_MAX); t.chunk_bins = (int)num; }
@@ -307,6 +308,7 @@ static void append_group(const Plan& p, const Traversal& tr, const std::vector<i
       } else {
         f.mode = kFOwn;
       }
+      if (!postorder && en.leafsep) f.pad[3] = 1;   // (only fast-class tasks come through here)
       if (pending) {
         const MsgDesc& x = p.msgs[pending->msg];
         f.mode |= kFPro;
@@ -1085,6 +1087,11 @@ static void build_traversals(const Plan& p, Tree& t, bool prologues) {
           e.edge = i;
           e.seq = n + i;
           e.reuse = 0;
+          {
+            // LEAF SEPSET (FEntry::pad[3]): the receiver only ever sent its whole belief up this edge
+            const MsgDesc& up = p.msgs[msg_to(i, t.pa[i])];
+            e.leafsep = (!nchild.count(t.ch[i]) && up.ni == 0 && up.s == up.mf) ? 1 : 0;
+          }
           if (prev_msg >= 0) {
             const MsgDesc& a = p.msgs[prev_msg];
             const MsgDesc& b = p.msgs[e.msg];
@@ -1491,6 +1498,29 @@ int pgbp_plan_prologues(const pgbp_plan* p, int32_t tree, int32_t dir, int32_t* 
         std::fill(chunk_pro + o, chunk_pro + o + nrec, -1);
       else
         dump(tr->centries, tr->cpros, (size_t)ch.group0 * pgbp::kTailWaves, (size_t)ch.group0 * pgbp::kTailWaves + nrec, chunk_pro + o);
+      o += nrec;
+    }
+  }
+  return PGBP_OK;
+}
+
+int pgbp_plan_leaf_sepset(const pgbp_plan* p, int32_t tree, int32_t dir, int32_t* level_leaf, int32_t* tail_leaf,
+                          int32_t* chunk_leaf) {
+  const pgbp::Traversal* tr = get_trav(p, tree, dir);
+  if (!tr) return PGBP_ERR_INVALID;
+  auto dump = [](const std::vector<pgbp::FEntry>& v, size_t i0, size_t i1, int32_t* out) {
+    for (size_t i = i0; i < i1; ++i) out[i - i0] = v[i].pad[3];
+  };
+  if (level_leaf) dump(tr->fentries, 0, tr->fentries.size(), level_leaf);
+  if (tail_leaf) dump(tr->tentries, 0, tr->tentries.size(), tail_leaf);
+  if (chunk_leaf) {
+    size_t o = 0;
+    for (const auto& ch : tr->chunks) {
+      const size_t nrec = (size_t)ch.n_groups * pgbp::kTailWaves;
+      if (ch.generic)
+        std::fill(chunk_leaf + o, chunk_leaf + o + nrec, 0);
+      else
+        dump(tr->centries, (size_t)ch.group0 * pgbp::kTailWaves, (size_t)ch.group0 * pgbp::kTailWaves + nrec, chunk_leaf + o);
       o += nrec;
     }
   }
