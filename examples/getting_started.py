@@ -272,6 +272,19 @@ def main():
     print(f"  largest lr over all edges at site 0: observed {sc['top_lr'][0]:.2f}, bootstrap 95 % quantile without a shift "
           f"{float(np.quantile(null['max_lr'], 0.95)):.2f} ({B} replicates)")
     batch.clear_optima_lg()
+    # in a real batch every site picks its own clades, so the shifts go in per site (set_clade_shifts_sites_lg: a short list of
+    # (family, delta) per site, no regime map) and the whole forward selection runs for all sites side by side: scan, the
+    # leading clade of each site into its next slot, exact joint refit of the site's deltas, next scan.  alpha and the rate stay
+    # at the plain fit; the bootstrap threshold of the first step is reused for the second (an approximation).
+    batch.assignfactors_lg_(fit0["R"].reshape(ns, 1, 1, 1), Xp[:, :1], model="ou", alpha=fit0["alpha"], theta=fit0["theta"][:, None])
+    sel = P.select_optimum_shifts_sites_lg(batch, prob.schedule[0], 2, float(np.quantile(null["max_lr"], 0.95)))
+    both = sum(sorted(sel["family"][:, s].tolist()) == sorted([k1 - 1, k2 - 1]) for s in range(ns))
+    print(f"forward selection at all {ns} sites at once: {int((sel['n_shifts'] == 2).sum())} sites take two shifts, {both} of them exactly the "
+          f"planted clades below nodes {k1} and {k2}; node: delta at the first four sites: " +
+          "; ".join(", ".join(f"{int(sel['family'][j, s]) + 1}: {sel['delta'][j, s]:+.2f}" for j in range(2) if sel["family"][j, s] >= 0)
+                    for s in range(4)) + f"; log-likelihood of site 0 along the path: " +
+          " -> ".join(f"{v:.2f}" for v in sel["loglik"][:, 0]))
+    batch.clear_clade_shifts_sites_lg()
     batch.lg_setup(synth.lg_tree_table(tr, prob, 1), np.ascontiguousarray(X[:, :, None]))   # (the unpainted batch again)
     # real batches have gaps, another set of unmeasured species at almost every site: a table with NaN at its gaps goes to
     # lg_setup with finite placeholders (split_missing_data) and its gaps to set_site_missing_lg; every site is then fitted to

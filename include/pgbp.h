@@ -745,6 +745,36 @@ int  pgbp_lg_optimum_scan_sites(pgbp_engine* e, int32_t site_begin, int32_t site
 int  pgbp_lg_optimum_scan_sites_timed(pgbp_engine* e, int32_t site_begin, int32_t site_end, double min_info, double* delta,
                                       double* lr, double* information, double* top_lr, int32_t* top_family, int32_t* info,
                                       double* ms4, int32_t* launches);
+/* PER-SITE CLADE SHIFTS OF THE OPTIMUM under OU, for a thread-per-site engine (p = 1, every belief of at most 2 variables, at
+ * least 8 sites, either layout) on a tree with pgbp_lg_set_topology done: the nested-shift parametrisation that
+ * pgbp_lg_optimum_scan_sites scans.  At site s the optimum of every edge of clade(family[j][s]) -- the parent edge of that
+ * family and all edges below it -- gains delta[j][s], j < n_slots; family and delta are [n_slots][n_sites], family -1 marks an
+ * empty slot (its delta is not read).  The optimum of an edge is theta (or its painted value, pgbp_lg_set_optima) plus the
+ * deltas of the site's slots whose clade holds it, added in slot order.  n_slots = 0 clears the setting.
+ * Refused with PGBP_ERR_INVALID, the previous setting left in force: another engine (the wording of
+ * pgbp_lg_set_site_missing), a family with two or more parents, a family out of range, a root-prior family (no parent edge),
+ * a family twice at one site (the reason names site and family), a delta that is not finite; PGBP_ERR_STATE without a table or
+ * a topology.  The setting takes effect at the next fill (pgbp_lg_assignfactors): a correction of its own after the shift and
+ * noise corrections (csrc/pgbp_shift.hip), lanes = sites, over the clusters that hold a family inside some site's clade; a
+ * thread whose site has no slot covering the cluster stores nothing.  Nothing is launched without a setting, and under BM
+ * (wc = 0) it has no effect, byte for byte.  It survives pgbp_lg_set_edges, _set_shifts, _set_optima, _set_tip_noise,
+ * _set_site_missing and _set_data; a new pgbp_lg_setup or pgbp_lg_set_topology clears it.
+ * pgbp_lg_optimum_scan_sites honours it (the next scan finds the next increment).  Every call that refuses painted optima,
+ * and pgbp_lg_gradient, pgbp_lg_gradient_sites and pgbp_lg_gradient_sites_optima, refuse while a setting is in force under OU
+ * (PGBP_ERR_INVALID, before any launch, naming this setter).
+ * _update_: the deltas alone [n_slots][n_sites] into the buffers of the setting in force, without allocation; the families are
+ * not checked again.  _slots: the number of slots in force (0: none; -1: no family table).  _get_: the setting in force.
+ * _score_: for every slot of every site of [site_begin, site_end) the scan's g_v, H_v and Kt_v at that site's own family v --
+ * g the exact derivative of the log-likelihood in delta_j, information the diagonal of the joint information -- as
+ * [n_slots][sites] rows; info [sites] and min_info as in pgbp_lg_optimum_scan_sites, whose frame and height launches it shares.
+ * An empty slot and a failed site are NaN; a slot with H_v <= min_info Kt_v is not identified: information NaN there, as the
+ * scan reports it.  The rows stay in scratch; one thread per (slot, site) picks row family[slot][site]. */
+int  pgbp_lg_set_clade_shifts_sites(pgbp_engine* e, int32_t n_slots, const int32_t* family, const double* delta);
+int  pgbp_lg_update_clade_shifts_sites(pgbp_engine* e, const double* delta);
+int32_t pgbp_lg_clade_shift_slots(pgbp_engine* e);
+int  pgbp_lg_get_clade_shifts_sites(pgbp_engine* e, int32_t* family, double* delta);
+int  pgbp_lg_clade_shift_score_sites(pgbp_engine* e, int32_t site_begin, int32_t site_end, double min_info, double* g,
+                                     double* information, double* kt, int32_t* info);
 /* pgbp_moments, pgbp_sample_posterior and pgbp_lg_impute for the sites of a UNIVARIATE BATCH, lanes = sites
  * (csrc/pgbp_post_uni.hip): what is asked of a fitted batch -- the posterior moments of every belief, joint draws of all
  * ancestral states, the predictions of the tips without data -- in the frame of the three calls above.  Accepted and refused

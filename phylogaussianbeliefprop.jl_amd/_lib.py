@@ -151,6 +151,11 @@ SYMBOLS = {
     "pgbp_loo_scratch_limit": (None, [C.c_int64]),
     "pgbp_lg_shift_scan_sites": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_double, _F64P, _F64P, _F64P, _F64P, _I32P, _I32P]),
     "pgbp_lg_optimum_scan_sites": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_double, _F64P, _F64P, _F64P, _F64P, _I32P, _I32P]),
+    "pgbp_lg_set_clade_shifts_sites": (C.c_int, [_P, C.c_int32, _I32P, _F64P]),
+    "pgbp_lg_update_clade_shifts_sites": (C.c_int, [_P, _F64P]),
+    "pgbp_lg_clade_shift_slots": (C.c_int32, [_P]),
+    "pgbp_lg_get_clade_shifts_sites": (C.c_int, [_P, _I32P, _F64P]),
+    "pgbp_lg_clade_shift_score_sites": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_double, _F64P, _F64P, _F64P, _I32P]),
     "pgbp_lg_optimum_scan_sites_timed": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_double, _F64P, _F64P, _F64P, _F64P, _I32P, _I32P,
                                                    _F64P, _I32P]),
     "pgbp_lg_edge_gradient_sites": (C.c_int, [_P, C.c_int32, C.c_int32, _F64P, _F64P, _F64P, _I32P]),

@@ -1426,6 +1426,84 @@ class ClusterGraphBelief:
         """pgbp_lg_optima_count: the number of regimes in force (0: none)."""
         return int(self._lib.pgbp_lg_optima_count(self._eng))
 
+    def set_clade_shifts_sites_lg(self, family, delta):
+        """pgbp_lg_set_clade_shifts_sites: per-site clade shifts of the OU optimum, the nested-shift parametrisation that
+        optimum_scan_sites_lg scans.  family: int [n_slots, n_sites] (a flat [n_sites] is one slot), -1 = an empty slot;
+        delta: float of the same shape.  At site s the optimum of every edge of clade(family[j, s]) -- that family's parent
+        edge and every edge below it -- gains delta[j, s], on top of theta or the painted value.  Accepted only on a
+        thread-per-site engine (p = 1, every belief of at most 2 variables, at least 8 sites) on a tree with set_topology_lg
+        done.  The call REPLACES the previous setting (no slots clears it); the next assignfactors_lg_ or loglik_lg uses it.
+        The fill, loglik_lg and optimum_scan_sites_lg honour it; moments, samples and posterior covariances read beliefs
+        only; every sweep that raises under painted optima, and gradient_lg / gradient_sites_lg, raise under OU while it is
+        in force.  Under BM it has no effect.  An invalid entry (a family out of range, a root-prior family, a family twice
+        at one site, a delta that is not finite) raises and leaves the previous setting in force."""
+        fam = np.asarray(family, np.int64)
+        if fam.ndim == 1:
+            fam = fam.reshape(1, -1)
+        n_slots = int(fam.shape[0]) if fam.size else 0
+        if n_slots == 0:
+            return self.clear_clade_shifts_sites_lg()
+        if fam.shape != (n_slots, self.n_sites):
+            raise ValueError(f"family: [n_slots, {self.n_sites}] expected, got {fam.shape}")
+        fam = np.ascontiguousarray(fam, np.int32)
+        d = np.ascontiguousarray(np.asarray(delta, np.float64).reshape(n_slots, self.n_sites))
+        _check(self._lib.pgbp_lg_set_clade_shifts_sites(self._eng, n_slots, L.i32p(fam), L.f64p(d)), self._eng)
+
+    def update_clade_shifts_sites_lg(self, delta):
+        """pgbp_lg_update_clade_shifts_sites: new deltas [n_slots, n_sites] for the families in force; nothing is allocated
+        and the families are not checked again (what fit_clade_shifts_sites_lg does at every step).  Takes effect at the
+        next fill; a delta that is not finite raises and leaves the previous values in force."""
+        n_slots = self.clade_shift_slots_lg()
+        if n_slots <= 0:
+            raise L.PgbpError(L.ERR_STATE, "no clade shifts are set (call set_clade_shifts_sites_lg first)")
+        d = np.ascontiguousarray(np.asarray(delta, np.float64).reshape(n_slots, self.n_sites))
+        _check(self._lib.pgbp_lg_update_clade_shifts_sites(self._eng, L.f64p(d)), self._eng)
+
+    def clear_clade_shifts_sites_lg(self):
+        """Remove the per-site clade shifts (pgbp_lg_set_clade_shifts_sites with no slot)."""
+        _check(self._lib.pgbp_lg_set_clade_shifts_sites(self._eng, 0, None, None), self._eng)
+
+    def clade_shift_slots_lg(self):
+        """pgbp_lg_clade_shift_slots: the number of slots in force (0: none)."""
+        return int(self._lib.pgbp_lg_clade_shift_slots(self._eng))
+
+    def clade_shifts_sites_lg(self):
+        """The per-site clade shifts in force: None, or a dict with family int32 [n_slots, n_sites] (-1: empty) and delta
+        [n_slots, n_sites] (0 at an empty slot), as the engine holds them."""
+        n_slots = self.clade_shift_slots_lg()
+        if n_slots <= 0:
+            return None
+        fam = np.zeros((n_slots, self.n_sites), np.int32)
+        d = np.zeros((n_slots, self.n_sites))
+        _check(self._lib.pgbp_lg_get_clade_shifts_sites(self._eng, L.i32p(fam), L.f64p(d)), self._eng)
+        return dict(family=fam, delta=d)
+
+    def clade_shift_score_sites_lg(self, min_info=1e-8):
+        """pgbp_lg_clade_shift_score_sites on the current beliefs: for every slot of every site the score g (the exact
+        derivative of the log-likelihood in that delta), the information H (the diagonal of the joint information) and Kt
+        of optimum_scan_sites_lg at the site's own family, picked on the device -- no [family, site] table is fetched.
+        Returns a dict: g, information, kt [n_slots, n_sites], identified (H finite) and info [n_sites].  An empty slot and
+        a failed site are NaN; a slot with H <= min_info Kt has NaN information, as the scan reports it."""
+        n_slots = self.clade_shift_slots_lg()
+        if n_slots <= 0:
+            raise L.PgbpError(L.ERR_STATE, "no clade shifts are set (call set_clade_shifts_sites_lg first)")
+        n = self.n_sites
+        g = np.zeros((n_slots, n))
+        H = np.zeros((n_slots, n))
+        kt = np.zeros((n_slots, n))
+        info = np.zeros(n, dtype=np.int32)
+        _check(self._lib.pgbp_lg_clade_shift_score_sites(self._eng, 0, n, float(min_info), L.f64p(g), L.f64p(H), L.f64p(kt),
+                                                         L.i32p(info)), self._eng)
+        return dict(g=g, information=H, kt=kt, identified=np.isfinite(H), info=info)
+
+    def loglik_and_clade_shift_score_sites_lg(self, schedule_tree, min_info=1e-8):
+        """The factors filled again (so that the deltas set since the last fill are in) -> one calibrate -> integratebelief!
+        at the root cluster, enqueued as loglik_and_gradient_sites_lg does -> clade_shift_score_sites_lg.  Returns
+        (loglik [n_sites], score dict); a failed site has info != 0 and NaN values."""
+        norm, sc, info = self._loglik_and_sites(schedule_tree, lambda: self.clade_shift_score_sites_lg(min_info=min_info), refill=True)
+        sc["info"] = np.where(sc["info"] != 0, sc["info"], info)
+        return np.where(sc["info"] != 0, np.nan, norm), sc
+
     def set_tip_noise_lg(self, families, sigma_e, scale=None, se2=None):
         """pgbp_lg_set_tip_noise: measurement error at the tips.  The conditional variance of every listed tip family f
         (child_pos < 0 with a data row) gains E_f = scale_f * sigma_e + diag(se2_f): the tip's data row is then an

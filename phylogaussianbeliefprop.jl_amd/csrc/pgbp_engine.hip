@@ -1701,6 +1701,7 @@ static int lg_fill_async(pgbp_engine* e, bool also_factors, bool skip_sepsets = 
   const LgModel& L = *e->lg;
   // the displacement correction: the shifted clusters, or with painted optima in force their union with the painted ones
   const LgOptima Op = L.optima_in_force();
+  const LgCladeShifts Cs = L.clade_in_force();   // per-site clade shifts of the optimum: a correction of their own, after the noise's
   const int32_t* dcl = Op.regime ? L.disp_cl.get() : L.shift_bufs.cl.get();
   const int32_t n_dcl = Op.regime ? L.n_disp_cl : L.n_shift_cl;
   if (e->layout_sm && L.T.uni_ok) {
@@ -1710,7 +1711,10 @@ static int lg_fill_async(pgbp_engine* e, bool also_factors, bool skip_sepsets = 
                            also_factors ? e->sm.fpool.get() : nullptr, e->d_packed_off.get(), e->d_bdim.get(), p.n_sites, e->st);
     launch_lg_noise_uni_sm(L.F, L.M, L.Sh, Op, L.Nz, L.noise_bufs.cl.get(), L.n_noise_cl, e->sm.pool.get(),
                            also_factors ? e->sm.fpool.get() : nullptr, e->d_packed_off.get(), e->d_bdim.get(), p.n_sites, e->st);
-    launch_lg_sitemiss(L.F, L.M, L.Sh, Op, L.Nz, L.Ms, L.miss_bufs.cl.get(), (int)L.miss.cl.size(), 1, e->sm.pool.get(), sm_row(p.n_sites),
+    launch_lg_clade_shift(L.F, L.M, L.Sh, Op, L.Nz, Cs, L.clade_bufs.cl.get(), L.n_clade_cl, 1, e->sm.pool.get(), sm_row(p.n_sites),
+                          also_factors ? e->sm.fpool.get() : nullptr, sm_row(p.n_sites), e->d_packed_off.get(), e->d_bdim.get(),
+                          p.n_sites, e->st);
+    launch_lg_sitemiss(L.F, L.M, L.Sh, Op, L.Nz, L.Ms, Cs, L.miss_bufs.cl.get(), (int)L.miss.cl.size(), 1, e->sm.pool.get(), sm_row(p.n_sites),
                        also_factors ? e->sm.fpool.get() : nullptr, sm_row(p.n_sites), e->d_packed_off.get(), e->d_bdim.get(), p.n_sites,
                        e->st);
     const int64_t nc = p.packed_off[p.n_clusters] * sm_row(p.n_sites), nall = p.packed_off.back() * sm_row(p.n_sites);
@@ -1730,7 +1734,12 @@ static int lg_fill_async(pgbp_engine* e, bool also_factors, bool skip_sepsets = 
                     e->layout_bs16 ? 1 : 0, p.fast_p, L.noise_max_dim, p.n_sites, e->st);
     if (L.Ms.words && e->layout_bs16)   // (a thread-per-site engine is never in the packed layout)
       return e->fail(PGBP_ERR_STATE, "a per-site mask of missing tips is in force but the engine is in the packed layout");
-    launch_lg_sitemiss(L.F, L.M, L.Sh, Op, L.Nz, L.Ms, L.miss_bufs.cl.get(), (int)L.miss.cl.size(), 0, e->d_pool.get(), p.pool_stride(),
+    if (Cs.family && e->layout_bs16)
+      return e->fail(PGBP_ERR_STATE, "per-site clade shifts of the optimum are in force but the engine is in the packed layout");
+    launch_lg_clade_shift(L.F, L.M, L.Sh, Op, L.Nz, Cs, L.clade_bufs.cl.get(), L.n_clade_cl, 0, e->d_pool.get(), p.pool_stride(),
+                          also_factors ? e->d_fpool.get() : nullptr, p.cluster_stride(), e->d_boff.get(), e->d_bdim.get(), p.n_sites,
+                          e->st);
+    launch_lg_sitemiss(L.F, L.M, L.Sh, Op, L.Nz, L.Ms, Cs, L.miss_bufs.cl.get(), (int)L.miss.cl.size(), 0, e->d_pool.get(), p.pool_stride(),
                        also_factors ? e->d_fpool.get() : nullptr, p.cluster_stride(), e->d_boff.get(), e->d_bdim.get(), p.n_sites,
                        e->st);
     if (!skip_sepsets)
@@ -2080,6 +2089,116 @@ int32_t pgbp_lg_site_missing_count(pgbp_engine* e) {
   return e->lg->Ms.words ? (int32_t)std::min<int64_t>(e->lg->miss.count, INT32_MAX) : 0;
 }
 
+// Per-site clade shifts of the optimum: every check (pgbp_cladeshift_host.hpp) before anything changes; new buffers into a local
+// group that the model takes once every copy has been made.  Rows [slot][site] padded to sm_row in both layouts, the padding
+// and the empty slots at family -1 and delta 0.
+static void clade_rows(int32_t n_slots, int n_sites, const int32_t* family, const double* delta, std::vector<int32_t>* fr,
+                       std::vector<double>& dr) {
+  const size_t row = (size_t)sm_row(n_sites), ns = (size_t)n_sites;
+  if (fr) fr->assign((size_t)n_slots * row, -1);
+  dr.assign((size_t)n_slots * row, 0.0);
+  for (size_t j = 0; j < (size_t)n_slots; ++j)
+    for (size_t s = 0; s < ns; ++s) {
+      const int32_t v = family[j * ns + s];
+      if (fr) (*fr)[j * row + s] = v;
+      dr[j * row + s] = v >= 0 ? delta[j * ns + s] : 0.0;
+    }
+}
+
+int pgbp_lg_set_clade_shifts_sites(pgbp_engine* e, int32_t n_slots, const int32_t* family, const double* delta) {
+  DeviceScope device_scope(e);
+  if (!e) return PGBP_ERR_INVALID;
+  const char* fn = "pgbp_lg_set_clade_shifts_sites";
+  if (!e->lg) return e->fail(PGBP_ERR_STATE, std::string(fn) + ": no family table (call pgbp_lg_setup first)");
+  LgModel& L = *e->lg;
+  if (n_slots < 0) return e->fail(PGBP_ERR_INVALID, std::string(fn) + ": negative number of slots");
+  if (n_slots == 0) {   // clear, on any engine with a table (kernels already enqueued may still read the old setting)
+    HIPCHK(e, hipStreamSynchronize(e->st));
+    L.clade_bufs = LgCladeBufs{};
+    L.Cs = LgCladeShifts{};
+    L.clade_family.clear();
+    L.clade_delta.clear();
+    L.n_clade_cl = 0;
+    return PGBP_OK;
+  }
+  // a thread-per-site engine, as the lanes-are-sites sweeps define it (pgbp_sites_host.hpp)
+  const SitesCall c{&L, engine_peek(e), engine_uni_view(e), 0};
+  int rc = sites_accept_engine(e, fn, "pgbp_lg_set_optima: one regime map for all sites", c);
+  if (rc) return rc;
+  if (!L.clade.built) return e->fail(PGBP_ERR_STATE, std::string(fn) + ": no topology (call pgbp_lg_set_topology first)");
+  std::string why;
+  if (!optscan_plan_single_parents(L.optscan, L.T.n_parents.data(), why)) return e->fail(PGBP_ERR_INVALID, std::string(fn) + ": " + why);
+  const int n_sites = e->plan.n_sites;
+  if (!clade_setting_check(L.clade, L.T.n_parents.data(), n_slots, n_sites, family, delta, why))
+    return e->fail(PGBP_ERR_INVALID, std::string(fn) + ": " + why);
+  std::vector<int32_t> cl, fr;
+  std::vector<double> dr;
+  clade_clusters(L.clade, L.T.cluster.data(), n_slots, n_sites, family, cl);
+  const int32_t n_cl = (int32_t)cl.size();
+  if (cl.empty()) cl.push_back(0);
+  clade_rows(n_slots, n_sites, family, delta, &fr, dr);
+  LgCladeBufs B;
+  if ((rc = dev_alloc(e, B.family, fr.size()))) return rc;
+  if ((rc = dev_alloc(e, B.delta, dr.size()))) return rc;
+  if ((rc = dev_alloc(e, B.cl, cl.size()))) return rc;
+  // every buffer exists: the copies, then ONE synchronisation whatever they returned (none may outlive the host vectors)
+  hipError_t herr = hipMemcpyAsync(B.family.get(), fr.data(), fr.size() * sizeof(int32_t), hipMemcpyHostToDevice, e->st);
+  if (herr == hipSuccess) herr = hipMemcpyAsync(B.delta.get(), dr.data(), dr.size() * sizeof(double), hipMemcpyHostToDevice, e->st);
+  if (herr == hipSuccess) herr = hipMemcpyAsync(B.cl.get(), cl.data(), cl.size() * sizeof(int32_t), hipMemcpyHostToDevice, e->st);
+  const hipError_t serr = hipStreamSynchronize(e->st);  // the host buffers may go away; kernels that read the old setting have finished
+  if (herr == hipSuccess) herr = serr;
+  if (herr != hipSuccess) return e->fail(PGBP_ERR_HIP, std::string(fn) + " (upload): " + hipGetErrorString(herr));
+  L.clade_bufs = std::move(B);
+  L.Cs = LgCladeShifts{L.clade_bufs.family.get(), L.clade_bufs.delta.get(), L.d_clade_pre.get(), L.d_clade_last.get(), n_slots,
+                       sm_row(n_sites)};
+  const size_t n = (size_t)n_slots * (size_t)n_sites;
+  L.clade_family.assign(family, family + n);
+  L.clade_delta.assign(delta, delta + n);
+  for (size_t i = 0; i < n; ++i)
+    if (family[i] < 0) L.clade_delta[i] = 0.0;
+  L.n_clade_cl = n_cl;
+  return PGBP_OK;
+}
+
+// The values alone, into the buffers of the setting in force: what a refit moves at every step.  The families, the cluster list
+// and the buffers stay; every check before anything changes.
+int pgbp_lg_update_clade_shifts_sites(pgbp_engine* e, const double* delta) {
+  DeviceScope device_scope(e);
+  if (!e) return PGBP_ERR_INVALID;
+  const char* fn = "pgbp_lg_update_clade_shifts_sites";
+  if (!e->lg) return e->fail(PGBP_ERR_STATE, std::string(fn) + ": no family table (call pgbp_lg_setup first)");
+  LgModel& L = *e->lg;
+  if (!L.Cs.family) return e->fail(PGBP_ERR_STATE, std::string(fn) + ": no clade shifts are set (call pgbp_lg_set_clade_shifts_sites first)");
+  const int n_sites = e->plan.n_sites;
+  std::string why;
+  if (!clade_values_check(L.Cs.n_slots, n_sites, L.clade_family.data(), delta, why))
+    return e->fail(PGBP_ERR_INVALID, std::string(fn) + ": " + why);
+  std::vector<double> dr;
+  clade_rows(L.Cs.n_slots, n_sites, L.clade_family.data(), delta, nullptr, dr);
+  hipError_t herr = hipStreamSynchronize(e->st);   // kernels that read the old values have finished
+  if (herr == hipSuccess) herr = hipMemcpyAsync(L.clade_bufs.delta.get(), dr.data(), dr.size() * sizeof(double), hipMemcpyHostToDevice, e->st);
+  const hipError_t serr = hipStreamSynchronize(e->st);   // the host buffer may go away
+  if (herr == hipSuccess) herr = serr;
+  if (herr != hipSuccess) return e->fail(PGBP_ERR_HIP, std::string(fn) + " (upload): " + hipGetErrorString(herr));
+  const size_t n = (size_t)L.Cs.n_slots * (size_t)n_sites;
+  for (size_t i = 0; i < n; ++i) L.clade_delta[i] = L.clade_family[i] >= 0 ? delta[i] : 0.0;
+  return PGBP_OK;
+}
+
+int32_t pgbp_lg_clade_shift_slots(pgbp_engine* e) {
+  if (!e || !e->lg) return -1;
+  return e->lg->Cs.family ? e->lg->Cs.n_slots : 0;
+}
+
+int pgbp_lg_get_clade_shifts_sites(pgbp_engine* e, int32_t* family, double* delta) {
+  if (!e) return PGBP_ERR_INVALID;
+  if (!e->lg) return e->fail(PGBP_ERR_STATE, "pgbp_lg_get_clade_shifts_sites: no family table (call pgbp_lg_setup first)");
+  const LgModel& L = *e->lg;
+  if (family) std::copy(L.clade_family.begin(), L.clade_family.end(), family);
+  if (delta) std::copy(L.clade_delta.begin(), L.clade_delta.end(), delta);
+  return PGBP_OK;
+}
+
 int pgbp_lg_set_topology(pgbp_engine* e, const int32_t* parent_family) {
   DeviceScope device_scope(e);
   if (!e) return PGBP_ERR_INVALID;
@@ -2100,16 +2219,34 @@ int pgbp_lg_set_topology(pgbp_engine* e, const int32_t* parent_family) {
   OptScanPlan os;
   if (!optscan_plan_build(nf, K, L.T.n_parents.data(), parent_family, os, why))
     return e->fail(PGBP_ERR_INVALID, "pgbp_lg_set_topology: " + why);
+  // the preorder ranks of the family tree: membership in a clade for pgbp_lg_set_clade_shifts_sites
+  CladePlan cp;
+  if (!clade_plan_build(nf, K, L.T.n_parents.data(), parent_family, cp, why))
+    return e->fail(PGBP_ERR_INVALID, "pgbp_lg_set_topology: " + why);
+  std::vector<int32_t> cp_pre = cp.pre, cp_last = cp.last;
+  if (cp_pre.empty()) { cp_pre.push_back(0); cp_last.push_back(0); }
   std::vector<int32_t> os_cf = os.child_fam, os_hf = os.height_fam;
   if (os_cf.empty()) os_cf.push_back(0);
   if (os_hf.empty()) os_hf.push_back(0);
-  DevBuf<int32_t> d_pf, d_lf, d_co, d_cf, d_hf;
+  DevBuf<int32_t> d_pf, d_lf, d_co, d_cf, d_hf, d_cpre, d_clast;
   int rc;
+  if ((rc = upload(e, d_cpre, cp_pre))) return rc;
+  if ((rc = upload(e, d_clast, cp_last))) return rc;
   if ((rc = upload(e, d_pf, pf))) return rc;
   if ((rc = upload(e, d_lf, level_fam))) return rc;
   if ((rc = upload(e, d_co, os.child_off))) return rc;
   if ((rc = upload(e, d_cf, os_cf))) return rc;
   if ((rc = upload(e, d_hf, os_hf))) return rc;
+  // a setting of clade shifts names families by the ranks of the topology it was checked against: a new one clears it
+  HIPCHK(e, hipStreamSynchronize(e->st));
+  L.clade_bufs = LgCladeBufs{};
+  L.Cs = LgCladeShifts{};
+  L.clade_family.clear();
+  L.clade_delta.clear();
+  L.n_clade_cl = 0;
+  L.clade = std::move(cp);
+  L.d_clade_pre = std::move(d_cpre);
+  L.d_clade_last = std::move(d_clast);
   L.optscan = std::move(os);
   L.d_os_child_off = std::move(d_co);
   L.d_os_child_fam = std::move(d_cf);

@@ -248,6 +248,7 @@ static int lg_gradient(pgbp_engine* e, int32_t site_begin, int32_t site_end, dou
   const LgModel* L = nullptr;
   int rc = lg_sweep_state(e, "pgbp_lg_gradient", site_begin, site_end, &L, "pgbp_lg_gradient_sites");
   if (rc) return rc;
+  if ((rc = lg_refuse_clade_shifts(e, "pgbp_lg_gradient", L))) return rc;
   const LgStatic& F = L->F;
   const LgParams& M = L->M;
   const LgShifts& Sh = L->Sh;

@@ -259,6 +259,7 @@ static int lg_gradient_sites(pgbp_engine* e, const char* fn, int32_t site_begin,
   int rc = sites_accept_state(e, fn, site_begin, site_end, &c);
   if (rc) return rc;
   const LgModel* L = c.L;
+  if ((rc = lg_refuse_clade_shifts(e, fn, L))) return rc;   // (grad_uni_family does not know the per-site membership)
   const LgOptima Op = L->optima_in_force();
   const int nopt = Op.regime ? Op.n : 0, nopt_out = L->Op.regime ? L->Op.n : 0;
   // painted optima change dtheta and dalpha: a caller that cannot take doptima would read them as the unpainted model's

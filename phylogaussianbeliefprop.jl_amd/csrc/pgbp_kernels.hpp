@@ -223,6 +223,17 @@ struct LgOptima {
   int32_t per_site, n;
   const double* value_sm;  // univariate per-site batches: the values once more as [n][site] (rows padded: sm_row), else null
 };
+// Per-site clade shifts of the optimum under OU (pgbp_lg_set_clade_shifts_sites): at site s the optimum of every edge of
+// clade(family[j][s]) gains delta[j][s], j < n_slots.  A struct of its own, which only the lanes-are-sites kernels of a
+// thread-per-site engine take: LgOptima and the kernels of the general engine stay as they are.  family == null: none in force
+// (none set, or the model is BM).  pre / last: preorder rank of a family and the largest rank in its clade (CladePlan).
+struct LgCladeShifts {
+  const int32_t* family;   // [n_slots][row], -1: an empty slot (the padding of a row too)
+  const double* delta;     // [n_slots][row]
+  const int32_t *pre, *last;
+  int32_t n_slots;
+  int64_t row;             // sm_row(n_sites), in both layouts
+};
 // the correction of a fill for the displacements -- shifts and painted optima (pgbp_shift.hip) --, launched right after it: one
 // workgroup per (cluster of d_shcl, site) adds Delta h and Delta g to the records in pool and, when not null, fpool (current
 // layout).  d_shcl: the clusters that hold a shifted or a painted family
@@ -265,9 +276,16 @@ struct LgSiteMiss {
 // families; every other thread stores nothing.  sm != 0: the site-minor layout (off: packed offsets, stride / fstride: the row
 // length), else the plain one (off: Plan::boff, stride / fstride: doubles per site of pool / fpool)
 void launch_lg_sitemiss(const LgStatic& F, const LgParams& M, const LgShifts& S, const LgOptima& Op, const LgNoise& Nz,
-                        const LgSiteMiss& Ms,
+                        const LgSiteMiss& Ms, const LgCladeShifts& Cs,
                         const int32_t* d_mcl, int n_mcl, int sm, double* pool, int64_t stride, double* fpool, int64_t fstride,
                         const int64_t* d_off, const int32_t* d_dim, int n_sites, hipStream_t st);
+// the correction of a fill for the per-site clade shifts (pgbp_shift.hip), launched after the shift and the noise corrections and before the mask's:
+// lanes = sites, one row of workgroups per cluster of d_ccl (the clusters that hold a family inside some site's clade); a thread
+// whose site has a slot covering a family of the cluster adds Delta h and Delta g to the record in pool and, when not null,
+// fpool; every other thread stores nothing.  sm, off, stride, fstride: as launch_lg_sitemiss takes them
+void launch_lg_clade_shift(const LgStatic& F, const LgParams& M, const LgShifts& S, const LgOptima& Op, const LgNoise& Nz,
+                           const LgCladeShifts& Cs, const int32_t* d_ccl, int n_ccl, int sm, double* pool, int64_t stride,
+                           double* fpool, int64_t fstride, const int64_t* d_off, const int32_t* d_dim, int n_sites, hipStream_t st);
 // the setter's own step: 0.0 into data [site][row] and data_sm [row][site] at every masked entry
 void launch_lg_sitemiss_zero(const LgSiteMiss& Ms, double* data, double* data_sm, int n_rows, int n_sites, hipStream_t st);
 // one workgroup per (cluster, site); pool / fpool in the current layout (fpool may be null: beliefs only)

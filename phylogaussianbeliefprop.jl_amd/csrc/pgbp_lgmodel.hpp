@@ -8,6 +8,7 @@
 #include "pgbp_devmem.hpp"
 #include "pgbp_kernels.hpp"
 #include "pgbp_lgtable.hpp"
+#include "pgbp_cladeshift_host.hpp"
 #include "pgbp_optscan_host.hpp"
 #include "pgbp_sitemiss_host.hpp"
 
@@ -41,6 +42,12 @@ struct LgNoiseBufs {
 struct LgSiteMissBufs {
   DevBuf<unsigned long long> words;
   DevBuf<int32_t> cl;
+};
+
+// what LgCladeShifts points at (pgbp_lg_set_clade_shifts_sites), and the clusters the correction kernel visits
+struct LgCladeBufs {
+  DevBuf<int32_t> family, cl;
+  DevBuf<double> delta;
 };
 
 struct LgModel {
@@ -79,6 +86,18 @@ struct LgModel {
   // child lists and the families by height, on the host and on the device
   OptScanPlan optscan;
   DevBuf<int32_t> d_os_child_off, d_os_child_fam, d_os_height_fam;
+  // the preorder ranks of the family tree, built and uploaded with the topology (pgbp_cladeshift_host.hpp), and
+  // pgbp_lg_set_clade_shifts_sites: Cs.family == null: none; the setting on the host as [slot][site] (clade_family, clade_delta)
+  // and the number of clusters that hold a family inside some site's clade (clade_bufs.cl)
+  CladePlan clade;
+  DevBuf<int32_t> d_clade_pre, d_clade_last;
+  LgCladeBufs clade_bufs;
+  LgCladeShifts Cs{};
+  std::vector<int32_t> clade_family;
+  std::vector<double> clade_delta;
+  int32_t n_clade_cl = 0;
+  // the clade shifts as the kernels take them: none under BM, where wc = 0 and they have no effect
+  LgCladeShifts clade_in_force() const { return (Cs.family && M.model == PGBP_LG_OU) ? Cs : LgCladeShifts{}; }
 };
 
 // the model of the engine's family table, null when there is none (defined in pgbp_engine.hip)
@@ -104,7 +123,15 @@ inline int lg_sweep_state(pgbp_engine* e, const char* fn, int32_t site_begin, in
 
 // A sweep `fn` that forms the families' offsets itself and does not know painted optima (pgbp_lg_set_optima): refused while
 // they are in force under OU, before any launch; PGBP_OK otherwise (under BM the optima have no effect).
+// The same for a sweep that does not know the per-site clade shifts of the optimum (pgbp_lg_set_clade_shifts_sites)
+inline int lg_refuse_clade_shifts(pgbp_engine* e, const char* fn, const LgModel* L) {
+  if (!L || !L->clade_in_force().family) return PGBP_OK;
+  return engine_fail(e, PGBP_ERR_INVALID, std::string(fn) + ": per-site clade shifts of the optimum are in force (pgbp_lg_set_clade_shifts_sites: " +
+                                              std::to_string(L->Cs.n_slots) + " slots), which this sweep does not honour; it would "
+                                              "return the answer without them");
+}
 inline int lg_refuse_optima(pgbp_engine* e, const char* fn, const LgModel* L) {
+  if (const int rc = lg_refuse_clade_shifts(e, fn, L)) return rc;
   if (!L || !L->optima_in_force().regime) return PGBP_OK;
   return engine_fail(e, PGBP_ERR_INVALID, std::string(fn) + ": painted optima are in force (pgbp_lg_set_optima: " + std::to_string(L->Op.n) +
                                               " regimes), which this sweep does not honour yet; it would return the unpainted answer");

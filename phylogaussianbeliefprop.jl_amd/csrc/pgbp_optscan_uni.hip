@@ -41,9 +41,11 @@ namespace pgbp {
 // fams[q], q < n: the families of this height.  child_off / child_fam: the child families of a family, in index order.
 // bad[site] != 0: a failed site, NaN throughout.  state: [n_fam][4][row]; delta, lr, hinf, cand: [n_fam][row] (any may be null);
 // cand: lr where the family is identified and lr is finite, NaN elsewhere
-template <bool SM>
+// CS: the instance that also reads the per-site clade shifts of the optimum (pgbp_lg_set_clade_shifts_sites); without it the
+// kernel is the scan's own, as it was
+template <bool SM, bool CS>
 __global__ __launch_bounds__(256) void optscan_level(SitesArgs A, LgStatic F, LgParams M, LgShifts Sh, LgOptima Op, LgNoise Nz,
-                                                     LgSiteMiss Ms, const int32_t* __restrict__ fams, int n,
+                                                     LgSiteMiss Ms, LgCladeShifts Cs, const int32_t* __restrict__ fams, int n,
                                                      const int32_t* __restrict__ child_off, const int32_t* __restrict__ child_fam,
                                                      const int32_t* __restrict__ bad, double min_info, double* __restrict__ state,
                                                      double* __restrict__ delta, double* __restrict__ lr,
@@ -71,7 +73,11 @@ __global__ __launch_bounds__(256) void optscan_level(SitesArgs A, LgStatic F, Lg
       } else {
         const FamUniParent P = fam_uni_parent(F, M, S, X.q, f, 0, S.mu[0]);
         const double dopt = Op.regime ? lg_optima_d(Op, theta, S.alpha, F.length, F.gamma, f, F.K, X.np, 0, 1, as, A.data_row_len) : 0.0;
-        const double e = X.e - dopt;
+        double e = X.e - dopt;
+        if (CS) {   // the offset gains wc_f times this site's deltas that cover f
+          bool any;
+          e = e - P.wc * lg_clade_sum(Cs, f, as, any);
+        }
         const double kap = P.wc * X.j;
         double B = 0.0, Sv = 0.0, G = 0.0, K = 0.0;
         for (int c = child_off[f], c1 = child_off[f + 1]; c < c1; ++c) {
@@ -128,6 +134,29 @@ __global__ __launch_bounds__(256) void optscan_level(SitesArgs A, LgStatic F, Lg
   }
 }
 
+// The score at a site's own slots (pgbp_lg_clade_shift_score_sites): thread = (slot, site) picks row family[slot][site] of the
+// scan's state (g: row 2, Kt: row 3) and of its information table.  An empty slot and a failed site are NaN; a slot that is not
+// identified has NaN information, as in the scan.  g, h, kt: [n_slots][row]
+__global__ __launch_bounds__(256) void optscan_gather_slots(LgCladeShifts Cs, int site0, int n_sites, int64_t row,
+                                                            const int32_t* __restrict__ bad, const double* __restrict__ state,
+                                                            const double* __restrict__ hinf, double* __restrict__ g,
+                                                            double* __restrict__ h, double* __restrict__ kt) {
+  const int s = blockIdx.x * 256 + threadIdx.x, j = blockIdx.y;
+  if (s >= n_sites) return;
+  const int v = Cs.family[(int64_t)j * Cs.row + site0 + s];
+  double gv = NAN, hv = NAN, kv = NAN;
+  if (v >= 0 && bad[s] == 0) {
+    const double* __restrict__ t = state + (int64_t)v * 4 * row + s;
+    gv = t[2 * row];
+    kv = t[3 * row];
+    hv = hinf[(int64_t)v * row + s];
+  }
+  const int64_t o = (int64_t)j * row + s;
+  g[o] = gv;
+  h[o] = hv;
+  kt[o] = kv;
+}
+
 // pbest / pfam: [blocks][row], the largest candidate of the block's families and the first family that has it (-inf, -1: none)
 __global__ __launch_bounds__(256) void optscan_top(const double* __restrict__ cand, int n_fam, int n_sites, int64_t row,
                                                    double* __restrict__ pbest, int32_t* __restrict__ pfam) {
@@ -175,10 +204,11 @@ using namespace pgbp;
 // ms[0 .. 3] = {validity pass, height launches, top fold, copies}; launches: the number of height launches of the call
 static int optimum_scan_sites(pgbp_engine* e, const char* fn, int32_t site_begin, int32_t site_end, double min_info, double* delta,
                               double* lr, double* information, double* top_lr, int32_t* top_family, int32_t* info, double* ms,
-                              int32_t* launches) {
+                              int32_t* launches, double* slot_g = nullptr, double* slot_h = nullptr, double* slot_kt = nullptr) {
   if (!e) return PGBP_ERR_INVALID;
   SitesCall c{};
-  const bool none = !delta && !lr && !information && !top_lr && !top_family;
+  const bool score = slot_g || slot_h || slot_kt;   // pgbp_lg_clade_shift_score_sites: the rows of every site's own slots
+  const bool none = !score && !delta && !lr && !information && !top_lr && !top_family;
   int rc = sites_accept(e, fn, "pgbp_lg_set_optima and two pgbp_loglik per clade", site_begin, site_end, none ? "no output buffer" : nullptr, &c);
   if (rc) return rc;
   const LgModel* L = c.L;
@@ -201,8 +231,13 @@ static int optimum_scan_sites(pgbp_engine* e, const char* fn, int32_t site_begin
   const PostUniPre pre = post_uni_pre(sp);
   const int nfb = std::max(1, (nf + kFamUniBlock - 1) / kFamUniBlock);
   const bool top = top_lr || top_family;
-  const int n_tab = (delta ? 1 : 0) + (lr ? 1 : 0) + (information ? 1 : 0);
-  const int64_t per_site = optscan_per_site(nf, n_tab, top, nfb, pre.nvb);
+  const LgCladeShifts Cs = L->clade_in_force();
+  if (score && !Cs.family)
+    return engine_fail(e, PGBP_ERR_STATE, std::string(fn) + ": no clade shifts are in force (call pgbp_lg_set_clade_shifts_sites first)");
+  const int n_slots = score ? Cs.n_slots : 0;
+  const bool want_h = information || score;
+  const int n_tab = (delta ? 1 : 0) + (lr ? 1 : 0) + (want_h ? 1 : 0);
+  const int64_t per_site = optscan_per_site(nf, n_tab, top, nfb, pre.nvb) + 3 * (int64_t)n_slots;
   const int64_t limit = g_fam_uni_limit.load();
   if (256 * per_site > limit)
     return engine_fail(e, PGBP_ERR_INVALID, std::string(fn) + ": the state rows and the requested tables of one workgroup of 256 sites take " +
@@ -216,7 +251,7 @@ static int optimum_scan_sites(pgbp_engine* e, const char* fn, int32_t site_begin
   std::vector<int32_t> rank(ns, 0);
   DevBuf<SampItem> d_tab;
   DevBuf<int32_t> d_idx, d_pfirst, d_rank, d_fcl, d_pfam, d_topf;
-  DevBuf<double> d_state, d_delta, d_lr, d_hinf, d_cand, d_pbest, d_top;
+  DevBuf<double> d_state, d_delta, d_lr, d_hinf, d_cand, d_pbest, d_top, d_sg, d_sh, d_sk;
   const size_t tab = (size_t)std::max(1, nf) * chunk, blk = (size_t)nfb * chunk;
   SitesScratch S(e, fn, c.v.st);
   S.alloc(d_tab, std::max<size_t>(1, pre.tab.size()));
@@ -227,7 +262,10 @@ static int optimum_scan_sites(pgbp_engine* e, const char* fn, int32_t site_begin
   S.alloc(d_state, 4 * tab);
   S.alloc(d_delta, tab, delta != nullptr);
   S.alloc(d_lr, tab, lr != nullptr);
-  S.alloc(d_hinf, tab, information != nullptr);
+  S.alloc(d_hinf, tab, want_h);
+  S.alloc(d_sg, (size_t)std::max(1, n_slots) * chunk, score);
+  S.alloc(d_sh, (size_t)std::max(1, n_slots) * chunk, score);
+  S.alloc(d_sk, (size_t)std::max(1, n_slots) * chunk, score);
   S.alloc(d_cand, tab, top);
   S.alloc(d_pbest, blk, top);
   S.alloc(d_pfam, blk, top);
@@ -253,11 +291,22 @@ static int optimum_scan_sites(pgbp_engine* e, const char* fn, int32_t site_begin
     for (int h = 0; h < nh; ++h) {
       const int nq = P.height_off[h + 1] - P.height_off[h];
       if (nq == 0) continue;
-      PGBP_SITES_LAUNCH(S, c.U.sm, optscan_level, dim3(gs.x, std::min(nq, 65535)), A, L->F, L->M, L->Sh, Op, L->Nz, L->Ms,
-                        L->d_os_height_fam.get() + P.height_off[h], nq, L->d_os_child_off.get(), L->d_os_child_fam.get(),
-                        d_rank.get() + s0, min_info, d_state.get(), d_delta.get(), d_lr.get(), d_hinf.get(), d_cand.get());
+      const dim3 gl(gs.x, std::min(nq, 65535));
+#define PGBP_OPTSCAN_LEVEL(SM_, CS_)                                                                                              \
+  S.launch(optscan_level<SM_, CS_>, gl, A, L->F, L->M, L->Sh, Op, L->Nz, L->Ms, Cs, L->d_os_height_fam.get() + P.height_off[h], \
+           nq, L->d_os_child_off.get(), L->d_os_child_fam.get(), d_rank.get() + s0, min_info, d_state.get(), d_delta.get(),     \
+           d_lr.get(), d_hinf.get(), d_cand.get())
+      if (Cs.family) {
+        if (c.U.sm) PGBP_OPTSCAN_LEVEL(true, true); else PGBP_OPTSCAN_LEVEL(false, true);
+      } else {
+        if (c.U.sm) PGBP_OPTSCAN_LEVEL(true, false); else PGBP_OPTSCAN_LEVEL(false, false);
+      }
+#undef PGBP_OPTSCAN_LEVEL
       ++n_launch;
     }
+    if (score)
+      S.launch(optscan_gather_slots, dim3(gs.x, n_slots), Cs, site_begin + s0, n, (int64_t)chunk, d_rank.get() + s0, d_state.get(),
+               d_hinf.get(), d_sg.get(), d_sh.get(), d_sk.get());
     S.check();
     phase(1);
     if (top) {
@@ -270,6 +319,9 @@ static int optimum_scan_sites(pgbp_engine* e, const char* fn, int32_t site_begin
     S.rows(delta, ns, s0, d_delta.get(), chunk, n, nf);
     S.rows(lr, ns, s0, d_lr.get(), chunk, n, nf);
     S.rows(information, ns, s0, d_hinf.get(), chunk, n, nf);
+    S.rows(slot_g, ns, s0, d_sg.get(), chunk, n, n_slots);
+    S.rows(slot_h, ns, s0, d_sh.get(), chunk, n, n_slots);
+    S.rows(slot_kt, ns, s0, d_sk.get(), chunk, n, n_slots);
     phase(3);
   }
   S.download(rank.data(), d_rank.get(), ns);
@@ -294,4 +346,12 @@ extern "C" int pgbp_lg_optimum_scan_sites_timed(pgbp_engine* e, int32_t site_beg
   if (e && !ms4) return engine_fail(e, PGBP_ERR_INVALID, "pgbp_lg_optimum_scan_sites_timed: no buffer for the phase times");
   return optimum_scan_sites(e, "pgbp_lg_optimum_scan_sites_timed", site_begin, site_end, min_info, delta, lr, information, top_lr,
                             top_family, info, ms4, launches);
+}
+
+extern "C" int pgbp_lg_clade_shift_score_sites(pgbp_engine* e, int32_t site_begin, int32_t site_end, double min_info, double* g,
+                                               double* information, double* kt, int32_t* info) {
+  if (e && (!g || !information || !kt))
+    return engine_fail(e, PGBP_ERR_INVALID, "pgbp_lg_clade_shift_score_sites: no output buffer");
+  return optimum_scan_sites(e, "pgbp_lg_clade_shift_score_sites", site_begin, site_end, min_info, nullptr, nullptr, nullptr, nullptr,
+                            nullptr, info, nullptr, nullptr, g, information, kt);
 }

@@ -21,6 +21,8 @@
 #include "pgbp_bs16.hpp"
 #include "pgbp_fam_dev.hpp"
 #include "pgbp_kernels.hpp"
+#include "pgbp_noise_dev.hpp"
+#include "pgbp_shift_dev.hpp"
 
 namespace pgbp {
 
@@ -226,6 +228,80 @@ __global__ __launch_bounds__(256) void shift_uni_sm_kernel(LgStatic F, LgParams 
   }
 }
 
+// Per-site clade shifts of the optimum (pgbp_lg_set_clade_shifts_sites), on a thread-per-site engine in either layout: lanes =
+// sites, a workgroup is 256 consecutive sites, grid.y runs over the clusters that hold a family inside some site's clade (the
+// setter's list).  It runs after the shift and the noise corrections, so the factor of family f already stands at the offset
+// z (shifts and painted optima included) and the variance V (+ E_f of a noisy tip); the clade's displacement
+// delta = wc_f sum_j delta_j [f in clade(v_j)] (lg_clade_d) moves it by
+//     Delta h_a = c_a j delta,   Delta g = -(delta j z + delta j delta / 2),   j = 1 / V,
+// the statement of shift_uni_sm_kernel with the noisy variance.  A thread whose site has no slot covering a family of the
+// cluster stores nothing; a record the per-site mask rewrites afterwards (pgbp_sitemiss.hip) is recomputed there with the same
+// displacement.  One writer per record, no atomics, no barrier, contraction off, every sum in table order.
+template <bool SM>
+__global__ __launch_bounds__(256) void clade_shift_kernel(LgStatic F, LgParams M, LgShifts Sh, LgOptima Op, LgNoise Nz,
+                                                          LgCladeShifts Cs, const int32_t* __restrict__ ccl,
+                                                          double* __restrict__ pool, int64_t stride, double* __restrict__ fpool,
+                                                          int64_t fstride, const int64_t* __restrict__ off,
+                                                          const int32_t* __restrict__ dim, int n_sites) {
+#pragma clang fp contract(off)
+  const int site = blockIdx.x * 256 + threadIdx.x;
+  if (site >= n_sites) return;   // (no barrier follows, and no other lane's store is this lane's to make)
+  const int c = ccl[blockIdx.y];
+  const int K = F.K;
+  const int64_t ps = M.per_site ? site : 0;
+  const double* __restrict__ R = M.R + ps * F.n_rates;
+  const double mu = M.mu[ps], theta = M.theta ? M.theta[ps] : 0.0, alpha = M.alpha[ps];   // (launched under OU only)
+  const int64_t drow = Cs.row;
+  const int m = dim[c];
+  double dh0 = 0.0, dh1 = 0.0, dg = 0.0;
+  bool touched = false;
+  for (int fi = F.cl_off[c]; fi < F.cl_off[c + 1]; ++fi) {
+    const int f = F.cl_fam[fi];
+    const int np = F.n_parents[f], cpos = F.child_pos[f];
+    if (np == 0) continue;                                       // a root-prior family has no edge
+    if (F.child_mask && !(F.child_mask[f] & 1ull)) continue;     // the factor is 1: nothing to displace
+    bool any = false;
+    const double d = lg_clade_d(Cs, alpha, F.length, F.gamma, f, K, np, site, any);
+    if (!any) continue;
+    touched = true;
+    double V = 0.0, z = 0.0;
+    for (int k = 0; k < np; ++k) {
+      double qc, vc, wc;
+      lg_coefs<true>(M.model, alpha, F.length[(int64_t)f * K + k], F.gamma[(int64_t)f * K + k], qc, vc, wc);
+      V = V + vc * R[F.color[(int64_t)f * K + k]];
+      z = z + wc * theta;
+      if (F.parent_pos[(int64_t)f * K + k] < 0) z = z + qc * mu;   // the fixed root
+    }
+    z = z + lg_disp_d(Sh, Op, &theta, alpha, F.length, F.gamma, f, K, np, 0, 1, site, drow);
+    if (cpos < 0) z = z - F.data_sm[(int64_t)F.data_row[f] * drow + site];   // a tip: its value
+    const int sn = lg_noise_slot(Nz, f);
+    if (sn >= 0) V = V + lg_noise_E(Nz, sn, 0, 0, 1, site);        // a noisy tip: V + E
+    const double j = 1.0 / V;
+    dg = dg + -((d * j) * z + 0.5 * ((d * j) * d));
+    for (int a = 0; a <= np; ++a) {   // in-scope nodes: at most two
+      const int pa = a == 0 ? cpos : F.parent_pos[(int64_t)f * K + a - 1];
+      if (pa < 0) continue;
+      double ca = 1.0, vc, wc;
+      if (a > 0) {
+        lg_coefs<true>(M.model, alpha, F.length[(int64_t)f * K + a - 1], F.gamma[(int64_t)f * K + a - 1], ca, vc, wc);
+        ca = -ca;
+      }
+      if (pa == 0) dh0 = dh0 + (ca * j) * d;
+      else dh1 = dh1 + (ca * j) * d;
+    }
+  }
+  if (!touched) return;              // this (cluster, site) keeps the bytes it has
+  // [J (m*m) | h (m) | g] of the cluster: element t of site s at (off + t) * stride + s, or at s * stride + off + t
+  const int64_t o = off[c] + (int64_t)m * m;
+  for (int t = 0; t <= m; ++t) {
+    const double add = t == m ? dg : (t == 0 ? dh0 : dh1);
+    const int64_t at = SM ? (o + t) * stride + site : (int64_t)site * stride + o + t;
+    const double v = pool[at] + add;
+    pool[at] = v;
+    if (fpool) fpool[SM ? (o + t) * fstride + site : (int64_t)site * fstride + o + t] = v;
+  }
+}
+
 void launch_lg_shift(const LgStatic& F, const LgParams& M, const LgShifts& S, const LgOptima& Op, const int32_t* d_shcl,
                      int n_shcl, double* pool,
                      int64_t pool_stride, double* fpool, int64_t fpool_stride, const int64_t* d_boff, const int32_t* d_dim,
@@ -260,6 +336,22 @@ void launch_lg_shift_uni_sm(const LgStatic& F, const LgParams& M, const LgShifts
   else
     hipLaunchKernelGGL(shift_uni_sm_kernel<false>, dim3(n_shcl, (n_sites + bs - 1) / bs), dim3(bs), 0, st, F, M, S, Op, d_shcl, pool_sm,
                        fpool_sm, d_poff, d_dim, n_sites);
+}
+
+void launch_lg_clade_shift(const LgStatic& F, const LgParams& M, const LgShifts& S, const LgOptima& Op, const LgNoise& Nz,
+                           const LgCladeShifts& Cs, const int32_t* d_ccl, int n_ccl, int sm, double* pool, int64_t stride,
+                           double* fpool, int64_t fstride, const int64_t* d_off, const int32_t* d_dim, int n_sites, hipStream_t st) {
+  if (n_ccl <= 0 || !Cs.family) return;
+  const int gx = (n_sites + 255) / 256;
+  for (int c0 = 0; c0 < n_ccl; c0 += 65535) {   // (grid.y is 16 bits wide)
+    const dim3 grid(gx, n_ccl - c0 < 65535 ? n_ccl - c0 : 65535);
+    if (sm)
+      hipLaunchKernelGGL(clade_shift_kernel<true>, grid, dim3(256), 0, st, F, M, S, Op, Nz, Cs, d_ccl + c0, pool, stride, fpool,
+                         fstride, d_off, d_dim, n_sites);
+    else
+      hipLaunchKernelGGL(clade_shift_kernel<false>, grid, dim3(256), 0, st, F, M, S, Op, Nz, Cs, d_ccl + c0, pool, stride, fpool,
+                         fstride, d_off, d_dim, n_sites);
+  }
 }
 
 }  // namespace pgbp

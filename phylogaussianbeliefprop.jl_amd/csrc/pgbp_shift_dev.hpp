@@ -66,6 +66,43 @@ __device__ __forceinline__ double lg_optima_d(const LgOptima& Op, const double* 
   return d;
 }
 
+// Per-site clade shifts of the optimum (pgbp_lg_set_clade_shifts_sites): the sum of the deltas of this site's slots whose
+// clade holds family f -- pre[v_j] <= pre[f] <= last[v_j] -- added in slot order.  any: does a slot cover f at all?
+__device__ __forceinline__ double lg_clade_sum(const LgCladeShifts& C, int64_t f, int64_t site, bool& any) {
+#pragma clang fp contract(off)
+  double s = 0.0;
+  bool hit = false;
+  if (C.family) {
+    const int r = C.pre[f];
+    for (int j = 0; j < C.n_slots; ++j) {
+      const int v = C.family[(int64_t)j * C.row + site];
+      if (v < 0) continue;
+      if (C.pre[v] <= r && r <= C.last[v]) {
+        s = s + C.delta[(int64_t)j * C.row + site];
+        hit = true;
+      }
+    }
+  }
+  any = hit;
+  return s;
+}
+
+// d_clade = sum_k wc_k times that sum over the parent edges of family f (one on a tree), wc_k as lg_coefs forms it: what the
+// offset w of family f gains at this site; 0 without a setting
+__device__ __forceinline__ double lg_clade_d(const LgCladeShifts& C, double alpha, const double* __restrict__ length,
+                                             const double* __restrict__ gamma, int64_t f, int K, int np, int64_t site,
+                                             bool& any) {
+#pragma clang fp contract(off)
+  const double s = lg_clade_sum(C, f, site, any);
+  if (!C.family) return 0.0;
+  double d = 0.0;
+  for (int k = 0; k < np; ++k) {
+    const double wc = gamma[f * K + k] * (1.0 - exp(-alpha * length[f * K + k]));
+    d = d + wc * s;
+  }
+  return d;
+}
+
 // The displacement of family f at this site and trait: what its offset w gains from the shifts on its edges and from the painted
 // optima.  The one statement of it for the correction of the fill (pgbp_shift.hip), the noise correction (pgbp_noise.hip) and
 // the per-site mask (pgbp_sitemiss.hip).  alpha, theta: of this site; sm_stride: the row length of value_sm.

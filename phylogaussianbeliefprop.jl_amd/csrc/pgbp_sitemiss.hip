@@ -27,7 +27,7 @@ namespace pgbp {
 #define PGBP_SITEMISS_LOG2PI 1.8378770664093454835606594728112
 
 template <bool SM>
-__global__ __launch_bounds__(256) void sitemiss_fill_kernel(LgStatic F, LgParams M, LgShifts Sh, LgOptima Op, LgNoise Nz, LgSiteMiss Ms,
+__global__ __launch_bounds__(256) void sitemiss_fill_kernel(LgStatic F, LgParams M, LgShifts Sh, LgOptima Op, LgNoise Nz, LgSiteMiss Ms, LgCladeShifts Cs,
                                                             const int32_t* __restrict__ mcl, double* __restrict__ pool,
                                                             int64_t stride, double* __restrict__ fpool, int64_t fstride,
                                                             const int64_t* __restrict__ off, const int32_t* __restrict__ dim,
@@ -65,6 +65,10 @@ __global__ __launch_bounds__(256) void sitemiss_fill_kernel(LgStatic F, LgParams
       }
       // a shift of the mean on a parent edge, a painted optimum
       z = z + lg_disp_d(Sh, Op, &theta, S.alpha, F.length, F.gamma, f, K, np, 0, 1, site, drow);
+      if (Cs.family) {   // this site's clade shifts of the optimum
+        bool any;
+        z = z + lg_clade_d(Cs, S.alpha, F.length, F.gamma, f, K, np, site, any);
+      }
       if (cpos < 0) z = z - F.data_sm[(int64_t)F.data_row[f] * drow + site];   // a tip: its value
       const int sn = lg_noise_slot(Nz, f);
       if (sn >= 0) V = V + lg_noise_E(Nz, sn, 0, 0, 1, site);        // a noisy tip: V + E
@@ -127,7 +131,7 @@ __global__ __launch_bounds__(256) void sitemiss_zero_kernel(LgSiteMiss Ms, doubl
 }
 
 void launch_lg_sitemiss(const LgStatic& F, const LgParams& M, const LgShifts& S, const LgOptima& Op, const LgNoise& Nz,
-                        const LgSiteMiss& Ms,
+                        const LgSiteMiss& Ms, const LgCladeShifts& Cs,
                         const int32_t* d_mcl, int n_mcl, int sm, double* pool, int64_t stride, double* fpool, int64_t fstride,
                         const int64_t* d_off, const int32_t* d_dim, int n_sites, hipStream_t st) {
   if (n_mcl <= 0 || !Ms.words) return;
@@ -135,10 +139,10 @@ void launch_lg_sitemiss(const LgStatic& F, const LgParams& M, const LgShifts& S,
   for (int c0 = 0; c0 < n_mcl; c0 += 65535) {   // (grid.y is 16 bits wide)
     const dim3 grid(gx, n_mcl - c0 < 65535 ? n_mcl - c0 : 65535);
     if (sm)
-      hipLaunchKernelGGL(sitemiss_fill_kernel<true>, grid, dim3(256), 0, st, F, M, S, Op, Nz, Ms, d_mcl + c0, pool, stride, fpool,
+      hipLaunchKernelGGL(sitemiss_fill_kernel<true>, grid, dim3(256), 0, st, F, M, S, Op, Nz, Ms, Cs, d_mcl + c0, pool, stride, fpool,
                          fstride, d_off, d_dim, n_sites);
     else
-      hipLaunchKernelGGL(sitemiss_fill_kernel<false>, grid, dim3(256), 0, st, F, M, S, Op, Nz, Ms, d_mcl + c0, pool, stride, fpool,
+      hipLaunchKernelGGL(sitemiss_fill_kernel<false>, grid, dim3(256), 0, st, F, M, S, Op, Nz, Ms, Cs, d_mcl + c0, pool, stride, fpool,
                          fstride, d_off, d_dim, n_sites);
   }
 }

@@ -317,6 +317,49 @@ function lg_optimum_scan_sites(o::DeviceClusterGraphBelief, nsites::Integer, nfa
 end
 
 """
+    lg_set_clade_shifts_sites!(obj, family, delta)
+    lg_update_clade_shifts_sites!(obj, delta)
+    lg_clear_clade_shifts_sites!(obj)
+    lg_clade_shift_slots(obj) -> Int
+    lg_clade_shift_score_sites(obj, nsites; min_info = 1e-8) -> (g, H, Kt, info)
+
+Per-site clade shifts of the OU optimum on a thread-per-site engine with a topology set (pgbp_lg_set_clade_shifts_sites and its
+companions): at site `s` the optimum of every edge of clade(`family[s, j]`) gains `delta[s, j]`.  `family` is `nsites x nslots`
+with 1-based families and 0 for an empty slot (Julia's column-major `[site, slot]` is the call's `[slot][site]`); `delta` has the
+same shape.  The setting takes effect at the next fill; `lg_optimum_scan_sites` honours it, the gradient calls refuse while it
+is in force.  `lg_update_clade_shifts_sites!` replaces the deltas alone.  The score call returns, per slot and site, the scan's
+g, H and Kt at the site's own family (`nsites x nslots`; NaN at an empty slot, H NaN where the slot is not identified).
+Written, not yet run.
+"""
+function lg_set_clade_shifts_sites!(o::DeviceClusterGraphBelief, family::AbstractMatrix{<:Integer}, delta::AbstractMatrix{<:Real})
+    size(family) == size(delta) || throw(ArgumentError("family and delta differ in shape"))
+    fam = Matrix{Int32}(family .- 1)
+    d = Matrix{Float64}(delta)
+    check(o.handle, @ccall LIB.pgbp_lg_set_clade_shifts_sites(o.handle::Ptr{Cvoid}, Int32(size(fam, 2))::Int32, fam::Ptr{Int32}, d::Ptr{Float64})::Cint)
+    return o
+end
+
+function lg_update_clade_shifts_sites!(o::DeviceClusterGraphBelief, delta::AbstractMatrix{<:Real})
+    d = Matrix{Float64}(delta)
+    check(o.handle, @ccall LIB.pgbp_lg_update_clade_shifts_sites(o.handle::Ptr{Cvoid}, d::Ptr{Float64})::Cint)
+    return o
+end
+
+function lg_clear_clade_shifts_sites!(o::DeviceClusterGraphBelief)
+    check(o.handle, @ccall LIB.pgbp_lg_set_clade_shifts_sites(o.handle::Ptr{Cvoid}, Int32(0)::Int32, C_NULL::Ptr{Int32}, C_NULL::Ptr{Float64})::Cint)
+    return o
+end
+
+lg_clade_shift_slots(o::DeviceClusterGraphBelief) = Int(@ccall LIB.pgbp_lg_clade_shift_slots(o.handle::Ptr{Cvoid})::Int32)
+
+function lg_clade_shift_score_sites(o::DeviceClusterGraphBelief, nsites::Integer; min_info::Real = 1e-8)
+    m = lg_clade_shift_slots(o)
+    g = zeros(nsites, m); H = zeros(nsites, m); kt = zeros(nsites, m); info = zeros(Int32, nsites)
+    check(o.handle, @ccall LIB.pgbp_lg_clade_shift_score_sites(o.handle::Ptr{Cvoid}, Int32(0)::Int32, Int32(nsites)::Int32, Float64(min_info)::Float64, g::Ptr{Float64}, H::Ptr{Float64}, kt::Ptr{Float64}, info::Ptr{Int32})::Cint)
+    return (g, H, kt, info)
+end
+
+"""
     lg_edge_gradient_sites(obj, nsites, nfamilies, K) -> (dlength, dgamma, dshift, info)
 
 `lg_edge_gradient` for every site of a univariate batch on the thread-per-site kernels (pgbp_lg_edge_gradient_sites), lanes =

@@ -521,6 +521,113 @@ def bootstrap_optimum_scan_lg(beliefs, schedule_tree, seed=None, z=None, min_inf
     return dict(max_lr=top, family=fam, loglik=ll, info=info, x=x, data=beliefs.get_data_lg(), data_before=before)
 
 
+def fit_clade_shifts_sites_lg(beliefs, schedule_tree, min_info=1e-8):
+    """Exact joint ML of every site's clade-shift deltas for the families in force (set_clade_shifts_sites_lg), all sites side
+    by side: fit_shifts_lg's device, batched over sites.  The log-likelihood of a site is quadratic in its deltas, so m + 1
+    evaluations (fill, calibration, clade_shift_score_sites_lg -- each for all sites at once) at the current point and at a
+    unit step in each of the m slots give the score g and the joint information H exactly: column k of H is g(d) - g(d + e_k).
+    H step = g is solved per site on the host by an elimination in slot order; a pivot that is not above min_info Kt of its
+    slot drops that slot AT THAT SITE (identified False, its delta left where it was) and does not raise.  One more
+    evaluation leaves the engine filled and calibrated at the estimate.  alpha and the rates are held where the last
+    assignfactors_lg_ put them.  Returns a dict: delta [m, n_sites], H [n_sites, m, m] (symmetrised; rows and columns of
+    empty slots 0), se [m, n_sites] (NaN at empty or dropped slots), loglik [n_sites] at the estimate, identified
+    [m, n_sites], g [m, n_sites] (the score at the starting point), info [n_sites]."""
+    st = beliefs.clade_shifts_sites_lg()
+    if st is None:
+        raise ValueError("fit_clade_shifts_sites_lg: no clade shifts are set (call set_clade_shifts_sites_lg first)")
+    fam, d0 = st["family"], st["delta"]
+    m, n = fam.shape
+    used = fam >= 0
+
+    def evaluate(d):
+        beliefs.update_clade_shifts_sites_lg(d)
+        ll, sc = beliefs.loglik_and_clade_shift_score_sites_lg(schedule_tree, min_info=min_info)
+        return ll, sc
+
+    ll0, sc0 = evaluate(d0)
+    g0 = np.where(used, sc0["g"], 0.0)
+    kt = np.where(used, sc0["kt"], 0.0)
+    H = np.zeros((n, m, m))
+    for k in range(m):
+        if not used[k].any():
+            continue
+        step = d0.copy()
+        step[k] += 1.0
+        _, sck = evaluate(step)
+        H[:, :, k] = (g0 - np.where(used, sck["g"], 0.0)).T
+    H = 0.5 * (H + H.transpose(0, 2, 1))
+    H[~(used.T[:, :, None] & used.T[:, None, :])] = 0.0
+    # elimination in slot order, vectorised over sites: which slots keep a positive pivot
+    keep = used.T & np.isfinite(g0.T) & np.isfinite(H).all(axis=2)       # [n, m]
+    Lc = np.zeros((n, m, m))
+    for k in range(m):
+        piv = H[:, k, k] - np.einsum("nj,nj->n", Lc[:, k, :k], Lc[:, k, :k])
+        ok = keep[:, k] & (piv > min_info * kt[k]) & (piv > 0.0)
+        keep[:, k] = ok
+        rt = np.sqrt(np.where(ok, piv, 1.0))
+        for i in range(k + 1, m):
+            v = (H[:, i, k] - np.einsum("nj,nj->n", Lc[:, i, :k], Lc[:, k, :k])) / rt
+            Lc[:, i, k] = np.where(ok, v, 0.0)
+        Lc[:, k, k] = np.where(ok, rt, 0.0)
+    pair = keep[:, :, None] & keep[:, None, :]
+    Hk = np.where(pair, H, 0.0) + np.eye(m)[None] * (~keep)[:, :, None]   # dropped slots: an identity row and column
+    gk = np.where(keep, g0.T, 0.0)
+    step = np.linalg.solve(Hk, gk[:, :, None])[:, :, 0]
+    cov = np.linalg.inv(Hk)
+    se = np.where(keep, np.sqrt(np.abs(np.einsum("nkk->nk", cov))), np.nan).T
+    delta = d0 + np.where(keep, step, 0.0).T
+    ll, sc = evaluate(delta)
+    return dict(delta=delta, H=np.where(used.T[:, :, None] & used.T[:, None, :], H, 0.0), se=se, loglik=ll, identified=keep.T.copy(),
+                g=g0, score=sc, info=sc["info"])
+
+
+def select_optimum_shifts_sites_lg(beliefs, schedule_tree, max_shifts, min_lr, min_info=1e-8):
+    """Forward selection of clade shifts of the optimum for all sites of a univariate batch at once (the workflow of l1ou,
+    bayou and PhylogeneticEM on the nested-shift parametrisation).  It starts from no clade shift (a setting in force is
+    cleared; painted optima, shifts, noise and masks stay) and repeats up to max_shifts times: scan
+    (optimum_scan_sites_lg(tables=False)); every site still going whose top_lr exceeds min_lr puts its top_family into its
+    next empty slot, the others stop for good; joint refit of all slots (fit_clade_shifts_sites_lg), whose last evaluation
+    leaves the engine calibrated for the next scan.  alpha and the rates are held at their fitted values, as PhylogeneticEM
+    holds alpha.  min_lr: a threshold for the first step comes from bootstrap_optimum_scan_lg under the null fit; the
+    simulation refuses while a setting is in force, so the later steps reuse that threshold -- an APPROXIMATION, since the null
+    distribution of the largest lr changes once clades are in the model.
+    Returns a dict: family int [max_shifts, n_sites] (-1: unused), delta [max_shifts, n_sites] (the final joint estimates),
+    lr [max_shifts, n_sites] (top_lr at entry, NaN where unused), loglik [steps + 1, n_sites] (row 0: no shift; a site that
+    has stopped keeps its value), n_shifts [n_sites], info [n_sites].  The engine is left with the selected setting in force."""
+    max_shifts = int(max_shifts)
+    n = beliefs.n_sites
+    beliefs.clear_clade_shifts_sites_lg()
+    fam = np.full((max(1, max_shifts), n), -1, np.int32)
+    delta = np.zeros((max(1, max_shifts), n))
+    lr = np.full((max(1, max_shifts), n), np.nan)
+    ll, scan = beliefs.loglik_and_optimum_scan_sites_lg(schedule_tree, min_info=min_info, tables=False)
+    path = [ll]
+    info = scan["info"].copy()
+    going = info == 0
+    n_shifts = np.zeros(n, np.int64)
+    for step in range(max_shifts):
+        top, tf = scan["top_lr"], scan["top_family"].astype(np.int64)
+        with np.errstate(invalid="ignore"):
+            enter = going & (tf >= 0) & (top > float(min_lr))
+        enter &= ~(fam == tf[None, :]).any(axis=0)      # (a family in force has lr ~ 0 after the refit: not reached)
+        going = enter
+        if not enter.any():
+            break
+        fam[step, enter] = tf[enter]
+        lr[step, enter] = top[enter]
+        n_shifts[enter] += 1
+        beliefs.set_clade_shifts_sites_lg(fam, delta)
+        fit = fit_clade_shifts_sites_lg(beliefs, schedule_tree, min_info=min_info)
+        delta = fit["delta"]
+        path.append(np.where(fit["info"] != 0, np.nan, fit["loglik"]))
+        info = np.where(info != 0, info, fit["info"])
+        going &= fit["info"] == 0
+        if step + 1 < max_shifts:
+            scan = beliefs.optimum_scan_sites_lg(min_info=min_info, tables=False)
+    return dict(family=fam[:max_shifts], delta=delta[:max_shifts], lr=lr[:max_shifts], loglik=np.array(path), n_shifts=n_shifts,
+                info=info)
+
+
 def lbfgs_sites(value_and_grad, x0, maxiter=200, gtol=1e-8, memory=8, c1=1e-4):
     """Batched L-BFGS: minimises n independent functions of d variables side by side, one callback per step for all of them.
     value_and_grad(X [n, d]) -> (f [n], g [n, d]) evaluates every site at its row of X; a site whose value or gradient is
